@@ -15,6 +15,11 @@ B boxes of a step are split over the N ranks ("scaling": "strong"; north_star's 
 strong-scaling one) and every rank walks its share in chunks of at most ``--boxes`` boxes that reuse one
 activation workspace (64 boxes = 352 GB of activations do not fit one GPU at once).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, `config`).
+``--full`` adds everything else the line has carried: the per-stage profile and `roofline` (runs of their own), the
+`host_resident_inputs`, `box1000`, `train64x1000` and `soap100k` legs and `cpu_baseline`.
+``--dump-outputs DIR`` writes what the last timed step returned (per-atom energies, dE/dR, per-box energies) as .npy.
 """
 import argparse
 import json
@@ -254,6 +259,29 @@ def leg_soap100k(no_cpu):
     return out
 
 
+def dump_outputs(path, outs, rank, world, limit=64 << 20):
+    """`--dump-outputs`: what a caller of the timed path receives from its last step, as .npy files -- per-atom energies
+    and dE/dR (float32, atoms in input order: chunk by chunk, box by box) and the per-box energies (float64 sums). With
+    more than one rank, every file carries a `_rank{r}` suffix. Past `limit` bytes over all ranks, the per-atom arrays
+    are a fixed seeded sample of atoms whose indices are written too (`sampled_atom_index`, float64)."""
+    import numpy as np
+
+    atomic = torch.cat([a for a, _ in outs]).cpu().numpy()
+    grad = torch.cat([g for _, g in outs]).cpu().numpy()
+    box = atomic.astype(np.float64).reshape(-1, ATOMS_PER_BOX).sum(axis=1)
+    arrays = {"atomic_energy": atomic, "positions_gradient": grad, "box_energy": box}
+    budget = limit // world - 4 * 128   # the .npy headers
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        per_atom = atomic.itemsize + grad.itemsize * 3 + 8   # energy, gradient row, sampled index
+        k = (budget - box.nbytes) // per_atom
+        idx = np.sort(np.random.default_rng(0).choice(len(atomic), size=k, replace=False))
+        arrays.update(atomic_energy=atomic[idx], positions_gradient=grad[idx], sampled_atom_index=idx.astype(np.float64))
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+
+
 def respawn_under_launcher(n_gpus):
     """`python bench.py --gpus N` without a launcher: start N ranks of this same script under torch.distributed.run
     (one process per GPU, rendezvous on 127.0.0.1) and hand its exit code back."""
@@ -280,15 +308,25 @@ def main():
     ap.add_argument("--total-boxes", type=int, default=0,
                     help="strong-scaling mode: this many boxes per step in the WHOLE job, split over the ranks and "
                          "walked in chunks of --boxes (0 = weak scaling, --boxes per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline figure: per-stage profile and roofline, the extra legs, "
+                         "cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the legs that are not `value` (box1000, host_resident_inputs): what the rocprofv3 passes run")
-    ap.add_argument("--profile-all", action="store_true", help="print a per-stage table to stderr")
+                    help="with --full: skip the legs that are not `value` (box1000, host_resident_inputs): what the "
+                         "rocprofv3 passes run")
+    ap.add_argument("--profile-all", action="store_true", help="with --full: print a per-stage table to stderr")
     ap.add_argument("--normalization", default="RMSNorm", choices=["RMSNorm", "LayerNorm"],
                     help="side runs only: the legacy-checkpoint norm; the headline metric is the default (RMSNorm)")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=INT",
                     help="library switch for A/B runs, e.g. --set side_stream=0 (pet_config_set)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
+    if args.profile_all and not args.full:
+        raise SystemExit("--profile-all needs --full (the per-stage table comes from the profiled step)")
 
     from metatrain_amd import distributed as pdist
 
@@ -364,7 +402,8 @@ def main():
     state = {}
 
     def step():
-        out = None
+        """One step over every chunk: the first chunk's graph and each chunk's (per-atom energies, dE/dR)."""
+        first, outs = None, []
         for ch in chunks:
             graph = rt.HipGraph(model, ch["positions"], ch["cells"], ch["centers"], ch["neighbors"], ch["shifts"],
                                 ch["species"], ch["sysidx"])
@@ -377,47 +416,53 @@ def main():
             state["fw"] = fw
             atomic = fw.forward()
             grad = fw.backward(ch["ones"])
-            out = out or (atomic, grad, graph)
-        return out
+            first = graph if first is None else first
+            outs.append((atomic, grad))
+        return first, outs
 
     def barrier():
         pdist.barrier(dev)
 
     for _ in range(args.warmup):
         step()
-    # ---- find the dominant stage: one untimed step on a single stream (clean per-stage durations),
-    #      then time K steps in the production configuration with HIP events on that stage only ----
-    rt.config_set("side_stream", 0)
-    rt.profile(True)
-    step()
-    torch.cuda.synchronize()
-    table = rt.profile_report()
-    rt.profile(False)
-    rt.config_set("side_stream", side_stream)
-    dominant = max(table, key=lambda r: r["total_ms"])["name"]
-    if args.profile_all and rank == 0:
-        for r in sorted(table, key=lambda r: -r["total_ms"]):
-            tf = r["flops"] / max(r["total_ms"], 1e-9) / 1e9
-            gb = r["bytes"] / max(r["total_ms"], 1e-9) / 1e6
-            print(f"  {r['name']:16s} {r['total_ms']:8.3f} ms x{r['calls']:<3d} {tf:8.1f} TFLOP/s {gb:8.0f} GB/s(alg)",
-                  file=sys.stderr)
-    step()  # back on two streams before the clock starts
+    if args.full:
+        # ---- find the dominant stage: one untimed step on a single stream (clean per-stage durations),
+        #      then time K steps in the production configuration with HIP events on that stage only ----
+        rt.config_set("side_stream", 0)
+        rt.profile(True)
+        step()
+        torch.cuda.synchronize()
+        table = rt.profile_report()
+        rt.profile(False)
+        rt.config_set("side_stream", side_stream)
+        dominant = max(table, key=lambda r: r["total_ms"])["name"]
+        if args.profile_all and rank == 0:
+            for r in sorted(table, key=lambda r: -r["total_ms"]):
+                tf = r["flops"] / max(r["total_ms"], 1e-9) / 1e9
+                gb = r["bytes"] / max(r["total_ms"], 1e-9) / 1e6
+                print(f"  {r['name']:16s} {r['total_ms']:8.3f} ms x{r['calls']:<3d} {tf:8.1f} TFLOP/s {gb:8.0f} GB/s(alg)",
+                      file=sys.stderr)
+    step()  # back on two streams before the clock starts (and the workspace allocated even at --warmup 0)
 
     # `value`: K steps with NO instrumentation in the timed region ...
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        atomic, grad, graph = step()
+        graph, outs = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    # ... and the dominant stage's launch durations in a SEPARATE pass of the same steps in the same (two-stream)
-    # configuration, HIP events on the stream the stage is launched on
-    rt.profile(True, stage=dominant)
-    for _ in range(min(args.steps, 10)):
-        step()
-    torch.cuda.synchronize()
-    dom = [r for r in rt.profile_report() if r["name"] == dominant][0]
-    rt.profile(False)
+    atomic, grad = outs[0]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs, rank, world)
+    if args.full:
+        # ... and the dominant stage's launch durations in a SEPARATE pass of the same steps in the same (two-stream)
+        # configuration, HIP events on the stream the stage is launched on
+        rt.profile(True, stage=dominant)
+        for _ in range(min(args.steps, 10)):
+            step()
+        torch.cuda.synchronize()
+        dom = [r for r in rt.profile_report() if r["name"] == dominant][0]
+        rt.profile(False)
 
     elapsed = pdist.max_over_ranks(elapsed, dev)
     total_atoms = args.total_boxes * ATOMS_PER_BOX if strong else n_atoms * world
@@ -427,6 +472,36 @@ def main():
     if rank == 0:
         e_total = float(atomic.double().sum())
         assert torch.isfinite(grad).all()
+        out = {
+            "metric": "atom-steps/sec (energy+forces) PET 10k-atom box",
+            "value": value,
+            "unit": "atom-steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic random periodic boxes (rho=0.05/A^3, 4 species), weights from a seeded generator",
+            "config": {
+                "workload": f"PET forward + dE/dR (preprocess+features+predict+backward), "
+                            + (f"{args.total_boxes} x {ATOMS_PER_BOX}-atom boxes per step in the whole job "
+                               f"({len(my_ids)} per GPU, chunks of {boxes})" if strong else
+                               f"{boxes} x {ATOMS_PER_BOX}-atom boxes per GPU per step") + ", default PET hypers"
+                            f"{'' if args.normalization == 'RMSNorm' else ' with normalization=' + args.normalization} (2.9M params), "
+                            f"4.5 A cutoff, {graph.n_edges // boxes} edges/box",
+                "atoms_per_gpu_per_step": n_atoms,
+                "edges_per_gpu_per_step": int(graph.n_edges),
+                "parallelism": f"boxes sharded over {world} rank(s), no data-path collective",
+                "chunks_per_step_per_gpu": len(chunks),
+                "arithmetic": ARITHMETIC,
+                "neighbor_list_gpu_ms_per_box": nl_ms / boxes,
+                "total_energy_rank0": e_total,
+            },
+        }
+    if rank == 0 and args.full:
         avg_ms = dom["total_ms"] / dom["calls"]
         flops_per_launch = dom["flops"] / dom["calls"]
         bytes_per_launch = dom["bytes"] / dom["calls"]
@@ -468,36 +543,7 @@ def main():
                                            (MFMA_SPLIT_EQUIV_PEAK_TFLOPS if r["name"] in SPLIT_MFMA_STAGES
                                             else MFMA_F32_PEAK_TFLOPS), 4) if r["flops"] else None,
             } for r in sorted(table, key=lambda r: -r["total_ms"])[:8]}
-        out = {
-            "metric": "atom-steps/sec (energy+forces) PET 10k-atom box",
-            "value": value,
-            "unit": "atom-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic random periodic boxes (rho=0.05/A^3, 4 species), weights from a seeded generator",
-            "config": {
-                "workload": f"PET forward + dE/dR (preprocess+features+predict+backward), "
-                            + (f"{args.total_boxes} x {ATOMS_PER_BOX}-atom boxes per step in the whole job "
-                               f"({len(my_ids)} per GPU, chunks of {boxes})" if strong else
-                               f"{boxes} x {ATOMS_PER_BOX}-atom boxes per GPU per step") + ", default PET hypers"
-                            f"{'' if args.normalization == 'RMSNorm' else ' with normalization=' + args.normalization} (2.9M params), "
-                            f"4.5 A cutoff, {graph.n_edges // boxes} edges/box",
-                "atoms_per_gpu_per_step": n_atoms,
-                "edges_per_gpu_per_step": int(graph.n_edges),
-                "parallelism": f"boxes sharded over {world} rank(s), no data-path collective",
-                "chunks_per_step_per_gpu": len(chunks),
-                "arithmetic": ARITHMETIC,
-                "neighbor_list_gpu_ms_per_box": nl_ms / boxes,
-                "total_energy_rank0": e_total,
-            },
-            "roofline": roof,
-        }
+        out["roofline"] = roof
         # whole-step view: SURVEY §8(d) algorithmic GEMM FLOPs, forward x2 for forces
         # (`graph` is the step's first chunk; the other chunks are boxes of the same size and density)
         chunk_atoms = boxes * ATOMS_PER_BOX
@@ -553,12 +599,13 @@ def main():
             # BASELINE configs[2] and configs[4] on this GPU, from their own benches (bench_train.py / bench_soap.py, each a
             # child process started once this process has released its workspaces): not `value`
             state.clear()
-            del atomic, grad, graph
+            del atomic, grad, graph, outs
             torch.cuda.empty_cache()
             out["train64x1000"] = leg_train64x1000(args.no_cpu_baseline)
             out["soap100k"] = leg_soap100k(args.no_cpu_baseline)
         if not args.no_cpu_baseline and world == 1:  # the reported CPU leg runs at N = 1 only
             out["cpu_baseline"] = cpu_baseline(hypers, params)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         pdist.barrier(dev)

@@ -166,6 +166,8 @@ def test_slurm_environment_and_process_group_call_sequence(monkeypatch):
     assert d.expand_hostlist("nid[001-003,007],login1") == ["nid001", "nid002", "nid003", "nid007", "login1"]
     assert d.expand_hostlist("node12") == ["node12"]
     assert d.expand_hostlist("rack[1-2]n[01-02],x") == ["rack1n01", "rack1n02", "rack2n01", "rack2n02", "x"]
+    # the call below writes MASTER_ADDR / WORLD_SIZE / ...: it gets a copy of the environment, so none of it outlives the test
+    monkeypatch.setattr(os, "environ", dict(os.environ))
     for k, v in {"SLURM_JOB_ID": "7", "SLURM_JOB_NODELIST": "gpu[05-06]", "SLURM_NTASKS": "16", "SLURM_PROCID": "11",
                  "SLURM_LOCALID": "3"}.items():
         monkeypatch.setenv(k, v)
@@ -182,5 +184,3 @@ def test_slurm_environment_and_process_group_call_sequence(monkeypatch):
     assert calls == [("set_device", "cuda:1"), ("init", "nccl", "cuda:1")]
     assert os.environ["MASTER_ADDR"] == "gpu05" and os.environ["MASTER_PORT"] == "39591"
     assert (os.environ["WORLD_SIZE"], os.environ["RANK"], os.environ["LOCAL_RANK"]) == ("16", "11", "3")
-    for k in ("MASTER_ADDR", "MASTER_PORT", "WORLD_SIZE", "RANK", "LOCAL_RANK"):
-        monkeypatch.delenv(k, raising=False)

@@ -402,9 +402,10 @@ int pet_profile_report(int max_entries, char (*names)[64], double* total_ms, int
 /* Runtime switches used by tests / the benchmark (every setting meets the same parity bar):
  *   "side_stream" 1 = node-feature chain on a second HIP stream (default); that stream is created one priority level below the
  *                 caller's (environment PET_HIP_SIDE_PRIO = same | high overrides; PET_HIP_SIDE = 0 disables the stream)
- *   "trr"         1 = transposed register-resident row kernels on f16x3 split-operand products (default); 0 = the LDS-tile
- *                 kernels for the transformer layers (the one fallback generation, also the transformer-layer path of
- *                 PostLN models). The combination stage has one implementation (the software-pipelined TRR kernel).
+ *   "trr"         1 = transposed register-resident row kernels on f16x3 split-operand products (default; environment
+ *                 PET_HIP_TRR = 0 makes 0 the default); 0 = the LDS-tile kernels for the transformer layers (the one fallback
+ *                 generation, also the transformer-layer path of PostLN models). The combination stage has one implementation
+ *                 (the software-pipelined TRR kernel).
  *   "attn_fused"  bits: 1 = the per-atom fused attention block in the forward (norm -> QKV -> soft-max attention -> output
  *                 projection in one kernel; Q, K, V and the attention output never reach HBM; csrc/pet_ablk.hip), 2 = its
  *                 adjoint (recomputes Q, K, V from the layer input), 4 = whatever the graph's size; default 3: graphs of
@@ -439,17 +440,19 @@ int pet_profile_report(int max_entries, char (*names)[64], double* total_ms, int
  *                 ~1e-3, NOT the 1e-5 parity mode; 20-step loss curve in tests/test_gpu_train.py); default 0
  *   "wgrad_bf16"  1 = weight-gradient GEMMs of the training passes as bf16x3 split-operand products (default); 0 = fp32 MFMA
  *   "so_f16x3"    1 = generic GEMMs of the second-order (training) pass as f16x3 (default); 0 = fp32 MFMA
- *   (removed in round 4 with the kernels they selected: "emlp_pipe", "emlp_bwd_pipe", "comb_pipe", "comb_bwd_pipe",
- *   "emlp_recompute", "line_stores", "lds_w"; in round 6: "attn_lds" with the two staged-adjoint instantiations only it reached,
- *   "tile_f16x3" (the fp32 fallback of the LDS-tile kernels remains for weights without fp16 planes), "soap_fused" with the
- *   first-generation fused SOAP kernels, the A/B value 3 of "node_planes" with its kernel)
- *   "soap_mfma"   1 = SOAP-BPNN LayerNorm + MLP tail on MFMA (default)
+ *   "soap_mfma"   1 = SOAP-BPNN LayerNorm + MLP tail on MFMA (default); 0 = per-atom tail kernels
  *   "soap_packed" 1 = SOAP-BPNN inference (legacy / per-species networks) stores the upper triangle of every power-spectrum block
  *                 only (p_l[a][b] = p_l[b][a]: 2 360 instead of 4 544 floats per atom for the default basis), LayerNorm statistics
  *                 weighted and the first Linear folded accordingly -- default; 0 = the full [N][S] layout (what the feature output,
  *                 the Alchemical centre encoding and the training pass use in any case)
- *   "soap_sorted" 1 = SOAP-BPNN tail GEMM on species-sorted atom tiles, one network per tile (default)
+ *   "soap_sorted" 1 = SOAP-BPNN tail GEMM on species-sorted atom tiles, one network per tile (default); 0 = all networks stacked
  *   "soap_pair"   1 = SOAP expansion one wave per atom, its adjoint one lane per pair (default); 0 = first generation
+ *   "attn_fused_prof" an action, not a switch (the value is ignored): prints and clears the per-phase cycle sums of the fused
+ *                 attention kernels in a library built with -DAB_PROFILE, does nothing otherwise
+ *   (removed in round 4 with the kernels they selected: "emlp_pipe", "emlp_bwd_pipe", "comb_pipe", "comb_bwd_pipe",
+ *   "emlp_recompute", "line_stores", "lds_w"; in round 6: "attn_lds" with the two staged-adjoint instantiations only it reached,
+ *   "tile_f16x3" (the fp32 fallback of the LDS-tile kernels remains for weights without fp16 planes), "soap_fused" with the
+ *   first-generation fused SOAP kernels, the A/B value 3 of "node_planes" with its kernel)
  * Unknown keys return PET_ERR_ARGUMENT. */
 int pet_config_set(const char* key, int value);
 

@@ -12,17 +12,49 @@ namespace pet {
 
 static thread_local std::string g_error;
 
-static int g_trr = -1;
+// ---------------------------------------------------------------------------------
+// runtime switches (switches.h): the keys pet_config_set accepts and how each stores its value
+// ---------------------------------------------------------------------------------
+static Switches g_switches;
+const Switches& switches() { return g_switches; }
+
+// how pet_config_set stores a value: BOOL v ? 1 : 0, RAW v (bit masks), CLAMP2 v > 2 ? 2 : v, EMLP_S v ? 1 : 0 and the row
+// threshold v > 1 ? v : EMLP_S_MIN_ROWS
+enum class SwitchKind { BOOL, RAW, CLAMP2, EMLP_S };
+struct SwitchKey {
+    const char* key;
+    int Switches::*field;
+    SwitchKind kind;
+};
+static const SwitchKey SWITCH_KEYS[] = {
+    {"side_stream", &Switches::side_stream, SwitchKind::BOOL},
+    {"trr", &Switches::trr, SwitchKind::BOOL},
+    {"attn_fused", &Switches::attn_fused, SwitchKind::RAW},
+    {"emlp_s", &Switches::emlp_s, SwitchKind::EMLP_S},
+    {"trr_compress", &Switches::trr_compress, SwitchKind::RAW},
+    {"node_planes", &Switches::node_planes, SwitchKind::CLAMP2},
+    {"so_trr", &Switches::so_trr, SwitchKind::BOOL},
+    {"soap_ps_mfma", &Switches::soap_ps_mfma, SwitchKind::BOOL},
+    {"node_split", &Switches::node_split, SwitchKind::BOOL},
+    {"center_fused", &Switches::center_fused, SwitchKind::BOOL},
+    {"sorted_shortcut", &Switches::sorted_shortcut, SwitchKind::BOOL},
+    {"dxf_fused", &Switches::dxf_fused, SwitchKind::BOOL},
+    {"train_bf16", &Switches::train_bf16, SwitchKind::BOOL},
+    {"wgrad_bf16", &Switches::wgrad_bf16, SwitchKind::BOOL},
+    {"so_f16x3", &Switches::so_f16x3, SwitchKind::BOOL},
+    {"soap_mfma", &Switches::soap_mfma, SwitchKind::BOOL},
+    {"soap_packed", &Switches::soap_packed, SwitchKind::BOOL},
+    {"soap_sorted", &Switches::soap_sorted, SwitchKind::BOOL},
+    {"soap_pair", &Switches::soap_pair, SwitchKind::BOOL},
+};
+
 bool use_trr() {
-    if (g_trr < 0) {
+    if (g_switches.trr < 0) {
         const char* e = getenv("PET_HIP_TRR");
-        g_trr = (e && e[0] == '0') ? 0 : 1;
+        g_switches.trr = (e && e[0] == '0') ? 0 : 1;
     }
-    return g_trr == 1;
+    return g_switches.trr == 1;
 }
-void set_use_trr(int v) { g_trr = v ? 1 : 0; }
-static int g_side_override = -1;  // -1: environment default
-void set_side_stream(int v) { g_side_override = v ? 1 : 0; }
 
 void set_error(const std::string& msg) { g_error = msg; }
 
@@ -30,7 +62,7 @@ const SideStream& side_stream() {
     static SideStream ss;
     static SideStream off;  // enabled == false: everything on the caller's stream
     static bool init = false;
-    if (g_side_override == 0) return off;
+    if (g_switches.side_stream == 0) return off;
     if (!init) {
         init = true;
         const char* e = getenv("PET_HIP_SIDE");
@@ -980,27 +1012,25 @@ int pet_profile_reset(void) {
 int pet_config_set(const char* key, int value) {
     PET_REQUIRE(key, PET_ERR_ARGUMENT, "null key");
     const std::string k(key);
-    if (k == "side_stream") set_side_stream(value);
-    else if (k == "trr") set_use_trr(value);
-    else if (k == "soap_mfma") set_soap_mfma(value);
-    else if (k == "soap_pair") set_soap_pair(value);
-    else if (k == "soap_packed") set_soap_packed(value);
-    else if (k == "soap_ps_mfma") set_soap_ps_mfma(value);
-    else if (k == "soap_sorted") set_soap_sorted(value);
-    else if (k == "attn_fused") set_attn_fused(value);
-    else if (k == "emlp_s") set_emlp_s(value);
-    else if (k == "attn_fused_prof") ablk_prof_dump();
-    else if (k == "trr_compress") set_trr_compress(value);
-    else if (k == "node_planes") set_node_planes(value);
-    else if (k == "center_fused") set_center_fused(value);
-    else if (k == "dxf_fused") set_dxf_fused(value);
-    else if (k == "node_split") set_node_split(value);
-    else if (k == "sorted_shortcut") set_sorted_shortcut(value);
-    else if (k == "so_trr") set_so_trr(value);
-    else if (k == "wgrad_bf16") set_wgrad_bf16(value);
-    else if (k == "train_bf16") set_train_bf16(value);
-    else if (k == "so_f16x3") set_so_f16x3(value);
-    else PET_REQUIRE(false, PET_ERR_ARGUMENT, "unknown config key '" + k + "'");
+    if (k == "attn_fused_prof") {  // an action, not a switch
+        ablk_prof_dump();
+        return PET_OK;
+    }
+    for (const SwitchKey& s : SWITCH_KEYS) {
+        if (k != s.key) continue;
+        int& f = g_switches.*s.field;
+        switch (s.kind) {
+            case SwitchKind::BOOL: f = value ? 1 : 0; break;
+            case SwitchKind::RAW: f = value; break;
+            case SwitchKind::CLAMP2: f = value > 2 ? 2 : value; break;
+            case SwitchKind::EMLP_S:
+                f = value ? 1 : 0;
+                g_switches.emlp_s_rows = value > 1 ? value : EMLP_S_MIN_ROWS;
+                break;
+        }
+        return PET_OK;
+    }
+    PET_REQUIRE(false, PET_ERR_ARGUMENT, "unknown config key '" + k + "'");
     return PET_OK;
 }
 

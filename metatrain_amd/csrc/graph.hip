@@ -258,9 +258,6 @@ __global__ void k_species_index(const int* __restrict__ species, const int* __re
     sp[i] = s;
 }
 
-static int g_sorted_shortcut = 1;  // pet_config_set("sorted_shortcut", 0): always run the radix sort of the edges
-void set_sorted_shortcut(int v) { g_sorted_shortcut = v ? 1 : 0; }
-
 // structures.py:206-221 and the non-strict mask of :265-267
 __global__ void k_edge_geometry(const float* __restrict__ pos, const float* __restrict__ cells,
                                 const int* __restrict__ centers, const int* __restrict__ neighbors,
@@ -442,7 +439,7 @@ static int bucket_atoms_by_tile_count(Graph& g, hipStream_t st, bool counted = f
         k_bucket_count<<<cdiv(g.n_nodes, T), T, 0, st>>>(g.rowptr, (int)g.n_nodes, g.scalars + 8);
     k_bucket_fill<<<cdiv(g.n_nodes, T), T, 0, st>>>(g.rowptr, (int)g.n_nodes, g.scalars + 8, g.scalars + 13, g.atom_order);
     // the per-atom attention tiles serve the fused block only (pet_ablk.hip: graphs of at least ABLK_MIN_TILES tiles, or forced; tiles <= atoms)
-    g.tiles_planned = g.n_nodes >= ABLK_MIN_TILES || (attn_fused() & 4);
+    g.tiles_planned = g.n_nodes >= ABLK_MIN_TILES || (switches().attn_fused & 4);
     if (!g.tiles_planned) return PET_OK;
     const int nb = cdiv(g.n_nodes, T);
     k_thist<<<nb, T, 0, st>>>(g.rowptr, (int)g.n_nodes, g.scalars + 24, g.tsort_tmp);
@@ -845,7 +842,7 @@ static int graph_build_once(const Model& m, const float* pos, const float* cells
     }
     g.adaptive = m.h.num_neighbors_adaptive > 0.f;
     const int* sorted_keys = g.sort_keys_out;
-    if (g.adaptive || !g_sorted_shortcut) mode = SORT_ALWAYS;
+    if (g.adaptive || !switches().sorted_shortcut) mode = SORT_ALWAYS;
     if (e0 > 0) {
         k_edge_geometry<<<cdiv(e0, T), T, 0, st>>>(pos, cells, centers, neighbors, shifts, g.sys, g.vin,
                                                    g.keep, g.sort_keys_in, g.sort_vals_in, (int)e0,
@@ -922,7 +919,7 @@ static int graph_build_once(const Model& m, const float* pos, const float* cells
         if (int rcb = bucket_atoms_by_tile_count(g, st, true)) return rcb;
     int host_scalars[61] = {0};
     if (int rcr = read_back(g.scalars, 61, nullptr, 0, host_scalars, st)) return rcr;
-    if (e0 > 0 && !g.adaptive && g_sorted_shortcut) {
+    if (e0 > 0 && !g.adaptive && switches().sorted_shortcut) {
         g_list_was_sorted.store(host_scalars[60] ? 0 : 1, std::memory_order_relaxed);
         if (mode == SORT_ASSUME_SORTED && host_scalars[60]) {
             *wrong_guess = true;

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "common.h"
+#include "switches.h"
 
 namespace pet {
 
@@ -246,23 +247,6 @@ int backward_geometry_abi(const Model& m, const Graph& g, void* ws, int64_t ws_b
 
 // pet_trr.hip: transposed register-resident stages (default; PET_HIP_TRR=0 selects the LDS-tile kernels)
 bool use_trr();
-void set_use_trr(int v);
-void set_side_stream(int v);
-void set_so_f16x3(int v);   // so.hip: 1 = generic training GEMMs as f16x3 on the 16-bit matrix cores (default), 0 = fp32 MFMA
-void set_train_bf16(int v);  // so.hip / train.hip: 1 = ONE 16-bit MFMA term per product in the training GEMMs (default 0: f16x3 / bf16x3)
-int train_bf16();
-void set_wgrad_bf16(int v);  // train.hip: 1 = weight gradients as bf16x3 products on the 16-bit matrix cores (default)
-void set_so_trr(int v);     // so.hip: 1 = K = 128 / n_out = 128 generic GEMMs as TRR kernels (default)
-void set_soap_mfma(int v);  // soap.hip: 1 = MFMA tail (default), 0 = per-atom tail kernels
-void set_soap_ps_mfma(int v);  // soap.hip: 1 = power spectrum and its adjoint on the fp32 matrix core (default)
-void set_soap_packed(int v); // soap.hip: 1 = inference stores the upper triangle of every power-spectrum block only (default)
-void set_trr_compress(int v);
-void set_node_planes(int v);  // pet_fwd.hip / pet_bwd.hip: node-row kernels on pre-split fp16 planes (default 1)
-bool node_planes();
-void set_dxf_fused(int v);     // pet_bwd.hip: 1 = dXF formed inside k_comb_bwd_p2 / k_emlp_bwd_p2 instead of by k_dxf (default)
-void set_node_split(int v);    // pet_fwd.hip: 1 = graphs of <= 4 096 atoms: four workgroups per 32-row tile of the node update (default)
-bool node_split_on();
-void set_center_fused(int v);  // pet_fwd.hip: 1 = k_node2 also writes the next layer's centre tokens (default)
 int node_rows(int64_t N);   // rows per workgroup of the node-row kernels (32: two workgroups per CU; 64)
 struct Graph;
 bool trr_compress(bool first, const Graph& g, const GnnLayerW& G, const float* Min, float* a0_out, float* Xout, int64_t E,
@@ -274,8 +258,6 @@ bool trr_head_edge(const Model& m, const float* Xin, const float* fc, float* ypr
 bool trr_head_edge_bwd(const Model& m, const float* Xin, const float* gA, const int* ctr, const float* fc,
                        const float* ypred, float* dfc, float* dXout, int64_t E, float* t_s1, float* t_da2, float* t_da1,
                        float* t_s2y, hipStream_t st);
-void set_soap_sorted(int v);  // soap.hip: 1 = tail GEMM on species-sorted tiles, one network per tile (default)
-void set_soap_pair(int v);  // soap.hip: 1 = wave-per-atom expansion / lane-per-pair adjoint (default), 0 = first generation
 // beta: the LayerNorm bias of the layer's norm, nullptr = RMSNorm
 void trr_qkv(const float* X, const float* gamma, const float* beta, const Lin& qkv, float* QKV, int64_t R,
              hipStream_t st);
@@ -297,11 +279,7 @@ bool trr_comb(bool first, const float* XF, const Graph& g, const GnnLayerW& G, c
 bool trr_comb_bwd(const float* dM, const float* XF, const Graph& g, const GnnLayerW& G, const float* LNS,
                   const float* CA, float* dcat, int64_t E, float* t_da, hipStream_t st, bool add_dm = false);  // add_dm: dcat[p][:D] += dM[p]
 
-// pet_ablk.hip: the per-atom fused attention block (norm -> QKV -> attention -> output projection in one kernel, the
-// adjoint recomputing Q, K, V); false = not served (an atom of more than 64 tokens, planes missing, switched off)
-void set_sorted_shortcut(int v);  // graph.hip: 1 = a neighbour list that is ordered by centre skips the radix sort (default)
-void set_attn_fused(int v);
-void set_emlp_s(int v);
+// pet_emlp_s.hip: the edge MLP and its adjoint with a workgroup-shared weight ring
 bool emlp_recompute_on(const Lin& win, const Lin& wout, int64_t E);
 bool emlp_s_serves(int64_t E);
 // pet_comb_bwd_s.hip: the inference adjoint of the combination stage with a workgroup-shared weight ring; false = not served
@@ -338,12 +316,13 @@ bool emlp_bwd_s(const float* dY, const float* X1, bool ln, const Lin& win_g, con
                 hipStream_t st, int ldy, const float* dY2, const int* rev2);
 bool emlp_s(const float* X1, const float* gamma, const float* beta, const Lin& win, const Lin& wout, float* VG, float* X2,
             int64_t E, hipStream_t st);
-int attn_fused();
 // graphs of at least this many 32-slot attention tiles (about 4 700 atoms at 19 neighbours) take the fused per-atom block:
 // measured crossover of one box, graph + forward + dE/dR, fused against three-kernel form -- 3 000 atoms 3.29 / 2.96 ms,
 // 5 000: 4.08 / 4.16, 7 000: 5.21 / 5.51, 10 000: 6.72 / 7.30 (round 5, k_ablk_fwd4 and the VGPR-form adjoint)
 constexpr int ABLK_MIN_TILES = 3840;
 void ablk_prof_dump();  // debugging aid: per-phase cycle sums of the fused kernels (library built with -DAB_PROFILE)
+// pet_ablk.hip: the per-atom fused attention block (norm -> QKV -> attention -> output projection in one kernel, the
+// adjoint recomputing Q, K, V); false = not served (an atom of more than 64 tokens, planes missing, switched off)
 bool ablk_fwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* X, float* X1, float* OC, float scale,
               hipStream_t st);
 bool ablk_bwd_on(const Graph& g);

@@ -516,14 +516,6 @@ __global__ __launch_bounds__(256, 2) void k_ablk_fwd4(
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// pet_config_set("attn_fused", bits): 1 = fused forward, 2 = fused adjoint (the forward of a call sequence whose adjoint
-// follows is fused only together with it: the three-kernel adjoint reads the saved Q, K, V), 4 = whatever the graph
-// (by default graphs of fewer than ABLK_MIN_TILES = 3 840 tiles, and graphs in which more than 5 % of the atoms have more than 32 tokens,
-// take the three-kernel form: ablk_serves); 0 = the three-kernel form (QKV / attention / projection) everywhere
-static int g_attn_fused = 3;
-void set_attn_fused(int v) { g_attn_fused = v; }
-int attn_fused() { return g_attn_fused; }
-
 #ifdef AB_PROFILE
 __device__ unsigned long long ab_prof[32];
 void ablk_prof_dump() {
@@ -595,19 +587,19 @@ static void tail_join(hipStream_t st, hipStream_t ts) {
 static bool ablk_serves(const Graph& g) {
     if (g.bucket_start[5] > g.bucket_start[4]) return false;  // an atom of more than 64 tokens
     if (!g.tiles_planned) return false;                       // a small graph built before the block was forced
-    if (g_attn_fused & 4) return true;
+    if (switches().attn_fused & 4) return true;
     // A tile is one wave's serial chain (40 us forward, 100 us adjoint): below a few waves per SIMD the launch costs that
     // latency whatever its size, and the three row-parallel kernels are quicker (one box, three-kernel / fused ms per step:
     // 1 000 atoms 1.69 / 2.18, 3 000: 2.96 / 3.29, 5 000: 4.16 / 4.08, 10 000: 7.30 / 6.72; model.h ABLK_MIN_TILES). Many
     // 64-slot tiles (the adjoint's instantiation for them spills): likewise.
     return g.n_tiles1 >= ABLK_MIN_TILES && (int64_t)g.n_tiles2 * 20 <= g.n_nodes;
 }
-bool ablk_bwd_on(const Graph& g) { return (g_attn_fused & 2) && ablk_serves(g); }
+bool ablk_bwd_on(const Graph& g) { return (switches().attn_fused & 2) && ablk_serves(g); }
 
 // atoms of at most 64 tokens (attention tile counts 1 .. 4 of the graph's bucket lists); false = not served
 bool ablk_fwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* X, float* X1, float* OC, float scale,
               hipStream_t st) {
-    if (!(g_attn_fused & 1) || !A.qkv.fwd2s || !A.out.fwd2s || !ablk_serves(g)) return false;
+    if (!(switches().attn_fused & 1) || !A.qkv.fwd2s || !A.out.fwd2s || !ablk_serves(g)) return false;
     const bool ln = m.layer_norm();
     const float qscale = scale * AB_LOG2E;
     const W2 wq = w2s_fwd(A.qkv), wo = w2s_fwd(A.out);

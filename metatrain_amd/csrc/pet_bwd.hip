@@ -227,10 +227,6 @@ __global__ __launch_bounds__(NTHREADS) void k_head_bwd(const float* __restrict__
     });
 }
 
-static int g_dxf_fused = 1;
-void set_dxf_fused(int v) { g_dxf_fused = v ? 1 : 0; }
-static inline bool dxf_fused_on() { return g_dxf_fused != 0; }
-
 // dXF[p] = dM[p] + dcat[p][:D] + dcat[rev[p]][D:]   (inference graphs on one rank: formed inside k_comb_bwd_p2 / k_emlp_bwd_p2
 // instead -- `dxf_fused` in backward())
 __global__ void k_dxf(const float* __restrict__ dM, const float* __restrict__ dcat, const int* __restrict__ rev,
@@ -1202,7 +1198,7 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
                 "configured for the three-kernel form: pet_config_set changed between forward and backward");
     // k_dxf folded into its producer and its consumer (pet_config_set("dxf_fused", 0): the separate kernel)
     bool node_cnt_zeroed = false;  // k_node_bwd2 SPLIT: arrival counters zeroed once per adjoint, then they reset themselves
-    const bool dxf_fused = trr_l && !tr && !res && !g.x_fn && m.h.num_attention_layers >= 1 && dxf_fused_on();
+    const bool dxf_fused = trr_l && !tr && !res && !g.x_fn && m.h.num_attention_layers >= 1 && switches().dxf_fused;
     PET_HIP_CHECK(hipMemsetAsync(w.dgeo, 0, E * 4 * sizeof(float), st));
     allow_big_lds(k_swiglu_bwd<256, DNF, false, true>, (BM * LD256 + BM * LD128) * 4);
     allow_big_lds(k_swiglu_bwd<256, DNF, true, true>, (BM * LD256 + BM * LD128) * 4);
@@ -1272,17 +1268,17 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
                 bool expand_done = false;
                 // large graphs: two shared-ring GEMMs and two row-wise kernels that can run BESIDE the edge kernels (pet_node_s.hip);
                 // scratch: the attention-output temporary of the forward pass, which no adjoint kernel touches
-                if (!tr && node_planes() && (size_t)N * 3 * DNF <= (size_t)R * D &&
+                if (!tr && switches().node_planes && (size_t)N * 3 * DNF <= (size_t)R * D &&
                     node_bwd_s(A, dH, Ab.H1, Ab.VGn, dH_alt, w.AO, N, ln, s2)) {
                 } else
-                if (!tr && node_planes() && wob.h && wib.h) {
+                if (!tr && switches().node_planes && wob.h && wib.h) {
                     const int nr = node_rows(N);
                     const size_t lds_nb = (size_t)nr * LD256 * 4 + (size_t)2 * nr * plane_ld(256) * 2 + nr * 8;
                     // small graphs: four workgroups per row tile (k_node_bwd2, SPLIT); partials and arrival counters in the
                     // attention-output temporary of the forward pass, which no adjoint kernel touches
                     const int nt32 = cdiv(N, 32);
                     const size_t p_floats = (size_t)(DNF / 128) * nt32 * 32 * DN;
-                    const bool split = nr == 32 && node_split_on() && nt32 <= 128 && p_floats + nt32 <= (size_t)R * D;
+                    const bool split = nr == 32 && switches().node_split && nt32 <= 128 && p_floats + nt32 <= (size_t)R * D;
                     if (split) {
                         int* cnt = reinterpret_cast<int*>(w.AO + p_floats);
                         if (!node_cnt_zeroed) PET_HIP_CHECK(hipMemsetAsync(cnt, 0, nt32 * sizeof(int), s2));

@@ -427,19 +427,13 @@ __global__ __launch_bounds__(256, 2) void k_emlp_bwd_s(const float* __restrict__
     store_rows_lines<16>(w, reinterpret_cast<float*>(tile), L, [&](int r) { return live && row0 + r < E ? dX1 + (row0 + r) * D : nullptr; });
 }
 
-// pet_config_set("emlp_s", v): 0 = the one-wave-per-SIMD pipelined kernels k_emlp_p2 / k_emlp_bwd_p2 everywhere; 1 = these
-// kernels for graphs of at least 28 672 edge rows (default: the measured crossover -- 1 000 atoms, 19 k rows: the pipelined
-// kernels 2 % ahead; 2 000 atoms, 38 k rows: these 1 % ahead); v > 1 = from v rows on (the tests force small graphs through)
-static int g_emlp_s = 1;
-static int64_t g_es_min_rows = 28672;
-void set_emlp_s(int v) {
-    g_emlp_s = v ? 1 : 0;
-    g_es_min_rows = v > 1 ? v : 28672;
-}
-bool emlp_s_serves(int64_t E) { return g_emlp_s && E >= g_es_min_rows; }
-bool emlp_s_forced() { return g_emlp_s && g_es_min_rows < 28672; }  // pet_config_set("emlp_s", v > 1): the tests' small graphs  // (the edge head's kernels follow the same policy: pet_head_s.hip)
+// pet_config_set("emlp_s", v): these kernels instead of the pipelined k_emlp_p2 / k_emlp_bwd_p2 from switches().emlp_s_rows
+// edge rows on (switches.h EMLP_S_MIN_ROWS; v > 1: the tests force small graphs through)
+bool emlp_s_serves(int64_t E) { return switches().emlp_s && E >= switches().emlp_s_rows; }
+// (the edge head's kernels follow the same policy: pet_head_s.hip)
+bool emlp_s_forced() { return switches().emlp_s && switches().emlp_s_rows < EMLP_S_MIN_ROWS; }
 bool emlp_recompute_on(const Lin& win, const Lin& wout, int64_t E) {
-    return g_emlp_s && E >= g_es_min_rows && win.fwd2s && wout.fwd2s && wout.bwd2s;
+    return emlp_s_serves(E) && win.fwd2s && wout.fwd2s && wout.bwd2s;
 }
 
 static inline W2 es_w2(const void* base, int n_out, int k_in) {
@@ -452,7 +446,7 @@ static inline W2 es_w2(const void* base, int n_out, int k_in) {
 // false = not served (weights not packed for it, or switched off)
 bool emlp_s(const float* X1, const float* gamma, const float* beta, const Lin& win, const Lin& wout, float* VG, float* X2,
             int64_t E, hipStream_t st) {
-    if (!g_emlp_s || !win.fwd2s || !wout.fwd2s || E < g_es_min_rows) return false;
+    if (!emlp_s_serves(E) || !win.fwd2s || !wout.fwd2s) return false;
     const size_t lds = ES_NW * 16384 + ES_NSLOT * ES_SLOT;
     const W2 wi = es_w2(win.fwd2s, win.n_out, win.k_in), wo = es_w2(wout.fwd2s, wout.n_out, wout.k_in);
     const int grid = (int)cdiv(E, ES_NW * WROWS);
@@ -469,7 +463,7 @@ bool emlp_s(const float* X1, const float* gamma, const float* beta, const Lin& w
 // the adjoint with recomputed pre-activations; false = not served
 bool emlp_bwd_s(const float* dY, const float* X1, bool ln, const Lin& win_g, const Lin& wout, float* dX1, int64_t E,
                 hipStream_t st, int ldy, const float* dY2, const int* rev2) {
-    if (!g_emlp_s || !win_g.fwd2s || !win_g.bwd2s || !wout.bwd2s) return false;
+    if (!switches().emlp_s || !win_g.fwd2s || !win_g.bwd2s || !wout.bwd2s) return false;
     if (E <= 0) return true;
     const size_t lds = ES_NW * 16384 + ES_NSLOT * ES_SLOT;
     const W2 wi = es_w2(win_g.fwd2s, win_g.n_out, win_g.k_in), wot = es_w2(wout.bwd2s, wout.n_out, wout.k_in),

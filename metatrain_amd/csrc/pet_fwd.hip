@@ -1007,18 +1007,10 @@ static Graph::FwdRecord& note_workspace(const Graph& g, const void* ws, bool gen
     return r;
 }
 
-static int g_node_split = 1;  // pet_config_set("node_split", 0): one workgroup per 32-row tile in k_node2<1> / k_node_bwd2<1>
-void set_node_split(int v) { g_node_split = v ? 1 : 0; }
-bool node_split_on() { return g_node_split != 0; }
-static int g_center_fused = 1;  // pet_config_set("center_fused", 0): the next layer's centre tokens by their own k_center launch
-void set_center_fused(int v) { g_center_fused = v ? 1 : 0; }
-static int g_node_planes = 1;  // k_node2 / k_node_bwd2: A tiles pre-split into fp16 planes (pet_config_set("node_planes", 0): k_node)
-void set_node_planes(int v) { g_node_planes = v > 2 ? 2 : v; }
-bool node_planes() { return g_node_planes != 0; }
 // rows per workgroup of k_node2 / k_node_bwd2: node_planes = 2 forces 32 (the tests' route to the 32-row kernels), 1 chooses by the number of atoms
 static int g_node_rows_threshold = 16384;  // measured: 1 000 / 3 000 / 10 000 atoms gain 14 / 8 / 2 %, 80 000 lose 8 % of the stage
 int node_rows(int64_t N) {
-    if (g_node_planes == 2) return 32;
+    if (switches().node_planes == 2) return 32;
     return N <= g_node_rows_threshold ? 32 : 64;
 }
 
@@ -1189,16 +1181,16 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
                 const WX wci = wx_fwd(A.cmlp_in), wce_ = wx_fwd(A.ce), wco = wx_fwd(A.cmlp_out);
                 // large graphs: three shared-ring GEMMs that can run BESIDE the edge MLP (pet_node_s.hip); its scratch lives in
                 // dQKV, which only the adjoint uses
-                if (node_planes() && (size_t)N * DNF <= (size_t)R * 3 * D &&
+                if (switches().node_planes && (size_t)N * DNF <= (size_t)R * 3 * D &&
                     node_fwd_s(A, Ab.H, Ab.OC, Ab.H1, Ab.VGn, Ab.Hn, w.dQKV, N, s2)) {
                 } else
-                if (node_planes() && wci.h && wce_.h && wco.h) {
+                if (switches().node_planes && wci.h && wce_.h && wco.h) {
                     const int nr = node_rows(N);
                     const size_t lds_n2 = (size_t)nr * LD256 * 4 + (size_t)2 * nr * plane_ld(256) * 2 + nr * 8;
                     // the next layer's centre tokens in the same launch when they are center_contraction(Hn) as it leaves this
                     // kernel: not behind the conditioning add, not into a residual GNN layer (its own embedding), f16x3 weights
                     const bool has_next = a + 1 < AL || gi + 1 < L;
-                    if (has_next && g_center_fused && nr == 32 && !(a + 1 == AL && (conditioned || res))) {  // (large graphs: k_center is quicker)
+                    if (has_next && switches().center_fused && nr == 32 && !(a + 1 == AL && (conditioned || res))) {  // (large graphs: k_center is quicker)
                         const AttnLayerW& An = a + 1 < AL ? G.attn[a + 1] : m.gnn[gi + 1].attn[0];
                         AttnBufs& Abn = a + 1 < AL ? B.attn[a + 1] : w.gnn[gi + 1].attn[0];
                         wcn = wx_fwd(An.cc);
@@ -1208,7 +1200,7 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
                     // arrival counters live in dQKV, which only the adjoint uses (k_node2, SPLIT)
                     const int nt32 = cdiv(N, 32);
                     const size_t p_floats = (size_t)(DNF / 128) * nt32 * 32 * DN;
-                    const bool split = nr == 32 && node_split_on() && nt32 <= 128 && p_floats + nt32 <= (size_t)R * 3 * D;
+                    const bool split = nr == 32 && switches().node_split && nt32 <= 128 && p_floats + nt32 <= (size_t)R * 3 * D;
                     if (split) {
                         int* cnt = reinterpret_cast<int*>(w.dQKV + p_floats);
                         if (!node_cnt_zeroed) PET_HIP_CHECK(hipMemsetAsync(cnt, 0, nt32 * sizeof(int), s2));

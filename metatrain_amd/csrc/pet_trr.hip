@@ -954,9 +954,6 @@ static inline int grid_rows(int64_t rows) { return cdiv(rows, WG_ROWS); }
 // MFMAs per K block; 1.7e-7 product error against fp64, tools/ubench). The fp32-MFMA and 3-way bf16 (bf16x6)
 // generations of round 1 were removed in round 2; pet_config_set("trr", 0) selects the LDS-tile kernels of
 // pet_fwd.hip / pet_bwd.hip, which are the one fallback (and the path of the LayerNorm / PostLN / residual variants).
-// pet_config_set("trr_compress", bits): 1 compress (+adjoint), 2 edge head (+adjoint); 0 = the LDS-tile kernels
-static int g_trr_tilek = 3;
-void set_trr_compress(int v) { g_trr_tilek = v; }
 
 // beta: the LayerNorm bias, nullptr = RMSNorm (here and below)
 void trr_qkv(const float* X, const float* gamma, const float* beta, const Lin& qkv, float* QKV, int64_t R,
@@ -1158,7 +1155,7 @@ __global__ __launch_bounds__(256) void k_head_bwd_h(const float* __restrict__ Xi
 
 bool trr_head_edge(const Model& m, const float* Xin, const float* fc, float* ypred, float* yout, int64_t E,
                    hipStream_t st) {
-    if (!((g_trr_tilek & 2) && m.eh0.fwd2 && m.eh2.fwd2)) return false;
+    if (!((switches().trr_compress & 2) && m.eh0.fwd2 && m.eh2.fwd2)) return false;
     if (head_edge_s(m, Xin, fc, ypred, yout, E, st)) return true;  // large graphs: two workgroups per CU, shared weight ring
     k_head_h<<<grid_rows(E), 256, 0, st>>>(Xin, w2_fwd(m.eh0), m.eh0.b, w2_fwd(m.eh2), m.eh2.b, m.ell_w, m.ell_b, fc, ypred,
                                            yout, E);
@@ -1167,7 +1164,7 @@ bool trr_head_edge(const Model& m, const float* Xin, const float* fc, float* ypr
 bool trr_head_edge_bwd(const Model& m, const float* Xin, const float* gA, const int* ctr, const float* fc,
                        const float* ypred, float* dfc, float* dXout, int64_t E, float* t_s1, float* t_da2, float* t_da1,
                        float* t_s2y, hipStream_t st) {
-    if (!((g_trr_tilek & 2) && m.eh0.fwd2 && m.eh2.fwd2 && m.eh0.bwd2 && m.eh2.bwd2)) return false;
+    if (!((switches().trr_compress & 2) && m.eh0.fwd2 && m.eh2.fwd2 && m.eh0.bwd2 && m.eh2.bwd2)) return false;
     if (!t_s1 && head_edge_bwd_s(m, Xin, gA, ctr, fc, ypred, dfc, dXout, E, st)) return true;  // (inference; pet_head_s.hip)
     const int grid = grid_rows(E);
     if (t_s1)
@@ -1183,7 +1180,7 @@ bool trr_head_edge_bwd(const Model& m, const float* Xin, const float* gA, const 
 
 bool trr_compress(bool first, const Graph& g, const GnnLayerW& G, const float* Min, float* a0_out, float* Xout,
                   int64_t E, hipStream_t st) {
-    if (!((g_trr_tilek & 1) && G.compress2.fwd2 && (first || G.compress0_msg.fwd2)) || E <= 0) return false;
+    if (!((switches().trr_compress & 1) && G.compress2.fwd2 && (first || G.compress0_msg.fwd2)) || E <= 0) return false;
     if (first)
         k_compress_h<true><<<grid_rows(E), 256, 0, st>>>(g.geo, g.sp_nbr, G.wc, G.tbl, nullptr, W2(), w2_fwd(G.compress2),
                                                        G.compress2.b, a0_out, Xout, E);
@@ -1194,7 +1191,7 @@ bool trr_compress(bool first, const Graph& g, const GnnLayerW& G, const float* M
 }
 bool trr_compress_bwd(bool first, const float* dXe, const float* a0, const GnnLayerW& G, float* dgeo, float* dM,
                       int64_t E, float* t_da0, hipStream_t st) {
-    if (!((g_trr_tilek & 1) && G.compress2.bwd2 && G.wc2 && (first || G.compress0_msg.bwd2)) || E <= 0) return false;
+    if (!((switches().trr_compress & 1) && G.compress2.bwd2 && G.wc2 && (first || G.compress0_msg.bwd2)) || E <= 0) return false;
     if (!t_da0 && compress_bwd_s(first, dXe, a0, G, dgeo, dM, E, st)) return true;  // (inference; pet_compress_s.hip)
     const int grid = grid_rows(E);
     if (first) {

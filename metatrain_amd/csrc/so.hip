@@ -360,18 +360,13 @@ __global__ __launch_bounds__(256) void k_rowgemm_n128(const float* __restrict__ 
     store_rows_lines<16>(y, lds, L, [&](int r) { return row0 + r < R ? Y + (row0 + r) * ldy : nullptr; });
 }
 
-static int g_so_trr = 1;  // pet_config_set("so_trr", 0): every generic GEMM through the LDS-tile k_gemm_h
-void set_so_trr(int v) { g_so_trr = v ? 1 : 0; }
 // Y[R, n_out] (=|+=) (X[R, K] * cs) W^T + bias on the TRR kernels when the shape allows; false otherwise
-static int g_train_bf16 = 0;  // pet_config_set("train_bf16", 1): ONE 16-bit MFMA term per product in the training GEMMs
-void set_train_bf16(int v) { g_train_bf16 = v ? 1 : 0; }
-int train_bf16() { return g_train_bf16; }
 static bool rowgemm_trr(hipStream_t st, const float* X, int K, const float* cs, W2 w, const float* bias, float* Y,
                         int n_out, int64_t R, bool acc) {
-    if (!g_so_trr) return false;
+    if (!switches().so_trr) return false;
     const int grid = (int)cdiv(R, WG_ROWS);
     if (K == 128 && n_out % 64 == 0) {
-        if (g_train_bf16) k_rowgemm_k128<true><<<grid, 256, 0, st>>>(X, K, cs, w, bias, Y, n_out, n_out, R, acc ? 1 : 0);
+        if (switches().train_bf16) k_rowgemm_k128<true><<<grid, 256, 0, st>>>(X, K, cs, w, bias, Y, n_out, n_out, R, acc ? 1 : 0);
         else k_rowgemm_k128<false><<<grid, 256, 0, st>>>(X, K, cs, w, bias, Y, n_out, n_out, R, acc ? 1 : 0);
         return true;
     }
@@ -379,7 +374,7 @@ static bool rowgemm_trr(hipStream_t st, const float* X, int K, const float* cs, 
         const size_t ts4 = (size_t)4 * (K / 16) * 64;  // four 32-column weight tiles
         for (int nb = 0; nb < n_out / 128; nb++) {
             W2 wn; wn.h = w.h + nb * ts4; wn.l = w.l + nb * ts4;
-            if (g_train_bf16)
+            if (switches().train_bf16)
                 k_rowgemm_n128<true><<<grid, 256, 0, st>>>(X, K, K, cs, wn, bias ? bias + 128 * nb : nullptr, Y + 128 * nb,
                                                            n_out, R, acc ? 1 : 0);
             else
@@ -391,8 +386,6 @@ static bool rowgemm_trr(hipStream_t st, const float* X, int K, const float* cs, 
     return false;
 }
 
-static int g_so_f16x3 = 1;  // pet_config_set("so_f16x3", 0): generic training GEMMs on the fp32 MFMA
-void set_so_f16x3(int v) { g_so_f16x3 = v ? 1 : 0; }
 static inline W2 w2_at(const void* base, int n_out, int k_in) {
     const size_t n8 = (size_t)(n_out / 32) * (k_in / 16) * 64;
     const f16x8* b = reinterpret_cast<const f16x8*>(base);
@@ -410,11 +403,12 @@ static void mm_fwd(const Ctx& c, const Lin& L, const float* X, float* Y, int64_t
                    bool acc = false) {
     if (R <= 0) return;
     ProfScope ps("so_gemm", c.st, 2.0 * (double)R * L.k_in * L.n_out, 4.0 * (double)R * (L.k_in + L.n_out));
-    if (g_so_f16x3 && !g_train_bf16 && g_so_trr &&
+    const Switches& sw = switches();
+    if (sw.so_f16x3 && !sw.train_bf16 && sw.so_trr &&
         rowgemm_s(c.st, X, L.k_in, cs, L.fwd2s, bias ? L.b : nullptr, Y, L.n_out, R, acc)) {  // large row counts (so_rows_s.hip)
-    } else if (g_so_f16x3 && L.fwd2 &&
+    } else if (sw.so_f16x3 && L.fwd2 &&
         rowgemm_trr(c.st, X, L.k_in, cs, w2_at(L.fwd2, L.n_out, L.k_in), bias ? L.b : nullptr, Y, L.n_out, R, acc)) {
-    } else if (g_so_f16x3 && L.fwd2)
+    } else if (sw.so_f16x3 && L.fwd2)
         k_gemm_h<<<cdiv(R, BM), NTHREADS, 2 * BM * LDB16 * 2 + BM * 4, c.st>>>(X, L.k_in, L.k_in, cs,
                                                                                w2_at(L.fwd2, L.n_out, L.k_in),
                                                                                bias ? L.b : nullptr, Y, L.n_out, L.n_out, R,
@@ -427,10 +421,11 @@ static void mm_fwd(const Ctx& c, const Lin& L, const float* X, float* Y, int64_t
 static void mm_bwd(const Ctx& c, const Lin& L, const float* Yadj, float* Xadj, int64_t R, bool acc = false) {
     if (R <= 0) return;
     ProfScope ps("so_gemm", c.st, 2.0 * (double)R * L.k_in * L.n_out, 4.0 * (double)R * (L.k_in + L.n_out));
-    if (g_so_f16x3 && !g_train_bf16 && g_so_trr && rowgemm_s(c.st, Yadj, L.n_out, nullptr, L.bwd2s, nullptr, Xadj, L.k_in, R, acc)) {
-    } else if (g_so_f16x3 && L.bwd2 &&
+    const Switches& sw = switches();
+    if (sw.so_f16x3 && !sw.train_bf16 && sw.so_trr && rowgemm_s(c.st, Yadj, L.n_out, nullptr, L.bwd2s, nullptr, Xadj, L.k_in, R, acc)) {
+    } else if (sw.so_f16x3 && L.bwd2 &&
         rowgemm_trr(c.st, Yadj, L.n_out, nullptr, w2_at(L.bwd2, L.k_in, L.n_out), nullptr, Xadj, L.k_in, R, acc)) {
-    } else if (g_so_f16x3 && L.bwd2)  // the transposed operand: tiles over k_in, K = n_out
+    } else if (sw.so_f16x3 && L.bwd2)  // the transposed operand: tiles over k_in, K = n_out
         k_gemm_h<<<cdiv(R, BM), NTHREADS, 2 * BM * LDB16 * 2 + BM * 4, c.st>>>(Yadj, L.n_out, L.n_out, nullptr,
                                                                                w2_at(L.bwd2, L.k_in, L.n_out), nullptr, Xadj,
                                                                                L.k_in, L.k_in, R, acc ? 1 : 0);

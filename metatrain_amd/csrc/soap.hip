@@ -32,9 +32,6 @@ __global__ void k_cell_grad(const float4* __restrict__ dv, const int* __restrict
 // abi.hip
 __global__ void k_pack(const float* __restrict__ W, int64_t s_n, int64_t s_k, int n_out, int k_in,
                        float4* __restrict__ out);
-static int g_soap_mfma = 1;  // pet_config_set("soap_mfma", 0) selects the per-atom tail kernels
-void set_soap_mfma(int v) { g_soap_mfma = v ? 1 : 0; }
-
 constexpr int MAXL = SOAP_MAX_L;
 constexpr int PC = 32;  // pairs per LDS chunk
 
@@ -86,9 +83,6 @@ struct SoapModel {
     int Kpp = 0;
     float *wallp = nullptr, *wallpb = nullptr;
     float4 *wallp_fwd_set = nullptr, *wallp_bwd_set = nullptr;
-    // which layout the last forward into a workspace left in its feature buffer (true = packed); soap_bwd and the training
-    // pass follow it (the training pass rebuilds the full layout from the stored expansion coefficients)
-    mutable std::map<const void*, bool> ws_packed;
     bool finalized = false;
 };
 
@@ -815,8 +809,6 @@ __global__ __launch_bounds__(256) void k_soap_ps_bwd_m(SoapDims d, const float* 
 // (The first-generation fused power-spectrum + tail kernels -- k_soap_ps_tail_fwd / _bwd behind pet_config_set("soap_fused", 1):
 // features never stored, but 4.3 + 7.0 ms against 0.5 + 0.6 + 0.9 + 0.7 for the separate kernels -- were removed in round 6:
 // the packed power spectrum halves the feature traffic at no cost in time.)
-static int g_soap_ps_mfma = 1;  // pet_config_set("soap_ps_mfma", 0): the power spectrum (and its adjoint) on the VALU kernels
-void set_soap_ps_mfma(int v) { g_soap_ps_mfma = v ? 1 : 0; }
 
 // ---------------------------------------------------------------------------------------------
 // a18, species-sorted tiles (pet_config_set("soap_sorted", 1), default): in legacy mode every atom uses ONE of the
@@ -1351,8 +1343,6 @@ __global__ __launch_bounds__(256) void k_soap_expand_bwd(SoapDims d, const float
 // otherwise soap_fwd / soap_bwd fall back to the first-generation kernels (pet_config_set("soap_pair", 0) too).
 // ---------------------------------------------------------------------------------------------
 constexpr int MAXI = 8;
-static int g_soap_pair = 1;
-void set_soap_pair(int v) { g_soap_pair = v ? 1 : 0; }
 
 template <int LMAX>
 struct ShLevels {  // the recurrences of sh_chain, all m-chains advanced one l at a time
@@ -1720,33 +1710,23 @@ static int soap_finalize(SoapModel& m, hipStream_t st) {
 }
 
 static bool soap_pair_ok(const SoapDims& d) {
-    return g_soap_pair && d.C == 4 && d.ITEMS <= 64 * MAXI && d.NLM <= 255 && d.F <= 255 && d.NCOEF < 32768;
+    return switches().soap_pair && d.C == 4 && d.ITEMS <= 64 * MAXI && d.NLM <= 255 && d.F <= 255 && d.NCOEF < 32768;
 }
-static int g_soap_sorted = 1;
-void set_soap_sorted(int v) { g_soap_sorted = v ? 1 : 0; }
 static bool soap_sorted_ok(const SoapModel& m) {
-    return g_soap_sorted && g_soap_mfma && m.NT > 0 && m.wall_fwd_set != nullptr && m.n_sets <= SP_MAXSETS;
+    return switches().soap_sorted && switches().soap_mfma && m.NT > 0 && m.wall_fwd_set != nullptr && m.n_sets <= SP_MAXSETS;
 }
-// pet_config_set("soap_packed", 0): the full [N][S] feature layout in inference too (the layout the training pass, the
-// feature output and the Alchemical centre encoding use)
-static int g_soap_packed = 1;
-void set_soap_packed(int v) { g_soap_packed = v ? 1 : 0; }
 static bool soap_packed_ok(const SoapModel& m) {
     for (int l = 0; l <= m.d.L; l++) {  // every block's triangle an even number of floats (k_soap_ps_m<true> stores 8 bytes per lane)
         const int nc = m.d.n_per_l[l] * m.d.C;
         if ((nc * (nc + 1) / 2) % 2) return false;
     }
-    return g_soap_packed && g_soap_pair && g_soap_ps_mfma && m.enc == nullptr && m.wallp_fwd_set != nullptr &&
+    const Switches& sw = switches();
+    return sw.soap_packed && sw.soap_pair && sw.soap_ps_mfma && m.enc == nullptr && m.wallp_fwd_set != nullptr &&
            m.d.ncmax <= 32 && (size_t)(m.d.NCOEF + m.d.Sp) * 4 <= 64 * 1024;
 }
-static void soap_note_layout(const SoapModel& m, const void* ws, bool packed) {
-    if (m.ws_packed.size() > 64) m.ws_packed.clear();
-    m.ws_packed[ws] = packed;
-}
-static bool soap_ws_packed(const SoapModel& m, const void* ws) {
-    auto it = m.ws_packed.find(ws);
-    return it != m.ws_packed.end() && it->second;
-}
+// soap_bwd / soap_train_grads without a record of the workspace's forward (Graph::FwdRecord: the last four workspaces)
+static constexpr const char* SOAP_NO_FORWARD =
+    "no soap_forward of this graph into this workspace (never run, or pushed out by forwards into four other workspaces)";
 static size_t lds_expand(const SoapDims& d) { return (size_t)PC * (d.NLM + d.F + 8 + 1) * 4; }
 static size_t lds_expand_bwd(const SoapDims& d) {
     return ((size_t)d.NCOEF + (size_t)PC * (4 * d.NLM + 2 * d.F + 8 + 1)) * 4;
@@ -1780,7 +1760,7 @@ static int soap_fwd(const SoapModel& m, const Graph& g, void* ws, int64_t ws_byt
         }
     }
     const bool packed = soap_sorted_ok(m) && soap_packed_ok(m) && features == nullptr;
-    soap_note_layout(m, ws, packed);
+    g.fwd_record_new(ws).soap_packed = packed;  // soap_bwd and the training pass follow the layout this forward stores
     {
     {
             ProfScope ps("soap_ps", st, 2.0 * (double)N * d.S * (d.L + 1), (double)N * (d.NCOEF + (packed ? d.Sp : d.S)) * 4);
@@ -1788,10 +1768,10 @@ static int soap_fwd(const SoapModel& m, const Graph& g, void* ws, int64_t ws_byt
                 const size_t lds_ps = (size_t)4 * (d.NCOEF + ((d.ncmax * (d.ncmax + 1) / 2 + 3) & ~3)) * 4;
                 allow_big_lds(k_soap_ps_m<true>, lds_ps);
                 k_soap_ps_m<true><<<cdiv(N, 4), 256, lds_ps, st>>>(d, w.Cf, g.sp, nullptr, w.feats, w.tail, N);
-            } else if (g_soap_pair && g_soap_ps_mfma && d.ncmax <= 32) {
+            } else if (switches().soap_pair && switches().soap_ps_mfma && d.ncmax <= 32) {
                 allow_big_lds(k_soap_ps_m<false>, (size_t)4 * d.NCOEF * 4);
                 k_soap_ps_m<false><<<cdiv(N, 4), 256, (size_t)4 * d.NCOEF * 4, st>>>(d, w.Cf, g.sp, m.enc, w.feats, w.tail, N);
-            } else if (g_soap_pair && d.ncmax < 128 && d.NCOEF < 65536) {
+            } else if (switches().soap_pair && d.ncmax < 128 && d.NCOEF < 65536) {
                 allow_big_lds(k_soap_ps_w, (size_t)4 * d.NCOEF * 4);
                 k_soap_ps_w<<<cdiv(N, 4), 256, (size_t)4 * d.NCOEF * 4, st>>>(d, w.Cf, g.sp, m.enc, m.feat_lut, w.feats,
                                                                             w.tail, N);
@@ -1812,7 +1792,7 @@ static int soap_fwd(const SoapModel& m, const Graph& g, void* ws, int64_t ws_byt
                 k_soap_tail_fwd_set<<<cdiv(N, BM) + m.n_sets, NTHREADS, lds, st>>>(
                     dt, w.feats, w.perm, w.info, m.n_sets, m.sets, packed ? m.wallp_fwd_set : m.wall_fwd_set,
                     packed ? m.Kpp : m.Kp, m.wall_rs, m.wall_b, w.tail, atomic);
-            } else if (m.NT > 0 && g_soap_mfma) {
+            } else if (m.NT > 0 && switches().soap_mfma) {
                 const int NOUTP = m.NOUTP, lda = lds_ld(128);
                 const size_t lds = ((size_t)BM * (NOUTP + 1 > lda ? NOUTP + 1 : lda) + BM * 32) * 4;
                 const int grid = cdiv(N, BM);
@@ -1844,6 +1824,8 @@ static int soap_bwd(const SoapModel& m, const Graph& g, void* ws, int64_t ws_byt
     PET_REQUIRE((int64_t)w.bytes <= ws_bytes, PET_ERR_ARGUMENT, "soap workspace too small");
     const int N = (int)g.n_nodes;
     if (N == 0) return PET_OK;
+    const Graph::FwdRecord* rec = g.fwd_record(ws);
+    PET_REQUIRE(rec, PET_ERR_ARGUMENT, SOAP_NO_FORWARD);
     if (g.n_edges == 0) {
         PET_HIP_CHECK(hipMemsetAsync(gpos, 0, (size_t)N * 3 * 4, st));
         if (gcell) PET_HIP_CHECK(hipMemsetAsync(gcell, 0, g.n_systems * 9 * 4, st));
@@ -1855,7 +1837,7 @@ static int soap_bwd(const SoapModel& m, const Graph& g, void* ws, int64_t ws_byt
         k_soap_tail_extra_bwd<<<cdiv(N, 4), 256, 0, st>>>(d, g.sp, m.sets, w.tail, w.tail_ext, gA, w.da2, N);
         da2x = w.da2;
     }
-    const bool packed = soap_ws_packed(m, ws);  // what the forward into this workspace stored
+    const bool packed = rec->soap_packed;  // what the forward into this workspace stored
     PET_REQUIRE(!packed || (soap_sorted_ok(m) && soap_packed_ok(m)), PET_ERR_ARGUMENT,
                 "the forward of this workspace stored the packed power spectrum but the adjoint is configured for the full "
                 "layout: pet_config_set changed between soap_forward and soap_backward");
@@ -1867,7 +1849,7 @@ static int soap_bwd(const SoapModel& m, const Graph& g, void* ws, int64_t ws_byt
             k_soap_tail_bwd_set<<<cdiv(N, BM) + m.n_sets, NTHREADS, lds, st>>>(
                 d, w.feats, w.perm, w.info, m.n_sets, g.sp, m.sets, packed ? m.wallp_bwd_set : m.wall_bwd_set,
                 packed ? m.Kpp : m.Kp, m.wall_rs, m.wall_b, m.enc, w.tail, gA, w.dF, da2x, packed ? 1 : 0);
-        } else if (m.NT > 0 && g_soap_mfma) {
+        } else if (m.NT > 0 && switches().soap_mfma) {
             const size_t lds = ((size_t)BM * lds_ld(m.NOUTP) + BM * 32 + BM * 4 + BM * lds_ld(128)) * 4;
             const int grid = cdiv(N, BM);
 #define SOAP_TAIL_BWD(NTV)                                                                                        \
@@ -1887,9 +1869,9 @@ static int soap_bwd(const SoapModel& m, const Graph& g, void* ws, int64_t ws_byt
         ProfScope ps("soap_ps_bwd", st, 4.0 * (double)N * d.S * (d.L + 1), (double)N * (2 * d.NCOEF + (packed ? d.Sp : d.S)) * 4);
         if (packed) {
             k_soap_ps_bwd_m<true><<<N, 256, (size_t)(d.NCOEF + d.Sp) * 4, st>>>(d, w.Cf, w.dF, w.dCf);
-        } else if (g_soap_pair && g_soap_ps_mfma && d.S % 4 == 0 && (size_t)(d.NCOEF + d.S) * 4 <= 64 * 1024) {
+        } else if (switches().soap_pair && switches().soap_ps_mfma && d.S % 4 == 0 && (size_t)(d.NCOEF + d.S) * 4 <= 64 * 1024) {
             k_soap_ps_bwd_m<false><<<N, 256, (size_t)(d.NCOEF + d.S) * 4, st>>>(d, w.Cf, w.dF, w.dCf);
-        } else if (g_soap_pair && d.S % 4 == 0 && d.NCOEF < 65536 && (size_t)(d.NCOEF + d.S) * 4 <= 64 * 1024) {
+        } else if (switches().soap_pair && d.S % 4 == 0 && d.NCOEF < 65536 && (size_t)(d.NCOEF + d.S) * 4 <= 64 * 1024) {
             k_soap_ps_bwd_s<<<N, 256, (size_t)(d.NCOEF + d.S) * 4, st>>>(d, w.Cf, w.dF, m.out_lut, w.dCf);
         } else {
             k_soap_ps_bwd<<<N, 256, (size_t)d.NCOEF * 4, st>>>(d, w.Cf, w.dF, m.coef_lut, w.dCf);

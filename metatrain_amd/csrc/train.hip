@@ -148,17 +148,13 @@ static void launch_k_wgrad(const WgradArgs& a, int nb, int nsplit, hipStream_t s
 }
 template <int XMODE>
 static void launch_k_wgrad_b(const WgradArgs& a, int nb, int nsplit, hipStream_t st) {
-    if (train_bf16()) {  // single-term mode: one plane per operand (20 KB)
+    if (switches().train_bf16) {  // single-term mode: one plane per operand (20 KB)
         k_wgrad_b<XMODE, true><<<nb * nsplit, NTHREADS, (size_t)2 * 128 * WB_LDW * sizeof(unsigned), st>>>(a, nb, nsplit);
         return;
     }
     const size_t lds = (size_t)6 * 128 * WB_LDW * sizeof(unsigned);  // 60 KB: two workgroups per CU
     k_wgrad_b<XMODE><<<nb * nsplit, NTHREADS, lds, st>>>(a, nb, nsplit);
 }
-
-// pet_config_set("wgrad_bf16", 0): weight gradients on the fp32 MFMA (k_wgrad) instead of bf16x3 (k_wgrad_b, default)
-static int g_wgrad_bf16 = 1;
-void set_wgrad_bf16(int v) { g_wgrad_bf16 = v ? 1 : 0; }
 
 // dW block [n_out, k_in] into dst (row stride ldw) and, if db_dst, the bias gradient
 static void wgrad_core(Trainer& t, int n_out, int k_in, Trainer::Y y, Trainer::X x, int xmode, int64_t n_rows,
@@ -168,7 +164,7 @@ static void wgrad_core(Trainer& t, int n_out, int k_in, Trainer::Y y, Trainer::X
     const int nb = n_out / 128;
     // bf16x3 kernel: 128 x columns per launch; the RMSNorm-hat source needs its whole row in one launch
     const bool whole_row = xmode == 1 || xmode == 5;  // the norm-hat sources need the whole row in one launch
-    const bool b16 = g_wgrad_bf16 && !(whole_row && k_in != 128);
+    const bool b16 = switches().wgrad_bf16 && !(whole_row && k_in != 128);
     const int KB = b16 ? 128 : ((whole_row || xmode == 4) ? k_in : 128);
     int nsplit = (b16 ? 512 : 768) / nb;  // two (bf16x3: 60 KB of LDS) / three (fp32: 34 - 50 KB) workgroups per CU
     const int64_t max_by_rows = (n_rows + WG_RB - 1) / WG_RB;

@@ -124,7 +124,27 @@ def test_config_switches_of_removed_kernel_generations_are_rejected(lib):
                 b"comb_bwd_pipe", b"emlp_recompute", b"line_stores", b"lds_w", b"attn_fwd4", b"emlp_s_min", b"tile_mask",
                 b"attn_lds", b"tile_f16x3", b"soap_fused", b"no_such_switch"):
         assert lib.pet_config_set(key, 0) == -3, key
-    for key, default in ((b"trr", 1), (b"attn_fused", 3), (b"trr_compress", 3), (b"soap_packed", 1),
-                         (b"node_planes", 1), (b"so_trr", 1), (b"so_f16x3", 1), (b"wgrad_bf16", 1), (b"side_stream", 1),
-                         (b"center_fused", 1), (b"dxf_fused", 1), (b"node_split", 1), (b"sorted_shortcut", 1), (b"train_bf16", 0), (b"soap_ps_mfma", 1), (b"emlp_s", 1)):
-        assert lib.pet_config_set(key, default) == 0, key
+    for key, default in DOCUMENTED_SWITCHES.items():
+        assert lib.pet_config_set(key.encode(), default) == 0, key
+
+
+# every key the pet_config_set description in include/pet_hip.h lists, with its documented default
+DOCUMENTED_SWITCHES = {
+    "side_stream": 1, "trr": 1, "attn_fused": 3, "emlp_s": 1, "trr_compress": 3, "node_planes": 1, "so_trr": 1,
+    "soap_ps_mfma": 1, "node_split": 1, "center_fused": 1, "sorted_shortcut": 1, "dxf_fused": 1, "train_bf16": 0,
+    "wgrad_bf16": 1, "so_f16x3": 1, "soap_mfma": 1, "soap_packed": 1, "soap_sorted": 1, "soap_pair": 1,
+}
+
+
+def test_config_keys_are_the_documented_ones(lib):
+    """The keys listed in the pet_config_set description of include/pet_hip.h (lines ``"key"  ...`` above the paragraph on
+    removed switches) are exactly the switches of DOCUMENTED_SWITCHES and the action key ``attn_fused_prof``: each one is
+    accepted, an undocumented probe is not."""
+    header = open(os.path.join(ROOT, "include", "pet_hip.h")).read()
+    block = header[header.index("/* Runtime switches"):header.index("int pet_config_set(")]
+    block = block[:block.index("(removed in round")]
+    documented = set(re.findall(r'^ \*   "([a-z0-9_]+)" ', block, re.M))
+    assert documented == set(DOCUMENTED_SWITCHES) | {"attn_fused_prof"}, documented ^ (set(DOCUMENTED_SWITCHES) | {"attn_fused_prof"})
+    for key in sorted(documented):
+        assert lib.pet_config_set(key.encode(), DOCUMENTED_SWITCHES.get(key, 0)) == 0, key
+    assert lib.pet_config_set(b"undocumented_probe", 0) == -3

@@ -447,6 +447,67 @@ def test_training_gradients_after_a_packed_forward():
     assert _relmax(res[1][1], res[0][1]) < 2e-6 and _relmax(res[1][2], res[0][2]) < 2e-6
 
 
+def test_feature_layout_is_recorded_per_graph_and_workspace():
+    """The layout a forward stored (packed power spectrum or full) is kept on the graph, one record per workspace
+    (Graph::FwdRecord). Two graphs through one model into two workspaces -- one packed, one full (features requested) -- and
+    their adjoints in the other order both match the oracle; an adjoint or a training pass on a workspace that no forward of
+    ITS graph wrote (a fresh one, or the other graph's) is refused instead of guessing a layout."""
+    from metatrain_amd import runtime as rt
+    from metatrain_amd._lib import PetHipError, check
+    from metatrain_amd.soap_bpnn import SoapBpnnHip
+
+    dev = torch.device("cuda:0")
+    types = [1, 6, 7, 8]
+    hypers = dict(osoap.DEFAULT_HYPERS, legacy=True)
+    params = osoap.synthetic_params(hypers, 4, osoap.basis(hypers)[0], 0, torch.float32)
+    p64 = {k: v.double() for k, v in params.items()}
+    model = SoapBpnnHip(hypers, types)
+    model.load({k: v.to(dev) for k, v in params.items()})
+    lib, h = model.lib, model._handle
+
+    systems = []
+    for n, seed in ((200, 9), (120, 4)):
+        pos, z, cells, ci, cj, cs, sysidx = _box(n, seed=seed)
+        _, g_ref, a_ref = osoap.energy_and_gradient(p64, hypers, types, pos, cells, ci, cj, cs, z, sysidx)
+        g = model.graph(pos.float().to(dev), cells.float().to(dev), ci.to(dev), cj.to(dev), cs.to(dev), z.to(dev),
+                        sysidx.int().to(dev))
+        systems.append((g, a_ref.numpy(), g_ref.numpy()))
+    # workspaces large enough for either graph: a refusal below is about the record, not the size
+    ws_bytes = max(int(lib.soap_workspace_bytes(h, g.n_nodes, g.n_edges)) for g, _, _ in systems)
+    wsa, wsb, fresh = (torch.empty(ws_bytes, dtype=torch.uint8, device=dev) for _ in range(3))
+
+    def forward(g, ws, features):
+        atomic = torch.empty(g.n_nodes, dtype=torch.float32, device=dev)
+        feats = torch.empty((g.n_nodes, model.feature_size), dtype=torch.float32, device=dev) if features else None
+        check(lib.soap_forward(h, g.handle, rt._ptr(ws), ws.numel(), rt._ptr(atomic), rt._ptr(feats), rt._stream()))
+        return atomic
+
+    def backward(g, ws):
+        ga = torch.ones(g.n_nodes, dtype=torch.float32, device=dev)
+        gpos = torch.empty((g.n_nodes, 3), dtype=torch.float32, device=dev)
+        check(lib.soap_backward(h, g.handle, rt._ptr(ws), ws.numel(), rt._ptr(ga), rt._ptr(gpos), None, rt._stream()))
+        return gpos
+
+    (ga_, a_ref_a, g_ref_a), (gb_, a_ref_b, g_ref_b) = systems
+    atomic_a = forward(ga_, wsa, features=False)  # packed layout (legacy model, no feature output)
+    atomic_b = forward(gb_, wsb, features=True)   # full layout
+    grad_b = backward(gb_, wsb)
+    grad_a = backward(ga_, wsa)
+    assert _relmax(atomic_a.cpu().numpy(), a_ref_a) < TOL and _relmax(grad_a.cpu().numpy(), g_ref_a) < TOL
+    assert _relmax(atomic_b.cpu().numpy(), a_ref_b) < TOL and _relmax(grad_b.cpu().numpy(), g_ref_b) < TOL
+
+    for ws in (fresh, wsb):  # never written / written by the other graph's forward only
+        with pytest.raises(PetHipError, match="no soap_forward of this graph"):
+            backward(ga_, ws)
+    model.zero_grad()
+    ga = torch.ones(ga_.n_nodes, dtype=torch.float32, device=dev)
+    tangent = torch.zeros(ga_.n_nodes, dtype=torch.float32, device=dev)
+    tws = torch.empty(int(lib.soap_train_workspace_bytes(h, ga_.n_nodes, ga_.n_edges)), dtype=torch.uint8, device=dev)
+    with pytest.raises(PetHipError, match="no soap_forward of this graph"):
+        check(lib.soap_train_gradients(h, ga_.handle, rt._ptr(fresh), fresh.numel(), rt._ptr(tws), tws.numel(),
+                                       rt._ptr(ga), None, rt._ptr(tangent), rt._stream()))
+
+
 @pytest.mark.parametrize("legacy,layers", [(True, 2), (False, 1), (True, 3)])
 def test_mlp_head(legacy, layers):
     """``heads: {energy: mlp}`` (soap_bpnn/documentation.py:117-122): one bias-free Linear(H, H) + SiLU per centre species between

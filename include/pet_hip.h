@@ -356,6 +356,22 @@ int pet_optimizer_state(pet_model_t* m, float* d_m, float* d_v, int64_t numel, i
  * the gradient slots of its two halves, counts the parameter once in the clipping norm and gives both halves the same
  * update, so that they stay equal. */
 int pet_model_tie_halves(pet_model_t* m, const char* key);
+/* ---- fine-tuning (pet/modules/finetuning.py) ---- */
+/* LoRA adapters. pet_model_set_param accepts the keys of a LoRA-injected Linear "<lin>" = gnn_layers.<g>.trans.layers.<a>.
+ * {attention.input_linear, attention.output_linear, mlp.w_in, mlp.w_out, center_mlp.w_in, center_mlp.w_out,
+ * center_contraction, center_expansion}: <lin>.linear.weight / .linear.bias (the base Linear), <lin>.lora_A.weight [r, k_in]
+ * and <lin>.lora_B.weight [n_out, r], rank r in 1 .. 64. They are ordinary parameters (gradient slots, Adam moments, places
+ * in the flat buffers, upload order). Adapter keys elsewhere: PET_ERR_UNSUPPORTED naming the key. The scale s = alpha / rank
+ * is not in the state dict: pet_model_set_lora_scaling(m, "<lin>", s). pet_model_finalize folds W_eff = W + s B A (fp64,
+ * deterministic) and builds every packed form from it (PET_ERR_ARGUMENT: no scaling, or A / B do not fit the base Linear;
+ * PET_ERR_UNSUPPORTED: a larger rank, or an adapter on a tied w_in -- activation = "SiLU"); the training reverse passes
+ * give lora_A dL/dA = s B^T dL/dW_eff and lora_B dL/dB = s dL/dW_eff A^T. pet_model_get_param("<lin>.linear.weight")
+ * is the base W. */
+int pet_model_set_lora_scaling(pet_model_t* m, const char* lin, float scaling);
+/* Frozen parameters (requires_grad = False; default: everything trainable). A frozen parameter's gradient slot stays zero
+ * after the training reverse passes, it is left out of the clipping norm, and pet_adam_step leaves it and its moments
+ * untouched (torch's optimizers skip a parameter without .grad). The weight-gradient work of frozen parameters is skipped. */
+int pet_model_set_trainable(pet_model_t* m, const char* key, int trainable);
 /* Workspace for pet_forward(save_for_backward = 2) + pet_backward_train. */
 int64_t pet_train_workspace_bytes(const pet_model_t* m, int64_t n_nodes, int64_t n_edges);
 int64_t pet_train_workspace_bytes_for(const pet_model_t* m, const pet_graph_t* g);   /* graph-aware (dense atoms) */

@@ -36,6 +36,7 @@ SYMBOLS = [
     "pet_model_zero_grad", "pet_model_get_grad", "pet_train_workspace_bytes", "pet_train_workspace_bytes_for",
     "pet_train2_workspace_bytes_for", "pet_backward_train",
     "pet_model_get_param", "pet_model_flat_grad", "pet_adam_step", "pet_optimizer_state", "pet_model_tie_halves",
+    "pet_model_set_lora_scaling", "pet_model_set_trainable",
     "pet_train2_workspace_bytes", "pet_backward_train2", "pet_backward_train2_cell",
     "pet_sum_over_atoms",
     "pet_profile_enable", "pet_profile_select", "pet_profile_reset", "pet_profile_report", "pet_config_set",
@@ -184,6 +185,8 @@ def load() -> ctypes.CDLL:
     lib.pet_adam_step.argtypes = [P, c_float, c_float, c_float, c_float, c_float, c_float, c_int64, P, P]
     lib.pet_optimizer_state.argtypes = [P, P, P, c_int64, c_int, P]
     lib.pet_model_tie_halves.argtypes = [P, c_char_p]
+    lib.pet_model_set_lora_scaling.argtypes = [P, c_char_p, c_float]
+    lib.pet_model_set_trainable.argtypes = [P, c_char_p, c_int]
     lib.pet_train2_workspace_bytes.argtypes = [P, c_int64, c_int64]
     lib.pet_train2_workspace_bytes.restype = c_int64
     lib.pet_backward_train2.argtypes = [P, P, P, c_int64, P, c_int64, P, P, P, P, P]

@@ -265,9 +265,15 @@ static int get(const Model& m, const std::string& key, int64_t numel, const floa
     return PET_OK;
 }
 
+// every raw-weight read of a Linear goes through here: an adapted Linear (LoRA, lora.hip) reads W_eff = W + s B A
 static int get_lin(Model& m, const std::string& key, int n_out, int k_in, Lin& L, hipStream_t st) {
     const float *w, *b;
     int rc;
+    if ((rc = lora_resolve(m, key, n_out, k_in, &w, &b, st)) != PET_OK) return rc;
+    if (w) {
+        m.lora_folded.insert(key);
+        return pack_lin(m, key, L, w, b, n_out, k_in, k_in, 0, st);
+    }
     if ((rc = get(m, key + ".weight", (int64_t)n_out * k_in, &w)) != PET_OK) return rc;
     if ((rc = get(m, key + ".bias", n_out, &b)) != PET_OK) return rc;
     return pack_lin(m, key, L, w, b, n_out, k_in, k_in, 0, st);
@@ -302,6 +308,7 @@ int finalize(Model& m, hipStream_t st) {
     // the model's own sizes (they shadow the compiled instantiation's constants, which only the tuned kernels use)
     const int D = h.d_pet, DN = h.d_node, DFF = h.d_feedforward, DNF = 2 * h.d_node, DH = h.d_head;
     const bool generic = m.generic(), expanded = DN != D;
+    m.lora_folded.clear();
     m.gnn.clear();
     m.gnn.resize(h.num_gnn_layers);
     for (int g = 0; g < h.num_gnn_layers; g++) {
@@ -467,6 +474,7 @@ int finalize(Model& m, hipStream_t st) {
         PET_HIP_CHECK(hipStreamSynchronize(st));
     }
     PET_REQUIRE(m.species_table != nullptr, PET_ERR_ARGUMENT, "missing species_to_species_index");
+    if ((rc = lora_check_all_folded(m, m.lora_folded))) return rc;
     m.finalized = true;
     return PET_OK;
 }
@@ -543,6 +551,10 @@ int pet_model_set_param(pet_model_t* pm, const char* key, const void* d_data, in
     }
     float* p;
     auto it = m.raw.find(k);
+    if (it == m.raw.end()) {
+        int rc = lora_register(m, k);  // LoRA-injected keys (<lin>.linear.weight, <lin>.lora_A.weight, ...)
+        if (rc) return rc;
+    }
     if (it != m.raw.end() && it->second.second == numel) {
         p = it->second.first;  // overwrite in place (weights updated by an optimizer step)
     } else {
@@ -565,6 +577,16 @@ int pet_model_set_param(pet_model_t* pm, const char* key, const void* d_data, in
 int pet_model_tie_halves(pet_model_t* pm, const char* key) {
     PET_REQUIRE(pm && key, PET_ERR_ARGUMENT, "null argument");
     return tie_halves(pm->m, key);
+}
+
+int pet_model_set_lora_scaling(pet_model_t* pm, const char* lin, float scaling) {
+    PET_REQUIRE(pm && lin, PET_ERR_ARGUMENT, "null argument");
+    return lora_set_scaling(pm->m, lin, scaling);
+}
+
+int pet_model_set_trainable(pet_model_t* pm, const char* key, int trainable) {
+    PET_REQUIRE(pm && key, PET_ERR_ARGUMENT, "null argument");
+    return set_trainable(pm->m, key, trainable != 0);
 }
 
 int pet_optimizer_state(pet_model_t* pm, float* d_m, float* d_v, int64_t numel, int direction, void* stream) {
@@ -656,8 +678,13 @@ int pet_backward_train(const pet_model_t* pm, const pet_graph_t* pg, void* d_wor
     if (pg && pg->g.n_nodes == 0) return PET_OK;  // an empty system: nothing to compute, zero-sized buffers may be null
     PET_REQUIRE(pm && pg && d_workspace && d_grad_atomic, PET_ERR_ARGUMENT, "null argument");
     PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
-    return backward_train(pm->m, pg->g, d_workspace, workspace_bytes, d_grad_atomic, d_grad_positions, d_grad_cells,
-                          (hipStream_t)stream);
+    Model& m = const_cast<Model&>(pm->m);  // the gradient slots (and LoRA scratch) are the model's mutable state
+    const hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = lora_begin(m, st))) return rc;
+    if ((rc = backward_train(m, pg->g, d_workspace, workspace_bytes, d_grad_atomic, d_grad_positions, d_grad_cells, st)))
+        return rc;
+    return lora_end(m, st);
 }
 
 int64_t pet_train2_workspace_bytes(const pet_model_t* pm, int64_t n_nodes, int64_t n_edges) {
@@ -671,8 +698,8 @@ int pet_backward_train2(const pet_model_t* pm, const pet_graph_t* pg, void* d_wo
     if (pg && pg->g.n_nodes == 0) return PET_OK;  // an empty system: nothing to compute, zero-sized buffers may be null
     PET_REQUIRE(pm && pg && d_workspace && d_workspace2 && d_lambda_atomic && d_u, PET_ERR_ARGUMENT, "null argument");
     PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
-    return backward_train2(pm->m, pg->g, d_workspace, workspace_bytes, d_workspace2, workspace2_bytes,
-                           d_lambda_atomic, d_nu_atomic, d_u, d_tangent_atomic, (hipStream_t)stream);
+    return pet_backward_train2_cell(pm, pg, d_workspace, workspace_bytes, d_workspace2, workspace2_bytes, d_lambda_atomic,
+                                    d_nu_atomic, d_u, nullptr, d_tangent_atomic, stream);
 }
 
 int pet_backward_train2_cell(const pet_model_t* pm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
@@ -683,8 +710,14 @@ int pet_backward_train2_cell(const pet_model_t* pm, const pet_graph_t* pg, void*
     PET_REQUIRE(pm && pg && d_workspace && d_workspace2 && d_lambda_atomic && d_u, PET_ERR_ARGUMENT, "null argument");
     PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
     PET_REQUIRE(!d_u_cell || pg->g.shift, PET_ERR_ARGUMENT, "a cell tangent needs a pet_graph_build handle (cell shifts)");
-    return backward_train2(pm->m, pg->g, d_workspace, workspace_bytes, d_workspace2, workspace2_bytes,
-                           d_lambda_atomic, d_nu_atomic, d_u, d_tangent_atomic, (hipStream_t)stream, d_u_cell);
+    Model& m = const_cast<Model&>(pm->m);
+    const hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = lora_begin(m, st))) return rc;
+    if ((rc = backward_train2(m, pg->g, d_workspace, workspace_bytes, d_workspace2, workspace2_bytes, d_lambda_atomic,
+                              d_nu_atomic, d_u, d_tangent_atomic, st, d_u_cell)))
+        return rc;
+    return lora_end(m, st);
 }
 
 int64_t pet_nl_workspace_bytes(int64_t n_atoms) { return nl_workspace_bytes(n_atoms); }

@@ -603,18 +603,21 @@ struct TOps {
     Lins lin;
     Ops o;
     TWs* w;
-    std::map<const float*, int64_t> off;   // raw parameter storage -> offset in the flat gradient
+    std::map<const float*, float*> off;   // raw parameter storage -> its gradient slot
     int err = PET_OK;
     TOps(const Model& m_, const Graph& g_, hipStream_t s, TWs* w_) : m(m_), g(g_), d(dims_of(m_)), st(s), lin{s}, o(m_, g_, s), w(w_) {
         for (const auto& kv : m.raw) {
             auto it = m.grad_off.find(kv.first);
-            if (it != m.grad_off.end()) off[kv.second.first] = it->second;
+            if (it != m.grad_off.end()) off[kv.second.first] = m.grad_flat + it->second;
         }
+        // a LoRA-adapted Linear is read as W_eff: its gradient goes to the adapter's dL/dW_eff (lora.hip projects it)
+        for (const auto& kv : m.lora)
+            if (kv.second.w_eff) off[kv.second.w_eff] = m.lora_grad + kv.second.dw_off;
     }
     float* slot(const float* raw) {
         auto it = off.find(raw);
         if (it == off.end()) { err = PET_ERR_ARGUMENT; set_error("gen_train: a parameter has no gradient slot"); return nullptr; }
-        return m.grad_flat + it->second;
+        return it->second;
     }
     float eps() const { return m.layer_norm() ? 1e-5f : 1.1920929e-07f; }
     // ---- dual forward pieces

@@ -2,6 +2,7 @@
 //  plus the packed / derived forms the kernels consume.
 #pragma once
 #include <map>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -75,6 +76,18 @@ inline bool compiled_size(const pet_hypers_t& h) {
     return h.d_pet == D && h.d_node == DN && h.d_feedforward == DFF && h.d_head == DH && h.num_heads == NHEAD;
 }
 
+// A LoRA adapter on one Linear "<lin>" (keys <lin>.linear.{weight,bias}, <lin>.lora_A.weight [r, k_in],
+// <lin>.lora_B.weight [n_out, r]): the kernels read W_eff = W + scaling B A, folded by finalize; the reverse passes write
+// dL/dW_eff into `dw` (a slice of Model::lora_grad) and lora_project() turns it into the A / B (and W) gradients.
+struct LoraW {
+    float scaling = 0.f;
+    bool has_scaling = false;
+    int rank = 0, n_out = 0, k_in = 0;
+    const float *w = nullptr, *a = nullptr, *b = nullptr;  // raw base weight, A, B
+    float* w_eff = nullptr;
+    int64_t dw_off = 0;  // offset of dL/dW_eff in Model::lora_grad
+};
+
 struct Model {
     pet_hypers_t h;
     bool generic() const { return !compiled_size(h); }
@@ -124,7 +137,34 @@ struct Model {
     int64_t* d_ties = nullptr;
     uint8_t* d_dup = nullptr;  // [n_params] 1 on the second copy of a tied parameter
     int64_t max_tie_half = 0;
+    // fine-tuning: LoRA adapters keyed by "<lin>", parameters frozen by pet_model_set_trainable
+    std::map<std::string, LoraW> lora;
+    float* lora_grad = nullptr;  // dL/dW_eff of every adapted Linear, cleared by every reverse entry point
+    int64_t lora_floats = 0;
+    std::set<std::string> lora_folded;  // adapters finalize has folded (each must meet its Linear)
+    std::set<std::string> frozen;
+    bool frozen_dirty = false;
+    uint8_t* d_frozen = nullptr;  // [n_params] 1 on a frozen parameter's entries
+    int64_t frozen_mask_n = 0;    // n_params the mask was built for
+    bool is_frozen(const std::string& key) const { return !frozen.empty() && frozen.count(key) > 0; }
+    // the adapter whose W_eff stands for "<lin>.weight" (nullptr: not adapted)
+    const LoraW* adapter(const std::string& lin) const {
+        if (lora.empty()) return nullptr;
+        auto it = lora.find(lin);
+        return it == lora.end() ? nullptr : &it->second;
+    }
 };
+
+// lora.hip: the fold W_eff = W + s B A (finalize), the gradient projection of the reverse entry points, frozen slots
+int lora_register(Model& m, const std::string& key);  // pet_model_set_param: placement check of an injected key
+int lora_set_scaling(Model& m, const std::string& lin, float scaling);
+// finalize: the weight and bias every raw read of Linear "<lin>" goes through (W_eff and <lin>.linear.bias when adapted)
+int lora_resolve(Model& m, const std::string& lin, int n_out, int k_in, const float** w, const float** b, hipStream_t st);
+int lora_check_all_folded(const Model& m, const std::set<std::string>& folded);
+int lora_begin(Model& m, hipStream_t st);                           // reverse entry: clear dL/dW_eff
+int lora_end(Model& m, hipStream_t st);                             // reverse exit: project, clear frozen slots
+int set_trainable(Model& m, const std::string& key, bool trainable);
+const uint8_t* frozen_mask(Model& m, hipStream_t st);  // nullptr: nothing frozen
 
 // abi.hip
 int dev_alloc(Model& m, void** p, size_t bytes);

@@ -17,14 +17,15 @@ constexpr int NORM_BLOCKS = 256;
 
 // `dup` (optional) marks the second copy of a tied parameter (activation = "SiLU": w_in is held as [W; W]): the norm is
 // that of the reference's parameter list, which has W once
+// `frozen` (optional) marks the entries of frozen parameters (pet_model_set_trainable): not in the norm, not updated
 __global__ void k_sumsq_partial(const float* __restrict__ g, int64_t n, double* __restrict__ partial,
-                                const uint8_t* __restrict__ dup) {
+                                const uint8_t* __restrict__ dup, const uint8_t* __restrict__ frozen) {
     __shared__ double red[256];
     const int64_t per = (n + gridDim.x - 1) / gridDim.x;
     const int64_t i0 = (int64_t)blockIdx.x * per, i1 = min(n, i0 + per);
     double s = 0.0;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256)
-        if (!dup || !dup[i]) s += (double)g[i] * (double)g[i];
+        if ((!dup || !dup[i]) && (!frozen || !frozen[i])) s += (double)g[i] * (double)g[i];
     red[threadIdx.x] = s;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -54,9 +55,9 @@ __global__ void k_clip_coef(const double* __restrict__ partial, int nb, float ma
 __global__ void k_adam(float* const* __restrict__ seg_ptr, const int64_t* __restrict__ seg_off, int n_seg,
                        float* __restrict__ g, float* __restrict__ mom, float* __restrict__ var, int64_t n,
                        const float* __restrict__ scalars, float lr, float beta1, float beta2, float eps,
-                       float weight_decay, float bc1, float bc2_sqrt) {
+                       float weight_decay, float bc1, float bc2_sqrt, const uint8_t* __restrict__ frozen) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n || (frozen && frozen[i])) return;  // torch skips a parameter without .grad: value and moments stay
     int lo = 0, hi = n_seg;  // last segment with seg_off[s] <= i
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
@@ -93,6 +94,10 @@ int tie_halves(Model& m, const std::string& key) {
     PET_REQUIRE(it != m.grad_off.end(), PET_ERR_ARGUMENT, "unknown parameter '" + key + "'");
     const int64_t numel = m.raw.at(key).second;
     PET_REQUIRE(numel % 2 == 0, PET_ERR_ARGUMENT, "a tied parameter has an even number of elements");
+    const std::string sfx = ".linear.weight";
+    PET_REQUIRE(!(key.size() > sfx.size() && key.compare(key.size() - sfx.size(), sfx.size(), sfx) == 0 &&
+                  m.lora.count(key.substr(0, key.size() - sfx.size()))),
+                PET_ERR_UNSUPPORTED, "'" + key + "': a LoRA adapter on a tied (activation = SiLU) w_in is not served");
     for (size_t k = 0; k + 1 < m.ties.size(); k += 2)
         if (m.ties[k] == it->second) return PET_OK;  // already registered
     m.ties.push_back(it->second);
@@ -165,13 +170,15 @@ int adam_step(Model& m, float lr, float beta1, float beta2, float eps, float wei
     if (n_ties > 0)
         k_tie_grads<<<dim3(cdiv(m.max_tie_half, 256), n_ties), 256, 0, st>>>(m.grad_flat, m.d_ties, n_ties);
     double* partial = reinterpret_cast<double*>(m.opt_scalars + 4);
-    k_sumsq_partial<<<NORM_BLOCKS, 256, 0, st>>>(m.grad_flat, m.n_params, partial, n_ties > 0 ? m.d_dup : nullptr);
+    const uint8_t* frozen = frozen_mask(m, st);  // (its failure has set the error message)
+    if (!m.frozen.empty() && !frozen) return PET_ERR_HIP;
+    k_sumsq_partial<<<NORM_BLOCKS, 256, 0, st>>>(m.grad_flat, m.n_params, partial, n_ties > 0 ? m.d_dup : nullptr, frozen);
     k_clip_coef<<<1, 1, 0, st>>>(partial, NORM_BLOCKS, max_grad_norm, m.opt_scalars);
     const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
     const float bc2_sqrt = (float)sqrt(1.0 - pow((double)beta2, (double)step));
     k_adam<<<cdiv(m.n_params, 256), 256, 0, st>>>(m.seg_ptr, m.seg_off, m.n_seg, m.grad_flat, m.adam_m, m.adam_v,
                                                   m.n_params, m.opt_scalars, lr, beta1, beta2, eps, weight_decay, bc1,
-                                                  bc2_sqrt);
+                                                  bc2_sqrt, frozen);
     PET_HIP_CHECK(hipGetLastError());
     if (d_grad_norm)
         PET_HIP_CHECK(hipMemcpyAsync(d_grad_norm, m.opt_scalars, sizeof(float), hipMemcpyDeviceToDevice, st));

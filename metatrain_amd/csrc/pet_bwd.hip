@@ -1643,6 +1643,7 @@ int backward_train(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, c
     Trainer tr{m, g, w, m.grad_flat, st};
     int rc;
     if ((rc = backward_predict(m, g, w, gA, st, &tr))) return rc;
+    if (!gpos && !tr.backbone_live()) return tr.err;  // only heads / last layers train
     if ((rc = backward_features(m, g, w, st, &tr))) return rc;
     if (tr.err) return tr.err;
     if (gpos) return backward_geometry(m, g, w, w.dgeo, w.dfc, w.dbias, gpos, gcell, st);

@@ -1232,8 +1232,8 @@ static void head_reverse(const Ctx& c, Trainer& tr, SoWs& s, bool edge, const Li
     float *l2 = s.tmp[0], *n2 = s.tmp[1], *G = s.tmp[2], *l1 = s.tmp[3], *n1 = s.tmp[4];
     k_last_layer<<<cdiv(rows, 8), 256, 0, c.st>>>(h.s2, h.Ts2, wl, bl, lA, nA, edge ? c.g.ctr : nullptr, c.g.fc, s.Tfc,
                                                   l2, n2, G, s.nep, tan_out, rows);
-    tr.colsum(G, rows, DH, tr.gp(lk + ".weight"));
-    tr.vecsum(s.nep, rows, tr.gp(lk + ".bias"));
+    tr.colsum(G, rows, DH, tr.gl(lk + ".weight"));
+    tr.vecsum(s.nep, rows, tr.gl(lk + ".bias"));
     k_silu_rev<<<grid1(rows * DH), 256, 0, c.st>>>(h.a2, h.Ta2, l2, n2, rows * DH);  // -> (l_a2, n_a2)
     tr.linear(hk + ".2", DH, DH, {n2, nullptr, 0, DH}, {h.s1, DH, 0, nullptr, nullptr}, 0, rows);
     tr.linear(hk + ".2", DH, DH, {l2, nullptr, 0, DH}, {h.Ts1, DH, 0, nullptr, nullptr}, 0, rows, false);
@@ -1345,6 +1345,7 @@ int backward_train2(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, 
     head_reverse(c, tr, s, false, m.nh0, m.nh2, m.nll_w, m.nll_b, last.Hout, THlast, DN, s.hn, lA, nA, s.tan_n, s.LH,
                  s.NH, N);
     if (tangent_atomic) k_tangent_atom_sum<<<grid1(N), 256, 0, st>>>(s.tan_n, s.tan_e, g.rowptr, tangent_atomic, (int)N);
+    if (!tr.backbone_live()) return tr.err;  // only heads / last layers train: the backbone's sweep has nothing to give
     float *t0 = s.tmp[0], *t1 = s.tmp[1], *t2 = s.tmp[2], *t3 = s.tmp[3], *t4 = s.tmp[4], *t5 = s.tmp[5];
     const bool lnm = m.layer_norm();
     const int nx = lnm ? 5 : 1;  // weight-gradient row source: LayerNorm-hat / RMSNorm-hat of the saved input
@@ -1463,8 +1464,8 @@ int backward_train2(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, 
         if (tr.err) return tr.err;
     }
     // embeddings: H0 = node_emb[species], M0 = edge_emb[neighbour species] (their tangents are zero)
-    tr.species_rows(s.NH, g.sp, N, DN, tr.gp("node_embedders.0.weight"));
-    tr.species_rows(s.NM, g.sp_nbr, E, D, tr.gp("edge_embedder.weight"));
+    tr.species_rows(s.NH, g.sp, N, DN, tr.gl("node_embedders.0.weight"));
+    tr.species_rows(s.NM, g.sp_nbr, E, D, tr.gl("edge_embedder.weight"));
     tr.cond_finish();
     PET_HIP_CHECK(hipGetLastError());
     return tr.err;

@@ -9,6 +9,7 @@
 #include <torch/custom_class.h>
 #include <torch/script.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -177,12 +178,27 @@ struct PetHipBackend : torch::CustomClassHolder {
     int64_t model_device = -1;
     std::vector<std::pair<void*, int64_t>> stamp;
     int64_t generation = 0;  // bumped by every re-upload: a backward checks that its forward saw the same weights
+    std::vector<std::string> lora_lins;  // adapted Linears, their scalings at hypers[n_fields + i]
+    size_t n_fields = 0;
 
     PetHipBackend(std::vector<double> hypers_, std::vector<int64_t> atomic_types_, std::vector<std::string> keys_)
         : hypers(std::move(hypers_)), atomic_types(std::move(atomic_types_)), keys(std::move(keys_)) {
-        TORCH_CHECK(hypers.size() == 17 || hypers.size() == 20 || hypers.size() == 21 || hypers.size() == 24,
+        // LoRA adapters (pet/modules/finetuning.py): one scaling per "<lin>.lora_A.weight" key, in key order, after the
+        // hypers fields (the scalings are not in the state dict; this way they are pickled with the class)
+        const std::string sfx = ".lora_A.weight";
+        for (const auto& k : keys)
+            if (k.size() > sfx.size() && k.compare(k.size() - sfx.size(), sfx.size(), sfx) == 0)
+                lora_lins.push_back(k.substr(0, k.size() - sfx.size()));
+        TORCH_CHECK(hypers.size() >= lora_lins.size(), "pet_hip: no LoRA scalings");
+        n_fields = hypers.size() - lora_lins.size();
+        TORCH_CHECK(n_fields == 17 || n_fields == 20 || n_fields == 21 || n_fields == 24,
                     "pet_hip: expected the first 16 fields of pet_hypers_t, the SiLU flag and (optionally) normalization, "
-                    "transformer_type, featurizer_type, adaptive_cutoff_method");
+                    "transformer_type, featurizer_type, adaptive_cutoff_method, then one scaling per LoRA adapter");
+        TORCH_CHECK(hypers[16] == 0.0 || std::none_of(lora_lins.begin(), lora_lins.end(), [](const std::string& l) {
+                        return l.size() > 5 && l.compare(l.size() - 5, 5, ".w_in") == 0;
+                    }),
+                    "pet_hip: a LoRA adapter on w_in of an activation = 'SiLU' model is not served (the kernels hold that "
+                    "projection as two tied copies)");
     }
     ~PetHipBackend() override {
         if (model) pet_model_destroy(model);
@@ -197,12 +213,12 @@ struct PetHipBackend : torch::CustomClassHolder {
         h.attention_temperature = (float)hypers[10]; h.nl_is_strict = (int32_t)hypers[11];
         h.n_species = (int32_t)hypers[12]; h.max_atomic_number = (int32_t)hypers[13];
         h.num_neighbors_adaptive = (float)hypers[14]; h.cutoff_width_adaptive = (float)hypers[15];
-        if (hypers.size() >= 20) {
+        if (n_fields >= 20) {
             h.normalization = (int32_t)hypers[17]; h.transformer_type = (int32_t)hypers[18];
             h.featurizer_type = (int32_t)hypers[19];
         }
-        if (hypers.size() >= 21) h.adaptive_cutoff_method = (int32_t)hypers[20];
-        if (hypers.size() >= 24) {
+        if (n_fields >= 21) h.adaptive_cutoff_method = (int32_t)hypers[20];
+        if (n_fields >= 24) {
             h.system_conditioning = (int32_t)hypers[21]; h.max_charge = (int32_t)hypers[22];
             h.max_spin_multiplicity = (int32_t)hypers[23];
         }
@@ -240,6 +256,8 @@ struct PetHipBackend : torch::CustomClassHolder {
             keep.push_back(t);
         }
         c10::hip::getCurrentHIPStream(like.device().index()).synchronize();  // the uploads read temporaries
+        for (size_t i = 0; i < lora_lins.size(); i++)
+            check(pet_model_set_lora_scaling(model, lora_lins[i].c_str(), (float)hypers[n_fields + i]), lora_lins[i].c_str());
         check(pet_model_finalize(model, st), "pet_model_finalize");
         model_device = like.device().index();
         stamp.clear();

@@ -18,7 +18,14 @@ struct Trainer {
     hipStream_t st;
     int err = PET_OK;
 
-    float* gp(const std::string& key) const;  // destination of one parameter's gradient
+    // destination of one parameter's gradient; "<lin>.weight" / "<lin>.bias" of a LoRA-adapted Linear name dL/dW_eff
+    // (lora.hip projects it) and <lin>.linear.bias
+    float* gp(const std::string& key) const;
+    // the gradient of `key` is wanted: not frozen, or an adapted weight (its adapters take dL/dW_eff)
+    bool live(const std::string& key) const;
+    // some parameter outside the fused heads and last layers is trainable
+    bool backbone_live() const;
+    float* gl(const std::string& key) const { return live(key) ? gp(key) : nullptr; }  // nullptr: frozen, skip the reduction
 
     // generic y = x W^T + b: dW [n_out, k_in] (+ db) from dY rows and rebuilt X rows
     struct Y { const float* p0; const float* p1; int64_t split; int ld; };

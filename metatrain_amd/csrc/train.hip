@@ -9,8 +9,41 @@
 namespace pet {
 
 float* Trainer::gp(const std::string& key) const {
+    if (!m.lora.empty()) {
+        const size_t dot = key.rfind('.');
+        if (dot != std::string::npos) {
+            const std::string lin = key.substr(0, dot), leaf = key.substr(dot + 1);
+            if (const LoraW* L = m.adapter(lin)) {
+                if (leaf == "weight") return m.lora_grad + L->dw_off;
+                if (leaf == "bias") return gp(lin + ".linear.bias");
+            }
+        }
+    }
     auto it = m.grad_off.find(key);
     return it == m.grad_off.end() ? nullptr : grads + it->second;
+}
+
+bool Trainer::backbone_live() const {
+    if (m.frozen.empty()) return true;
+    for (const auto& kv : m.grad_off) {
+        const std::string& k = kv.first;
+        const bool head = k.rfind("node_heads.", 0) == 0 || k.rfind("edge_heads.", 0) == 0 ||
+                          k.rfind("node_last_layers.", 0) == 0 || k.rfind("edge_last_layers.", 0) == 0;
+        if (!head && !m.is_frozen(k)) return true;
+    }
+    return false;
+}
+
+bool Trainer::live(const std::string& key) const {
+    if (m.frozen.empty()) return true;
+    const size_t dot = key.rfind('.');
+    if (dot != std::string::npos && m.adapter(key.substr(0, dot))) {
+        const std::string lin = key.substr(0, dot);
+        if (key.compare(dot + 1, std::string::npos, "bias") == 0) return !m.is_frozen(lin + ".linear.bias");
+        return !m.is_frozen(lin + ".linear.weight") || !m.is_frozen(lin + ".lora_A.weight") ||
+               !m.is_frozen(lin + ".lora_B.weight");
+    }
+    return !m.is_frozen(key);
 }
 
 #define TR_CHECK(expr)                                         \
@@ -210,6 +243,7 @@ static void wgrad_core(Trainer& t, int n_out, int k_in, Trainer::Y y, Trainer::X
 
 void Trainer::linear(const std::string& key, int n_out, int k_in, Y y, X x, int xmode, int64_t n_rows,
                      bool with_bias) {
+    if (!live(key + ".weight") && !(with_bias && live(key + ".bias"))) return;  // frozen: no weight-gradient GEMM
     float* dW = gp(key + ".weight");
     float* db = with_bias ? gp(key + ".bias") : nullptr;
     if (!dW) { err = PET_ERR_ARGUMENT; set_error("no gradient slot for " + key); return; }
@@ -220,6 +254,8 @@ void Trainer::linear_after_norm(const std::string& key, const float* W, int n_ou
                                 int64_t n_rows, const std::string& gamma_key, const float* gamma,
                                 const std::string& beta_key, const float* beta, bool tangent_pair) {
     if (n_rows <= 0 || err) return;
+    if (!live(key + ".weight") && !live(key + ".bias") && !live(gamma_key) && (beta_key.empty() || !live(beta_key)))
+        return;  // the Linear and its norm are frozen
     float* dW = gp(key + ".weight");
     float* db = gp(key + ".bias");
     float* dgamma = gp(gamma_key);
@@ -334,6 +370,10 @@ void Trainer::cond_accumulate(const float* dHout, bool first) {
 void Trainer::cond_finish() {
     if (!m.h.system_conditioning || err) return;
     const std::string sc = "system_conditioning.";
+    if (!live(sc + "charge_embedding.weight") && !live(sc + "spin_multiplicity_embedding.weight") &&
+        !live(sc + "project.0.weight") && !live(sc + "project.0.bias") && !live(sc + "project.2.weight") &&
+        !live(sc + "project.2.bias"))
+        return;
     float *gq = gp(sc + "charge_embedding.weight"), *gm = gp(sc + "spin_multiplicity_embedding.weight");
     float *gw0 = gp(sc + "project.0.weight"), *gb0 = gp(sc + "project.0.bias");
     float *gw2 = gp(sc + "project.2.weight"), *gb2 = gp(sc + "project.2.bias");
@@ -356,28 +396,32 @@ void Trainer::heads(bool edge, const float* Xin, int k_in, int64_t n_rows, const
     linear(h + ".2", DH, DH, {w.hda2, nullptr, 0, DH}, {w.hs1, DH, 0, nullptr, nullptr}, 0, n_rows);
     // last layer: d w = colsum(gy * s2), d b = sum gy
     const int nsplit = 256;
-    k_colsum_partial<<<nsplit, 128, 0, st>>>(w.hs2y, n_rows, DH, w.partial);
-    reduce_2d(w.partial, nsplit, DH, 1, gp(l + ".weight"), 1, 0, 1, st);
-    k_edge_gy_sum_partial<<<nsplit, 256, 0, st>>>(gA, edge ? g.ctr : nullptr, g.fc, n_rows, w.partial);
-    reduce_2d(w.partial, nsplit, 1, 1, gp(l + ".bias"), 1, 0, 1, st);
+    if (float* dw = gl(l + ".weight")) {
+        k_colsum_partial<<<nsplit, 128, 0, st>>>(w.hs2y, n_rows, DH, w.partial);
+        reduce_2d(w.partial, nsplit, DH, 1, dw, 1, 0, 1, st);
+    }
+    if (float* db = gl(l + ".bias")) {
+        k_edge_gy_sum_partial<<<nsplit, 256, 0, st>>>(gA, edge ? g.ctr : nullptr, g.fc, n_rows, w.partial);
+        reduce_2d(w.partial, nsplit, 1, 1, db, 1, 0, 1, st);
+    }
 }
 
 void Trainer::colsum(const float* buf, int64_t n_rows, int C, float* dst) {
-    if (n_rows <= 0 || err) return;
+    if (n_rows <= 0 || err || !dst) return;
     const int nsplit = 256;
     k_colsum_partial<<<nsplit, 256, 0, st>>>(buf, n_rows, C, w.partial);
     reduce_2d(w.partial, nsplit, C, 1, dst, 1, 0, 1, st);
 }
 
 void Trainer::vecsum(const float* vec, int64_t n_rows, float* dst) {
-    if (n_rows <= 0 || err) return;
+    if (n_rows <= 0 || err || !dst) return;
     const int nsplit = 256;
     k_edge_gy_sum_partial<<<nsplit, 256, 0, st>>>(vec, nullptr, nullptr, n_rows, w.partial);
     reduce_2d(w.partial, nsplit, 1, 1, dst, 1, 0, 1, st);
 }
 
 static void species_sum(Trainer& t, const float* buf, const int* idx, int64_t n_rows, int C, float* dst /*[ns,C]*/) {
-    if (n_rows <= 0 || t.err) return;
+    if (n_rows <= 0 || t.err || !dst) return;  // no destination: a frozen embedding
     const int ns = t.m.h.n_species;
     const int nsplit = 2048;
     // the species axis in chunks of 64 KB / (4 C): 64 species for the node embedding (C = 256), 128 for the edge ones
@@ -394,9 +438,9 @@ void Trainer::species_rows(const float* buf, const int* idx, int64_t n_rows, int
 }
 
 void Trainer::embeddings(const float* dH0, const float* dM0) {
-    species_sum(*this, dH0, g.sp, g.n_nodes, DN, gp("node_embedders.0.weight"));
+    species_sum(*this, dH0, g.sp, g.n_nodes, DN, gl("node_embedders.0.weight"));
     // layer-0 messages are edge_embedder[species of the neighbour] (backend.py:516): residual path
-    species_sum(*this, dM0, g.sp_nbr, g.n_edges, D, gp("edge_embedder.weight"));
+    species_sum(*this, dM0, g.sp_nbr, g.n_edges, D, gl("edge_embedder.weight"));
 }
 
 // compress.0 was folded at load time (abi.hip finalize):
@@ -409,6 +453,9 @@ void Trainer::compress0(int gi, const float* da0, const float* Min, const float*
     const int ns = m.h.n_species;
     const int kin = (gi == 0 ? 2 : 3) * D;
     const std::string pre = "gnn_layers." + std::to_string(gi);
+    if (!live(pre + ".compress.0.weight") && !live(pre + ".compress.0.bias") && !live(pre + ".edge_embedder.weight") &&
+        !live(pre + ".edge_embedder.bias") && !live(gi == 0 ? "edge_embedder.weight" : pre + ".neighbor_embedder.weight"))
+        return;  // compress.0 and everything folded into it are frozen
     const int nsplit = 2048;
     // dWc [D,4]
     k_geo_wgrad_partial<<<nsplit, 128, 0, st>>>(da0, g.geo, E, w.partial);

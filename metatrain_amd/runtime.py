@@ -3,7 +3,7 @@ does the work. Nothing here computes on the CPU and nothing falls back to torch 
 """
 import ctypes
 from ctypes import byref, c_double, c_float, c_int, c_int32, c_int64, c_void_p
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, Iterable, List, Optional, Tuple, Union
 
 import torch
 
@@ -93,12 +93,29 @@ class HipModel:
     def handle(self) -> c_void_p:
         return self._handle
 
-    def load(self, params: Dict[str, torch.Tensor], target: Optional[str], block: Optional[str] = None) -> None:
+    def load(self, params: Dict[str, torch.Tensor], target: Optional[str], block: Optional[str] = None,
+             lora_scaling: Union[None, float, Dict[str, float]] = None) -> None:
         """Upload a reference-schema state dict and pack it. ``target`` / ``block`` name the FUSED head
         (what ``pet_forward`` and the native training step evaluate; its last layers must have one property): its keys
         are uploaded with both names replaced by "@". Every other head / last layer of the state dict (other targets,
         blocks with several properties, further readout layers) is uploaded under its own name and served by
-        :meth:`HipForward.predict`. ``target=None``: no fused head (features + ``predict`` only)."""
+        :meth:`HipForward.predict`. ``target=None``: no fused head (features + ``predict`` only).
+
+        A LoRA-injected state dict (``<lin>.linear.weight``, ``<lin>.lora_A.weight``, ... -- pet/modules/finetuning.py)
+        needs ``lora_scaling``: the ``alpha / rank`` of every adapter, which the state dict does not hold -- one number for
+        all, or ``{"<lin>": scaling}``."""
+        adapted = [k[: -len(".lora_A.weight")] for k in params if k.endswith(".lora_A.weight")]
+        if adapted and self.hypers["activation"] == "SiLU" and any(lin.endswith(".w_in") for lin in adapted):
+            raise PetHipError("a LoRA adapter on w_in of an activation = 'SiLU' model is not served (the kernels hold "
+                              "that projection as two tied copies): " + next(lin for lin in adapted if lin.endswith(".w_in")))
+        scalings: Dict[str, float] = {}
+        for lin in adapted:
+            s = lora_scaling.get(lin) if isinstance(lora_scaling, dict) else lora_scaling
+            if s is None:
+                raise PetHipError(f"LoRA adapter '{lin}': no scaling given (HipModel.load(..., lora_scaling=alpha / rank); "
+                                  "the state dict does not hold it)")
+            scalings[lin] = float(s)
+        self.lora_scaling = scalings
         block = block or target
         self.target = target
         self._fused_block = block
@@ -136,9 +153,25 @@ class HipModel:
                 self._ckeys[key] = (ckey, tuple(src.shape))
             check(self.lib.pet_model_set_param(self._handle, ckey.encode(), _ptr(src), src.numel(), _stream()))
             torch.cuda.current_stream().synchronize()  # src may be a temporary
+        for lin, s in scalings.items():
+            check(self.lib.pet_model_set_lora_scaling(self._handle, lin.encode(), s))
         check(self.lib.pet_model_finalize(self._handle, _stream()))
         for key in self._tied:  # the fused Adam step keeps the two copies of a tied projection equal
             check(self.lib.pet_model_tie_halves(self._handle, self._ckeys[key][0].encode()))
+
+    def set_trainable(self, trainable: Union[Dict[str, bool], Iterable[str]]) -> None:
+        """Freeze parameters (``pet_model_set_trainable``): ``{key: requires_grad}`` for the keys named, or a collection of
+        the keys that stay trainable (every other key is frozen). A frozen parameter gets no gradient and no update."""
+        if not isinstance(trainable, dict):
+            keep = set(trainable)
+            unknown = keep - set(self._ckeys)
+            if unknown:
+                raise PetHipError(f"unknown parameter(s): {sorted(unknown)[:4]}")
+            trainable = {k: k in keep for k in self._ckeys}
+        for key, on in trainable.items():
+            if key not in self._ckeys:
+                raise PetHipError(f"unknown parameter '{key}'")
+            check(self.lib.pet_model_set_trainable(self._handle, self._ckeys[key][0].encode(), int(bool(on))))
 
     def load_species_table(self) -> None:
         """Upload only ``species_to_species_index`` (enough for graph building: the SOAP path shares the

@@ -405,6 +405,42 @@ int pet_backward_train2_cell(const pet_model_t* m, const pet_graph_t* g, void* d
 /* Per-system sum (utils/sum_over_atoms.py:10-48): d_out[S] = sum_{atoms of s} d_atomic. */
 int pet_sum_over_atoms(const pet_graph_t* g, const float* d_atomic, float* d_out, void* stream);
 
+/* ---- LLPR: last-layer prediction rigidity (llpr/model.py) ------------------------------------------------------
+ * Uncertainties and last-layer ensembles from the last-layer features (LLF) of one target. F = 2 L d_head with
+ * L = pet_model_num_readout_layers (pet/model.py:118-120); every entry point below checks F against the model.
+ * All products are fp32 MFMA, every sum has a fixed order: results are the same bits run to run. Arguments are checked
+ * on the host before any launch: NULL buffers, a wrong F, R <= 0 or K P above PET_LLPR_MAX_ENSEMBLE give PET_ERR_ARGUMENT.
+ *
+ * pet_llpr_features: per-atom LLF [N, F] of (target, block) -- the names the heads were uploaded with, "@" for the
+ *   fused target -- from the features of every readout layer (pet_forward / pet_forward_layers outputs, two HOST arrays
+ *   of n_layers device pointers). Columns node0 | edge0 | node1 | edge1 | ... (the concatenation of
+ *   last_layer_parameter_names, pet/model.py:788-875, 1064-1072); each edge part is the cutoff-weighted sum over the
+ *   atom's edges. d_atomic [N, P] optional out: the target's prediction, summed over readout layers (backend.py:468-476).
+ * pet_llpr_rows: d_rows [S, F] = per-system sums of d_llf [N, F] over the atoms whose d_mask [N] byte is non-zero (NULL =
+ *   all; selected_atoms), divided by the system's atom count when mean != 0 (covariance rows, llpr/model.py:898-908).
+ *   d_system_indices [N] int32: non-decreasing runs inside [0, S), as pet_graph_build requires.
+ * pet_llpr_covariance_accumulate: d_cov [F, F] fp64 += X^T X for X = d_x [R, F] (llpr/model.py:912). Only the upper
+ *   triangle (by 64-column tiles) is accumulated: call pet_llpr_covariance_finalize once after the last batch to mirror it.
+ * pet_llpr_variance: d_sigma [R] = alpha sqrt(|M x_r|^2) with d_inv_cholesky M = L^-1 [F, F] lower triangular, zeros
+ *   above the diagonal (llpr/model.py:427-436: solve_triangular(L, x) then the sum of squares; alpha: the multiplier).
+ * pet_llpr_ensemble: d_out [R, K P] = X W^T with d_weights W [K P, F] (llpr_ensemble_layers.<target>.weight, member-major
+ *   index k P + p, llpr/model.py:1125-1138), then, when d_prediction [R, P] is given, re-centred on it:
+ *   out - mean_k out + prediction (llpr/model.py:578-587). */
+#define PET_LLPR_MAX_ENSEMBLE 16384
+int64_t pet_llpr_feature_size(const pet_model_t* m);
+int pet_llpr_features(const pet_model_t* m, const pet_graph_t* g, const char* target, const char* block,
+                      const float* const* h_node_features, const float* const* h_edge_features, int32_t n_layers,
+                      float* d_atomic, float* d_llf, void* stream);
+int pet_llpr_rows(const pet_model_t* m, int64_t F, const float* d_llf, int64_t n_atoms, const int32_t* d_system_indices,
+                  int64_t n_systems, const uint8_t* d_mask, int mean, float* d_rows, void* stream);
+int pet_llpr_covariance_accumulate(const pet_model_t* m, int64_t F, const float* d_x, int64_t R, double* d_cov,
+                                   void* stream);
+int pet_llpr_covariance_finalize(const pet_model_t* m, int64_t F, double* d_cov, void* stream);
+int pet_llpr_variance(const pet_model_t* m, int64_t F, const float* d_x, int64_t R, const float* d_inv_cholesky,
+                      float alpha, float* d_sigma, void* stream);
+int pet_llpr_ensemble(const pet_model_t* m, int64_t F, const float* d_x, int64_t R, const float* d_weights, int32_t K,
+                      int32_t P, const float* d_prediction, float* d_out, void* stream);
+
 /* ---- profiling hooks used by bench.py ------------------------------------------ */
 /* When enabled, every kernel launch of pet_forward/pet_backward is bracketed with HIP
  * events on the launch stream; pet_profile_report fills name / total ms / calls / algorithmic

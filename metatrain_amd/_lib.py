@@ -19,6 +19,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libpet_hip.so")
 PET_OK = 0
 PET_CUTOFF_COSINE = 0
 PET_CUTOFF_BUMP = 1
+PET_ERR_ARGUMENT = -3
+PET_LLPR_MAX_ENSEMBLE = 16384
 
 # every symbol include/pet_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -39,6 +41,8 @@ SYMBOLS = [
     "pet_model_set_lora_scaling", "pet_model_set_trainable",
     "pet_train2_workspace_bytes", "pet_backward_train2", "pet_backward_train2_cell",
     "pet_sum_over_atoms",
+    "pet_llpr_feature_size", "pet_llpr_features", "pet_llpr_rows", "pet_llpr_covariance_accumulate",
+    "pet_llpr_covariance_finalize", "pet_llpr_variance", "pet_llpr_ensemble",
     "pet_profile_enable", "pet_profile_select", "pet_profile_reset", "pet_profile_report", "pet_config_set",
 ]
 
@@ -198,6 +202,14 @@ def load() -> ctypes.CDLL:
         fn.restype = c_int64
     lib.pet_backward_train.argtypes = [P, P, P, c_int64, P, P, P, P]
     lib.pet_sum_over_atoms.argtypes = [P, P, P, P]
+    lib.pet_llpr_feature_size.argtypes = [P]
+    lib.pet_llpr_feature_size.restype = c_int64
+    lib.pet_llpr_features.argtypes = [P, P, c_char_p, c_char_p, P, P, c_int32, P, P, P]
+    lib.pet_llpr_rows.argtypes = [P, c_int64, P, c_int64, P, c_int64, P, c_int, P, P]
+    lib.pet_llpr_covariance_accumulate.argtypes = [P, c_int64, P, c_int64, P, P]
+    lib.pet_llpr_covariance_finalize.argtypes = [P, c_int64, P, P]
+    lib.pet_llpr_variance.argtypes = [P, c_int64, P, c_int64, P, c_float, P, P]
+    lib.pet_llpr_ensemble.argtypes = [P, c_int64, P, c_int64, P, c_int32, c_int32, P, P, P]
     lib.pet_profile_enable.argtypes = [c_int]
     lib.pet_profile_select.argtypes = [c_char_p]
     lib.pet_profile_report.argtypes = [c_int, P, POINTER(c_double), POINTER(c_int64), POINTER(c_double),

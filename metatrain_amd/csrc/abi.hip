@@ -1021,6 +1021,73 @@ int pet_sum_over_atoms(const pet_graph_t* pg, const float* d_atomic, float* d_ou
     return sum_over_atoms(pg->g, d_atomic, d_out, (hipStream_t)stream);
 }
 
+// ---- LLPR (llpr/model.py) -----------------------------------------------------------------------------------------
+int64_t pet_llpr_feature_size(const pet_model_t* pm) {
+    if (!pm) return -1;
+    return 2 * (int64_t)pm->m.num_readout_layers() * pm->m.h.d_head;  // pet/model.py:118-120
+}
+
+static int llpr_check_f(const pet_model_t* pm, int64_t F) {
+    PET_REQUIRE(pm, PET_ERR_ARGUMENT, "null model");
+    PET_REQUIRE(F == pet_llpr_feature_size(pm), PET_ERR_ARGUMENT,
+                "F = " + std::to_string(F) + " is not this model's last-layer feature size " +
+                    std::to_string(pet_llpr_feature_size(pm)) + " (2 num_readout_layers d_head)");
+    return PET_OK;
+}
+
+int pet_llpr_features(const pet_model_t* pm, const pet_graph_t* pg, const char* target, const char* block,
+                      const float* const* h_node_features, const float* const* h_edge_features, int32_t n_layers,
+                      float* d_atomic, float* d_llf, void* stream) {
+    PET_REQUIRE(pm && pg && target && block && h_node_features && h_edge_features, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
+    PET_REQUIRE(n_layers == pm->m.num_readout_layers(), PET_ERR_ARGUMENT,
+                "expected one feature pair per readout layer (" + std::to_string(pm->m.num_readout_layers()) + ")");
+    if (pg->g.n_nodes == 0) return PET_OK;
+    PET_REQUIRE(d_llf, PET_ERR_ARGUMENT, "null last-layer feature buffer");
+    return llpr_features(pm->m, pg->g, target, block, h_node_features, h_edge_features, n_layers, d_atomic, d_llf,
+                         (hipStream_t)stream);
+}
+
+int pet_llpr_rows(const pet_model_t* pm, int64_t F, const float* d_llf, int64_t n_atoms, const int32_t* d_system_indices,
+                  int64_t n_systems, const uint8_t* d_mask, int mean, float* d_rows, void* stream) {
+    if (int rc = llpr_check_f(pm, F)) return rc;
+    PET_REQUIRE(n_atoms >= 0 && n_systems > 0, PET_ERR_ARGUMENT, "n_atoms < 0 or n_systems <= 0");
+    PET_REQUIRE(d_rows && (n_atoms == 0 || (d_llf && d_system_indices)), PET_ERR_ARGUMENT, "null argument");
+    return llpr_rows(d_llf, n_atoms, (int)F, d_system_indices, n_systems, d_mask, mean, d_rows, (hipStream_t)stream);
+}
+
+int pet_llpr_covariance_accumulate(const pet_model_t* pm, int64_t F, const float* d_x, int64_t R, double* d_cov,
+                                   void* stream) {
+    if (int rc = llpr_check_f(pm, F)) return rc;
+    PET_REQUIRE(R > 0, PET_ERR_ARGUMENT, "R <= 0 rows");
+    PET_REQUIRE(d_x && d_cov, PET_ERR_ARGUMENT, "null argument");
+    return llpr_covariance_accumulate(d_x, R, (int)F, d_cov, (hipStream_t)stream);
+}
+
+int pet_llpr_covariance_finalize(const pet_model_t* pm, int64_t F, double* d_cov, void* stream) {
+    if (int rc = llpr_check_f(pm, F)) return rc;
+    PET_REQUIRE(d_cov, PET_ERR_ARGUMENT, "null argument");
+    return llpr_covariance_finalize(d_cov, (int)F, (hipStream_t)stream);
+}
+
+int pet_llpr_variance(const pet_model_t* pm, int64_t F, const float* d_x, int64_t R, const float* d_inv_cholesky,
+                      float alpha, float* d_sigma, void* stream) {
+    if (int rc = llpr_check_f(pm, F)) return rc;
+    PET_REQUIRE(R > 0, PET_ERR_ARGUMENT, "R <= 0 rows");
+    PET_REQUIRE(d_x && d_inv_cholesky && d_sigma, PET_ERR_ARGUMENT, "null argument");
+    return llpr_variance(d_x, R, (int)F, d_inv_cholesky, alpha, d_sigma, (hipStream_t)stream);
+}
+
+int pet_llpr_ensemble(const pet_model_t* pm, int64_t F, const float* d_x, int64_t R, const float* d_weights, int32_t K,
+                      int32_t P, const float* d_prediction, float* d_out, void* stream) {
+    if (int rc = llpr_check_f(pm, F)) return rc;
+    PET_REQUIRE(R > 0, PET_ERR_ARGUMENT, "R <= 0 rows");
+    PET_REQUIRE(K > 0 && P > 0 && (int64_t)K * P <= PET_LLPR_MAX_ENSEMBLE, PET_ERR_ARGUMENT,
+                "K P = " + std::to_string((int64_t)K * P) + " outside [1, " + std::to_string(PET_LLPR_MAX_ENSEMBLE) + "]");
+    PET_REQUIRE(d_x && d_weights && d_out, PET_ERR_ARGUMENT, "null argument");
+    return llpr_ensemble(d_x, R, (int)F, d_weights, K, P, d_prediction, d_out, (hipStream_t)stream);
+}
+
 int pet_profile_enable(int on) {
     g_prof_on = on != 0;
     return PET_OK;

@@ -268,6 +268,15 @@ int aux_outputs(const Model& m, const Graph& g, const float* node_feat, const fl
                 float* last_layer, float* scratch, hipStream_t st);
 int backward_train(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* grad_atomic,
                    float* grad_pos, float* grad_cells, hipStream_t st);
+// llpr.hip: last-layer features of every readout layer and the four LLPR kernels (pet_hip.h, pet_llpr_*)
+int llpr_features(const Model& m, const Graph& g, const char* target, const char* block, const float* const* node_feats,
+                  const float* const* edge_feats, int n_layers, float* atomic, float* llf, hipStream_t st);
+int llpr_rows(const float* llf, int64_t N, int F, const int* sysidx, int64_t S, const uint8_t* mask, int mean, float* rows,
+              hipStream_t st);
+int llpr_covariance_accumulate(const float* X, int64_t R, int F, double* C, hipStream_t st);
+int llpr_covariance_finalize(double* C, int F, hipStream_t st);
+int llpr_variance(const float* X, int64_t R, int F, const float* M, float alpha, float* sigma, hipStream_t st);
+int llpr_ensemble(const float* X, int64_t R, int F, const float* W, int K, int P, const float* pred, float* Y, hipStream_t st);
 // so.hip: second-order (force-loss) reverse pass
 int64_t so_workspace_bytes(const Model& m, int64_t n_nodes, int64_t n_edges);
 // tangents of (edge vector, distance), cutoff factor and key bias along (u, ucell), adaptive cutoffs ('solver') included

@@ -97,13 +97,22 @@ struct PetHipModule : torch::CustomClassHolder {
     at::Tensor atomic_energies(const at::Tensor& positions, const at::Tensor& cells, const at::Tensor& centers,
                                const at::Tensor& neighbors, const at::Tensor& cell_shifts, const at::Tensor& species,
                                const at::Tensor& system_indices);
+    std::tuple<at::Tensor, at::Tensor> atomic_energies_and_llf(const at::Tensor& positions, const at::Tensor& cells,
+                                                               const at::Tensor& centers, const at::Tensor& neighbors,
+                                                               const at::Tensor& cell_shifts, const at::Tensor& species,
+                                                               const at::Tensor& system_indices);
+    at::Tensor llpr_rows(const at::Tensor& llf, const at::Tensor& system_indices, int64_t n_systems, const at::Tensor& mask);
+    at::Tensor llpr_variance(const at::Tensor& x, const at::Tensor& inv_cholesky, double alpha);
+    at::Tensor llpr_ensemble(const at::Tensor& x, const at::Tensor& weights, int64_t K, const at::Tensor& prediction);
 };
 
 struct EnergyFn : torch::autograd::Function<EnergyFn> {
     static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& positions,
                               const at::Tensor& cells, c10::intrusive_ptr<PetHipModule> mod, const at::Tensor& centers,
                               const at::Tensor& neighbors, const at::Tensor& cell_shifts, const at::Tensor& species,
-                              const at::Tensor& system_indices) {
+                              const at::Tensor& system_indices, at::Tensor llf) {
+        // llf: empty, or [N, F] filled here with the last-layer features of the fused target from the SAME backbone
+        // forward (pet_forward's feature copies -> pet_llpr_features); it is not differentiated
         mod->ensure_model(positions);
         auto gh = c10::make_intrusive<GraphHolder>();
         void* st = stream_of(positions);
@@ -124,9 +133,24 @@ struct EnergyFn : torch::autograd::Function<EnergyFn> {
               "pet_graph_build");
         gh->fwd_ws = at::empty({pet_forward_workspace_bytes_for(mod->model, gh->g)}, bytes);
         at::Tensor atomic = at::empty({gh->n_nodes}, positions.options().dtype(at::kFloat));
+        at::Tensor nf, ef;
+        if (llf.defined() && llf.numel() > 0) {
+            TORCH_CHECK(llf.is_contiguous() && llf.scalar_type() == at::kFloat && llf.size(0) == gh->n_nodes &&
+                            llf.size(1) == pet_llpr_feature_size(mod->model),
+                        "pet_hip: last-layer feature buffer of the wrong shape");
+            const int64_t e = pet_graph_num_edges(gh->g);
+            nf = at::empty({gh->n_nodes, (int64_t)mod->hypers[5]}, atomic.options());
+            ef = at::empty({std::max<int64_t>(e, 1), (int64_t)mod->hypers[3]}, atomic.options());
+        }
         check(pet_forward(mod->model, gh->g, gh->fwd_ws.data_ptr(), gh->fwd_ws.numel(), 1, atomic.data_ptr<float>(),
-                          nullptr, nullptr, st),
+                          nf.defined() ? nf.data_ptr<float>() : nullptr, ef.defined() ? ef.data_ptr<float>() : nullptr, st),
               "pet_forward");
+        if (nf.defined()) {
+            const float* pn[1] = {nf.data_ptr<float>()};
+            const float* pe[1] = {ef.data_ptr<float>()};
+            check(pet_llpr_features(mod->model, gh->g, "@", "@", pn, pe, 1, nullptr, llf.data_ptr<float>(), st),
+                  "pet_llpr_features");
+        }
         ctx->saved_data["graph"] = gh;
         ctx->saved_data["module"] = mod;
         ctx->saved_data["pos_dtype"] = (int64_t)positions.scalar_type();
@@ -150,7 +174,7 @@ struct EnergyFn : torch::autograd::Function<EnergyFn> {
         const auto pd = (at::ScalarType)ctx->saved_data["pos_dtype"].toInt();
         const auto cd = (at::ScalarType)ctx->saved_data["cell_dtype"].toInt();
         return {gpos.to(pd), gcell.to(cd), at::Tensor(), at::Tensor(), at::Tensor(),
-                at::Tensor(), at::Tensor(), at::Tensor()};
+                at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
     }
 };
 
@@ -159,7 +183,69 @@ at::Tensor PetHipModule::atomic_energies(const at::Tensor& positions, const at::
                                          const at::Tensor& cell_shifts, const at::Tensor& species,
                                          const at::Tensor& system_indices) {
     return EnergyFn::apply(positions, cells, c10::intrusive_ptr<PetHipModule>::reclaim_copy(this), centers, neighbors,
-                           cell_shifts, species, system_indices);
+                           cell_shifts, species, system_indices, at::empty({0}, positions.options().dtype(at::kFloat)));
+}
+
+// ---- LLPR (llpr/model.py): the fused target's per-atom predictions and last-layer features from one backbone forward,
+// and the three LLPR kernels (pet_hip.h, pet_llpr_*) for an exported model
+std::tuple<at::Tensor, at::Tensor> PetHipModule::atomic_energies_and_llf(
+    const at::Tensor& positions, const at::Tensor& cells, const at::Tensor& centers, const at::Tensor& neighbors,
+    const at::Tensor& cell_shifts, const at::Tensor& species, const at::Tensor& system_indices) {
+    ensure_model(positions);
+    TORCH_CHECK(pet_model_num_readout_layers(model) == 1,
+                "pet_hip: the fused head reads one readout layer (feed-forward featuriser only)");
+    at::Tensor llf = at::empty({positions.size(0), pet_llpr_feature_size(model)},
+                               positions.options().dtype(at::kFloat));
+    at::Tensor atomic = EnergyFn::apply(positions, cells, c10::intrusive_ptr<PetHipModule>::reclaim_copy(this), centers,
+                                        neighbors, cell_shifts, species, system_indices, llf);
+    return {atomic, llf};
+}
+
+at::Tensor PetHipModule::llpr_rows(const at::Tensor& llf, const at::Tensor& system_indices, int64_t n_systems,
+                                   const at::Tensor& mask) {
+    ensure_model(llf);
+    const int64_t F = pet_llpr_feature_size(model);
+    TORCH_CHECK(llf.is_cuda() && system_indices.device() == llf.device() && (mask.numel() == 0 || mask.device() == llf.device()),
+                "pet_hip: llpr_rows needs every tensor on the device of the last-layer features");
+    at::Tensor x = as_f32(llf), sys = as_i32(system_indices);
+    at::Tensor m = mask.numel() > 0 ? mask.to(at::kByte).contiguous() : at::Tensor();
+    at::Tensor rows = at::empty({n_systems, F}, x.options());
+    check(pet_llpr_rows(model, F, x.data_ptr<float>(), x.size(0), sys.data_ptr<int32_t>(), n_systems,
+                        m.defined() ? m.data_ptr<uint8_t>() : nullptr, 0, rows.data_ptr<float>(), stream_of(x)),
+          "pet_llpr_rows");
+    return rows;
+}
+
+at::Tensor PetHipModule::llpr_variance(const at::Tensor& x_, const at::Tensor& inv_cholesky, double alpha) {
+    ensure_model(x_);
+    TORCH_CHECK(x_.is_cuda() && inv_cholesky.device() == x_.device(),
+                "pet_hip: llpr_variance needs the inverse Cholesky factor on the device of the rows");
+    at::Tensor x = as_f32(x_), M = as_f32(inv_cholesky);
+    TORCH_CHECK(M.dim() == 2 && M.size(0) == x.size(1) && M.size(1) == x.size(1), "pet_hip: inverse Cholesky factor is not [F, F]");
+    at::Tensor sigma = at::empty({x.size(0)}, x.options());
+    if (x.size(0) == 0) return sigma;
+    check(pet_llpr_variance(model, x.size(1), x.data_ptr<float>(), x.size(0), M.data_ptr<float>(), (float)alpha,
+                            sigma.data_ptr<float>(), stream_of(x)),
+          "pet_llpr_variance");
+    return sigma;
+}
+
+at::Tensor PetHipModule::llpr_ensemble(const at::Tensor& x_, const at::Tensor& weights, int64_t K,
+                                       const at::Tensor& prediction) {
+    ensure_model(x_);
+    TORCH_CHECK(x_.is_cuda() && weights.device() == x_.device() && prediction.device() == x_.device(),
+                "pet_hip: llpr_ensemble needs the weights and the prediction on the device of the rows");
+    at::Tensor x = as_f32(x_), W = as_f32(weights), p = as_f32(prediction);
+    TORCH_CHECK(K > 0 && W.dim() == 2 && W.size(1) == x.size(1) && W.size(0) % K == 0,
+                "pet_hip: ensemble weights are not [K P, F]");
+    const int64_t P = W.size(0) / K;
+    TORCH_CHECK(p.numel() == x.size(0) * P, "pet_hip: the prediction is not [R, P]");
+    at::Tensor out = at::empty({x.size(0), K * P}, x.options());
+    if (x.size(0) == 0) return out;
+    check(pet_llpr_ensemble(model, x.size(1), x.data_ptr<float>(), x.size(0), W.data_ptr<float>(), (int32_t)K,
+                            (int32_t)P, p.data_ptr<float>(), out.data_ptr<float>(), stream_of(x)),
+          "pet_llpr_ensemble");
+    return out;
 }
 
 
@@ -618,6 +704,10 @@ TORCH_LIBRARY(pet_hip, m) {
     m.class_<PetHipModule>("PetHipModule")
         .def(torch::init<std::vector<double>, std::vector<int64_t>, std::vector<std::string>, std::vector<at::Tensor>>())
         .def("atomic_energies", &PetHipModule::atomic_energies)
+        .def("atomic_energies_and_llf", &PetHipModule::atomic_energies_and_llf)
+        .def("llpr_rows", &PetHipModule::llpr_rows)
+        .def("llpr_variance", &PetHipModule::llpr_variance)
+        .def("llpr_ensemble", &PetHipModule::llpr_ensemble)
         .def("num_tensors", [](const c10::intrusive_ptr<PetHipModule>& self) { return (int64_t)self->tensors.size(); })
         .def_pickle(
             [](const c10::intrusive_ptr<PetHipModule>& self) -> State {

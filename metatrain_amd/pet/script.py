@@ -152,3 +152,99 @@ class ExportedEnergyModel(torch.nn.Module):
             energies = energies + torch.zeros_like(energies).index_add(
                 0, sysl, torch.where(keep, base, torch.zeros_like(base)))
         return energies, -g_pos, stress, per_atom[keep]
+
+
+class ExportedLLPRModel(torch.nn.Module):
+    """:class:`ExportedEnergyModel` plus the LLPR outputs of the energy (``llpr/model.py:362-670``), scriptable end to end:
+    the per-atom energies and the last-layer features come from ONE backbone forward (``atomic_energies_and_llf``), the
+    per-system rows, sigma and the ensemble from the HIP kernels behind ``pet_llpr_*``.
+
+    ``llpr_state``: ``LLPRUncertainty.state_dict()`` of the same model (``covariance_energy_uncertainty``,
+    ``cholesky_energy_uncertainty``, ``multiplier_energy_uncertainty`` and, for an ensemble,
+    ``llpr_ensemble_layers.energy.weight``); pickled with the module as buffers (the dots of the last name replaced by
+    underscores), with the fp32 inverse Cholesky factor the variance kernel reads.
+
+    ``forward`` returns ``(energies [S], forces [N, 3], stress [S, 3, 3] or empty, per_atom [n_selected],
+    energy_uncertainty [S], energy_uncertainty per selected atom [n_selected] or empty, energy_ensemble [S, K] or empty)``.
+    Ensemble members carry no forces (one adjoint per member: not served)."""
+
+    def __init__(self, core, llpr_state: Dict[str, torch.Tensor], scale: float = 1.0,
+                 composition: Optional[torch.Tensor] = None):
+        super().__init__()
+        self.pet = PETScriptModule(core)
+        self.scale = float(scale)
+        self.register_buffer("composition", composition.detach().clone().to(torch.float32)
+                             if composition is not None else torch.zeros(0, dtype=torch.float32))
+        chol = llpr_state["cholesky_energy_uncertainty"].detach().to(torch.float64).cpu()
+        mult = llpr_state["multiplier_energy_uncertainty"].detach().to(torch.float64).cpu().reshape(-1)
+        if mult.numel() != 1:
+            raise PetHipError("the energy has one property: multiplier_energy_uncertainty must hold one number")
+        if not bool(chol.diagonal().ne(0).all()):
+            raise PetHipError("no Cholesky factor in the LLPR state (compute_cholesky_decomposition)")
+        inv = torch.tril(torch.linalg.solve_triangular(chol, torch.eye(chol.shape[0], dtype=torch.float64), upper=False))
+        self.register_buffer("covariance_energy_uncertainty",
+                             llpr_state["covariance_energy_uncertainty"].detach().clone().to(torch.float64))
+        self.register_buffer("cholesky_energy_uncertainty", chol.clone())
+        self.register_buffer("multiplier_energy_uncertainty", mult.clone())
+        self.register_buffer("inverse_cholesky", inv.to(torch.float32))
+        w = llpr_state.get("llpr_ensemble_layers.energy.weight")
+        self.register_buffer("llpr_ensemble_layers_energy_weight",
+                             w.detach().clone().to(torch.float32) if w is not None else torch.zeros((0, chol.shape[0])))
+        self.alpha = float(mult[0])
+        self.num_ensemble_members = int(self.llpr_ensemble_layers_energy_weight.shape[0])
+
+    def forward(self, positions: torch.Tensor, cells: torch.Tensor, centers: torch.Tensor, neighbors: torch.Tensor,
+                cell_shifts: torch.Tensor, species: torch.Tensor, system_indices: torch.Tensor,
+                selected_atoms: Optional[torch.Tensor] = None, with_stress: bool = False,
+                per_atom_uncertainty: bool = False, with_ensemble: bool = True):
+        # energies, forces, stress, per-atom energies: the operations of ExportedEnergyModel.forward, in the same order
+        positions = positions.detach().requires_grad_(True)
+        cells = cells.detach().requires_grad_(with_stress)
+        atomic2, llf = self.pet.core.atomic_energies_and_llf(positions, cells, centers, neighbors, cell_shifts, species,
+                                                             system_indices)
+        atomic = atomic2[:, 0]
+        atomic = atomic * self.scale
+        keep = torch.ones(positions.shape[0], dtype=torch.bool, device=positions.device)
+        if selected_atoms is not None:
+            if selected_atoms.dtype == torch.bool:
+                keep = selected_atoms.to(positions.device)
+            else:
+                keep = torch.zeros_like(keep).index_fill(0, selected_atoms.to(positions.device, torch.long), True)
+        masked = torch.where(keep, atomic, torch.zeros_like(atomic))
+        sysl = system_indices.to(torch.long)
+        energies = torch.zeros(cells.shape[0], dtype=atomic.dtype, device=atomic.device).index_add(0, sysl, masked)
+        wrt = [positions, cells] if with_stress else [positions]
+        grads = torch.autograd.grad([energies.sum()], wrt)
+        g_pos = grads[0]
+        assert g_pos is not None
+        stress = torch.zeros((0, 3, 3), dtype=atomic.dtype, device=atomic.device)
+        if with_stress:
+            g_cell = grads[1]
+            assert g_cell is not None
+            outer = positions.detach().unsqueeze(2) * g_pos.unsqueeze(1)
+            virial = torch.zeros((cells.shape[0], 3, 3), dtype=atomic.dtype, device=atomic.device).index_add(
+                0, sysl, outer)
+            virial = virial + torch.matmul(cells.detach().transpose(1, 2), g_cell)
+            volume = torch.abs(torch.linalg.det(cells.detach()))
+            stress = virial / volume.clamp_min(1e-30).reshape(-1, 1, 1)
+        per_atom = atomic.detach()
+        energies = energies.detach()
+        if self.composition.numel() > 0:
+            base = self.composition[species.to(torch.long)].to(atomic.dtype)
+            per_atom = per_atom + base
+            energies = energies + torch.zeros_like(energies).index_add(
+                0, sysl, torch.where(keep, base, torch.zeros_like(base)))
+        # LLPR: per-system rows of the selected atoms -> sigma and the ensemble re-centred on the energies
+        mask = keep.to(torch.uint8) if selected_atoms is not None else torch.zeros(0, dtype=torch.uint8)
+        # (the buffers follow the inputs' device: a no-op once the module was moved there)
+        inv = self.inverse_cholesky.to(llf.device)
+        rows = self.pet.core.llpr_rows(llf, system_indices.to(llf.device), cells.shape[0], mask.to(llf.device))
+        sigma = self.pet.core.llpr_variance(rows, inv, self.alpha)
+        sigma_atom = torch.zeros(0, dtype=sigma.dtype, device=sigma.device)
+        if per_atom_uncertainty:
+            sigma_atom = self.pet.core.llpr_variance(llf[keep], inv, self.alpha)
+        ensemble = torch.zeros((0, 0), dtype=sigma.dtype, device=sigma.device)
+        if with_ensemble and self.num_ensemble_members > 0:
+            ensemble = self.pet.core.llpr_ensemble(rows, self.llpr_ensemble_layers_energy_weight.to(llf.device),
+                                                   self.num_ensemble_members, energies.unsqueeze(1))
+        return energies, -g_pos, stress, per_atom[keep], sigma, sigma_atom, ensemble

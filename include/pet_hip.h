@@ -402,6 +402,37 @@ int pet_backward_train2_cell(const pet_model_t* m, const pet_graph_t* g, void* d
                              int64_t workspace_bytes, void* d_workspace2, int64_t workspace2_bytes,
                              const float* d_lambda_atomic, const float* d_nu_atomic, const float* d_u,
                              const float* d_u_cell, float* d_tangent_atomic, void* stream);
+/* ---- further targets of a training step (non-conservative forces / stress, several blocks or properties) --------------
+ * A step trains every target from ONE pet_forward(save_for_backward = 2) and ONE backbone reverse sweep:
+ *   1. pet_train_predict: the prediction of one (target, readout layer, block) from the features that forward left in
+ *      the training workspace (no second backbone forward): d_atomic [N, P] out. target / block as in pet_predict.
+ *   2. pet_train_predict_backward: for the seeds d_grad_atomic[b] = dL/d(prediction of blocks[b]) [N, P_b] of some blocks
+ *      of one target, ADDS dL/dtheta of the target's heads (recomputed once for all its blocks) and of those blocks' last
+ *      layers to the gradient slots, and ADDS the adjoints of the heads' inputs to d_seed_node_features [N, d_node] and
+ *      d_seed_edge_features [E, d_pet] (CSR rows; either may be NULL). Frozen parameters are skipped.
+ *   3. pet_backward_train_seeded / pet_backward_train2_seeded: pet_backward_train / pet_backward_train2_cell with the
+ *      summed seeds of step 2 (h_seed_*_features: host arrays of n_layers device pointers, one per readout layer, NULL
+ *      entries = 0; n_layers = 0: none) added where the fused head's adjoint enters the backbone (the second-order pass:
+ *      its first-order adjoint only; these targets do not enter dE/dR). pet_backward_train_seeded takes
+ *      d_grad_atomic = NULL when the loss has no fused target (a model loaded without one trains this way). The seeds
+ *      carry no cutoff-factor adjoint, so pet_backward_train_seeded refuses d_grad_positions / d_grad_cells with seeds.
+ * Default model size, PreLN + feedforward featuriser, graphs with edges and at most 127 neighbours per atom; elsewhere
+ * PET_ERR_UNSUPPORTED. pet_backward_train / pet_backward_train2_cell are the seeded calls with no seed. */
+int pet_train_predict(const pet_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,
+                      const char* target, int32_t readout_layer, const char* block, float* d_atomic, void* stream);
+int pet_train_predict_backward(const pet_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,
+                               const char* target, int32_t readout_layer, int32_t n_blocks, const char* const* blocks,
+                               const float* const* d_grad_atomic, float* d_seed_node_features,
+                               float* d_seed_edge_features, void* stream);
+int pet_backward_train_seeded(const pet_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,
+                              const float* d_grad_atomic, float* d_grad_positions, float* d_grad_cells,
+                              const float* const* h_seed_node_features, const float* const* h_seed_edge_features,
+                              int32_t n_layers, void* stream);
+int pet_backward_train2_seeded(const pet_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,
+                               void* d_workspace2, int64_t workspace2_bytes, const float* d_lambda_atomic,
+                               const float* d_nu_atomic, const float* d_u, const float* d_u_cell, float* d_tangent_atomic,
+                               const float* const* h_seed_node_features, const float* const* h_seed_edge_features,
+                               int32_t n_layers, void* stream);
 /* Per-system sum (utils/sum_over_atoms.py:10-48): d_out[S] = sum_{atoms of s} d_atomic. */
 int pet_sum_over_atoms(const pet_graph_t* g, const float* d_atomic, float* d_out, void* stream);
 

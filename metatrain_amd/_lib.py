@@ -40,6 +40,7 @@ SYMBOLS = [
     "pet_model_get_param", "pet_model_flat_grad", "pet_adam_step", "pet_optimizer_state", "pet_model_tie_halves",
     "pet_model_set_lora_scaling", "pet_model_set_trainable",
     "pet_train2_workspace_bytes", "pet_backward_train2", "pet_backward_train2_cell",
+    "pet_train_predict", "pet_train_predict_backward", "pet_backward_train_seeded", "pet_backward_train2_seeded",
     "pet_sum_over_atoms",
     "pet_llpr_feature_size", "pet_llpr_features", "pet_llpr_rows", "pet_llpr_covariance_accumulate",
     "pet_llpr_covariance_finalize", "pet_llpr_variance", "pet_llpr_ensemble",
@@ -201,6 +202,10 @@ def load() -> ctypes.CDLL:
         fn.argtypes = [P, P]
         fn.restype = c_int64
     lib.pet_backward_train.argtypes = [P, P, P, c_int64, P, P, P, P]
+    lib.pet_train_predict.argtypes = [P, P, P, c_int64, c_char_p, c_int32, c_char_p, P, P]
+    lib.pet_train_predict_backward.argtypes = [P, P, P, c_int64, c_char_p, c_int32, c_int32, P, P, P, P, P]
+    lib.pet_backward_train_seeded.argtypes = [P, P, P, c_int64, P, P, P, P, P, c_int32, P]
+    lib.pet_backward_train2_seeded.argtypes = [P, P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, c_int32, P]
     lib.pet_sum_over_atoms.argtypes = [P, P, P, P]
     lib.pet_llpr_feature_size.argtypes = [P]
     lib.pet_llpr_feature_size.restype = c_int64

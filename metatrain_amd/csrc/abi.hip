@@ -673,18 +673,68 @@ int64_t pet_train2_workspace_bytes_for(const pet_model_t* pm, const pet_graph_t*
     return so_workspace_bytes(pm->m, pg->g.n_nodes, pg->g.n_edges);
 }
 
+static int find_head(const Model& m, const char* target, int32_t layer, const char* block, const HeadW** H, const LastW** Lw);
+
 int pet_backward_train(const pet_model_t* pm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
                        const float* d_grad_atomic, float* d_grad_positions, float* d_grad_cells, void* stream) {
     if (pg && pg->g.n_nodes == 0) return PET_OK;  // an empty system: nothing to compute, zero-sized buffers may be null
-    PET_REQUIRE(pm && pg && d_workspace && d_grad_atomic, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(d_grad_atomic, PET_ERR_ARGUMENT, "null argument");
+    return pet_backward_train_seeded(pm, pg, d_workspace, workspace_bytes, d_grad_atomic, d_grad_positions, d_grad_cells,
+                                     nullptr, nullptr, 0, stream);
+}
+
+int pet_backward_train_seeded(const pet_model_t* pm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
+                              const float* d_grad_atomic, float* d_grad_positions, float* d_grad_cells,
+                              const float* const* h_seed_node_features, const float* const* h_seed_edge_features,
+                              int32_t n_layers, void* stream) {
+    if (pg && pg->g.n_nodes == 0) return PET_OK;  // an empty system: nothing to compute, zero-sized buffers may be null
+    PET_REQUIRE(pm && pg && d_workspace, PET_ERR_ARGUMENT, "null argument");
     PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
+    PET_REQUIRE(n_layers == 0 || (h_seed_node_features && h_seed_edge_features), PET_ERR_ARGUMENT, "null seed list");
     Model& m = const_cast<Model&>(pm->m);  // the gradient slots (and LoRA scratch) are the model's mutable state
     const hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = lora_begin(m, st))) return rc;
-    if ((rc = backward_train(m, pg->g, d_workspace, workspace_bytes, d_grad_atomic, d_grad_positions, d_grad_cells, st)))
+    if ((rc = backward_train(m, pg->g, d_workspace, workspace_bytes, d_grad_atomic, d_grad_positions, d_grad_cells, st,
+                             h_seed_node_features, h_seed_edge_features, n_layers)))
         return rc;
     return lora_end(m, st);
+}
+
+int pet_train_predict(const pet_model_t* pm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
+                      const char* target, int32_t readout_layer, const char* block, float* d_atomic, void* stream) {
+    PET_REQUIRE(pm && pg && d_workspace, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
+    const HeadW* H;
+    const LastW* Lw;
+    int rc = find_head(pm->m, target, readout_layer, block, &H, &Lw);
+    if (rc) return rc;
+    if (pg->g.n_nodes == 0) return PET_OK;
+    PET_REQUIRE(d_atomic, PET_ERR_ARGUMENT, "null argument");
+    return train_predict(pm->m, pg->g, d_workspace, workspace_bytes, readout_layer, *H, *Lw, d_atomic, (hipStream_t)stream);
+}
+
+int pet_train_predict_backward(const pet_model_t* pm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
+                               const char* target, int32_t readout_layer, int32_t n_blocks, const char* const* blocks,
+                               const float* const* d_grad_atomic, float* d_seed_node_features, float* d_seed_edge_features,
+                               void* stream) {
+    PET_REQUIRE(pm && pg && d_workspace, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
+    PET_REQUIRE(n_blocks >= 1 && blocks && d_grad_atomic, PET_ERR_ARGUMENT, "no block to back-propagate");
+    const HeadW* H = nullptr;
+    std::vector<const LastW*> lw((size_t)n_blocks);
+    for (int b = 0; b < n_blocks; b++) {
+        const HeadW* Hb;
+        int rc = find_head(pm->m, target, readout_layer, blocks[b], &Hb, &lw[b]);
+        if (rc) return rc;
+        PET_REQUIRE(b == 0 || strcmp(blocks[b], blocks[b - 1]) != 0, PET_ERR_ARGUMENT, "a block is named twice");
+        H = Hb;
+    }
+    if (pg->g.n_nodes == 0) return PET_OK;
+    for (int b = 0; b < n_blocks; b++) PET_REQUIRE(d_grad_atomic[b], PET_ERR_ARGUMENT, "null seed of a block");
+    Model& m = const_cast<Model&>(pm->m);
+    return train_predict_backward(m, pg->g, d_workspace, workspace_bytes, target, readout_layer, *H, n_blocks, blocks,
+                                  lw.data(), d_grad_atomic, d_seed_node_features, d_seed_edge_features, (hipStream_t)stream);
 }
 
 int64_t pet_train2_workspace_bytes(const pet_model_t* pm, int64_t n_nodes, int64_t n_edges) {
@@ -706,16 +756,27 @@ int pet_backward_train2_cell(const pet_model_t* pm, const pet_graph_t* pg, void*
                              void* d_workspace2, int64_t workspace2_bytes, const float* d_lambda_atomic,
                              const float* d_nu_atomic, const float* d_u, const float* d_u_cell, float* d_tangent_atomic,
                              void* stream) {
+    return pet_backward_train2_seeded(pm, pg, d_workspace, workspace_bytes, d_workspace2, workspace2_bytes, d_lambda_atomic,
+                                      d_nu_atomic, d_u, d_u_cell, d_tangent_atomic, nullptr, nullptr, 0, stream);
+}
+
+int pet_backward_train2_seeded(const pet_model_t* pm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
+                               void* d_workspace2, int64_t workspace2_bytes, const float* d_lambda_atomic,
+                               const float* d_nu_atomic, const float* d_u, const float* d_u_cell, float* d_tangent_atomic,
+                               const float* const* h_seed_node_features, const float* const* h_seed_edge_features,
+                               int32_t n_layers, void* stream) {
     if (pg && pg->g.n_nodes == 0) return PET_OK;  // an empty system: nothing to compute, zero-sized buffers may be null
     PET_REQUIRE(pm && pg && d_workspace && d_workspace2 && d_lambda_atomic && d_u, PET_ERR_ARGUMENT, "null argument");
     PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
     PET_REQUIRE(!d_u_cell || pg->g.shift, PET_ERR_ARGUMENT, "a cell tangent needs a pet_graph_build handle (cell shifts)");
+    PET_REQUIRE(n_layers == 0 || (h_seed_node_features && h_seed_edge_features), PET_ERR_ARGUMENT, "null seed list");
     Model& m = const_cast<Model&>(pm->m);
     const hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = lora_begin(m, st))) return rc;
     if ((rc = backward_train2(m, pg->g, d_workspace, workspace_bytes, d_workspace2, workspace2_bytes, d_lambda_atomic,
-                              d_nu_atomic, d_u, d_tangent_atomic, st, d_u_cell)))
+                              d_nu_atomic, d_u, d_tangent_atomic, st, d_u_cell, h_seed_node_features, h_seed_edge_features,
+                              n_layers)))
         return rc;
     return lora_end(m, st);
 }

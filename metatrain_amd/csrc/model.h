@@ -267,7 +267,14 @@ int predict_backward(const Model& m, const Graph& g, const HeadW& H, const LastW
 int aux_outputs(const Model& m, const Graph& g, const float* node_feat, const float* edge_feat, float* feature,
                 float* last_layer, float* scratch, hipStream_t st);
 int backward_train(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* grad_atomic,
-                   float* grad_pos, float* grad_cells, hipStream_t st);
+                   float* grad_pos, float* grad_cells, hipStream_t st, const float* const* seed_node = nullptr,
+                   const float* const* seed_edge = nullptr, int n_seed = 0);
+// extra targets of a training step, from the features the training forward left in `ws` (pet_train_predict*)
+int train_predict(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, const HeadW& H, const LastW& Lw,
+                  float* atomic, hipStream_t st);
+int train_predict_backward(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const std::string& target, int layer,
+                           const HeadW& H, int n_blocks, const char* const* blocks, const LastW* const* Lw,
+                           const float* const* gA, float* seed_node, float* seed_edge, hipStream_t st);
 // llpr.hip: last-layer features of every readout layer and the four LLPR kernels (pet_hip.h, pet_llpr_*)
 int llpr_features(const Model& m, const Graph& g, const char* target, const char* block, const float* const* node_feats,
                   const float* const* edge_feats, int n_layers, float* atomic, float* llf, hipStream_t st);
@@ -284,7 +291,8 @@ int geometry_tangent(const Model& m, const Graph& g, const float* u, const float
                      hipStream_t st);
 int backward_train2(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, void* ws2, int64_t ws2_bytes,
                     const float* lambda_atomic, const float* nu_atomic, const float* u, float* tangent_atomic,
-                    hipStream_t st, const float* u_cell = nullptr);
+                    hipStream_t st, const float* u_cell = nullptr, const float* const* seed_node = nullptr,
+                    const float* const* seed_edge = nullptr, int n_seed = 0);
 int backward_predict_abi(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* grad_atomic,
                          float* g_node, float* g_edge, float* g_fc, hipStream_t st);
 int backward_features_abi(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* g_node,

@@ -1475,7 +1475,7 @@ int backward_geometry(const Model& m, const Graph& g, Workspace& w, const float*
 // Gn[i][c] = sum_p gA[i][p] Wn[p][c], Ge likewise with We, gb[i] = sum_p gA[i][p] be[p]
 __global__ void k_last_bwd(const float* __restrict__ gA, const float* __restrict__ nw, const float* __restrict__ ew,
                            const float* __restrict__ eb, int P, float* __restrict__ Gn, float* __restrict__ Ge,
-                           float* __restrict__ gbv, int n) {
+                           float* __restrict__ gbv, int n, int accumulate = 0) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (int64_t)n * DH) return;
     const int i = (int)(idx / DH), c = (int)(idx % DH);
@@ -1486,9 +1486,9 @@ __global__ void k_last_bwd(const float* __restrict__ gA, const float* __restrict
         b = fmaf(gv, ew[(int64_t)p * DH + c], b);
         s = fmaf(gv, eb[p], s);
     }
-    Gn[idx] = a;
-    Ge[idx] = b;
-    if (c == 0) gbv[i] = s;
+    Gn[idx] = accumulate ? Gn[idx] + a : a;  // accumulate: the blocks of one target share its heads
+    Ge[idx] = accumulate ? Ge[idx] + b : b;
+    if (c == 0) gbv[i] = accumulate ? gbv[i] + s : s;
 }
 
 // adjoint of predict() (pet_fwd.hip) for the features the caller passes in
@@ -1516,6 +1516,94 @@ int predict_backward(const Model& m, const Graph& g, const HeadW& H, const LastW
             nullptr, g_fc, g_edge, E, nullptr, nullptr, nullptr, nullptr, Ge, gbv);
     PET_HIP_CHECK(hipGetLastError());
     return PET_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// extra targets of a training step (non-conservative forces / stress, several blocks or properties): their predictions
+// and adjoints read the features pet_forward(save_for_backward = 2) left in the training workspace (last.Hout /
+// last.Mout), so a step runs ONE backbone forward and ONE backbone reverse sweep for all of its targets.
+// ---------------------------------------------------------------------------------------------
+// dst += src, float4 granularity
+__global__ void k_add_seed(float4* __restrict__ dst, const float4* __restrict__ src, int64_t n4) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    const float4 a = dst[i], b = src[i];
+    dst[i] = make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+static void add_seed(float* dst, const float* src, int64_t n, hipStream_t st) {
+    if (n > 0) k_add_seed<<<cdiv(n / 4, 256), 256, 0, st>>>(reinterpret_cast<float4*>(dst), reinterpret_cast<const float4*>(src), n / 4);
+}
+
+static int train_workspace(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, Workspace& w) {
+    PET_REQUIRE(!train_generic_for(m, g) && !generic_workspace(g, ws), PET_ERR_UNSUPPORTED,
+                "training extra targets is built for the tuned path (default size, PreLN + feedforward featuriser, at most "
+                "127 neighbours per atom, a batch with edges)");
+    PET_REQUIRE(layer == 0, PET_ERR_ARGUMENT, "the feedforward featuriser has one readout layer (0)");
+    carve_workspace(m, g.n_nodes, g.n_edges, ws, w, true);
+    PET_REQUIRE((int64_t)w.bytes <= ws_bytes, PET_ERR_ARGUMENT, "workspace too small for training");
+    return PET_OK;
+}
+
+int train_predict(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, const HeadW& H, const LastW& Lw,
+                  float* atomic, hipStream_t st) {
+    Workspace w;
+    int rc = train_workspace(m, g, ws, ws_bytes, layer, w);
+    if (rc || g.n_nodes == 0) return rc;
+    PoolBuf scratch;
+    PET_HIP_CHECK(scratch.alloc((size_t)predict_scratch_floats(g.n_nodes, g.n_edges) * sizeof(float), st));
+    const GnnBufs& last = w.gnn.back();
+    return predict(m, g, H, Lw, last.Hout, last.Mout, nullptr, atomic, nullptr, nullptr, scratch.as<float>(), st);
+}
+
+// dL/dtheta of one target's heads and of the last layers of `n_blocks` of its blocks (seeds gA[b] [N, P_b]) ADDED to the
+// gradient slots; the adjoints of the heads' inputs ADDED to seed_node [N, DN] / seed_edge [E, D] (either may be NULL).
+// The head MLPs run once per (target, layer): their hidden adjoint is the sum over the blocks (k_last_bwd).
+int train_predict_backward(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const std::string& target, int layer,
+                           const HeadW& H, int n_blocks, const char* const* blocks, const LastW* const* Lw,
+                           const float* const* gA, float* seed_node, float* seed_edge, hipStream_t st) {
+    Workspace w;
+    int rc = train_workspace(m, g, ws, ws_bytes, layer, w);
+    if (rc || g.n_nodes == 0 || n_blocks == 0) return rc;
+    PET_REQUIRE(m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
+    const int64_t N = g.n_nodes, E = g.n_edges;
+    auto al = [](int64_t n) { return (n + 63) & ~(int64_t)63; };
+    const int64_t nX = N * DN > E * D ? N * DN : E * D;
+    PoolBuf scratch;  // Gn, Ge [N, DH] | gb [N] | input adjoint rows | dfc [E] (not wanted: fc has no parameter)
+    PET_HIP_CHECK(scratch.alloc((size_t)(2 * al(N * DH) + al(N) + al(nX) + al(E)) * sizeof(float), st));
+    float* Gn = scratch.as<float>();
+    float* Ge = Gn + al(N * DH);
+    float* gbv = Ge + al(N * DH);
+    float* dX = gbv + al(N);
+    float* dfc = dX + al(nX);
+    for (int b = 0; b < n_blocks; b++)
+        k_last_bwd<<<cdiv(N * DH, 256), 256, 0, st>>>(gA[b], Lw[b]->nw, Lw[b]->ew, Lw[b]->eb, Lw[b]->P, Gn, Ge, gbv, (int)N,
+                                                       b > 0);
+    Trainer tr{m, g, w, m.grad_flat, st};
+    const std::string tl = target + "." + std::to_string(layer);
+    const GnnBufs& last = w.gnn.back();
+    const size_t ldsn = (BM * LD256 + BM * LD128) * 4 + 768 + BM * 4, ldse = 2 * BM * LD128 * 4 + 768 + BM * 4;
+    allow_big_lds(k_head_bwd<256, false, true, true>, ldsn);
+    allow_big_lds(k_head_bwd<128, true, true, true>, ldse);
+    {
+        ProfScope ps("extra_head_node_bwd", st, (double)N * 2.0 * (DN * DH + 2 * DH * DH));
+        k_head_bwd<256, false, true, true><<<cdiv(N, BM), NTHREADS, ldsn, st>>>(
+            last.Hout, wx_f(H.nh0), H.nh0.b, wx_f(H.nh2), H.nh2.b, wx_b(H.nh0), wx_b(H.nh2), nullptr, nullptr, nullptr,
+            nullptr, nullptr, nullptr, dX, N, w.hs1, w.hda2, w.hda1, w.hs2y, Gn, gbv);
+        tr.head_linears("node_heads." + tl, last.Hout, DN, N);
+        for (int b = 0; b < n_blocks; b++) tr.last_layer(false, "node_last_layers." + tl + "." + blocks[b], gA[b], Lw[b]->P, N);
+        if (seed_node) add_seed(seed_node, dX, N * DN, st);
+    }
+    if (E > 0) {
+        ProfScope ps("extra_head_edge_bwd", st, (double)E * 2.0 * (D * DH + 2 * DH * DH));
+        k_head_bwd<128, true, true, true><<<cdiv(E, BM), NTHREADS, ldse, st>>>(
+            last.Mout, wx_f(H.eh0), H.eh0.b, wx_f(H.eh2), H.eh2.b, wx_b(H.eh0), wx_b(H.eh2), nullptr, nullptr, g.ctr, g.fc,
+            nullptr, dfc, dX, E, w.hs1, w.hda2, w.hda1, w.hs2y, Ge, gbv);
+        tr.head_linears("edge_heads." + tl, last.Mout, D, E);
+        for (int b = 0; b < n_blocks; b++) tr.last_layer(true, "edge_last_layers." + tl + "." + blocks[b], gA[b], Lw[b]->P, E);
+        if (seed_edge) add_seed(seed_edge, dX, E * D, st);
+    }
+    PET_HIP_CHECK(hipGetLastError());
+    return tr.err;
 }
 
 #define PET_CARVE(w)                                                                      \
@@ -1618,11 +1706,18 @@ int backward(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const f
 // Training reverse pass (energy term): dL/dtheta accumulated into the model's flat gradient
 // buffer for the seeds gA = dL/d(atomic prediction), plus dL/dR (and dL/dcell) when requested.
 // Needs a forward run with save_for_backward = 2 on a training workspace.
+// seed_node / seed_edge [n_seed] (NULL entries = 0): feature adjoints of further targets (train_predict_backward), added
+// where the fused head's adjoint enters the backbone; gA may then be NULL (no fused target in the loss).
 int backward_train(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* gA, float* gpos,
-                   float* gcell, hipStream_t st) {
+                   float* gcell, hipStream_t st, const float* const* seed_node, const float* const* seed_edge, int n_seed) {
+    const float* sn = n_seed > 0 && seed_node ? seed_node[0] : nullptr;
+    const float* se = n_seed > 0 && seed_edge ? seed_edge[0] : nullptr;
     // other sizes, PostLN, residual, and any graph with an atom of more than 127 neighbours: the energy term alone = the
     // size-generic second-order pass without a tangent
     if (train_generic_for(m, g)) {
+        PET_REQUIRE(gA && !sn && !se, PET_ERR_UNSUPPORTED,
+                    "training extra targets is built for the tuned path (default size, PreLN + feedforward featuriser, at "
+                    "most 127 neighbours per atom, a batch with edges)");
         PET_REQUIRE(generic_workspace(g, ws), PET_ERR_ARGUMENT, "pet_forward with save_for_backward = 2 has not run on this workspace");
         // (the energy-only step has no second-order workspace of its own in the ABI: the dual activations come from the
         // stream's pool and go back to it on every exit)
@@ -1640,9 +1735,24 @@ int backward_train(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, c
     PET_REQUIRE((int64_t)w.bytes <= ws_bytes, PET_ERR_ARGUMENT, "workspace too small for training");
     if (g.n_nodes == 0) return PET_OK;
     PET_REQUIRE(g.n_edges > 0, PET_ERR_UNSUPPORTED, "training on a batch without any edge is not supported");
+    PET_REQUIRE(n_seed == 0 || n_seed == m.num_readout_layers(), PET_ERR_ARGUMENT, "expected one seed pair per readout layer");
+    // the seeds carry the further targets' feature adjoints only, not their cutoff-factor adjoint (d fc / dR): dL/dR and
+    // dL/dcell of such a loss would be incomplete
+    PET_REQUIRE(!(gpos || gcell) || !(sn || se), PET_ERR_UNSUPPORTED,
+                "d_grad_positions / d_grad_cells with feature seeds: the further targets' cutoff-factor adjoint is not "
+                "carried; ask for the parameter gradients only");
     Trainer tr{m, g, w, m.grad_flat, st};
     int rc;
-    if ((rc = backward_predict(m, g, w, gA, st, &tr))) return rc;
+    if (gA) {
+        PET_REQUIRE(m.has_fused_head, PET_ERR_ARGUMENT, "d_grad_atomic needs the fused single-property target");
+        if ((rc = backward_predict(m, g, w, gA, st, &tr))) return rc;
+    } else {
+        PET_HIP_CHECK(hipMemsetAsync(w.dH, 0, g.n_nodes * DN * sizeof(float), st));
+        PET_HIP_CHECK(hipMemsetAsync(w.dM, 0, g.n_edges * D * sizeof(float), st));
+        PET_HIP_CHECK(hipMemsetAsync(w.dfc, 0, g.n_edges * sizeof(float), st));
+    }
+    if (sn) add_seed(w.dH, sn, g.n_nodes * DN, st);
+    if (se) add_seed(w.dM, se, g.n_edges * D, st);
     if (!gpos && !tr.backbone_live()) return tr.err;  // only heads / last layers train
     if ((rc = backward_features(m, g, w, st, &tr))) return rc;
     if (tr.err) return tr.err;

@@ -453,6 +453,15 @@ __global__ void k_add3(const float* __restrict__ a, const float* __restrict__ b,
 static void add3(const Ctx& c, const float* a, const float* b, const float* cc, float* out, int64_t n) {
     if (n > 0) k_add3<<<cdiv(n / 4, 256), 256, 0, c.st>>>(a, b, cc, out, n / 4);
 }
+// dst += src in place, float4 granularity (the further targets' seeds into nu)
+__global__ void k_add_into(float* __restrict__ dst, const float* __restrict__ src, int64_t n4) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n4) return;
+    float4 x = reinterpret_cast<float4*>(dst)[i];
+    const float4 y = reinterpret_cast<const float4*>(src)[i];
+    x.x += y.x; x.y += y.y; x.z += y.z; x.w += y.w;
+    reinterpret_cast<float4*>(dst)[i] = x;
+}
 
 template <int LPR>
 __device__ __forceinline__ float group_sum(float v) {
@@ -1251,12 +1260,22 @@ static void head_reverse(const Ctx& c, Trainer& tr, SoWs& s, bool edge, const Li
 // ---------------------------------------------------------------------------------------------
 int backward_train2(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, void* ws2, int64_t ws2_bytes,
                     const float* lA, const float* nA, const float* u, float* tangent_atomic, hipStream_t st,
-                    const float* ucell) {
+                    const float* ucell, const float* const* seed_node, const float* const* seed_edge, int n_seed) {
+    // seed_node / seed_edge: first-order feature adjoints of further targets (train_predict_backward), added to nu
+    const float* sn = n_seed > 0 && seed_node ? seed_node[0] : nullptr;
+    const float* se = n_seed > 0 && seed_edge ? seed_edge[0] : nullptr;
     // other sizes, PostLN, residual, more than 127 neighbours per atom: gen_train.hip (it recomputes what it needs in ws2)
-    if (train_generic_for(m, g)) return gen_train2(m, g, ws2, ws2_bytes, lA, nA, u, ucell, tangent_atomic, st);
+    if (train_generic_for(m, g)) {
+        PET_REQUIRE(!sn && !se, PET_ERR_UNSUPPORTED,
+                    "training extra targets is built for the tuned path (default size, PreLN + feedforward featuriser, at "
+                    "most 127 neighbours per atom, a batch with edges)");
+        return gen_train2(m, g, ws2, ws2_bytes, lA, nA, u, ucell, tangent_atomic, st);
+    }
     PET_REQUIRE(m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
     PET_REQUIRE(m.trainable(), PET_ERR_UNSUPPORTED,
                 "training is built for transformer_type=PreLN, featurizer_type=feedforward only");
+    PET_REQUIRE(m.has_fused_head, PET_ERR_ARGUMENT, "the second-order pass needs the fused single-property target");
+    PET_REQUIRE(n_seed == 0 || n_seed == m.num_readout_layers(), PET_ERR_ARGUMENT, "expected one seed pair per readout layer");
     Workspace w;
     carve_workspace(m, g.n_nodes, g.n_edges, ws, w, true);
     PET_REQUIRE((int64_t)w.bytes <= ws_bytes, PET_ERR_ARGUMENT, "workspace too small for training");
@@ -1346,6 +1365,9 @@ int backward_train2(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, 
                  s.NH, N);
     if (tangent_atomic) k_tangent_atom_sum<<<grid1(N), 256, 0, st>>>(s.tan_n, s.tan_e, g.rowptr, tangent_atomic, (int)N);
     if (!tr.backbone_live()) return tr.err;  // only heads / last layers train: the backbone's sweep has nothing to give
+    // further targets do not move with R (no tangent): their adjoints join nu only
+    if (sn) k_add_into<<<grid1(N * DN / 4), 256, 0, st>>>(s.NH, sn, N * DN / 4);
+    if (se) k_add_into<<<grid1(E * D / 4), 256, 0, st>>>(s.NM, se, E * D / 4);
     float *t0 = s.tmp[0], *t1 = s.tmp[1], *t2 = s.tmp[2], *t3 = s.tmp[3], *t4 = s.tmp[4], *t5 = s.tmp[5];
     const bool lnm = m.layer_norm();
     const int nx = lnm ? 5 : 1;  // weight-gradient row source: LayerNorm-hat / RMSNorm-hat of the saved input

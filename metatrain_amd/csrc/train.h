@@ -42,7 +42,14 @@ struct Trainer {
     void vecsum(const float* vec, int64_t n_rows, float* dst);         // dst[0] += sum_rows vec[row]
     void species_rows(const float* buf, const int* idx, int64_t n_rows, int C, float* dst);
 
+    // the fused head ("@"): its two Linears and its one-property last layer
     void heads(bool edge, const float* Xin, int k_in, int64_t n_rows, const float* gA);
+    // the two Linears "<head>.0" / "<head>.2" of a head MLP (head = "{node,edge}_heads.<target>.<layer>") from the
+    // temporaries k_head_bwd<..., TRAIN> left in w.hs1 / w.hda2 / w.hda1
+    void head_linears(const std::string& head, const float* Xin, int k_in, int64_t n_rows);
+    // last layer `key` with P outputs from the seeds gA [N, P]: dW[p][c] += sum_rows gA[atom][p] w.hs2y[row][c] and
+    // db[p] += sum_rows gy[row] gA[atom][p] (edge rows: atom = ctr[row], gy = fc[row]; node rows: atom = row, gy = 1)
+    void last_layer(bool edge, const std::string& key, const float* gA, int P, int64_t n_rows);
     void embeddings(const float* dH0, const float* dM0);
     // system conditioning (conditioning.py:82-100; backend.py:543-545 adds the per-system embedding to the node features
     // LEAVING every GNN layer): cond_accumulate sums that layer's node-feature adjoint over the atoms of each system

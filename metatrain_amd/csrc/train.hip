@@ -388,12 +388,73 @@ void Trainer::cond_finish() {
     k_cond_bwd_emb<<<1, DN, 0, st>>>(g.cond_charge, g.cond_spin, dx, ns, m.h.max_charge, m.h.max_spin_multiplicity, gq, gm);
 }
 
-void Trainer::heads(bool edge, const float* Xin, int k_in, int64_t n_rows, const float* gA) {
+void Trainer::head_linears(const std::string& h, const float* Xin, int k_in, int64_t n_rows) {
     if (n_rows <= 0 || err) return;
-    const std::string h = edge ? "edge_heads.@.0" : "node_heads.@.0";
-    const std::string l = edge ? "edge_last_layers.@.0.@" : "node_last_layers.@.0.@";
     linear(h + ".0", DH, k_in, {w.hda1, nullptr, 0, DH}, {Xin, k_in, 0, nullptr, nullptr}, 0, n_rows);
     linear(h + ".2", DH, DH, {w.hda2, nullptr, 0, DH}, {w.hs1, DH, 0, nullptr, nullptr}, 0, n_rows);
+}
+
+// last layer with P outputs, one pass over s2y per PC outputs: pw[split][p][c] = sum_rows gA[atom][p] s2y[row][c],
+// pb[split][p] = sum_rows gy[row] gA[atom][p]. s2y already holds gy * silu(a2). Fixed split order (reduce_2d): no atomics.
+template <int PC>
+__global__ __launch_bounds__(DH) void k_last_wgrad_partial(const float* __restrict__ s2y, const float* __restrict__ gA, int P,
+                                                           int p0, const int* __restrict__ ctr, const float* __restrict__ fc,
+                                                           int64_t n_rows, float* __restrict__ pw, float* __restrict__ pb) {
+    const int c = threadIdx.x;
+    const int nsplit = gridDim.x;
+    const int64_t per = (n_rows + nsplit - 1) / nsplit;
+    const int64_t r0 = (int64_t)blockIdx.x * per, r1 = min(n_rows, r0 + per);
+    const int np = P - p0 < PC ? P - p0 : PC;
+    float acc[PC], accb[PC];
+#pragma unroll
+    for (int q = 0; q < PC; q++) acc[q] = accb[q] = 0.f;
+#pragma unroll 4  // several rows' loads in flight
+    for (int64_t r = r0; r < r1; r++) {
+        const int64_t a = ctr ? (int64_t)ctr[r] : r;
+        const float gy = ctr ? fc[r] : 1.f;
+        const float s = s2y[r * DH + c];
+        const float* ga = gA + a * P + p0;
+#pragma unroll
+        for (int q = 0; q < PC; q++)
+            if (q < np) {
+                const float gv = ga[q];
+                acc[q] = fmaf(gv, s, acc[q]);
+                accb[q] = fmaf(gy, gv, accb[q]);
+            }
+    }
+#pragma unroll
+    for (int q = 0; q < PC; q++)
+        if (q < np) {
+            pw[((size_t)blockIdx.x * P + p0 + q) * DH + c] = acc[q];
+            if (c == 0) pb[(size_t)blockIdx.x * P + p0 + q] = accb[q];
+        }
+}
+
+void Trainer::last_layer(bool edge, const std::string& key, const float* gA, int P, int64_t n_rows) {
+    if (n_rows <= 0 || err || P < 1) return;
+    float* dw = gl(key + ".weight");
+    float* db = gl(key + ".bias");
+    if (!dw && !db) return;  // frozen
+    int nsplit = 1024;
+    if (nsplit > n_rows) nsplit = (int)n_rows;
+    while ((size_t)nsplit * P * (DH + 1) > w.partial_floats && nsplit > 1) nsplit /= 2;
+    float* pw = w.partial;
+    float* pb = w.partial + (size_t)nsplit * P * DH;
+    // one read of s2y for up to 16 properties (NC stress: 9); more properties take further passes
+    for (int p0 = 0; p0 < P; p0 += 16) {
+        const int* ctr = edge ? g.ctr : nullptr;
+        if (P - p0 <= 4) k_last_wgrad_partial<4><<<nsplit, DH, 0, st>>>(w.hs2y, gA, P, p0, ctr, g.fc, n_rows, pw, pb);
+        else if (P - p0 <= 8) k_last_wgrad_partial<8><<<nsplit, DH, 0, st>>>(w.hs2y, gA, P, p0, ctr, g.fc, n_rows, pw, pb);
+        else k_last_wgrad_partial<16><<<nsplit, DH, 0, st>>>(w.hs2y, gA, P, p0, ctr, g.fc, n_rows, pw, pb);
+    }
+    if (dw) reduce_2d(pw, nsplit, P, DH, dw, DH, 0, 1, st);
+    if (db) reduce_2d(pb, nsplit, P, 1, db, 1, 0, 1, st);
+}
+
+void Trainer::heads(bool edge, const float* Xin, int k_in, int64_t n_rows, const float* gA) {
+    if (n_rows <= 0 || err) return;
+    const std::string l = edge ? "edge_last_layers.@.0.@" : "node_last_layers.@.0.@";
+    head_linears(edge ? "edge_heads.@.0" : "node_heads.@.0", Xin, k_in, n_rows);
     // last layer: d w = colsum(gy * s2), d b = sum gy
     const int nsplit = 256;
     if (float* dw = gl(l + ".weight")) {

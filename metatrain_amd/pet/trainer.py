@@ -71,6 +71,84 @@ def strain_loss_and_seeds(positions: torch.Tensor, cells: torch.Tensor, system_o
     return loss, u, cells @ g
 
 
+def process_non_conservative_stress(pred: torch.Tensor, cells: torch.Tensor, system_of_atom: torch.Tensor) -> torch.Tensor:
+    """``backend.py`` ``process_non_conservative_stress`` on per-atom predictions ``[N, 9 P]``: divided by the volume of
+    the atom's cell (a zero volume -- a non-periodic system -- counts as infinite) and symmetrised."""
+    n, p = pred.shape[0], pred.shape[1] // 9
+    t = pred.reshape(n, 3, 3, p)
+    c = cells.to(pred.dtype)
+    vol = torch.abs((c[:, 0] * torch.linalg.cross(c[:, 1], c[:, 2])).sum(-1))  # |det|, elementwise (fixed order)
+    vol = torch.where(vol == 0.0, torch.full_like(vol, float("inf")), vol)
+    t = t / vol[system_of_atom][:, None, None, None]
+    return ((t + t.transpose(1, 2)) / 2.0).reshape(n, 9 * p)
+
+
+def _extra_blocks(name: str, spec: dict) -> Dict[str, torch.Tensor]:
+    values = spec["values"]
+    return values if isinstance(values, dict) else {name: values}
+
+
+def extra_target_count(name: str, spec: dict) -> int:
+    """The number of non-NaN target entries of one extra target (the denominator of its MSE)."""
+    return int(sum(int((~torch.isnan(t)).sum()) for t in _extra_blocks(name, spec).values()))
+
+
+class _SumOverAtoms(torch.autograd.Function):
+    """Per-structure sums of per-atom columns in a fixed order (``pet_sum_over_atoms``; index_add's float atomics make
+    the step's seeds vary run to run)."""
+
+    @staticmethod
+    def forward(ctx, p, fw, system_of_atom):
+        ctx.save_for_backward(system_of_atom)
+        return torch.stack([fw.sum_over_atoms(p[:, j].contiguous()) for j in range(p.shape[1])], dim=1)
+
+    @staticmethod
+    def backward(ctx, g):
+        (s,) = ctx.saved_tensors
+        return g[s], None, None
+
+
+def extra_target_loss(name: str, spec: dict, preds: Dict[str, torch.Tensor], system_of_atom: torch.Tensor,
+                      n_atoms: torch.Tensor, cells: Optional[torch.Tensor], weight: float, per_structure_targets=(),
+                      count: Optional[int] = None, structure_sum=None) -> torch.Tensor:
+    """The reference's loss term of one further target (``pet/trainer.py:430-451``, ``utils/loss.py:144-217``, "mse" /
+    "mean"): every block's per-atom predictions ``preds[block]`` ``[N, P]`` -> (``non_conservative_stress``:
+    :func:`process_non_conservative_stress`) -> per-structure targets (``spec["per_atom"] = False``): summed over the atoms
+    -> ``average_by_num_atoms`` (``utils/per_atom.py``): per-structure predictions AND targets divided by n_atoms unless
+    the name is in ``per_structure_targets`` -> per-property scales (``spec["scales"] = {block: [n_properties]}``,
+    ``scaler.apply_scales(use_per_property_scales=True)``: predictions only) -> one MSE over the concatenation of all
+    blocks' flattened values, NaN targets dropped. ``count``: the denominator (the whole step's non-NaN entries when
+    micro-batched); ``structure_sum(p)``: the per-structure sum ``[S, P]`` (default: index_add)."""
+    per_atom = spec.get("per_atom", True)
+    scales = spec.get("scales") or {}
+    diffs = []
+    for b, target in _extra_blocks(name, spec).items():
+        p = preds[b]
+        if name == "non_conservative_stress":
+            if cells is None:
+                raise ValueError("a non_conservative_stress target needs `cells`")
+            p = process_non_conservative_stress(p, cells, system_of_atom)
+        t = target.to(device=p.device, dtype=p.dtype)
+        if not per_atom:
+            if structure_sum is not None:
+                p = structure_sum(p)
+            else:
+                p = torch.zeros((n_atoms.numel(), p.shape[1]), dtype=p.dtype, device=p.device).index_add(0, system_of_atom, p)
+            t = t.reshape(p.shape)
+            if name not in per_structure_targets:
+                n = n_atoms.to(device=p.device, dtype=p.dtype)[:, None]
+                p, t = p / n, t / n
+        t = t.reshape(p.shape)
+        if b in scales:  # the innermost axis of a block's values is its properties
+            sc = torch.as_tensor(scales[b]).to(device=p.device, dtype=p.dtype).reshape(-1)
+            p = (p.reshape(p.shape[0], -1, sc.numel()) * sc).reshape(p.shape)
+        valid = ~torch.isnan(t)
+        diffs.append((p - torch.nan_to_num(t))[valid])
+    d = torch.cat(diffs)
+    n = d.numel() if count is None else count
+    return weight * (d * d).sum() / max(n, 1)
+
+
 class TrainStep:
     """One optimizer step on one batch (a ``HipGraph`` of several structures)."""
 
@@ -99,17 +177,23 @@ class TrainStep:
         h = self.hypers
         return h["learning_rate"] * lr_lambda(self.step_index, self.total_steps, h["warmup_fraction"])
 
-    def __call__(self, graph: HipGraph, fw: HipForward, target_energies: torch.Tensor,
+    def __call__(self, graph: HipGraph, fw: HipForward, target_energies: Optional[torch.Tensor],
                  n_atoms: torch.Tensor, target_gradients: Optional[torch.Tensor] = None,
                  target_strain_gradients: Optional[torch.Tensor] = None, positions: Optional[torch.Tensor] = None,
-                 cells: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+                 cells: Optional[torch.Tensor] = None, extra_targets: Optional[Dict[str, dict]] = None
+                 ) -> Dict[str, torch.Tensor]:
         """``target_gradients`` [N,3] = dE/dR targets (-forces); None trains on energies only.
         ``target_strain_gradients`` [S,3,3] = dE/dstrain targets (stress x volume; needs ``positions`` and ``cells``,
-        weight ``loss_weights["strain"]``, default 1)."""
+        weight ``loss_weights["strain"]``, default 1).
+        ``extra_targets``: further targets whose heads were uploaded under their own names (non-conservative forces and
+        stress, several blocks or properties), ``{name: {"values": [N|S, ...] or {block: [N|S, ...]}, "per_atom": bool
+        (default True), "weight": float (default loss_weights[name]), "scales": optional {block: per-property scales}}}``; NaN target entries are dropped, a
+        ``non_conservative_stress`` target needs ``cells``. ``target_energies`` may then be None (a model loaded with
+        ``target=None``). One forward and one backbone reverse sweep serve all targets."""
         self.model.zero_grad()
         loss, energies = self._accumulate(graph, fw, target_energies, n_atoms, target_gradients, target_strain_gradients,
-                                          positions, cells, 1.0, 1.0, 1.0)
-        norm = self._finish()
+                                          positions, cells, 1.0, 1.0, 1.0, extra_targets)
+        norm = self._finish(self._trained(target_energies is not None, [extra_targets]))
         return {"loss": loss, "grad_norm": norm, "energies": energies}
 
     def microbatched(self, batches) -> Dict[str, torch.Tensor]:
@@ -121,61 +205,119 @@ class TrainStep:
         (``utils/loss.py`` "mean" reduction over ALL structures / components), so the result equals the one-batch step up
         to fp32 summation order."""
         batches = list(batches)
-        s_tot = float(sum(int(b["target_energies"].numel()) for b in batches))
+        s_tot = float(sum(int(b["n_atoms"].numel()) for b in batches))
         n_tot = float(sum(int(b["graph"].n_nodes) for b in batches))
+        counts = {}  # extra targets: the whole step's non-NaN entries (their MSE's denominator)
+        for b in batches:
+            for name, spec in (b.get("extra_targets") or {}).items():
+                counts[name] = counts.get(name, 0) + extra_target_count(name, spec)
         self.model.zero_grad()
         loss, energies = None, []
         for b in batches:
-            s_b, n_b = float(b["target_energies"].numel()), float(b["graph"].n_nodes)
-            l_b, e_b = self._accumulate(b["graph"], b["fw"], b["target_energies"], b["n_atoms"], b.get("target_gradients"),
-                                        b.get("target_strain_gradients"), b.get("positions"), b.get("cells"),
-                                        s_b / s_tot, n_b / n_tot, s_b / s_tot)
+            s_b, n_b = float(b["n_atoms"].numel()), float(b["graph"].n_nodes)
+            l_b, e_b = self._accumulate(b["graph"], b["fw"], b.get("target_energies"), b["n_atoms"],
+                                        b.get("target_gradients"), b.get("target_strain_gradients"), b.get("positions"),
+                                        b.get("cells"), s_b / s_tot, n_b / n_tot, s_b / s_tot, b.get("extra_targets"), counts)
             loss = l_b if loss is None else loss + l_b
             energies.append(e_b)
-        norm = self._finish()
-        return {"loss": loss, "grad_norm": norm, "energies": torch.cat(energies)}
+        norm = self._finish(self._trained(any(b.get("target_energies") is not None for b in batches),
+                                          [b.get("extra_targets") for b in batches]))
+        return {"loss": loss, "grad_norm": norm, "energies": None if energies[0] is None else torch.cat(energies)}
 
-    def begin(self, graph: HipGraph, fw: HipForward, target_energies: torch.Tensor, n_atoms: torch.Tensor,
+    def begin(self, graph: HipGraph, fw: HipForward, target_energies: Optional[torch.Tensor], n_atoms: torch.Tensor,
               target_gradients: Optional[torch.Tensor] = None, target_strain_gradients: Optional[torch.Tensor] = None,
-              positions: Optional[torch.Tensor] = None, cells: Optional[torch.Tensor] = None) -> None:
+              positions: Optional[torch.Tensor] = None, cells: Optional[torch.Tensor] = None,
+              extra_targets: Optional[Dict[str, dict]] = None) -> None:
         """First half of :meth:`__call__`: the three sweeps of the batch, then the gradient all-reduce is STARTED
         (``distributed.all_reduce_gradients_async``: RCCL runs it on its own stream). Whatever the caller launches before
         :meth:`end` -- the next batch's neighbour lists and graph build, as the reference's DataLoader workers do beside
         ``loss.backward()`` (``pet/trainer.py:417-472``) -- overlaps the collective."""
         self.model.zero_grad()
         self._pending = self._accumulate(graph, fw, target_energies, n_atoms, target_gradients, target_strain_gradients,
-                                         positions, cells, 1.0, 1.0, 1.0)
+                                         positions, cells, 1.0, 1.0, 1.0, extra_targets)
+        self._pending_trained = self._trained(target_energies is not None, [extra_targets])
         self._reduce = D.all_reduce_gradients_async(self.model, self.comm_events)
 
     def end(self) -> Dict[str, torch.Tensor]:
         """Second half: wait for the reduced gradients (a stream dependency under RCCL), clip + AdamW + schedule."""
         loss, energies = self._pending
-        norm = self._finish()
+        norm = self._finish(self._pending_trained)
         self._pending = None
         return {"loss": loss, "grad_norm": norm, "energies": energies}
 
-    def _finish(self) -> torch.Tensor:
+    def _trained(self, with_energy: bool, extra_list) -> Dict[str, Optional[set]]:
+        """target -> the blocks this step's loss reads (None: every block)."""
+        out: Dict[str, Optional[set]] = {}
+        if with_energy and self.model.target is not None:
+            out[self.model.target] = None
+        for extra in extra_list:
+            for name, spec in (extra or {}).items():
+                out.setdefault(name, set()).update(_extra_blocks(name, spec))
+        return out
+
+    def _finish(self, trained: Optional[Dict[str, Optional[set]]] = None) -> torch.Tensor:
         m = self.model
         reduce = getattr(self, "_reduce", None) or D.all_reduce_gradients_async(m, self.comm_events)
         self._reduce = None
         reduce.wait()
-        norm = m.adam_step(self.current_lr(), self.step_index + 1, weight_decay=self.hypers["weight_decay"],
-                           max_grad_norm=self.hypers["grad_clip_norm"] or 0.0)
+        # heads and last layers of targets (blocks) absent from this step's loss have no .grad in the reference's loop,
+        # so torch's optimizer leaves them and their moments alone (weight decay included)
+        idle = []
+        if trained is not None:
+            for key, (t, b) in m.head_keys().items():
+                if t not in trained or (b is not None and trained[t] is not None and b not in trained[t]):
+                    idle.append(key)
+        with m.frozen_for_step(idle):
+            norm = m.adam_step(self.current_lr(), self.step_index + 1, weight_decay=self.hypers["weight_decay"],
+                               max_grad_norm=self.hypers["grad_clip_norm"] or 0.0)
         self.step_index += 1
         return norm
 
+    def _extra(self, graph, fw, n_atoms, cells, extra_targets, extra_counts):
+        """Predictions of the further targets from the training forward's features, their loss terms, and the summed
+        adjoints of the heads' inputs (``train_predict_backward``, which also adds the heads' parameter gradients)."""
+        w = self.hypers["loss_weights"]
+        sys = graph.system_of_atom().long()
+        loss, seed_features = None, None
+        for name, spec in extra_targets.items():
+            preds = {b: fw.train_predict(name, b).requires_grad_(True) for b in _extra_blocks(name, spec)}
+            weight = float(spec.get("weight", w.get(name, 1.0)))
+            count = None if extra_counts is None else extra_counts[name]
+            loss_t = extra_target_loss(name, spec, preds, sys, n_atoms, cells, weight,
+                                       self.hypers.get("per_structure_targets", ()), count,
+                                       lambda p: _SumOverAtoms.apply(p, fw, sys))
+            grads = torch.autograd.grad(loss_t, list(preds.values()))
+            seed_features = fw.train_predict_backward(name, dict(zip(preds, grads)), seed_features=seed_features)
+            loss = loss_t.detach() if loss is None else loss + loss_t.detach()
+        return loss, seed_features
+
     def _accumulate(self, graph, fw, target_energies, n_atoms, target_gradients, target_strain_gradients, positions, cells,
-                    share_e: float, share_f: float, share_s: float):
+                    share_e: float, share_f: float, share_s: float, extra_targets=None, extra_counts=None):
         """Forward + reverse passes of one (micro-)batch, parameter gradients ADDED to the model's slots; ``share_*`` =
-        this batch's fraction of the structures / force components / strain components of the whole step."""
+        this batch's fraction of the structures / force components / strain components of the whole step.
+        ``extra_targets``: further targets (see :meth:`__call__`), served by the same forward and the same one backbone
+        reverse sweep."""
         w = self.hypers["loss_weights"]
         if fw.graph is not graph:  # micro-batches may share one workspace allocation
             fw.rebind(graph)
-        atomic = fw.forward()
-        energies = fw.sum_over_atoms(atomic)
-        loss, seeds = energy_loss_and_seeds(energies, target_energies, n_atoms, graph.system_of_atom(), w["energy"] * share_e)
+        if target_energies is None:
+            if target_gradients is not None or target_strain_gradients is not None:
+                raise ValueError("force / strain-gradient targets need the energy target")
+            if not extra_targets:
+                raise ValueError("no target to train")
+            fw.forward(want_atomic=False)
+            loss, seeds, energies = None, None, None
+        else:
+            atomic = fw.forward()
+            energies = fw.sum_over_atoms(atomic)
+            loss, seeds = energy_loss_and_seeds(energies, target_energies, n_atoms, graph.system_of_atom(),
+                                                w["energy"] * share_e)
+        seed_features = None
+        if extra_targets:
+            loss_x, seed_features = self._extra(graph, fw, n_atoms, cells, extra_targets, extra_counts)
+            loss = loss_x if loss is None else loss + loss_x
         if target_gradients is None and target_strain_gradients is None:
-            fw.backward_train(seeds)
+            fw.backward_train(seeds, seed_features=seed_features)
         else:
             ones = torch.ones_like(atomic)
             # evaluate_model: autograd.grad(E.sum(), [R, strain], create_graph=True)
@@ -193,5 +335,5 @@ class TrainStep:
                     grad_cells, target_strain_gradients, w.get("strain", 1.0) * share_s)
                 loss = loss + loss_s
                 u = u + u_s
-            fw.backward_train2(ones, seeds, u, u_cell=u_cell)
+            fw.backward_train2(ones, seeds, u, u_cell=u_cell, seed_features=seed_features)
         return loss, energies

@@ -1,8 +1,9 @@
 """Thin host layer over the C ABI: torch owns device memory and streams, libpet_hip
 does the work. Nothing here computes on the CPU and nothing falls back to torch ops.
 """
+import contextlib
 import ctypes
-from ctypes import byref, c_double, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 from typing import Dict, Iterable, List, Optional, Tuple, Union
 
 import torch
@@ -120,6 +121,7 @@ class HipModel:
         self.target = target
         self._fused_block = block
         self._ckeys: Dict[str, tuple] = {}
+        self._frozen = set()  # keys frozen by set_trainable
         self._tied = set()  # SiLU variant: w_in parameters uploaded twice (value half = gate half)
         last_w = params.get(f"node_last_layers.{target}.0.{block}.weight") if target is not None else None
         # the fused target: one property. Its heads and last layers go up under the name "@" -- of readout layer 0, and with
@@ -172,6 +174,31 @@ class HipModel:
             if key not in self._ckeys:
                 raise PetHipError(f"unknown parameter '{key}'")
             check(self.lib.pet_model_set_trainable(self._handle, self._ckeys[key][0].encode(), int(bool(on))))
+            (self._frozen.discard if on else self._frozen.add)(key)
+
+    def head_keys(self) -> Dict[str, Tuple[str, Optional[str]]]:
+        """Every uploaded head / last-layer key -> (target, block; None for a head), under the state dict's names."""
+        out = {}
+        for key in self._ckeys:
+            parts = key.split(".")
+            if parts[0] in ("node_heads", "edge_heads"):
+                out[key] = (parts[1], None)
+            elif parts[0] in ("node_last_layers", "edge_last_layers"):
+                out[key] = (parts[1], ".".join(parts[3:-1]))
+        return out
+
+    @contextlib.contextmanager
+    def frozen_for_step(self, keys: Iterable[str]):
+        """Freeze ``keys`` for what runs inside (one optimizer step: torch's optimizers skip a parameter whose ``.grad``
+        is None), leaving what :meth:`set_trainable` chose untouched."""
+        keys = [k for k in keys if k not in self._frozen]
+        for k in keys:
+            check(self.lib.pet_model_set_trainable(self._handle, self._ckeys[k][0].encode(), 0))
+        try:
+            yield
+        finally:
+            for k in keys:
+                check(self.lib.pet_model_set_trainable(self._handle, self._ckeys[k][0].encode(), 1))
 
     def load_species_table(self) -> None:
         """Upload only ``species_to_species_index`` (enough for graph building: the SOAP path shares the
@@ -492,10 +519,12 @@ class HipForward:
                                              _ptr(gfc), _ptr(gpos), _ptr(gcell), _stream()))
         return (gpos, gcell) if want_cell_grad else gpos
 
-    def forward(self, want_features: bool = False):
+    def forward(self, want_features: bool = False, want_atomic: bool = True):
+        """``want_atomic=False``: no fused head is evaluated (a model loaded with ``target=None``); the training forward
+        still saves what :meth:`train_predict` and the reverse passes read. Returns None for the atomic predictions."""
         g = self.graph
         dev = self.workspace.device
-        atomic = torch.empty(g.n_nodes, dtype=torch.float32, device=dev)
+        atomic = torch.empty(g.n_nodes, dtype=torch.float32, device=dev) if want_atomic else None
         nf = torch.empty((g.n_nodes, self.model.hypers["d_node"]), dtype=torch.float32, device=dev) if want_features else None
         ef = torch.empty((g.n_edges, self.model.hypers["d_pet"]), dtype=torch.float32, device=dev) if want_features else None
         check(self.lib.pet_forward(self.model.handle, g.handle, _ptr(self.workspace), self.nbytes,
@@ -538,27 +567,85 @@ class HipForward:
             raise ValueError("system conditioning: training needs non-decreasing system_indices (concatenate_structures "
                              "order); the per-system sums of the conditioning gradients run over contiguous atoms")
 
-    def backward_train(self, grad_atomic: torch.Tensor, want_position_grad: bool = False,
-                       want_cell_grad: bool = False):
+    def train_predict(self, target: str, block: Optional[str] = None, readout_layer: int = 0) -> torch.Tensor:
+        """Prediction ``[N, P]`` of one (target, readout layer, block) from the features the training forward left in
+        this workspace (``pet_train_predict``): no second backbone forward."""
+        if not self.train:
+            raise PetHipError("train_predict needs HipForward(..., train=True)")
+        tname, bname = _head_names(self.model, target, block, readout_layer == 0)
+        p = int(self.lib.pet_model_block_properties(self.model.handle, tname, readout_layer, bname))
+        if p < 1:
+            raise PetHipError(f"no head / last layer uploaded for target '{target}', readout layer {readout_layer}, block "
+                              f"'{block or target}'")
+        out = torch.empty((self.graph.n_nodes, p), dtype=torch.float32, device=self.workspace.device)
+        check(self.lib.pet_train_predict(self.model.handle, self.graph.handle, _ptr(self.workspace), self.nbytes, tname,
+                                         readout_layer, bname, _ptr(out), _stream()))
+        return out
+
+    def train_predict_backward(self, target: str, grad_atomic: Dict[str, torch.Tensor], readout_layer: int = 0,
+                               seed_features=None):
+        """Adjoint of :meth:`train_predict` for some blocks of one target (``{block: dL/d(prediction) [N, P]}``,
+        ``pet_train_predict_backward``): ADDS dL/dtheta of the target's heads and of those blocks' last layers to the
+        gradient slots, and ADDS the adjoints of the heads' inputs to ``seed_features = (node [N, d_node], edge [E, d_pet])``
+        (zeros when None), which it returns for :meth:`backward_train` / :meth:`backward_train2`."""
+        if not self.train:
+            raise PetHipError("train_predict_backward needs HipForward(..., train=True)")
+        g = self.graph
+        dev = self.workspace.device
+        if seed_features is None:
+            seed_features = (torch.zeros((g.n_nodes, self.model.hypers["d_node"]), dtype=torch.float32, device=dev),
+                             torch.zeros((g.n_edges, self.model.hypers["d_pet"]), dtype=torch.float32, device=dev))
+        names = [_head_names(self.model, target, b, readout_layer == 0) for b in grad_atomic]
+        seeds = [t.detach().to(dev, torch.float32).reshape(g.n_nodes, -1).contiguous() for t in grad_atomic.values()]
+        nb = len(seeds)
+        blocks = (c_char_p * nb)(*[b for _, b in names])
+        ptrs = (c_void_p * nb)(*[t.data_ptr() for t in seeds])
+        check(self.lib.pet_train_predict_backward(self.model.handle, g.handle, _ptr(self.workspace), self.nbytes,
+                                                  names[0][0], readout_layer, nb, blocks, ptrs, _ptr(seed_features[0]),
+                                                  _ptr(seed_features[1]), _stream()))
+        return seed_features
+
+    @staticmethod
+    def _seed_lists(seed_features):
+        if seed_features is None:
+            return None, None, 0
+        node, edge = seed_features
+        node = node if isinstance(node, (list, tuple)) else [node]
+        edge = edge if isinstance(edge, (list, tuple)) else [edge]
+        n = len(node)
+        return ((c_void_p * n)(*[0 if t is None else t.data_ptr() for t in node]),
+                (c_void_p * n)(*[0 if t is None else t.data_ptr() for t in edge]), n)
+
+    def backward_train(self, grad_atomic: Optional[torch.Tensor], want_position_grad: bool = False,
+                       want_cell_grad: bool = False, seed_features=None):
         """loss.backward() for dL/d(atomic prediction) = ``grad_atomic``: accumulates dL/dtheta into
-        the model's gradient slots (``HipModel.grad``); optionally also returns dL/dR."""
+        the model's gradient slots (``HipModel.grad``); optionally also returns dL/dR. ``seed_features``: the feature
+        adjoints of further targets (:meth:`train_predict_backward`), which this one backbone sweep serves too;
+        ``grad_atomic`` may then be None (no fused target in the loss)."""
         if not self.train:
             raise PetHipError("backward_train needs HipForward(..., train=True)")
         self._check_conditioning_for_training()
         g = self.graph
-        _require_cuda(grad_atomic)
-        ga = grad_atomic.to(torch.float32).contiguous()
+        ga = None
+        if grad_atomic is not None:
+            _require_cuda(grad_atomic)
+            ga = grad_atomic.to(torch.float32).contiguous()
         dev = self.workspace.device
         gpos = torch.empty((g.n_nodes, 3), dtype=torch.float32, device=dev) if want_position_grad or want_cell_grad else None
         gcell = torch.empty((g.n_systems, 3, 3), dtype=torch.float32, device=dev) if want_cell_grad else None
-        check(self.lib.pet_backward_train(self.model.handle, g.handle, _ptr(self.workspace), self.nbytes,
-                                          _ptr(ga), _ptr(gpos), _ptr(gcell), _stream()))
+        if seed_features is None:
+            check(self.lib.pet_backward_train(self.model.handle, g.handle, _ptr(self.workspace), self.nbytes,
+                                              _ptr(ga), _ptr(gpos), _ptr(gcell), _stream()))
+        else:
+            pn, pe, n_l = self._seed_lists(seed_features)
+            check(self.lib.pet_backward_train_seeded(self.model.handle, g.handle, _ptr(self.workspace), self.nbytes,
+                                                     _ptr(ga), _ptr(gpos), _ptr(gcell), pn, pe, n_l, _stream()))
         if want_cell_grad:
             return gpos, gcell
         return gpos
 
     def backward_train2(self, lambda_atomic: torch.Tensor, nu_atomic: Optional[torch.Tensor], u: torch.Tensor,
-                        want_tangent: bool = False, u_cell: Optional[torch.Tensor] = None):
+                        want_tangent: bool = False, u_cell: Optional[torch.Tensor] = None, seed_features=None):
         """Second-order reverse pass (loss on dE/dR, and with ``u_cell`` [S,3,3] on dE/dcell: the stress term):
         accumulates d/dtheta [ sum_i nu_i E_i + <u, dE/dR> + <u_cell, dE/dcell> ] where the gradients were taken with
         seeds ``lambda_atomic``; optionally returns dE_i/d(eps) along (dR, dcell) = (u, u_cell)."""
@@ -576,9 +663,15 @@ class HipForward:
         uu = u.to(torch.float32).contiguous()
         tan = torch.empty(g.n_nodes, dtype=torch.float32, device=dev) if want_tangent else None
         uc = None if u_cell is None else u_cell.to(dev, torch.float32).reshape(g.n_systems, 3, 3).contiguous()
-        check(self.lib.pet_backward_train2_cell(self.model.handle, g.handle, _ptr(self.workspace), self.nbytes,
-                                                _ptr(self.workspace2), self.workspace2.numel(), _ptr(la), _ptr(nu),
-                                                _ptr(uu), _ptr(uc), _ptr(tan), _stream()))
+        if seed_features is None:
+            check(self.lib.pet_backward_train2_cell(self.model.handle, g.handle, _ptr(self.workspace), self.nbytes,
+                                                    _ptr(self.workspace2), self.workspace2.numel(), _ptr(la), _ptr(nu),
+                                                    _ptr(uu), _ptr(uc), _ptr(tan), _stream()))
+        else:  # further targets' feature adjoints join the first-order adjoint nu (train_predict_backward)
+            pn, pe, n_l = self._seed_lists(seed_features)
+            check(self.lib.pet_backward_train2_seeded(self.model.handle, g.handle, _ptr(self.workspace), self.nbytes,
+                                                      _ptr(self.workspace2), self.workspace2.numel(), _ptr(la), _ptr(nu),
+                                                      _ptr(uu), _ptr(uc), _ptr(tan), pn, pe, n_l, _stream()))
         return tan
 
     def sum_over_atoms(self, atomic: torch.Tensor) -> torch.Tensor:

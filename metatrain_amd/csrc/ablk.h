@@ -231,6 +231,30 @@ __device__ __forceinline__ void ab_key_bias(float (&bias)[NQ][16], const AbAtom&
         }
 }
 
+// a float at a WAVE-UNIFORM address through the scalar cache. Read through the constant address space (the vectors read this way
+// -- biases, norm weights -- are not written while a kernel runs), because only there is a uniform load an s_load whatever
+// the compiler can prove about the kernel's stores: inside the stage loops it otherwise makes vector loads of them, which queue
+// behind the ring requests (vmcnt retires in order) and whose waits drain the whole ring at every chunk.
+typedef const float __attribute__((address_space(4)))* ab_const_ptr;
+__device__ __forceinline__ float ab_sload(const float* p) {
+#ifdef AB_ABL_NOSLOAD  // A/B: the plain load the compiler is free to make a vector load of
+    return *p;
+#else
+    return *reinterpret_cast<ab_const_ptr>(reinterpret_cast<uintptr_t>(p));
+#endif
+}
+
+// accumulator tile initialised with 4096 x bias (wave-uniform b), the bias read through the SCALAR cache: both halves of a column
+// group, selected by lane half. For the stage loops of the ring kernels, where a vector load would queue behind the ring requests.
+__device__ __forceinline__ void ab_bias_tile_s(f32x16& acc, const float* __restrict__ b, int h) {
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float lo = ab_sload(b + 8 * j + i), hi = ab_sload(b + 8 * j + 4 + i);
+            acc[4 * j + i] = (h ? hi : lo) * ABQ;
+        }
+}
 // accumulators of a token-form tile initialised with 4096 x bias (features 8 j + 4 h .. + 3 of the tile at b)
 __device__ __forceinline__ void ab_bias_tile(f32x16& acc, const float* __restrict__ b, int h) {
 #pragma unroll
@@ -255,6 +279,42 @@ __device__ __forceinline__ void ab_dma_piece(const f16x8* plane, int idx, unsign
         __syncthreads();                                  \
     } while (0)
 #endif
+
+// ---- the shared weight ring of the four-wave kernels, read ONE STAGE AHEAD (k_emlp_s, k_ablk_fwd4).
+// Four 4-KB slots; a stage is four 1-KB fragments, one brought by each wave, all four read by every wave. The fragments of
+// stage g + 1 are read into registers DURING stage g, so no wave starts a stage with an LDS round trip behind its barrier:
+//   prologue     request stages 0 .. 3; RING_PRIME: own fragment of stage 0 landed, barrier, read stage 0 -> nx
+//   stage g      sync: own fragment of stage g + 1 landed (vmcnt(2): g + 2, g + 3 stay in flight), lgkmcnt(0) (this wave's
+//                reads of stage g, issued during g - 1, have returned), barrier: stage g + 1 is complete for everybody and
+//                everybody holds stage g in registers;
+//                ring_turn: request g + 4 into the slot of g, cur = nx, read stage g + 1 -> nx;  the stage's MFMAs on cur
+// A slot is re-requested only after the reads of its previous contents have returned, as before; the counts at a sync are
+// those of the schedule that read a stage behind its own barrier (requested three ahead), moved by one stage.
+constexpr int RING_SLOT = 4096, RING_NSLOT = 4;
+struct RingFrag {
+    f16x8 f[4];
+};
+__device__ __forceinline__ void ring_read(RingFrag& d, const char* ring, int g, unsigned lane16) {  // (g: only g mod 4 matters)
+    const char* slot = ring + (g & (RING_NSLOT - 1)) * RING_SLOT + lane16;
+#pragma unroll
+    for (int i = 0; i < 4; i++) d.f[i] = *reinterpret_cast<const f16x8*>(slot + i * 1024);
+}
+// behind the sync of stage g (req(n): this wave's request of stage n, clamped to the stream's last stage; more: stage g + 1
+// exists -- reading past the end is harmless, the slot holds a landed older stage, but it is four reads for nothing)
+template <class Req>
+__device__ __forceinline__ void ring_turn(RingFrag& cur, RingFrag& nx, int g, bool more, Req req, const char* ring,
+                                          unsigned lane16) {
+    req(g + 4);
+    cur = nx;
+    if (more) ring_read(nx, ring, g + 1, lane16);
+    __builtin_amdgcn_sched_barrier(0);  // the reads go out HERE, in front of the stage's MFMAs (the scheduler otherwise sinks them to the next sync)
+}
+#define RING_PRIME(nx, ring, lane16)                                      \
+    do {                                                                  \
+        asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");       \
+        __syncthreads();                                                  \
+        ring_read((nx), (ring), 0, (lane16));                             \
+    } while (0)
 
 struct AbSel {
     f16x8 i0, i1;  // selection matrices of the two K blocks of a 32-wide tile, B-operand form

@@ -302,7 +302,7 @@ __global__ __launch_bounds__(256) void k_ablk_fwd(
 // one eight-wave workgroup. In k_ablk_fwd the eight waves meet at every stage barrier, so the two waves of a SIMD run their
 // matrix phases and their vector phases at the same time; two independent workgroups drift apart and fill each other's
 // stalls (what made k_emlp_s faster than k_emlp_p2, pet_emlp_s.hip). Each workgroup has its own weight ring: four slots
-// of four fragments (one per wave and stage), requested three stages ahead:
+// of four fragments (one per wave and stage), requested four stages ahead and read one stage ahead (ablk.h ring_turn):
 //   stage g = 12 hp + r (r = 0 .. 11): fragments 4 r .. 4 r + 3 of the head pair's 48 = [K block kb][Qh Ql Kh Kl Vh Vl]
 //                                       (r % 3 = 0: Q, K of kb = 2 (r / 3); 1: V of that kb, Q of the next; 2: K, V of the next)
 //   stage g = 48 + n (n = 0 .. 15):     W_o step n (c = n / 8, kb = n % 8): tiles 2 c, 2 c + 1 x (h, l)
@@ -346,6 +346,10 @@ __global__ __launch_bounds__(256, 2) void k_ablk_fwd4(
     const char* ring = ab_smem + NW * 16384;
     const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);
     const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+    float bvq[4];  // V's bias of this lane's token-form column, all four head pairs (a per-lane load: it must not sit in the ring's queue)
+#pragma unroll
+    for (int hp = 0; hp < 4; hp++) bvq[hp] = bqkv[2 * D + 32 * hp + L.r] * ABQ;
+    asm volatile("" ::"v"(bvq[0]), "v"(bvq[1]), "v"(bvq[2]), "v"(bvq[3]));
     float bias[1][16];
     ab_key_bias<1>(bias, a, fc, L);  // (its loads are consumed before the requests below: nothing but fragments in the queue)
     asm volatile("" ::"v"(bias[0][0]), "v"(bias[0][15]));
@@ -353,7 +357,8 @@ __global__ __launch_bounds__(256, 2) void k_ablk_fwd4(
     ab4_request(0, wqkv, wo, ring_u, wave, lane16);
     ab4_request(1, wqkv, wo, ring_u, wave, lane16);
     ab4_request(2, wqkv, wo, ring_u, wave, lane16);
-    asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // the rows
+    ab4_request(3, wqkv, wo, ring_u, wave, lane16);
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // the rows
     {
         float4 x[16];
         tile128_to_frag(x, tile, L);
@@ -365,29 +370,26 @@ __global__ __launch_bounds__(256, 2) void k_ablk_fwd4(
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
 
+    const auto req = [&](int g) { ab4_request(g, wqkv, wo, ring_u, wave, lane16); };
+    RingFrag w, wn;  // the fragments of the stage at work, of the stage after it (ablk.h: the ring read one stage ahead)
+    RING_PRIME(wn, ring, lane16);
     f16x8 aoh[8], aol[8];  // attention output: planes of the row fragment, K block = head
 #pragma unroll
     for (int hp = 0; hp < 4; hp++) {
         f32x16 q, k, v;
         {
-            const float bv = bqkv[2 * D + 32 * hp + L.r] * ABQ;
-            ab_bias_tile(q, bqkv + 32 * hp, L.h);
-            ab_bias_tile(k, bqkv + D + 32 * hp, L.h);
+            ab_bias_tile_s(q, bqkv + 32 * hp, L.h);  // (scalar loads: no vector load between two stages of the ring)
+            ab_bias_tile_s(k, bqkv + D + 32 * hp, L.h);
 #pragma unroll
-            for (int i = 0; i < 16; i++) v[i] = bv;
+            for (int i = 0; i < 16; i++) v[i] = bvq[hp];
         }
-        asm volatile("" ::"v"(q[0]), "v"(k[0]), "v"(v[0]));  // the bias loads are consumed before the stage waits
         f16x8 xh, xl;
 #pragma unroll
         for (int r = 0; r < 12; r++) {
             const int g = 12 * hp + r;
             AB4_STAGE_SYNC();
-            ab4_request(g + 3, wqkv, wo, ring_u, wave, lane16);
-            const char* slot = ring + (g & (AB4_NSLOT - 1)) * AB4_SLOT + lane16;
-            const f16x8 f0 = *reinterpret_cast<const f16x8*>(slot + 0 * 1024);
-            const f16x8 f1 = *reinterpret_cast<const f16x8*>(slot + 1 * 1024);
-            const f16x8 f2 = *reinterpret_cast<const f16x8*>(slot + 2 * 1024);
-            const f16x8 f3 = *reinterpret_cast<const f16x8*>(slot + 3 * 1024);
+            ring_turn(w, wn, g, true, req, ring, lane16);
+            const f16x8 &f0 = w.f[0], &f1 = w.f[1], &f2 = w.f[2], &f3 = w.f[3];
             const int m = r / 3;
             if (r % 3 == 0) {  // Q, K of K block 2 m
                 xh = *reinterpret_cast<const f16x8*>(tile + (((2 * m) * 2 + 0) * 64 + L.lane) * 16);
@@ -468,14 +470,9 @@ __global__ __launch_bounds__(256, 2) void k_ablk_fwd4(
     for (int n = 0; n < 16; n++) {
         const int g = 48 + n, c = n >> 3, kb = n & 7;
         AB4_STAGE_SYNC();
-        ab4_request(g + 3, wqkv, wo, ring_u, wave, lane16);
-        const char* slot = ring + (g & (AB4_NSLOT - 1)) * AB4_SLOT + lane16;
+        ring_turn(w, wn, g, g + 1 < AB4_NSTAGE, req, ring, lane16);
 #pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const f16x8 wh = *reinterpret_cast<const f16x8*>(slot + (2 * t) * 1024);
-            const f16x8 wl = *reinterpret_cast<const f16x8*>(slot + (2 * t + 1) * 1024);
-            AB_MFMA3(y[c][t], wh, wl, aoh[kb], aol[kb]);
-        }
+        for (int t = 0; t < 2; t++) AB_MFMA3(y[c][t], w.f[2 * t], w.f[2 * t + 1], aoh[kb], aol[kb]);
     }
     // ---- bias is in, residual, whole-line stores: X1 = X + Wo AO + bo (edge rows); OC = Wo AO + bo (the centre token)
     __builtin_amdgcn_wave_barrier();

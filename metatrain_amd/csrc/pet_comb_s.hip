@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void k_comb_s(const float* __restrict__ XF,
 #pragma unroll
         for (int j = 0; j < 4; j++)
 #pragma unroll
-            for (int i = 0; i < 4; i++) aa[4 * j + i] = hs_vec(b0 + 32 * hc, 0, j, i, L.h) * ABQ;
+            for (int i = 0; i < 4; i++) aa[4 * j + i] = hs_vec_s(b0 + 32 * hc, 0, j, i, L.h) * ABQ;
 #pragma unroll
         for (int s = 0; s < 8; s++) {
             CB_STAGE_SYNC(false);

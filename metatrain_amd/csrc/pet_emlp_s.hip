@@ -10,7 +10,8 @@
 // SIMD were in their matrix phase or in their vector phase at the same time -- SQ_VALU_MFMA_COEXEC_CYCLES 875 per wave against
 // 5 600 in k_emlp_p2 -- and it ran no faster than k_emlp_p2). The four waves of a workgroup share ONE stream of weight fragments
 // through a four-slot LDS ring (each weight byte is fetched once per four row tiles instead of once per tile), requested
-// three stages ahead (an LDS-DMA request takes ~1 us to land; a stage is 6 MFMAs per wave).
+// three stages ahead (an LDS-DMA request takes ~1 us to land; a stage is 6 MFMAs per wave); the forward reads its fragments one
+// stage ahead of the stage that uses them and requests four ahead (ablk.h ring_turn).
 //
 //   rows      32 per wave, LDS-DMA; residual + output bias = initial value of the out accumulators; RMSNorm / LayerNorm;
 //             planes of 64 xn parked over the rows
@@ -48,15 +49,18 @@ __device__ __forceinline__ void es_request(int hc, int s, const W2& win, const W
         ab_dma_piece((wave & 1) ? wout.l : wout.h, t * (DFF / 16) + 2 * hc + kb2, lane16, dst);
     }
 }
-// this wave's fragment of the stage has landed (everything but its fragments of the two stages requested after it), then
-// the workgroup barrier: the stage is complete for everybody, and everybody is done with the stage before it
+// ES_STAGE_SYNC: this wave's fragment of the stage it waits for has landed (everything but its fragments of the two stages
+// requested after it) and its own fragment reads have returned, then the workgroup barrier. k_emlp_bwd_s reads a stage behind
+// the stage's own sync (requests three ahead: the stage waited for is the one about to be consumed); k_emlp_s reads one stage
+// ahead (ablk.h ring_turn, requests four ahead: the stage waited for is the NEXT one) -- the counts are the same.
 #ifdef AB_ABL_NOBAR
 #define ES_BARRIER()
 #else
 #define ES_BARRIER() __syncthreads()
 #endif
-// (vmcnt retires in order, stores included: behind the chunk's eight [v; g] store instructions -- issued between the requests of stages 12 hc + 10 and 12 hc + 11 -- the
-// count is 2 + 8 for the three stages whose fragments were requested before them and are waited for after them: 12 hc + 8 .. + 10)
+// (vmcnt retires in order, stores included: behind the chunk's eight [v; g] store instructions -- issued between the requests of stages 12 hc + 11 and 12 hc + 12 -- the
+// count is 2 + 8 for the three stages whose fragments were requested before them and are waited for after them: 12 hc + 9 .. + 11,
+// at the syncs of stages 12 hc + 8 .. + 10)
 #define ES_STAGE_SYNC(AFTER_STORES)                                           \
     do {                                                                      \
         if ((AFTER_STORES) && !full) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   /* a partial tile skips store instructions */ \
@@ -64,17 +68,9 @@ __device__ __forceinline__ void es_request(int hc, int s, const W2& win, const W
         else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");                 \
         ES_BARRIER();                                                         \
     } while (0)
-// accumulator tile initialised with 4096 x bias, the bias read through the SCALAR cache (wave-uniform addresses, both halves
-// of a column group, selected by lane half): a vector load here would sit in the in-order vmcnt queue behind the ring requests
-__device__ __forceinline__ void es_bias_tile(f32x16& acc, const float* __restrict__ b, int h) {
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const float lo = b[8 * j + i], hi = b[8 * j + 4 + i];
-            acc[4 * j + i] = (h ? hi : lo) * ABQ;
-        }
-}
+// accumulator tile initialised with 4096 x bias through the SCALAR cache (ablk.h ab_bias_tile_s): a vector load here would sit in
+// the in-order vmcnt queue behind the ring requests
+__device__ __forceinline__ void es_bias_tile(f32x16& acc, const float* __restrict__ b, int h) { ab_bias_tile_s(acc, b, h); }
 
 template <bool LN>
 __global__ __launch_bounds__(256, 2) void k_emlp_s(const float* __restrict__ X1, const float* __restrict__ gamma,
@@ -96,7 +92,8 @@ __global__ __launch_bounds__(256, 2) void k_emlp_s(const float* __restrict__ X1,
     es_request(0, 0, win, wout, ring_u, wave, lane16);
     es_request(0, 1, win, wout, ring_u, wave, lane16);
     es_request(0, 2, win, wout, ring_u, wave, lane16);
-    asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // the rows (the three ring requests may still be in flight)
+    es_request(0, 3, win, wout, ring_u, wave, lane16);
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");  // the rows (the four ring requests may still be in flight)
     f32x16 out[4];
     f16x8 xph[8], xpl[8];
     {
@@ -124,24 +121,21 @@ __global__ __launch_bounds__(256, 2) void k_emlp_s(const float* __restrict__ X1,
     float* const otile = reinterpret_cast<float*>(tile);  // [32][TILE32_LD] staging (trr.h store_tile32_lines)
     const bool full = row0 + WROWS <= E;        // every row of the tile exists: each store instruction has active lanes
     const bool stores = VG != nullptr && live;  // wave-uniform: the chunk's eight store instructions are issued
+    RingFrag w, wn;  // the fragments of the stage at work, of the stage after it (ablk.h: the ring read one stage ahead)
+    RING_PRIME(wn, ring, lane16);
 
 #pragma unroll 1
     for (int hc = 0; hc < DFF / 32; hc++) {
+        const auto req = [&](int s) { es_request(hc, s, win, wout, ring_u, wave, lane16); };
         f32x16 va, ga;
         es_bias_tile(va, bin + 32 * hc, L.h);
         es_bias_tile(ga, bin + DFF + 32 * hc, L.h);
 #pragma unroll
         for (int s = 0; s < 8; s++) {
-            const int g = ES_SPC * hc + s;
             ES_STAGE_SYNC(false);
-            es_request(hc, s + 3, win, wout, ring_u, wave, lane16);
-            const char* slot = ring + (g & (ES_NSLOT - 1)) * ES_SLOT + lane16;
-            const f16x8 wvh = *reinterpret_cast<const f16x8*>(slot + 0 * 1024);
-            const f16x8 wvl = *reinterpret_cast<const f16x8*>(slot + 1 * 1024);
-            const f16x8 wgh = *reinterpret_cast<const f16x8*>(slot + 2 * 1024);
-            const f16x8 wgl = *reinterpret_cast<const f16x8*>(slot + 3 * 1024);
-            AB_MFMA3(va, wvh, wvl, xph[s], xpl[s]);
-            AB_MFMA3(ga, wgh, wgl, xph[s], xpl[s]);
+            ring_turn(w, wn, s, true, req, ring, lane16);  // (12 hc is a multiple of the slot count)
+            AB_MFMA3(va, w.f[0], w.f[1], xph[s], xpl[s]);
+            AB_MFMA3(ga, w.f[2], w.f[3], xph[s], xpl[s]);
         }
         // pre-activations, saved for the adjoint; u = v sigmoid(g) (transformer.py:42-43) as planes at scale 1
         f32x16 u;
@@ -164,17 +158,11 @@ __global__ __launch_bounds__(256, 2) void k_emlp_s(const float* __restrict__ X1,
         ab_tile_planes(u, uh, ul);
 #pragma unroll
         for (int s = 8; s < 12; s++) {
-            const int g = ES_SPC * hc + s;
-            ES_STAGE_SYNC(s < 11 && stores);  // (the fragments of stages 8 .. 10 were requested before the stores)
-            es_request(hc, s + 3, win, wout, ring_u, wave, lane16);
-            const char* slot = ring + (g & (ES_NSLOT - 1)) * ES_SLOT + lane16;
+            ES_STAGE_SYNC(s < 11 && stores);  // (the fragments of stages 9 .. 11 were requested before the stores)
+            ring_turn(w, wn, s, true, req, ring, lane16);  // (behind the stream's last stage: a landed older stage, unused)
             const int kb2 = (s - 8) >> 1, th = (s - 8) & 1;
 #pragma unroll
-            for (int t = 0; t < 2; t++) {
-                const f16x8 wh = *reinterpret_cast<const f16x8*>(slot + (2 * t) * 1024);
-                const f16x8 wl = *reinterpret_cast<const f16x8*>(slot + (2 * t + 1) * 1024);
-                AB_MFMA3(out[2 * th + t], wh, wl, uh[kb2], ul[kb2]);
-            }
+            for (int t = 0; t < 2; t++) AB_MFMA3(out[2 * th + t], w.f[2 * t], w.f[2 * t + 1], uh[kb2], ul[kb2]);
         }
     }
     // ---- X2 = out / 64: whole lines through the wave's own tile (the planes are dead)

@@ -53,5 +53,11 @@ __device__ __forceinline__ float hs_vec(const float* __restrict__ v, int t, int 
     const float lo = v[32 * t + 8 * j + i], hi = v[32 * t + 8 * j + 4 + i];
     return h ? hi : lo;
 }
+// the same for a vector whose address changes inside a stage loop (v + 32 hc): the compiler makes VECTOR loads of those, which queue
+// behind the ring requests and drain the ring when they are waited for; ablk.h ab_sload keeps them in the scalar cache
+__device__ __forceinline__ float hs_vec_s(const float* __restrict__ v, int t, int j, int i, int h) {
+    const float lo = ab_sload(v + 32 * t + 8 * j + i), hi = ab_sload(v + 32 * t + 8 * j + 4 + i);
+    return h ? hi : lo;
+}
 
 }  // namespace pet

@@ -409,15 +409,20 @@ int pet_backward_train2_cell(const pet_model_t* m, const pet_graph_t* g, void* d
  *   2. pet_train_predict_backward: for the seeds d_grad_atomic[b] = dL/d(prediction of blocks[b]) [N, P_b] of some blocks
  *      of one target, ADDS dL/dtheta of the target's heads (recomputed once for all its blocks) and of those blocks' last
  *      layers to the gradient slots, and ADDS the adjoints of the heads' inputs to d_seed_node_features [N, d_node] and
- *      d_seed_edge_features [E, d_pet] (CSR rows; either may be NULL). Frozen parameters are skipped.
+ *      d_seed_edge_features [E, d_pet] (CSR rows; either may be NULL). Frozen parameters get no gradient (the tuned
+ *      pass skips them; the size-generic pass clears their slots when the seeded call of step 3 returns).
  *   3. pet_backward_train_seeded / pet_backward_train2_seeded: pet_backward_train / pet_backward_train2_cell with the
  *      summed seeds of step 2 (h_seed_*_features: host arrays of n_layers device pointers, one per readout layer, NULL
  *      entries = 0; n_layers = 0: none) added where the fused head's adjoint enters the backbone (the second-order pass:
  *      its first-order adjoint only; these targets do not enter dE/dR). pet_backward_train_seeded takes
  *      d_grad_atomic = NULL when the loss has no fused target (a model loaded without one trains this way). The seeds
  *      carry no cutoff-factor adjoint, so pet_backward_train_seeded refuses d_grad_positions / d_grad_cells with seeds.
- * Default model size, PreLN + feedforward featuriser, graphs with edges and at most 127 neighbours per atom; elsewhere
- * PET_ERR_UNSUPPORTED. pet_backward_train / pet_backward_train2_cell are the seeded calls with no seed. */
+ * Every model and graph that trains: the tuned pass, and the size-generic pass (other sizes, PostLN, the residual
+ * featuriser, an atom with more than 127 neighbours, a batch without any edge). readout_layer < the model's number of
+ * readout layers (pet_model_num_readout_layers; the residual featuriser has one per GNN layer): the prediction of a block
+ * is the SUM over the readout layers of pet_train_predict, so one dL/d(prediction) seeds every layer, step 2 runs once per
+ * layer into that layer's seed pair, and step 3 takes n_layers = the number of readout layers (any other count but 0 is
+ * PET_ERR_ARGUMENT). pet_backward_train / pet_backward_train2_cell are the seeded calls with no seed. */
 int pet_train_predict(const pet_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,
                       const char* target, int32_t readout_layer, const char* block, float* d_atomic, void* stream);
 int pet_train_predict_backward(const pet_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,

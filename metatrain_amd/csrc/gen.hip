@@ -501,6 +501,21 @@ int gen_backward_predict(const Model& m, const Graph& g, void* ws, int64_t ws_by
     return rc;
 }
 
+// prediction of one (target, readout layer, block) of a training step from the features the forward left in the workspace
+// (pet_train_predict): the readout layer's node features, and its edge features -- the last layer's messages, or with the
+// residual featuriser the layer's own edge tokens
+int gen_train_predict(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, const HeadW& H, const LastW& Lw,
+                      float* atomic, hipStream_t st) {
+    GWs w;
+    gen_carve(m, g.n_nodes, g.n_edges, ws, w);
+    PET_REQUIRE((int64_t)w.bytes <= ws_bytes, PET_ERR_ARGUMENT, "workspace too small for training");
+    PET_REQUIRE(layer >= 0 && layer < m.num_readout_layers(), PET_ERR_ARGUMENT, "readout layer out of range");
+    if (g.n_nodes == 0) return PET_OK;
+    const bool res = m.residual();
+    const GGnn& Bl = res ? w.gnn[layer] : w.gnn.back();
+    return gen_predict(m, g, H, Lw, Bl.Hout, res ? Bl.XF : Bl.Mout, g.fc, atomic, nullptr, nullptr, st);
+}
+
 int gen_backward_geometry(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* g_geo, const float* g_fc,
                           float* gpos, float* gcell, hipStream_t st) {
     GWs w;

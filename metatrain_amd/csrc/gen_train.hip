@@ -510,6 +510,28 @@ __global__ void k_gt_seeds(const float* __restrict__ nA, const float* __restrict
     }
 }
 
+// further targets (first order, P properties): the seed rows of one block's last layer and their way back to the head MLP's
+// output. Row r is an atom (ctr, fc null) or an edge: dY[r][p] = fc_r gA[ctr_r][p] (the cutoff factor of the atom sum, the
+// centre's seed), dS[r][c] (+)= sum_p dY[r][p] W[p][c]. One launch per block, in block order: the hidden adjoint of the
+// head MLP the blocks share is their sum in that fixed order.
+__global__ void k_gt_last_rev(const float* __restrict__ gA, const int* __restrict__ ctr, const float* __restrict__ fc,
+                              const float* __restrict__ W, int P, int DH, int64_t rows, float* __restrict__ dY,
+                              float* __restrict__ dS, int acc) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= rows * DH) return;
+    const int64_t r = idx / DH;
+    const int c = (int)(idx % DH);
+    const int64_t i = ctr ? (int64_t)ctr[r] : r;
+    const float f = fc ? fc[r] : 1.f;
+    float s = 0.f;
+    for (int p = 0; p < P; p++) {
+        const float v = f * gA[i * P + p];
+        s = fmaf(v, W[(int64_t)p * DH + c], s);
+        if (dY && c == 0) dY[r * P + p] = v;
+    }
+    dS[idx] = acc ? dS[idx] + s : s;
+}
+
 // ---------------------------------------------------------------------------------------------
 // workspace of the pass
 // ---------------------------------------------------------------------------------------------
@@ -822,9 +844,22 @@ int64_t gen_train_workspace_bytes(const Model& m, int64_t N, int64_t E) {
 
 // dL/d theta of J = sum_i (nu_i e_i + lambda_i e'_i) ADDED to the flat gradient; tangent_atomic [N] = e'_i (optional).
 // nA / lA may be null (zero). u null = no tangent (energy-only loss).
+// seed_node / seed_edge [n_seed] (NULL entries = 0): feature adjoints of further targets (gen_train_predict_backward), one
+// pair per readout layer, added to the nu half where the fused head's adjoint enters the backbone (first-order terms: the
+// lambda half is theirs no more than a tangent is). lA and nA both null: no fused target in the loss, its heads are
+// neither needed nor touched.
 int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, const float* lA, const float* nA, const float* u,
-               const float* ucell, float* tangent_atomic, hipStream_t st) {
+               const float* ucell, float* tangent_atomic, hipStream_t st, const float* const* seed_node,
+               const float* const* seed_edge, int n_seed) {
     PET_REQUIRE(m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
+    PET_REQUIRE(n_seed == 0 || n_seed == m.num_readout_layers(), PET_ERR_ARGUMENT, "expected one seed pair per readout layer");
+    const bool fused = lA || nA;
+    if (!fused) {
+        if (tangent_atomic && g.n_nodes > 0) PET_HIP_CHECK(hipMemsetAsync(tangent_atomic, 0, g.n_nodes * sizeof(float), st));
+        bool seeded = false;
+        for (int l = 0; l < n_seed; l++) seeded = seeded || (seed_node && seed_node[l]) || (seed_edge && seed_edge[l]);
+        if (!seeded || !backbone_trainable(m)) return PET_OK;  // nothing enters the backbone / only heads and last layers train
+    }
     const bool conditioned = m.h.system_conditioning != 0;
     if (conditioned)
         PET_REQUIRE(g.cond_charge && g.n_cond_systems >= 1 && g.n_cond_systems <= g.n_nodes, PET_ERR_ARGUMENT,
@@ -845,7 +880,7 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
     // the heads of the trained target, one per readout layer ("@": runtime.HipModel.load)
     std::vector<const HeadW*> heads(NR);
     std::vector<const LastW*> lasts(NR);
-    for (int l = 0; l < NR; l++) {
+    for (int l = 0; fused && l < NR; l++) {
         auto hi = m.heads.find("@|" + std::to_string(l));
         auto li = m.lasts.find("@|" + std::to_string(l) + "|@");
         PET_REQUIRE(hi != m.heads.end() && li != m.lasts.end() && li->second.P == 1, PET_ERR_ARGUMENT,
@@ -992,8 +1027,12 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
             dMl[l] = D2{ex, ex + E * D}; ex += 2 * E * D;
         } else { dHl[l] = w.dH; dMl[l] = w.dM; }
     }
-    k_gt_seeds<<<g1(R), 256, 0, st>>>(nA, lA, g.ctr, g.fc, w.fcd, nnp.p, nnp.t, nep.p, nep.t, N, E);
-    for (int l = 0; l < NR; l++) {
+    if (fused) k_gt_seeds<<<g1(R), 256, 0, st>>>(nA, lA, g.ctr, g.fc, w.fcd, nnp.p, nnp.t, nep.p, nep.t, N, E);
+    for (int l = 0; !fused && l < NR; l++) {   // no fused head: the further targets' seeds are all that enters
+        t.zero(dHl[l], N * DN);
+        t.zero(dMl[l], E * D);
+    }
+    for (int l = 0; fused && l < NR; l++) {
         const TGnn& Bl = res ? w.gnn[l] : w.gnn.back();
         const D2 Hf = Bl.Hout, Mf = res ? Bl.XF : Bl.Mout;
         const HeadW& H = *heads[l];
@@ -1026,6 +1065,10 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
         if (E > 0) k_gt_silu_rev<<<g1(E * DH), 256, 0, st>>>(w.tE[0].p, w.tE[0].t, w.tE[1].p, w.tE[1].t, w.tE[1].p, w.tE[1].t, E * DH);
         t.wgrad(H.eh0, w.tE[1], DH, Mf, D, E);
         t.linb(w.tE[1], DH, H.eh0, dMl[l], D, E);
+    }
+    for (int l = 0; l < n_seed; l++) {
+        if (seed_node && seed_node[l]) t.o.axpby(1.f, seed_node[l], DN, 0.f, nullptr, 0, nullptr, dHl[l].p, DN, true, N, DN);
+        if (seed_edge && seed_edge[l]) t.o.axpby(1.f, seed_edge[l], D, 0.f, nullptr, 0, nullptr, dMl[l].p, D, true, E, D);
     }
     // ---------------- sweep 2: joint reverse through the backbone ----------------
     if (res) t.zero(w.dM, E * D);   // the last layer's messages are never read
@@ -1168,6 +1211,71 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
                                                                   m.h.max_charge, m.h.max_spin_multiplicity, DN, gq, gm, gw0,
                                                                   gb0, gw2, gb2);
     }
+    PET_HIP_CHECK(hipGetLastError());
+    return t.err;
+}
+
+// Adjoint of gen_train_predict for `n_blocks` blocks of one (target, readout layer), seeds gA[b] [N, P_b]: dL/dtheta of the
+// blocks' last layers and of the two head MLPs ADDED to the gradient slots (through TOps' pointer-to-slot map: a LoRA-adapted
+// Linear receives dL/dW_eff, a frozen parameter's slot is cleared at the exit of the step's reverse entry point like every
+// other slot of this pass), the adjoints of the heads' inputs ADDED to seed_node [N, d_node] / seed_edge [E, d_pet] (either
+// may be null). The head MLPs run once: their hidden adjoint is the sum over the blocks in block order (k_gt_last_rev).
+// First order: the weight-gradient reductions run without a tangent half. Features are read from the FORWARD workspace.
+int gen_train_predict_backward(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, const HeadW& H,
+                               int n_blocks, const LastW* const* Lw, const float* const* gA, float* seed_node,
+                               float* seed_edge, hipStream_t st) {
+    PET_REQUIRE(m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
+    PET_REQUIRE(layer >= 0 && layer < m.num_readout_layers(), PET_ERR_ARGUMENT, "readout layer out of range");
+    GWs f;
+    gen_carve(m, g.n_nodes, g.n_edges, ws, f);
+    PET_REQUIRE((int64_t)f.bytes <= ws_bytes, PET_ERR_ARGUMENT, "workspace too small for training");
+    const int64_t N = g.n_nodes, E = g.n_edges, M = N > E ? N : E;
+    if (N == 0 || n_blocks == 0) return PET_OK;
+    const GD d = dims_of(m);
+    const int DH = d.DH;
+    int pmax = 1;
+    for (int b = 0; b < n_blocks; b++) pmax = imax(pmax, Lw[b]->P);
+    // a1, s1, a2, s2, ds [rows][DH] | dY [E][P] | partial sums of the largest weight gradient (32 row chunks at most)
+    TWs w;
+    w.part_floats = (size_t)32 * DH * imax(imax(d.DN, d.D), imax(DH, pmax));
+    PoolBuf pool;
+    PET_HIP_CHECK(pool.alloc(((size_t)5 * M * DH + (size_t)(E > 0 ? E : 1) * pmax + w.part_floats) * sizeof(float), st));
+    float* a1 = pool.as<float>();
+    float* s1 = a1 + M * DH;
+    float* a2 = s1 + M * DH;
+    float* s2 = a2 + M * DH;
+    float* ds = s2 + M * DH;
+    float* dY = ds + M * DH;
+    w.part = dY + (size_t)(E > 0 ? E : 1) * pmax;
+    TOps t(m, g, st, &w);
+    auto half = [](const float* p) { return D2{const_cast<float*>(p), nullptr}; };   // first order: no tangent half
+    auto branch = [&](bool edge, const Lin& h0, const Lin& h2, const float* X, int W, int64_t rows, float* seed) {
+        if (rows <= 0) return;
+        t.lin.fwd(X, W, h0, a1, DH, rows);
+        k_gen_silu<<<g1(rows * DH), 256, 0, st>>>(a1, s1, rows * DH);
+        t.lin.fwd(s1, DH, h2, a2, DH, rows);
+        k_gen_silu<<<g1(rows * DH), 256, 0, st>>>(a2, s2, rows * DH);
+        for (int b = 0; b < n_blocks; b++) {
+            Lin ll;
+            ll.w = edge ? Lw[b]->ew : Lw[b]->nw;
+            ll.b = edge ? Lw[b]->eb : Lw[b]->nb;
+            ll.n_out = Lw[b]->P;
+            ll.k_in = DH;
+            k_gt_last_rev<<<g1(rows * DH), 256, 0, st>>>(gA[b], edge ? g.ctr : nullptr, edge ? g.fc : nullptr, ll.w, ll.n_out, DH,
+                                                        rows, edge ? dY : nullptr, ds, b > 0);
+            t.wgrad(ll, half(edge ? dY : gA[b]), ll.n_out, half(s2), DH, rows);
+        }
+        k_gen_silu_bwd<<<g1(rows * DH), 256, 0, st>>>(a2, ds, ds, rows * DH);                  // d a2
+        t.wgrad(h2, half(ds), DH, half(s1), DH, rows);
+        t.lin.bwd(ds, DH, h2, s2, DH, rows);                                                    // d s1
+        k_gen_silu_bwd<<<g1(rows * DH), 256, 0, st>>>(a1, s2, s2, rows * DH);                  // d a1
+        t.wgrad(h0, half(s2), DH, half(X), W, rows);
+        if (seed) t.lin.bwd(s2, DH, h0, seed, W, rows, true);
+    };
+    const bool res = m.residual();
+    const GGnn& Bl = res ? f.gnn[layer] : f.gnn.back();
+    branch(false, H.nh0, H.nh2, Bl.Hout, d.DN, N, seed_node);
+    branch(true, H.eh0, H.eh2, res ? Bl.XF : Bl.Mout, d.D, E, seed_edge);
     PET_HIP_CHECK(hipGetLastError());
     return t.err;
 }

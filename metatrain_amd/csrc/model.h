@@ -155,6 +155,18 @@ struct Model {
     }
 };
 
+// some parameter outside the heads and last layers takes a gradient (false: a reverse pass may stop at the heads)
+inline bool backbone_trainable(const Model& m) {
+    if (m.frozen.empty()) return true;
+    for (const auto& kv : m.grad_off) {
+        const std::string& k = kv.first;
+        const bool head = k.rfind("node_heads.", 0) == 0 || k.rfind("edge_heads.", 0) == 0 ||
+                          k.rfind("node_last_layers.", 0) == 0 || k.rfind("edge_last_layers.", 0) == 0;
+        if (!head && !m.is_frozen(k)) return true;
+    }
+    return false;
+}
+
 // lora.hip: the fold W_eff = W + s B A (finalize), the gradient projection of the reverse entry points, frozen slots
 int lora_register(Model& m, const std::string& key);  // pet_model_set_param: placement check of an injected key
 int lora_set_scaling(Model& m, const std::string& lin, float scaling);
@@ -236,8 +248,17 @@ int gen_backward_geometry(const Model& m, const Graph& g, void* ws, int64_t ws_b
 int64_t gen_train_workspace_bytes(const Model& m, int64_t n_nodes, int64_t n_edges);
 int norm_rev_rows(const float* Xp, const float* Xt, const float* gamma, int ln, float eps, const float* NYp, const float* NYt,
                   float* NXp, float* NXt, int64_t R, int W, hipStream_t st);
+// seed_node / seed_edge [n_seed] (n_seed = 0 or num_readout_layers(); NULL entries = 0): first-order feature adjoints of
+// further targets, added to the nu half of every readout layer's adjoint. lA and nA both NULL: no fused target in the loss
 int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, const float* lA, const float* nA, const float* u,
-               const float* ucell, float* tangent_atomic, hipStream_t st);
+               const float* ucell, float* tangent_atomic, hipStream_t st, const float* const* seed_node = nullptr,
+               const float* const* seed_edge = nullptr, int n_seed = 0);
+// further targets of a training step on a size-generic training workspace (train_predict / train_predict_backward)
+int gen_train_predict(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, const HeadW& H, const LastW& Lw,
+                      float* atomic, hipStream_t st);
+int gen_train_predict_backward(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, const HeadW& H,
+                               int n_blocks, const LastW* const* Lw, const float* const* gA, float* seed_node,
+                               float* seed_edge, hipStream_t st);
 // a model whose TRAINING runs on the size-generic path: other sizes, PostLN layers, the residual featuriser
 inline bool train_generic(const Model& m) { return m.generic() || !m.trainable(); }
 // ... and for a built graph: an atom of more than 127 neighbours, or NO edge at all (a batch of isolated atoms -- reference

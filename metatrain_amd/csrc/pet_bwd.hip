@@ -1534,10 +1534,16 @@ static void add_seed(float* dst, const float* src, int64_t n, hipStream_t st) {
     if (n > 0) k_add_seed<<<cdiv(n / 4, 256), 256, 0, st>>>(reinterpret_cast<float4*>(dst), reinterpret_cast<const float4*>(src), n / 4);
 }
 
+// the step runs on the size-generic training pass (other sizes, PostLN, residual, a dense atom, no edge): its forward left
+// a generic workspace, read by gen_train_predict / gen_train_predict_backward
+static int train_on_generic(const Model& m, const Graph& g, const void* ws, bool& gen) {
+    gen = train_generic_for(m, g) || generic_workspace(g, ws);
+    PET_REQUIRE(!gen || generic_workspace(g, ws), PET_ERR_ARGUMENT,
+                "pet_forward with save_for_backward = 2 has not run on this workspace");
+    return PET_OK;
+}
+
 static int train_workspace(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, Workspace& w) {
-    PET_REQUIRE(!train_generic_for(m, g) && !generic_workspace(g, ws), PET_ERR_UNSUPPORTED,
-                "training extra targets is built for the tuned path (default size, PreLN + feedforward featuriser, at most "
-                "127 neighbours per atom, a batch with edges)");
     PET_REQUIRE(layer == 0, PET_ERR_ARGUMENT, "the feedforward featuriser has one readout layer (0)");
     carve_workspace(m, g.n_nodes, g.n_edges, ws, w, true);
     PET_REQUIRE((int64_t)w.bytes <= ws_bytes, PET_ERR_ARGUMENT, "workspace too small for training");
@@ -1546,8 +1552,12 @@ static int train_workspace(const Model& m, const Graph& g, void* ws, int64_t ws_
 
 int train_predict(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, const HeadW& H, const LastW& Lw,
                   float* atomic, hipStream_t st) {
+    bool gen;
+    int rc = train_on_generic(m, g, ws, gen);
+    if (rc) return rc;
+    if (gen) return gen_train_predict(m, g, ws, ws_bytes, layer, H, Lw, atomic, st);
     Workspace w;
-    int rc = train_workspace(m, g, ws, ws_bytes, layer, w);
+    rc = train_workspace(m, g, ws, ws_bytes, layer, w);
     if (rc || g.n_nodes == 0) return rc;
     PoolBuf scratch;
     PET_HIP_CHECK(scratch.alloc((size_t)predict_scratch_floats(g.n_nodes, g.n_edges) * sizeof(float), st));
@@ -1561,8 +1571,12 @@ int train_predict(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, in
 int train_predict_backward(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const std::string& target, int layer,
                            const HeadW& H, int n_blocks, const char* const* blocks, const LastW* const* Lw,
                            const float* const* gA, float* seed_node, float* seed_edge, hipStream_t st) {
+    bool gen;
+    int rc = train_on_generic(m, g, ws, gen);
+    if (rc) return rc;
+    if (gen) return gen_train_predict_backward(m, g, ws, ws_bytes, layer, H, n_blocks, Lw, gA, seed_node, seed_edge, st);
     Workspace w;
-    int rc = train_workspace(m, g, ws, ws_bytes, layer, w);
+    rc = train_workspace(m, g, ws, ws_bytes, layer, w);
     if (rc || g.n_nodes == 0 || n_blocks == 0) return rc;
     PET_REQUIRE(m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
     const int64_t N = g.n_nodes, E = g.n_edges;
@@ -1712,20 +1726,24 @@ int backward_train(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, c
                    float* gcell, hipStream_t st, const float* const* seed_node, const float* const* seed_edge, int n_seed) {
     const float* sn = n_seed > 0 && seed_node ? seed_node[0] : nullptr;
     const float* se = n_seed > 0 && seed_edge ? seed_edge[0] : nullptr;
-    // other sizes, PostLN, residual, and any graph with an atom of more than 127 neighbours: the energy term alone = the
+    // other sizes, PostLN, residual, and any graph with an atom of more than 127 neighbours: the first-order terms alone = the
     // size-generic second-order pass without a tangent
     if (train_generic_for(m, g)) {
-        PET_REQUIRE(gA && !sn && !se, PET_ERR_UNSUPPORTED,
-                    "training extra targets is built for the tuned path (default size, PreLN + feedforward featuriser, at "
-                    "most 127 neighbours per atom, a batch with edges)");
         PET_REQUIRE(generic_workspace(g, ws), PET_ERR_ARGUMENT, "pet_forward with save_for_backward = 2 has not run on this workspace");
+        PET_REQUIRE(n_seed == 0 || n_seed == m.num_readout_layers(), PET_ERR_ARGUMENT, "expected one seed pair per readout layer");
+        bool seeded = false;
+        for (int l = 0; l < n_seed; l++) seeded = seeded || (seed_node && seed_node[l]) || (seed_edge && seed_edge[l]);
+        PET_REQUIRE(!(gpos || gcell) || !seeded, PET_ERR_UNSUPPORTED,
+                    "d_grad_positions / d_grad_cells with feature seeds: the further targets' cutoff-factor adjoint is not "
+                    "carried; ask for the parameter gradients only");
+        PET_REQUIRE(gA || !(gpos || gcell), PET_ERR_ARGUMENT, "d_grad_positions needs d_grad_atomic (the fused target's seeds)");
         // (the energy-only step has no second-order workspace of its own in the ABI: the dual activations come from the
         // stream's pool and go back to it on every exit)
         const int64_t n2 = gen_train_workspace_bytes(m, g.n_nodes, g.n_edges);
         PoolBuf ws2_pool;
         PET_HIP_CHECK(ws2_pool.alloc((size_t)n2, st));
         void* ws2 = ws2_pool.p;
-        int rc = gen_train2(m, g, ws2, n2, nullptr, gA, nullptr, nullptr, nullptr, st);
+        int rc = gen_train2(m, g, ws2, n2, nullptr, gA, nullptr, nullptr, nullptr, st, seed_node, seed_edge, n_seed);
         if (!rc && gpos) rc = gen_backward(m, g, ws, ws_bytes, gA, gpos, gcell, st);
         return rc;
     }

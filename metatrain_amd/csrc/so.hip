@@ -1266,10 +1266,7 @@ int backward_train2(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, 
     const float* se = n_seed > 0 && seed_edge ? seed_edge[0] : nullptr;
     // other sizes, PostLN, residual, more than 127 neighbours per atom: gen_train.hip (it recomputes what it needs in ws2)
     if (train_generic_for(m, g)) {
-        PET_REQUIRE(!sn && !se, PET_ERR_UNSUPPORTED,
-                    "training extra targets is built for the tuned path (default size, PreLN + feedforward featuriser, at "
-                    "most 127 neighbours per atom, a batch with edges)");
-        return gen_train2(m, g, ws2, ws2_bytes, lA, nA, u, ucell, tangent_atomic, st);
+        return gen_train2(m, g, ws2, ws2_bytes, lA, nA, u, ucell, tangent_atomic, st, seed_node, seed_edge, n_seed);
     }
     PET_REQUIRE(m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
     PET_REQUIRE(m.trainable(), PET_ERR_UNSUPPORTED,

@@ -23,16 +23,7 @@ float* Trainer::gp(const std::string& key) const {
     return it == m.grad_off.end() ? nullptr : grads + it->second;
 }
 
-bool Trainer::backbone_live() const {
-    if (m.frozen.empty()) return true;
-    for (const auto& kv : m.grad_off) {
-        const std::string& k = kv.first;
-        const bool head = k.rfind("node_heads.", 0) == 0 || k.rfind("edge_heads.", 0) == 0 ||
-                          k.rfind("node_last_layers.", 0) == 0 || k.rfind("edge_last_layers.", 0) == 0;
-        if (!head && !m.is_frozen(k)) return true;
-    }
-    return false;
-}
+bool Trainer::backbone_live() const { return backbone_trainable(m); }
 
 bool Trainer::live(const std::string& key) const {
     if (m.frozen.empty()) return true;

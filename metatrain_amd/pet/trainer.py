@@ -275,19 +275,31 @@ class TrainStep:
 
     def _extra(self, graph, fw, n_atoms, cells, extra_targets, extra_counts):
         """Predictions of the further targets from the training forward's features, their loss terms, and the summed
-        adjoints of the heads' inputs (``train_predict_backward``, which also adds the heads' parameter gradients)."""
+        adjoints of the heads' inputs (``train_predict_backward``, which also adds the heads' parameter gradients).
+
+        With several readout layers (the residual featuriser) a block's prediction is the sum over the layers of that
+        layer's head output (``backend.py:468-481``); post-processing and the loss act on the sum, so one
+        dL/d(prediction) seeds every layer, and the seeds come back as ``(node list, edge list)``, one pair per layer."""
         w = self.hypers["loss_weights"]
         sys = graph.system_of_atom().long()
+        n_layers = self.model.num_readout_layers()
         loss, seed_features = None, None
         for name, spec in extra_targets.items():
-            preds = {b: fw.train_predict(name, b).requires_grad_(True) for b in _extra_blocks(name, spec)}
+            preds = {}
+            for b in _extra_blocks(name, spec):
+                p = fw.train_predict(name, b)
+                for layer in range(1, n_layers):  # fixed order
+                    p = p + fw.train_predict(name, b, readout_layer=layer)
+                preds[b] = p.requires_grad_(True)
             weight = float(spec.get("weight", w.get(name, 1.0)))
             count = None if extra_counts is None else extra_counts[name]
             loss_t = extra_target_loss(name, spec, preds, sys, n_atoms, cells, weight,
                                        self.hypers.get("per_structure_targets", ()), count,
                                        lambda p: _SumOverAtoms.apply(p, fw, sys))
             grads = torch.autograd.grad(loss_t, list(preds.values()))
-            seed_features = fw.train_predict_backward(name, dict(zip(preds, grads)), seed_features=seed_features)
+            for layer in range(n_layers):
+                seed_features = fw.train_predict_backward(name, dict(zip(preds, grads)), readout_layer=layer,
+                                                          seed_features=seed_features)
             loss = loss_t.detach() if loss is None else loss + loss_t.detach()
         return loss, seed_features
 

@@ -176,6 +176,10 @@ class HipModel:
             check(self.lib.pet_model_set_trainable(self._handle, self._ckeys[key][0].encode(), int(bool(on))))
             (self._frozen.discard if on else self._frozen.add)(key)
 
+    def num_readout_layers(self) -> int:
+        """Readout layers of the model: one, or with the residual featuriser one per GNN layer."""
+        return int(self.lib.pet_model_num_readout_layers(self._handle))
+
     def head_keys(self) -> Dict[str, Tuple[str, Optional[str]]]:
         """Every uploaded head / last-layer key -> (target, block; None for a head), under the state dict's names."""
         out = {}
@@ -587,22 +591,43 @@ class HipForward:
         """Adjoint of :meth:`train_predict` for some blocks of one target (``{block: dL/d(prediction) [N, P]}``,
         ``pet_train_predict_backward``): ADDS dL/dtheta of the target's heads and of those blocks' last layers to the
         gradient slots, and ADDS the adjoints of the heads' inputs to ``seed_features = (node [N, d_node], edge [E, d_pet])``
-        (zeros when None), which it returns for :meth:`backward_train` / :meth:`backward_train2`."""
+        (zeros when None), which it returns for :meth:`backward_train` / :meth:`backward_train2`. A model with several
+        readout layers (the residual featuriser) takes and returns ``(node list, edge list)`` with one entry per readout
+        layer (``None``: nothing added yet); this call fills the entry of ``readout_layer``."""
         if not self.train:
             raise PetHipError("train_predict_backward needs HipForward(..., train=True)")
         g = self.graph
         dev = self.workspace.device
+        n_l = self.model.num_readout_layers()
+        if not 0 <= readout_layer < n_l:
+            raise PetHipError(f"readout layer {readout_layer} out of range (the model has {n_l})")
+
+        def zeros():
+            return (torch.zeros((g.n_nodes, self.model.hypers["d_node"]), dtype=torch.float32, device=dev),
+                    torch.zeros((g.n_edges, self.model.hypers["d_pet"]), dtype=torch.float32, device=dev))
+
         if seed_features is None:
-            seed_features = (torch.zeros((g.n_nodes, self.model.hypers["d_node"]), dtype=torch.float32, device=dev),
-                             torch.zeros((g.n_edges, self.model.hypers["d_pet"]), dtype=torch.float32, device=dev))
+            seed_features = zeros() if n_l == 1 else ([None] * n_l, [None] * n_l)
+        if isinstance(seed_features[0], (list, tuple)):
+            node, edge = list(seed_features[0]), list(seed_features[1])
+            if len(node) != n_l or len(edge) != n_l:
+                raise PetHipError(f"expected one seed pair per readout layer ({n_l})")
+            if node[readout_layer] is None or edge[readout_layer] is None:
+                zn, ze = zeros()
+                node[readout_layer] = zn if node[readout_layer] is None else node[readout_layer]
+                edge[readout_layer] = ze if edge[readout_layer] is None else edge[readout_layer]
+            seed_features = (node, edge)
+            seed_node, seed_edge = node[readout_layer], edge[readout_layer]
+        else:
+            seed_node, seed_edge = seed_features
         names = [_head_names(self.model, target, b, readout_layer == 0) for b in grad_atomic]
         seeds = [t.detach().to(dev, torch.float32).reshape(g.n_nodes, -1).contiguous() for t in grad_atomic.values()]
         nb = len(seeds)
         blocks = (c_char_p * nb)(*[b for _, b in names])
         ptrs = (c_void_p * nb)(*[t.data_ptr() for t in seeds])
         check(self.lib.pet_train_predict_backward(self.model.handle, g.handle, _ptr(self.workspace), self.nbytes,
-                                                  names[0][0], readout_layer, nb, blocks, ptrs, _ptr(seed_features[0]),
-                                                  _ptr(seed_features[1]), _stream()))
+                                                  names[0][0], readout_layer, nb, blocks, ptrs, _ptr(seed_node),
+                                                  _ptr(seed_edge), _stream()))
         return seed_features
 
     @staticmethod

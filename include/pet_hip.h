@@ -477,6 +477,35 @@ int pet_llpr_variance(const pet_model_t* m, int64_t F, const float* d_x, int64_t
 int pet_llpr_ensemble(const pet_model_t* m, int64_t F, const float* d_x, int64_t R, const float* d_weights, int32_t K,
                       int32_t P, const float* d_prediction, float* d_out, void* stream);
 
+/* ---- ZBL short-range repulsion (utils/additive/zbl.py): the additive model of `zbl: true` ----------------------------
+ * e(r) = 1/2 [E(r) + A/3 r^3 + B/4 r^4 + C] for r <= rc = rad(Zi) + rad(Zj), else 0, E(r) = K Zi Zj / r * phi(r / a)
+ * (LAMMPS pair_style zbl with inner cutoff 0; eV and Angstrom). Per-atom energies a_i = sum over the CSR row of atom i.
+ * The pair term is evaluated in fp64, rows are summed in edge order in fp64, outputs are fp32; no atomics: every result
+ * is the same bits run to run, and a system gives the same bits alone as inside a batch.
+ *   pet_zbl_create: h_atomic_types [n_types] = the atomic_types of the model that builds the graphs, in the same order
+ *     (the graph's species indices index it); h_covalent_radii [n_types] in Angstrom. Builds the [n_types, n_types, 6]
+ *     fp64 table (rc, 1/a, K Zi Zj, A, B, C) on the host. Neither it nor pet_zbl_pair_table needs a GPU.
+ *   pet_zbl_cutoff: 2 * the largest radius = the range a neighbour list must cover (full list).
+ *   pet_zbl_forward: d_atomic [N]. pet_zbl_backward: d_grad_atomic [N] = dL/d(a_i), NULL = ones;
+ *     d_grad_positions [N,3] = dL/dR; d_grad_cells [S,3,3] = dL/dcell through the S.cell term (may be NULL);
+ *     d_grad_strain [S,3,3] = dE/d(strain) = R^T dE/dR + cell^T dE/dcell formed directly from the edge vectors (may be
+ *     NULL; unit weights only: PET_ERR_ARGUMENT together with d_grad_atomic). The pair terms are recomputed: nothing is
+ *     kept between the two calls. d_workspace: pet_zbl_workspace_bytes(N, S) bytes, needed for either 3x3 output.
+ * The launches run on the caller's stream without a synchronisation, with one exception: the FIRST launch on a device
+ * uploads the table and the radii (two allocations kept until pet_zbl_destroy, two blocking copies that have completed
+ * before any thread or stream can see the entry), so it must not sit inside a stream capture. Later ones allocate nothing.
+ * PET_ERR_ARGUMENT: a graph whose cutoff is below pet_zbl_cutoff, a graph built under an adaptive cutoff (it drops edges
+ * inside the range), a pet_graph_from_batch handle (no shifts / system indices). */
+typedef struct pet_zbl pet_zbl_t;
+int pet_zbl_create(const int32_t* h_atomic_types, const double* h_covalent_radii, int32_t n_types, pet_zbl_t** out);
+void pet_zbl_destroy(pet_zbl_t* z);
+double pet_zbl_cutoff(const pet_zbl_t* z);
+int pet_zbl_pair_table(const pet_zbl_t* z, double* h_out);
+int64_t pet_zbl_workspace_bytes(int64_t n_nodes, int64_t n_systems);
+int pet_zbl_forward(const pet_zbl_t* z, const pet_graph_t* g, float* d_atomic, void* stream);
+int pet_zbl_backward(const pet_zbl_t* z, const pet_graph_t* g, const float* d_grad_atomic, float* d_grad_positions,
+                     float* d_grad_cells, float* d_grad_strain, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- profiling hooks used by bench.py ------------------------------------------ */
 /* When enabled, every kernel launch of pet_forward/pet_backward is bracketed with HIP
  * events on the launch stream; pet_profile_report fills name / total ms / calls / algorithmic

@@ -44,6 +44,8 @@ SYMBOLS = [
     "pet_sum_over_atoms",
     "pet_llpr_feature_size", "pet_llpr_features", "pet_llpr_rows", "pet_llpr_covariance_accumulate",
     "pet_llpr_covariance_finalize", "pet_llpr_variance", "pet_llpr_ensemble",
+    "pet_zbl_create", "pet_zbl_destroy", "pet_zbl_cutoff", "pet_zbl_pair_table", "pet_zbl_workspace_bytes",
+    "pet_zbl_forward", "pet_zbl_backward",
     "pet_profile_enable", "pet_profile_select", "pet_profile_reset", "pet_profile_report", "pet_config_set",
 ]
 
@@ -215,6 +217,16 @@ def load() -> ctypes.CDLL:
     lib.pet_llpr_covariance_finalize.argtypes = [P, c_int64, P, P]
     lib.pet_llpr_variance.argtypes = [P, c_int64, P, c_int64, P, c_float, P, P]
     lib.pet_llpr_ensemble.argtypes = [P, c_int64, P, c_int64, P, c_int32, c_int32, P, P, P]
+    lib.pet_zbl_create.argtypes = [POINTER(c_int32), POINTER(c_double), c_int32, POINTER(P)]
+    lib.pet_zbl_destroy.argtypes = [P]
+    lib.pet_zbl_destroy.restype = None
+    lib.pet_zbl_cutoff.argtypes = [P]
+    lib.pet_zbl_cutoff.restype = c_double
+    lib.pet_zbl_pair_table.argtypes = [P, POINTER(c_double)]
+    lib.pet_zbl_workspace_bytes.argtypes = [c_int64, c_int64]
+    lib.pet_zbl_workspace_bytes.restype = c_int64
+    lib.pet_zbl_forward.argtypes = [P, P, P, P]
+    lib.pet_zbl_backward.argtypes = [P, P, P, P, P, P, P, c_int64, P]
     lib.pet_profile_enable.argtypes = [c_int]
     lib.pet_profile_select.argtypes = [c_char_p]
     lib.pet_profile_report.argtypes = [c_int, P, POINTER(c_double), POINTER(c_int64), POINTER(c_double),

@@ -36,6 +36,24 @@ struct GraphHolder : torch::CustomClassHolder {  // one preprocess() result kept
     }
 };
 
+// The ZBL additive model of a `zbl: true` checkpoint (pet_zbl_t): atomic types in the model's order and their covalent
+// radii; pickled as those two lists, the pair table is rebuilt on load (host only).
+struct ZblTable : torch::CustomClassHolder {
+    std::vector<int64_t> atomic_types;
+    std::vector<double> radii;
+    pet_zbl_t* z = nullptr;
+    ZblTable(std::vector<int64_t> atomic_types_, std::vector<double> radii_)
+        : atomic_types(std::move(atomic_types_)), radii(std::move(radii_)) {
+        TORCH_CHECK(atomic_types.size() == radii.size() && !radii.empty(), "pet_hip: one covalent radius per atomic type");
+        std::vector<int32_t> t(atomic_types.begin(), atomic_types.end());
+        check(pet_zbl_create(t.data(), radii.data(), (int32_t)t.size(), &z), "pet_zbl_create");
+    }
+    ~ZblTable() override {
+        if (z) pet_zbl_destroy(z);
+    }
+    double cutoff() const { return pet_zbl_cutoff(z); }
+};
+
 struct PetHipModule : torch::CustomClassHolder {
     std::vector<double> hypers;  // pet_hypers_t, field by field (see hypers_struct())
     std::vector<int64_t> atomic_types;
@@ -101,16 +119,33 @@ struct PetHipModule : torch::CustomClassHolder {
                                                                const at::Tensor& centers, const at::Tensor& neighbors,
                                                                const at::Tensor& cell_shifts, const at::Tensor& species,
                                                                const at::Tensor& system_indices);
+    // the same with the ZBL per-atom energies [N, 1] as a second output of the SAME graph and autograd node
+    std::tuple<at::Tensor, at::Tensor> atomic_energies_zbl(const at::Tensor& positions, const at::Tensor& cells,
+                                                           const at::Tensor& centers, const at::Tensor& neighbors,
+                                                           const at::Tensor& cell_shifts, const at::Tensor& species,
+                                                           const at::Tensor& system_indices,
+                                                           c10::intrusive_ptr<ZblTable> zbl);
+    std::tuple<at::Tensor, at::Tensor, at::Tensor> atomic_energies_and_llf_zbl(
+        const at::Tensor& positions, const at::Tensor& cells, const at::Tensor& centers, const at::Tensor& neighbors,
+        const at::Tensor& cell_shifts, const at::Tensor& species, const at::Tensor& system_indices,
+        c10::intrusive_ptr<ZblTable> zbl);
+    void check_zbl(const c10::intrusive_ptr<ZblTable>& zbl) const {
+        TORCH_CHECK(zbl, "pet_hip: no ZBL table");
+        TORCH_CHECK(zbl->atomic_types == atomic_types, "pet_hip: the ZBL table and the model list different atomic types");
+    }
     at::Tensor llpr_rows(const at::Tensor& llf, const at::Tensor& system_indices, int64_t n_systems, const at::Tensor& mask);
     at::Tensor llpr_variance(const at::Tensor& x, const at::Tensor& inv_cholesky, double alpha);
     at::Tensor llpr_ensemble(const at::Tensor& x, const at::Tensor& weights, int64_t K, const at::Tensor& prediction);
 };
 
 struct EnergyFn : torch::autograd::Function<EnergyFn> {
-    static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& positions,
-                              const at::Tensor& cells, c10::intrusive_ptr<PetHipModule> mod, const at::Tensor& centers,
-                              const at::Tensor& neighbors, const at::Tensor& cell_shifts, const at::Tensor& species,
-                              const at::Tensor& system_indices, at::Tensor llf) {
+    // returns {atomic [N, 1]} or, with a ZBL table, {atomic [N, 1], ZBL atomic [N, 1]} (pet_zbl_forward on the same graph)
+    static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, const at::Tensor& positions,
+                                                  const at::Tensor& cells, c10::intrusive_ptr<PetHipModule> mod,
+                                                  const at::Tensor& centers, const at::Tensor& neighbors,
+                                                  const at::Tensor& cell_shifts, const at::Tensor& species,
+                                                  const at::Tensor& system_indices, at::Tensor llf,
+                                                  c10::intrusive_ptr<ZblTable> zbl) {
         // llf: empty, or [N, F] filled here with the last-layer features of the fused target from the SAME backbone
         // forward (pet_forward's feature copies -> pet_llpr_features); it is not differentiated
         mod->ensure_model(positions);
@@ -155,14 +190,20 @@ struct EnergyFn : torch::autograd::Function<EnergyFn> {
         ctx->saved_data["module"] = mod;
         ctx->saved_data["pos_dtype"] = (int64_t)positions.scalar_type();
         ctx->saved_data["cell_dtype"] = (int64_t)cells.scalar_type();
-        return atomic.unsqueeze(1).to(positions.scalar_type());
+        if (!zbl) return {atomic.unsqueeze(1).to(positions.scalar_type())};
+        at::Tensor zatomic = at::empty({gh->n_nodes}, atomic.options());
+        check(pet_zbl_forward(zbl->z, gh->g, zatomic.data_ptr<float>(), st), "pet_zbl_forward");
+        ctx->saved_data["zbl"] = zbl;
+        return {atomic.unsqueeze(1).to(positions.scalar_type()), zatomic.unsqueeze(1).to(positions.scalar_type())};
     }
 
     static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
                                                    torch::autograd::variable_list grad_out) {
         auto gh = ctx->saved_data["graph"].toCustomClass<GraphHolder>();
         auto mod = ctx->saved_data["module"].toCustomClass<PetHipModule>();
+        const bool has_zbl = grad_out.size() > 1;
         at::Tensor ga = grad_out[0];
+        if (has_zbl && !ga.defined()) ga = at::zeros({gh->n_nodes}, gh->fwd_ws.options().dtype(at::kFloat));
         TORCH_CHECK(!ga.requires_grad(), "pet_hip: double backward (create_graph=True) is not available through the "
                                          "TorchScript op; train through metatrain_amd.pet (PETBackend / TrainStep)");
         ga = as_f32(ga.reshape({-1}));
@@ -171,10 +212,22 @@ struct EnergyFn : torch::autograd::Function<EnergyFn> {
         check(pet_backward(mod->model, gh->g, gh->fwd_ws.data_ptr(), gh->fwd_ws.numel(), ga.data_ptr<float>(),
                            gpos.data_ptr<float>(), gcell.data_ptr<float>(), stream_of(ga)),
               "pet_backward");
+        if (has_zbl && grad_out[1].defined()) {  // + the ZBL term's dL/dR and dL/dcell for the weights it received
+            TORCH_CHECK(!grad_out[1].requires_grad(), "pet_hip: double backward through the ZBL term is not built");
+            auto zbl = ctx->saved_data["zbl"].toCustomClass<ZblTable>();
+            at::Tensor gz = as_f32(grad_out[1].reshape({-1}));
+            at::Tensor zpos = at::empty({gh->n_nodes, 3}, ga.options()), zcell = at::empty({gh->n_systems, 3, 3}, ga.options());
+            at::Tensor zws = at::empty({pet_zbl_workspace_bytes(gh->n_nodes, gh->n_systems)}, gh->fwd_ws.options());
+            check(pet_zbl_backward(zbl->z, gh->g, gz.data_ptr<float>(), zpos.data_ptr<float>(), zcell.data_ptr<float>(), nullptr,
+                                   zws.data_ptr(), zws.numel(), stream_of(ga)),
+                  "pet_zbl_backward");
+            gpos.add_(zpos);
+            gcell.add_(zcell);
+        }
         const auto pd = (at::ScalarType)ctx->saved_data["pos_dtype"].toInt();
         const auto cd = (at::ScalarType)ctx->saved_data["cell_dtype"].toInt();
         return {gpos.to(pd), gcell.to(cd), at::Tensor(), at::Tensor(), at::Tensor(),
-                at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+                at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
     }
 };
 
@@ -183,7 +236,33 @@ at::Tensor PetHipModule::atomic_energies(const at::Tensor& positions, const at::
                                          const at::Tensor& cell_shifts, const at::Tensor& species,
                                          const at::Tensor& system_indices) {
     return EnergyFn::apply(positions, cells, c10::intrusive_ptr<PetHipModule>::reclaim_copy(this), centers, neighbors,
-                           cell_shifts, species, system_indices, at::empty({0}, positions.options().dtype(at::kFloat)));
+                           cell_shifts, species, system_indices, at::empty({0}, positions.options().dtype(at::kFloat)),
+                           c10::intrusive_ptr<ZblTable>())[0];
+}
+
+std::tuple<at::Tensor, at::Tensor> PetHipModule::atomic_energies_zbl(const at::Tensor& positions, const at::Tensor& cells,
+                                                                     const at::Tensor& centers, const at::Tensor& neighbors,
+                                                                     const at::Tensor& cell_shifts, const at::Tensor& species,
+                                                                     const at::Tensor& system_indices,
+                                                                     c10::intrusive_ptr<ZblTable> zbl) {
+    check_zbl(zbl);
+    auto out = EnergyFn::apply(positions, cells, c10::intrusive_ptr<PetHipModule>::reclaim_copy(this), centers, neighbors,
+                               cell_shifts, species, system_indices, at::empty({0}, positions.options().dtype(at::kFloat)), zbl);
+    return {out[0], out[1]};
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> PetHipModule::atomic_energies_and_llf_zbl(
+    const at::Tensor& positions, const at::Tensor& cells, const at::Tensor& centers, const at::Tensor& neighbors,
+    const at::Tensor& cell_shifts, const at::Tensor& species, const at::Tensor& system_indices,
+    c10::intrusive_ptr<ZblTable> zbl) {
+    check_zbl(zbl);
+    ensure_model(positions);
+    TORCH_CHECK(pet_model_num_readout_layers(model) == 1,
+                "pet_hip: the fused head reads one readout layer (feed-forward featuriser only)");
+    at::Tensor llf = at::empty({positions.size(0), pet_llpr_feature_size(model)}, positions.options().dtype(at::kFloat));
+    auto out = EnergyFn::apply(positions, cells, c10::intrusive_ptr<PetHipModule>::reclaim_copy(this), centers, neighbors,
+                               cell_shifts, species, system_indices, llf, zbl);
+    return {out[0], out[1], llf};
 }
 
 // ---- LLPR (llpr/model.py): the fused target's per-atom predictions and last-layer features from one backbone forward,
@@ -197,7 +276,7 @@ std::tuple<at::Tensor, at::Tensor> PetHipModule::atomic_energies_and_llf(
     at::Tensor llf = at::empty({positions.size(0), pet_llpr_feature_size(model)},
                                positions.options().dtype(at::kFloat));
     at::Tensor atomic = EnergyFn::apply(positions, cells, c10::intrusive_ptr<PetHipModule>::reclaim_copy(this), centers,
-                                        neighbors, cell_shifts, species, system_indices, llf);
+                                        neighbors, cell_shifts, species, system_indices, llf, c10::intrusive_ptr<ZblTable>())[0];
     return {atomic, llf};
 }
 
@@ -683,12 +762,18 @@ std::vector<at::Tensor> PetHipBackend::predict(std::vector<at::Tensor> params, s
 using BackendState = std::tuple<std::vector<double>, std::vector<int64_t>, std::vector<std::string>>;
 
 using State = std::tuple<std::vector<double>, std::vector<int64_t>, std::vector<std::string>, std::vector<at::Tensor>>;
+using ZblState = std::tuple<std::vector<int64_t>, std::vector<double>>;
 
 }  // namespace
 
 TORCH_LIBRARY(pet_hip, m) {
     m.class_<GraphHolder>("GraphHolder");
     m.class_<BatchGraph>("BatchGraph");
+    m.class_<ZblTable>("ZblTable")
+        .def(torch::init<std::vector<int64_t>, std::vector<double>>())
+        .def("cutoff", &ZblTable::cutoff)
+        .def_pickle([](const c10::intrusive_ptr<ZblTable>& self) -> ZblState { return ZblState(self->atomic_types, self->radii); },
+                    [](ZblState s) { return c10::make_intrusive<ZblTable>(std::get<0>(s), std::get<1>(s)); });
     m.class_<PetHipBackend>("PetHipBackend")
         .def(torch::init<std::vector<double>, std::vector<int64_t>, std::vector<std::string>>())
         .def("preprocess", &PetHipBackend::preprocess)
@@ -705,6 +790,8 @@ TORCH_LIBRARY(pet_hip, m) {
         .def(torch::init<std::vector<double>, std::vector<int64_t>, std::vector<std::string>, std::vector<at::Tensor>>())
         .def("atomic_energies", &PetHipModule::atomic_energies)
         .def("atomic_energies_and_llf", &PetHipModule::atomic_energies_and_llf)
+        .def("atomic_energies_zbl", &PetHipModule::atomic_energies_zbl)
+        .def("atomic_energies_and_llf_zbl", &PetHipModule::atomic_energies_and_llf_zbl)
         .def("llpr_rows", &PetHipModule::llpr_rows)
         .def("llpr_variance", &PetHipModule::llpr_variance)
         .def("llpr_ensemble", &PetHipModule::llpr_ensemble)

@@ -413,6 +413,11 @@ class LLPRUncertainty:
         ``explicit_gradients`` of an ensemble output raise ``NotImplementedError``; ``{"energy": ["positions"]}`` adds
         ``"energy/positions"`` (dE/dR of the per-system energies' sum, fused energy head)."""
         explicit_gradients = explicit_gradients or {}
+        if self.model.hypers.get("zbl", False):
+            # predictions (and the mean an ensemble is centred on) would lack the additive ZBL term of pet/model.py:616-660
+            raise PetHipError("this wrapper evaluates the network alone, and the model has `zbl: true`: evaluate through "
+                              "ExportedLLPRModel(..., zbl=...), which adds the ZBL term (covariance, Cholesky factor, "
+                              "calibration and ensemble weights of this object do not depend on it)")
         for name, grads in explicit_gradients.items():
             if name.endswith("_ensemble") and grads:
                 raise NotImplementedError(f"explicit gradients ({', '.join(grads)}) of '{name}' are not implemented: each "

@@ -44,14 +44,30 @@ import torch
 from ..partition import slab_partition
 
 
+def _zbl_of(model, zbl, what: str):
+    """The ZBL term of a ``zbl: true`` model (``metatrain_amd/zbl.py``), evaluated on the sub-system's own graph: ZBL is
+    row-local and its range lies inside one cutoff, so owned atoms have complete rows in every halo scheme here, and the
+    owned-atom seeds of the reverse pass are its ``grad_atomic``."""
+    if zbl is False or (zbl is None and not model.hypers.get("zbl", False)):
+        return None
+    from ..zbl import zbl_on_model_graph
+
+    return zbl_on_model_graph(zbl, bool(model.hypers.get("zbl", False)), model.atomic_types, float(model.hypers["cutoff"]),
+                              model.hypers.get("num_neighbors_adaptive") is not None, what)
+
+
 def energy_and_gradient(model, positions: torch.Tensor, species: torch.Tensor, cell: torch.Tensor, pbc: Sequence[bool],
                         world: int, rank: int, all_reduce: Optional[Callable[[torch.Tensor], None]] = None,
-                        neighbor_list: Optional[Callable] = None, runtime=None, hops: Optional[int] = None):
+                        neighbor_list: Optional[Callable] = None, runtime=None, hops: Optional[int] = None, zbl=None):
     """Energy and dE/dR ``[N, 3]`` of one box, rank ``rank``'s share computed here and summed over ranks by
     ``all_reduce(tensor)`` (in place; ``None``: return the partial results -- the caller, or a single-process test,
     adds them). ``model``: a loaded :class:`metatrain_amd.runtime.HipModel` (single energy target); ``neighbor_list``:
     the device neighbour list by default; ``hops``: halo thickness in cutoffs (default: exact, ``num_gnn_layers + 1``, one
-    more with the adaptive cutoff). Returns ``(energy [1], gradient [N, 3], n_sub, n_owned)``."""
+    more with the adaptive cutoff). ``zbl``: the model's :class:`~metatrain_amd.zbl.ZBLHip` (a checkpoint's radii), ``True``
+    (default radii), ``False`` (the network alone) or None (``model.hypers["zbl"]`` decides): energy and gradient include
+    the ZBL term; a model whose neighbour list cannot serve it (cutoff below the ZBL cutoff, adaptive cutoff) is refused.
+    Returns ``(energy [1], gradient [N, 3], n_sub, n_owned)``."""
+    z = _zbl_of(model, zbl, "the partitioned box")
     if runtime is None:
         from .. import runtime
     if neighbor_list is None:
@@ -73,10 +89,13 @@ def energy_and_gradient(model, positions: torch.Tensor, species: torch.Tensor, c
                                  torch.zeros(index.numel(), dtype=torch.int32, device=dev))
         fw = runtime.HipForward(model, graph)
         seeds = owned.to(torch.float32)
-        atomic = fw.forward()
+        atomic = fw.forward().reshape(-1)
         grad_sub = fw.backward(seeds)
+        if z is not None:
+            atomic = atomic + z.forward(graph)
+            grad_sub = grad_sub + z.backward(graph, seeds)
         buf[: 3 * n].view(n, 3)[index] = grad_sub
-        buf[3 * n] = (atomic.reshape(-1) * seeds).sum()
+        buf[3 * n] = (atomic * seeds).sum()
     if all_reduce is not None:
         all_reduce(buf)
     return buf[3 * n:], buf[: 3 * n].view(n, 3), int(index.numel()), int(owned.sum())
@@ -120,17 +139,20 @@ class ExchangePlan:
 def energy_and_gradient_exchange(model, positions: torch.Tensor, species: torch.Tensor, cell: torch.Tensor,
                                  pbc: Sequence[bool], world: int, rank: int, all_to_all: Callable,
                                  all_reduce: Optional[Callable[[torch.Tensor], None]] = None,
-                                 neighbor_list: Optional[Callable] = None, runtime=None):
+                                 neighbor_list: Optional[Callable] = None, runtime=None, zbl=None):
     """Energy and dE/dR of one box with ONE-cutoff halos: rank ``rank`` runs the transformer layers on the atoms it owns; the
     edge tokens its combination stage needs from foreign centres arrive by ``all_to_all(out, inp, out_splits, in_splits)``
     once per GNN layer (and their adjoints go back once per layer in the reverse pass) -- ``torch.distributed.
     all_to_all_single`` on RCCL: one message per peer over its xGMI link. Then ONE all-reduce(sum) of ``[gradient | energy]``
-    as in :func:`energy_and_gradient`. Default model size, PreLN + feedforward, fixed cutoff.
+    as in :func:`energy_and_gradient`. Default model size, PreLN + feedforward, fixed cutoff. ``zbl`` as in
+    :func:`energy_and_gradient`: the kept edges (every edge that touches an owned atom) hold every ZBL pair the owned energies
+    and their gradient read.
     Returns ``(energy [1], gradient [N, 3], n_sub, n_owned, n_rows, n_ghost_rows)``."""
     import ctypes
 
     from ..partition import slab_owner
 
+    z = _zbl_of(model, zbl, "the per-layer exchange")
     if runtime is None:
         from .. import runtime
     if neighbor_list is None:
@@ -209,12 +231,15 @@ def energy_and_gradient_exchange(model, positions: torch.Tensor, species: torch.
         try:
             fw = runtime.HipForward(model, graph)
             seeds = owned.to(torch.float32)
-            atomic = fw.forward()
+            atomic = fw.forward().reshape(-1)
             while calls[0] < n_layers:  # a sub-system without edges: the library had nothing to exchange
                 exchange(0)
             grad_sub = fw.backward(seeds)
+            if z is not None:
+                atomic = atomic + z.forward(graph)
+                grad_sub = grad_sub + z.backward(graph, seeds)
             buf[: 3 * n].view(n, 3)[index] = grad_sub
-            buf[3 * n] = (atomic.reshape(-1) * seeds).sum()
+            buf[3 * n] = (atomic * seeds).sum()
         except Exception as exc:  # noqa: BLE001 -- the peers still get their collectives below
             run_error = getattr(plan, "error", None) or exc
         finally:

@@ -8,7 +8,7 @@ cells inside TorchScript, weights pickled with the module. MD engines load it af
 ``torch.ops.load_library("libpet_hip_torch.so")``.
 """
 import os
-from typing import Dict, List, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -33,9 +33,59 @@ def load_ops() -> None:
     _loaded = True
 
 
+def make_zbl(hypers: dict, atomic_types: List[int], zbl=None):
+    """``torch.classes.pet_hip.ZblTable`` of a model, or None when it has no ZBL term. ``zbl``: a
+    :class:`~metatrain_amd.zbl.ZBLHip` (e.g. ``ZBLHip.from_state_dict`` of the checkpoint's ``additive_models`` buffers),
+    ``True`` (the default radii table) or None (``hypers["zbl"]`` decides). The exported model evaluates ZBL on the model's
+    own neighbour list (one graph per call), so a model whose list does not hold every ZBL pair is refused."""
+    from ..zbl import ZBLHip
+
+    if zbl is None or zbl is False:
+        if not hypers.get("zbl", False) or zbl is False:
+            return None
+        zbl = True
+    if zbl is True:
+        zbl = ZBLHip(atomic_types)
+    if list(zbl.atomic_types) != [int(z) for z in atomic_types]:
+        raise PetHipError("the ZBL model and the PET model list different atomic types")
+    if hypers.get("num_neighbors_adaptive"):
+        raise PetHipError("zbl with num_neighbors_adaptive: the adaptive cutoff drops edges inside the ZBL range, so the "
+                          "exported model cannot share its neighbour list; evaluate ZBLHip on its own graph "
+                          "(ZBLHip.graph_for)")
+    if float(hypers["cutoff"]) + 1e-6 < zbl.cutoff:
+        raise PetHipError(f"zbl needs a neighbour list of {zbl.cutoff:.2f} A (twice the largest covalent radius) but the "
+                          f"model's cutoff is {float(hypers['cutoff']):.2f} A: the exported model cannot share its "
+                          "neighbour list; evaluate ZBLHip on its own graph (ZBLHip.graph_for)")
+    load_ops()
+    return torch.classes.pet_hip.ZblTable([int(z) for z in zbl.atomic_types], [float(r) for r in zbl.covalent_radii])
+
+
+class CoreAndZbl(NamedTuple):
+    """What :func:`make_core_and_zbl` returns: the ``PetHipModule`` and the model's ``ZblTable`` (None without ZBL)."""
+    core: object
+    zbl: object
+
+
+def make_core_and_zbl(hypers: dict, atomic_types: List[int], state_dict: Dict[str, torch.Tensor], target: str,
+                      block: Optional[str] = None, zbl=None) -> CoreAndZbl:
+    """The two parts of an exported model, whatever ``hypers["zbl"]`` says: ``(core, zbl)`` with ``zbl`` the ``ZblTable``
+    of :func:`make_zbl` or None. ``ExportedEnergyModel(parts.core, scale, composition, zbl=parts.zbl)``."""
+    table = make_zbl(hypers, atomic_types, zbl)
+    return CoreAndZbl(make_core(hypers, atomic_types, state_dict, target, block, zbl=table if table is not None else False),
+                      table)
+
+
 def make_core(hypers: dict, atomic_types: List[int], state_dict: Dict[str, torch.Tensor], target: str,
-              block: Optional[str] = None):
-    """``torch.classes.pet_hip.PetHipModule`` for one target of a reference-schema state dict."""
+              block: Optional[str] = None, zbl=None):
+    """``torch.classes.pet_hip.PetHipModule`` for one target of a reference-schema state dict: the network alone, always.
+    For a model with ``hypers["zbl"]`` set the caller must say what becomes of the ZBL term, since the core does not hold
+    it: ``zbl`` is the ``ZblTable`` of :func:`make_zbl` that goes to :class:`ExportedEnergyModel` /
+    :class:`ExportedLLPRModel` ``(..., zbl=table)`` with this core (:func:`make_core_and_zbl` does both), or ``False`` for
+    the bare network (training-side comparisons). Leaving it None for such a model raises."""
+    if hypers.get("zbl", False) and zbl is None:
+        raise PetHipError("this model has `zbl: true` and the core evaluates the network alone: build both parts with "
+                          "make_core_and_zbl(...) and pass its table as ExportedEnergyModel(core, ..., zbl=table), or "
+                          "pass zbl=False for the bare network")
     load_ops()
     block = block or target
     h = hypers_struct(hypers, atomic_types)
@@ -71,6 +121,37 @@ class PETScriptModule(torch.nn.Module):
                 cell_shifts: torch.Tensor, species: torch.Tensor, system_indices: torch.Tensor) -> torch.Tensor:
         return self.core.atomic_energies(positions, cells, centers, neighbors, cell_shifts, species, system_indices)
 
+    @torch.jit.export
+    def energies_and_llf(self, positions: torch.Tensor, cells: torch.Tensor, centers: torch.Tensor,
+                         neighbors: torch.Tensor, cell_shifts: torch.Tensor, species: torch.Tensor,
+                         system_indices: torch.Tensor):
+        return self.core.atomic_energies_and_llf(positions, cells, centers, neighbors, cell_shifts, species,
+                                                 system_indices)
+
+
+class PETZblScriptModule(torch.nn.Module):
+    """:class:`PETScriptModule` with the ZBL per-atom energies as a second column: ``[N, 2]`` = (PET, ZBL), both from one
+    graph build and one autograd node (its backward adds the ZBL ``dL/dR`` and ``dL/dcell``)."""
+
+    def __init__(self, core, zbl):
+        super().__init__()
+        self.core = core
+        self.zbl = zbl
+
+    def forward(self, positions: torch.Tensor, cells: torch.Tensor, centers: torch.Tensor, neighbors: torch.Tensor,
+                cell_shifts: torch.Tensor, species: torch.Tensor, system_indices: torch.Tensor) -> torch.Tensor:
+        pet, rep = self.core.atomic_energies_zbl(positions, cells, centers, neighbors, cell_shifts, species,
+                                                 system_indices, self.zbl)
+        return torch.cat([pet, rep], dim=1)
+
+    @torch.jit.export
+    def energies_and_llf(self, positions: torch.Tensor, cells: torch.Tensor, centers: torch.Tensor,
+                         neighbors: torch.Tensor, cell_shifts: torch.Tensor, species: torch.Tensor,
+                         system_indices: torch.Tensor):
+        pet, rep, llf = self.core.atomic_energies_and_llf_zbl(positions, cells, centers, neighbors, cell_shifts, species,
+                                                              system_indices, self.zbl)
+        return torch.cat([pet, rep], dim=1), llf
+
 
 class EnergyAndForces(torch.nn.Module):
     """What an exported model does around the core: total energies per system and forces by autograd, all inside
@@ -105,11 +186,15 @@ class ExportedEnergyModel(torch.nn.Module):
       ``dE/dcell`` of the HIP backward (``utils/evaluate_model.py`` strain trick, done analytically:
       ``dE/deps = R^T dE/dR + h^T dE/dh``).
 
+    * ``zbl``: the ``ZblTable`` of a ``zbl: true`` model (:func:`make_zbl`, :func:`make_core_and_zbl`): per-atom
+      and per-system energies are ``scale * PET + composition + ZBL`` -- the scaler does not touch additive terms
+      (``pet/model.py:595-660``) --, forces and stress include the ZBL term, ``selected_atoms`` masks it like the rest.
+
     ``forward`` returns ``(energies [S], forces [N, 3], stress [S, 3, 3] or empty, per_atom [n_selected])``."""
 
-    def __init__(self, core, scale: float = 1.0, composition: Optional[torch.Tensor] = None):
+    def __init__(self, core, scale: float = 1.0, composition: Optional[torch.Tensor] = None, zbl=None):
         super().__init__()
-        self.pet = PETScriptModule(core)
+        self.pet = PETScriptModule(core) if zbl is None else PETZblScriptModule(core, zbl)
         self.scale = float(scale)
         self.register_buffer("composition", composition.detach().clone().to(torch.float32)
                              if composition is not None else torch.zeros(0, dtype=torch.float32))
@@ -119,8 +204,11 @@ class ExportedEnergyModel(torch.nn.Module):
                 selected_atoms: Optional[torch.Tensor] = None, with_stress: bool = False):
         positions = positions.detach().requires_grad_(True)
         cells = cells.detach().requires_grad_(with_stress)
-        atomic = self.pet(positions, cells, centers, neighbors, cell_shifts, species, system_indices)[:, 0]
+        out = self.pet(positions, cells, centers, neighbors, cell_shifts, species, system_indices)
+        atomic = out[:, 0]
         atomic = atomic * self.scale
+        if out.shape[1] > 1:  # the ZBL column of PETZblScriptModule: added after the scaler
+            atomic = atomic + out[:, 1]
         keep = torch.ones(positions.shape[0], dtype=torch.bool, device=positions.device)
         if selected_atoms is not None:
             if selected_atoms.dtype == torch.bool:
@@ -166,12 +254,14 @@ class ExportedLLPRModel(torch.nn.Module):
 
     ``forward`` returns ``(energies [S], forces [N, 3], stress [S, 3, 3] or empty, per_atom [n_selected],
     energy_uncertainty [S], energy_uncertainty per selected atom [n_selected] or empty, energy_ensemble [S, K] or empty)``.
-    Ensemble members carry no forces (one adjoint per member: not served)."""
+    Ensemble members carry no forces (one adjoint per member: not served). With ``zbl`` (as in
+    :class:`ExportedEnergyModel`) the energies -- and so the mean the ensemble is centred on -- include the ZBL term;
+    uncertainties and the spread of the ensemble do not change."""
 
     def __init__(self, core, llpr_state: Dict[str, torch.Tensor], scale: float = 1.0,
-                 composition: Optional[torch.Tensor] = None):
+                 composition: Optional[torch.Tensor] = None, zbl=None):
         super().__init__()
-        self.pet = PETScriptModule(core)
+        self.pet = PETScriptModule(core) if zbl is None else PETZblScriptModule(core, zbl)
         self.scale = float(scale)
         self.register_buffer("composition", composition.detach().clone().to(torch.float32)
                              if composition is not None else torch.zeros(0, dtype=torch.float32))
@@ -200,10 +290,11 @@ class ExportedLLPRModel(torch.nn.Module):
         # energies, forces, stress, per-atom energies: the operations of ExportedEnergyModel.forward, in the same order
         positions = positions.detach().requires_grad_(True)
         cells = cells.detach().requires_grad_(with_stress)
-        atomic2, llf = self.pet.core.atomic_energies_and_llf(positions, cells, centers, neighbors, cell_shifts, species,
-                                                             system_indices)
+        atomic2, llf = self.pet.energies_and_llf(positions, cells, centers, neighbors, cell_shifts, species, system_indices)
         atomic = atomic2[:, 0]
         atomic = atomic * self.scale
+        if atomic2.shape[1] > 1:  # the ZBL column: added after the scaler
+            atomic = atomic + atomic2[:, 1]
         keep = torch.ones(positions.shape[0], dtype=torch.bool, device=positions.device)
         if selected_atoms is not None:
             if selected_atoms.dtype == torch.bool:

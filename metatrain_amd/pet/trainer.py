@@ -150,7 +150,11 @@ def extra_target_loss(name: str, spec: dict, preds: Dict[str, torch.Tensor], sys
 
 
 class TrainStep:
-    """One optimizer step on one batch (a ``HipGraph`` of several structures)."""
+    """One optimizer step on one batch (a ``HipGraph`` of several structures).
+
+    A ``zbl: true`` model is trained on ``ZBLHip.remove_from_targets(...)`` of its energy, gradient and strain-gradient
+    targets (``metatrain_amd/zbl.py``), as the reference's ``get_remove_additive_transform`` does: the ZBL term has no
+    parameters, is not part of the loss graph and is added back at evaluation (``ExportedEnergyModel(..., zbl=...)``)."""
 
     def __init__(self, model: HipModel, hypers: Optional[dict] = None, steps_per_epoch: int = 1):
         self.model = model

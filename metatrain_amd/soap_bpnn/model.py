@@ -18,8 +18,18 @@ from . import radial
 
 
 class SoapBpnnHip:
-    def __init__(self, hypers: dict, atomic_types: List[int], n_grid: int = 2049):
+    def __init__(self, hypers: dict, atomic_types: List[int], n_grid: int = 2049, zbl=None):
+        """``zbl``: a :class:`~metatrain_amd.zbl.ZBLHip`, ``True`` (default radii) or None (``hypers["zbl"]`` decides): the
+        additive ZBL term :meth:`evaluate` adds. ``forward`` / ``backward`` stay the network alone, which is what trains
+        (on ``ZBLHip.remove_from_targets`` of the targets)."""
         self.lib = _lib.load()
+        if zbl is None and hypers.get("zbl", False):
+            zbl = True
+        if zbl is True:
+            from ..zbl import ZBLHip
+
+            zbl = ZBLHip(atomic_types)
+        self.zbl = zbl or None
         self.hypers = hypers
         self.atomic_types = list(atomic_types)
         so = hypers["soap"]
@@ -116,6 +126,21 @@ class SoapBpnnHip:
         check(self.lib.soap_backward(self._handle, g.handle, rt._ptr(ws), ws.numel(), rt._ptr(ga), rt._ptr(gpos),
                                      rt._ptr(gcell), rt._stream()))
         return (gpos, gcell) if want_cell_grad else gpos
+
+    def evaluate(self, g: rt.HipGraph, want_cell_grad: bool = False, pbcs=None):
+        """Evaluation-time per-atom energies and ``dE/dR`` (and ``dE/dcell``): the network plus, for a model with
+        ``zbl``, the ZBL term on the same graph (or on a second one at the ZBL cutoff when this graph's is shorter: ``pbcs`` as in ``ZBLHip.graph_for``)."""
+        atomic = self.forward(g)
+        res = self.backward(g, torch.ones_like(atomic), want_cell_grad=want_cell_grad)
+        gpos, gcell = res if want_cell_grad else (res, None)
+        if self.zbl is not None:
+            zg = self.zbl.graph_for(g, pbcs)
+            atomic = atomic + self.zbl.forward(zg)
+            zres = self.zbl.backward(zg, want_cell_grad=want_cell_grad)
+            zpos, zcell = zres if want_cell_grad else (zres, None)
+            gpos = gpos + zpos
+            gcell = gcell + zcell if want_cell_grad else None
+        return (atomic, gpos, gcell) if want_cell_grad else (atomic, gpos)
 
     # ---- training (soap_bpnn/trainer.py:344-391) ---------------------------------------------------------------
     def sum_over_atoms(self, g: rt.HipGraph, atomic: torch.Tensor) -> torch.Tensor:

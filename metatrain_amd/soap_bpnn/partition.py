@@ -24,12 +24,19 @@ def energy_and_gradient(model, positions: torch.Tensor, species: torch.Tensor, c
     """Energy and dE/dR ``[N, 3]`` of one box, rank ``rank``'s share computed here and summed over ranks by
     ``all_reduce(tensor)`` (in place; ``None``: return the partial results -- the caller, or a single-process test,
     adds them). ``model``: a loaded :class:`SoapBpnnHip` (anything with ``cutoff``, ``graph``, ``forward``, ``backward``);
-    ``neighbor_list``: the device neighbour list by default. Returns ``(energy [1], gradient [N, 3], n_sub, n_owned)``."""
+    ``neighbor_list``: the device neighbour list by default. A model with a ZBL term (``SoapBpnnHip(..., zbl=...)`` or
+    ``zbl: true``) gets it added on the same graph, weighted by the same owned-atom seeds; one whose cutoff is below the ZBL
+    cutoff is refused (the halo is one model cutoff). Returns ``(energy [1], gradient [N, 3], n_sub, n_owned)``."""
     if neighbor_list is None:
         from .. import runtime as rt
 
         neighbor_list = rt.neighbor_list
     cutoff = float(model.cutoff)
+    z = getattr(model, "zbl", None)
+    if z is not None:
+        from ..zbl import zbl_on_model_graph
+
+        z = zbl_on_model_graph(z, True, model.atomic_types, cutoff, False, "the partitioned box")
     index, owned, _ = slab_partition(positions, cell, pbc, cutoff, world, rank)
     dev = positions.device
     n = positions.shape[0]
@@ -44,6 +51,9 @@ def energy_and_gradient(model, positions: torch.Tensor, species: torch.Tensor, c
         seeds = owned.to(torch.float32)
         atomic = model.forward(g)
         grad_sub = model.backward(g, seeds)
+        if z is not None:
+            atomic = atomic + z.forward(g)
+            grad_sub = grad_sub + z.backward(g, seeds)
         buf[: 3 * n].view(n, 3)[index] = grad_sub
         buf[3 * n] = (atomic * seeds).sum()
     if all_reduce is not None:

@@ -438,6 +438,25 @@ int pet_backward_train2_seeded(const pet_model_t* m, const pet_graph_t* g, void*
                                const float* d_nu_atomic, const float* d_u, const float* d_u_cell, float* d_tangent_atomic,
                                const float* const* h_seed_node_features, const float* const* h_seed_edge_features,
                                int32_t n_layers, void* stream);
+/* ---- Hessian-vector products of the fused single-property target (second derivatives w.r.t. positions and cells) ------
+ * With e_i the per-atom predictions and e'_i = d/d eps e_i(R + eps u, cell + eps u_cell):
+ *   d_hvp_positions [N,3] = grad_R    sum_i lambda_i e'_i      (lambda = ones: H u of the total energy, H = d2E/dR dR,
+ *   d_hvp_cells [S,3,3]   = grad_cell sum_i lambda_i e'_i       and its mixed position / cell blocks),
+ *   d_tangent_atomic [N]  = e'_i  (so that sum_i lambda_i e'_i = <u, dE_lambda/dR> + <u_cell, dE_lambda/dcell>).
+ * d_lambda_atomic NULL = ones; d_u_cell, d_hvp_cells and d_tangent_atomic may be NULL (a cell direction or a cell result
+ * needs a pet_graph_build handle, for the cell shifts). No pet_forward and no pet_model_zero_grad is needed, and no
+ * gradient slot is touched: the call evaluates the model itself, as a dual (primal, tangent) forward along (u, u_cell)
+ * and a joint reverse sweep down to the geometry. It runs on the SIZE-GENERIC kernels of the training pass for every
+ * model and graph that pass serves -- every size (the default size included: there is no tuned Hessian-vector path),
+ * PreLN / PostLN, both featurisers, both normalisations, system conditioning, any number of neighbours per atom -- in
+ * fp32 FMA with fixed summation orders and no float atomics (the same bits run to run).
+ * PET_ERR_UNSUPPORTED: an adaptive-cutoff model (the second-order implicit derivative of the cutoff solver is not built)
+ * and a graph with a per-layer exchange (pet_graph_set_exchange). A batch without edges and empty systems give zeros.
+ * The ZBL term (pet_zbl_*) is not part of it. */
+int64_t pet_hvp_workspace_bytes_for(const pet_model_t* m, const pet_graph_t* g);
+int pet_hessian_vector(const pet_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,
+                       const float* d_lambda_atomic, const float* d_u, const float* d_u_cell, float* d_hvp_positions,
+                       float* d_hvp_cells, float* d_tangent_atomic, void* stream);
 /* Per-system sum (utils/sum_over_atoms.py:10-48): d_out[S] = sum_{atoms of s} d_atomic. */
 int pet_sum_over_atoms(const pet_graph_t* g, const float* d_atomic, float* d_out, void* stream);
 

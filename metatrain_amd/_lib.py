@@ -20,6 +20,7 @@ PET_OK = 0
 PET_CUTOFF_COSINE = 0
 PET_CUTOFF_BUMP = 1
 PET_ERR_ARGUMENT = -3
+PET_ERR_UNSUPPORTED = -2
 PET_LLPR_MAX_ENSEMBLE = 16384
 
 # every symbol include/pet_hip.h declares (tests check the library exports them all)
@@ -41,7 +42,7 @@ SYMBOLS = [
     "pet_model_set_lora_scaling", "pet_model_set_trainable",
     "pet_train2_workspace_bytes", "pet_backward_train2", "pet_backward_train2_cell",
     "pet_train_predict", "pet_train_predict_backward", "pet_backward_train_seeded", "pet_backward_train2_seeded",
-    "pet_sum_over_atoms",
+    "pet_sum_over_atoms", "pet_hvp_workspace_bytes_for", "pet_hessian_vector",
     "pet_llpr_feature_size", "pet_llpr_features", "pet_llpr_rows", "pet_llpr_covariance_accumulate",
     "pet_llpr_covariance_finalize", "pet_llpr_variance", "pet_llpr_ensemble",
     "pet_zbl_create", "pet_zbl_destroy", "pet_zbl_cutoff", "pet_zbl_pair_table", "pet_zbl_workspace_bytes",
@@ -209,6 +210,9 @@ def load() -> ctypes.CDLL:
     lib.pet_backward_train_seeded.argtypes = [P, P, P, c_int64, P, P, P, P, P, c_int32, P]
     lib.pet_backward_train2_seeded.argtypes = [P, P, P, c_int64, P, c_int64, P, P, P, P, P, P, P, c_int32, P]
     lib.pet_sum_over_atoms.argtypes = [P, P, P, P]
+    lib.pet_hvp_workspace_bytes_for.argtypes = [P, P]
+    lib.pet_hvp_workspace_bytes_for.restype = c_int64
+    lib.pet_hessian_vector.argtypes = [P, P, P, c_int64, P, P, P, P, P, P, P]
     lib.pet_llpr_feature_size.argtypes = [P]
     lib.pet_llpr_feature_size.restype = c_int64
     lib.pet_llpr_features.argtypes = [P, P, c_char_p, c_char_p, P, P, c_int32, P, P, P]

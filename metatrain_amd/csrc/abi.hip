@@ -781,6 +781,29 @@ int pet_backward_train2_seeded(const pet_model_t* pm, const pet_graph_t* pg, voi
     return lora_end(m, st);
 }
 
+int64_t pet_hvp_workspace_bytes_for(const pet_model_t* pm, const pet_graph_t* pg) {
+    if (!pm || !pg) return -1;
+    return gen_hvp_workspace_bytes(pm->m, pg->g.n_nodes, pg->g.n_edges);
+}
+
+int pet_hessian_vector(const pet_model_t* pm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
+                       const float* d_lambda_atomic, const float* d_u, const float* d_u_cell, float* d_hvp_positions,
+                       float* d_hvp_cells, float* d_tangent_atomic, void* stream) {
+    PET_REQUIRE(pm && pg, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
+    PET_REQUIRE(pm->m.h.num_neighbors_adaptive <= 0.f && !pg->g.adaptive, PET_ERR_UNSUPPORTED,
+                "Hessian-vector products of an adaptive-cutoff model are not built (the cutoff solver's second-order "
+                "implicit derivative)");
+    PET_REQUIRE(!pg->g.x_fn, PET_ERR_UNSUPPORTED,
+                "Hessian-vector products on a graph with a per-layer exchange (pet_graph_set_exchange) are not built");
+    PET_REQUIRE(!(d_u_cell || d_hvp_cells) || pg->g.shift || pg->g.n_edges == 0, PET_ERR_ARGUMENT,
+                "a cell direction / cell result needs a pet_graph_build handle (cell shifts)");
+    if (pg->g.n_nodes > 0)
+        PET_REQUIRE(d_workspace && d_u && d_hvp_positions, PET_ERR_ARGUMENT, "null argument");
+    return gen_hvp(pm->m, pg->g, d_workspace, workspace_bytes, d_lambda_atomic, d_u, d_u_cell, d_hvp_positions, d_hvp_cells,
+                   d_tangent_atomic, (hipStream_t)stream);
+}
+
 int64_t pet_nl_workspace_bytes(int64_t n_atoms) { return nl_workspace_bytes(n_atoms); }
 
 int pet_nl_build(const float* d_positions, const float* h_cell, const int32_t* h_pbc, int64_t n_atoms,

@@ -333,8 +333,11 @@ __global__ __launch_bounds__(64) void k_gt_attn_rev_q(const float* __restrict__ 
     }
 }
 
-// pass K (lanes = keys): (nu, lambda) of k and v
-template <int HDM>
+// pass K (lanes = keys): (nu, lambda) of k and v. TAP (the Hessian-vector product): also the adjoints of the key's mask bias
+// b = log max(fc, 1e-15) and of its tangent b', SB / SDB [NH][E] = sum over the queries of p (pbar - d_q) and p (pdb - c_q)
+// (no `scale`: the bias enters the logit unscaled). A lane owns one key and walks ALL queries of the row, so the sums are
+// complete whichever 64-key chunk the key sits in. TAP = false is the training pass' kernel, unchanged.
+template <int HDM, bool TAP = false>
 __global__ __launch_bounds__(64) void k_gt_attn_rev_k(const float* __restrict__ Qp, const float* __restrict__ Qt,
                                                       const float* __restrict__ NOp, const float* __restrict__ NOt,
                                                       const float* __restrict__ LSE, const float* __restrict__ MS,
@@ -342,7 +345,7 @@ __global__ __launch_bounds__(64) void k_gt_attn_rev_k(const float* __restrict__ 
                                                       const int* __restrict__ rowptr, const float* __restrict__ fc,
                                                       const float* __restrict__ bd, float* __restrict__ NQp,
                                                       float* __restrict__ NQt, int64_t E, int D, int NH, int HD,
-                                                      float scale) {
+                                                      float scale, float* __restrict__ SB, float* __restrict__ SDB) {
     const int i = blockIdx.x, h = blockIdx.y, lane = threadIdx.x;
     const int p0 = rowptr[i], T = rowptr[i + 1] - p0 + 1;
     const int64_t ld = 3 * (int64_t)D;
@@ -361,6 +364,7 @@ __global__ __launch_bounds__(64) void k_gt_attn_rev_k(const float* __restrict__ 
         }
         const float bias = tk == 0 ? 0.f : logf(fmaxf(fc[p0 + tk - 1], 1e-15f));
         const float biasd = tk == 0 ? 0.f : bd[p0 + tk - 1];
+        float tb = 0.f, tdb = 0.f;
         for (int tq = 0; tq < T; tq++) {
             const int64_t rq = tq == 0 ? E + i : (int64_t)p0 + tq - 1;
             const float* qp = Qp + rq * ld + h * HD;
@@ -383,6 +387,7 @@ __global__ __launch_bounds__(64) void k_gt_attn_rev_k(const float* __restrict__ 
             const float p = expf(s - LSE[rq * NH + h]);
             const float pb = av + bvd + pdb * (sd - m) - sd * cc;
             const float sb = p * (pb - dq) * scale, sdb = p * (pdb - cc) * scale, pd = p * (sd - m);
+            if constexpr (TAP) { tb += p * (pb - dq); tdb += p * (pdb - cc); }
 #pragma unroll
             for (int d = 0; d < HDM; d++)
                 if (d < HD) {
@@ -400,7 +405,75 @@ __global__ __launch_bounds__(64) void k_gt_attn_rev_k(const float* __restrict__ 
                 NQp[rk * ld + 2 * D + h * HD + d] = vb[d];
                 NQt[rk * ld + 2 * D + h * HD + d] = vdb[d];
             }
+        if constexpr (TAP) if (tk > 0) {   // (the centre token carries no bias); p0 + tk - 1 < rowptr[i + 1] <= E
+            SB[(int64_t)h * E + p0 + tk - 1] = tb;
+            SDB[(int64_t)h * E + p0 + tk - 1] = tdb;
+        }
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Hessian-vector product: the three taps of sweep 2 that reach the geometry, and the geometry kernel
+// ---------------------------------------------------------------------------------------------
+// tap 2, reduction: (db, db') (+)= sum over the heads, in head order, of one attention layer's SB / SDB
+__global__ void k_hvp_bias_sum(const float* __restrict__ SB, const float* __restrict__ SDB, int NH, int64_t E,
+                               float* __restrict__ db, float* __restrict__ dbd, int acc) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= E) return;
+    float a = 0.f, b = 0.f;
+    for (int h = 0; h < NH; h++) { a += SB[(int64_t)h * E + p]; b += SDB[(int64_t)h * E + p]; }
+    db[p] = acc ? db[p] + a : a;
+    dbd[p] = acc ? dbd[p] + b : b;
+}
+// tap 3: e_i = .. + sum_e fc_e ep_e, e'_i = .. + sum_e (fc'_e ep_e + fc_e ep'_e)  =>  dJ/dfc = nu_i ep + lambda_i ep',
+// dJ/dfc' = lambda_i ep (summed over the readout layers in layer order)
+__global__ void k_hvp_fc_adj(const float* __restrict__ nA, const float* __restrict__ lA, const int* __restrict__ ctr,
+                             const float* __restrict__ epp, const float* __restrict__ ept, float* __restrict__ dfc,
+                             float* __restrict__ dfcd, int acc, int64_t E) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= E) return;
+    const int64_t i = ctr[p];
+    const float n = nA ? nA[i] : 0.f, l = lA ? lA[i] : 0.f;
+    const float a = n * epp[p] + l * ept[p], b = l * epp[p];
+    dfc[p] = acc ? dfc[p] + a : a;
+    dfcd[p] = acc ? dfcd[p] + b : b;
+}
+// the geometry kernel: the (nu, lambda) pairs of geo = (v, d), of the key bias b and of the cutoff factor fc folded into
+// ONE dJ/dv per edge -- the reverse of exactly what k_gt_geo computes, with v' held fixed (it does not depend on R):
+//   d = sqrt(v.v + 1e-15), d' = w / d (w = v.v'):     dd/dv = v / d,            dd'/dv = v'/d - w v / d^3
+//   fc = f(d0), fc' = f'(d0) w / |v| (d0 = |v|):      dfc/dv = f' v / |v|,      dfc'/dv = f'' w v / |v|^2 + f' (v'/|v| - w v / |v|^3)
+//   b = log max(fc, 1e-15), b' = fc' / fc:            both flat where fc <= 1e-15; else dJ/dfc += db / fc - db' fc' / fc^2,
+//                                                     dJ/dfc' += db' / fc
+// The lambda half of geo's adjoint (that of v' and d') multiplies quantities that do not move with R, except d' above.
+// fc and fc' in the fold of b' are the fp32 values the dual forward used (k_gt_geo: fc' from the fp32 cutoff_deriv), while
+// f' and f'' here are evaluated in double: the adjoint of the formulas, not of the forward's roundings -- they differ by
+// the fp32 rounding of f' (1e-7 relative), far inside the bar.
+// Written as a [E, 4] "dgeo" with a zero distance slot: the scatter backward_geometry_generic then passes it through.
+__global__ void k_hvp_geo(const float4* __restrict__ geo, const float4* __restrict__ geod, const float* __restrict__ d0,
+                          const float* __restrict__ fc, const float* __restrict__ fcd, const float4* __restrict__ ngeo,
+                          const float4* __restrict__ lgeo, const float* __restrict__ db, const float* __restrict__ dbd,
+                          const float* __restrict__ dfc, const float* __restrict__ dfcd, float4* __restrict__ dv, int64_t E,
+                          float cutoff, float width, int fn) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= E) return;
+    const float4 g = geo[p], gt = geod[p], ng = ngeo[p], lg = lgeo[p];
+    const double vx = g.x, vy = g.y, vz = g.z, tx = gt.x, ty = gt.y, tz = gt.z, dist = g.w;
+    const double w = vx * tx + vy * ty + vz * tz, nrm = sqrt(vx * vx + vy * vy + vz * vz);
+    double af = dfc[p], afd = dfcd[p];
+    const double f = fc[p], fd = fcd[p];
+    if (fc[p] > 1e-15f) {
+        af += (double)db[p] / f - (double)dbd[p] * fd / (f * f);
+        afd += (double)dbd[p] / f;
+    }
+    // dJ/dv = ng.xyz + cv v + ct v'
+    double cv = (double)ng.w / dist - (double)lg.w * w / (dist * dist * dist), ct = (double)lg.w / dist;
+    if (nrm > 0.0) {
+        double f1, f2;
+        cutoff_deriv2(d0[p], cutoff, width, fn, &f1, &f2);
+        cv += af * f1 / nrm + afd * (f2 * w / (nrm * nrm) - f1 * w / (nrm * nrm * nrm));
+        ct += afd * f1 / nrm;
+    }
+    dv[p] = make_float4((float)(ng.x + cv * vx + ct * tx), (float)(ng.y + cv * vy + ct * ty), (float)(ng.z + cv * vz + ct * tz), 0.f);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -627,7 +700,10 @@ struct TOps {
     TWs* w;
     std::map<const float*, float*> off;   // raw parameter storage -> its gradient slot
     int err = PET_OK;
-    TOps(const Model& m_, const Graph& g_, hipStream_t s, TWs* w_) : m(m_), g(g_), d(dims_of(m_)), st(s), lin{s}, o(m_, g_, s), w(w_) {
+    bool hvp = false;   // Hessian-vector mode: the sweep forms no parameter gradient and never looks at a gradient slot
+    TOps(const Model& m_, const Graph& g_, hipStream_t s, TWs* w_, bool hvp_ = false)
+        : m(m_), g(g_), d(dims_of(m_)), st(s), lin{s}, o(m_, g_, s), w(w_), hvp(hvp_) {
+        if (hvp) return;
         for (const auto& kv : m.raw) {
             auto it = m.grad_off.find(kv.first);
             if (it != m.grad_off.end()) off[kv.second.first] = m.grad_flat + it->second;
@@ -687,7 +763,7 @@ struct TOps {
     }
     // dW += nu_y^T x + lambda_y^T x', db += colsum(nu_y)
     void wgrad(const Lin& L, const D2& NY, int64_t ldy, const D2& X, int64_t ldx, int64_t rows) {
-        if (rows <= 0 || err) return;
+        if (rows <= 0 || err || hvp) return;
         int nc; int64_t per;
         chunked(rows, nc, per);
         float* gw = slot(L.w);
@@ -706,7 +782,7 @@ struct TOps {
         k_gt_reduce<<<g1(W), 256, 0, st>>>(w->part, nc, W, dst);
     }
     void embed_grad(const int* index, const float* NU, int64_t ld, int64_t rows, int W, const float* table) {
-        if (rows <= 0 || err) return;
+        if (rows <= 0 || err || hvp) return;
         float* dst = slot(table);
         if (!dst) return;
         int nc; int64_t per;
@@ -726,7 +802,9 @@ struct TOps {
                   int W, int ln = -1, float e = -1.f) {
         if (rows <= 0) return;
         const int l = ln < 0 ? (int)m.layer_norm() : ln;
-        k_gt_norm_rev<<<(int)cdiv(rows, 4), 256, 0, st>>>(X.p, X.t, gamma, l, e < 0 ? eps() : e, NY.p, NY.t, NX.p, NX.t, acc, G, rows, W);
+        k_gt_norm_rev<<<(int)cdiv(rows, 4), 256, 0, st>>>(X.p, X.t, gamma, l, e < 0 ? eps() : e, NY.p, NY.t, NX.p, NX.t, acc,
+                                                          hvp ? nullptr : G, rows, W);
+        if (hvp) return;
         colsum(G, W, rows, W, slot(gamma));
         if (l && beta) colsum(NY.p, W, rows, W, slot(beta));
     }
@@ -848,10 +926,14 @@ int64_t gen_train_workspace_bytes(const Model& m, int64_t N, int64_t E) {
 // pair per readout layer, added to the nu half where the fused head's adjoint enters the backbone (first-order terms: the
 // lambda half is theirs no more than a tangent is). lA and nA both null: no fused target in the loss, its heads are
 // neither needed nor touched.
+// hv (gen_hvp below): Hessian-vector mode. No parameter gradient is formed and no gradient slot is touched; sweep 2 instead
+// keeps the adjoints that reach the geometry -- of geo = (v, d), of the key bias and of the cutoff factor, each a
+// (nu, lambda) pair -- and k_hvp_geo folds them into hv->dv = dJ/dv [E, 4]. Needs u and a static cutoff.
 int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, const float* lA, const float* nA, const float* u,
                const float* ucell, float* tangent_atomic, hipStream_t st, const float* const* seed_node,
-               const float* const* seed_edge, int n_seed) {
-    PET_REQUIRE(m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
+               const float* const* seed_edge, int n_seed, const HvpTaps* hv) {
+    PET_REQUIRE(hv || m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
+    PET_REQUIRE(!hv || (u && !g.adaptive && n_seed == 0), PET_ERR_ARGUMENT, "Hessian-vector mode: a direction, a static cutoff, no seeds");
     PET_REQUIRE(n_seed == 0 || n_seed == m.num_readout_layers(), PET_ERR_ARGUMENT, "expected one seed pair per readout layer");
     const bool fused = lA || nA;
     if (!fused) {
@@ -867,7 +949,7 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
     TWs w;
     train_carve(m, g.n_nodes, g.n_edges, ws2, w);
     PET_REQUIRE((int64_t)w.bytes <= ws2_bytes, PET_ERR_ARGUMENT, "second-order workspace too small");
-    TOps t(m, g, st, &w);
+    TOps t(m, g, st, &w, hv != nullptr);
     const GD& d = t.d;
     const int64_t N = g.n_nodes, E = g.n_edges, R = N + E;
     if (N == 0) return PET_OK;
@@ -1047,6 +1129,7 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
         if (tangent_atomic)
             k_gt_atom_sum<<<g1(N), 256, 0, st>>>(npred.p, npred.t, epred.p, epred.t, g.fc, w.fcd, g.rowptr, tangent_atomic,
                                                  l > 0, N);
+        if (hv && E > 0) k_hvp_fc_adj<<<g1(E), 256, 0, st>>>(nA, lA, g.ctr, epred.p, epred.t, hv->dfc, hv->dfcd, l > 0, E);
         // reverse of the node head
         t.wgrad(ln, nnp, 1, w.tN[3], DH, N);
         t.linb(nnp, 1, ln, w.tN[3], DH, N);                                                       // (nu, lambda) of s2
@@ -1104,7 +1187,7 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
             t.axpby(1.f, w.tE[1], 2 * D, 1.f, dCATr, 2 * D, g.rev, dXF, D, true, E, D);
             t.copy(w.dM, dMin, E, D);
         }
-        if (conditioned)
+        if (conditioned && !hv)
             k_gt_cond_accum<<<(int)g.n_cond_systems, 256, 0, st>>>(w.dH.p, g.sys, g.cond_sys, (int)N, DN, dcond, gi == L - 1 ? 0 : 1);
         for (int a = AL - 1; a >= 0; a--) {
             const AttnLayerW& A = G.attn[a];
@@ -1158,10 +1241,18 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
                 k_gt_attn_rev_q<HDM><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
                     Ab.QKV.p, Ab.QKV.t, dAO.p, dAO.t, Ab.LSE, Ab.MS, g.rowptr, g.fc, w.bd, w.dQKV.p, w.dQKV.t, w.CC, w.DD, E, D, d.NH,
                     d.HD, scale);
-                k_gt_attn_rev_k<HDM><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
-                    Ab.QKV.p, Ab.QKV.t, dAO.p, dAO.t, Ab.LSE, Ab.MS, w.CC, w.DD, g.rowptr, g.fc, w.bd, w.dQKV.p, w.dQKV.t, E, D, d.NH,
-                    d.HD, scale);
+                if (!hv)
+                    k_gt_attn_rev_k<HDM><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
+                        Ab.QKV.p, Ab.QKV.t, dAO.p, dAO.t, Ab.LSE, Ab.MS, w.CC, w.DD, g.rowptr, g.fc, w.bd, w.dQKV.p, w.dQKV.t, E, D,
+                        d.NH, d.HD, scale, nullptr, nullptr);
+                else
+                    k_gt_attn_rev_k<HDM, true><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
+                        Ab.QKV.p, Ab.QKV.t, dAO.p, dAO.t, Ab.LSE, Ab.MS, w.CC, w.DD, g.rowptr, g.fc, w.bd, w.dQKV.p, w.dQKV.t, E, D,
+                        d.NH, d.HD, scale, hv->sb, hv->sdb);
             });
+            if (hv && E > 0) {   // heads in head order, attention layers and GNN layers in the order the sweep visits them
+                k_hvp_bias_sum<<<g1(E), 256, 0, st>>>(hv->sb, hv->sdb, d.NH, E, hv->db, hv->dbd, !(gi == L - 1 && a == AL - 1));
+            }
             if (!post) {
                 t.norm(Ab.X, A.g_attn, A.b_attn, w.tE[0], R, D);                                  // input of input_linear
                 t.wgrad(A.qkv, w.dQKV, 3 * D, w.tE[0], D, R);
@@ -1189,6 +1280,7 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
             D2 dTOK = w.tE[1];
             t.linb(w.tE[0], D, G.c0, dTOK, kin, E);
             t.wgrad(G.eemb, dTOK, kin, w.geo, 4, E);
+            if (hv) t.linb(dTOK, kin, G.eemb, D2{hv->ngeo, hv->lgeo}, 4, E, gi != L - 1);   // (nu, lambda) of geo, over the layers
             if (gi > 0) t.embed_grad(g.sp_nbr, dTOK.p + D, kin, E, D, G.nbr_emb);
             D2 dMsg{dTOK.p + (gi == 0 ? D : 2 * D), dTOK.t + (gi == 0 ? D : 2 * D)};
             t.axpby(1.f, dMsg, kin, 0.f, D2(), 0, nullptr, dMin, D, true, E, D);
@@ -1202,7 +1294,7 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
         }
     }
     t.embed_grad(g.sp_nbr, w.dM.p, D, E, D, m.edge_emb);   // the first layer's messages are the neighbour embedding
-    if (conditioned) {
+    if (conditioned && !hv) {
         float *gq = t.slot(m.cond_qe), *gm = t.slot(m.cond_se), *gw0 = t.slot(m.cond_w0), *gb0 = t.slot(m.cond_b0),
               *gw2 = t.slot(m.cond_w2), *gb2 = t.slot(m.cond_b2);
         if (!t.err)
@@ -1211,8 +1303,69 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
                                                                   m.h.max_charge, m.h.max_spin_multiplicity, DN, gq, gm, gw0,
                                                                   gb0, gw2, gb2);
     }
+    if (hv && E > 0)
+        k_hvp_geo<<<g1(E), 256, 0, st>>>(g.geo, reinterpret_cast<const float4*>(w.geo.t), g.d0, g.fc, w.fcd,
+                                         reinterpret_cast<const float4*>(hv->ngeo), reinterpret_cast<const float4*>(hv->lgeo),
+                                         hv->db, hv->dbd, hv->dfc, hv->dfcd, reinterpret_cast<float4*>(hv->dv), E, m.h.cutoff,
+                                         m.h.cutoff_width, m.h.cutoff_function);
     PET_HIP_CHECK(hipGetLastError());
     return t.err;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Hessian-vector product of the fused single-property target (pet_hessian_vector)
+// ---------------------------------------------------------------------------------------------
+namespace {
+__global__ void k_hvp_fill(float* __restrict__ x, float v, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) x[i] = v;
+}
+// the taps and the unit weights, carved behind the dual activations of the training pass
+static size_t hvp_carve(const Model& m, int64_t N, int64_t E, void* base, size_t train_bytes, HvpTaps& h, float** ones) {
+    Carver c(base);
+    c.off = train_bytes;
+    const size_t Ea = E > 0 ? E : 1, Na = N > 0 ? N : 1;
+    h.ngeo = c.take<float>(4 * Ea); h.lgeo = c.take<float>(4 * Ea);
+    h.sb = c.take<float>(Ea * m.h.num_heads); h.sdb = c.take<float>(Ea * m.h.num_heads);
+    h.db = c.take<float>(Ea); h.dbd = c.take<float>(Ea);
+    h.dfc = c.take<float>(Ea); h.dfcd = c.take<float>(Ea);
+    h.dv = c.take<float>(4 * Ea);
+    *ones = c.take<float>(Na);
+    return c.off;
+}
+}  // namespace
+
+int64_t gen_hvp_workspace_bytes(const Model& m, int64_t N, int64_t E) {
+    HvpTaps h;
+    float* ones;
+    return (int64_t)hvp_carve(m, N, E, nullptr, (size_t)gen_train_workspace_bytes(m, N, E), h, &ones);
+}
+
+// hvp_pos [N, 3] (and hvp_cell [S, 3, 3]) = grad_R (grad_cell) of sum_i lambda_i e'_i, e'_i = d/d eps e_i(R + eps u,
+// cell + eps ucell): gen_train2 with nu = 0 in Hessian-vector mode, then the scatter of the first-order geometry adjoint.
+int gen_hvp(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* lA, const float* u, const float* ucell,
+            float* hvp_pos, float* hvp_cell, float* tangent_atomic, hipStream_t st) {
+    const int64_t N = g.n_nodes, E = g.n_edges;
+    if (hvp_cell && g.n_systems > 0) PET_HIP_CHECK(hipMemsetAsync(hvp_cell, 0, g.n_systems * 9 * sizeof(float), st));
+    if (N == 0) return PET_OK;
+    if (E == 0) {   // isolated atoms: nothing moves with the positions
+        PET_HIP_CHECK(hipMemsetAsync(hvp_pos, 0, N * 3 * sizeof(float), st));
+        if (tangent_atomic) PET_HIP_CHECK(hipMemsetAsync(tangent_atomic, 0, N * sizeof(float), st));
+        return PET_OK;
+    }
+    HvpTaps h;
+    float* ones;
+    const size_t train_bytes = (size_t)gen_train_workspace_bytes(m, N, E);
+    const size_t need = hvp_carve(m, N, E, ws, train_bytes, h, &ones);
+    PET_REQUIRE((int64_t)need <= ws_bytes, PET_ERR_ARGUMENT, "Hessian-vector workspace too small");
+    if (!lA) {
+        k_hvp_fill<<<g1(N), 256, 0, st>>>(ones, 1.f, N);
+        lA = ones;
+    }
+    int rc = gen_train2(m, g, ws, (int64_t)train_bytes, lA, nullptr, u, ucell, tangent_atomic, st, nullptr, nullptr, 0, &h);
+    if (rc) return rc;
+    // (h.ngeo is spent: it serves as the scatter's d/d(edge vector) scratch)
+    return backward_geometry_generic(m, g, h.ngeo, h.dv, nullptr, nullptr, hvp_pos, hvp_cell, st);
 }
 
 // Adjoint of gen_train_predict for `n_blocks` blocks of one (target, readout layer), seeds gA[b] [N, P_b]: dL/dtheta of the

@@ -248,11 +248,23 @@ int gen_backward_geometry(const Model& m, const Graph& g, void* ws, int64_t ws_b
 int64_t gen_train_workspace_bytes(const Model& m, int64_t n_nodes, int64_t n_edges);
 int norm_rev_rows(const float* Xp, const float* Xt, const float* gamma, int ln, float eps, const float* NYp, const float* NYt,
                   float* NXp, float* NXt, int64_t R, int W, hipStream_t st);
+// Hessian-vector mode of gen_train2 (gen_hvp): no parameter gradients, the adjoints that reach the geometry are kept instead
+struct HvpTaps {
+    float *ngeo, *lgeo;   // (nu, lambda) of geo = (v, d) [E, 4], summed over the GNN layers
+    float *sb, *sdb;      // one attention layer's key-bias adjoints per head [NH][E]
+    float *db, *dbd;      // ... summed over heads and layers [E]: adjoints of b = log max(fc, 1e-15) and of b'
+    float *dfc, *dfcd;    // adjoints of fc and fc' from the atom sums of the readout layers [E]
+    float* dv;            // result: dJ/d(edge vector) [E, 4], last slot zero
+};
 // seed_node / seed_edge [n_seed] (n_seed = 0 or num_readout_layers(); NULL entries = 0): first-order feature adjoints of
 // further targets, added to the nu half of every readout layer's adjoint. lA and nA both NULL: no fused target in the loss
 int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, const float* lA, const float* nA, const float* u,
                const float* ucell, float* tangent_atomic, hipStream_t st, const float* const* seed_node = nullptr,
-               const float* const* seed_edge = nullptr, int n_seed = 0);
+               const float* const* seed_edge = nullptr, int n_seed = 0, const HvpTaps* hv = nullptr);
+// Hessian-vector product of the fused single-property target on the size-generic dual pass (pet_hessian_vector)
+int64_t gen_hvp_workspace_bytes(const Model& m, int64_t n_nodes, int64_t n_edges);
+int gen_hvp(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* lA, const float* u, const float* ucell,
+            float* hvp_pos, float* hvp_cell, float* tangent_atomic, hipStream_t st);
 // further targets of a training step on a size-generic training workspace (train_predict / train_predict_backward)
 int gen_train_predict(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int layer, const HeadW& H, const LastW& Lw,
                       float* atomic, hipStream_t st);

@@ -138,6 +138,107 @@ struct PetHipModule : torch::CustomClassHolder {
     at::Tensor llpr_ensemble(const at::Tensor& x, const at::Tensor& weights, int64_t K, const at::Tensor& prediction);
 };
 
+// dE_lambda/dR and dE_lambda/dcell as a differentiable function of (lambda = grad_atomic, positions, cells): the node
+// EnergyFn::backward goes through when a graph is being recorded (create_graph=True). Its own backward is one
+// pet_hessian_vector call: for the incoming (u, u_cell) = d/d(dE/dR), d/d(dE/dcell)
+//   d/d positions = grad_R sum_i lambda_i e'_i,  d/d cells = grad_cell of the same,  d/d lambda_i = e'_i,
+// so torch.autograd.grad(<dE/dR, u>, positions) and torch.autograd.functional.hvp work, eagerly and scripted.
+struct EnergyGradFn : torch::autograd::Function<EnergyGradFn> {
+    static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, const at::Tensor& grad_atomic,
+                                                  const at::Tensor& positions, const at::Tensor& cells,
+                                                  c10::intrusive_ptr<GraphHolder> gh, c10::intrusive_ptr<PetHipModule> mod,
+                                                  bool has_zbl) {
+        at::Tensor ga = as_f32(grad_atomic.reshape({-1}));
+        at::Tensor gpos = at::empty({gh->n_nodes, 3}, ga.options());
+        at::Tensor gcell = at::empty({gh->n_systems, 3, 3}, ga.options());
+        check(pet_backward(mod->model, gh->g, gh->fwd_ws.data_ptr(), gh->fwd_ws.numel(), ga.data_ptr<float>(),
+                           gpos.data_ptr<float>(), gcell.data_ptr<float>(), stream_of(ga)),
+              "pet_backward");
+        ctx->save_for_backward({grad_atomic});
+        ctx->saved_data["graph"] = gh;
+        ctx->saved_data["module"] = mod;
+        ctx->saved_data["has_zbl"] = has_zbl;
+        ctx->saved_data["pos_dtype"] = (int64_t)positions.scalar_type();
+        ctx->saved_data["cell_dtype"] = (int64_t)cells.scalar_type();
+        return {gpos.to(positions.scalar_type()), gcell.to(cells.scalar_type())};
+    }
+
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
+                                                   torch::autograd::variable_list go);
+};
+
+// One pet_hessian_vector call: (hvp_positions [N,3], hvp_cells [S,3,3], tangent_atomic [N]) in fp32 for the weights lam [N]
+// and the direction (u, u_cell); undefined u / u_cell = zero.
+static std::vector<at::Tensor> hessian_vector(const c10::intrusive_ptr<PetHipModule>& mod, const c10::intrusive_ptr<GraphHolder>& gh,
+                                              const at::Tensor& lam, const at::Tensor& u_, const at::Tensor& ucell_) {
+    auto f32 = lam.options();
+    at::Tensor u = u_.defined() ? as_f32(u_).reshape({gh->n_nodes, 3}) : at::zeros({gh->n_nodes, 3}, f32);
+    at::Tensor ucell;
+    if (ucell_.defined()) ucell = as_f32(ucell_).reshape({gh->n_systems, 3, 3});
+    at::Tensor hp = at::empty({gh->n_nodes, 3}, f32), hc = at::empty({gh->n_systems, 3, 3}, f32), tan = at::empty({gh->n_nodes}, f32);
+    at::Tensor ws = at::empty({std::max<int64_t>(pet_hvp_workspace_bytes_for(mod->model, gh->g), 1)}, gh->fwd_ws.options());
+    check(pet_hessian_vector(mod->model, gh->g, ws.data_ptr(), ws.numel(), lam.data_ptr<float>(), u.data_ptr<float>(),
+                             ucell.defined() ? ucell.data_ptr<float>() : nullptr, hp.data_ptr<float>(), hc.data_ptr<float>(),
+                             tan.data_ptr<float>(), stream_of(lam)),
+          "pet_hessian_vector");
+    return {hp, hc, tan};
+}
+
+// The Hessian-vector product as a differentiable function of its DIRECTION (u, u_cell): it is linear in it, and the Hessian
+// of E_lambda over (positions, cells) is symmetric, so the adjoint for incoming (g_R, g_cell) is the same product along
+// (g_R, g_cell) -- what the double-backward trick of torch.autograd.functional.hvp differentiates. Its dependence on the
+// positions, cells and weights (third order) is not part of the graph.
+struct HvpFn : torch::autograd::Function<HvpFn> {
+    static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, const at::Tensor& u,
+                                                  const at::Tensor& ucell, const at::Tensor& lam,
+                                                  c10::intrusive_ptr<GraphHolder> gh, c10::intrusive_ptr<PetHipModule> mod) {
+        ctx->set_materialize_grads(false);
+        ctx->saved_data["graph"] = gh;
+        ctx->saved_data["module"] = mod;
+        ctx->saved_data["lam"] = lam;
+        auto out = hessian_vector(mod, gh, lam, u, ucell);
+        return {out[0].to(u.scalar_type()), out[1].to(ucell.scalar_type()), out[2]};
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
+                                                   torch::autograd::variable_list go) {
+        auto gh = ctx->saved_data["graph"].toCustomClass<GraphHolder>();
+        auto mod = ctx->saved_data["module"].toCustomClass<PetHipModule>();
+        const at::Tensor lam = ctx->saved_data["lam"].toTensor();
+        TORCH_CHECK(!go[2].defined(), "pet_hip: derivatives of the tangent energies w.r.t. the direction are not built "
+                                      "through the TorchScript op");
+        at::Tensor gp = go[0].defined() ? go[0] : at::zeros({gh->n_nodes, 3}, lam.options());
+        at::Tensor gc = go[1].defined() ? go[1] : at::zeros({gh->n_systems, 3, 3}, lam.options());
+        if (torch::GradMode::is_enabled() && (gp.requires_grad() || gc.requires_grad())) {
+            auto out = HvpFn::apply(gp, gc, lam, gh, mod);
+            return {out[0], out[1], at::Tensor(), at::Tensor(), at::Tensor()};
+        }
+        auto out = hessian_vector(mod, gh, lam, gp, gc);
+        return {out[0].to(gp.scalar_type()), out[1].to(gc.scalar_type()), at::Tensor(), at::Tensor(), at::Tensor()};
+    }
+};
+
+torch::autograd::variable_list EnergyGradFn::backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list go) {
+    auto gh = ctx->saved_data["graph"].toCustomClass<GraphHolder>();
+    auto mod = ctx->saved_data["module"].toCustomClass<PetHipModule>();
+    TORCH_CHECK(!ctx->saved_data["has_zbl"].toBool(),
+                "pet_hip: second derivatives of a model with a ZBL term are not built (the pair term's Hessian)");
+    const at::Tensor grad_atomic = ctx->get_saved_variables()[0];
+    at::Tensor lam = as_f32(grad_atomic.reshape({-1}));
+    const auto pd = (at::ScalarType)ctx->saved_data["pos_dtype"].toInt();
+    const auto cd = (at::ScalarType)ctx->saved_data["cell_dtype"].toInt();
+    at::Tensor u = go[0], ucell = go.size() > 1 ? go[1] : at::Tensor();
+    std::vector<at::Tensor> out;
+    if (torch::GradMode::is_enabled() && ((u.defined() && u.requires_grad()) || (ucell.defined() && ucell.requires_grad()))) {
+        // a graph is recorded again (torch.autograd.functional.hvp's double-backward trick): differentiable in the direction
+        if (!u.defined()) u = at::zeros({gh->n_nodes, 3}, lam.options());
+        if (!ucell.defined()) ucell = at::zeros({gh->n_systems, 3, 3}, lam.options());
+        out = HvpFn::apply(u, ucell, lam, gh, mod);
+    } else
+        out = hessian_vector(mod, gh, lam, u, ucell);
+    return {out[2].reshape(grad_atomic.sizes()).to(grad_atomic.scalar_type()), out[0].to(pd), out[1].to(cd), at::Tensor(), at::Tensor(),
+            at::Tensor()};
+}
+
 struct EnergyFn : torch::autograd::Function<EnergyFn> {
     // returns {atomic [N, 1]} or, with a ZBL table, {atomic [N, 1], ZBL atomic [N, 1]} (pet_zbl_forward on the same graph)
     static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, const at::Tensor& positions,
@@ -186,6 +287,7 @@ struct EnergyFn : torch::autograd::Function<EnergyFn> {
             check(pet_llpr_features(mod->model, gh->g, "@", "@", pn, pe, 1, nullptr, llf.data_ptr<float>(), st),
                   "pet_llpr_features");
         }
+        ctx->save_for_backward({positions, cells});   // (the inputs of the differentiable gradient node, EnergyGradFn)
         ctx->saved_data["graph"] = gh;
         ctx->saved_data["module"] = mod;
         ctx->saved_data["pos_dtype"] = (int64_t)positions.scalar_type();
@@ -204,14 +306,26 @@ struct EnergyFn : torch::autograd::Function<EnergyFn> {
         const bool has_zbl = grad_out.size() > 1;
         at::Tensor ga = grad_out[0];
         if (has_zbl && !ga.defined()) ga = at::zeros({gh->n_nodes}, gh->fwd_ws.options().dtype(at::kFloat));
-        TORCH_CHECK(!ga.requires_grad(), "pet_hip: double backward (create_graph=True) is not available through the "
-                                         "TorchScript op; train through metatrain_amd.pet (PETBackend / TrainStep)");
-        ga = as_f32(ga.reshape({-1}));
-        at::Tensor gpos = at::empty({gh->n_nodes, 3}, ga.options());
-        at::Tensor gcell = at::empty({gh->n_systems, 3, 3}, ga.options());
-        check(pet_backward(mod->model, gh->g, gh->fwd_ws.data_ptr(), gh->fwd_ws.numel(), ga.data_ptr<float>(),
-                           gpos.data_ptr<float>(), gcell.data_ptr<float>(), stream_of(ga)),
-              "pet_backward");
+        // A graph is being recorded (create_graph=True): the gradient is a differentiable function of (grad_atomic,
+        // positions, cells) whose backward is the Hessian-vector product. Second derivatives w.r.t. the PARAMETERS are
+        // not part of it: train through metatrain_amd.pet (PETBackend / TrainStep).
+        const auto saved = ctx->get_saved_variables();
+        const bool second = torch::GradMode::is_enabled() &&
+                            (ga.requires_grad() || saved[0].requires_grad() || saved[1].requires_grad());
+        at::Tensor gpos, gcell;
+        if (second) {
+            auto out = EnergyGradFn::apply(ga, saved[0], saved[1], gh, mod, has_zbl);
+            gpos = out[0].to(at::kFloat);
+            gcell = out[1].to(at::kFloat);
+            ga = as_f32(ga.reshape({-1}));
+        } else {
+            ga = as_f32(ga.reshape({-1}));
+            gpos = at::empty({gh->n_nodes, 3}, ga.options());
+            gcell = at::empty({gh->n_systems, 3, 3}, ga.options());
+            check(pet_backward(mod->model, gh->g, gh->fwd_ws.data_ptr(), gh->fwd_ws.numel(), ga.data_ptr<float>(),
+                               gpos.data_ptr<float>(), gcell.data_ptr<float>(), stream_of(ga)),
+                  "pet_backward");
+        }
         if (has_zbl && grad_out[1].defined()) {  // + the ZBL term's dL/dR and dL/dcell for the weights it received
             TORCH_CHECK(!grad_out[1].requires_grad(), "pet_hip: double backward through the ZBL term is not built");
             auto zbl = ctx->saved_data["zbl"].toCustomClass<ZblTable>();
@@ -221,8 +335,8 @@ struct EnergyFn : torch::autograd::Function<EnergyFn> {
             check(pet_zbl_backward(zbl->z, gh->g, gz.data_ptr<float>(), zpos.data_ptr<float>(), zcell.data_ptr<float>(), nullptr,
                                    zws.data_ptr(), zws.numel(), stream_of(ga)),
                   "pet_zbl_backward");
-            gpos.add_(zpos);
-            gcell.add_(zcell);
+            gpos = gpos + zpos;   // (out of place: gpos may be the output of the differentiable gradient node)
+            gcell = gcell + zcell;
         }
         const auto pd = (at::ScalarType)ctx->saved_data["pos_dtype"].toInt();
         const auto cd = (at::ScalarType)ctx->saved_data["cell_dtype"].toInt();

@@ -705,6 +705,40 @@ class HipForward:
         return out
 
 
+def hessian_vector_product(model: HipModel, graph: HipGraph, u: torch.Tensor, u_cell: Optional[torch.Tensor] = None,
+                           weights: Optional[torch.Tensor] = None, want_cells: bool = False, want_tangent: bool = False,
+                           workspace: Optional[torch.Tensor] = None):
+    """Hessian-vector product of the fused single-property target (``pet_hessian_vector``): with ``e'_i`` the derivative
+    of the per-atom predictions along ``(dR, dcell) = (u [N,3], u_cell [S,3,3])``, returns ``grad_R sum_i w_i e'_i``
+    ``[N,3]`` -- ``H u`` of the total energy for ``weights = None`` (ones) -- then, if asked for, ``grad_cell`` of the same
+    ``[S,3,3]`` and the tangents ``e'_i [N]``. Needs no forward pass and touches no gradient slot; it runs on the
+    size-generic dual pass for every model size. Adaptive-cutoff models and graphs with a per-layer exchange raise
+    (``PET_ERR_UNSUPPORTED``). ``workspace``: a uint8 buffer of at least ``hvp_workspace_bytes(model, graph)`` to reuse."""
+    _require_cuda(u)
+    dev = u.device
+    n, s = graph.n_nodes, graph.n_systems
+    nbytes = hvp_workspace_bytes(model, graph)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    uu = u.detach().to(torch.float32).reshape(n, 3).contiguous()
+    uc = None if u_cell is None else u_cell.detach().to(dev, torch.float32).reshape(s, 3, 3).contiguous()
+    w = None if weights is None else weights.detach().to(dev, torch.float32).reshape(n).contiguous()
+    hp = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    hc = torch.empty((s, 3, 3), dtype=torch.float32, device=dev) if want_cells else None
+    tan = torch.empty(n, dtype=torch.float32, device=dev) if want_tangent else None
+    check(model.lib.pet_hessian_vector(model.handle, graph.handle, _ptr(workspace), workspace.numel(), _ptr(w), _ptr(uu),
+                                       _ptr(uc), _ptr(hp), _ptr(hc), _ptr(tan), _stream()))
+    out = (hp,) + ((hc,) if want_cells else ()) + ((tan,) if want_tangent else ())
+    return out[0] if len(out) == 1 else out
+
+
+def hvp_workspace_bytes(model: HipModel, graph: HipGraph) -> int:
+    nbytes = int(model.lib.pet_hvp_workspace_bytes_for(model.handle, graph.handle))
+    if nbytes < 0:
+        raise PetHipError("pet_hvp_workspace_bytes_for failed")
+    return nbytes
+
+
 def _head_names(model: HipModel, target: str, block: Optional[str], readout_zero: bool = True):
     block = block or target
     if model.target is not None and target == model.target and block == model._fused_block and \

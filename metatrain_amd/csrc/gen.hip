@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "gen_common.h"
+#include "gen_walk.h"
 
 namespace pet {
 
@@ -36,17 +36,53 @@ int64_t gen_workspace_bytes(const Model& m, int64_t N, int64_t E) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// the primal pass of gen_walk.h on a forward workspace: inference and its reverse (dE/d geometry)
+// ---------------------------------------------------------------------------------------------
+namespace {
+struct Infer : Ops {
+    GWs& w;
+    Roles<float*> s;
+    const float* geo;
+    const float* const* g_node = nullptr;   // reverse: the read-out adjoints per layer (null = zero) and the two sinks
+    const float* const* g_edge = nullptr;
+    float *g_geo = nullptr, *g_fc = nullptr;
+    Infer(const Model& m_, const Graph& g_, hipStream_t st_, GWs& w_)
+        : Ops(m_, g_, st_), w(w_), geo(reinterpret_cast<const float*>(g_.geo)) {
+        s.normed = w.tE1; s.OUT = w.tE2; s.act = w.tE3; s.nNormed = w.tN1; s.nAct = w.tN2;
+        s.dAO = w.tE1; s.dOUT = w.tE2; s.dXin = w.tE3; s.dVG = w.tE4;
+        s.dH1 = w.tN1; s.nA = w.tN2; s.nB = w.tN3; s.dTOKo = w.tN3;
+        // s.re / s.nRe stay null: only the recompute hooks and the weight gradients read them, and this pass has neither.
+        // A hook that becomes non-empty here needs them carved first.
+    }
+    void attn(const GAttn& A) const {
+        attn_dispatch(d.HD, [&](auto hdm) {
+            k_gen_attn_fwd<decltype(hdm)::value><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
+                A.QKV, g.rowptr, g.fc, A.AO, A.LSE, E, d.D, d.NH, d.HD, scale);
+        });
+    }
+    void add_cond(float* H) const { k_gen_add_cond<<<g1(N * d.DN), 256, 0, st>>>(H, w.cond, g.sys, g.cond_sys, N, d.DN); }
+    void attn_rev(const GAttn& A, const float* dAO) const {
+        attn_dispatch(d.HD, [&](auto hdm) {
+            constexpr int HDM = decltype(hdm)::value;
+            k_gen_attn_bwd_q<HDM><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
+                A.QKV, A.AO, dAO, A.LSE, g.rowptr, g.fc, w.dQKV, w.DELTA, E, d.D, d.NH, d.HD, scale);
+            k_gen_attn_bwd_k<HDM><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
+                A.QKV, dAO, A.LSE, w.DELTA, g.rowptr, g.fc, w.dQKV, w.dbias_h, E, d.D, d.NH, d.HD, scale);
+        });
+    }
+    void key_bias_sink(bool) const { if (E > 0) k_gen_dfc<<<g1(E), 256, 0, st>>>(w.dbias_h, g.fc, g_fc, E, d.NH); }
+    void geo_sink(const float* dTOK, int kin, const Lin& eemb, bool) const { lin.bwd(dTOK, kin, eemb, g_geo, 4, E, true); }
+    void cond_accum(const float*, bool) const {}
+    void seed(int l, float* dH, float* dE) const {
+        if (g_node[l]) copy(g_node[l], dH, N, d.DN); else zero(dH, N * d.DN);
+        if (g_edge[l]) copy(g_edge[l], dE, E, d.D); else zero(dE, E * d.D);
+    }
+};
+}  // namespace
+
+// ---------------------------------------------------------------------------------------------
 // predict (a function of the features it is given) and its adjoint
 // ---------------------------------------------------------------------------------------------
-static int gen_head_fwd(const Ops& o, const Lin& h0, const Lin& h2, const float* X, int W, int64_t rows, float* a1, float* s1,
-                        float* a2, float* s2) {
-    o.lin.fwd(X, W, h0, a1, o.d.DH, rows);
-    if (rows > 0) k_gen_silu<<<g1(rows * o.d.DH), 256, 0, o.st>>>(a1, s1, rows * o.d.DH);
-    o.lin.fwd(s1, o.d.DH, h2, a2, o.d.DH, rows);
-    if (rows > 0) k_gen_silu<<<g1(rows * o.d.DH), 256, 0, o.st>>>(a2, s2, rows * o.d.DH);
-    return PET_OK;
-}
-
 int gen_predict(const Model& m, const Graph& g, const HeadW& H, const LastW& Lw, const float* node_feat,
                 const float* edge_feat, const float* fc, float* atomic, float* node_hidden, float* edge_hidden,
                 hipStream_t st) {
@@ -64,11 +100,11 @@ int gen_predict(const Model& m, const Graph& g, const HeadW& H, const LastW& Lw,
     float* a1n = scratch; float* s1n = a1n + N * DH; float* a2n = s1n + N * DH; float* s2n = a2n + N * DH;
     float* a1e = s2n + N * DH; float* s1e = a1e + E * DH; float* a2e = s1e + E * DH; float* s2e = a2e + E * DH;
     float* np = s2e + E * DH; float* ep = np + N * P;
-    gen_head_fwd(o, H.nh0, H.nh2, node_feat, o.d.DN, N, a1n, s1n, a2n, s2n);
+    gen_head(o, H.nh0, H.nh2, node_feat, o.d.DN, N, a1n, s1n, a2n, s2n);
     Lin ln; ln.w = Lw.nw; ln.b = Lw.nb; ln.n_out = P; ln.k_in = DH;
     o.lin.fwd(s2n, DH, ln, np, P, N);
     if (E > 0) {
-        gen_head_fwd(o, H.eh0, H.eh2, edge_feat, o.d.D, E, a1e, s1e, a2e, s2e);
+        gen_head(o, H.eh0, H.eh2, edge_feat, o.d.D, E, a1e, s1e, a2e, s2e);
         Lin le; le.w = Lw.ew; le.b = Lw.eb; le.n_out = P; le.k_in = DH;
         o.lin.fwd(s2e, DH, le, ep, P, E);
     }
@@ -95,7 +131,7 @@ int gen_predict_backward(const Model& m, const Graph& g, const HeadW& H, const L
     float* a1 = scratch; float* s1 = a1 + M * DH; float* a2 = s1 + M * DH; float* s2 = a2 + M * DH;
     float* pr = s2 + M * DH; float* dpr = pr + M * P;
     // node branch (recomputed from the features: nothing is read from a forward workspace)
-    gen_head_fwd(o, H.nh0, H.nh2, node_feat, o.d.DN, N, a1, s1, a2, s2);
+    gen_head(o, H.nh0, H.nh2, node_feat, o.d.DN, N, a1, s1, a2, s2);
     Lin ln; ln.w = Lw.nw; ln.b = Lw.nb; ln.n_out = P; ln.k_in = DH;
     o.lin.bwd(gA, P, ln, s2, DH, N);                                                   // d s2
     k_gen_silu_bwd<<<g1(N * DH), 256, 0, st>>>(a2, s2, s2, N * DH);                    // d a2
@@ -103,7 +139,7 @@ int gen_predict_backward(const Model& m, const Graph& g, const HeadW& H, const L
     k_gen_silu_bwd<<<g1(N * DH), 256, 0, st>>>(a1, s1, s1, N * DH);                    // d a1
     o.lin.bwd(s1, DH, H.nh0, g_node, o.d.DN, N);
     if (E > 0) {
-        gen_head_fwd(o, H.eh0, H.eh2, edge_feat, o.d.D, E, a1, s1, a2, s2);
+        gen_head(o, H.eh0, H.eh2, edge_feat, o.d.D, E, a1, s1, a2, s2);
         Lin le; le.w = Lw.ew; le.b = Lw.eb; le.n_out = P; le.k_in = DH;
         o.lin.fwd(s2, DH, le, pr, P, E);
         k_gen_edge_seed<<<g1(E), 256, 0, st>>>(gA, g.ctr, fc, pr, dpr, g_fc, 0, E, P);
@@ -135,10 +171,10 @@ int gen_aux_outputs(const Model& m, const Graph& g, const float* node_feat, cons
         PET_HIP_CHECK(tmp_pool.alloc((size_t)4 * M * d.DH * sizeof(float), st));
         float* tmp = tmp_pool.as<float>();
         float* b1 = tmp; float* b2 = b1 + M * d.DH; float* b3 = b2 + M * d.DH; float* b4 = b3 + M * d.DH;
-        gen_head_fwd(o, m.nh0, m.nh2, node_feat, d.DN, N, b1, b2, b3, b4);
+        gen_head(o, m.nh0, m.nh2, node_feat, d.DN, N, b1, b2, b3, b4);
         o.axpby(1.f, b4, d.DH, 0.f, nullptr, 0, nullptr, last_layer, 2 * d.DH, false, N, d.DH);
         if (E > 0) {
-            gen_head_fwd(o, m.eh0, m.eh2, edge_feat, d.D, E, b1, b2, b3, b4);
+            gen_head(o, m.eh0, m.eh2, edge_feat, d.D, E, b1, b2, b3, b4);
             k_gen_edge_sum<<<g1(N * d.DH), 256, 0, st>>>(b4, g.fc, g.rowptr, last_layer + d.DH, 2 * d.DH, N, d.DH);
         } else
             o.axpby(0.f, b4, d.DH, 0.f, nullptr, 0, nullptr, last_layer + d.DH, 2 * d.DH, false, N, d.DH);
@@ -150,26 +186,21 @@ int gen_aux_outputs(const Model& m, const Graph& g, const float* node_feat, cons
 // ---------------------------------------------------------------------------------------------
 // forward (backend.py:496-649)
 // ---------------------------------------------------------------------------------------------
-int gen_forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int save, float* atomic,
+int gen_forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, int, float* atomic,
                        float* const* node_feats, float* const* edge_feats, int n_layers, hipStream_t st) {
+    // (no `save` switch: everything the reverse passes need is kept anyway; the training pass, gen_train.hip, recomputes)
     GWs w;
     gen_carve(m, g.n_nodes, g.n_edges, ws, w);
     PET_REQUIRE((int64_t)w.bytes <= ws_bytes, PET_ERR_ARGUMENT,
                 "forward workspace too small for the size-generic path (other model sizes, or an atom with more than 127 "
                 "neighbours): size it with pet_forward_workspace_bytes_for(model, graph)");
-    (void)save;  // everything the reverse passes need is kept anyway; the training pass (gen_train.hip) recomputes
-    const bool post = m.post_ln(), res = m.residual();
+    const bool res = m.residual();
     PET_REQUIRE(res ? (n_layers == m.h.num_gnn_layers || (n_layers == 1 && !node_feats[0] && !edge_feats[0])) : n_layers == 1,
                 PET_ERR_ARGUMENT, "expected one feature pair per readout layer");
-    Ops o(m, g, st);
-    const GD& d = o.d;
-    const int64_t N = o.N, E = o.E, R = o.R;
+    Infer p(m, g, st, w);
+    const int64_t N = p.N, E = p.E;
     if (N == 0) return PET_OK;
-    const int D = d.D, DN = d.DN;
-    const float scale = 1.0f / (sqrtf((float)d.HD) * m.h.attention_temperature);
-    const int L = m.h.num_gnn_layers, AL = m.h.num_attention_layers;
-    k_gen_embed<<<g1(N * DN), 256, 0, st>>>(g.sp, m.node_emb, w.H0, DN, N, DN);
-    if (E > 0) k_gen_embed<<<g1(E * D), 256, 0, st>>>(g.sp_nbr, m.edge_emb, w.M0, D, E, D);
+    const int D = p.d.D, DN = p.d.DN;
     if (m.h.system_conditioning) {
         PET_REQUIRE(g.cond_charge && g.n_cond_systems >= 1 && g.n_cond_systems <= N, PET_ERR_ARGUMENT,
                     "system_conditioning: call pet_graph_set_conditioning (charge, spin multiplicity, system indices) first");
@@ -177,79 +208,7 @@ int gen_forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_byte
             g.cond_charge, g.cond_spin, m.cond_qe, m.cond_se, m.cond_w0, m.cond_b0, m.cond_w2, m.cond_b2, w.cond,
             m.h.max_charge, DN);
     }
-    const float* Min = w.M0;
-    for (int gi = 0; gi < L; gi++) {
-        const GnnLayerW& G = m.gnn[gi];
-        GGnn& B = w.gnn[gi];
-        if (res && gi > 0) k_gen_embed<<<g1(N * DN), 256, 0, st>>>(g.sp, m.node_embs[gi], B.Hin, DN, N, DN);
-        if (E > 0) {
-            // tokens = [edge_embedder([v, d]) ; (gi > 0: neighbor_embedder[species]) ; message] -> compress (transformer.py:499-521)
-            const int kin = (gi == 0 ? 2 : 3) * D;
-            float* TOK = w.tE1;
-            o.lin.fwd(reinterpret_cast<const float*>(g.geo), 4, G.eemb, TOK, kin, E);
-            if (gi > 0) k_gen_embed<<<g1(E * D), 256, 0, st>>>(g.sp_nbr, G.nbr_emb, TOK + D, kin, E, D);
-            o.axpby(1.f, Min, D, 0.f, nullptr, 0, nullptr, TOK + (gi == 0 ? D : 2 * D), kin, false, E, D);
-            o.lin.fwd(TOK, kin, G.c0, B.a0, D, E);
-            k_gen_silu<<<g1(E * D), 256, 0, st>>>(B.a0, w.tE2, E * D);
-            o.lin.fwd(w.tE2, D, G.compress2, B.attn[0].X, D, E);
-        }
-        for (int a = 0; a < AL; a++) {
-            const AttnLayerW& A = G.attn[a];
-            GAttn& Ab = B.attn[a];
-            float* Xnext = (a + 1 < AL) ? B.attn[a + 1].X : B.XF;
-            // centre token (transformer.py:210-214)
-            if (d.expanded) o.lin.fwd(Ab.H, DN, A.cc, Ab.X + E * D, D, N);
-            else o.copy(Ab.H, Ab.X + E * D, N, D);
-            const float* Xatt = Ab.X;
-            if (!post) { o.norm(Ab.X, A.g_attn, A.b_attn, w.tE1, R, D); Xatt = w.tE1; }
-            o.lin.fwd(Xatt, D, A.qkv, Ab.QKV, 3 * D, R);
-            attn_dispatch(d.HD, [&](auto hdm) {
-                k_gen_attn_fwd<decltype(hdm)::value><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
-                    Ab.QKV, g.rowptr, g.fc, Ab.AO, Ab.LSE, E, D, d.NH, d.HD, scale);
-            });
-            float* OUT = w.tE2;  // output_linear of every token
-            o.lin.fwd(Ab.AO, D, A.out, OUT, D, R);
-            if (!post) {
-                o.copy(OUT + E * D, Ab.TOKo, N, D);
-                // edges: residual + MLP (transformer.py:229-232)
-                if (E > 0) {
-                    o.axpby(1.f, Ab.X, D, 1.f, OUT, D, nullptr, Ab.X1, D, false, E, D);
-                    o.ffn(Ab.X1, true, A.g_mlp, A.b_mlp, A.mlp_in, A.mlp_out, Ab.VG, Ab.X1, Xnext, w.tE1, w.tE3, E, D, d.DFF);
-                }
-            } else {
-                // transformer.py:245-247 on every token: S1 = tokens + attention; T1 = norm(S1); S2 = T1 + MLP(T1); T2 = norm(S2)
-                o.axpby(1.f, Ab.X, D, 1.f, OUT, D, nullptr, Ab.X1, D, false, R, D);
-                o.norm(Ab.X1, A.g_attn, A.b_attn, Ab.T1, R, D);
-                o.ffn(Ab.T1, false, nullptr, nullptr, A.mlp_in, A.mlp_out, Ab.VG, Ab.T1, Ab.S2, w.tE1, w.tE3, R, D, d.DFF);
-                o.norm(Ab.S2, A.g_mlp, A.b_mlp, w.tE1, R, D);
-                if (E > 0) o.copy(w.tE1, Xnext, E, D);
-                o.copy(w.tE1 + E * D, Ab.TOKo, N, D);
-            }
-            // node update (transformer.py:221-227)
-            if (d.expanded) {
-                o.copy(Ab.H, Ab.H1, N, DN);
-                o.lin.fwd(Ab.TOKo, D, A.ce, Ab.H1, DN, N, true);
-                o.ffn(Ab.H1, true, A.g_center, A.b_center, A.cmlp_in, A.cmlp_out, Ab.VGn, Ab.H1, Ab.Hn, w.tN1, w.tN2, N, DN, d.DNF);
-            } else
-                o.copy(Ab.TOKo, Ab.Hn, N, DN);
-            if (a + 1 == AL && m.h.system_conditioning)
-                k_gen_add_cond<<<g1(N * DN), 256, 0, st>>>(Ab.Hn, w.cond, g.sys, g.cond_sys, N, DN);
-        }
-        if (E > 0 && res) {
-            if (gi + 1 < L) o.axpby(0.5f, Min, D, 0.5f, B.XF, D, g.rev, B.Mout, D, false, E, D);   // backend.py:640-647
-        } else if (E > 0) {
-            // backend.py:559-575: m = m + e + MLP(LayerNorm([e ; e[rev]]))
-            float* CAT = w.tE1;
-            o.axpby(1.f, B.XF, D, 0.f, nullptr, 0, nullptr, CAT, 2 * D, false, E, D);
-            o.axpby(0.f, nullptr, 0, 1.f, B.XF, D, g.rev, CAT + D, 2 * D, false, E, D);
-            k_gen_norm<<<(int)cdiv(E, 4), 256, 0, st>>>(CAT, G.ln_g, G.ln_b, 1, 1e-5f, w.tE2, E, 2 * D);
-            o.lin.fwd(w.tE2, 2 * D, G.comb0, B.CA, 2 * D, E);
-            k_gen_silu<<<g1(E * 2 * D), 256, 0, st>>>(B.CA, w.tE3, E * 2 * D);
-            o.axpby(1.f, Min, D, 1.f, B.XF, D, nullptr, B.Mout, D, false, E, D);
-            o.lin.fwd(w.tE3, 2 * D, G.comb2, B.Mout, D, E, true);
-        }
-        Min = B.Mout;
-    }
+    gen_walk_forward(p, w);
     const GGnn& last = w.gnn.back();
     if (atomic) {
         // the fused single-property target; with the residual featuriser the sum over the readout layers (backend.py:468-481)
@@ -258,16 +217,15 @@ int gen_forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_byte
         if (NR > 1) PET_HIP_CHECK(tmp_pool.alloc((size_t)N * sizeof(float), st));
         float* tmp = tmp_pool.as<float>();
         for (int l = 0; l < NR; l++) {
-            auto hi = m.heads.find("@|" + std::to_string(l));
-            auto li = m.lasts.find("@|" + std::to_string(l) + "|@");
-            PET_REQUIRE(hi != m.heads.end() && li != m.lasts.end() && li->second.P == 1, PET_ERR_ARGUMENT,
-                        "pet_forward with d_atomic needs the fused single-property target (of every readout layer); use "
-                        "pet_predict for other heads");
-            const GGnn& Bl = res ? w.gnn[l] : last;
-            int rc = gen_predict(m, g, hi->second, li->second, Bl.Hout, res ? Bl.XF : Bl.Mout, g.fc, l == 0 ? atomic : tmp,
-                                 nullptr, nullptr, st);
+            const HeadW* H;
+            const LastW* Lw;
+            int rc = fused_heads(m, l, H, Lw, "pet_forward with d_atomic needs the fused single-property target (of every readout "
+                                              "layer); use pet_predict for other heads");
             if (rc) return rc;
-            if (l > 0) o.add(tmp, atomic, N, 1);
+            const GGnn& Bl = res ? w.gnn[l] : last;
+            rc = gen_predict(m, g, *H, *Lw, Bl.Hout, res ? Bl.XF : Bl.Mout, g.fc, l == 0 ? atomic : tmp, nullptr, nullptr, st);
+            if (rc) return rc;
+            if (l > 0) p.add(tmp, atomic, N, 1);
         }
     }
     for (int l = 0; l < n_layers; l++) {
@@ -291,150 +249,12 @@ int gen_backward_features(const Model& m, const Graph& g, void* ws, int64_t ws_b
     gen_carve(m, g.n_nodes, g.n_edges, ws, w);
     PET_REQUIRE((int64_t)w.bytes <= ws_bytes, PET_ERR_ARGUMENT, "workspace too small");
     PET_REQUIRE(n_layers == m.num_readout_layers(), PET_ERR_ARGUMENT, "expected one gradient pair per readout layer");
-    Ops o(m, g, st);
-    const GD& d = o.d;
-    const int64_t N = o.N, E = o.E, R = o.R;
-    if (N == 0) return PET_OK;
-    const int D = d.D, DN = d.DN;
-    const bool post = m.post_ln(), res = m.residual();
-    const float scale = 1.0f / (sqrtf((float)d.HD) * m.h.attention_temperature);
-    const int L = m.h.num_gnn_layers, AL = m.h.num_attention_layers;
-    if (E > 0) {
-        PET_HIP_CHECK(hipMemsetAsync(g_geo, 0, E * 4 * sizeof(float), st));
-        PET_HIP_CHECK(hipMemsetAsync(g_fc, 0, E * sizeof(float), st));
-    }
-    auto seed = [&](const float* src, float* dst, int64_t rows, int W) -> int {
-        if (rows <= 0) return PET_OK;
-        if (src) o.copy(src, dst, rows, W);
-        else PET_HIP_CHECK(hipMemsetAsync(dst, 0, rows * W * sizeof(float), st));
-        return PET_OK;
-    };
-    int rc;
-    // dH: adjoint of the node features entering the next stage; dM: adjoint of the messages leaving layer gi
-    if (!res) {
-        if ((rc = seed(g_node[0], w.dH, N, DN))) return rc;
-        if ((rc = seed(g_edge[0], w.dM, E, D))) return rc;
-    } else {
-        if ((rc = seed(nullptr, w.dM, E, D))) return rc;   // the last layer's messages are never read
-    }
-    for (int gi = L - 1; gi >= 0; gi--) {
-        const GnnLayerW& G = m.gnn[gi];
-        GGnn& B = w.gnn[gi];
-        const float* Min = gi == 0 ? w.M0 : w.gnn[gi - 1].Mout;
-        (void)Min;
-        float* dXF = w.dX;   // adjoint of the edge tokens leaving the transformer, [E][D] (rows E.. are scratch)
-        float* dMin = w.dX2; // adjoint of the incoming messages
-        if (res) {
-            // readout of this layer + (gi + 1 < L) the averaged messages: Mout = 0.5 (Min + XF[rev])
-            if ((rc = seed(g_node[gi], w.dH, N, DN))) return rc;
-            if ((rc = seed(g_edge[gi], dXF, E, D))) return rc;
-            if (E > 0) {
-                if (gi + 1 < L) {
-                    o.axpby(0.f, nullptr, 0, 0.5f, w.dM, D, g.rev, dXF, D, true, E, D);  // rev is an involution
-                    o.axpby(0.5f, w.dM, D, 0.f, nullptr, 0, nullptr, dMin, D, false, E, D);
-                } else
-                    PET_HIP_CHECK(hipMemsetAsync(dMin, 0, E * D * sizeof(float), st));
-            }
-        } else if (E > 0) {
-            // Mout = Min + XF + comb2(silu(comb0(LN([XF ; XF[rev]]))))
-            float* dS = w.tE1;                        // [E][2D]
-            o.lin.bwd(w.dM, D, G.comb2, dS, 2 * D, E);
-            k_gen_silu_bwd<<<g1(E * 2 * D), 256, 0, st>>>(B.CA, dS, dS, E * 2 * D);
-            float* dCN = w.tE2;
-            o.lin.bwd(dS, 2 * D, G.comb0, dCN, 2 * D, E);
-            float* CAT = w.tE3;
-            o.axpby(1.f, B.XF, D, 0.f, nullptr, 0, nullptr, CAT, 2 * D, false, E, D);
-            o.axpby(0.f, nullptr, 0, 1.f, B.XF, D, g.rev, CAT + D, 2 * D, false, E, D);
-            float* dCAT = w.tE1;
-            k_gen_norm_bwd<<<(int)cdiv(E, 4), 256, 0, st>>>(CAT, G.ln_g, 1, 1e-5f, dCN, dCAT, 0, E, 2 * D);
-            // dXF = dM + dCAT[:, :D] + dCAT[rev][:, D:]
-            o.axpby(1.f, w.dM, D, 0.f, nullptr, 0, nullptr, dXF, D, false, E, D);
-            o.axpby(1.f, dCAT, 2 * D, 1.f, dCAT + D, 2 * D, g.rev, dXF, D, true, E, D);
-            o.copy(w.dM, dMin, E, D);
-        }
-        // transformer layers, last to first. dTok: adjoint of the tokens LEAVING layer a = [dXF ; centre part via dH]
-        for (int a = AL - 1; a >= 0; a--) {
-            const AttnLayerW& A = G.attn[a];
-            GAttn& Ab = B.attn[a];
-            // ---- node update adjoint: dH (of Hn) -> dTOKo [N][D] (tN3) and dH (of H entering the layer)
-            float* dTOKo = w.tN3;
-            if (d.expanded) {
-                // Hn = H1 + cmlp(norm(H1)); H1 = H + ce(TOKo)
-                float* dH1 = w.tN1;
-                o.copy(w.dH, dH1, N, DN);
-                {   // ffn_bwd needs two temporaries of width max(2 DNF, DN): tN2 and tN3 (dTOKo is produced after)
-                    o.ffn_bwd(Ab.H1, true, A.g_center, A.cmlp_in, A.cmlp_out, Ab.VGn, w.dH, dH1, true, w.tN2, w.tN3, N, DN, d.DNF);
-                }
-                o.lin.bwd(dH1, DN, A.ce, dTOKo, D, N);
-                o.copy(dH1, w.dH, N, DN);             // through the residual H1 = H + ...
-            } else {
-                o.copy(w.dH, dTOKo, N, D);
-                PET_HIP_CHECK(hipMemsetAsync(w.dH, 0, N * DN * sizeof(float), st));
-            }
-            // ---- token adjoint entering output_linear: dOUT [R][D] in tE2, and dX (adjoint of the tokens ENTERING the layer)
-            float* dOUT = w.tE2;
-            float* dXin = w.tE3;   // [R][D]
-            if (!post) {
-                // edges: X2 = X1 + mlp(norm(X1)); X1 = X + OUT_e
-                if (E > 0) {
-                    float* dX1 = dXin;   // reuse: rows 0..E
-                    o.copy(dXF, dX1, E, D);
-                    o.ffn_bwd(Ab.X1, true, A.g_mlp, A.mlp_in, A.mlp_out, Ab.VG, dXF, dX1, true, w.tE1, w.tE2, E, D, d.DFF);
-                    o.copy(dX1, dOUT, E, D);          // dOUT_e = dX1 ; dX_e (residual) = dX1 (already in dXin rows 0..E)
-                }
-                o.copy(dTOKo, dOUT + E * D, N, D);
-                PET_HIP_CHECK(hipMemsetAsync(dXin + E * D, 0, N * D * sizeof(float), st));  // centre token has no residual
-            } else {
-                // T2 = norm_mlp(S2) [edges -> next tokens, centre -> TOKo]; S2 = T1 + mlp(T1); T1 = norm_attn(S1); S1 = X + OUT
-                float* dT2 = w.tE1;
-                if (E > 0) o.copy(dXF, dT2, E, D);
-                o.copy(dTOKo, dT2 + E * D, N, D);
-                float* dS2 = w.tE2;
-                o.norm_bwd(Ab.S2, A.g_mlp, dT2, dS2, false, R, D);
-                float* dT1 = dXin;
-                o.copy(dS2, dT1, R, D);
-                o.ffn_bwd(Ab.T1, false, nullptr, A.mlp_in, A.mlp_out, Ab.VG, dS2, dT1, true, w.tE1, w.tE4, R, D, d.DFF);
-                float* dS1 = w.tE1;
-                o.norm_bwd(Ab.X1, A.g_attn, dT1, dS1, false, R, D);
-                o.copy(dS1, dOUT, R, D);
-                o.copy(dS1, dXin, R, D);
-            }
-            // ---- output_linear, attention, input_linear
-            float* dAO = w.tE1;
-            o.lin.bwd(dOUT, D, A.out, dAO, D, R);
-            attn_dispatch(d.HD, [&](auto hdm) {
-                constexpr int HDM = decltype(hdm)::value;
-                k_gen_attn_bwd_q<HDM><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
-                    Ab.QKV, Ab.AO, dAO, Ab.LSE, g.rowptr, g.fc, w.dQKV, w.DELTA, E, D, d.NH, d.HD, scale);
-                k_gen_attn_bwd_k<HDM><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
-                    Ab.QKV, dAO, Ab.LSE, w.DELTA, g.rowptr, g.fc, w.dQKV, w.dbias_h, E, D, d.NH, d.HD, scale);
-            });
-            if (E > 0) k_gen_dfc<<<g1(E), 256, 0, st>>>(w.dbias_h, g.fc, g_fc, E, d.NH);
-            if (!post) {
-                float* dXN = w.tE2;
-                o.lin.bwd(w.dQKV, 3 * D, A.qkv, dXN, D, R);
-                o.norm_bwd(Ab.X, A.g_attn, dXN, dXin, true, R, D);
-            } else
-                o.lin.bwd(w.dQKV, 3 * D, A.qkv, dXin, D, R, true);
-            // ---- split the token adjoint: edges -> dXF of the previous layer, centre -> dH through center_contraction
-            if (E > 0) o.copy(dXin, dXF, E, D);
-            if (d.expanded) o.lin.bwd(dXin + E * D, D, A.cc, w.dH, DN, N, true);
-            else o.add(dXin + E * D, w.dH, N, DN);
-        }
-        // ---- compress adjoint: X0 = c2(silu(a0)), a0 = c0 [EE ; (nbr emb) ; Min]
-        if (E > 0) {
-            const int kin = (gi == 0 ? 2 : 3) * D;
-            float* dS = w.tE1;
-            o.lin.bwd(dXF, D, G.compress2, dS, D, E);
-            k_gen_silu_bwd<<<g1(E * D), 256, 0, st>>>(B.a0, dS, dS, E * D);
-            float* dTOK = w.tE2;
-            o.lin.bwd(dS, D, G.c0, dTOK, kin, E);
-            o.lin.bwd(dTOK, kin, G.eemb, g_geo, 4, E, true);                       // through edge_embedder([v, d])
-            o.axpby(1.f, dTOK + (gi == 0 ? D : 2 * D), kin, 0.f, nullptr, 0, nullptr, dMin, D, true, E, D);
-            o.copy(dMin, w.dM, E, D);                                               // adjoint of the previous layer's messages
-        }
-        if (res) PET_HIP_CHECK(hipMemsetAsync(w.dH, 0, N * DN * sizeof(float), st));  // each layer starts from an embedding
-    }
+    Infer p(m, g, st, w);
+    if (p.N == 0) return PET_OK;
+    p.g_node = g_node; p.g_edge = g_edge; p.g_geo = g_geo; p.g_fc = g_fc;
+    p.zero(g_geo, p.E * 4);
+    p.zero(g_fc, p.E);
+    gen_walk_reverse(p, w);
     PET_HIP_CHECK(hipGetLastError());
     return PET_OK;
 }
@@ -463,15 +283,14 @@ int gen_backward(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, con
     std::vector<const float*> gnp(NR), gep(NR);
     int rc = PET_OK;
     for (int l = 0; l < NR && !rc; l++) {
-        auto hi = m.heads.find("@|" + std::to_string(l));
-        auto li = m.lasts.find("@|" + std::to_string(l) + "|@");
-        PET_REQUIRE(hi != m.heads.end() && li != m.lasts.end() && li->second.P == 1, PET_ERR_ARGUMENT,
-                    "pet_backward needs the fused single-property target (of every readout layer)");
+        const HeadW* H;
+        const LastW* Lw;
+        if ((rc = fused_heads(m, l, H, Lw, "pet_backward needs the fused single-property target (of every readout layer)"))) return rc;
         const GGnn& Bl = res ? w.gnn[l] : w.gnn.back();
         float* gn = buf + per * l;
         float* ge = gn + (size_t)N * d.DN;
         gnp[l] = gn; gep[l] = ge;
-        rc = gen_predict_backward(m, g, hi->second, li->second, Bl.Hout, res ? Bl.XF : Bl.Mout, g.fc, gA, gn, ge, l == 0 ? gfh : gft, st);
+        rc = gen_predict_backward(m, g, *H, *Lw, Bl.Hout, res ? Bl.XF : Bl.Mout, g.fc, gA, gn, ge, l == 0 ? gfh : gft, st);
         if (!rc && l > 0 && E > 0) { Ops o(m, g, st); o.add(gft, gfh, E, 1); }
     }
     if (!rc) rc = gen_backward_features(m, g, ws, ws_bytes, gnp.data(), gep.data(), NR, ggeo, gfc, st);

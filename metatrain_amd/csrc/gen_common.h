@@ -1,5 +1,6 @@
 // Shared building blocks of the size-generic PET path (gen.hip: inference + dE/dR; gen_train.hip: training): fp32 FMA
-// GEMM over raw torch weights, run-time-width row kernels, wave-per-(atom, head) attention, workspace carve. Everything
+// GEMM over raw torch weights, run-time-width row kernels, wave-per-(atom, head) attention, workspace carve, the primal
+// operations and the FFN / head blocks over a pass' value type (the walks over the layers: gen_walk.h). Everything
 // here lives in an anonymous namespace: each translation unit gets its own copy of the kernels.
 #pragma once
 #include <type_traits>
@@ -557,13 +558,80 @@ __global__ void k_gen_edge_seed(const float* __restrict__ gA, const int* __restr
 // ---------------------------------------------------------------------------------------------
 // workspace
 // ---------------------------------------------------------------------------------------------
-struct GAttn {
-    float *X, *QKV, *AO, *LSE, *X1, *VG, *T1, *S2, *H, *H1, *VGn, *Hn, *TOKo;
+// A value of a pass is one array (inference) or the primal / tangent halves of an activation -- for an adjoint its
+// (nu, lambda) -- two arrays of one shape (the dual pass of gen_train.hip)
+struct D2 {
+    float* p = nullptr;
+    float* t = nullptr;
 };
-struct GGnn {
-    std::vector<GAttn> attn;
-    float *a0, *XF, *CA, *Mout, *Hin, *Hout;
+// "rows E.. of X", "columns D.. of CAT": both halves move
+static inline float* off(float* v, int64_t n) { return v + n; }
+static inline D2 off(const D2& v, int64_t n) { return D2{v.p + n, v.t + n}; }
+static inline const float* prim(const float* v) { return v; }
+static inline const float* prim(const D2& v) { return v.p; }
+static inline void take(Carver& c, size_t n, float*& v) { v = c.take<float>(n); }
+static inline void take(Carver& c, size_t n, D2& v) { v.p = c.take<float>(n); v.t = c.take<float>(n); }
+
+template <class V>
+struct WAttn {
+    V X{}, QKV{}, AO{}, X1{}, VG{}, T1{}, S2{}, TOKo{}, H{}, H1{}, VGn{}, Hn{};
+    float *LSE = nullptr, *MS = nullptr;
 };
+template <class V>
+struct WGnn {
+    std::vector<WAttn<V>> attn;
+    V TOK{}, a0{}, XF{}, CA{}, Mout{}, Hin{}, Hout{};
+};
+using GAttn = WAttn<float*>;
+using GGnn = WGnn<float*>;
+// the saved activations of every layer, in the order both workspaces keep them. The dual one also keeps the compress
+// input TOK and the attention's tangent sums MS; the primal one rebuilds TOK in a temporary.
+template <class V>
+static void carve_layers(const Model& m, const GD& d, Carver& c, int64_t Na, int64_t Ea, int64_t Ra, V prev,
+                         std::vector<WGnn<V>>& gnn) {
+    const bool dual = std::is_same<V, D2>::value, post = m.post_ln();
+    gnn.resize(m.h.num_gnn_layers);
+    for (size_t gi = 0; gi < gnn.size(); gi++) {
+        WGnn<V>& G = gnn[gi];
+        G.attn.resize(m.h.num_attention_layers);
+        if (dual) take(c, Ea * 3 * d.D, G.TOK);
+        take(c, Ea * d.D, G.a0);
+        take(c, Ea * d.D, G.XF);
+        take(c, Ea * 2 * d.D, G.CA);
+        take(c, Ea * d.D, G.Mout);
+        if (m.residual() && gi > 0) take(c, Na * d.DN, prev);
+        G.Hin = prev;
+        for (auto& A : G.attn) {
+            take(c, Ra * d.D, A.X);
+            take(c, Ra * 3 * d.D, A.QKV);
+            take(c, Ra * d.D, A.AO);
+            A.LSE = c.take<float>(Ra * d.NH);
+            if (dual) A.MS = c.take<float>(Ra * d.NH);
+            take(c, Ra * d.D, A.X1);
+            take(c, Ra * 2 * d.DFF, A.VG);
+            if (post) { take(c, Ra * d.D, A.T1); take(c, Ra * d.D, A.S2); }
+            take(c, Na * d.D, A.TOKo);   // the centre token leaving the layer (attention output / PostLN norm_mlp row)
+            A.H = prev;
+            if (d.expanded) { take(c, Na * d.DN, A.H1); take(c, Na * 2 * d.DNF, A.VGn); }
+            take(c, Na * d.DN, A.Hn);
+            prev = A.Hn;
+        }
+        G.Hout = prev;
+    }
+}
+// Scratch of the walks of gen_walk.h by role; a pass fills it from its own workspace. Two roles may name one buffer
+// where no kernel of the walk reads the one while it writes the other.
+template <class V>
+struct Roles {
+    // forward, [R][wmax]: norm outputs and [e ; e[rev]] | SiLU(a0), output_linear of every token, LN([e ; e[rev]]) | SwiGLU / SiLU outputs
+    V normed{}, OUT{}, act{};
+    V nNormed{}, nAct{};   // [N][nmax]: the centre MLP's
+    // reverse, [R][wmax]: adjoint of the attention output (and whatever is short-lived before it) | of output_linear's
+    // result | of the tokens entering the layer | of the SwiGLU input, norm products | a recomputed norm
+    V dAO{}, dOUT{}, dXin{}, dVG{}, re{};
+    V dH1{}, nA{}, nB{}, nRe{}, dTOKo{};   // [N][nmax]: centre MLP adjoint and its three temporaries, centre token adjoint
+};
+
 struct GWs {
     std::vector<GGnn> gnn;
     float *H0, *M0, *cond;
@@ -578,39 +646,10 @@ static void gen_carve(const Model& m, int64_t N, int64_t E, void* base, GWs& w) 
     const GD d = dims_of(m);
     Carver c(base);
     const int64_t R = E + N, Ra = R > 0 ? R : 1, Na = N > 0 ? N : 1, Ea = E > 0 ? E : 1;
-    const bool post = m.post_ln();
-    w.gnn.resize(m.h.num_gnn_layers);
     w.H0 = c.take<float>(Na * d.DN);
     w.M0 = c.take<float>(Ea * d.D);
     w.cond = m.h.system_conditioning ? c.take<float>(Na * d.DN) : nullptr;
-    float* prev = w.H0;
-    for (size_t gi = 0; gi < w.gnn.size(); gi++) {
-        GGnn& G = w.gnn[gi];
-        G.attn.resize(m.h.num_attention_layers);
-        G.a0 = c.take<float>(Ea * d.D);
-        G.XF = c.take<float>(Ea * d.D);
-        G.CA = c.take<float>(Ea * 2 * d.D);
-        G.Mout = c.take<float>(Ea * d.D);
-        if (m.residual() && gi > 0) prev = c.take<float>(Na * d.DN);
-        G.Hin = prev;
-        for (auto& A : G.attn) {
-            A.X = c.take<float>(Ra * d.D);
-            A.QKV = c.take<float>(Ra * 3 * d.D);
-            A.AO = c.take<float>(Ra * d.D);
-            A.LSE = c.take<float>(Ra * d.NH);
-            A.X1 = c.take<float>(Ra * d.D);
-            A.VG = c.take<float>(Ra * 2 * d.DFF);
-            A.T1 = post ? c.take<float>(Ra * d.D) : nullptr;
-            A.S2 = post ? c.take<float>(Ra * d.D) : nullptr;
-            A.TOKo = c.take<float>(Na * d.D);   // the centre token leaving the layer (attention output / PostLN norm_mlp row)
-            A.H = prev;
-            A.H1 = d.expanded ? c.take<float>(Na * d.DN) : nullptr;
-            A.VGn = d.expanded ? c.take<float>(Na * 2 * d.DNF) : nullptr;
-            A.Hn = c.take<float>(Na * d.DN);
-            prev = A.Hn;
-        }
-        G.Hout = prev;
-    }
+    carve_layers(m, d, c, Na, Ea, Ra, w.H0, w.gnn);
     const int wmax = imax(imax(3 * d.D, 2 * d.DFF), imax(2 * d.D, d.DH));
     const int nmax = imax(imax(2 * d.DNF, d.DN), imax(d.DH, d.D));
     w.tE1 = c.take<float>(Ra * wmax); w.tE2 = c.take<float>(Ra * wmax); w.tE3 = c.take<float>(Ra * wmax);
@@ -623,25 +662,50 @@ static void gen_carve(const Model& m, int64_t N, int64_t E, void* base, GWs& w) 
     w.dbias_h = c.take<float>(Ea * d.NH);
     w.dgeo = c.take<float>(Ea * 4); w.dfc = c.take<float>(Ea); w.dv = c.take<float>(Ea * 4);
     w.bytes = c.off;
+    for (auto& G : w.gnn) G.TOK = w.tE1;
 }
 
 static inline int g1(int64_t n) { return (int)cdiv(n > 0 ? n : 1, 256); }
 
-struct Ops {   // launch helpers of one pass
+// Launch helpers on plain arrays: the forward and reverse operations of the primal pass (gen.hip adds the buffers and the
+// sinks of inference). Every helper skips zero rows, so a batch without an edge needs no guard.
+struct Ops {
+    using V = float*;
+    using CV = const float*;
     const Model& m;
     const Graph& g;
     GD d;
     hipStream_t st;
     Lins lin;
     int64_t N, E, R;
+    float scale;   // of the attention logits
     Ops(const Model& m_, const Graph& g_, hipStream_t s) : m(m_), g(g_), d(dims_of(m_)), st(s), lin{s}, N(g_.n_nodes),
-        E(g_.n_edges), R(g_.n_nodes + g_.n_edges) {}
+        E(g_.n_edges), R(g_.n_nodes + g_.n_edges), scale(1.0f / (sqrtf((float)d.HD) * m_.h.attention_temperature)) {}
     float eps() const { return m.layer_norm() ? 1e-5f : 1.1920929e-07f; }
-    void norm(const float* X, const float* gamma, const float* beta, float* Y, int64_t rows, int W) const {
-        if (rows > 0) k_gen_norm<<<(int)cdiv(rows, 4), 256, 0, st>>>(X, gamma, m.layer_norm() ? beta : nullptr, m.layer_norm(), eps(), Y, rows, W);
+    void linf(const float* X, int64_t ldx, const Lin& L, float* Y, int64_t ldy, int64_t rows, bool acc = false) const {
+        lin.fwd(X, ldx, L, Y, ldy, rows, acc);
     }
-    void norm_bwd(const float* X, const float* gamma, const float* dY, float* dX, bool acc, int64_t rows, int W) const {
-        if (rows > 0) k_gen_norm_bwd<<<(int)cdiv(rows, 4), 256, 0, st>>>(X, gamma, m.layer_norm(), eps(), dY, dX, acc, rows, W);
+    void linb(const float* dY, int64_t ldy, const Lin& L, float* dX, int64_t ldx, int64_t rows, bool acc = false) const {
+        lin.bwd(dY, ldy, L, dX, ldx, rows, acc);
+    }
+    // ln / e: the model's norm, or a LayerNorm of its own (the [e ; e[rev]] one)
+    void norm(const float* X, const float* gamma, const float* beta, float* Y, int64_t rows, int W, int ln = -1, float e = -1.f) const {
+        const int l = ln < 0 ? (int)m.layer_norm() : ln;
+        if (rows > 0) k_gen_norm<<<(int)cdiv(rows, 4), 256, 0, st>>>(X, gamma, l ? beta : nullptr, l, e < 0 ? eps() : e, Y, rows, W);
+    }
+    // (beta and the scratch G serve the dual pass' parameter gradients: unused here, G may be null)
+    void norm_rev(const float* X, const float* gamma, const float*, const float* dY, float* dX, bool acc, const float*, int64_t rows,
+                  int W, int ln = -1, float e = -1.f) const {
+        const int l = ln < 0 ? (int)m.layer_norm() : ln;
+        if (rows > 0) k_gen_norm_bwd<<<(int)cdiv(rows, 4), 256, 0, st>>>(X, gamma, l, e < 0 ? eps() : e, dY, dX, acc, rows, W);
+    }
+    void silu(const float* A, float* S, int64_t n) const { if (n > 0) k_gen_silu<<<g1(n), 256, 0, st>>>(A, S, n); }
+    void silu_rev(const float* A, float* dS, int64_t n) const { if (n > 0) k_gen_silu_bwd<<<g1(n), 256, 0, st>>>(A, dS, dS, n); }
+    void swiglu(const float* VG, float* S, int64_t rows, int F) const {
+        if (rows > 0) k_gen_swiglu<<<g1(rows * F), 256, 0, st>>>(VG, S, rows, F);
+    }
+    void swiglu_rev(const float* VG, const float* dS, float* dVG, int64_t rows, int F) const {
+        if (rows > 0) k_gen_swiglu_bwd<<<g1(rows * F), 256, 0, st>>>(VG, dS, dVG, rows, F);
     }
     void axpby(float a, const float* A, int64_t lda, float b, const float* B, int64_t ldb, const int* index, float* Y,
                int64_t ldy, bool acc, int64_t rows, int W) const {
@@ -649,29 +713,70 @@ struct Ops {   // launch helpers of one pass
     }
     void copy(const float* A, float* Y, int64_t rows, int W) const { axpby(1.f, A, W, 0.f, nullptr, 0, nullptr, Y, W, false, rows, W); }
     void add(const float* A, float* Y, int64_t rows, int W) const { axpby(1.f, A, W, 0.f, nullptr, 0, nullptr, Y, W, true, rows, W); }
-    // y = x + w_out(swiglu(w_in(norm(x))))  -> VG saved; out may alias nothing of the inputs
-    // FFN block on `rows` rows of width W: N = (normed ? norm(X) : X); VG = w_in N; S = swiglu(VG); Y = base + w_out S
-    void ffn(const float* Xin, bool normed, const float* gamma, const float* beta, const Lin& w_in, const Lin& w_out,
-             float* VG, const float* base, float* Y, float* tA, float* tB, int64_t rows, int W, int F) const {
-        const float* Nn = Xin;
-        if (normed) { norm(Xin, gamma, beta, tA, rows, W); Nn = tA; }
-        lin.fwd(Nn, W, w_in, VG, 2 * F, rows);
-        if (rows > 0) k_gen_swiglu<<<g1(rows * F), 256, 0, st>>>(VG, tB, rows, F);
-        if (base != Y) copy(base, Y, rows, W);
-        lin.fwd(tB, F, w_out, Y, W, rows, true);   // += w_out S + bias
+    // A failing memset does not end the walk where it happens: the launches after it are still queued, and the entry
+    // point's hipGetLastError at its exit reports the failure (the dual pass always worked this way).
+    void zero(float* A, int64_t n) const { if (n > 0) (void)hipMemsetAsync(A, 0, n * sizeof(float), st); }
+    void embed(const int* index, const float* table, float* Y, int64_t ldy, int64_t rows, int W) const {
+        if (rows > 0) k_gen_embed<<<g1(rows * W), 256, 0, st>>>(index, table, Y, ldy, rows, W);
     }
-    // adjoint of the FFN branch: dIn (+)= d/dXin [w_out(swiglu(w_in(norm(Xin))))] for dY; the residual path is the caller's
-    void ffn_bwd(const float* Xin, bool normed, const float* gamma, const Lin& w_in, const Lin& w_out, const float* VG,
-                 const float* dY, float* dIn, bool acc, float* tA, float* tB, int64_t rows, int W, int F) const {
-        lin.bwd(dY, W, w_out, tA, F, rows);                                       // dS
-        if (rows > 0) k_gen_swiglu_bwd<<<g1(rows * F), 256, 0, st>>>(VG, tA, tB, rows, F);  // dVG
-        if (normed) {
-            lin.bwd(tB, 2 * F, w_in, tA, W, rows);                                // dN
-            norm_bwd(Xin, gamma, tA, dIn, acc, rows, W);
-        } else
-            lin.bwd(tB, 2 * F, w_in, dIn, W, rows, acc);
-    }
+    // what only the dual training pass has: weight gradients and the operands it recomputes for them
+    template <class... A> void wgrad(A&&...) const {}
+    template <class... A> void embed_grad(A&&...) const {}
+    template <class... A> void re_norm(A&&...) const {}
+    template <class... A> void re_silu(A&&...) const {}
+    template <class... A> void re_swiglu(A&&...) const {}
 };
+
+// FFN block on `rows` rows of width W: Nn = (normed ? norm(Xin) : Xin); VG = w_in Nn (saved); S = swiglu(VG);
+// Y = base + w_out S. Y may be base, and nothing else of the inputs.
+template <class P>
+static void gen_ffn(const P& p, typename P::V Xin, bool normed, const float* gamma, const float* beta, const Lin& w_in,
+                    const Lin& w_out, typename P::V VG, typename P::V base, typename P::V Y, typename P::V tA, typename P::V tB,
+                    int64_t rows, int W, int F) {
+    typename P::V Nn = Xin;
+    if (normed) { p.norm(Xin, gamma, beta, tA, rows, W); Nn = tA; }
+    p.linf(Nn, W, w_in, VG, 2 * F, rows);
+    p.swiglu(VG, tB, rows, F);
+    if (prim(base) != prim(Y)) p.copy(base, Y, rows, W);
+    p.linf(tB, F, w_out, Y, W, rows, true);   // += w_out S + bias
+}
+// adjoint of the FFN branch: dIn (+)= d/dXin [w_out(swiglu(w_in(norm(Xin))))] for dY, the residual path is the caller's.
+// A pass with weight gradients recomputes their operands: Nn into tC, S into tA before the adjoint of S lands there.
+template <class P>
+static void gen_ffn_rev(P& p, typename P::V Xin, bool normed, const float* gamma, const float* beta, const Lin& w_in,
+                        const Lin& w_out, typename P::V VG, typename P::V dY, typename P::V dIn, bool acc, typename P::V tA,
+                        typename P::V tB, typename P::V tC, int64_t rows, int W, int F) {
+    typename P::V Nn = Xin;
+    if (normed) { p.re_norm(Xin, gamma, beta, tC, rows, W); Nn = tC; }
+    p.re_swiglu(VG, tA, rows, F);
+    p.wgrad(w_out, dY, W, tA, F, rows);
+    p.linb(dY, W, w_out, tA, F, rows);        // of S
+    p.swiglu_rev(VG, tA, tB, rows, F);        // of VG
+    p.wgrad(w_in, tB, 2 * F, Nn, W, rows);
+    if (normed) {
+        p.linb(tB, 2 * F, w_in, tA, W, rows);   // of Nn
+        p.norm_rev(Xin, gamma, beta, tA, dIn, acc, tC, rows, W);
+    } else
+        p.linb(tB, 2 * F, w_in, dIn, W, rows, acc);
+}
+// head MLP (backend.py:651-777): s2 = silu(h2 silu(h0 X)); the intermediates stay for the adjoint
+template <class P>
+static void gen_head(const P& p, const Lin& h0, const Lin& h2, typename P::CV X, int W, int64_t rows, typename P::V a1,
+                     typename P::V s1, typename P::V a2, typename P::V s2) {
+    p.linf(X, W, h0, a1, p.d.DH, rows);
+    p.silu(a1, s1, rows * p.d.DH);
+    p.linf(s1, p.d.DH, h2, a2, p.d.DH, rows);
+    p.silu(a2, s2, rows * p.d.DH);
+}
+// the fused single-property target's head and last layer of readout layer l ("@": runtime.HipModel.load)
+static int fused_heads(const Model& m, int l, const HeadW*& H, const LastW*& Lw, const char* why) {
+    auto hi = m.heads.find("@|" + std::to_string(l));
+    auto li = m.lasts.find("@|" + std::to_string(l) + "|@");
+    PET_REQUIRE(hi != m.heads.end() && li != m.lasts.end() && li->second.P == 1, PET_ERR_ARGUMENT, why);
+    H = &hi->second;
+    Lw = &li->second;
+    return PET_OK;
+}
 
 }  // namespace
 

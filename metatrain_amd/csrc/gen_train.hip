@@ -15,18 +15,13 @@
 #include <map>
 #include <string>
 
-#include "gen_common.h"
+#include "gen_walk.h"
 #include "cutoff.h"
 
 namespace pet {
 
 
 namespace {
-
-struct D2 {   // primal / tangent halves of an activation, or (nu, lambda) of an adjoint: two arrays of one shape
-    float* p = nullptr;
-    float* t = nullptr;
-};
 
 // ---------------------------------------------------------------------------------------------
 // geometry tangents: geo' = (v', d'), fc', b' = (log max(fc, 1e-15))'
@@ -608,14 +603,8 @@ __global__ void k_gt_last_rev(const float* __restrict__ gA, const int* __restric
 // ---------------------------------------------------------------------------------------------
 // workspace of the pass
 // ---------------------------------------------------------------------------------------------
-struct TAttn {
-    D2 X, QKV, AO, X1, VG, T1, S2, TOKo, H, H1, VGn, Hn;
-    float *LSE, *MS;
-};
-struct TGnn {
-    std::vector<TAttn> attn;
-    D2 TOK, a0, XF, CA, Mout, Hin, Hout;
-};
+using TAttn = WAttn<D2>;
+using TGnn = WGnn<D2>;
 struct TWs {
     std::vector<TGnn> gnn;
     D2 H0, M0, geo;
@@ -626,59 +615,24 @@ struct TWs {
     size_t part_floats;
     size_t bytes;
 };
-static D2 take2(Carver& c, size_t n) {
-    D2 d;
-    d.p = c.take<float>(n);
-    d.t = c.take<float>(n);
-    return d;
-}
 static int n_chunks_for(int64_t rows) { return (int)std::min<int64_t>(32, std::max<int64_t>(1, (rows + 1023) / 1024)); }
 static void train_carve(const Model& m, int64_t N, int64_t E, void* base, TWs& w) {
     const GD d = dims_of(m);
     Carver c(base);
     const int64_t R = E + N, Ra = R > 0 ? R : 1, Na = N > 0 ? N : 1, Ea = E > 0 ? E : 1;
-    const bool post = m.post_ln();
-    w.gnn.resize(m.h.num_gnn_layers);
-    w.H0 = take2(c, Na * d.DN);
-    w.M0 = take2(c, Ea * d.D);
-    w.geo = take2(c, Ea * 4);
+    take(c, Na * d.DN, w.H0);
+    take(c, Ea * d.D, w.M0);
+    take(c, Ea * 4, w.geo);
     w.fcd = c.take<float>(Ea);
     w.bd = c.take<float>(Ea);
-    D2 prev = w.H0;
-    for (size_t gi = 0; gi < w.gnn.size(); gi++) {
-        TGnn& G = w.gnn[gi];
-        G.attn.resize(m.h.num_attention_layers);
-        G.TOK = take2(c, Ea * 3 * d.D);
-        G.a0 = take2(c, Ea * d.D);
-        G.XF = take2(c, Ea * d.D);
-        G.CA = take2(c, Ea * 2 * d.D);
-        G.Mout = take2(c, Ea * d.D);
-        if (m.residual() && gi > 0) prev = take2(c, Na * d.DN);
-        G.Hin = prev;
-        for (auto& A : G.attn) {
-            A.X = take2(c, Ra * d.D);
-            A.QKV = take2(c, Ra * 3 * d.D);
-            A.AO = take2(c, Ra * d.D);
-            A.LSE = c.take<float>(Ra * d.NH);
-            A.MS = c.take<float>(Ra * d.NH);
-            A.X1 = take2(c, Ra * d.D);
-            A.VG = take2(c, Ra * 2 * d.DFF);
-            if (post) { A.T1 = take2(c, Ra * d.D); A.S2 = take2(c, Ra * d.D); }
-            A.TOKo = take2(c, Na * d.D);
-            A.H = prev;
-            if (d.expanded) { A.H1 = take2(c, Na * d.DN); A.VGn = take2(c, Na * 2 * d.DNF); }
-            A.Hn = take2(c, Na * d.DN);
-            prev = A.Hn;
-        }
-        G.Hout = prev;
-    }
+    carve_layers(m, d, c, Na, Ea, Ra, w.H0, w.gnn);
     const int wmax = imax(imax(3 * d.D, 2 * d.DFF), imax(2 * d.D, d.DH));
     const int nmax = imax(imax(2 * d.DNF, d.DN), imax(d.DH, d.D));
-    for (auto& t : w.tE) t = take2(c, Ra * wmax);
-    for (auto& t : w.tN) t = take2(c, Na * nmax);
-    w.dX = take2(c, Ra * d.D); w.dX2 = take2(c, Ra * d.D);
-    w.dM = take2(c, Ea * d.D); w.dH = take2(c, Na * d.DN);
-    w.dQKV = take2(c, Ra * 3 * d.D);
+    for (auto& t : w.tE) take(c, Ra * wmax, t);
+    for (auto& t : w.tN) take(c, Na * nmax, t);
+    take(c, Ra * d.D, w.dX); take(c, Ra * d.D, w.dX2);
+    take(c, Ea * d.D, w.dM); take(c, Na * d.DN, w.dH);
+    take(c, Ra * 3 * d.D, w.dQKV);
     w.CC = c.take<float>(Ra * d.NH);
     w.DD = c.take<float>(Ra * d.NH);
     // partial sums of the largest weight gradient (and of the embedding tables)
@@ -689,143 +643,6 @@ static void train_carve(const Model& m, int64_t N, int64_t E, void* base, TWs& w
     w.part = c.take<float>(w.part_floats);
     w.bytes = c.off;
 }
-
-struct TOps {
-    const Model& m;
-    const Graph& g;
-    GD d;
-    hipStream_t st;
-    Lins lin;
-    Ops o;
-    TWs* w;
-    std::map<const float*, float*> off;   // raw parameter storage -> its gradient slot
-    int err = PET_OK;
-    bool hvp = false;   // Hessian-vector mode: the sweep forms no parameter gradient and never looks at a gradient slot
-    TOps(const Model& m_, const Graph& g_, hipStream_t s, TWs* w_, bool hvp_ = false)
-        : m(m_), g(g_), d(dims_of(m_)), st(s), lin{s}, o(m_, g_, s), w(w_), hvp(hvp_) {
-        if (hvp) return;
-        for (const auto& kv : m.raw) {
-            auto it = m.grad_off.find(kv.first);
-            if (it != m.grad_off.end()) off[kv.second.first] = m.grad_flat + it->second;
-        }
-        // a LoRA-adapted Linear is read as W_eff: its gradient goes to the adapter's dL/dW_eff (lora.hip projects it)
-        for (const auto& kv : m.lora)
-            if (kv.second.w_eff) off[kv.second.w_eff] = m.lora_grad + kv.second.dw_off;
-    }
-    float* slot(const float* raw) {
-        auto it = off.find(raw);
-        if (it == off.end()) { err = PET_ERR_ARGUMENT; set_error("gen_train: a parameter has no gradient slot"); return nullptr; }
-        return it->second;
-    }
-    float eps() const { return m.layer_norm() ? 1e-5f : 1.1920929e-07f; }
-    // ---- dual forward pieces
-    void linf(const D2& X, int64_t ldx, const Lin& L, const D2& Y, int64_t ldy, int64_t rows, bool acc = false) const {
-        if (rows <= 0) return;
-        lin.fwd(X.p, ldx, L, Y.p, ldy, rows, acc);
-        Lin nb = L;
-        nb.b = nullptr;   // the tangent of a Linear has no bias
-        lin.fwd(X.t, ldx, nb, Y.t, ldy, rows, acc);
-    }
-    void norm(const D2& X, const float* gamma, const float* beta, const D2& Y, int64_t rows, int W, int ln = -1, float e = -1.f) const {
-        if (rows <= 0) return;
-        const int l = ln < 0 ? (int)m.layer_norm() : ln;
-        k_gt_norm<<<(int)cdiv(rows, 4), 256, 0, st>>>(X.p, X.t, gamma, l ? beta : nullptr, l, e < 0 ? eps() : e, Y.p, Y.t, rows, W);
-    }
-    void silu(const D2& A, const D2& S, int64_t n) const { if (n > 0) k_gt_silu<<<g1(n), 256, 0, st>>>(A.p, A.t, S.p, S.t, n); }
-    void swiglu(const D2& VG, const D2& S, int64_t rows, int F) const {
-        if (rows > 0) k_gt_swiglu<<<g1(rows * F), 256, 0, st>>>(VG.p, VG.t, S.p, S.t, rows, F);
-    }
-    void axpby(float a, const D2& A, int64_t lda, float b, const D2& B, int64_t ldb, const int* index, const D2& Y, int64_t ldy,
-               bool acc, int64_t rows, int W) const {
-        o.axpby(a, A.p, lda, b, B.p, ldb, index, Y.p, ldy, acc, rows, W);
-        o.axpby(a, A.t, lda, b, B.t, ldb, index, Y.t, ldy, acc, rows, W);
-    }
-    void copy(const D2& A, const D2& Y, int64_t rows, int W) const { axpby(1.f, A, W, 0.f, D2(), 0, nullptr, Y, W, false, rows, W); }
-    void zero(const D2& A, int64_t n) const {
-        if (n <= 0) return;
-        (void)hipMemsetAsync(A.p, 0, n * sizeof(float), st);
-        (void)hipMemsetAsync(A.t, 0, n * sizeof(float), st);
-    }
-    // Y = base + w_out(swiglu(w_in(normed ? norm(X) : X))); VG saved
-    void ffn(const D2& Xin, bool normed, const float* gamma, const float* beta, const Lin& w_in, const Lin& w_out, const D2& VG,
-             const D2& base, const D2& Y, const D2& tA, const D2& tB, int64_t rows, int W, int F) const {
-        D2 Nn = Xin;
-        if (normed) { norm(Xin, gamma, beta, tA, rows, W); Nn = tA; }
-        linf(Nn, W, w_in, VG, 2 * F, rows);
-        swiglu(VG, tB, rows, F);
-        if (base.p != Y.p) copy(base, Y, rows, W);
-        linf(tB, F, w_out, Y, W, rows, true);
-    }
-    // ---- reverse pieces
-    void chunked(int64_t rows, int& nc, int64_t& per) const {
-        nc = n_chunks_for(rows);
-        per = (rows + nc - 1) / nc;
-    }
-    // dW += nu_y^T x + lambda_y^T x', db += colsum(nu_y)
-    void wgrad(const Lin& L, const D2& NY, int64_t ldy, const D2& X, int64_t ldx, int64_t rows) {
-        if (rows <= 0 || err || hvp) return;
-        int nc; int64_t per;
-        chunked(rows, nc, per);
-        float* gw = slot(L.w);
-        if (!gw) return;
-        dim3 grid((unsigned)cdiv(L.n_out, 64), (unsigned)cdiv(L.k_in, 64), (unsigned)nc);
-        k_gt_wgrad<<<grid, 256, 0, st>>>(NY.p, X.p, NY.t, X.t, ldy, ldx, rows, L.n_out, L.k_in, per, w->part);
-        const int64_t n = (int64_t)L.n_out * L.k_in;
-        k_gt_reduce<<<g1(n), 256, 0, st>>>(w->part, nc, n, gw);
-        if (L.b) colsum(NY.p, ldy, rows, L.n_out, slot(L.b));
-    }
-    void colsum(const float* A, int64_t lda, int64_t rows, int W, float* dst) {
-        if (rows <= 0 || !dst) return;
-        int nc; int64_t per;
-        chunked(rows, nc, per);
-        k_gt_colsum<<<dim3((unsigned)cdiv(W, 64), (unsigned)nc), 64, 0, st>>>(A, lda, rows, W, per, w->part);
-        k_gt_reduce<<<g1(W), 256, 0, st>>>(w->part, nc, W, dst);
-    }
-    void embed_grad(const int* index, const float* NU, int64_t ld, int64_t rows, int W, const float* table) {
-        if (rows <= 0 || err || hvp) return;
-        float* dst = slot(table);
-        if (!dst) return;
-        int nc; int64_t per;
-        chunked(rows, nc, per);
-        const int ns = m.h.n_species;
-        k_gt_embed_grad<<<dim3((unsigned)cdiv(W, 64), (unsigned)nc), 64, 0, st>>>(index, NU, ld, rows, W, ns, per, w->part);
-        k_gt_reduce<<<g1((int64_t)ns * W), 256, 0, st>>>(w->part, nc, (int64_t)ns * W, dst);
-    }
-    // (nu_x, lambda_x) (+)= W^T (nu_y, lambda_y)
-    void linb(const D2& NY, int64_t ldy, const Lin& L, const D2& NX, int64_t ldx, int64_t rows, bool acc = false) const {
-        if (rows <= 0) return;
-        lin.bwd(NY.p, ldy, L, NX.p, ldx, rows, acc);
-        lin.bwd(NY.t, ldy, L, NX.t, ldx, rows, acc);
-    }
-    // norm reverse incl. the norm's own parameter gradients; G: scratch [rows][W]
-    void norm_rev(const D2& X, const float* gamma, const float* beta, const D2& NY, const D2& NX, bool acc, float* G, int64_t rows,
-                  int W, int ln = -1, float e = -1.f) {
-        if (rows <= 0) return;
-        const int l = ln < 0 ? (int)m.layer_norm() : ln;
-        k_gt_norm_rev<<<(int)cdiv(rows, 4), 256, 0, st>>>(X.p, X.t, gamma, l, e < 0 ? eps() : e, NY.p, NY.t, NX.p, NX.t, acc,
-                                                          hvp ? nullptr : G, rows, W);
-        if (hvp) return;
-        colsum(G, W, rows, W, slot(gamma));
-        if (l && beta) colsum(NY.p, W, rows, W, slot(beta));
-    }
-    // adjoint of the FFN branch (not of the residual path): NIn (+)= ..., parameter gradients added
-    void ffn_rev(const D2& Xin, bool normed, const float* gamma, const float* beta, const Lin& w_in, const Lin& w_out, const D2& VG,
-                 const D2& NY, const D2& NIn, bool acc, const D2& tA, const D2& tB, const D2& tC, int64_t rows, int W, int F) {
-        // recompute N (input of w_in) and S (input of w_out)
-        D2 Nn = Xin;
-        if (normed) { norm(Xin, gamma, beta, tC, rows, W); Nn = tC; }
-        swiglu(VG, tA, rows, F);
-        wgrad(w_out, NY, W, tA, F, rows);
-        linb(NY, W, w_out, tA, F, rows);                                           // (nu, lambda) of S
-        if (rows > 0) k_gt_swiglu_rev<<<g1(rows * F), 256, 0, st>>>(VG.p, VG.t, tA.p, tA.t, tB.p, tB.t, rows, F);  // of VG
-        wgrad(w_in, tB, 2 * F, Nn, W, rows);
-        if (normed) {
-            linb(tB, 2 * F, w_in, tA, W, rows);                                    // of N
-            norm_rev(Xin, gamma, beta, tA, NIn, acc, tC.p, rows, W);
-        } else
-            linb(tB, 2 * F, w_in, NIn, W, rows, acc);
-    }
-};
 
 // ---- system conditioning (conditioning.py:82-100; backend.py:543-545, :628-629): cond_s = W2 silu(W0 [emb_q ; emb_m] + b0)
 // + b2 is added to the node features LEAVING every GNN layer. It does not move with the positions (no tangent), so its
@@ -902,6 +719,190 @@ __global__ __launch_bounds__(256) void k_gt_cond_bwd(const int64_t* __restrict__
     }
 }
 
+// The dual pass of gen_walk.h: every value a (primal, tangent) pair, every adjoint (nu, lambda). In training it forms the
+// parameter gradients; in Hessian-vector mode (hv) none, and the adjoints that reach the geometry are kept instead.
+struct TOps {
+    using V = D2;
+    using CV = D2;
+    const Model& m;
+    const Graph& g;
+    GD d;
+    hipStream_t st;
+    Lins lin;
+    Ops o;
+    TWs* w;
+    std::map<const float*, float*> off;   // raw parameter storage -> its gradient slot
+    int err = PET_OK;
+    const HvpTaps* hv;   // Hessian-vector mode: the sweep forms no parameter gradient and never looks at a gradient slot
+    int64_t N, E, R;
+    Roles<D2> s;
+    D2 geo;
+    float *cond = nullptr, *dcond = nullptr;   // [n_systems][DN] per-system conditioning embedding and its nu-adjoint
+    std::vector<D2> dHl, dMl;                  // adjoints entering the backbone from the heads, per readout layer
+    TOps(const Model& m_, const Graph& g_, hipStream_t st_, TWs* w_, const HvpTaps* hv_ = nullptr)
+        : m(m_), g(g_), d(dims_of(m_)), st(st_), lin{st_}, o(m_, g_, st_), w(w_), hv(hv_), N(o.N), E(o.E), R(o.R), geo(w_->geo) {
+        s.normed = w->tE[0]; s.OUT = w->tE[1]; s.act = w->tE[2]; s.nNormed = w->tN[0]; s.nAct = w->tN[1];
+        s.dAO = w->tE[0]; s.dOUT = w->tE[1]; s.dVG = w->tE[2]; s.re = w->tE[3]; s.dXin = w->tE[4];
+        s.dH1 = w->tN[0]; s.nA = w->tN[1]; s.nB = w->tN[2]; s.nRe = w->tN[3]; s.dTOKo = w->tN[3];
+        if (hv) return;
+        for (const auto& kv : m.raw) {
+            auto it = m.grad_off.find(kv.first);
+            if (it != m.grad_off.end()) off[kv.second.first] = m.grad_flat + it->second;
+        }
+        // a LoRA-adapted Linear is read as W_eff: its gradient goes to the adapter's dL/dW_eff (lora.hip projects it)
+        for (const auto& kv : m.lora)
+            if (kv.second.w_eff) off[kv.second.w_eff] = m.lora_grad + kv.second.dw_off;
+    }
+    float* slot(const float* raw) {
+        auto it = off.find(raw);
+        if (it == off.end()) { err = PET_ERR_ARGUMENT; set_error("gen_train: a parameter has no gradient slot"); return nullptr; }
+        return it->second;
+    }
+    // ---- forward operations
+    void linf(const D2& X, int64_t ldx, const Lin& L, const D2& Y, int64_t ldy, int64_t rows, bool acc = false) const {
+        if (rows <= 0) return;
+        lin.fwd(X.p, ldx, L, Y.p, ldy, rows, acc);
+        Lin nb = L;
+        nb.b = nullptr;   // the tangent of a Linear has no bias
+        lin.fwd(X.t, ldx, nb, Y.t, ldy, rows, acc);
+    }
+    void norm(const D2& X, const float* gamma, const float* beta, const D2& Y, int64_t rows, int W, int ln = -1, float e = -1.f) const {
+        if (rows <= 0) return;
+        const int l = ln < 0 ? (int)m.layer_norm() : ln;
+        k_gt_norm<<<(int)cdiv(rows, 4), 256, 0, st>>>(X.p, X.t, gamma, l ? beta : nullptr, l, e < 0 ? o.eps() : e, Y.p, Y.t, rows, W);
+    }
+    void silu(const D2& A, const D2& S, int64_t n) const { if (n > 0) k_gt_silu<<<g1(n), 256, 0, st>>>(A.p, A.t, S.p, S.t, n); }
+    void swiglu(const D2& VG, const D2& S, int64_t rows, int F) const {
+        if (rows > 0) k_gt_swiglu<<<g1(rows * F), 256, 0, st>>>(VG.p, VG.t, S.p, S.t, rows, F);
+    }
+    void axpby(float a, const D2& A, int64_t lda, float b, const D2& B, int64_t ldb, const int* index, const D2& Y, int64_t ldy,
+               bool acc, int64_t rows, int W) const {
+        o.axpby(a, A.p, lda, b, B.p, ldb, index, Y.p, ldy, acc, rows, W);
+        o.axpby(a, A.t, lda, b, B.t, ldb, index, Y.t, ldy, acc, rows, W);
+    }
+    void copy(const D2& A, const D2& Y, int64_t rows, int W) const { axpby(1.f, A, W, 0.f, D2(), 0, nullptr, Y, W, false, rows, W); }
+    void zero(const D2& A, int64_t n) const { o.zero(A.p, n); o.zero(A.t, n); }
+    // a table row does not move with the positions: the tangent half is zero (a strided one by the row kernel)
+    void embed(const int* index, const float* table, const D2& Y, int64_t ldy, int64_t rows, int W) const {
+        o.embed(index, table, Y.p, ldy, rows, W);
+        if (ldy == W) o.zero(Y.t, rows * W);
+        else o.axpby(0.f, nullptr, 0, 0.f, nullptr, 0, nullptr, Y.t, ldy, false, rows, W);
+    }
+    void attn(const TAttn& A) const {
+        attn_dispatch(d.HD, [&](auto hdm) {
+            k_gt_attn<decltype(hdm)::value><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
+                A.QKV.p, A.QKV.t, g.rowptr, g.fc, w->bd, A.AO.p, A.AO.t, A.LSE, A.MS, E, d.D, d.NH, d.HD, o.scale);
+        });
+    }
+    void add_cond(const D2& H) const { k_gen_add_cond<<<g1(N * d.DN), 256, 0, st>>>(H.p, cond, g.sys, g.cond_sys, N, d.DN); }
+    void re_norm(const D2& X, const float* gamma, const float* beta, const D2& Y, int64_t rows, int W, int ln = -1, float e = -1.f) const {
+        norm(X, gamma, beta, Y, rows, W, ln, e);
+    }
+    void re_silu(const D2& A, const D2& S, int64_t n) const { silu(A, S, n); }
+    void re_swiglu(const D2& VG, const D2& S, int64_t rows, int F) const { swiglu(VG, S, rows, F); }
+    // ---- reverse operations
+    void chunked(int64_t rows, int& nc, int64_t& per) const {
+        nc = n_chunks_for(rows);
+        per = (rows + nc - 1) / nc;
+    }
+    // dW += nu_y^T x + lambda_y^T x', db += colsum(nu_y)
+    void wgrad(const Lin& L, const D2& NY, int64_t ldy, const D2& X, int64_t ldx, int64_t rows) {
+        if (rows <= 0 || err || hv) return;
+        int nc; int64_t per;
+        chunked(rows, nc, per);
+        float* gw = slot(L.w);
+        if (!gw) return;
+        dim3 grid((unsigned)cdiv(L.n_out, 64), (unsigned)cdiv(L.k_in, 64), (unsigned)nc);
+        k_gt_wgrad<<<grid, 256, 0, st>>>(NY.p, X.p, NY.t, X.t, ldy, ldx, rows, L.n_out, L.k_in, per, w->part);
+        const int64_t n = (int64_t)L.n_out * L.k_in;
+        k_gt_reduce<<<g1(n), 256, 0, st>>>(w->part, nc, n, gw);
+        if (L.b) colsum(NY.p, ldy, rows, L.n_out, slot(L.b));
+    }
+    void colsum(const float* A, int64_t lda, int64_t rows, int W, float* dst) {
+        if (rows <= 0 || !dst) return;
+        int nc; int64_t per;
+        chunked(rows, nc, per);
+        k_gt_colsum<<<dim3((unsigned)cdiv(W, 64), (unsigned)nc), 64, 0, st>>>(A, lda, rows, W, per, w->part);
+        k_gt_reduce<<<g1(W), 256, 0, st>>>(w->part, nc, W, dst);
+    }
+    void embed_grad(const int* index, const D2& NU, int64_t ld, int64_t rows, int W, const float* table) {   // (the nu half)
+        if (rows <= 0 || err || hv) return;
+        float* dst = slot(table);
+        if (!dst) return;
+        int nc; int64_t per;
+        chunked(rows, nc, per);
+        const int ns = m.h.n_species;
+        k_gt_embed_grad<<<dim3((unsigned)cdiv(W, 64), (unsigned)nc), 64, 0, st>>>(index, NU.p, ld, rows, W, ns, per, w->part);
+        k_gt_reduce<<<g1((int64_t)ns * W), 256, 0, st>>>(w->part, nc, (int64_t)ns * W, dst);
+    }
+    // (nu_x, lambda_x) (+)= W^T (nu_y, lambda_y)
+    void linb(const D2& NY, int64_t ldy, const Lin& L, const D2& NX, int64_t ldx, int64_t rows, bool acc = false) const {
+        if (rows <= 0) return;
+        lin.bwd(NY.p, ldy, L, NX.p, ldx, rows, acc);
+        lin.bwd(NY.t, ldy, L, NX.t, ldx, rows, acc);
+    }
+    // norm reverse incl. the norm's own parameter gradients; G: scratch [rows][W] (its primal half)
+    void norm_rev(const D2& X, const float* gamma, const float* beta, const D2& NY, const D2& NX, bool acc, const D2& G, int64_t rows,
+                  int W, int ln = -1, float e = -1.f) {
+        if (rows <= 0) return;
+        const int l = ln < 0 ? (int)m.layer_norm() : ln;
+        k_gt_norm_rev<<<(int)cdiv(rows, 4), 256, 0, st>>>(X.p, X.t, gamma, l, e < 0 ? o.eps() : e, NY.p, NY.t, NX.p, NX.t, acc,
+                                                          hv ? nullptr : G.p, rows, W);
+        if (hv) return;
+        colsum(G.p, W, rows, W, slot(gamma));
+        if (l && beta) colsum(NY.p, W, rows, W, slot(beta));
+    }
+    void silu_rev(const D2& A, const D2& NS, int64_t n) const {   // in place on the adjoint
+        if (n > 0) k_gt_silu_rev<<<g1(n), 256, 0, st>>>(A.p, A.t, NS.p, NS.t, NS.p, NS.t, n);
+    }
+    void swiglu_rev(const D2& VG, const D2& NS, const D2& NVG, int64_t rows, int F) const {
+        if (rows > 0) k_gt_swiglu_rev<<<g1(rows * F), 256, 0, st>>>(VG.p, VG.t, NS.p, NS.t, NVG.p, NVG.t, rows, F);
+    }
+    void attn_rev(const TAttn& A, const D2& dAO) const {   // -> w->dQKV; hv: the key-bias adjoints per head too
+        attn_dispatch(d.HD, [&](auto hdm) {
+            constexpr int HDM = decltype(hdm)::value;
+            const dim3 grid((unsigned)N, (unsigned)d.NH);
+            k_gt_attn_rev_q<HDM><<<grid, 64, 0, st>>>(A.QKV.p, A.QKV.t, dAO.p, dAO.t, A.LSE, A.MS, g.rowptr, g.fc, w->bd, w->dQKV.p,
+                                                      w->dQKV.t, w->CC, w->DD, E, d.D, d.NH, d.HD, o.scale);
+            if (!hv)
+                k_gt_attn_rev_k<HDM><<<grid, 64, 0, st>>>(A.QKV.p, A.QKV.t, dAO.p, dAO.t, A.LSE, A.MS, w->CC, w->DD, g.rowptr, g.fc,
+                                                          w->bd, w->dQKV.p, w->dQKV.t, E, d.D, d.NH, d.HD, o.scale, nullptr, nullptr);
+            else
+                k_gt_attn_rev_k<HDM, true><<<grid, 64, 0, st>>>(A.QKV.p, A.QKV.t, dAO.p, dAO.t, A.LSE, A.MS, w->CC, w->DD, g.rowptr,
+                                                                g.fc, w->bd, w->dQKV.p, w->dQKV.t, E, d.D, d.NH, d.HD, o.scale, hv->sb,
+                                                                hv->sdb);
+        });
+    }
+    // ---- sinks: heads in head order, attention layers and GNN layers in the order the sweep visits them
+    void key_bias_sink(bool first) const {
+        if (hv && E > 0) k_hvp_bias_sum<<<g1(E), 256, 0, st>>>(hv->sb, hv->sdb, d.NH, E, hv->db, hv->dbd, !first);
+    }
+    void geo_sink(const D2& dTOK, int kin, const Lin& eemb, bool first) const {   // (nu, lambda) of geo, over the layers
+        if (hv) linb(dTOK, kin, eemb, D2{hv->ngeo, hv->lgeo}, 4, E, !first);
+    }
+    void cond_accum(const D2& dH, bool first) const {
+        if (dcond && !hv) k_gt_cond_accum<<<(int)g.n_cond_systems, 256, 0, st>>>(dH.p, g.sys, g.cond_sys, (int)N, d.DN, dcond, !first);
+    }
+    void seed(int l, const D2& dH, const D2& dE) const {   // (one readout layer, no residual: the heads wrote them in place)
+        if (dHl[l].p == dH.p) return;
+        copy(dHl[l], dH, N, d.DN);
+        copy(dMl[l], dE, E, d.D);
+    }
+    // reverse of one head branch (gen_head on X, then the last layer): gradients of its three Linears, the adjoint of X -> dX
+    void head_rev(const Lin& last, const Lin& h2, const Lin& h0, const D2& seeds, const D2& X, int W, int64_t rows, const D2& a1,
+                  const D2& s1, const D2& a2, const D2& s2, const D2& dX) {
+        const int DH = d.DH;
+        wgrad(last, seeds, 1, s2, DH, rows);
+        linb(seeds, 1, last, s2, DH, rows);   // (nu, lambda) of s2
+        silu_rev(a2, s2, rows * DH);
+        wgrad(h2, s2, DH, s1, DH, rows);
+        linb(s2, DH, h2, s1, DH, rows);       // of s1
+        silu_rev(a1, s1, rows * DH);
+        wgrad(h0, s1, DH, X, W, rows);
+        linb(s1, DH, h0, dX, W, rows);
+    }
+};
+
 }  // namespace
 
 // (nu_x, lambda_x) = adjoint of (y, y') = norm(x, x') on rows of any width (k_gt_norm_rev) for another caller: the
@@ -949,36 +950,28 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
     TWs w;
     train_carve(m, g.n_nodes, g.n_edges, ws2, w);
     PET_REQUIRE((int64_t)w.bytes <= ws2_bytes, PET_ERR_ARGUMENT, "second-order workspace too small");
-    TOps t(m, g, st, &w, hv != nullptr);
+    TOps t(m, g, st, &w, hv);
     const GD& d = t.d;
-    const int64_t N = g.n_nodes, E = g.n_edges, R = N + E;
+    const int64_t N = t.N, E = t.E, R = t.R;
     if (N == 0) return PET_OK;
-    // E == 0 (a batch of isolated atoms): every helper below skips zero-row work, the raw E-row launches are guarded; what
-    // remains is the node path -- embeddings, centre tokens attending to themselves, centre MLPs, node heads
-    const int D = d.D, DN = d.DN;
-    const bool post = m.post_ln(), res = m.residual();
-    const float scale = 1.0f / (sqrtf((float)d.HD) * m.h.attention_temperature);
-    const int L = m.h.num_gnn_layers, AL = m.h.num_attention_layers, NR = m.num_readout_layers();
-    // the heads of the trained target, one per readout layer ("@": runtime.HipModel.load)
+    const int D = d.D, DN = d.DN, DH = d.DH, NR = m.num_readout_layers();
+    const bool res = m.residual();
+    // the heads of the trained target, one per readout layer
     std::vector<const HeadW*> heads(NR);
     std::vector<const LastW*> lasts(NR);
     for (int l = 0; fused && l < NR; l++) {
-        auto hi = m.heads.find("@|" + std::to_string(l));
-        auto li = m.lasts.find("@|" + std::to_string(l) + "|@");
-        PET_REQUIRE(hi != m.heads.end() && li != m.lasts.end() && li->second.P == 1, PET_ERR_ARGUMENT,
-                    "training needs the single-property target uploaded as the fused head of every readout layer");
-        heads[l] = &hi->second;
-        lasts[l] = &li->second;
+        int rc = fused_heads(m, l, heads[l], lasts[l],
+                             "training needs the single-property target uploaded as the fused head of every readout layer");
+        if (rc) return rc;
     }
-    float *cond = nullptr, *dcond = nullptr;   // [n_systems][DN] per-system embedding and its nu-adjoint
-    PoolBuf cond_pool, extra_pool;             // returned to the stream's pool on every exit
+    PoolBuf cond_pool, extra_pool;   // returned to the stream's pool on every exit
     if (conditioned) {
         const size_t nc = (size_t)g.n_cond_systems * DN;
         PET_HIP_CHECK(cond_pool.alloc(2 * nc * sizeof(float), st));
-        cond = cond_pool.as<float>();
-        dcond = cond + nc;
+        t.cond = cond_pool.as<float>();
+        t.dcond = t.cond + nc;
         k_gen_system_cond<<<(int)g.n_cond_systems, 128, 3 * DN * sizeof(float), st>>>(
-            g.cond_charge, g.cond_spin, m.cond_qe, m.cond_se, m.cond_w0, m.cond_b0, m.cond_w2, m.cond_b2, cond, m.h.max_charge,
+            g.cond_charge, g.cond_spin, m.cond_qe, m.cond_se, m.cond_w0, m.cond_b0, m.cond_w2, m.cond_b2, t.cond, m.h.max_charge,
             DN);
     }
     // ---------------- sweep 1: dual forward ----------------
@@ -986,11 +979,10 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
     PET_HIP_CHECK(hipMemcpyAsync(w.geo.p, g.geo, E * 4 * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (u) {
         PET_REQUIRE(!ucell || g.shift, PET_ERR_ARGUMENT, "a cell tangent needs a pet_graph_build handle (cell shifts)");
-        if (E == 0) {
-        } else if (g.adaptive) {   // the pair cutoffs move with the positions too (so.hip: implicit-function tangent of the solver)
+        if (E > 0 && g.adaptive) {   // the pair cutoffs move with the positions too (so.hip: implicit-function tangent of the solver)
             int rc = geometry_tangent(m, g, u, ucell, w.geo.t, w.fcd, w.bd, st);
             if (rc) return rc;
-        } else
+        } else if (E > 0)
             k_gt_geo<<<g1(E), 256, 0, st>>>(g.geo, g.d0, g.fc, g.ctr, g.nbr, g.shift, g.sys, u, ucell,
                                             reinterpret_cast<float4*>(w.geo.t), w.fcd, w.bd, E, m.h.cutoff, m.h.cutoff_width,
                                             m.h.cutoff_function);
@@ -999,120 +991,32 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
         PET_HIP_CHECK(hipMemsetAsync(w.fcd, 0, E * sizeof(float), st));
         PET_HIP_CHECK(hipMemsetAsync(w.bd, 0, E * sizeof(float), st));
     }
-    k_gen_embed<<<g1(N * DN), 256, 0, st>>>(g.sp, m.node_emb, w.H0.p, DN, N, DN);
-    PET_HIP_CHECK(hipMemsetAsync(w.H0.t, 0, N * DN * sizeof(float), st));
-    if (E > 0) k_gen_embed<<<g1(E * D), 256, 0, st>>>(g.sp_nbr, m.edge_emb, w.M0.p, D, E, D);
-    PET_HIP_CHECK(hipMemsetAsync(w.M0.t, 0, E * D * sizeof(float), st));
-    D2 Min = w.M0;
-    for (int gi = 0; gi < L; gi++) {
-        const GnnLayerW& G = m.gnn[gi];
-        TGnn& B = w.gnn[gi];
-        if (res && gi > 0) {
-            k_gen_embed<<<g1(N * DN), 256, 0, st>>>(g.sp, m.node_embs[gi], B.Hin.p, DN, N, DN);
-            PET_HIP_CHECK(hipMemsetAsync(B.Hin.t, 0, N * DN * sizeof(float), st));
-        }
-        const int kin = (gi == 0 ? 2 : 3) * D;
-        t.linf(w.geo, 4, G.eemb, B.TOK, kin, E);
-        if (gi > 0) {
-            if (E > 0) k_gen_embed<<<g1(E * D), 256, 0, st>>>(g.sp_nbr, G.nbr_emb, B.TOK.p + D, kin, E, D);
-            t.o.axpby(0.f, nullptr, 0, 0.f, nullptr, 0, nullptr, B.TOK.t + D, kin, false, E, D);
-        }
-        {
-            D2 dst{B.TOK.p + (gi == 0 ? D : 2 * D), B.TOK.t + (gi == 0 ? D : 2 * D)};
-            t.axpby(1.f, Min, D, 0.f, D2(), 0, nullptr, dst, kin, false, E, D);
-        }
-        t.linf(B.TOK, kin, G.c0, B.a0, D, E);
-        t.silu(B.a0, w.tE[1], E * D);
-        t.linf(w.tE[1], D, G.compress2, B.attn[0].X, D, E);
-        for (int a = 0; a < AL; a++) {
-            const AttnLayerW& A = G.attn[a];
-            TAttn& Ab = B.attn[a];
-            D2 Xnext = (a + 1 < AL) ? B.attn[a + 1].X : B.XF;
-            D2 Xc{Ab.X.p + E * D, Ab.X.t + E * D};
-            if (d.expanded) t.linf(Ab.H, DN, A.cc, Xc, D, N);
-            else t.copy(Ab.H, Xc, N, D);
-            D2 Xatt = Ab.X;
-            if (!post) { t.norm(Ab.X, A.g_attn, A.b_attn, w.tE[0], R, D); Xatt = w.tE[0]; }
-            t.linf(Xatt, D, A.qkv, Ab.QKV, 3 * D, R);
-            attn_dispatch(d.HD, [&](auto hdm) {
-                k_gt_attn<decltype(hdm)::value><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
-                    Ab.QKV.p, Ab.QKV.t, g.rowptr, g.fc, w.bd, Ab.AO.p, Ab.AO.t, Ab.LSE, Ab.MS, E, D, d.NH, d.HD, scale);
-            });
-            D2 OUT = w.tE[1];
-            t.linf(Ab.AO, D, A.out, OUT, D, R);
-            D2 OUTc{OUT.p + E * D, OUT.t + E * D};
-            if (!post) {
-                t.copy(OUTc, Ab.TOKo, N, D);
-                t.axpby(1.f, Ab.X, D, 1.f, OUT, D, nullptr, Ab.X1, D, false, E, D);
-                t.ffn(Ab.X1, true, A.g_mlp, A.b_mlp, A.mlp_in, A.mlp_out, Ab.VG, Ab.X1, Xnext, w.tE[0], w.tE[2], E, D, d.DFF);
-            } else {
-                t.axpby(1.f, Ab.X, D, 1.f, OUT, D, nullptr, Ab.X1, D, false, R, D);
-                t.norm(Ab.X1, A.g_attn, A.b_attn, Ab.T1, R, D);
-                t.ffn(Ab.T1, false, nullptr, nullptr, A.mlp_in, A.mlp_out, Ab.VG, Ab.T1, Ab.S2, w.tE[0], w.tE[2], R, D, d.DFF);
-                t.norm(Ab.S2, A.g_mlp, A.b_mlp, w.tE[0], R, D);
-                t.copy(w.tE[0], Xnext, E, D);
-                D2 T2c{w.tE[0].p + E * D, w.tE[0].t + E * D};
-                t.copy(T2c, Ab.TOKo, N, D);
-            }
-            if (d.expanded) {
-                t.copy(Ab.H, Ab.H1, N, DN);
-                t.linf(Ab.TOKo, D, A.ce, Ab.H1, DN, N, true);
-                t.ffn(Ab.H1, true, A.g_center, A.b_center, A.cmlp_in, A.cmlp_out, Ab.VGn, Ab.H1, Ab.Hn, w.tN[0], w.tN[1], N, DN, d.DNF);
-            } else
-                t.copy(Ab.TOKo, Ab.Hn, N, DN);
-        }
-        if (conditioned)   // backend.py:543-545: the node features LEAVING the GNN layer (primal only: no tangent)
-            k_gen_add_cond<<<g1(N * DN), 256, 0, st>>>(B.Hout.p, cond, g.sys, g.cond_sys, N, DN);
-        if (res) {
-            if (gi + 1 < L) t.axpby(0.5f, Min, D, 0.5f, B.XF, D, g.rev, B.Mout, D, false, E, D);
-        } else {
-            D2 CAT = w.tE[0];
-            t.axpby(1.f, B.XF, D, 0.f, D2(), 0, nullptr, CAT, 2 * D, false, E, D);
-            D2 CATr{CAT.p + D, CAT.t + D};
-            t.axpby(0.f, D2(), 0, 1.f, B.XF, D, g.rev, CATr, 2 * D, false, E, D);
-            t.norm(CAT, G.ln_g, G.ln_b, w.tE[1], E, 2 * D, 1, 1e-5f);
-            t.linf(w.tE[1], 2 * D, G.comb0, B.CA, 2 * D, E);
-            t.silu(B.CA, w.tE[2], E * 2 * D);
-            t.axpby(1.f, Min, D, 1.f, B.XF, D, nullptr, B.Mout, D, false, E, D);
-            t.linf(w.tE[2], 2 * D, G.comb2, B.Mout, D, E, true);
-        }
-        Min = B.Mout;
-    }
+    gen_walk_forward(t, w);
     // ---------------- heads: tangent energies and the seeds of sweep 2 ----------------
-    // scratch per readout layer (recomputed in the reverse part): a1, s1, a2, s2 [rows][DH], predictions [rows]
-    const int DH = d.DH;
-    auto head_dual = [&](const Lin& h0, const Lin& h2, const D2& X, int W, int64_t rows, const D2& a1, const D2& s1, const D2& a2,
-                         const D2& s2) {
-        t.linf(X, W, h0, a1, DH, rows);
-        t.silu(a1, s1, rows * DH);
-        t.linf(s1, DH, h2, a2, DH, rows);
-        t.silu(a2, s2, rows * DH);
-    };
-    // adjoints entering the backbone from the heads, per readout layer: kept for the residual featuriser in dHl / dMl
-    std::vector<D2> dHl(NR), dMl(NR);
-    float* extra = nullptr;
+    // adjoints entering the backbone from the heads, per readout layer: kept apart for the residual featuriser
+    t.dHl.resize(NR);
+    t.dMl.resize(NR);
     {
         size_t fl = 0;
-        if (NR > 1 || res) fl = (size_t)NR * 2 * ((size_t)N * DN + (size_t)E * D);   // (residual, one layer: dM is zeroed below)
+        if (NR > 1 || res) fl = (size_t)NR * 2 * ((size_t)N * DN + (size_t)E * D);   // (residual, one layer: dM is zeroed by the walk)
         fl += 2 * (size_t)(N + E) + 4 * (size_t)(N + E);   // predictions (dual) and their adjoints
         PET_HIP_CHECK(extra_pool.alloc(fl * sizeof(float), st));
-        extra = extra_pool.as<float>();
     }
-    float* ex = extra;
+    float* ex = extra_pool.as<float>();
     D2 npred{ex, ex + N}; ex += 2 * N;
     D2 epred{ex, ex + E}; ex += 2 * E;
     D2 nnp{ex, ex + N}; ex += 2 * N;
     D2 nep{ex, ex + E}; ex += 2 * E;
     for (int l = 0; l < NR; l++) {
         if (NR > 1 || res) {
-            dHl[l] = D2{ex, ex + N * DN}; ex += 2 * N * DN;
-            dMl[l] = D2{ex, ex + E * D}; ex += 2 * E * D;
-        } else { dHl[l] = w.dH; dMl[l] = w.dM; }
+            t.dHl[l] = D2{ex, ex + N * DN}; ex += 2 * N * DN;
+            t.dMl[l] = D2{ex, ex + E * D}; ex += 2 * E * D;
+        } else { t.dHl[l] = w.dH; t.dMl[l] = w.dM; }
     }
     if (fused) k_gt_seeds<<<g1(R), 256, 0, st>>>(nA, lA, g.ctr, g.fc, w.fcd, nnp.p, nnp.t, nep.p, nep.t, N, E);
     for (int l = 0; !fused && l < NR; l++) {   // no fused head: the further targets' seeds are all that enters
-        t.zero(dHl[l], N * DN);
-        t.zero(dMl[l], E * D);
+        t.zero(t.dHl[l], N * DN);
+        t.zero(t.dMl[l], E * D);
     }
     for (int l = 0; fused && l < NR; l++) {
         const TGnn& Bl = res ? w.gnn[l] : w.gnn.back();
@@ -1121,185 +1025,30 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
         const LastW& Lw = *lasts[l];
         Lin ln; ln.w = Lw.nw; ln.b = Lw.nb; ln.n_out = 1; ln.k_in = DH;
         Lin le; le.w = Lw.ew; le.b = Lw.eb; le.n_out = 1; le.k_in = DH;
-        // node branch: forward (dual), then reverse with weight gradients
-        head_dual(H.nh0, H.nh2, Hf, DN, N, w.tN[0], w.tN[1], w.tN[2], w.tN[3]);
+        // both branches forward (dual; the intermediates stay in the temporaries), then in reverse with weight gradients
+        gen_head(t, H.nh0, H.nh2, Hf, DN, N, w.tN[0], w.tN[1], w.tN[2], w.tN[3]);
         t.linf(w.tN[3], DH, ln, npred, 1, N);
-        head_dual(H.eh0, H.eh2, Mf, D, E, w.tE[0], w.tE[1], w.tE[2], w.tE[3]);
+        gen_head(t, H.eh0, H.eh2, Mf, D, E, w.tE[0], w.tE[1], w.tE[2], w.tE[3]);
         t.linf(w.tE[3], DH, le, epred, 1, E);
         if (tangent_atomic)
             k_gt_atom_sum<<<g1(N), 256, 0, st>>>(npred.p, npred.t, epred.p, epred.t, g.fc, w.fcd, g.rowptr, tangent_atomic,
                                                  l > 0, N);
         if (hv && E > 0) k_hvp_fc_adj<<<g1(E), 256, 0, st>>>(nA, lA, g.ctr, epred.p, epred.t, hv->dfc, hv->dfcd, l > 0, E);
-        // reverse of the node head
-        t.wgrad(ln, nnp, 1, w.tN[3], DH, N);
-        t.linb(nnp, 1, ln, w.tN[3], DH, N);                                                       // (nu, lambda) of s2
-        k_gt_silu_rev<<<g1(N * DH), 256, 0, st>>>(w.tN[2].p, w.tN[2].t, w.tN[3].p, w.tN[3].t, w.tN[3].p, w.tN[3].t, N * DH);
-        t.wgrad(H.nh2, w.tN[3], DH, w.tN[1], DH, N);
-        t.linb(w.tN[3], DH, H.nh2, w.tN[1], DH, N);                                               // of s1
-        k_gt_silu_rev<<<g1(N * DH), 256, 0, st>>>(w.tN[0].p, w.tN[0].t, w.tN[1].p, w.tN[1].t, w.tN[1].p, w.tN[1].t, N * DH);
-        t.wgrad(H.nh0, w.tN[1], DH, Hf, DN, N);
-        t.linb(w.tN[1], DH, H.nh0, dHl[l], DN, N);
-        // reverse of the edge head
-        t.wgrad(le, nep, 1, w.tE[3], DH, E);
-        t.linb(nep, 1, le, w.tE[3], DH, E);
-        if (E > 0) k_gt_silu_rev<<<g1(E * DH), 256, 0, st>>>(w.tE[2].p, w.tE[2].t, w.tE[3].p, w.tE[3].t, w.tE[3].p, w.tE[3].t, E * DH);
-        t.wgrad(H.eh2, w.tE[3], DH, w.tE[1], DH, E);
-        t.linb(w.tE[3], DH, H.eh2, w.tE[1], DH, E);
-        if (E > 0) k_gt_silu_rev<<<g1(E * DH), 256, 0, st>>>(w.tE[0].p, w.tE[0].t, w.tE[1].p, w.tE[1].t, w.tE[1].p, w.tE[1].t, E * DH);
-        t.wgrad(H.eh0, w.tE[1], DH, Mf, D, E);
-        t.linb(w.tE[1], DH, H.eh0, dMl[l], D, E);
+        t.head_rev(ln, H.nh2, H.nh0, nnp, Hf, DN, N, w.tN[0], w.tN[1], w.tN[2], w.tN[3], t.dHl[l]);
+        t.head_rev(le, H.eh2, H.eh0, nep, Mf, D, E, w.tE[0], w.tE[1], w.tE[2], w.tE[3], t.dMl[l]);
     }
     for (int l = 0; l < n_seed; l++) {
-        if (seed_node && seed_node[l]) t.o.axpby(1.f, seed_node[l], DN, 0.f, nullptr, 0, nullptr, dHl[l].p, DN, true, N, DN);
-        if (seed_edge && seed_edge[l]) t.o.axpby(1.f, seed_edge[l], D, 0.f, nullptr, 0, nullptr, dMl[l].p, D, true, E, D);
+        if (seed_node && seed_node[l]) t.o.axpby(1.f, seed_node[l], DN, 0.f, nullptr, 0, nullptr, t.dHl[l].p, DN, true, N, DN);
+        if (seed_edge && seed_edge[l]) t.o.axpby(1.f, seed_edge[l], D, 0.f, nullptr, 0, nullptr, t.dMl[l].p, D, true, E, D);
     }
     // ---------------- sweep 2: joint reverse through the backbone ----------------
-    if (res) t.zero(w.dM, E * D);   // the last layer's messages are never read
-    for (int gi = L - 1; gi >= 0; gi--) {
-        const GnnLayerW& G = m.gnn[gi];
-        TGnn& B = w.gnn[gi];
-        const D2 MinF = gi == 0 ? w.M0 : w.gnn[gi - 1].Mout;
-        D2 dXF = w.dX, dMin = w.dX2;
-        if (res) {
-            t.copy(dHl[gi], w.dH, N, DN);
-            t.copy(dMl[gi], dXF, E, D);
-            if (gi + 1 < L) {
-                t.axpby(0.f, D2(), 0, 0.5f, w.dM, D, g.rev, dXF, D, true, E, D);
-                t.axpby(0.5f, w.dM, D, 0.f, D2(), 0, nullptr, dMin, D, false, E, D);
-            } else
-                t.zero(dMin, E * D);
-        } else {
-            // Mout = Min + XF + comb2(silu(comb0(LN([XF ; XF[rev]]))))
-            D2 CAT = w.tE[0];
-            t.axpby(1.f, B.XF, D, 0.f, D2(), 0, nullptr, CAT, 2 * D, false, E, D);
-            D2 CATr{CAT.p + D, CAT.t + D};
-            t.axpby(0.f, D2(), 0, 1.f, B.XF, D, g.rev, CATr, 2 * D, false, E, D);
-            t.silu(B.CA, w.tE[1], E * 2 * D);                                                   // input of comb2
-            t.wgrad(G.comb2, w.dM, D, w.tE[1], 2 * D, E);
-            t.linb(w.dM, D, G.comb2, w.tE[1], 2 * D, E);                                        // of silu(CA)
-            if (E > 0) k_gt_silu_rev<<<g1(E * 2 * D), 256, 0, st>>>(B.CA.p, B.CA.t, w.tE[1].p, w.tE[1].t, w.tE[1].p, w.tE[1].t, E * 2 * D);
-            t.norm(CAT, G.ln_g, G.ln_b, w.tE[2], E, 2 * D, 1, 1e-5f);                            // input of comb0
-            t.wgrad(G.comb0, w.tE[1], 2 * D, w.tE[2], 2 * D, E);
-            t.linb(w.tE[1], 2 * D, G.comb0, w.tE[2], 2 * D, E);                                  // of LN(CAT)
-            t.norm_rev(CAT, G.ln_g, G.ln_b, w.tE[2], w.tE[1], false, w.tE[3].p, E, 2 * D, 1, 1e-5f);   // of CAT -> tE[1]
-            t.copy(w.dM, dXF, E, D);
-            D2 dCATr{w.tE[1].p + D, w.tE[1].t + D};
-            t.axpby(1.f, w.tE[1], 2 * D, 1.f, dCATr, 2 * D, g.rev, dXF, D, true, E, D);
-            t.copy(w.dM, dMin, E, D);
-        }
-        if (conditioned && !hv)
-            k_gt_cond_accum<<<(int)g.n_cond_systems, 256, 0, st>>>(w.dH.p, g.sys, g.cond_sys, (int)N, DN, dcond, gi == L - 1 ? 0 : 1);
-        for (int a = AL - 1; a >= 0; a--) {
-            const AttnLayerW& A = G.attn[a];
-            TAttn& Ab = B.attn[a];
-            // ---- node update
-            D2 dTOKo = w.tN[3];
-            if (d.expanded) {
-                D2 dH1 = w.tN[0];
-                t.copy(w.dH, dH1, N, DN);
-                t.ffn_rev(Ab.H1, true, A.g_center, A.b_center, A.cmlp_in, A.cmlp_out, Ab.VGn, w.dH, dH1, true, w.tN[1], w.tN[2],
-                          w.tN[3], N, DN, d.DNF);
-                t.wgrad(A.ce, dH1, DN, Ab.TOKo, D, N);
-                t.linb(dH1, DN, A.ce, dTOKo, D, N);
-                t.copy(dH1, w.dH, N, DN);
-            } else {
-                t.copy(w.dH, dTOKo, N, D);
-                t.zero(w.dH, N * DN);
-            }
-            D2 dOUT = w.tE[1], dXin = w.tE[4];
-            D2 dOUTc{dOUT.p + E * D, dOUT.t + E * D}, dXinc{dXin.p + E * D, dXin.t + E * D};
-            if (!post) {
-                D2 dX1 = dXin;
-                t.copy(dXF, dX1, E, D);
-                t.ffn_rev(Ab.X1, true, A.g_mlp, A.b_mlp, A.mlp_in, A.mlp_out, Ab.VG, dXF, dX1, true, w.tE[0], w.tE[2], w.tE[3], E, D,
-                          d.DFF);
-                t.copy(dX1, dOUT, E, D);
-                t.copy(dTOKo, dOUTc, N, D);
-                t.zero(dXinc, N * D);
-            } else {
-                D2 dT2 = w.tE[0];
-                t.copy(dXF, dT2, E, D);
-                D2 dT2c{dT2.p + E * D, dT2.t + E * D};
-                t.copy(dTOKo, dT2c, N, D);
-                D2 dS2 = w.tE[1];
-                t.norm_rev(Ab.S2, A.g_mlp, A.b_mlp, dT2, dS2, false, w.tE[2].p, R, D);
-                D2 dT1 = dXin;
-                t.copy(dS2, dT1, R, D);
-                t.ffn_rev(Ab.T1, false, nullptr, nullptr, A.mlp_in, A.mlp_out, Ab.VG, dS2, dT1, true, w.tE[0], w.tE[2], w.tE[3], R, D,
-                          d.DFF);
-                D2 dS1 = w.tE[0];
-                t.norm_rev(Ab.X1, A.g_attn, A.b_attn, dT1, dS1, false, w.tE[2].p, R, D);
-                t.copy(dS1, dOUT, R, D);
-                t.copy(dS1, dXin, R, D);
-            }
-            // ---- output_linear, attention, input_linear
-            t.wgrad(A.out, dOUT, D, Ab.AO, D, R);
-            D2 dAO = w.tE[0];
-            t.linb(dOUT, D, A.out, dAO, D, R);
-            attn_dispatch(d.HD, [&](auto hdm) {
-                constexpr int HDM = decltype(hdm)::value;
-                k_gt_attn_rev_q<HDM><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
-                    Ab.QKV.p, Ab.QKV.t, dAO.p, dAO.t, Ab.LSE, Ab.MS, g.rowptr, g.fc, w.bd, w.dQKV.p, w.dQKV.t, w.CC, w.DD, E, D, d.NH,
-                    d.HD, scale);
-                if (!hv)
-                    k_gt_attn_rev_k<HDM><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
-                        Ab.QKV.p, Ab.QKV.t, dAO.p, dAO.t, Ab.LSE, Ab.MS, w.CC, w.DD, g.rowptr, g.fc, w.bd, w.dQKV.p, w.dQKV.t, E, D,
-                        d.NH, d.HD, scale, nullptr, nullptr);
-                else
-                    k_gt_attn_rev_k<HDM, true><<<dim3((unsigned)N, (unsigned)d.NH), 64, 0, st>>>(
-                        Ab.QKV.p, Ab.QKV.t, dAO.p, dAO.t, Ab.LSE, Ab.MS, w.CC, w.DD, g.rowptr, g.fc, w.bd, w.dQKV.p, w.dQKV.t, E, D,
-                        d.NH, d.HD, scale, hv->sb, hv->sdb);
-            });
-            if (hv && E > 0) {   // heads in head order, attention layers and GNN layers in the order the sweep visits them
-                k_hvp_bias_sum<<<g1(E), 256, 0, st>>>(hv->sb, hv->sdb, d.NH, E, hv->db, hv->dbd, !(gi == L - 1 && a == AL - 1));
-            }
-            if (!post) {
-                t.norm(Ab.X, A.g_attn, A.b_attn, w.tE[0], R, D);                                  // input of input_linear
-                t.wgrad(A.qkv, w.dQKV, 3 * D, w.tE[0], D, R);
-                t.linb(w.dQKV, 3 * D, A.qkv, w.tE[1], D, R);
-                t.norm_rev(Ab.X, A.g_attn, A.b_attn, w.tE[1], dXin, true, w.tE[2].p, R, D);
-            } else {
-                t.wgrad(A.qkv, w.dQKV, 3 * D, Ab.X, D, R);
-                t.linb(w.dQKV, 3 * D, A.qkv, dXin, D, R, true);
-            }
-            t.copy(dXin, dXF, E, D);
-            if (d.expanded) {
-                t.wgrad(A.cc, dXinc, D, Ab.H, DN, N);
-                t.linb(dXinc, D, A.cc, w.dH, DN, N, true);
-            } else
-                t.axpby(1.f, dXinc, D, 0.f, D2(), 0, nullptr, w.dH, DN, true, N, DN);
-        }
-        // ---- compress
-        {
-            const int kin = (gi == 0 ? 2 : 3) * D;
-            t.silu(B.a0, w.tE[0], E * D);
-            t.wgrad(G.compress2, dXF, D, w.tE[0], D, E);
-            t.linb(dXF, D, G.compress2, w.tE[0], D, E);
-            if (E > 0) k_gt_silu_rev<<<g1(E * D), 256, 0, st>>>(B.a0.p, B.a0.t, w.tE[0].p, w.tE[0].t, w.tE[0].p, w.tE[0].t, E * D);
-            t.wgrad(G.c0, w.tE[0], D, B.TOK, kin, E);
-            D2 dTOK = w.tE[1];
-            t.linb(w.tE[0], D, G.c0, dTOK, kin, E);
-            t.wgrad(G.eemb, dTOK, kin, w.geo, 4, E);
-            if (hv) t.linb(dTOK, kin, G.eemb, D2{hv->ngeo, hv->lgeo}, 4, E, gi != L - 1);   // (nu, lambda) of geo, over the layers
-            if (gi > 0) t.embed_grad(g.sp_nbr, dTOK.p + D, kin, E, D, G.nbr_emb);
-            D2 dMsg{dTOK.p + (gi == 0 ? D : 2 * D), dTOK.t + (gi == 0 ? D : 2 * D)};
-            t.axpby(1.f, dMsg, kin, 0.f, D2(), 0, nullptr, dMin, D, true, E, D);
-            t.copy(dMin, w.dM, E, D);
-            (void)MinF;
-        }
-        // node features entering the layer: an embedding per layer (residual) or the previous layer's output
-        if (res || gi == 0) {
-            t.embed_grad(g.sp, w.dH.p, DN, N, DN, m.node_embs[res ? gi : 0]);
-            if (res) t.zero(w.dH, N * DN);
-        }
-    }
-    t.embed_grad(g.sp_nbr, w.dM.p, D, E, D, m.edge_emb);   // the first layer's messages are the neighbour embedding
+    gen_walk_reverse(t, w);
     if (conditioned && !hv) {
         float *gq = t.slot(m.cond_qe), *gm = t.slot(m.cond_se), *gw0 = t.slot(m.cond_w0), *gb0 = t.slot(m.cond_b0),
               *gw2 = t.slot(m.cond_w2), *gb2 = t.slot(m.cond_b2);
         if (!t.err)
             k_gt_cond_bwd<<<1, 256, 6 * DN * sizeof(float), st>>>(g.cond_charge, g.cond_spin, m.cond_qe, m.cond_se, m.cond_w0,
-                                                                  m.cond_b0, m.cond_w2, dcond, (int)g.n_cond_systems,
+                                                                  m.cond_b0, m.cond_w2, t.dcond, (int)g.n_cond_systems,
                                                                   m.h.max_charge, m.h.max_spin_multiplicity, DN, gq, gm, gw0,
                                                                   gb0, gw2, gb2);
     }

@@ -535,7 +535,8 @@ int pet_profile_select(const char* stage);
 int pet_profile_reset(void);
 int pet_profile_report(int max_entries, char (*names)[64], double* total_ms, int64_t* calls,
                        double* flops, double* bytes, int* n_entries);
-/* Runtime switches used by tests / the benchmark (every setting meets the same parity bar):
+/* Runtime switches used by tests / the benchmark (every setting meets the same parity bar). Which kernel serves a stage of the
+ * tuned pass under them is decided in one place, csrc/pet_plan.hip; DESIGN.md section 4.7 has every condition as one table.
  *   "side_stream" 1 = node-feature chain on a second HIP stream (default); that stream is created one priority level below the
  *                 caller's (environment PET_HIP_SIDE_PRIO = same | high overrides; PET_HIP_SIDE = 0 disables the stream)
  *   "trr"         1 = transposed register-resident row kernels on f16x3 split-operand products (default; environment
@@ -544,10 +545,9 @@ int pet_profile_report(int max_entries, char (*names)[64], double* total_ms, int
  *                 (the software-pipelined TRR kernel).
  *   "attn_fused"  bits: 1 = the per-atom fused attention block in the forward (norm -> QKV -> soft-max attention -> output
  *                 projection in one kernel; Q, K, V and the attention output never reach HBM; csrc/pet_ablk.hip), 2 = its
- *                 adjoint (recomputes Q, K, V from the layer input), 4 = whatever the graph's size; default 3: graphs of
- *                 fewer than 3 840 attention tiles (fewer than about 4 700 atoms: latency-bound there) and graphs in which more
- *                 than 5 % of the atoms have more than 32 tokens keep the three-kernel form, as do training forwards,
- *                 graphs with an atom of more than 64 tokens and PostLN models. 0 = the three-kernel form everywhere.
+ *                 adjoint (recomputes Q, K, V from the layer input), 4 = whatever the graph's size; default 3: large graphs only
+ *                 (at least 3 840 attention tiles). 0 = the three-kernel form everywhere. A forward that ran the block saved no
+ *                 Q, K, V: switching its adjoint off in between makes pet_backward fail (PET_ERR_ARGUMENT).
  *   "emlp_s"      the edge MLP and its adjoint -- and, in inference, the edge head and its adjoint (csrc/pet_head_s.hip), the compress
  *                 adjoint (pet_compress_s.hip), the combination stage and its adjoint (pet_comb_s.hip, pet_comb_bwd_s.hip), from
  *                 16 384 atoms on the node-row Linear layers around the attention block (pet_center_s.hip), and in training the

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "../../include/pet_hip.h"
+#include "pet_plan.h"
 
 namespace pet {
 
@@ -38,6 +39,14 @@ void set_error(const std::string& msg);
         }                                                                           \
     } while (0)
 
+#define PET_TRY(expr)                                                               \
+    do {                                                                            \
+        if (int _rc = (expr)) return _rc;                                           \
+    } while (0)
+
+// a launcher called without the packed planes of its kernel: a programming error, the plan (pet_plan.hip) asks before it chooses
+#define PET_REQUIRE_PLANES(cond, what) PET_REQUIRE(cond, PET_ERR_ARGUMENT, what ": the weight planes of this kernel are missing (pet_model_finalize)")
+
 // bump allocator over a caller-provided device buffer (256-byte aligned carves);
 // with base == nullptr it only measures.
 struct Carver {
@@ -68,6 +77,17 @@ inline void allow_big_lds(Kern kern, size_t bytes) {
 // Edge graph in CSR order (edges stably sorted by centre; pet/modules/nef.py:63-70
 // defines exactly this order as the NEF slot order).
 // --------------------------------------------------------------------------------
+// What a graph's last forward into a given workspace left there (pet_fwd.hip note_workspace, soap.hip soap_fwd): whether it ran
+// the size-generic path, its save level, and the plan it followed (pet_plan.h) -- which attention layers ran the fused per-atom
+// block WITHOUT saving Q, K, V and which edge MLPs did not write [v; g]: the adjoint follows that, or refuses.
+struct FwdRecord {
+    const void* ws = nullptr;
+    bool generic = false;
+    int save = -1;              // the forward's save level (0 = nothing kept for an adjoint: pet_backward must refuse)
+    bool soap_packed = false;   // SOAP-BPNN: the feature buffer holds the packed power spectrum (upper triangles only)
+    StagePlan plan;             // tuned path only (a record of another path has no layers)
+};
+
 constexpr int GRID_MAX_PROBES = 64;  // adaptive_cutoff_method = "grid": probe cutoffs 0.5, 0.5 + w/4, .. < cutoff
 
 struct Graph {
@@ -107,18 +127,9 @@ struct Graph {
     int* tsort_tmp = nullptr;  // [ceil(N / 256)][33] per-block counts / first positions of that sort
     int4* tile_desc = nullptr; // [2 N]: the 32-slot tiles first (n_tiles1), then the 64-slot ones (n_tiles2)
     int n_tiles1 = 0, n_tiles2 = 0;  // host copies
-    // What this graph's last forward into a given workspace left there (pet_fwd.hip note_workspace, soap.hip soap_fwd): whether
-    // it ran the size-generic path, and whether its attention layers ran the fused per-atom block WITHOUT saving Q, K, V (the
-    // adjoint must then be the fused one). One record per workspace (the last four), so that forwards of the same graph into
-    // different workspaces do not overwrite each other's record.
-    struct FwdRecord {
-        const void* ws = nullptr;
-        bool generic = false;
-        bool attn_unsaved = false;  // some attention layer ran the fused block: its QKV / AO buffers were not written
-        bool emlp_unsaved = false;  // the edge MLPs did not write [v; g]: the adjoint recomputes them (pet_emlp_s.hip)
-        int save = -1;              // the forward's save level (0 = nothing kept for an adjoint: pet_backward must refuse)
-        bool soap_packed = false;   // SOAP-BPNN: the feature buffer holds the packed power spectrum (upper triangles only)
-    };
+    // one FwdRecord per workspace (the last four), so that forwards of the same graph into different workspaces do not
+    // overwrite each other's record
+    using FwdRecord = pet::FwdRecord;
     mutable FwdRecord fwd_rec[4];
     mutable int fwd_rec_next = 0;
     FwdRecord* fwd_record(const void* ws) const {

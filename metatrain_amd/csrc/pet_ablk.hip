@@ -580,23 +580,10 @@ static void tail_join(hipStream_t st, hipStream_t ts) {
     (void)hipStreamWaitEvent(st, t.join_ev, 0);
 }
 
-// whether the adjoint of this graph's attention layers runs fused (the forward of the same call sequence did, then)
-static bool ablk_serves(const Graph& g) {
-    if (g.bucket_start[5] > g.bucket_start[4]) return false;  // an atom of more than 64 tokens
-    if (!g.tiles_planned) return false;                       // a small graph built before the block was forced
-    if (switches().attn_fused & 4) return true;
-    // A tile is one wave's serial chain (40 us forward, 100 us adjoint): below a few waves per SIMD the launch costs that
-    // latency whatever its size, and the three row-parallel kernels are quicker (one box, three-kernel / fused ms per step:
-    // 1 000 atoms 1.69 / 2.18, 3 000: 2.96 / 3.29, 5 000: 4.16 / 4.08, 10 000: 7.30 / 6.72; model.h ABLK_MIN_TILES). Many
-    // 64-slot tiles (the adjoint's instantiation for them spills): likewise.
-    return g.n_tiles1 >= ABLK_MIN_TILES && (int64_t)g.n_tiles2 * 20 <= g.n_nodes;
-}
-bool ablk_bwd_on(const Graph& g) { return (switches().attn_fused & 2) && ablk_serves(g); }
-
-// atoms of at most 64 tokens (attention tile counts 1 .. 4 of the graph's bucket lists); false = not served
-bool ablk_fwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* X, float* X1, float* OC, float scale,
-              hipStream_t st) {
-    if (!(switches().attn_fused & 1) || !A.qkv.fwd2s || !A.out.fwd2s || !ablk_serves(g)) return false;
+// atoms of at most 64 tokens (attention tile counts 1 .. 4 of the graph's bucket lists)
+int ablk_fwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* X, float* X1, float* OC, float scale,
+             hipStream_t st) {
+    PET_REQUIRE_PLANES(A.qkv.fwd2s && A.out.fwd2s && g.tiles_planned, "fused attention block");
     const bool ln = m.layer_norm();
     const float qscale = scale * AB_LOG2E;
     const W2 wq = w2s_fwd(A.qkv), wo = w2s_fwd(A.out);
@@ -631,13 +618,14 @@ bool ablk_fwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* 
     }
     tail_join(st1, ts);
 #undef PET_ABLK_FWD
-    return true;
+    return PET_OK;
 }
 
 // dXin [E + N, D] = adjoint of the layer input; dbias [E] = key-bias gradient of this layer summed over the heads
-bool ablk_bwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* X, const float* dX1, const float* dOC,
-              float* dXin, float* dbias, float scale, hipStream_t st) {
-    if (!ablk_bwd_on(g) || !A.qkv_g.fwd2s || !A.qkv_g.bwd2s || !A.out.bwd2s) return false;
+int ablk_bwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* X, const float* dX1, const float* dOC,
+             float* dXin, float* dbias, float scale, hipStream_t st) {
+    PET_REQUIRE(A.qkv_g.fwd2s && A.qkv_g.bwd2s && A.out.bwd2s && g.tiles_planned, PET_ERR_ARGUMENT,
+                "the fused attention adjoint refused a layer (weights not packed for it)");
     const bool ln = m.layer_norm();
     const float qscale = scale * AB_LOG2E;
     const W2 wq = w2s_fwd(A.qkv_g), wqt = w2s_bwd(A.qkv_g), wot = w2s_bwd(A.out);  // (norm_attention folded into W_qkv)
@@ -664,7 +652,7 @@ bool ablk_bwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* 
                          dXin, dbias, st);
     tail_join(st1, ts);
 #undef PET_ABLK_BWD
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

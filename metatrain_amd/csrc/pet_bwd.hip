@@ -1134,18 +1134,27 @@ int backward_predict(const Model& m, const Graph& g, Workspace& w, const float* 
     allow_big_lds(k_head_bwd<128, true, false>, lds2 + 768);
     allow_big_lds(k_head_bwd<128, true, true>, lds2 + 768);
     const GnnBufs& last = w.gnn.back();
+    StagePlan plan;  // (no record: what this stage reads, the heads' inputs, every forward leaves behind)
+    PET_TRY(plan_backward(m, g, nullptr, tr != nullptr, plan));
     if (E > 0) {
         ProfScope ps("head_edge_bwd", st, fE * 2.0 * (D * DH + DH * DH + DH));
-        if (!(use_trr() && trr_head_edge_bwd(m, last.Mout, gA, g.ctr, g.fc, w.ypred_e, w.dfc, w.dM, E, tr ? w.hs1 : nullptr,
-                                              tr ? w.hda2 : nullptr, tr ? w.hda1 : nullptr, tr ? w.hs2y : nullptr, st)))
-        PET_LAUNCH_TR(tr, k_head_bwd, PET_TA(128, true), gE, lds2 + 768, st, last.Mout, wx_f(m.eh0), m.eh0.b, wx_f(m.eh2),
-            m.eh2.b, wx_b(m.eh0), wx_b(m.eh2), m.ell_w, gA, g.ctr, g.fc, w.ypred_e, w.dfc, w.dM, E, tr ? w.hs1 : nullptr,
-            tr ? w.hda2 : nullptr, tr ? w.hda1 : nullptr, tr ? w.hs2y : nullptr);
+        switch (plan.head_edge) {
+        case Rows::Ring: PET_TRY(head_edge_bwd_s(m, last.Mout, gA, g.ctr, g.fc, w.ypred_e, w.dfc, w.dM, E, st)); break;
+        case Rows::Pipelined:
+            PET_TRY(trr_head_edge_bwd(m, last.Mout, gA, g.ctr, g.fc, w.ypred_e, w.dfc, w.dM, E, tr ? w.hs1 : nullptr,
+                                      tr ? w.hda2 : nullptr, tr ? w.hda1 : nullptr, tr ? w.hs2y : nullptr, st));
+            break;
+        case Rows::LdsTile:
+            PET_LAUNCH_TR(tr, k_head_bwd, PET_TA(128, true), gE, lds2 + 768, st, last.Mout, wx_f(m.eh0), m.eh0.b, wx_f(m.eh2),
+                m.eh2.b, wx_b(m.eh0), wx_b(m.eh2), m.ell_w, gA, g.ctr, g.fc, w.ypred_e, w.dfc, w.dM, E, tr ? w.hs1 : nullptr,
+                tr ? w.hda2 : nullptr, tr ? w.hda1 : nullptr, tr ? w.hs2y : nullptr);
+            break;
+        }
         if (tr) tr->heads(true, last.Mout, D, E, gA);
     }
     {
         SideStream ss = side_stream();
-        if (tr) ss.enabled = false;  // the weight-gradient scratch is shared: one stream
+        ss.enabled = plan.side_heads;
         const hipStream_t s2 = ss.stream(st);
         ss.fork(st);
         {
@@ -1182,23 +1191,12 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
     const int gE = cdiv(E, BM), gN = cdiv(N, BM), gR = cdiv(R, BM);
     const size_t lds1 = BM * LD128 * 4, lds2 = 2 * BM * LD128 * 4;
     const double fE = (double)E, fN = (double)N, fR = (double)R;
-    const bool trr = use_trr();
-    const bool trr_l = trr && m.plain_layers();  // the TRR transformer-layer kernels are PreLN (RMSNorm or LayerNorm)
-    const bool fused_attn = trr_l && !tr && ablk_bwd_on(g) && m.gnn[0].attn[0].qkv.bwd2s;
-    // the forward that filled this workspace decided by itself whether Q, K, V were written: if it ran the fused block, the
-    // three-kernel adjoint would read buffers nobody wrote (a switch flipped between the two calls) -- refuse
-    const Graph::FwdRecord* fwd_rec = w.base ? g.fwd_record(w.base) : nullptr;
-    const bool fwd_unsaved = fwd_rec && fwd_rec->attn_unsaved;
-    // a forward that kept nothing (save_for_backward = 0) wrote neither [v; g] nor the compress pre-activations: no adjoint
-    // can follow it, whatever the switches say
-    PET_REQUIRE(!fwd_rec || fwd_rec->save != 0, PET_ERR_ARGUMENT,
-                "the last forward into this workspace ran with save_for_backward = 0: nothing was kept for an adjoint");
-    PET_REQUIRE(!fwd_unsaved || fused_attn, PET_ERR_ARGUMENT,
-                "the forward of this workspace ran the fused attention block (Q, K, V not saved) but the adjoint is "
-                "configured for the three-kernel form: pet_config_set changed between forward and backward");
-    // k_dxf folded into its producer and its consumer (pet_config_set("dxf_fused", 0): the separate kernel)
+    // which kernel serves every stage below: decided here, once, from what the forward of this workspace left behind; an adjoint
+    // that the switches no longer allow to follow that forward is refused before anything is launched (pet_plan.hip)
+    StagePlan plan;
+    PET_TRY(plan_backward(m, g, w.base ? g.fwd_record(w.base) : nullptr, tr != nullptr, plan));
     bool node_cnt_zeroed = false;  // k_node_bwd2 SPLIT: arrival counters zeroed once per adjoint, then they reset themselves
-    const bool dxf_fused = trr_l && !tr && !res && !g.x_fn && m.h.num_attention_layers >= 1 && switches().dxf_fused;
+    const bool dxf_fused = plan.dxf_fused;
     PET_HIP_CHECK(hipMemsetAsync(w.dgeo, 0, E * 4 * sizeof(float), st));
     allow_big_lds(k_swiglu_bwd<256, DNF, false, true>, (BM * LD256 + BM * LD128) * 4);
     allow_big_lds(k_swiglu_bwd<256, DNF, true, true>, (BM * LD256 + BM * LD128) * 4);
@@ -1213,12 +1211,13 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
     // node-feature adjoint chain on the side stream: it only meets the edge chain at output_linear^T
     // (needs dOC) and at the centre rows of the token gradient (k_center_bwd)
     SideStream ss = side_stream();
-    if (tr || post || res) ss.enabled = false;
+    ss.enabled = plan.side;
     const hipStream_t s2 = ss.stream(st);
     ss.fork(st);  // the seeds in w.dH / w.dM were produced on the main stream
     for (int gi = m.h.num_gnn_layers - 1; gi >= 0; gi--) {
         const GnnLayerW& G = m.gnn[gi];
         const GnnBufs& B = w.gnn[gi];
+        const GnnPlan& P = plan.gnn[gi];
         // dH is the adjoint of the node features LEAVING this layer, where the system embedding was added (training:
         // the side stream is off, so dH is complete on this stream)
         if (tr) tr->cond_accumulate(dH, gi == m.h.num_gnn_layers - 1);
@@ -1234,10 +1233,10 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
         } else {
             {
                 ProfScope ps("comb_bwd", st, fE * 2.0 * (2 * D * 2 * D + 2 * D * D), fE * 4.0 * (3 * D + 2 * D + 2 * D));  // dM, e, e[rev], CA in; dcat out
-                if (!tr && comb_bwd_s(dM, B.XF, g.rev, B.LNS, B.CA, G.comb0_g, G.comb2, w.dcat, E, dxf_fused, st)) {  // large graphs (pet_comb_bwd_s.hip)
-                } else
-                PET_REQUIRE(trr_comb_bwd(dM, B.XF, g, G, B.LNS, B.CA, w.dcat, E, tr ? w.dCA : nullptr, st, dxf_fused), PET_ERR_ARGUMENT,
-                            "combination adjoint: the split weight planes are missing (pet_model_finalize)");
+                if (P.comb == Rows::Ring)
+                    PET_TRY(comb_bwd_s(dM, B.XF, g.rev, B.LNS, B.CA, G.comb0_g, G.comb2, w.dcat, E, dxf_fused, st));
+                else
+                    PET_TRY(trr_comb_bwd(dM, B.XF, g, G, B.LNS, B.CA, w.dcat, E, tr ? w.dCA : nullptr, st, dxf_fused));
                 if (tr) {
                     const std::string gs = std::to_string(gi);
                     tr->linear("combination_mlps." + gs + ".2", D, 2 * D, {dM, nullptr, 0, D},
@@ -1260,48 +1259,48 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
         for (int a = m.h.num_attention_layers - 1; a >= 0; a--) {
             const AttnLayerW& A = G.attn[a];
             const AttnBufs& Ab = B.attn[a];
+            const LayerPlan& Q = P.layers[a];
+            const bool trr_l = Q.attn != Attn::LdsTile;  // (the pipelined QKV / projection adjoints and edge-MLP adjoint go together)
             const std::string lp = "gnn_layers." + std::to_string(gi) + ".trans.layers." + std::to_string(a);
             // dX (edge rows) = grad wrt the edge MLP output; dH = grad wrt Hn
             {
                 ProfScope ps("node_bwd", s2, fN * 2.0 * (D * DN + DN * 2 * DNF + DNF * DN));
                 const WX wob = wx_b(A.cmlp_out), wib = wx_b(A.cmlp_in);
-                bool expand_done = false;
-                // large graphs: two shared-ring GEMMs and two row-wise kernels that can run BESIDE the edge kernels (pet_node_s.hip);
-                // scratch: the attention-output temporary of the forward pass, which no adjoint kernel touches
-                if (!tr && switches().node_planes && (size_t)N * 3 * DNF <= (size_t)R * D &&
-                    node_bwd_s(A, dH, Ab.H1, Ab.VGn, dH_alt, w.AO, N, ln, s2)) {
-                } else
-                if (!tr && switches().node_planes && wob.h && wib.h) {
-                    const int nr = node_rows(N);
-                    const size_t lds_nb = (size_t)nr * LD256 * 4 + (size_t)2 * nr * plane_ld(256) * 2 + nr * 8;
-                    // small graphs: four workgroups per row tile (k_node_bwd2, SPLIT); partials and arrival counters in the
-                    // attention-output temporary of the forward pass, which no adjoint kernel touches
+                const int nr = Q.node == Node::Rows64 ? 64 : 32;
+                const size_t lds_nb = (size_t)nr * LD256 * 4 + (size_t)2 * nr * plane_ld(256) * 2 + nr * 8;
+                switch (Q.node) {
+                case Node::Ring:  // two ring GEMMs BESIDE the edge kernels (pet_node_s.hip); scratch: the attention-output temporary of
+                                  // the forward pass, which no adjoint kernel touches
+                    PET_TRY(node_bwd_s(A, dH, Ab.H1, Ab.VGn, dH_alt, w.AO, N, ln, s2));
+                    break;
+                case Node::Split: {  // four workgroups per row tile; partials and arrival counters in the same temporary
                     const int nt32 = cdiv(N, 32);
                     const size_t p_floats = (size_t)(DNF / 128) * nt32 * 32 * DN;
-                    const bool split = nr == 32 && switches().node_split && nt32 <= 128 && p_floats + nt32 <= (size_t)R * D;
-                    if (split) {
-                        int* cnt = reinterpret_cast<int*>(w.AO + p_floats);
-                        if (!node_cnt_zeroed) PET_HIP_CHECK(hipMemsetAsync(cnt, 0, nt32 * sizeof(int), s2));
-                        node_cnt_zeroed = true;
-                        allow_big_lds(k_node_bwd2<1, true>, lds_nb);
-                        k_node_bwd2<1, true><<<dim3(nt32, DNF / 128), NTHREADS, lds_nb, s2>>>(
-                            dH, Ab.H1, Ab.VGn, A.g_center, wob, wib, dH_alt, N, ln, A.ce.bwd, w.dOC, w.AO, cnt);
-                        expand_done = true;
-                    } else if (nr == 32) {  // the expansion adjoint in the same launch
-                        allow_big_lds(k_node_bwd2<1>, lds_nb);
-                        k_node_bwd2<1><<<cdiv(N, 32), NTHREADS, lds_nb, s2>>>(dH, Ab.H1, Ab.VGn, A.g_center, wob, wib, dH_alt, N, ln,
-                                                                             A.ce.bwd, w.dOC, nullptr, nullptr);
-                        expand_done = true;
-                    } else {
-                        allow_big_lds(k_node_bwd2<2>, lds_nb);
-                        k_node_bwd2<2><<<gN, NTHREADS, lds_nb, s2>>>(dH, Ab.H1, Ab.VGn, A.g_center, wob, wib, dH_alt, N, ln,
-                                                                     nullptr, nullptr, nullptr, nullptr);
-                    }
-                } else
-                PET_LAUNCH_TR(tr, k_swiglu_bwd, PET_TA(256, DNF), gN, (BM * LD256 + BM * LD128) * 4, s2,  dH, Ab.H1,
-                    Ab.VGn, A.g_center, A.cmlp_out.bwd, A.cmlp_in.bwd, dH_alt, N, tr ? w.dVGn : nullptr, ln);
-                if (!expand_done && !(!tr && expand_bwd_s(A.ce, dH_alt, w.dOC, N, s2)))
-                    k_expand_bwd<<<gN, NTHREADS, BM * LD256 * 4, s2>>>(dH_alt, A.ce.bwd, w.dOC, N);
+                    int* cnt = reinterpret_cast<int*>(w.AO + p_floats);
+                    if (!node_cnt_zeroed) PET_HIP_CHECK(hipMemsetAsync(cnt, 0, nt32 * sizeof(int), s2));
+                    node_cnt_zeroed = true;
+                    allow_big_lds(k_node_bwd2<1, true>, lds_nb);
+                    k_node_bwd2<1, true><<<dim3(nt32, DNF / 128), NTHREADS, lds_nb, s2>>>(
+                        dH, Ab.H1, Ab.VGn, A.g_center, wob, wib, dH_alt, N, ln, A.ce.bwd, w.dOC, w.AO, cnt);
+                    break;
+                }
+                case Node::Rows32:  // the expansion adjoint in the same launch
+                    allow_big_lds(k_node_bwd2<1>, lds_nb);
+                    k_node_bwd2<1><<<cdiv(N, 32), NTHREADS, lds_nb, s2>>>(dH, Ab.H1, Ab.VGn, A.g_center, wob, wib, dH_alt, N, ln,
+                                                                         A.ce.bwd, w.dOC, nullptr, nullptr);
+                    break;
+                case Node::Rows64:
+                    allow_big_lds(k_node_bwd2<2>, lds_nb);
+                    k_node_bwd2<2><<<gN, NTHREADS, lds_nb, s2>>>(dH, Ab.H1, Ab.VGn, A.g_center, wob, wib, dH_alt, N, ln,
+                                                                 nullptr, nullptr, nullptr, nullptr);
+                    break;
+                case Node::LdsTile:
+                    PET_LAUNCH_TR(tr, k_swiglu_bwd, PET_TA(256, DNF), gN, (BM * LD256 + BM * LD128) * 4, s2,  dH, Ab.H1,
+                        Ab.VGn, A.g_center, A.cmlp_out.bwd, A.cmlp_in.bwd, dH_alt, N, tr ? w.dVGn : nullptr, ln);
+                    break;
+                }
+                if (Q.expand == Center::Ring) PET_TRY(expand_bwd_s(A.ce, dH_alt, w.dOC, N, s2));
+                else if (Q.expand == Center::LdsTile) k_expand_bwd<<<gN, NTHREADS, BM * LD256 * 4, s2>>>(dH_alt, A.ce.bwd, w.dOC, N);
                 if (tr) {
                     tr->linear(lp + ".center_mlp.w_out", DN, DNF, {dH, nullptr, 0, DN},
                                {Ab.VGn, 2 * DNF, DNF, nullptr, nullptr}, 2, N);
@@ -1322,27 +1321,28 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
                                                                                  A.mlp_in.bwd, dX, R, nullptr, false);
                 k_rownorm_bwd<<<gR, NTHREADS, lds1, st>>>(dX, dX + E * D, Ab.X1, A.g_attn, ln, dX_alt, E, R);
             } else {
-                const bool recompute = fwd_rec ? fwd_rec->emlp_unsaved : (!tr && trr_l && emlp_recompute_on(A.mlp_in, A.mlp_out, E));
-                ProfScope ps("emlp_bwd", st, fE * 2.0 * (D * 2 * DFF + DFF * D), fE * 4.0 * (3 * D + (recompute ? 0 : 2 * DFF)));  // dY, X1 (and the saved VG) in; dX1 out
-                // the forward of this workspace did not save [v; g] (its record says so; without a record -- a graph handle
-                // made anew for the adjoint call -- the forward followed the same switches as this call does)
-                if (recompute) {
-                    const bool gat = dxf_fused && a == m.h.num_attention_layers - 1;
-                    PET_REQUIRE(!tr && trr_l && emlp_bwd_s(gat ? w.dcat : dX, Ab.X1, ln, A.mlp_in_g, A.mlp_out, dX_alt, E, st,
-                                                          gat ? 2 * D : D, gat ? w.dcat + D : nullptr, gat ? g.rev : nullptr),
-                                PET_ERR_ARGUMENT, "the forward of this workspace did not save the edge MLP's pre-activations "
-                                "and the recomputing adjoint is switched off: pet_config_set changed between forward and backward");
-                } else if (dxf_fused && a == m.h.num_attention_layers - 1) {
-                    // dXF[p] = (dM[p] + dcat[p][:D]) + dcat[rev[p]][D:]: the bracket left k_comb_bwd_p2 in dcat's first
-                    // half, the gather is made while this kernel reads its tile
-                    trr_emlp_bwd(w.dcat, Ab.X1, Ab.VG, A.g_mlp, ln ? A.b_mlp : nullptr, A.mlp_in, A.mlp_out, dX_alt, E, st,
-                                 nullptr, 2 * D, w.dcat + D, g.rev);
-                } else if (trr_l) {
-                    trr_emlp_bwd(dX, Ab.X1, Ab.VG, A.g_mlp, ln ? A.b_mlp : nullptr, A.mlp_in, A.mlp_out, dX_alt, E, st,
-                                 tr ? w.dVG : nullptr);
+                ProfScope ps("emlp_bwd", st, fE * 2.0 * (D * 2 * DFF + DFF * D), fE * 4.0 * (3 * D + (Q.emlp_saved ? 2 * DFF : 0)));  // dY, X1 (and the saved VG) in; dX1 out
+                // dxf_fused, last attention layer: dXF[p] = (dM[p] + dcat[p][:D]) + dcat[rev[p]][D:] -- the bracket left the
+                // combination adjoint in dcat's first half, the gather is made while the kernel reads its tile
+                const bool gat = dxf_fused && a == m.h.num_attention_layers - 1;
+                switch (Q.emlp) {
+                case Rows::Ring:  // the forward of this workspace did not save [v; g]: recomputed
+                    PET_TRY(emlp_bwd_s(gat ? w.dcat : dX, Ab.X1, ln, A.mlp_in_g, A.mlp_out, dX_alt, E, st, gat ? 2 * D : D,
+                                       gat ? w.dcat + D : nullptr, gat ? g.rev : nullptr));
+                    break;
+                case Rows::Pipelined:
+                    if (gat)
+                        trr_emlp_bwd(w.dcat, Ab.X1, Ab.VG, A.g_mlp, ln ? A.b_mlp : nullptr, A.mlp_in, A.mlp_out, dX_alt, E, st,
+                                     nullptr, 2 * D, w.dcat + D, g.rev);
+                    else
+                        trr_emlp_bwd(dX, Ab.X1, Ab.VG, A.g_mlp, ln ? A.b_mlp : nullptr, A.mlp_in, A.mlp_out, dX_alt, E, st,
+                                     tr ? w.dVG : nullptr);
+                    break;
+                case Rows::LdsTile:
+                    PET_LAUNCH_TR(tr, k_swiglu_bwd, PET_TA(128, DFF), gE, lds2, st, dX, Ab.X1, Ab.VG, A.g_mlp,
+                        A.mlp_out.bwd, A.mlp_in.bwd, dX_alt, E, tr ? w.dVG : nullptr, ln);
+                    break;
                 }
-                else PET_LAUNCH_TR(tr, k_swiglu_bwd, PET_TA(128, DFF), gE, lds2, st, dX, Ab.X1, Ab.VG, A.g_mlp,
-                    A.mlp_out.bwd, A.mlp_in.bwd, dX_alt, E, tr ? w.dVG : nullptr, ln);
                 if (tr) {
                     tr->linear(lp + ".mlp.w_out", D, DFF, {dX, nullptr, 0, D}, {Ab.VG, 2 * DFF, DFF, nullptr, nullptr},
                                2, E);
@@ -1355,15 +1355,12 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
             // dX_alt (edge rows) = dX1, dH_alt = dH1; PostLN: dX_alt holds all E+N rows of d(tokens + attention output)
             const float* dOCr = post ? dX_alt + E * D : w.dOC;
             // the per-atom fused adjoint (pet_ablk.hip): Q, K, V recomputed from X, only dX and the key-bias gradient leave
-            bool fusedb = false;
-            if (fused_attn) {
+            if (Q.attn == Attn::Fused) {
                 ProfScope ps("attn_blk_bwd", st, fR * 2.0 * D * 4 * D + 2.0 * 4.0 * D * g_sum_t2(g), fR * 4.0 * 3 * D);  // algorithmic: the adjoint's own products (the Q, K, V recomputation is this design's choice, not counted); X, dX1 in; dX out
-                fusedb = ablk_bwd(m, g, A, Ab.X, dX_alt, w.dOC, dX,
-                                  w.dbias_l + ((int64_t)gi * m.h.num_attention_layers + a) * NHEAD * E, scale, st);
-                // (the key-bias reduction below assumes every layer took the same form)
-                PET_REQUIRE(fusedb, PET_ERR_ARGUMENT, "the fused attention adjoint refused a layer (weights not packed for it)");
-            }
-            if (!fusedb) {
+                // (the key-bias reduction below assumes every layer took the same form: the plan gives all of them one)
+                PET_TRY(ablk_bwd(m, g, A, Ab.X, dX_alt, w.dOC, dX,
+                                 w.dbias_l + ((int64_t)gi * m.h.num_attention_layers + a) * NHEAD * E, scale, st));
+            } else {
             {
                 ProfScope ps("oproj_bwd", st, fR * 2.0 * D * D, fR * 4.0 * 2 * D);  // dX1 (| dOC) in; dAO out
                 if (trr_l) trr_oproj_bwd(dX_alt, w.dOC, A.out, w.dAO, E, R, st);
@@ -1375,7 +1372,7 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
             {
                 ProfScope ps("attn_bwd", st, 2.0 * 4.0 * D * g_sum_t2(g), fR * 4.0 * (3 * D + D + 3 * D));
                 float* dbias_h = w.dbias_l + ((int64_t)gi * m.h.num_attention_layers + a) * NHEAD * E;
-                if (!(trr && attn_bwd_preload(nt, Ab.QKV, w.dAO, g, w.dQKV, dbias_h, scale, st))) switch (nt) {
+                if (!(plan.attn_preload && attn_bwd_preload(nt, Ab.QKV, w.dAO, g, w.dQKV, dbias_h, scale, st))) switch (nt) {
                     case 1: launch_attn_bwd<1>(Ab.QKV, w.dAO, g, w.dQKV, dbias_h, scale, st); break;
                     case 2: launch_attn_bwd<2>(Ab.QKV, w.dAO, g, w.dQKV, dbias_h, scale, st); break;
                     case 3: launch_attn_bwd<3>(Ab.QKV, w.dAO, g, w.dQKV, dbias_h, scale, st); break;
@@ -1398,8 +1395,8 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
             ss.fork(st);  // centre rows of dX ready
             {
                 ProfScope ps("center_bwd", s2, fN * 2.0 * DN * D);
-                if (!tr && center_bwd_s(A.cc, dX + E * D, dH_alt, dH, N, s2)) {
-                } else if (N <= 4096) k_center_bwd<true><<<gN, NTHREADS, lds1, s2>>>(dX + E * D, dH_alt, A.cc.bwd, dH, N);
+                if (Q.center == Center::Ring) PET_TRY(center_bwd_s(A.cc, dX + E * D, dH_alt, dH, N, s2));
+                else if (plan.center_bwd_deep) k_center_bwd<true><<<gN, NTHREADS, lds1, s2>>>(dX + E * D, dH_alt, A.cc.bwd, dH, N);
                 else k_center_bwd<false><<<gN, NTHREADS, lds1, s2>>>(dX + E * D, dH_alt, A.cc.bwd, dH, N);
                 if (tr)
                     tr->linear(lp + ".center_contraction", D, DN, {dX + E * D, nullptr, 0, D},
@@ -1409,9 +1406,10 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
         }
         {
             ProfScope ps("compress_bwd", st, fE * 2.0 * (D * D * (gi == 0 ? 3 : 4) + 4 * D));
-            if (trr && trr_compress_bwd(gi == 0, dX, B.a0, G, w.dgeo, dM, E, tr ? w.da0 : nullptr, st)) {
-                // TRR kernel on f16x3 (pet_trr.hip)
-            } else if (gi == 0)
+            if (P.compress == Rows::Ring) PET_TRY(compress_bwd_s(gi == 0, dX, B.a0, G, w.dgeo, dM, E, st));
+            else if (P.compress == Rows::Pipelined)
+                PET_TRY(trr_compress_bwd(gi == 0, dX, B.a0, G, w.dgeo, dM, E, tr ? w.da0 : nullptr, st));
+            else if (gi == 0)
                 PET_LAUNCH_TR(tr, k_compress_bwd, PET_TA(true), gE, lds1, st, dX, B.a0, G.compress2.bwd, G.wct,
                     nullptr, w.dgeo, nullptr, E, tr ? w.da0 : nullptr);
             else
@@ -1433,7 +1431,7 @@ int backward_features(const Model& m, const Graph& g, Workspace& w, hipStream_t 
     }
     // fused adjoint: one slice per attention layer (the head sum), at the place of the layer's first head slice
     k_dfc_attn<<<cdiv(E, 256), 256, 0, st>>>(g.fc, w.dbias_l, m.h.num_gnn_layers * m.h.num_attention_layers, w.dbias, E,
-                                             fused_attn ? NHEAD : 1);
+                                             plan.dbias_stride);
     PET_HIP_CHECK(hipGetLastError());
     return PET_OK;
 }

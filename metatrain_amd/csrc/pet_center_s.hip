@@ -120,8 +120,6 @@ static inline W2 ns_w2(const void* base, int tiles, int kbs) {
     W2 w; w.h = b; w.l = b + (size_t)tiles * kbs * 64;
     return w;
 }
-// the node chain takes this form from 16 384 atoms on (below: the 32-row node kernels fuse these layers, pet_fwd.hip node_rows)
-static bool center_s_serves(int64_t N) { return emlp_s_serves((int64_t)1 << 40) && (N >= 16384 || emlp_s_forced()); }
 
 template <int KIN, int NOUT, bool ADD>
 static void rowlin_s_launch(const float* X, W2 w, const float* bias, const float* addend, float* Y, int64_t N, hipStream_t st) {
@@ -129,21 +127,20 @@ static void rowlin_s_launch(const float* X, W2 w, const float* bias, const float
     allow_big_lds(k_rowlin_s<KIN, NOUT, ADD>, lds);
     k_rowlin_s<KIN, NOUT, ADD><<<(int)cdiv(N, HS_NW * WROWS), 256, lds, st>>>(X, w, bias, addend, Y, N);
 }
-// false = not served (weights not packed for it, small graph, or pet_config_set("emlp_s", 0))
-bool center_s(const Lin& cc, const float* H, float* Xc, int64_t N, hipStream_t st) {  // X[E + i] = H[i] Wcc^T + b
-    if (!center_s_serves(N) || !cc.fwd2s) return false;
+int center_s(const Lin& cc, const float* H, float* Xc, int64_t N, hipStream_t st) {  // X[E + i] = H[i] Wcc^T + b
+    PET_REQUIRE_PLANES(cc.fwd2s, "centre contraction");
     rowlin_s_launch<DN, D, false>(H, ns_w2(cc.fwd2s, D / 32, DN / 16), cc.b, nullptr, Xc, N, st);
-    return true;
+    return PET_OK;
 }
-bool expand_bwd_s(const Lin& ce, const float* dH1, float* dOC, int64_t N, hipStream_t st) {  // dOC = dH1 Wce
-    if (!center_s_serves(N) || !ce.bwd2s) return false;
+int expand_bwd_s(const Lin& ce, const float* dH1, float* dOC, int64_t N, hipStream_t st) {  // dOC = dH1 Wce
+    PET_REQUIRE_PLANES(ce.bwd2s, "centre expansion adjoint");
     rowlin_s_launch<DN, D, false>(dH1, ns_w2(ce.bwd2s, D / 32, DN / 16), nullptr, nullptr, dOC, N, st);
-    return true;
+    return PET_OK;
 }
-bool center_bwd_s(const Lin& cc, const float* dC, const float* dH1, float* dHin, int64_t N, hipStream_t st) {  // dHin = dH1 + dC Wcc
-    if (!center_s_serves(N) || !cc.bwd2s) return false;
+int center_bwd_s(const Lin& cc, const float* dC, const float* dH1, float* dHin, int64_t N, hipStream_t st) {  // dHin = dH1 + dC Wcc
+    PET_REQUIRE_PLANES(cc.bwd2s, "centre contraction adjoint");
     rowlin_s_launch<D, DN, true>(dC, ns_w2(cc.bwd2s, DN / 32, D / 16), nullptr, dH1, dHin, N, st);
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

@@ -261,10 +261,10 @@ static inline W2 w2_of(const void* base, int n_tiles_dim, int k_dim) {
     return w;
 }
 
-bool trr_comb(bool first, const float* XF, const Graph& g, const GnnLayerW& G, const float* Min,
-              const float* edge_emb, float* CA, float* LNS, float* Mout, int64_t E, hipStream_t st) {
-    if (!G.comb0.fwd2 || !G.comb2.fwd2 || E <= 0) return false;
-    if (comb_s(first, XF, g.rev, G.comb0_g, G.comb2, Min, edge_emb, g.sp_nbr, CA, LNS, Mout, E, st)) return true;  // large graphs (pet_comb_s.hip)
+int trr_comb(bool first, const float* XF, const Graph& g, const GnnLayerW& G, const float* Min,
+             const float* edge_emb, float* CA, float* LNS, float* Mout, int64_t E, hipStream_t st) {
+    PET_REQUIRE(G.comb0.fwd2 && G.comb2.fwd2 && E > 0, PET_ERR_ARGUMENT,
+                "combination stage: the split weight planes are missing (pet_model_finalize)");
     const W2 w0 = w2_of(G.comb0.fwd2, G.comb0.n_out, G.comb0.k_in), w2 = w2_of(G.comb2.fwd2, G.comb2.n_out, G.comb2.k_in);
     const int grid = cdiv(E, WG_ROWS);
     const size_t lds = (size_t)4 * 32768;  // per wave: e tile (then operands / staging / bias), e[rev] tile (then its planes)
@@ -277,7 +277,7 @@ bool trr_comb(bool first, const float* XF, const Graph& g, const GnnLayerW& G, c
         k_comb_p2<false><<<grid, 256, lds, st>>>(XF, g.rev, G.ln_g, G.ln_b, w0, G.comb0.b, w2, G.comb2.b, Min, edge_emb,
                                                  g.sp_nbr, CA, LNS, Mout, E);
     }
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

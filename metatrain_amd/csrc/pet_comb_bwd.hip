@@ -270,15 +270,15 @@ static inline W2 w2_of(const void* base, int n_tiles_dim, int k_dim) {
     return w;
 }
 
-bool trr_comb_bwd(const float* dM, const float* XF, const Graph& g, const GnnLayerW& G, const float* LNS,
-                  const float* CA, float* dcat, int64_t E, float* t_da, hipStream_t st, bool add_dm) {
-    if (!G.comb0.bwd2 || !G.comb2.bwd2 || E <= 0) return false;
+int trr_comb_bwd(const float* dM, const float* XF, const Graph& g, const GnnLayerW& G, const float* LNS,
+                 const float* CA, float* dcat, int64_t E, float* t_da, hipStream_t st, bool add_dm) {
+    PET_REQUIRE(G.comb0.bwd2 && G.comb2.bwd2 && E > 0 && !(t_da && add_dm), PET_ERR_ARGUMENT,
+                "combination adjoint: the split weight planes are missing (pet_model_finalize)");
     // bwd2 operands: tiles over k_in, K = n_out
     const W2 w2b = w2_of(G.comb2.bwd2, G.comb2.k_in, G.comb2.n_out), w0b = w2_of(G.comb0.bwd2, G.comb0.k_in, G.comb0.n_out);
     const int grid = cdiv(E, WG_ROWS);
     const size_t lds = (size_t)4 * 40960;  // per wave: parked da planes 32 KB, pre-activation chunks 2 x 4 KB
     if (t_da) {
-        if (add_dm) return false;
         allow_big_lds(k_comb_bwd_p2<true>, lds);
         k_comb_bwd_p2<true><<<grid, 256, lds, st>>>(dM, XF, g.rev, LNS, CA, G.ln_g, w2b, w0b, dcat, E, t_da);
     } else if (add_dm) {
@@ -288,7 +288,7 @@ bool trr_comb_bwd(const float* dM, const float* XF, const Graph& g, const GnnLay
         allow_big_lds(k_comb_bwd_p2<false>, lds);
         k_comb_bwd_p2<false><<<grid, 256, lds, st>>>(dM, XF, g.rev, LNS, CA, G.ln_g, w2b, w0b, dcat, E, nullptr);
     }
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

@@ -258,10 +258,10 @@ static inline W2 cbs_w2(const void* base, int n_tiles_dim, int k_dim) {
     return w;
 }
 
-// false = not served (small graphs, planes missing, or pet_config_set("emlp_s", 0)); c0g = comb0 with the LayerNorm folded in
-bool comb_bwd_s(const float* dM, const float* XF, const int* rev, const float* LNS, const float* CA, const Lin& c0g, const Lin& c2,
-                float* dcat, int64_t E, bool add_dm, hipStream_t st) {
-    if (!emlp_s_serves(E) || !c0g.bwd2s || !c2.bwd2s || !c0g.b) return false;
+// c0g = comb0 with the LayerNorm folded in
+int comb_bwd_s(const float* dM, const float* XF, const int* rev, const float* LNS, const float* CA, const Lin& c0g, const Lin& c2,
+               float* dcat, int64_t E, bool add_dm, hipStream_t st) {
+    PET_REQUIRE_PLANES(c0g.bwd2s && c2.bwd2s && c0g.b, "combination adjoint");
     const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
     // bwd2s operands: tiles over k_in, K = n_out
     const W2 w2b = cbs_w2(c2.bwd2s, c2.k_in, c2.n_out), w0b = cbs_w2(c0g.bwd2s, c0g.k_in, c0g.n_out);
@@ -273,7 +273,7 @@ bool comb_bwd_s(const float* dM, const float* XF, const int* rev, const float* L
         allow_big_lds(k_comb_bwd_s<false>, lds);
         k_comb_bwd_s<false><<<grid, 256, lds, st>>>(dM, XF, rev, LNS, CA, c0g.b, w2b, w0b, dcat, E);
     }
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

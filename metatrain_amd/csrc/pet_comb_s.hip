@@ -221,10 +221,10 @@ static inline W2 cb_w2(const void* base, int n_out, int k_in) {
     return w;
 }
 
-// false = not served (small graphs, weights not packed for it, or pet_config_set("emlp_s", 0)); c0g = comb0 with the LayerNorm folded in
-bool comb_s(bool first, const float* XF, const int* rev, const Lin& c0g, const Lin& c2, const float* Min, const float* edge_emb,
-            const int* sp_nbr, float* CA, float* LNS, float* Mout, int64_t E, hipStream_t st) {
-    if (!emlp_s_serves(E) || !c0g.fwd2s || !c2.fwd2s) return false;
+// c0g = comb0 with the LayerNorm folded in
+int comb_s(bool first, const float* XF, const int* rev, const Lin& c0g, const Lin& c2, const float* Min, const float* edge_emb,
+           const int* sp_nbr, float* CA, float* LNS, float* Mout, int64_t E, hipStream_t st) {
+    PET_REQUIRE_PLANES(c0g.fwd2s && c2.fwd2s, "combination stage");
     const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
     const W2 w0 = cb_w2(c0g.fwd2s, c0g.n_out, c0g.k_in), w2 = cb_w2(c2.fwd2s, c2.n_out, c2.k_in);
     const int grid = (int)cdiv(E, HS_NW * WROWS);
@@ -235,7 +235,7 @@ bool comb_s(bool first, const float* XF, const int* rev, const Lin& c0g, const L
         allow_big_lds(k_comb_s<false>, lds);
         k_comb_s<false><<<grid, 256, lds, st>>>(XF, rev, w0, c0g.b, w2, c2.b, Min, edge_emb, sp_nbr, CA, LNS, Mout, E);
     }
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

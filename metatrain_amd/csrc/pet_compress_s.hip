@@ -133,10 +133,9 @@ static inline W2 cs_w2(const void* base, int tiles, int kbs) {
     return w;
 }
 
-// false = not served (weights not packed for it, small graph, or the edge MLP's switch is off: pet_config_set("emlp_s"))
-bool compress_bwd_s(bool first, const float* dXe, const float* a0, const GnnLayerW& G, float* dgeo, float* dM, int64_t E,
-                    hipStream_t st) {
-    if (!emlp_s_serves(E) || !G.compress2.bwd2s || !G.wc2s || !(first || G.compress0_msg.bwd2s)) return false;
+int compress_bwd_s(bool first, const float* dXe, const float* a0, const GnnLayerW& G, float* dgeo, float* dM, int64_t E,
+                   hipStream_t st) {
+    PET_REQUIRE_PLANES(G.compress2.bwd2s && G.wc2s && (first || G.compress0_msg.bwd2s), "compress adjoint");
     const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
     const int grid = (int)cdiv(E, HS_NW * WROWS);
     const W2 w2b = cs_w2(G.compress2.bwd2s, D / 32, D / 16), wcp = cs_w2(G.wc2s, 1, D / 16);
@@ -147,7 +146,7 @@ bool compress_bwd_s(bool first, const float* dXe, const float* a0, const GnnLaye
         allow_big_lds(k_compress_bwd_s<false>, lds);
         k_compress_bwd_s<false><<<grid, 256, lds, st>>>(dXe, a0, w2b, wcp, cs_w2(G.compress0_msg.bwd2s, D / 32, D / 16), dgeo, dM, E);
     }
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

@@ -415,15 +415,6 @@ __global__ __launch_bounds__(256, 2) void k_emlp_bwd_s(const float* __restrict__
     store_rows_lines<16>(w, reinterpret_cast<float*>(tile), L, [&](int r) { return live && row0 + r < E ? dX1 + (row0 + r) * D : nullptr; });
 }
 
-// pet_config_set("emlp_s", v): these kernels instead of the pipelined k_emlp_p2 / k_emlp_bwd_p2 from switches().emlp_s_rows
-// edge rows on (switches.h EMLP_S_MIN_ROWS; v > 1: the tests force small graphs through)
-bool emlp_s_serves(int64_t E) { return switches().emlp_s && E >= switches().emlp_s_rows; }
-// (the edge head's kernels follow the same policy: pet_head_s.hip)
-bool emlp_s_forced() { return switches().emlp_s && switches().emlp_s_rows < EMLP_S_MIN_ROWS; }
-bool emlp_recompute_on(const Lin& win, const Lin& wout, int64_t E) {
-    return emlp_s_serves(E) && win.fwd2s && wout.fwd2s && wout.bwd2s;
-}
-
 static inline W2 es_w2(const void* base, int n_out, int k_in) {
     const size_t n8 = (size_t)(n_out / 32) * (k_in / 16) * 64;
     const f16x8* b = reinterpret_cast<const f16x8*>(base);
@@ -431,10 +422,9 @@ static inline W2 es_w2(const void* base, int n_out, int k_in) {
     return w;
 }
 
-// false = not served (weights not packed for it, or switched off)
-bool emlp_s(const float* X1, const float* gamma, const float* beta, const Lin& win, const Lin& wout, float* VG, float* X2,
-            int64_t E, hipStream_t st) {
-    if (!emlp_s_serves(E) || !win.fwd2s || !wout.fwd2s) return false;
+int emlp_s(const float* X1, const float* gamma, const float* beta, const Lin& win, const Lin& wout, float* VG, float* X2,
+           int64_t E, hipStream_t st) {
+    PET_REQUIRE_PLANES(win.fwd2s && wout.fwd2s, "edge MLP");
     const size_t lds = ES_NW * 16384 + ES_NSLOT * ES_SLOT;
     const W2 wi = es_w2(win.fwd2s, win.n_out, win.k_in), wo = es_w2(wout.fwd2s, wout.n_out, wout.k_in);
     const int grid = (int)cdiv(E, ES_NW * WROWS);
@@ -445,14 +435,14 @@ bool emlp_s(const float* X1, const float* gamma, const float* beta, const Lin& w
         allow_big_lds(k_emlp_s<false>, lds);
         k_emlp_s<false><<<grid, 256, lds, st>>>(X1, gamma, beta, wi, win.b, wo, wout.b, VG, X2, E);
     }
-    return true;
+    return PET_OK;
 }
 
-// the adjoint with recomputed pre-activations; false = not served
-bool emlp_bwd_s(const float* dY, const float* X1, bool ln, const Lin& win_g, const Lin& wout, float* dX1, int64_t E,
-                hipStream_t st, int ldy, const float* dY2, const int* rev2) {
-    if (!switches().emlp_s || !win_g.fwd2s || !win_g.bwd2s || !wout.bwd2s) return false;
-    if (E <= 0) return true;
+// the adjoint with recomputed pre-activations
+int emlp_bwd_s(const float* dY, const float* X1, bool ln, const Lin& win_g, const Lin& wout, float* dX1, int64_t E,
+               hipStream_t st, int ldy, const float* dY2, const int* rev2) {
+    PET_REQUIRE_PLANES(win_g.fwd2s && win_g.bwd2s && wout.bwd2s, "edge MLP adjoint");
+    if (E <= 0) return PET_OK;
     const size_t lds = ES_NW * 16384 + ES_NSLOT * ES_SLOT;
     const W2 wi = es_w2(win_g.fwd2s, win_g.n_out, win_g.k_in), wot = es_w2(wout.bwd2s, wout.n_out, wout.k_in),
              wit = es_w2(win_g.bwd2s, win_g.n_out, win_g.k_in);
@@ -465,7 +455,7 @@ bool emlp_bwd_s(const float* dY, const float* X1, bool ln, const Lin& win_g, con
     if (ln) { if (dY2) PET_EB(true, true) else PET_EB(true, false) }
     else { if (dY2) PET_EB(false, true) else PET_EB(false, false) }
 #undef PET_EB
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

@@ -1007,13 +1007,6 @@ static Graph::FwdRecord& note_workspace(const Graph& g, const void* ws, bool gen
     return r;
 }
 
-// rows per workgroup of k_node2 / k_node_bwd2: node_planes = 2 forces 32 (the tests' route to the 32-row kernels), 1 chooses by the number of atoms
-static int g_node_rows_threshold = 16384;  // measured: 1 000 / 3 000 / 10 000 atoms gain 14 / 8 / 2 %, 80 000 lose 8 % of the stage
-int node_rows(int64_t N) {
-    if (switches().node_planes == 2) return 32;
-    return N <= g_node_rows_threshold ? 32 : 64;
-}
-
 // sum_i (n_i + 1)^2 estimated from the mean neighbour count (exact value is not needed on the hot path)
 double g_sum_t2(const Graph& g) {
     if (g.n_nodes == 0) return 0.0;
@@ -1068,8 +1061,8 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
     const size_t lds1 = BM * LD128 * 4, lds2 = 2 * BM * LD128 * 4;
     const size_t lds_c = lds2 + BM * 20 + BM * 8;
     const double fE = (double)E, fN = (double)N, fR = (double)R;
-    const bool trr = use_trr();
-    const bool trr_l = trr && m.plain_layers();  // the TRR transformer-layer kernels are PreLN (RMSNorm or LayerNorm)
+    // which kernel serves every stage below: decided here, once (pet_plan.hip); the adjoint of this workspace follows it
+    const StagePlan& plan = fwd_rec.plan = plan_forward(m, g, save);
     // attention: 4 T^2 d FLOPs per atom per layer; T^2 summed on the host side of the graph
     const double attn_flops = 4.0 * D * g_sum_t2(g);
     const int L = m.h.num_gnn_layers, AL = m.h.num_attention_layers;
@@ -1078,17 +1071,18 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
     allow_big_lds(k_node, (BM * LD256 + BM * LD128) * 4 + BM * 8);
     allow_big_lds(k_head<256>, (BM * LD256 + BM * LD128) * 4 + BM * 8);
     SideStream ss = side_stream();
-    if (post) ss.enabled = false;  // PostLN: the node update needs the MLP output of the centre token, one chain
+    ss.enabled = plan.side;
     const hipStream_t s2 = ss.stream(st);  // node-feature chain
     bool side_busy = false;
-    auto launch_center = [&](int gi, int a) {
+    auto launch_center = [&](int gi, int a) -> int {
         const AttnLayerW& A = m.gnn[gi].attn[a];
         AttnBufs& Ab = w.gnn[gi].attn[a];
         if (a == 0 && res && gi > 0)  // backend.py:617: every GNN layer starts from its own node embedding
             k_node_embed<<<cdiv(N * (DN / 4), 256), 256, 0, s2>>>(g.sp, m.node_embs[gi], w.gnn[gi].Hin, (int)N);
         ProfScope ps("center", s2, fN * 2.0 * DN * D);
-        if (save != 2 && center_s(A.cc, Ab.H, Ab.X + E * D, N, s2)) return;  // large graphs (pet_center_s.hip)
+        if (plan.gnn[gi].layers[a].center == Center::Ring) return center_s(A.cc, Ab.H, Ab.X + E * D, N, s2);
         k_center<<<gN, NTHREADS, BM * LD256 * 4 + BM * 8, s2>>>(Ab.H, wx_fwd(A.cc), A.cc.b, Ab.X + E * D, N);
+        return PET_OK;
     };
     k_node_embed<<<cdiv(N * (DN / 4), 256), 256, 0, st>>>(g.sp, m.node_emb, w.H0, (int)N);
     const bool conditioned = m.h.system_conditioning != 0;
@@ -1100,18 +1094,19 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
                                                              m.h.max_spin_multiplicity);
     }
     ss.fork(st);
-    launch_center(0, 0);
+    PET_TRY(launch_center(0, 0));
     side_busy = true;
     bool node_cnt_zeroed = false;  // k_node2 SPLIT: the arrival counters are zeroed once per forward, then reset themselves
     for (int gi = 0; gi < L; gi++) {
         const GnnLayerW& G = m.gnn[gi];
         GnnBufs& B = w.gnn[gi];
+        const GnnPlan& P = plan.gnn[gi];
         const float* Min = gi == 0 ? nullptr : w.gnn[gi - 1].Mout;
         if (E > 0) {
             ProfScope ps("compress", st, fE * 2.0 * (D * D * (gi == 0 ? 3 : 4) + 4 * D));
-            if (trr && trr_compress(gi == 0, g, G, Min, save == 0 ? nullptr : B.a0, B.attn[0].X, E, st)) {  // (no adjoint follows: the pre-activation is not stored)
-                // TRR kernel on f16x3 (pet_trr.hip)
-            } else if (gi == 0)
+            if (P.compress == Rows::Pipelined)  // (save = 0, no adjoint follows: the pre-activation is not stored)
+                PET_TRY(trr_compress(gi == 0, g, G, Min, save == 0 ? nullptr : B.a0, B.attn[0].X, E, st));
+            else if (gi == 0)
                 k_compress<true><<<gE, NTHREADS, lds1 + BM * 20 + BM * 8, st>>>(g.geo, g.sp_nbr, G.wc, G.tbl, nullptr, WX(),
                                                                         wx_fwd(G.compress2), G.compress2.b, B.a0,
                                                                         B.attn[0].X, E);
@@ -1123,20 +1118,18 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
         for (int a = 0; a < AL; a++) {
             const AttnLayerW& A = G.attn[a];
             AttnBufs& Ab = B.attn[a];
+            const LayerPlan& Q = P.layers[a];
             float* Xnext = (a + 1 < AL) ? B.attn[a + 1].X : B.XF;
             if (side_busy) {  // the centre rows of this layer's tokens come from the node chain
                 ss.join(st);
                 side_busy = false;
             }
-            // the per-atom fused block (pet_ablk.hip): QKV, attention output and nothing else of this stage reach HBM.
-            // Training keeps the three-kernel form (its second-order pass reads the saved QKV and AO).
-            bool fused = false;
-            if (trr_l && save != 2 && E > 0 && (save == 0 || ablk_bwd_on(g))) {
+            const bool trr_l = Q.attn == Attn::Pipelined;
+            if (Q.attn == Attn::Fused) {
+                // the per-atom fused block (pet_ablk.hip): QKV, attention output and nothing else of this stage reach HBM
                 ProfScope ps("attn_blk", st, fR * 2.0 * D * 4 * D + attn_flops, fR * 4.0 * 2 * D);  // X in; X1 | OC out
-                fused = ablk_fwd(m, g, A, Ab.X, Ab.X1, Ab.OC, scale, st);
-                if (fused && save) fwd_rec.attn_unsaved = true;  // the adjoint of this workspace must be the fused one
-            }
-            if (!fused) {
+                PET_TRY(ablk_fwd(m, g, A, Ab.X, Ab.X1, Ab.OC, scale, st));
+            } else {
             {
                 ProfScope ps("qkv", st, fR * 2.0 * D * 3 * D, fR * 4.0 * (D + 3 * D));  // X in, QKV out
                 if (trr_l) trr_qkv(Ab.X, A.g_attn, m.layer_norm() ? A.b_attn : nullptr, A.qkv, Ab.QKV, R, st);
@@ -1145,7 +1138,7 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
             }
             {
                 ProfScope ps("attn_fwd", st, attn_flops, fR * 4.0 * (3 * D + D));
-                if (!(trr && attn_fwd_preload(nt, Ab.QKV, g, Ab.AO, scale, st))) switch (nt) {
+                if (!(plan.attn_preload && attn_fwd_preload(nt, Ab.QKV, g, Ab.AO, scale, st))) switch (nt) {
                     case 1: launch_attn_fwd<1>(Ab.QKV, g, Ab.AO, scale, st); break;
                     case 2: launch_attn_fwd<2>(Ab.QKV, g, Ab.AO, scale, st); break;
                     case 3: launch_attn_fwd<3>(Ab.QKV, g, Ab.AO, scale, st); break;
@@ -1172,77 +1165,73 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
             }
             // node chain (side stream): node update of this layer, then the centre token of the next
             ss.fork(st);
-            bool center_done = false;
+            const bool has_next = a + 1 < AL || gi + 1 < L;
+            const AttnLayerW* An = !has_next ? nullptr : a + 1 < AL ? &G.attn[a + 1] : &m.gnn[gi + 1].attn[0];
+            AttnBufs* Abn = !has_next ? nullptr : a + 1 < AL ? &B.attn[a + 1] : &w.gnn[gi + 1].attn[0];
+            const bool center_done = has_next && (a + 1 < AL ? P.layers[a + 1] : plan.gnn[gi + 1].layers[0]).center == Center::ByNode;
             {
                 ProfScope ps("node", s2, fN * 2.0 * (D * DN + DN * 2 * DNF + DNF * DN));
+                // the next layer's centre tokens in the same launch: center_contraction(Hn) as it leaves this kernel
                 WX wcn;
                 const float* bcn = nullptr;
                 float* xcn = nullptr;
+                if (center_done) {
+                    PET_REQUIRE(Abn->H == Ab.Hn, PET_ERR_ARGUMENT, "node update: the next layer does not start from this layer's node features");
+                    wcn = wx_fwd(An->cc); bcn = An->cc.b; xcn = Abn->X + E * D;
+                }
                 const WX wci = wx_fwd(A.cmlp_in), wce_ = wx_fwd(A.ce), wco = wx_fwd(A.cmlp_out);
-                // large graphs: three shared-ring GEMMs that can run BESIDE the edge MLP (pet_node_s.hip); its scratch lives in
-                // dQKV, which only the adjoint uses
-                if (switches().node_planes && (size_t)N * DNF <= (size_t)R * 3 * D &&
-                    node_fwd_s(A, Ab.H, Ab.OC, Ab.H1, Ab.VGn, Ab.Hn, w.dQKV, N, s2)) {
-                } else
-                if (switches().node_planes && wci.h && wce_.h && wco.h) {
-                    const int nr = node_rows(N);
-                    const size_t lds_n2 = (size_t)nr * LD256 * 4 + (size_t)2 * nr * plane_ld(256) * 2 + nr * 8;
-                    // the next layer's centre tokens in the same launch when they are center_contraction(Hn) as it leaves this
-                    // kernel: not behind the conditioning add, not into a residual GNN layer (its own embedding), f16x3 weights
-                    const bool has_next = a + 1 < AL || gi + 1 < L;
-                    if (has_next && switches().center_fused && nr == 32 && !(a + 1 == AL && (conditioned || res))) {  // (large graphs: k_center is quicker)
-                        const AttnLayerW& An = a + 1 < AL ? G.attn[a + 1] : m.gnn[gi + 1].attn[0];
-                        AttnBufs& Abn = a + 1 < AL ? B.attn[a + 1] : w.gnn[gi + 1].attn[0];
-                        wcn = wx_fwd(An.cc);
-                        if (wcn.h && Abn.H == Ab.Hn) { bcn = An.cc.b; xcn = Abn.X + E * D; center_done = true; }
-                    }
-                    // small graphs: the hidden chunks of a row tile on four workgroups; partial outputs and the tiles'
-                    // arrival counters live in dQKV, which only the adjoint uses (k_node2, SPLIT)
+                const int nr = Q.node == Node::Rows64 ? 64 : 32;
+                const size_t lds_n2 = (size_t)nr * LD256 * 4 + (size_t)2 * nr * plane_ld(256) * 2 + nr * 8;
+                switch (Q.node) {
+                case Node::Ring:  // three ring GEMMs BESIDE the edge MLP (pet_node_s.hip); scratch in dQKV, which only the adjoint uses
+                    PET_TRY(node_fwd_s(A, Ab.H, Ab.OC, Ab.H1, Ab.VGn, Ab.Hn, w.dQKV, N, s2));
+                    break;
+                case Node::Split: {  // the hidden chunks of a row tile on four workgroups; partial outputs and the tiles' arrival counters in dQKV
                     const int nt32 = cdiv(N, 32);
                     const size_t p_floats = (size_t)(DNF / 128) * nt32 * 32 * DN;
-                    const bool split = nr == 32 && switches().node_split && nt32 <= 128 && p_floats + nt32 <= (size_t)R * 3 * D;
-                    if (split) {
-                        int* cnt = reinterpret_cast<int*>(w.dQKV + p_floats);
-                        if (!node_cnt_zeroed) PET_HIP_CHECK(hipMemsetAsync(cnt, 0, nt32 * sizeof(int), s2));
-                        node_cnt_zeroed = true;
-                        allow_big_lds(k_node2<1, true>, lds_n2);
-                        k_node2<1, true><<<dim3(nt32, DNF / 128), NTHREADS, lds_n2, s2>>>(
-                            Ab.H, Ab.OC, wce_, A.ce.b, A.g_center, A.b_center, wci, A.cmlp_in.b, wco, A.cmlp_out.b, Ab.H1, Ab.VGn,
-                            Ab.Hn, N, wcn, bcn, xcn, w.dQKV, cnt);
-                    } else if (nr == 32) {
-                        allow_big_lds(k_node2<1>, lds_n2);
-                        k_node2<1><<<cdiv(N, 32), NTHREADS, lds_n2, s2>>>(Ab.H, Ab.OC, wce_, A.ce.b, A.g_center, A.b_center, wci,
-                                                                         A.cmlp_in.b, wco, A.cmlp_out.b, Ab.H1, Ab.VGn, Ab.Hn, N,
-                                                                         wcn, bcn, xcn, nullptr, nullptr);
-                    } else {
-                        allow_big_lds(k_node2w, lds_n2);
-                        k_node2w<<<gN, NTHREADS, lds_n2, s2>>>(Ab.H, Ab.OC, wce_, A.ce.b, A.g_center, A.b_center, wci,
-                                                               A.cmlp_in.b, wco, A.cmlp_out.b, Ab.H1, Ab.VGn, Ab.Hn, N, wcn, bcn, xcn);
-                    }
-                } else
-                k_node<<<gN, NTHREADS, (BM * LD256 + BM * LD128) * 4 + BM * 8, s2>>>(
-                    Ab.H, Ab.OC, wx_fwd(A.ce), A.ce.b, A.g_center, A.b_center, wx_fwd(A.cmlp_in), A.cmlp_in.b,
-                    wx_fwd(A.cmlp_out), A.cmlp_out.b, Ab.H1, Ab.VGn, Ab.Hn, N);
+                    int* cnt = reinterpret_cast<int*>(w.dQKV + p_floats);
+                    if (!node_cnt_zeroed) PET_HIP_CHECK(hipMemsetAsync(cnt, 0, nt32 * sizeof(int), s2));
+                    node_cnt_zeroed = true;
+                    allow_big_lds(k_node2<1, true>, lds_n2);
+                    k_node2<1, true><<<dim3(nt32, DNF / 128), NTHREADS, lds_n2, s2>>>(
+                        Ab.H, Ab.OC, wce_, A.ce.b, A.g_center, A.b_center, wci, A.cmlp_in.b, wco, A.cmlp_out.b, Ab.H1, Ab.VGn,
+                        Ab.Hn, N, wcn, bcn, xcn, w.dQKV, cnt);
+                    break;
+                }
+                case Node::Rows32:
+                    allow_big_lds(k_node2<1>, lds_n2);
+                    k_node2<1><<<cdiv(N, 32), NTHREADS, lds_n2, s2>>>(Ab.H, Ab.OC, wce_, A.ce.b, A.g_center, A.b_center, wci,
+                                                                     A.cmlp_in.b, wco, A.cmlp_out.b, Ab.H1, Ab.VGn, Ab.Hn, N,
+                                                                     wcn, bcn, xcn, nullptr, nullptr);
+                    break;
+                case Node::Rows64:
+                    allow_big_lds(k_node2w, lds_n2);
+                    k_node2w<<<gN, NTHREADS, lds_n2, s2>>>(Ab.H, Ab.OC, wce_, A.ce.b, A.g_center, A.b_center, wci,
+                                                           A.cmlp_in.b, wco, A.cmlp_out.b, Ab.H1, Ab.VGn, Ab.Hn, N, wcn, bcn, xcn);
+                    break;
+                case Node::LdsTile:
+                    k_node<<<gN, NTHREADS, (BM * LD256 + BM * LD128) * 4 + BM * 8, s2>>>(
+                        Ab.H, Ab.OC, wce_, A.ce.b, A.g_center, A.b_center, wci, A.cmlp_in.b, wco, A.cmlp_out.b, Ab.H1, Ab.VGn,
+                        Ab.Hn, N);
+                    break;
+                }
             }
             if (a + 1 == AL && conditioned)  // backend.py:543-545: the node features LEAVING the GNN layer
                 k_add_cond<<<cdiv(N * (DN / 4), 256), 256, 0, s2>>>(Ab.Hn, w.cond, g.sys, g.cond_sys, (int)N);
-            if (center_done) {
-            } else if (a + 1 < AL) launch_center(gi, a + 1);
-            else if (gi + 1 < L) launch_center(gi + 1, 0);
+            if (has_next && !center_done) PET_TRY(a + 1 < AL ? launch_center(gi, a + 1) : launch_center(gi + 1, 0));
             side_busy = true;
             if (E > 0 && !post) {
-                const bool vg_out = save != 0 && !(trr_l && save == 1 && emlp_recompute_on(A.mlp_in, A.mlp_out, E));
-                ProfScope ps("emlp", st, fE * 2.0 * (D * 2 * DFF + DFF * D), fE * 4.0 * (2 * D + (vg_out ? 2 * DFF : 0)));  // X1 in; X2 (and VG, when it is saved) out
-                if (trr_l) {
-                    float* vg = save == 0 ? nullptr : Ab.VG;  // [v; g] is stored for the adjoint unless none follows ...
-                    if (save == 1 && emlp_recompute_on(A.mlp_in, A.mlp_out, E)) {  // ... or the adjoint recomputes it (noted on the graph)
-                        vg = nullptr;
-                        fwd_rec.emlp_unsaved = true;
-                    }
-                    trr_emlp(Ab.X1, A.g_mlp, m.layer_norm() ? A.b_mlp : nullptr, A.mlp_in, A.mlp_out, vg, Xnext, E, st);
+                ProfScope ps("emlp", st, fE * 2.0 * (D * 2 * DFF + DFF * D), fE * 4.0 * (2 * D + (Q.emlp_saved ? 2 * DFF : 0)));  // X1 in; X2 (and VG, when it is saved) out
+                float* vg = Q.emlp_saved ? Ab.VG : nullptr;  // [v; g]: not stored when no adjoint follows or the adjoint recomputes it
+                const float* beta = m.layer_norm() ? A.b_mlp : nullptr;
+                switch (Q.emlp) {
+                case Rows::Ring: PET_TRY(emlp_s(Ab.X1, A.g_mlp, beta, A.mlp_in, A.mlp_out, vg, Xnext, E, st)); break;
+                case Rows::Pipelined: trr_emlp(Ab.X1, A.g_mlp, beta, A.mlp_in, A.mlp_out, vg, Xnext, E, st); break;
+                case Rows::LdsTile:
+                    k_emlp<true><<<gE, NTHREADS, lds2, st>>>(Ab.X1, A.g_mlp, A.b_mlp, A.mlp_in.fwd, A.mlp_in.b, A.mlp_out.fwd,
+                                                             A.mlp_out.b, Ab.VG, Xnext, E);
+                    break;
                 }
-                else k_emlp<true><<<gE, NTHREADS, lds2, st>>>(Ab.X1, A.g_mlp, A.b_mlp, A.mlp_in.fwd, A.mlp_in.b, A.mlp_out.fwd,
-                                                              A.mlp_out.b, Ab.VG, Xnext, E);
             }
         }
         if (g.x_fn) {   // one box over several ranks: the transformer outputs of foreign centres arrive from their owners
@@ -1258,9 +1247,11 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
             }
         } else if (E > 0) {
             ProfScope ps("comb", st, fE * 2.0 * (2 * D * 2 * D + 2 * D * D), fE * 4.0 * (3 * D + 2 * D + D));  // e, e[rev], M in; CA, M out
-            // the software-pipelined TRR kernel (pet_comb.hip) is the one implementation of this stage
-            PET_REQUIRE(trr_comb(gi == 0, B.XF, g, G, Min, m.edge_emb, B.CA, B.LNS, B.Mout, E, st), PET_ERR_ARGUMENT,
-                        "combination stage: the split weight planes are missing (pet_model_finalize)");
+            // (no LDS-tile form: the software-pipelined kernel of pet_comb.hip is the fallback of this stage)
+            if (P.comb == Rows::Ring)
+                PET_TRY(comb_s(gi == 0, B.XF, g.rev, G.comb0_g, G.comb2, Min, m.edge_emb, g.sp_nbr, B.CA, B.LNS, B.Mout, E, st));
+            else
+                PET_TRY(trr_comb(gi == 0, B.XF, g, G, Min, m.edge_emb, B.CA, B.LNS, B.Mout, E, st));
         }
     }
     const GnnBufs& last = w.gnn.back();
@@ -1276,9 +1267,14 @@ int forward_layers(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, i
     }
     if (atomic && E > 0) {
         ProfScope ps("head_edge", st, fE * 2.0 * (D * DH + DH * DH + DH));
-        if (!(trr && trr_head_edge(m, last.Mout, g.fc, w.ypred_e, w.ye, E, st)))
-        k_head<128><<<gE, NTHREADS, lds2 + BM * 8, st>>>(last.Mout, wx_fwd(m.eh0), m.eh0.b, wx_fwd(m.eh2), m.eh2.b, m.ell_w,
-                                                m.ell_b, g.fc, w.ypred_e, w.ye, E);
+        switch (plan.head_edge) {
+        case Rows::Ring: PET_TRY(head_edge_s(m, last.Mout, g.fc, w.ypred_e, w.ye, E, st)); break;
+        case Rows::Pipelined: PET_TRY(trr_head_edge(m, last.Mout, g.fc, w.ypred_e, w.ye, E, st)); break;
+        case Rows::LdsTile:
+            k_head<128><<<gE, NTHREADS, lds2 + BM * 8, st>>>(last.Mout, wx_fwd(m.eh0), m.eh0.b, wx_fwd(m.eh2), m.eh2.b, m.ell_w,
+                                                             m.ell_b, g.fc, w.ypred_e, w.ye, E);
+            break;
+        }
     }
     ss.join(st);
     if (atomic) k_atom_sum<<<cdiv(N, 256), 256, 0, st>>>(w.ynode, w.ye, g.rowptr, atomic, (int)N);

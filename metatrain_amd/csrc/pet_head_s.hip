@@ -237,24 +237,23 @@ static inline W2 hs_w2(const void* base, int n_out, int k_in) {
     return w;
 }
 
-// false = not served (weights not packed for it, small graph, or the edge MLP's switch is off: pet_config_set("emlp_s"))
-bool head_edge_s(const Model& m, const float* Xin, const float* fc, float* ypred, float* yout, int64_t E, hipStream_t st) {
-    if (!emlp_s_serves(E) || !m.eh0.fwd2s || !m.eh2.fwd2s) return false;
+int head_edge_s(const Model& m, const float* Xin, const float* fc, float* ypred, float* yout, int64_t E, hipStream_t st) {
+    PET_REQUIRE_PLANES(m.eh0.fwd2s && m.eh2.fwd2s, "edge head");
     const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
     allow_big_lds(k_head_s, lds);
     k_head_s<<<(int)cdiv(E, HS_NW * WROWS), 256, lds, st>>>(Xin, hs_w2(m.eh0.fwd2s, DH, D), m.eh0.b, hs_w2(m.eh2.fwd2s, DH, DH), m.eh2.b,
                                                              m.ell_w, m.ell_b, fc, ypred, yout, E);
-    return true;
+    return PET_OK;
 }
-bool head_edge_bwd_s(const Model& m, const float* Xin, const float* gA, const int* ctr, const float* fc, const float* ypred,
-                     float* dfc, float* dXout, int64_t E, hipStream_t st) {
-    if (!emlp_s_serves(E) || !m.eh0.fwd2s || !m.eh2.fwd2s || !m.eh0.bwd2s || !m.eh2.bwd2s) return false;
+int head_edge_bwd_s(const Model& m, const float* Xin, const float* gA, const int* ctr, const float* fc, const float* ypred,
+                    float* dfc, float* dXout, int64_t E, hipStream_t st) {
+    PET_REQUIRE_PLANES(m.eh0.fwd2s && m.eh2.fwd2s && m.eh0.bwd2s && m.eh2.bwd2s, "edge head adjoint");
     const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
     allow_big_lds(k_head_bwd_s, lds);
     k_head_bwd_s<<<(int)cdiv(E, HS_NW * WROWS), 256, lds, st>>>(Xin, hs_w2(m.eh0.fwd2s, DH, D), m.eh0.b, hs_w2(m.eh2.fwd2s, DH, DH),
                                                                  m.eh2.b, hs_w2(m.eh2.bwd2s, DH, DH), hs_w2(m.eh0.bwd2s, DH, D), m.ell_w, gA,
                                                                  ctr, fc, ypred, dfc, dXout, E);
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

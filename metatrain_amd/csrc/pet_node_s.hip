@@ -27,32 +27,32 @@ __global__ __launch_bounds__(256) void k_node_swiglu(const float* __restrict__ V
         make_float4(v.x * sigmoidf_(g.x), v.y * sigmoidf_(g.y), v.z * sigmoidf_(g.z), v.w * sigmoidf_(g.w));
 }
 
-// false = not served (fewer atoms than the row kernels' threshold, planes missing, or pet_config_set("emlp_s", 0)); nothing has been
-// launched in that case. tmp: [N, DNF] floats of scratch (the SwiGLU output)
-bool node_fwd_s(const AttnLayerW& A, const float* H, const float* OC, float* H1, float* VGn, float* Hn, float* tmp, int64_t N,
-                hipStream_t st) {
-    if (!emlp_s_serves(N) || !A.ce.fwd2s || !A.cmlp_in.fwd2s || !A.cmlp_out.fwd2s || !VGn || N <= 0) return false;
+// tmp: [N, DNF] floats of scratch (the SwiGLU output). (The row GEMMs of so_rows_s.hip decline without planes and below the ring
+// kernels' row threshold; the plan asks the same before it chooses this chain.)
+int node_fwd_s(const AttnLayerW& A, const float* H, const float* OC, float* H1, float* VGn, float* Hn, float* tmp, int64_t N,
+               hipStream_t st) {
     float* U = tmp;
-    if (!rowgemm_s_ex(st, OC, D, nullptr, A.ce.fwd2s, A.ce.b, H, H1, DN, N, 0, nullptr)) return false;
+    PET_REQUIRE_PLANES(A.cmlp_in.fwd2s && A.cmlp_out.fwd2s && VGn && N > 0 &&
+                       rowgemm_s_ex(st, OC, D, nullptr, A.ce.fwd2s, A.ce.b, H, H1, DN, N, 0, nullptr), "node update");
     rowgemm_s_ex(st, H1, DN, A.g_center, A.cmlp_in.fwd2s, A.cmlp_in.b, nullptr, VGn, 2 * DNF, N, A.b_center ? 2 : 1, A.b_center);
     k_node_swiglu<<<(int)cdiv(N * (DNF / 4), 256), 256, 0, st>>>(VGn, U, N * (DNF / 4));
     rowgemm_s_ex(st, U, DNF, nullptr, A.cmlp_out.fwd2s, A.cmlp_out.b, H1, Hn, DN, N, 0, nullptr);
-    return true;
+    return PET_OK;
 }
 
 // The adjoint of the same update (inference): dH1 = dHn + norm^T(W_in^T swiglu'(W_out^T dHn)). tmp: [N, 3 DNF] floats of scratch.
 //   dvg = swiglu'(saved vg) (dHn Wout)         k_rowgemm_s_k2<0, 1>  (256 -> 512, the SwiGLU adjoint in the epilogue)
 //   dH1 = dHn + norm^T(dvg Win; h1)            k_rowgemm_s_n2<1>     (1024 -> 256, the norm adjoint and the residual in the epilogue)
 // (the first form of this chain ran the two row-wise steps as kernels of their own: four links instead of two, 42.98 against 42.82 ms)
-bool node_bwd_s(const AttnLayerW& A, const float* dHn, const float* H1, const float* VGn, float* dH1, float* tmp, int64_t N, bool ln,
-                hipStream_t st) {
-    if (!emlp_s_serves(N) || !A.cmlp_in.bwd2s || !A.cmlp_out.bwd2s || N <= 0) return false;
+int node_bwd_s(const AttnLayerW& A, const float* dHn, const float* H1, const float* VGn, float* dH1, float* tmp, int64_t N, bool ln,
+               hipStream_t st) {
     float* dVG = tmp;  // [N, 2 DNF]
     // the SwiGLU adjoint is the first GEMM's epilogue, the norm adjoint and the residual the second one's (so_rows_s.hip): two
     // launches in the dependent chain beside the edge kernels instead of four
-    if (!rowgemm_s_swiglu_bwd(st, dHn, A.cmlp_out.bwd2s, VGn, dVG, DNF, N)) return false;
+    PET_REQUIRE_PLANES(A.cmlp_in.bwd2s && N > 0 && rowgemm_s_swiglu_bwd(st, dHn, A.cmlp_out.bwd2s, VGn, dVG, DNF, N),
+                       "node update adjoint");
     rowgemm_s_norm_bwd(st, dVG, 2 * DNF, A.cmlp_in.bwd2s, H1, A.g_center, ln ? 1 : 0, dHn, dH1, N);
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

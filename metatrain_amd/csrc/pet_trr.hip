@@ -983,7 +983,6 @@ void trr_oproj_bwd(const float* dX1, const float* dOC, const Lin& out, float* dA
 void trr_emlp(const float* X1, const float* gamma, const float* beta, const Lin& win, const Lin& wout, float* VG,
               float* X2, int64_t E, hipStream_t st) {
     if (E <= 0) return;
-    if (emlp_s(X1, gamma, beta, win, wout, VG, X2, E, st)) return;  // large graphs: two waves per SIMD (pet_emlp_s.hip)
     const size_t lds = (size_t)4 * EP2_WAVE_LDS;
     if (beta) {
         allow_big_lds(k_emlp_p2<true>, lds);
@@ -1153,19 +1152,17 @@ __global__ __launch_bounds__(256) void k_head_bwd_h(const float* __restrict__ Xi
     });
 }
 
-bool trr_head_edge(const Model& m, const float* Xin, const float* fc, float* ypred, float* yout, int64_t E,
-                   hipStream_t st) {
-    if (!((switches().trr_compress & 2) && m.eh0.fwd2 && m.eh2.fwd2)) return false;
-    if (head_edge_s(m, Xin, fc, ypred, yout, E, st)) return true;  // large graphs: two workgroups per CU, shared weight ring
+int trr_head_edge(const Model& m, const float* Xin, const float* fc, float* ypred, float* yout, int64_t E,
+                  hipStream_t st) {
+    PET_REQUIRE_PLANES(m.eh0.fwd2 && m.eh2.fwd2, "edge head");
     k_head_h<<<grid_rows(E), 256, 0, st>>>(Xin, w2_fwd(m.eh0), m.eh0.b, w2_fwd(m.eh2), m.eh2.b, m.ell_w, m.ell_b, fc, ypred,
                                            yout, E);
-    return true;
+    return PET_OK;
 }
-bool trr_head_edge_bwd(const Model& m, const float* Xin, const float* gA, const int* ctr, const float* fc,
+int trr_head_edge_bwd(const Model& m, const float* Xin, const float* gA, const int* ctr, const float* fc,
                        const float* ypred, float* dfc, float* dXout, int64_t E, float* t_s1, float* t_da2, float* t_da1,
                        float* t_s2y, hipStream_t st) {
-    if (!((switches().trr_compress & 2) && m.eh0.fwd2 && m.eh2.fwd2 && m.eh0.bwd2 && m.eh2.bwd2)) return false;
-    if (!t_s1 && head_edge_bwd_s(m, Xin, gA, ctr, fc, ypred, dfc, dXout, E, st)) return true;  // (inference; pet_head_s.hip)
+    PET_REQUIRE_PLANES(m.eh0.fwd2 && m.eh2.fwd2 && m.eh0.bwd2 && m.eh2.bwd2, "edge head adjoint");
     const int grid = grid_rows(E);
     if (t_s1)
         k_head_bwd_h<true><<<grid, 256, 0, st>>>(Xin, w2_fwd(m.eh0), m.eh0.b, w2_fwd(m.eh2), m.eh2.b, w2_bwd(m.eh0),
@@ -1175,24 +1172,23 @@ bool trr_head_edge_bwd(const Model& m, const float* Xin, const float* gA, const 
         k_head_bwd_h<false><<<grid, 256, 0, st>>>(Xin, w2_fwd(m.eh0), m.eh0.b, w2_fwd(m.eh2), m.eh2.b, w2_bwd(m.eh0),
                                                   w2_bwd(m.eh2), m.ell_w, gA, ctr, fc, ypred, dfc, dXout, E, nullptr, nullptr,
                                                   nullptr, nullptr);
-    return true;
+    return PET_OK;
 }
 
-bool trr_compress(bool first, const Graph& g, const GnnLayerW& G, const float* Min, float* a0_out, float* Xout,
-                  int64_t E, hipStream_t st) {
-    if (!((switches().trr_compress & 1) && G.compress2.fwd2 && (first || G.compress0_msg.fwd2)) || E <= 0) return false;
+int trr_compress(bool first, const Graph& g, const GnnLayerW& G, const float* Min, float* a0_out, float* Xout,
+                 int64_t E, hipStream_t st) {
+    PET_REQUIRE_PLANES(G.compress2.fwd2 && (first || G.compress0_msg.fwd2), "compress");
     if (first)
         k_compress_h<true><<<grid_rows(E), 256, 0, st>>>(g.geo, g.sp_nbr, G.wc, G.tbl, nullptr, W2(), w2_fwd(G.compress2),
                                                        G.compress2.b, a0_out, Xout, E);
     else
         k_compress_h<false><<<grid_rows(E), 256, 0, st>>>(g.geo, g.sp_nbr, G.wc, G.tbl, Min, w2_fwd(G.compress0_msg),
                                                         w2_fwd(G.compress2), G.compress2.b, a0_out, Xout, E);
-    return true;
+    return PET_OK;
 }
-bool trr_compress_bwd(bool first, const float* dXe, const float* a0, const GnnLayerW& G, float* dgeo, float* dM,
-                      int64_t E, float* t_da0, hipStream_t st) {
-    if (!((switches().trr_compress & 1) && G.compress2.bwd2 && G.wc2 && (first || G.compress0_msg.bwd2)) || E <= 0) return false;
-    if (!t_da0 && compress_bwd_s(first, dXe, a0, G, dgeo, dM, E, st)) return true;  // (inference; pet_compress_s.hip)
+int trr_compress_bwd(bool first, const float* dXe, const float* a0, const GnnLayerW& G, float* dgeo, float* dM,
+                     int64_t E, float* t_da0, hipStream_t st) {
+    PET_REQUIRE_PLANES(G.compress2.bwd2 && G.wc2 && (first || G.compress0_msg.bwd2), "compress adjoint");
     const int grid = grid_rows(E);
     if (first) {
         if (t_da0) k_compress_bwd_h<true, true><<<grid, 256, 0, st>>>(dXe, a0, w2_bwd(G.compress2), w2_wc(G), W2(), dgeo, nullptr, E, t_da0);
@@ -1201,7 +1197,7 @@ bool trr_compress_bwd(bool first, const float* dXe, const float* a0, const GnnLa
         if (t_da0) k_compress_bwd_h<false, true><<<grid, 256, 0, st>>>(dXe, a0, w2_bwd(G.compress2), w2_wc(G), w2_bwd(G.compress0_msg), dgeo, dM, E, t_da0);
         else k_compress_bwd_h<false, false><<<grid, 256, 0, st>>>(dXe, a0, w2_bwd(G.compress2), w2_wc(G), w2_bwd(G.compress0_msg), dgeo, dM, E, nullptr);
     }
-    return true;
+    return PET_OK;
 }
 
 }  // namespace pet

@@ -539,13 +539,16 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s_n2(const float* __restrict
     rs_store_block(acc1, f, bias ? bias + 128 : nullptr, A, Y, ldy, 128, r0, R, live, tile, Lq);
 }
 
+// the ring kernels' row policy (pet_config_set("emlp_s"); the first-order pass states the same in pet_plan.hip)
+static bool rows_s_serves(int64_t R) { return switches().emlp_s && R >= switches().emlp_s_rows; }
+
 // false = not served: planes missing, shape not a multiple of 128 both ways, a small matrix of rows, or the row kernels'
 // switch is off (pet_config_set("emlp_s", 0); "emlp_s" = 2 serves the tests' small graphs too).
 // Y = [A +] (norm(X) | X * cs) W^T [+ bias]; A may be Y (accumulate in place); norm 1 / 2: RMSNorm / LayerNorm of the 256-wide rows
 // with weight cs (and bias cb) before the product (K == 256 only)
 bool rowgemm_s_ex(hipStream_t st, const float* X, int K, const float* cs, const void* planes, const float* bias, const float* A,
                   float* Y, int n_out, int64_t R, int norm, const float* cb) {
-    if (!planes || K % 128 || n_out % 128 || K > 1024 || n_out > 1024 || !emlp_s_serves(R)) return false;
+    if (!planes || K % 128 || n_out % 128 || K > 1024 || n_out > 1024 || !rows_s_serves(R)) return false;
     if (norm && (K != 256 || !cs || (norm == 2 && !cb))) return false;
     const size_t n8 = (size_t)(n_out / 32) * (K / 16) * 64;
     const f16x8* b = reinterpret_cast<const f16x8*>(planes);
@@ -572,7 +575,7 @@ bool rowgemm_s_ex(hipStream_t st, const float* X, int K, const float* cs, const 
 }
 // dVG[R, 2 hid] = swiglu'(VG) ((X[R, 256]) W^T): the node update's adjoint, first half (hid a multiple of 128)
 bool rowgemm_s_swiglu_bwd(hipStream_t st, const float* X, const void* planes, const float* VG, float* dVG, int hid, int64_t R) {
-    if (!planes || hid % 128 || hid > 1024 || !emlp_s_serves(R)) return false;
+    if (!planes || hid % 128 || hid > 1024 || !rows_s_serves(R)) return false;
     const f16x8* b = reinterpret_cast<const f16x8*>(planes);
     W2 w; w.h = b; w.l = b + (size_t)(hid / 32) * (256 / 16) * 64;
     const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
@@ -583,7 +586,7 @@ bool rowgemm_s_swiglu_bwd(hipStream_t st, const float* X, const void* planes, co
 // out[R, 256] = dres + norm^T((X[R, K]) W^T; xn): the node update's adjoint, second half (gamma: the norm's weight; ln: LayerNorm)
 bool rowgemm_s_norm_bwd(hipStream_t st, const float* X, int K, const void* planes, const float* xn, const float* gamma, int ln,
                         const float* dres, float* out, int64_t R) {
-    if (!planes || K % 128 || K < 256 || K > 1024 || !emlp_s_serves(R)) return false;
+    if (!planes || K % 128 || K < 256 || K > 1024 || !rows_s_serves(R)) return false;
     const f16x8* b = reinterpret_cast<const f16x8*>(planes);
     W2 w; w.h = b; w.l = b + (size_t)(256 / 32) * (K / 16) * 64;
     const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;

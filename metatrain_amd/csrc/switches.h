@@ -3,11 +3,9 @@
 #pragma once
 #include <stdint.h>
 
-namespace pet {
+#include "pet_plan.h"  // EMLP_S_MIN_ROWS
 
-// emlp_s = 1: the shared-ring edge kernels from this many edge rows on (the measured crossover -- 1 000 atoms, 19 k rows:
-// the pipelined kernels 2 % ahead; 2 000 atoms, 38 k rows: the shared-ring ones 1 % ahead); v > 1 sets the row count itself
-constexpr int64_t EMLP_S_MIN_ROWS = 28672;
+namespace pet {
 
 struct Switches {
     int side_stream = -1;  // -1: the environment decides (abi.hip side_stream())

@@ -525,6 +525,42 @@ int pet_zbl_forward(const pet_zbl_t* z, const pet_graph_t* g, float* d_atomic, v
 int pet_zbl_backward(const pet_zbl_t* z, const pet_graph_t* g, const float* d_grad_atomic, float* d_grad_positions,
                      float* d_grad_cells, float* d_grad_strain, void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Rotational augmentation (utils/augmentation.py:O3Augmenter; pet/trainer.py:187-193, 288-303) -------------------------
+ * A random element of O(3) per system of a collated batch, drawn and applied on the device. A rigid transformation of
+ * positions and cell leaves fractional coordinates alone, so the batch's (center, neighbor, cell_shift) list stays valid:
+ * nothing here touches it, and no neighbour search is needed after the call.
+ *   pet_o3_draw replaces augmentation.py:57-71 (random_transformations, the +-identity draw of lines 58-63): d_matrices
+ *     [n_systems,3,3], one thread per system. Philox-4x32-10 on the counter block (counter low, counter high, system ordinal,
+ *     0) under the 64-bit `key`: a system's matrix is a function of (key, counter, ordinal) alone -- not of the grid, of
+ *     n_systems or of earlier calls. PET_O3_GROUP_O3: a Haar-uniform rotation from Shoemake's unit quaternion, negated with
+ *     probability 1/2 by an independent bit. PET_O3_GROUP_INVERSIONS: +-identity from that same bit. fp64 arithmetic, the
+ *     nine entries rounded to fp32 once.
+ *   pet_o3_apply replaces augmentation.py:97-124 (transform_systems, transform_tensormap for Cartesian targets): up to
+ *     PET_O3_MAX_ARRAYS arrays in one launch, each OUT OF PLACE (dst != src; the sources are the cached batch). Row r of an
+ *     array uses the matrix of system system_of_row[r], or of system r when system_of_row is NULL (then rows <= n_systems).
+ *     PET_O3_VECTOR: rows [3, P], P innermost, out[a,p] = sum_b R[a,b] x[b,p] (positions, forces, gradients; cells as [3 S]
+ *     lattice-vector rows with system_of_row[r] = r / 3). PET_O3_TENSOR2: rows [3, 3, P], out = R T R^T per property
+ *     (stress, strain gradients). fp32. Scalars are not passed at all. A NaN anywhere in a vector or tensor makes that whole
+ *     output vector or tensor NaN (a partly known vector cannot be rotated), and only that one; a zero row stays exactly
+ *     zero. A system index outside [0, n_systems) is not followed: that row comes out NaN.
+ * No atomics, no allocation, no host read-back, no synchronisation: results are the same bits run to run.
+ * PET_ERR_ARGUMENT: an unknown group or kind, n_arrays above PET_O3_MAX_ARRAYS, a negative count, dst == src. */
+#define PET_O3_GROUP_O3 0
+#define PET_O3_GROUP_INVERSIONS 1
+#define PET_O3_VECTOR 0
+#define PET_O3_TENSOR2 1
+#define PET_O3_MAX_ARRAYS 8
+typedef struct pet_o3_array {
+    const float* src;             /* device, rows x (3 or 9) x n_properties */
+    float* dst;                   /* device, same shape */
+    int64_t rows;
+    const int32_t* system_of_row; /* device [rows], or NULL: row r belongs to system r */
+    int32_t n_properties;         /* P, the innermost dimension */
+    int32_t kind;                 /* PET_O3_VECTOR or PET_O3_TENSOR2 */
+} pet_o3_array_t;
+int pet_o3_draw(uint64_t key, uint64_t counter, int32_t group, int64_t n_systems, float* d_matrices, void* stream);
+int pet_o3_apply(const float* d_matrices, int64_t n_systems, int32_t n_arrays, const pet_o3_array_t* h_arrays, void* stream);
+
 /* ---- profiling hooks used by bench.py ------------------------------------------ */
 /* When enabled, every kernel launch of pet_forward/pet_backward is bracketed with HIP
  * events on the launch stream; pet_profile_report fills name / total ms / calls / algorithmic

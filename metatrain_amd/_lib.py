@@ -11,7 +11,7 @@ import os
 # (torch/lib/libamdhip64.so). Loading our library first would pull in /opt/rocm's copy and the
 # process would end up with two runtimes ("no ROCm-capable device is detected").
 import torch  # noqa: F401
-from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import POINTER, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libpet_hip.so")
@@ -22,6 +22,9 @@ PET_CUTOFF_BUMP = 1
 PET_ERR_ARGUMENT = -3
 PET_ERR_UNSUPPORTED = -2
 PET_LLPR_MAX_ENSEMBLE = 16384
+PET_O3_GROUPS = {"O3": 0, "inversions": 1}
+PET_O3_KINDS = {"vector": 0, "tensor2": 1}
+PET_O3_MAX_ARRAYS = 8
 
 # every symbol include/pet_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -47,6 +50,7 @@ SYMBOLS = [
     "pet_llpr_covariance_finalize", "pet_llpr_variance", "pet_llpr_ensemble",
     "pet_zbl_create", "pet_zbl_destroy", "pet_zbl_cutoff", "pet_zbl_pair_table", "pet_zbl_workspace_bytes",
     "pet_zbl_forward", "pet_zbl_backward",
+    "pet_o3_draw", "pet_o3_apply",
     "pet_profile_enable", "pet_profile_select", "pet_profile_reset", "pet_profile_report", "pet_config_set",
 ]
 
@@ -78,6 +82,19 @@ class SoapHypers(ctypes.Structure):
         ("layernorm", c_int32),
         ("num_hidden_layers", c_int32),
         ("num_neurons_per_layer", c_int32),
+    ]
+
+
+class O3Array(ctypes.Structure):
+    """Mirror of ``pet_o3_array_t``."""
+
+    _fields_ = [
+        ("src", c_void_p),
+        ("dst", c_void_p),
+        ("rows", c_int64),
+        ("system_of_row", c_void_p),
+        ("n_properties", c_int32),
+        ("kind", c_int32),
     ]
 
 
@@ -231,6 +248,8 @@ def load() -> ctypes.CDLL:
     lib.pet_zbl_workspace_bytes.restype = c_int64
     lib.pet_zbl_forward.argtypes = [P, P, P, P]
     lib.pet_zbl_backward.argtypes = [P, P, P, P, P, P, P, c_int64, P]
+    lib.pet_o3_draw.argtypes = [c_uint64, c_uint64, c_int32, c_int64, P, P]
+    lib.pet_o3_apply.argtypes = [P, c_int64, c_int32, POINTER(O3Array), P]
     lib.pet_profile_enable.argtypes = [c_int]
     lib.pet_profile_select.argtypes = [c_char_p]
     lib.pet_profile_report.argtypes = [c_int, P, POINTER(c_double), POINTER(c_int64), POINTER(c_double),

@@ -1,0 +1,180 @@
+"""Rotational augmentation on the device data path (``utils/augmentation.py:O3Augmenter``; ``pet/trainer.py:187-193,
+288-303``): a fresh random rotation or improper rotation for every structure of every training batch, which is where PET
+-- not equivariant by construction -- learns its approximate invariance from.
+
+:class:`O3Augmenter` works on collated batches, the dicts of :func:`metatrain_amd.data.collate`. A rigid transformation
+of positions and cell leaves fractional coordinates alone, so the augmented structure has the SAME ``(center, neighbor,
+cell_shift)`` list as the original: the batch is collated (neighbour search included) once and kept for all epochs, and a
+step only draws ``S`` matrices and transforms a few arrays (``csrc/augment.hip``: two launches, no synchronisation, no
+read-back). The reference rotates first and re-runs the neighbour search on every structure at every step.
+
+Sequence of matrices. ``pet_o3_draw`` is counter based: the matrix of system ``s`` of the ``n``-th call is a function of
+``(key, n, s)`` alone, with ``key = stream << 32 | seed`` (``seed`` and ``stream`` both below 2^32; ``stream`` is for the
+rank: two ranks with one seed hold different keys, and no counter value of one rank's sequence is another's).
+:meth:`O3Augmenter.state_dict` holds seed, stream and counter, so a resumed run continues the same sequence.
+"""
+from typing import Dict, Optional, Union
+
+import torch
+
+from . import runtime as rt
+
+# what a collated batch holds besides targets: the first two are transformed, the others shared with the input by reference
+TRANSFORMED = ("positions", "cells")
+SHARED = ("centers", "neighbors", "cell_shifts", "species", "system_indices")
+MATRICES = "o3_matrices"
+ORTHOGONALITY_TOLERANCE = 1e-4
+
+
+def _normalise_kind(name: str, spec: Union[str, dict]) -> dict:
+    if isinstance(spec, str):
+        spec = {"kind": spec}
+    if not isinstance(spec, dict) or "kind" not in spec:
+        raise ValueError(f"target '{name}': expected 'scalar', 'vector', 'tensor2' or a dict with a 'kind', got {spec!r}")
+    unknown = set(spec) - {"kind", "per_atom", "lambda", "sigma"}
+    if unknown:
+        raise ValueError(f"target '{name}': unknown entries {sorted(unknown)}")
+    kind = spec["kind"]
+    if kind == "spherical":
+        lam, sigma = int(spec.get("lambda", 0)), int(spec.get("sigma", 1))
+        if lam > 0 or sigma != 1:
+            raise ValueError(f"target '{name}': spherical targets with lambda > 0 (or sigma = -1) need Wigner-D matrices, which "
+                             f"the device augmenter does not build (got lambda = {lam}, sigma = {sigma})")
+        kind = "scalar"
+    elif "lambda" in spec or "sigma" in spec:
+        raise ValueError(f"target '{name}': 'lambda' / 'sigma' belong to the kind 'spherical'")
+    if kind not in ("scalar", "vector", "tensor2"):
+        raise ValueError(f"target '{name}': unknown kind '{kind}', expected 'scalar', 'vector' or 'tensor2'")
+    per_atom = spec.get("per_atom")
+    return {"kind": kind, "per_atom": None if per_atom is None else bool(per_atom)}
+
+
+class O3Augmenter:
+    """Random O(3) transformations of collated batches, ``O3Augmenter`` of the reference on the device.
+
+    ``kinds``: ``{name in the batch: "scalar" | "vector" | "tensor2"}``, or ``{"kind": ..., "per_atom": bool}`` where the
+    first dimension does not tell (default: ``N`` rows is per atom, ``S`` rows per system). ``vector``: trailing dimensions
+    ``[3, P]``, flattened or not (forces ``[N,3]``, ``[N, 3 P]``); ``tensor2``: ``[3, 3, P]`` (stress ``[S,3,3]``, the
+    ``reshape(n, 3, 3, p)`` layout of ``trainer.process_non_conservative_stress``). Scalars, entries whose name ends in
+    ``_mask`` (``augmentation.py:118-120``) and entries that are no tensors pass through untouched. Every other tensor of a
+    batch must be named in ``kinds``: an unnamed one raises, since leaving a Cartesian target unrotated is silent and wrong.
+    ``{"kind": "spherical", "lambda": l}`` is refused for ``l > 0``. float32 only; a NaN anywhere in a vector or tensor
+    makes that whole output vector or tensor NaN.
+
+    ``group``: ``"O3"`` (Haar-uniform rotations, improper with probability 1/2) or ``"inversions"`` (+-identity).
+    ``seed``, ``stream``: integers in ``[0, 2^32)``; ``stream`` is for the rank (see the module's text)."""
+
+    def __init__(self, kinds: Optional[Dict[str, Union[str, dict]]] = None, group: str = "O3", seed: int = 0, stream: int = 0):
+        if group not in ("O3", "inversions"):
+            raise ValueError(f"unknown transformation group '{group}', expected 'O3' or 'inversions'")
+        for what, v in (("seed", seed), ("stream", stream)):
+            if not 0 <= int(v) < 2**32:
+                raise ValueError(f"{what} must be in [0, 2^32), got {v}")
+        self.group = group
+        self.seed, self.stream = int(seed), int(stream)
+        self.counter = 0  # calls of apply_random_augmentations so far
+        self.kinds = {}
+        for name, spec in (kinds or {}).items():
+            if name in TRANSFORMED + SHARED or name == MATRICES:
+                raise ValueError(f"'{name}' is part of the batch itself, not a target")
+            self.kinds[name] = _normalise_kind(name, spec)
+        self._cell_rows: Dict[tuple, torch.Tensor] = {}  # (S, device) -> int32 [3 S], the system of every lattice vector
+
+    @property
+    def key(self) -> int:
+        """The generator's 64-bit key: the stream in the high word, the seed in the low one."""
+        return (self.stream << 32) | self.seed
+
+    def state_dict(self) -> Dict[str, object]:
+        """Seed, stream, group and the number of draws made: kept next to ``TrainStep.state_dict`` so that a resumed run
+        continues the same sequence of matrices."""
+        return {"seed": self.seed, "stream": self.stream, "counter": self.counter, "group": self.group}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        if state["group"] not in ("O3", "inversions"):
+            raise ValueError(f"unknown transformation group '{state['group']}'")
+        seed, stream, counter = int(state["seed"]), int(state["stream"]), int(state["counter"])
+        if not (0 <= seed < 2**32 and 0 <= stream < 2**32 and 0 <= counter < 2**64):
+            raise ValueError(f"seed / stream / counter out of range: {seed}, {stream}, {counter}")
+        self.group, self.seed, self.stream, self.counter = state["group"], seed, stream, counter
+
+    # ---- what to do with every entry of a batch (host only: shapes and names) ------------------------------------------
+    def _plan(self, batch: Dict[str, object]):
+        for k in TRANSFORMED + SHARED:
+            if k not in batch:
+                raise ValueError(f"not a collated batch: '{k}' is missing")
+        pos, cells = batch["positions"], batch["cells"]
+        if pos.dim() != 2 or pos.shape[1] != 3 or cells.dim() != 3 or tuple(cells.shape[1:]) != (3, 3):
+            raise ValueError(f"positions must be [N,3] and cells [S,3,3], got {tuple(pos.shape)} and {tuple(cells.shape)}")
+        n, s = int(pos.shape[0]), int(cells.shape[0])
+        plan = [("positions", "vector", True), ("cells", "vector", "cells")]
+        for name, v in batch.items():
+            if name in TRANSFORMED + SHARED or name == MATRICES or name.endswith("_mask") or not torch.is_tensor(v):
+                continue
+            if name not in self.kinds:
+                raise ValueError(f"the batch holds '{name}', which the augmenter was not told the kind of: name it in `kinds` "
+                                 "('scalar', 'vector' or 'tensor2')")
+            kind, per_atom = self.kinds[name]["kind"], self.kinds[name]["per_atom"]
+            if kind == "scalar":
+                continue
+            width = 3 if kind == "vector" else 9
+            if v.dim() < 2 or int(v.shape[1:].numel()) % width:
+                raise ValueError(f"target '{name}': a {kind} needs {width} x P values per row, got the shape {tuple(v.shape)}")
+            rows = int(v.shape[0])
+            if per_atom is None:
+                if rows not in (n, s):
+                    raise ValueError(f"target '{name}': {rows} rows are neither the batch's {n} atoms nor its {s} systems")
+                per_atom = rows == n
+            elif rows != (n if per_atom else s):
+                raise ValueError(f"target '{name}': {rows} rows for {n if per_atom else s} {'atoms' if per_atom else 'systems'}")
+            if v.dtype != torch.float32:
+                raise ValueError(f"target '{name}': the transformation kernels are float32, got {v.dtype}")
+            plan.append((name, kind, per_atom))
+        if pos.dtype != torch.float32 or cells.dtype != torch.float32:
+            raise ValueError("positions and cells must be float32")
+        tensors = [batch[k] for k in SHARED] + [batch[name] for name, _, _ in plan]
+        return plan, n, s, tensors
+
+    def _apply(self, batch, plan, s: int, matrices: torch.Tensor) -> Dict[str, object]:
+        sysidx = batch["system_indices"]
+        if sysidx.dtype != torch.int32:
+            raise ValueError(f"system_indices must be int32 (as collate makes them), got {sysidx.dtype}")
+        arrays = []
+        for name, kind, owner in plan:
+            if owner == "cells":  # lattice vectors are the rows of a cell: [3 S] vectors, three per system
+                ck = (s, batch["cells"].device)
+                if ck not in self._cell_rows:
+                    self._cell_rows[ck] = torch.arange(3 * s, dtype=torch.int32, device=ck[1]) // 3
+                arrays.append((batch["cells"].reshape(3 * s, 3), "vector", self._cell_rows[ck]))
+            else:
+                arrays.append((batch[name], kind, sysidx if owner else None))
+        outs = rt.o3_apply(matrices, arrays)
+        new = dict(batch)  # everything else, the pair list first of all, is shared by reference
+        for (name, _, _), out in zip(plan, outs):
+            new[name] = out.reshape(batch[name].shape)
+        new[MATRICES] = matrices
+        return new
+
+    def apply_random_augmentations(self, batch: Dict[str, object]) -> Dict[str, object]:
+        """A new batch with one freshly drawn matrix per system applied to ``positions``, ``cells`` and the targets;
+        ``centers / neighbors / cell_shifts / species / system_indices`` are the input's own tensors, the matrices are
+        under ``"o3_matrices"``. The input is left alone. Advances the step counter on the host: no synchronisation."""
+        plan, _, s, tensors = self._plan(batch)
+        rt._require_cuda(*tensors)
+        matrices = rt.o3_draw(s, self.key, self.counter, self.group, batch["positions"].device)
+        self.counter += 1
+        return self._apply(batch, plan, s, matrices)
+
+    def apply_augmentations(self, batch: Dict[str, object], matrices: torch.Tensor) -> Dict[str, object]:
+        """The same with given ``matrices [S,3,3]`` (``augmentation.py:73-95``; determinant -1: improper). Matrices that
+        are not orthogonal to 1e-4 are refused, which costs one read-back. The step counter does not move."""
+        plan, _, s, tensors = self._plan(batch)
+        matrices = torch.as_tensor(matrices)
+        if matrices.dim() != 3 or tuple(matrices.shape) != (s, 3, 3):
+            raise ValueError(f"matrices must be [{s},3,3], one per system, got {tuple(matrices.shape)}")
+        m64 = matrices.detach().to(torch.float64)
+        err = (m64.transpose(1, 2) @ m64 - torch.eye(3, dtype=torch.float64, device=m64.device)).abs().amax() if s else 0.0
+        if not float(err) <= ORTHOGONALITY_TOLERANCE:  # (a NaN is refused too)
+            raise ValueError(f"matrices are not orthogonal: max |R^T R - I| = {float(err):.3e} > {ORTHOGONALITY_TOLERANCE}")
+        rt._require_cuda(*tensors)
+        return self._apply(batch, plan, s, matrices.to(batch["positions"].device, torch.float32).contiguous())

@@ -5,6 +5,17 @@ Replaces, for the PET / SOAP-BPNN hot path, ``utils/neighbor_lists.py:100-135`` 
 trip per system) and the pickled-blob ``CollateFn`` of ``utils/data/dataset.py:381-445``: the batch is the seven
 plain tensors ``systems_to_batch`` / ``PETBackend.preprocess`` take (``pet/modules/structures.py:20-95``), with atom
 indices offset per system exactly as ``concatenate_structures`` does.
+
+Rotational augmentation (``metatrain_amd/augmentation.py``) keeps the neighbour search out of the training step: a rigid
+O(3) transformation leaves a structure's pair list as it is, so a batch is collated once and kept for all epochs, and every
+step transforms it and builds the graph from the cached pairs::
+
+    batch = collate(systems, cutoff, targets)        # once: the neighbour search
+    augmenter = O3Augmenter({"energy": "scalar", "forces": "vector"}, seed=seed, stream=rank)
+    for epoch in ...:
+        rotated = augmenter.apply_random_augmentations(batch)   # two launches, no read-back
+        graph = graph_of(model, rotated)
+        ...                                          # TrainStep on rotated["energy"], rotated["forces"]
 """
 from typing import Dict, List, Optional, Sequence, Tuple
 

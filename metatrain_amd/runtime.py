@@ -838,6 +838,65 @@ def neighbor_list(positions: torch.Tensor, cell: torch.Tensor, pbc, cutoff: floa
                                cutoff)
 
 
+def o3_draw(n_systems: int, key: int, counter: int, group: str, device) -> torch.Tensor:
+    """``[n_systems,3,3]`` fp32 matrices of O(3) (``pet_o3_draw``): the matrix of system ``s`` is a function of
+    ``(key, counter, s)`` alone. ``group``: ``"O3"`` (Haar rotations, improper with probability 1/2) or ``"inversions"``
+    (+-identity). No synchronisation, no read-back."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise PetHipError(f"metatrain_amd runs on MI355X only: got the device '{device}'. There is no CPU path in this package.")
+    if group not in _lib.PET_O3_GROUPS:
+        raise ValueError(f"unknown transformation group '{group}', expected 'O3' or 'inversions'")
+    out = torch.empty((int(n_systems), 3, 3), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        check(_lib.load().pet_o3_draw(int(key) & (2**64 - 1), int(counter) & (2**64 - 1), _lib.PET_O3_GROUPS[group],
+                                      int(n_systems), _ptr(out), _stream()))
+    return out
+
+
+def o3_apply(matrices: torch.Tensor, arrays) -> List[torch.Tensor]:
+    """Transform ``arrays = [(tensor [rows, ...], kind, system_of_row), ...]`` by ``matrices [S,3,3]`` into fresh tensors of
+    the same shapes (``pet_o3_apply``, eight arrays per launch). ``kind``: ``"vector"`` (trailing dimensions ``[3, P]``
+    flattened or not: ``out[a,p] = sum_b R[a,b] x[b,p]``) or ``"tensor2"`` (``[3, 3, P]``: ``R T R^T`` per property);
+    ``system_of_row``: int32 ``[rows]`` or None (row ``r`` belongs to system ``r``). The inputs are left alone. A NaN anywhere
+    in a vector or tensor makes that whole output vector or tensor NaN."""
+    arrays = list(arrays)
+    _require_cuda(matrices, *[a[0] for a in arrays], *[a[2] for a in arrays if a[2] is not None])
+    if matrices.dim() != 3 or tuple(matrices.shape[1:]) != (3, 3):
+        raise ValueError(f"matrices must be [S,3,3], got {tuple(matrices.shape)}")
+    mats = matrices.detach().to(torch.float32).contiguous()
+    n_sys = int(mats.shape[0])
+    keep, descs, outs = [mats], [], []
+    for src, kind, sor in arrays:
+        if kind not in _lib.PET_O3_KINDS:
+            raise ValueError(f"unknown kind '{kind}', expected 'vector' or 'tensor2'")
+        width = 3 if kind == "vector" else 9
+        rows = int(src.shape[0]) if src.dim() else 0
+        per_row = int(src.shape[1:].numel())
+        if src.dim() < 2 or per_row % width:
+            raise ValueError(f"a {kind} array needs {width} x P values per row, got the shape {tuple(src.shape)}")
+        if src.dtype != torch.float32:
+            raise ValueError(f"the transformation kernels are float32, got {src.dtype}")
+        x = src.detach().contiguous()
+        out = torch.empty_like(x)
+        if sor is not None:
+            if sor.dtype != torch.int32 or sor.numel() != rows:
+                raise ValueError(f"system_of_row must be int32 [{rows}], got {sor.dtype} {tuple(sor.shape)}")
+            sor = sor.contiguous()
+        elif rows > n_sys:
+            raise ValueError(f"{rows} rows for {n_sys} systems and no system_of_row")
+        keep += [x, sor]
+        descs.append(_lib.O3Array(x.data_ptr(), out.data_ptr(), rows, None if sor is None else sor.data_ptr(), per_row // width,
+                                  _lib.PET_O3_KINDS[kind]))
+        outs.append(out)
+    lib = _lib.load()
+    with torch.cuda.device(mats.device):
+        for i in range(0, len(descs), _lib.PET_O3_MAX_ARRAYS):
+            chunk = descs[i:i + _lib.PET_O3_MAX_ARRAYS]
+            check(lib.pet_o3_apply(_ptr(mats), n_sys, len(chunk), (_lib.O3Array * len(chunk))(*chunk), _stream()))
+    return outs
+
+
 def profile(enable: bool, stage: Optional[str] = None) -> None:
     """Bracket every stage (or only ``stage``) of forward/backward with HIP events."""
     lib = _lib.load()

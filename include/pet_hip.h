@@ -452,7 +452,8 @@ int pet_backward_train2_seeded(const pet_model_t* m, const pet_graph_t* g, void*
  * fp32 FMA with fixed summation orders and no float atomics (the same bits run to run).
  * PET_ERR_UNSUPPORTED: an adaptive-cutoff model (the second-order implicit derivative of the cutoff solver is not built)
  * and a graph with a per-layer exchange (pet_graph_set_exchange). A batch without edges and empty systems give zeros.
- * The ZBL term (pet_zbl_*) is not part of it. */
+ * The ZBL term (pet_zbl_*) is not part of it: pet_zbl_hessian_vector is the same product of the pair term, and the two add
+ * (the network's after the scaler's factor, the pair term's as it is). */
 int64_t pet_hvp_workspace_bytes_for(const pet_model_t* m, const pet_graph_t* g);
 int pet_hessian_vector(const pet_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,
                        const float* d_lambda_atomic, const float* d_u, const float* d_u_cell, float* d_hvp_positions,
@@ -510,6 +511,17 @@ int pet_llpr_ensemble(const pet_model_t* m, int64_t F, const float* d_x, int64_t
  *     d_grad_strain [S,3,3] = dE/d(strain) = R^T dE/dR + cell^T dE/dcell formed directly from the edge vectors (may be
  *     NULL; unit weights only: PET_ERR_ARGUMENT together with d_grad_atomic). The pair terms are recomputed: nothing is
  *     kept between the two calls. d_workspace: pet_zbl_workspace_bytes(N, S) bytes, needed for either 3x3 output.
+ *   pet_zbl_hessian_vector: the second derivatives of E_lambda = sum_i lambda_i a_i along (u [N,3], u_cell [S,3,3]), in the
+ *     convention of pet_hessian_vector. With D = R_j - R_i + S . cell_s and D' = u_j - u_i + S . u_cell_s per edge,
+ *       q = D . D',  f = e'(r) / r,  t = f D' + ((e''(r) - f) / r^2) q D                    (the tangent of f D)
+ *       E''(r) = K Zi Zj (phi''/r - 2 phi'/r^2 + 2 phi/r^3),  e'' = 1/2 (E'' + 2 A r + 3 B r^2) for r <= rc, 0 beyond,
+ *       d_hvp_positions [N,3]: (H u)_k = -sum_{row k} (lambda_k + lambda_nbr) t        (row-local: the list is full)
+ *       d_hvp_cells [S,3,3]:   (H u)_ab =  sum_{edges of the system} lambda_i S_a t_b   (may be NULL)
+ *       d_tangent_atomic [N]:  e'_i = sum_{row i} f q = d/d(lambda_i) of the contracted gradient (may be NULL)
+ *     d_lambda_atomic NULL = ones, d_u_cell NULL = zero. e', e'', D', q and t are fp64 (S . u_cell too), rows are summed as in
+ *     the other two launches. An edge from an atom to its own image contributes to the cell block and the tangent only (it
+ *     depends on no position). d_workspace: pet_zbl_workspace_bytes(N, S) bytes, needed for d_hvp_cells only. NULL z, g,
+ *     d_u or d_hvp_positions: PET_ERR_ARGUMENT. Third derivatives are not built.
  * The launches run on the caller's stream without a synchronisation, with one exception: the FIRST launch on a device
  * uploads the table and the radii (two allocations kept until pet_zbl_destroy, two blocking copies that have completed
  * before any thread or stream can see the entry), so it must not sit inside a stream capture. Later ones allocate nothing.
@@ -524,6 +536,9 @@ int64_t pet_zbl_workspace_bytes(int64_t n_nodes, int64_t n_systems);
 int pet_zbl_forward(const pet_zbl_t* z, const pet_graph_t* g, float* d_atomic, void* stream);
 int pet_zbl_backward(const pet_zbl_t* z, const pet_graph_t* g, const float* d_grad_atomic, float* d_grad_positions,
                      float* d_grad_cells, float* d_grad_strain, void* d_workspace, int64_t workspace_bytes, void* stream);
+int pet_zbl_hessian_vector(const pet_zbl_t* z, const pet_graph_t* g, const float* d_lambda_atomic, const float* d_u,
+                           const float* d_u_cell, float* d_hvp_positions, float* d_hvp_cells, float* d_tangent_atomic,
+                           void* d_workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- Rotational augmentation (utils/augmentation.py:O3Augmenter; pet/trainer.py:187-193, 288-303) -------------------------
  * A random element of O(3) per system of a collated batch, drawn and applied on the device. A rigid transformation of

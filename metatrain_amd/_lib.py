@@ -49,7 +49,7 @@ SYMBOLS = [
     "pet_llpr_feature_size", "pet_llpr_features", "pet_llpr_rows", "pet_llpr_covariance_accumulate",
     "pet_llpr_covariance_finalize", "pet_llpr_variance", "pet_llpr_ensemble",
     "pet_zbl_create", "pet_zbl_destroy", "pet_zbl_cutoff", "pet_zbl_pair_table", "pet_zbl_workspace_bytes",
-    "pet_zbl_forward", "pet_zbl_backward",
+    "pet_zbl_forward", "pet_zbl_backward", "pet_zbl_hessian_vector",
     "pet_o3_draw", "pet_o3_apply",
     "pet_profile_enable", "pet_profile_select", "pet_profile_reset", "pet_profile_report", "pet_config_set",
 ]
@@ -248,6 +248,7 @@ def load() -> ctypes.CDLL:
     lib.pet_zbl_workspace_bytes.restype = c_int64
     lib.pet_zbl_forward.argtypes = [P, P, P, P]
     lib.pet_zbl_backward.argtypes = [P, P, P, P, P, P, P, c_int64, P]
+    lib.pet_zbl_hessian_vector.argtypes = [P, P, P, P, P, P, P, P, P, c_int64, P]
     lib.pet_o3_draw.argtypes = [c_uint64, c_uint64, c_int32, c_int64, P, P]
     lib.pet_o3_apply.argtypes = [P, c_int64, c_int32, POINTER(O3Array), P]
     lib.pet_profile_enable.argtypes = [c_int]

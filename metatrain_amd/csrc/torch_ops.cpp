@@ -146,8 +146,7 @@ struct PetHipModule : torch::CustomClassHolder {
 struct EnergyGradFn : torch::autograd::Function<EnergyGradFn> {
     static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, const at::Tensor& grad_atomic,
                                                   const at::Tensor& positions, const at::Tensor& cells,
-                                                  c10::intrusive_ptr<GraphHolder> gh, c10::intrusive_ptr<PetHipModule> mod,
-                                                  bool has_zbl) {
+                                                  c10::intrusive_ptr<GraphHolder> gh, c10::intrusive_ptr<PetHipModule> mod) {
         at::Tensor ga = as_f32(grad_atomic.reshape({-1}));
         at::Tensor gpos = at::empty({gh->n_nodes, 3}, ga.options());
         at::Tensor gcell = at::empty({gh->n_systems, 3, 3}, ga.options());
@@ -157,7 +156,6 @@ struct EnergyGradFn : torch::autograd::Function<EnergyGradFn> {
         ctx->save_for_backward({grad_atomic});
         ctx->saved_data["graph"] = gh;
         ctx->saved_data["module"] = mod;
-        ctx->saved_data["has_zbl"] = has_zbl;
         ctx->saved_data["pos_dtype"] = (int64_t)positions.scalar_type();
         ctx->saved_data["cell_dtype"] = (int64_t)cells.scalar_type();
         return {gpos.to(positions.scalar_type()), gcell.to(cells.scalar_type())};
@@ -220,8 +218,6 @@ struct HvpFn : torch::autograd::Function<HvpFn> {
 torch::autograd::variable_list EnergyGradFn::backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list go) {
     auto gh = ctx->saved_data["graph"].toCustomClass<GraphHolder>();
     auto mod = ctx->saved_data["module"].toCustomClass<PetHipModule>();
-    TORCH_CHECK(!ctx->saved_data["has_zbl"].toBool(),
-                "pet_hip: second derivatives of a model with a ZBL term are not built (the pair term's Hessian)");
     const at::Tensor grad_atomic = ctx->get_saved_variables()[0];
     at::Tensor lam = as_f32(grad_atomic.reshape({-1}));
     const auto pd = (at::ScalarType)ctx->saved_data["pos_dtype"].toInt();
@@ -238,6 +234,92 @@ torch::autograd::variable_list EnergyGradFn::backward(torch::autograd::AutogradC
     return {out[2].reshape(grad_atomic.sizes()).to(grad_atomic.scalar_type()), out[0].to(pd), out[1].to(cd), at::Tensor(), at::Tensor(),
             at::Tensor()};
 }
+
+// ---- the same two nodes for the ZBL column: pet_zbl_backward as a differentiable function of (lambda = the column's
+// grad_atomic, positions, cells), whose backward is one pet_zbl_hessian_vector call, and that product as a differentiable
+// (linear, self-adjoint) function of its direction. The column is added after the scaler, so its weights are not the
+// network column's: the two terms keep separate nodes and their results add. Third order is not part of the graph.
+static std::vector<at::Tensor> zbl_hessian_vector(const c10::intrusive_ptr<ZblTable>& zbl, const c10::intrusive_ptr<GraphHolder>& gh,
+                                                  const at::Tensor& lam, const at::Tensor& u_, const at::Tensor& ucell_) {
+    auto f32 = lam.options();
+    at::Tensor u = u_.defined() ? as_f32(u_).reshape({gh->n_nodes, 3}) : at::zeros({gh->n_nodes, 3}, f32);
+    at::Tensor ucell;
+    if (ucell_.defined()) ucell = as_f32(ucell_).reshape({gh->n_systems, 3, 3});
+    at::Tensor hp = at::empty({gh->n_nodes, 3}, f32), hc = at::empty({gh->n_systems, 3, 3}, f32), tan = at::empty({gh->n_nodes}, f32);
+    at::Tensor ws = at::empty({std::max<int64_t>(pet_zbl_workspace_bytes(gh->n_nodes, gh->n_systems), 1)}, gh->fwd_ws.options());
+    check(pet_zbl_hessian_vector(zbl->z, gh->g, lam.data_ptr<float>(), u.data_ptr<float>(),
+                                 ucell.defined() ? ucell.data_ptr<float>() : nullptr, hp.data_ptr<float>(), hc.data_ptr<float>(),
+                                 tan.data_ptr<float>(), ws.data_ptr(), ws.numel(), stream_of(lam)),
+          "pet_zbl_hessian_vector");
+    return {hp, hc, tan};
+}
+
+struct ZblHvpFn : torch::autograd::Function<ZblHvpFn> {
+    static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, const at::Tensor& u,
+                                                  const at::Tensor& ucell, const at::Tensor& lam,
+                                                  c10::intrusive_ptr<GraphHolder> gh, c10::intrusive_ptr<ZblTable> zbl) {
+        ctx->set_materialize_grads(false);
+        ctx->saved_data["graph"] = gh;
+        ctx->saved_data["zbl"] = zbl;
+        ctx->saved_data["lam"] = lam;
+        auto out = zbl_hessian_vector(zbl, gh, lam, u, ucell);
+        return {out[0].to(u.scalar_type()), out[1].to(ucell.scalar_type()), out[2]};
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
+                                                   torch::autograd::variable_list go) {
+        auto gh = ctx->saved_data["graph"].toCustomClass<GraphHolder>();
+        auto zbl = ctx->saved_data["zbl"].toCustomClass<ZblTable>();
+        const at::Tensor lam = ctx->saved_data["lam"].toTensor();
+        TORCH_CHECK(!go[2].defined(), "pet_hip: derivatives of the ZBL tangent energies w.r.t. the direction are not built "
+                                      "through the TorchScript op");
+        at::Tensor gp = go[0].defined() ? go[0] : at::zeros({gh->n_nodes, 3}, lam.options());
+        at::Tensor gc = go[1].defined() ? go[1] : at::zeros({gh->n_systems, 3, 3}, lam.options());
+        if (torch::GradMode::is_enabled() && (gp.requires_grad() || gc.requires_grad())) {
+            auto out = ZblHvpFn::apply(gp, gc, lam, gh, zbl);
+            return {out[0], out[1], at::Tensor(), at::Tensor(), at::Tensor()};
+        }
+        auto out = zbl_hessian_vector(zbl, gh, lam, gp, gc);
+        return {out[0].to(gp.scalar_type()), out[1].to(gc.scalar_type()), at::Tensor(), at::Tensor(), at::Tensor()};
+    }
+};
+
+struct ZblGradFn : torch::autograd::Function<ZblGradFn> {
+    static torch::autograd::variable_list forward(torch::autograd::AutogradContext* ctx, const at::Tensor& grad_atomic,
+                                                  const at::Tensor& positions, const at::Tensor& cells,
+                                                  c10::intrusive_ptr<GraphHolder> gh, c10::intrusive_ptr<ZblTable> zbl) {
+        at::Tensor gz = as_f32(grad_atomic.reshape({-1}));
+        at::Tensor zpos = at::empty({gh->n_nodes, 3}, gz.options()), zcell = at::empty({gh->n_systems, 3, 3}, gz.options());
+        at::Tensor zws = at::empty({pet_zbl_workspace_bytes(gh->n_nodes, gh->n_systems)}, gh->fwd_ws.options());
+        check(pet_zbl_backward(zbl->z, gh->g, gz.data_ptr<float>(), zpos.data_ptr<float>(), zcell.data_ptr<float>(), nullptr,
+                               zws.data_ptr(), zws.numel(), stream_of(gz)),
+              "pet_zbl_backward");
+        ctx->save_for_backward({grad_atomic});
+        ctx->saved_data["graph"] = gh;
+        ctx->saved_data["zbl"] = zbl;
+        ctx->saved_data["pos_dtype"] = (int64_t)positions.scalar_type();
+        ctx->saved_data["cell_dtype"] = (int64_t)cells.scalar_type();
+        return {zpos, zcell};
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
+                                                   torch::autograd::variable_list go) {
+        auto gh = ctx->saved_data["graph"].toCustomClass<GraphHolder>();
+        auto zbl = ctx->saved_data["zbl"].toCustomClass<ZblTable>();
+        const at::Tensor grad_atomic = ctx->get_saved_variables()[0];
+        at::Tensor lam = as_f32(grad_atomic.reshape({-1}));
+        const auto pd = (at::ScalarType)ctx->saved_data["pos_dtype"].toInt();
+        const auto cd = (at::ScalarType)ctx->saved_data["cell_dtype"].toInt();
+        at::Tensor u = go[0], ucell = go.size() > 1 ? go[1] : at::Tensor();
+        std::vector<at::Tensor> out;
+        if (torch::GradMode::is_enabled() && ((u.defined() && u.requires_grad()) || (ucell.defined() && ucell.requires_grad()))) {
+            if (!u.defined()) u = at::zeros({gh->n_nodes, 3}, lam.options());
+            if (!ucell.defined()) ucell = at::zeros({gh->n_systems, 3, 3}, lam.options());
+            out = ZblHvpFn::apply(u, ucell, lam, gh, zbl);
+        } else
+            out = zbl_hessian_vector(zbl, gh, lam, u, ucell);
+        return {out[2].reshape(grad_atomic.sizes()).to(grad_atomic.scalar_type()), out[0].to(pd), out[1].to(cd), at::Tensor(),
+                at::Tensor()};
+    }
+};
 
 struct EnergyFn : torch::autograd::Function<EnergyFn> {
     // returns {atomic [N, 1]} or, with a ZBL table, {atomic [N, 1], ZBL atomic [N, 1]} (pet_zbl_forward on the same graph)
@@ -314,7 +396,7 @@ struct EnergyFn : torch::autograd::Function<EnergyFn> {
                             (ga.requires_grad() || saved[0].requires_grad() || saved[1].requires_grad());
         at::Tensor gpos, gcell;
         if (second) {
-            auto out = EnergyGradFn::apply(ga, saved[0], saved[1], gh, mod, has_zbl);
+            auto out = EnergyGradFn::apply(ga, saved[0], saved[1], gh, mod);
             gpos = out[0].to(at::kFloat);
             gcell = out[1].to(at::kFloat);
             ga = as_f32(ga.reshape({-1}));
@@ -327,14 +409,22 @@ struct EnergyFn : torch::autograd::Function<EnergyFn> {
                   "pet_backward");
         }
         if (has_zbl && grad_out[1].defined()) {  // + the ZBL term's dL/dR and dL/dcell for the weights it received
-            TORCH_CHECK(!grad_out[1].requires_grad(), "pet_hip: double backward through the ZBL term is not built");
             auto zbl = ctx->saved_data["zbl"].toCustomClass<ZblTable>();
-            at::Tensor gz = as_f32(grad_out[1].reshape({-1}));
-            at::Tensor zpos = at::empty({gh->n_nodes, 3}, ga.options()), zcell = at::empty({gh->n_systems, 3, 3}, ga.options());
-            at::Tensor zws = at::empty({pet_zbl_workspace_bytes(gh->n_nodes, gh->n_systems)}, gh->fwd_ws.options());
-            check(pet_zbl_backward(zbl->z, gh->g, gz.data_ptr<float>(), zpos.data_ptr<float>(), zcell.data_ptr<float>(), nullptr,
-                                   zws.data_ptr(), zws.numel(), stream_of(ga)),
-                  "pet_zbl_backward");
+            at::Tensor zpos, zcell;
+            if (torch::GradMode::is_enabled() &&
+                (grad_out[1].requires_grad() || saved[0].requires_grad() || saved[1].requires_grad())) {
+                auto out = ZblGradFn::apply(grad_out[1], saved[0], saved[1], gh, zbl);  // differentiable, as the network's
+                zpos = out[0];
+                zcell = out[1];
+            } else {
+                at::Tensor gz = as_f32(grad_out[1].reshape({-1}));
+                zpos = at::empty({gh->n_nodes, 3}, ga.options());
+                zcell = at::empty({gh->n_systems, 3, 3}, ga.options());
+                at::Tensor zws = at::empty({pet_zbl_workspace_bytes(gh->n_nodes, gh->n_systems)}, gh->fwd_ws.options());
+                check(pet_zbl_backward(zbl->z, gh->g, gz.data_ptr<float>(), zpos.data_ptr<float>(), zcell.data_ptr<float>(),
+                                       nullptr, zws.data_ptr(), zws.numel(), stream_of(ga)),
+                      "pet_zbl_backward");
+            }
             gpos = gpos + zpos;   // (out of place: gpos may be the output of the differentiable gradient node)
             gcell = gcell + zcell;
         }

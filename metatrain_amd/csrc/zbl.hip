@@ -5,6 +5,7 @@
 //   dL/dR_k  = -sum_{row k} (w_k + w_nbr) e'(r) D / r        (row-local: the list is full)
 //   dL/dh_ab =  sum_{edges of the system} w_i e'(r) S_a D_b / r
 //   dE/deps_ab = sum_{edges of the system} e'(r) D_a D_b / r  (unit weights)
+// and, along a direction (u, u_cell), the second derivatives of sum_i w_i a_i (k_zbl_hvp, formulas there).
 // Layout. One wave (a 64-thread workgroup) owns ZR consecutive atoms, i.e. one contiguous range of CSR edges. It walks the
 // range 64 edges at a time; a lane only tests r <= rad[sp] + rad[sp_nbr] (radii in LDS) and the hits are compacted, in edge
 // order, into an LDS queue. The pair term runs when 64 hits are queued (and once at the end), so the exponentials run on
@@ -175,6 +176,154 @@ __global__ __launch_bounds__(64) void k_zbl_rows(const int* __restrict__ rowptr,
             if (strain_part) strain_part[(int64_t)a0 * 9 + i] = (float)s_acc[(i / 9) * K + 12 + i % 9];
         }
     }
+}
+
+// e'(r) and e''(r) of the same pair: E'' = K Zi Zj (phi''/r - 2 phi'/r^2 + 2 phi/r^3), e'' = 1/2 (E'' + 2 A r + 3 B r^2)
+// inside rc, both 0 beyond (A, B, C make e, e' and e'' vanish at rc)
+__device__ inline void zbl_pair_d2(const double* __restrict__ tb, double r, double& de, double& d2e) {
+    const double rc = tb[0], inva = tb[1], kzz = tb[2], A = tb[3], B = tb[4];
+    double phi = 0.0, dphi = 0.0, d2phi = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const double da = ZBL_D[k] * inva;
+        const double t = ZBL_C[k] * exp(-da * r);
+        phi += t;
+        dphi -= da * t;
+        d2phi += da * da * t;
+    }
+    const double ir = 1.0 / r, r2 = r * r;
+    const double dE = kzz * ir * (dphi - phi * ir);
+    const double d2E = kzz * ir * (d2phi - 2.0 * ir * dphi + 2.0 * phi * ir * ir);
+    const bool in = r <= rc;
+    de = in ? 0.5 * (dE + A * r2 + B * r2 * r) : 0.0;
+    d2e = in ? 0.5 * (d2E + 2.0 * A * r + 3.0 * B * r2) : 0.0;
+}
+
+// Hessian-vector mode of the row walk: the same ranges, test, queue and row sums as k_zbl_rows. Along the direction
+// (u [N,3], u_cell [S,3,3] or nullptr = zero) an edge has D' = u_j - u_i + S . u_cell_s, q = D . D', f = e'/r and the tangent of
+// f D, t = f D' + ((e'' - f) / r^2) q D. Per atom: hvp [N,3] = -sum_row (w_i + w_nbr) t, the partial cell_part [N,9] =
+// sum_row w_i S_a t_b of the per-system 3x3 sum (when given) and tangent [N] = sum_row f q (when given).
+// An edge from an atom to its own image depends on no position (D = S . cell): its position term is left out instead of
+// being cancelled against the opposite image's, so such rows give exact zeros whatever order their edges come in.
+constexpr int ZH = 13;  // accumulators per atom: H u (3) | cell (9) | tangent (1)
+
+__global__ __launch_bounds__(64) void k_zbl_hvp(const int* __restrict__ rowptr, const int* __restrict__ ctr,
+                                                const int* __restrict__ nbr, const int* __restrict__ shift,
+                                                const int* __restrict__ sp, const int* __restrict__ sp_nbr,
+                                                const int* __restrict__ sys, const float4* __restrict__ geo,
+                                                const float* __restrict__ rad, const double* __restrict__ table, int T,
+                                                int N, const float* __restrict__ w, const float* __restrict__ u,
+                                                const float* __restrict__ u_cell, float* __restrict__ hvp,
+                                                float* __restrict__ cell_part, float* __restrict__ tangent) {
+    constexpr int K = ZH;
+    constexpr int V = 9;  // (w_i + w_nbr, w_i, t[3], S[3], f q)
+    __shared__ float s_rad[MAX_SPECIES];
+    __shared__ int s_sp[ZR];
+    __shared__ int s_q[ZQ];
+    __shared__ int s_row[64];
+    __shared__ double s_val[64 * V];
+    __shared__ double s_acc[ZR * K];
+    const int lane = threadIdx.x;
+    const int a0 = blockIdx.x * ZR, a1 = min(N, a0 + ZR);
+    for (int t = lane; t < T; t += 64) s_rad[t] = rad[t];
+    if (lane < a1 - a0) s_sp[lane] = sp[a0 + lane];
+    for (int i = lane; i < ZR * K; i += 64) s_acc[i] = 0.0;
+    const int p0 = rowptr[a0], p1 = rowptr[a1];
+    __syncthreads();
+
+    auto flush = [&](int n) {
+        if (lane < n) {
+            const int p = s_q[lane];
+            const float4 g = geo[p];
+            const int i = ctr[p], j = nbr[p];
+            const int ti = s_sp[i - a0], tj = sp_nbr[p];
+            double de, d2e;
+            const double r = (double)g.w;
+            zbl_pair_d2(table + ((int64_t)ti * T + tj) * 6, r, de, d2e);
+            const double d[3] = {(double)g.x, (double)g.y, (double)g.z};
+            const double sh[3] = {(double)shift[3 * (int64_t)p], (double)shift[3 * (int64_t)p + 1],
+                                  (double)shift[3 * (int64_t)p + 2]};
+            double dp[3];
+#pragma unroll
+            for (int b = 0; b < 3; b++) dp[b] = (double)u[3 * (int64_t)j + b] - (double)u[3 * (int64_t)i + b];
+            if (u_cell) {
+                const float* uc = u_cell + 9 * (int64_t)sys[i];
+#pragma unroll
+                for (int b = 0; b < 3; b++)
+                    dp[b] += sh[0] * (double)uc[b] + sh[1] * (double)uc[3 + b] + sh[2] * (double)uc[6 + b];
+            }
+            const double q = d[0] * dp[0] + d[1] * dp[1] + d[2] * dp[2];
+            const double f = de / r, h = (d2e - f) / (r * r) * q;
+            const double wi = w ? (double)w[i] : 1.0, wj = w ? (double)w[j] : 1.0;
+            s_row[lane] = i - a0;
+            double* v = s_val + lane * V;
+            v[0] = j == i ? 0.0 : wi + wj;
+            v[1] = wi;
+#pragma unroll
+            for (int b = 0; b < 3; b++) {
+                v[2 + b] = f * dp[b] + h * d[b];
+                v[5 + b] = sh[b];
+            }
+            v[8] = f * q;
+        }
+        __syncthreads();
+        if (lane < n) {
+            const int row = s_row[lane];
+            if (lane == 0 || s_row[lane - 1] != row) {  // this lane holds the row's first queued term
+                double acc[K];
+#pragma unroll
+                for (int k = 0; k < K; k++) acc[k] = s_acc[row * K + k];
+                for (int j = lane; j < n && s_row[j] == row; j++) {
+                    const double* v = s_val + j * V;
+#pragma unroll
+                    for (int a = 0; a < 3; a++) {
+                        {   // the product rounded on its own, as in the reverse pass: opposite terms of equal weight cancel
+#pragma clang fp contract(off)
+                            const double prod = v[0] * v[2 + a];
+                            acc[a] += prod;
+                        }
+#pragma unroll
+                        for (int b = 0; b < 3; b++) acc[3 + 3 * a + b] += v[1] * v[5 + a] * v[2 + b];
+                    }
+                    acc[12] += v[8];
+                }
+#pragma unroll
+                for (int k = 0; k < K; k++) s_acc[row * K + k] = acc[k];
+            }
+        }
+        __syncthreads();
+    };
+
+    int nq = 0;  // queued hits (the same number in every lane)
+    for (int base = p0; base < p1; base += 64) {
+        const int p = base + lane;
+        bool hit = false;
+        if (p < p1) {
+            const int tj = sp_nbr[p], ti = s_sp[ctr[p] - a0];
+            if (ti < T && tj < T) hit = geo[p].w <= (s_rad[ti] + s_rad[tj]) * 1.000001f;
+        }
+        const unsigned long long m = __ballot(hit);
+        if (m == 0) continue;
+        if (hit) s_q[nq + __popcll(m & ((1ull << lane) - 1ull))] = p;
+        nq += __popcll(m);
+        __syncthreads();
+        if (nq >= 64) {
+            flush(64);
+            const int rem = nq - 64;
+            const int keep = lane < rem ? s_q[64 + lane] : 0;
+            __syncthreads();
+            if (lane < rem) s_q[lane] = keep;
+            nq = rem;
+            __syncthreads();
+        }
+    }
+    if (nq > 0) flush(nq);
+
+    const int na = a1 - a0;
+    for (int i = lane; i < na * 3; i += 64) hvp[(int64_t)a0 * 3 + i] = -(float)s_acc[(i / 3) * K + i % 3];
+    if (cell_part)
+        for (int i = lane; i < na * 9; i += 64) cell_part[(int64_t)a0 * 9 + i] = (float)s_acc[(i / 9) * K + 3 + i % 9];
+    if (tangent && lane < na) tangent[a0 + lane] = (float)s_acc[lane * K + 12];
 }
 
 // stage 2: out[s][c] = sum over the atoms of system s of part[atom][c]. One workgroup per (system, which of the two sums);
@@ -411,6 +560,40 @@ int pet_zbl_backward(const pet_zbl_t* z, const pet_graph_t* pg, const float* d_g
                                                  z->n_types, (int)N, d_grad_atomic, d_grad_positions, cell_part, strain_part);
     if ((cell_part || strain_part) && S > 0)
         k_zbl_sys<<<dim3((unsigned)S, 2), 256, 0, st>>>(cell_part, strain_part, g.sys, (int)N, d_grad_cells, d_grad_strain);
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
+}
+
+int pet_zbl_hessian_vector(const pet_zbl_t* z, const pet_graph_t* pg, const float* d_lambda_atomic, const float* d_u,
+                           const float* d_u_cell, float* d_hvp_positions, float* d_hvp_cells, float* d_tangent_atomic,
+                           void* d_workspace, int64_t workspace_bytes, void* stream) {
+    if (int rc = zbl_check_graph(z, pg)) return rc;
+    PET_REQUIRE(d_u && d_hvp_positions, PET_ERR_ARGUMENT, "null argument");
+    const Graph& g = pg->g;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t N = g.n_nodes, S = g.n_systems;
+    if (d_hvp_cells && S > 0) PET_HIP_CHECK(hipMemsetAsync(d_hvp_cells, 0, (size_t)S * 9 * sizeof(float), st));
+    if (N == 0) return PET_OK;
+    if (g.n_edges == 0) {
+        PET_HIP_CHECK(hipMemsetAsync(d_hvp_positions, 0, (size_t)N * 3 * sizeof(float), st));
+        if (d_tangent_atomic) PET_HIP_CHECK(hipMemsetAsync(d_tangent_atomic, 0, (size_t)N * sizeof(float), st));
+        return PET_OK;
+    }
+    float* cell_part = nullptr;
+    if (d_hvp_cells) {
+        PET_REQUIRE(d_workspace && workspace_bytes >= pet_zbl_workspace_bytes(N, S), PET_ERR_ARGUMENT,
+                    "ZBL workspace too small (pet_zbl_workspace_bytes)");
+        Carver c(d_workspace);
+        cell_part = c.take<float>((size_t)N * 9);
+    }
+    pet_zbl::Dev d;
+    if (int rc = zbl_device(z, d)) return rc;
+    ProfScope ps("zbl_hvp", st, 0.0, zbl_bytes(g));
+    k_zbl_hvp<<<cdiv(N, ZR), 64, 0, st>>>(g.rowptr, g.ctr, g.nbr, g.shift, g.sp, g.sp_nbr, g.sys, g.geo, d.rad, d.table,
+                                          z->n_types, (int)N, d_lambda_atomic, d_u, d_u_cell, d_hvp_positions, cell_part,
+                                          d_tangent_atomic);
+    if (cell_part && S > 0)
+        k_zbl_sys<<<dim3((unsigned)S, 1), 256, 0, st>>>(cell_part, nullptr, g.sys, (int)N, d_hvp_cells, nullptr);
     PET_HIP_CHECK(hipGetLastError());
     return PET_OK;
 }

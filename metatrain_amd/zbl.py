@@ -2,9 +2,9 @@
 
 The reference subtracts the ZBL energy and its gradients from the targets before training (``utils/additive/remove.py``),
 trains the network on the remainder and adds the ZBL term back, after the scaler, at evaluation (``pet/model.py:616-660``).
-:class:`ZBLHip` is that model: per-atom energies, ``dL/dR``, ``dL/dcell`` and the strain gradient from the kernels of
-``csrc/zbl.hip`` on a :class:`~metatrain_amd.runtime.HipGraph`, :meth:`ZBLHip.remove_from_targets` for training and the
-reference's two checkpoint buffers. eV and Angstrom only, like the reference.
+:class:`ZBLHip` is that model: per-atom energies, ``dL/dR``, ``dL/dcell``, the strain gradient and Hessian-vector
+products from the kernels of ``csrc/zbl.hip`` on a :class:`~metatrain_amd.runtime.HipGraph`,
+:meth:`ZBLHip.remove_from_targets` for training and the reference's two checkpoint buffers. eV and Angstrom only, like the reference.
 """
 import logging
 from ctypes import byref, c_double, c_int32, c_void_p
@@ -208,6 +208,29 @@ class ZBLHip:
                                         rt._ptr(gstrain), rt._ptr(ws), 0 if ws is None else ws.numel(), rt._stream()))
         out = [gpos] + ([gcell] if want_cell_grad else []) + ([gstrain] if want_strain else [])
         return out[0] if len(out) == 1 else tuple(out)
+
+    def hessian_vector_product(self, graph: rt.HipGraph, u: torch.Tensor, u_cell: Optional[torch.Tensor] = None,
+                               weights: Optional[torch.Tensor] = None, want_cells: bool = False, want_tangent: bool = False):
+        """Hessian-vector product of the ZBL term (``pet_zbl_hessian_vector``), in the convention of
+        :func:`metatrain_amd.runtime.hessian_vector_product`, to which it adds: with ``a'_i`` the derivative of the per-atom
+        ZBL energies along ``(dR, dcell) = (u [N,3], u_cell [S,3,3])``, returns ``grad_R sum_i w_i a'_i`` ``[N,3]`` -- ``H u``
+        of the ZBL energy for ``weights = None`` (ones) -- then, if asked for, ``grad_cell`` of the same ``[S,3,3]`` and the
+        tangents ``a'_i [N]``. The pair terms are recomputed: no forward is needed."""
+        rt._require_cuda(u)
+        dev = u.device
+        n, s = graph.n_nodes, graph.n_systems
+        uu = u.detach().to(torch.float32).reshape(n, 3).contiguous()
+        uc = None if u_cell is None else u_cell.detach().to(dev, torch.float32).reshape(s, 3, 3).contiguous()
+        w = None if weights is None else weights.detach().to(dev, torch.float32).reshape(n).contiguous()
+        hp = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        hc = torch.empty((s, 3, 3), dtype=torch.float32, device=dev) if want_cells else None
+        tan = torch.empty(n, dtype=torch.float32, device=dev) if want_tangent else None
+        ws = torch.empty(int(self.lib.pet_zbl_workspace_bytes(n, s)), dtype=torch.uint8, device=dev) if want_cells else None
+        check(self.lib.pet_zbl_hessian_vector(self._handle, graph.handle, rt._ptr(w), rt._ptr(uu), rt._ptr(uc), rt._ptr(hp),
+                                              rt._ptr(hc), rt._ptr(tan), rt._ptr(ws), 0 if ws is None else ws.numel(),
+                                              rt._stream()))
+        out = (hp,) + ((hc,) if want_cells else ()) + ((tan,) if want_tangent else ())
+        return out[0] if len(out) == 1 else out
 
     def energies(self, graph: rt.HipGraph, atomic: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Per-structure ZBL energies ``[S]`` (fixed-order sums, ``pet_sum_over_atoms``)."""

@@ -12,10 +12,17 @@ Within one process the arms alternate after a warm-up, each timed by a host cloc
 what counts is the ratio of the medians in the same run. There is no speed bar: the size-generic pass is correctness-first.
 ``--accuracy-log`` takes the output of ``pytest -s tests/test_gpu_hvp.py`` and records its ``(case, y, relmax)`` lines.
 
+``--zbl`` measures the ZBL arm instead (``profiles/zbl_hvp_bench.json``): on the same box, default model, ``pet_hessian_vector``
+alone against ``pet_hessian_vector`` + ``pet_zbl_hessian_vector`` on the same graph, what ``hessian(..., zbl=table)`` and the
+exported op of a ``zbl: true`` model run per product; ``--accuracy-log`` then takes ``pytest -s tests/test_gpu_zbl_hvp.py``, and
+``--bench-log`` a file of ``bench.py`` result lines, each prefixed ``parent `` or ``this `` (the inference step of the two
+commits, alternating), whose medians are recorded beside it.
+
 The driver itself does not touch the GPU: every model is a child process under its own time limit, and the first failure
 ends the run.
 
   python tools/gpu_hvp_bench.py --out profiles/hvp_bench.json [--accuracy-log FILE]
+  python tools/gpu_hvp_bench.py --zbl [--accuracy-log FILE] [--bench-log FILE]
 """
 import argparse
 import json
@@ -69,6 +76,16 @@ def worker(args):
         tr.backward_train2(ones, None, u)
 
     arms = {"hvp": hvp, "fd": fd, "train2": train2}
+    if args.zbl:
+        from metatrain_amd.zbl import ZBLHip
+
+        table = ZBLHip(types)
+        touched = int((table.forward(graph) != 0).sum())
+
+        def hvp_zbl():
+            rt.hessian_vector_product(model, graph, u, workspace=ws) + table.hessian_vector_product(graph, u)
+
+        arms = {"hvp": hvp, "hvp_zbl": hvp_zbl}
     for _ in range(args.warmup):
         for fn in arms.values():
             fn()
@@ -81,6 +98,10 @@ def worker(args):
             torch.cuda.synchronize()
             times[k].append((time.perf_counter() - t0) * 1e3)
     med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    if args.zbl:
+        print(json.dumps({"atoms": n, "graph_edges": graph.n_edges, "atoms_with_a_zbl_energy": touched, "ms_median": med,
+                          "hvp_zbl_over_hvp": med["hvp_zbl"] / med["hvp"], "ms_all": times}))
+        return
     print(json.dumps({"atoms": n, "graph_edges": graph.n_edges, "hvp_workspace_bytes": int(ws.numel()),
                       "ms_median": med, "hvp_over_fd": med["hvp"] / med["fd"], "hvp_over_train2": med["hvp"] / med["train2"],
                       "ms_all": times}))
@@ -111,6 +132,21 @@ def accuracy(path):
     return out
 
 
+def bench_medians(path):
+    """Medians of the ``parent <json>`` / ``this <json>`` lines of alternating ``bench.py`` runs."""
+    runs = {"parent": [], "this": []}
+    for ln in open(path):
+        who, _, rest = ln.partition(" ")
+        if who in runs and rest.startswith("{"):
+            runs[who].append(json.loads(rest))
+    out = {}
+    for who, rows in runs.items():
+        keys = [k for k, v in rows[0].items() if isinstance(v, (int, float)) and not isinstance(v, bool)] if rows else []
+        out[who] = {"runs": len(rows), "median": {k: sorted(r[k] for r in rows)[len(rows) // 2] for k in keys},
+                    "all": rows}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worker", choices=list(MODELS), default=None)
@@ -118,18 +154,28 @@ def main():
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--accuracy-log", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "hvp_bench.json"))
+    ap.add_argument("--zbl", action="store_true", help="the ZBL arm: pet_hessian_vector with and without the pair term's")
+    ap.add_argument("--bench-log", default=None)
+    ap.add_argument("--out", default=None)
     ap.add_argument("--limit", type=int, default=240, help="seconds allowed to each GPU step")
     args = ap.parse_args()
     if args.worker:
         return worker(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "zbl_hvp_bench.json" if args.zbl else "hvp_bench.json")
     me = [sys.executable, os.path.abspath(__file__)]
     common = ["--atoms", str(args.atoms), "--rounds", str(args.rounds), "--warmup", str(args.warmup)]
     result = {"workload": "one Hessian-vector product on one periodic box, arms alternating in one process (ms, host clock); "
                           "train2 is THIS build's pet_backward_train2 (its gradient has the bits of the build before the "
                           "Hessian-vector mode: tests/golden/gen_train_parent_digest.json)"}
-    for name in MODELS:
-        result[name] = run(me + ["--worker", name] + common, args.limit)
+    if args.zbl:
+        result = {"workload": "one Hessian-vector product on one periodic box, default model, without and with the ZBL pair "
+                              "term's product on the same graph, arms alternating in one process (ms, host clock)",
+                  "default": run(me + ["--worker", "default", "--zbl"] + common, args.limit)}
+        if args.bench_log:
+            result["bench_py_gpus1_steps20_warmup5"] = bench_medians(args.bench_log)
+    else:
+        for name in MODELS:
+            result[name] = run(me + ["--worker", name] + common, args.limit)
     if args.accuracy_log:
         result["accuracy_vs_fp64_oracle"] = accuracy(args.accuracy_log)
     line = json.dumps(result)

@@ -576,6 +576,59 @@ typedef struct pet_o3_array {
 int pet_o3_draw(uint64_t key, uint64_t counter, int32_t group, int64_t n_systems, float* d_matrices, void* stream);
 int pet_o3_apply(const float* d_matrices, int64_t n_systems, int32_t n_arrays, const pet_o3_array_t* h_arrays, void* stream);
 
+/* ---- Composition baselines and target scales (composition/_base_composition.py; scaler/_base_scaler.py) ----------------------
+ * What the reference fits on the training set before the first optimizer step, from the plain tensors of a collated batch:
+ * species [N] i32 (atomic numbers), system_indices [N] i32 (non-decreasing, in [0, n_systems)) and targets. No model or graph
+ * handle: fitting happens before a model exists. Atomic numbers go through d_type_index [max_z + 1] i32 (-1: not a model
+ * type). Targets are fp32 or fp64 (`*_is_f64`), rows [n_values] with n_values = components x properties, properties innermost.
+ *   pet_species_counts replaces _base_composition.py:_compute_X_per_structure: d_counts [S, T] i32, the atoms of every type in
+ *     every system, and d_n_atoms [S] i32. One wave per system.
+ *   pet_composition_accumulate replaces _base_composition.py:306-322. per_atom = 0, Y [S, n_values]: XTX [T, T] += sum_s c_s c_s^T
+ *     (int64, exact), XTY [T, n_values] += sum_s c_s y_s^T (fp64; a NaN spreads as in tensordot). per_atom = 1, Y [N, n_values]:
+ *     the diagonal of XTX += the types' atom counts, XTY[t] += sum of y_i over the atoms of type t (a NaN stays inside its type).
+ *   pet_target_moments replaces _base_scaler.py:_compute_N_and_Y2 (:308-370) on the residual r that utils/additive/remove.py,
+ *     utils/per_atom.py:average_by_num_atoms and (for n_out > 1) the scaler's own remove=True would have built; no residual
+ *     tensor is materialised. per_atom = 0: r = (y - sum_t c_t w[t,:]) / n_atoms (divide_by_n_atoms = 0: the target is one of
+ *     per_structure_targets), one output row. per_atom = 1: r = y_i - w[type_i,:], one output row per type. r /= d_scale[row]
+ *     (fp64, NULL: 1). d_weights [T, n_values] fp64 or NULL (no baseline). n_out = 1: d_n [rows] i64 += number of non-NaN
+ *     entries, d_y2 [rows] fp64 += sum r^2 (accumulate, :372-429). n_out = n_properties: the same per property, [rows, n_out],
+ *     summed over rows and components (accumulate_per_property, :459-491).
+ *   pet_targets_remove replaces the per-step remove_additive + scaler(remove=True, per-target scales): arrays[0] is the target,
+ *     per_atom = 0: out[s,p] = (y[s,p] - sum_t counts[s,t] w[t,p]) / scale[0]; per_atom = 1: out[i,p] = (y[i,p] - w[type_i,p]) /
+ *     scale[type_i]. arrays[1..] (per_atom = 0 only) are its gradient arrays (dE/dR [N,3], strain gradients [S,3,3]): divided by
+ *     scale[0] only (_base_scaler.py:726-751; the baseline does not depend on positions). One launch, out of place, fp64
+ *     arithmetic, rounded to fp32 once on the store. NaN stays NaN.
+ * Determinism: every sum is over chunks of 256 rows in ascending order (stage one, partials in the workspace), then over the
+ * chunks in ascending order (stage two), in fp64 or exact integers; no floating-point atomics; accumulators are += across
+ * calls. Workspace: pet_baseline_workspace_bytes(rows, T, n_values) bytes.
+ * *d_error (i32, zeroed by the caller) |= 1 when an atom's species is no model type (the host raises, _base_composition.py:
+ * 247-254; such an atom is counted nowhere and its row of pet_targets_remove comes out NaN), |= 2 when system_indices leave
+ * [0, n_systems). PET_ERR_ARGUMENT: null or negative arguments, n_out not dividing n_values, a workspace too small, dst == src. */
+#define PET_TARGET_MAX_ARRAYS 4
+typedef struct pet_target_array {
+    const void* src;  /* device, rows x width, fp32 or fp64 */
+    float* dst;       /* device, rows x width */
+    int64_t rows;
+    int32_t width;    /* values per row */
+    int32_t is_f64;   /* 1: src is fp64 */
+} pet_target_array_t;
+int64_t pet_baseline_workspace_bytes(int64_t n_rows, int32_t n_types, int32_t n_values);
+int pet_species_counts(const int32_t* d_species, const int32_t* d_system_indices, int64_t n_atoms, int64_t n_systems,
+                       const int32_t* d_type_index, int32_t max_z, int32_t n_types, int32_t* d_counts, int32_t* d_n_atoms,
+                       int32_t* d_error, void* stream);
+int pet_composition_accumulate(int32_t per_atom, const void* d_y, int32_t y_is_f64, int64_t n_rows, int32_t n_values,
+                               const int32_t* d_counts, const int32_t* d_species, const int32_t* d_type_index, int32_t max_z,
+                               int32_t n_types, int64_t* d_xtx, double* d_xty, int32_t* d_error, void* d_workspace,
+                               int64_t workspace_bytes, void* stream);
+int pet_target_moments(int32_t per_atom, const void* d_y, int32_t y_is_f64, int64_t n_rows, int32_t n_values, int32_t n_out,
+                       const int32_t* d_counts, const int32_t* d_n_atoms, int32_t divide_by_n_atoms, const int32_t* d_species,
+                       const int32_t* d_type_index, int32_t max_z, int32_t n_types, const double* d_weights,
+                       const double* d_scale, int64_t* d_n, double* d_y2, int32_t* d_error, void* d_workspace,
+                       int64_t workspace_bytes, void* stream);
+int pet_targets_remove(int32_t per_atom, int32_t n_arrays, const pet_target_array_t* h_arrays, const int32_t* d_counts,
+                       const int32_t* d_species, const int32_t* d_type_index, int32_t max_z, int32_t n_types,
+                       const double* d_weights, const double* d_scale, int32_t* d_error, void* stream);
+
 /* ---- profiling hooks used by bench.py ------------------------------------------ */
 /* When enabled, every kernel launch of pet_forward/pet_backward is bracketed with HIP
  * events on the launch stream; pet_profile_report fills name / total ms / calls / algorithmic

@@ -25,6 +25,7 @@ PET_LLPR_MAX_ENSEMBLE = 16384
 PET_O3_GROUPS = {"O3": 0, "inversions": 1}
 PET_O3_KINDS = {"vector": 0, "tensor2": 1}
 PET_O3_MAX_ARRAYS = 8
+PET_TARGET_MAX_ARRAYS = 4
 
 # every symbol include/pet_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -51,6 +52,8 @@ SYMBOLS = [
     "pet_zbl_create", "pet_zbl_destroy", "pet_zbl_cutoff", "pet_zbl_pair_table", "pet_zbl_workspace_bytes",
     "pet_zbl_forward", "pet_zbl_backward", "pet_zbl_hessian_vector",
     "pet_o3_draw", "pet_o3_apply",
+    "pet_baseline_workspace_bytes", "pet_species_counts", "pet_composition_accumulate", "pet_target_moments",
+    "pet_targets_remove",
     "pet_profile_enable", "pet_profile_select", "pet_profile_reset", "pet_profile_report", "pet_config_set",
 ]
 
@@ -95,6 +98,18 @@ class O3Array(ctypes.Structure):
         ("system_of_row", c_void_p),
         ("n_properties", c_int32),
         ("kind", c_int32),
+    ]
+
+
+class TargetArray(ctypes.Structure):
+    """Mirror of ``pet_target_array_t``."""
+
+    _fields_ = [
+        ("src", c_void_p),
+        ("dst", c_void_p),
+        ("rows", c_int64),
+        ("width", c_int32),
+        ("is_f64", c_int32),
     ]
 
 
@@ -251,6 +266,14 @@ def load() -> ctypes.CDLL:
     lib.pet_zbl_hessian_vector.argtypes = [P, P, P, P, P, P, P, P, P, c_int64, P]
     lib.pet_o3_draw.argtypes = [c_uint64, c_uint64, c_int32, c_int64, P, P]
     lib.pet_o3_apply.argtypes = [P, c_int64, c_int32, POINTER(O3Array), P]
+    lib.pet_baseline_workspace_bytes.argtypes = [c_int64, c_int32, c_int32]
+    lib.pet_baseline_workspace_bytes.restype = c_int64
+    lib.pet_species_counts.argtypes = [P, P, c_int64, c_int64, P, c_int32, c_int32, P, P, P, P]
+    lib.pet_composition_accumulate.argtypes = [c_int32, P, c_int32, c_int64, c_int32, P, P, P, c_int32, c_int32, P, P, P, P,
+                                               c_int64, P]
+    lib.pet_target_moments.argtypes = [c_int32, P, c_int32, c_int64, c_int32, c_int32, P, P, c_int32, P, P, c_int32, c_int32,
+                                       P, P, P, P, P, P, c_int64, P]
+    lib.pet_targets_remove.argtypes = [c_int32, c_int32, POINTER(TargetArray), P, P, P, c_int32, c_int32, P, P, P, P]
     lib.pet_profile_enable.argtypes = [c_int]
     lib.pet_profile_select.argtypes = [c_char_p]
     lib.pet_profile_report.argtypes = [c_int, P, POINTER(c_double), POINTER(c_int64), POINTER(c_double),

@@ -629,6 +629,49 @@ int pet_targets_remove(int32_t per_atom, int32_t n_arrays, const pet_target_arra
                        const int32_t* d_species, const int32_t* d_type_index, int32_t max_z, int32_t n_types,
                        const double* d_weights, const double* d_scale, int32_t* d_error, void* stream);
 
+/* ---- Pointwise training losses (utils/loss.py; utils/per_atom.py; utils/metrics.py) -------------------------------------------
+ * What the reference's trainer forms per target and per gradient from its `loss` hyper (pet/documentation.py:368, utils/loss.py:
+ * 144-217 compute_flattened with torch.nn.MSELoss / L1Loss / HuberLoss, :247-279 the masked forms): the loss value, its
+ * derivative with respect to the prediction (the seed of a reverse pass) and the sums of utils/metrics.py's RMSEAccumulator /
+ * MAEAccumulator. One TERM is one prediction array against one target array, both [rows, width] fp32, row-major.
+ *   Residual: d = p rs[row] cs[col mod n_col_scale] - t rs[row]. d_row_scale [rows] fp64 or NULL carries 1 / n_atoms (utils/
+ *     per_atom.py average_by_num_atoms: prediction AND target), d_col_scale [n_col_scale] fp64 or NULL (then n_col_scale = 0) the
+ *     per-property scales of scaler.apply_scales (predictions only); properties are the innermost axis of a row. d, l, l' and
+ *     every sum are fp64.
+ *   Validity: an entry counts when its target is not NaN (utils/loss.py:203-207) and, with d_mask [rows, width] u8, its mask byte
+ *     is non-zero (:187-194). An invalid entry adds to no sum or count; its seed is exactly 0. A NaN prediction at a valid entry
+ *     spreads to the loss, as in torch.
+ *   Kinds: PET_LOSS_MSE l = d^2, l' = 2 d; PET_LOSS_MAE l = |d|, l' = sign(d) with sign(0) = 0; PET_LOSS_HUBER l = d^2 / 2 for |d|
+ *     <= delta, else delta (|d| - delta / 2), l' = d or delta sign(d). delta is read for PET_LOSS_HUBER only.
+ *   pet_loss_count adds the term's number of valid entries to *d_count (i64; an integer atomic, exact in any order).
+ *   pet_loss_pointwise: D = *d_count for PET_LOSS_MEAN -- read on the device, no host count -- and 1 for PET_LOSS_SUM (d_count
+ *     may then be NULL). *d_loss += weight sum l(d) / D; d_seed[row, col] = weight l'(d) rs[row] cs[col] / D, rounded to fp32
+ *     once on the store (NULL: the evaluation form, no seeds); *d_stats += that loss, sum d^2, sum |d| and the valid count.
+ *     d_loss or d_stats may be NULL. D = 0 (no valid entry in the whole step): loss 0 and seeds 0 (utils/loss.py:209-215).
+ *     A one-batch step is count, then pointwise; a micro-batched step counts every micro-batch first.
+ * Determinism: sums go over chunks of 256 rows (a fixed tree inside the chunk) into the workspace, then over the chunks in
+ * ascending order, in fp64; a term of one chunk is one launch; no floating-point atomics; two identical calls give the same
+ * bits; accumulators are += across calls. No host read-back, no synchronisation. Workspace: pet_loss_workspace_bytes.
+ * PET_ERR_ARGUMENT: null or negative arguments, a workspace too small, d_seed == d_pred, n_col_scale not dividing width, an
+ * unknown kind or reduction, delta <= 0 for PET_LOSS_HUBER, PET_LOSS_MEAN without d_count. */
+#define PET_LOSS_MSE 0
+#define PET_LOSS_MAE 1
+#define PET_LOSS_HUBER 2
+#define PET_LOSS_MEAN 0
+#define PET_LOSS_SUM 1
+typedef struct pet_loss_stats {
+    double loss;    /* sum over calls of weight sum l(d) / D */
+    double sum_sq;  /* sum d^2 */
+    double sum_abs; /* sum |d| */
+    int64_t count;  /* valid entries */
+} pet_loss_stats_t;
+int64_t pet_loss_workspace_bytes(int64_t rows, int32_t width);
+int pet_loss_count(const float* d_target, const uint8_t* d_mask, int64_t rows, int32_t width, int64_t* d_count, void* stream);
+int pet_loss_pointwise(const float* d_pred, const float* d_target, const uint8_t* d_mask, const double* d_row_scale,
+                       const double* d_col_scale, int32_t n_col_scale, int64_t rows, int32_t width, int32_t kind, double delta,
+                       double weight, int32_t reduction, const int64_t* d_count, float* d_seed, double* d_loss,
+                       pet_loss_stats_t* d_stats, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- profiling hooks used by bench.py ------------------------------------------ */
 /* When enabled, every kernel launch of pet_forward/pet_backward is bracketed with HIP
  * events on the launch stream; pet_profile_report fills name / total ms / calls / algorithmic

@@ -26,6 +26,8 @@ PET_O3_GROUPS = {"O3": 0, "inversions": 1}
 PET_O3_KINDS = {"vector": 0, "tensor2": 1}
 PET_O3_MAX_ARRAYS = 8
 PET_TARGET_MAX_ARRAYS = 4
+PET_LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2}
+PET_LOSS_REDUCTIONS = {"mean": 0, "sum": 1}
 
 # every symbol include/pet_hip.h declares (tests check the library exports them all)
 SYMBOLS = [
@@ -54,6 +56,7 @@ SYMBOLS = [
     "pet_o3_draw", "pet_o3_apply",
     "pet_baseline_workspace_bytes", "pet_species_counts", "pet_composition_accumulate", "pet_target_moments",
     "pet_targets_remove",
+    "pet_loss_workspace_bytes", "pet_loss_count", "pet_loss_pointwise",
     "pet_profile_enable", "pet_profile_select", "pet_profile_reset", "pet_profile_report", "pet_config_set",
 ]
 
@@ -274,6 +277,11 @@ def load() -> ctypes.CDLL:
     lib.pet_target_moments.argtypes = [c_int32, P, c_int32, c_int64, c_int32, c_int32, P, P, c_int32, P, P, c_int32, c_int32,
                                        P, P, P, P, P, P, c_int64, P]
     lib.pet_targets_remove.argtypes = [c_int32, c_int32, POINTER(TargetArray), P, P, P, c_int32, c_int32, P, P, P, P]
+    lib.pet_loss_workspace_bytes.argtypes = [c_int64, c_int32]
+    lib.pet_loss_workspace_bytes.restype = c_int64
+    lib.pet_loss_count.argtypes = [P, P, c_int64, c_int32, P, P]
+    lib.pet_loss_pointwise.argtypes = [P, P, P, P, P, c_int32, c_int64, c_int32, c_int32, c_double, c_double, c_int32, P, P, P, P,
+                                       P, c_int64, P]
     lib.pet_profile_enable.argtypes = [c_int]
     lib.pet_profile_select.argtypes = [c_char_p]
     lib.pet_profile_report.argtypes = [c_int, P, POINTER(c_double), POINTER(c_int64), POINTER(c_double),

@@ -6,7 +6,8 @@
 
 Everything that touches activations or weights runs in libpet_hip (forward, reverse pass, weight
 gradients, clip + Adam, re-pack); torch only does the per-structure loss arithmetic on ``[S]`` /
-``[N,3]`` tensors and the RCCL all-reduce of the flat gradient bucket.
+``[N,3]`` tensors and the RCCL all-reduce of the flat gradient bucket. With a ``loss`` hyper (MAE, Huber, masked losses,
+sum reduction: ``metatrain_amd/loss.py``) the loss terms and their seeds come from ``csrc/loss.hip`` instead.
 """
 import math
 from typing import Dict, Optional
@@ -14,6 +15,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import distributed as D
+from ..loss import STATE_WORDS, PointwiseLoss, expand_loss_hypers
 from ..runtime import HipForward, HipGraph, HipModel
 
 DEFAULT_TRAINER_HYPERS = {  # pet/documentation.py TrainerHypers defaults that the step depends on
@@ -160,9 +162,30 @@ class TrainStep:
         self.model = model
         self.hypers = dict(DEFAULT_TRAINER_HYPERS)
         self.hypers.update(hypers or {})
+        self._terms: Dict[str, PointwiseLoss] = {}
+        self._set_loss_spec()
         self.total_steps = int(self.hypers["num_epochs"]) * int(steps_per_epoch)
         self.step_index = 0  # optimizer steps taken so far (LambdaLR's last_epoch)
         self.comm_events: Optional[list] = None  # a list here collects (start, end) events around every gradient all-reduce
+
+    def _set_loss_spec(self) -> None:
+        """The ``loss`` hyper (``pet/documentation.py:368``), expanded and validated; None without one: the MSE / mean
+        functions of this module with ``loss_weights``. The targets are the model's: the fused target may carry position
+        and strain gradients, every further target with an uploaded head is a plain one."""
+        self.loss_spec = None
+        if self.hypers.get("loss") is None:
+            return
+        if self.hypers["loss_weights"] != DEFAULT_TRAINER_HYPERS["loss_weights"]:
+            raise ValueError("both `loss` and `loss_weights` were given: with a `loss` hyper the weights are its `weight` entries")
+        targets = {}
+        if self.model.target is not None:
+            targets[self.model.target] = {"is_energy": True, "gradients": ["positions", "strain"]}
+        for t, _ in (self.model.head_keys() if hasattr(self.model, "_ckeys") else {}).values():  # (nothing before load())
+            targets.setdefault(t, {"is_energy": False})
+        if not targets:
+            raise ValueError("a `loss` hyper names the model's targets: load the model before building its TrainStep")
+        self.loss_spec = expand_loss_hypers(self.hypers["loss"], targets)
+        self.hypers["loss"] = self.loss_spec  # (expanding an expanded spec changes nothing: state_dict round-trips it)
 
     def state_dict(self) -> Dict[str, object]:
         """What the reference's trainer checkpoint keeps of the optimizer and scheduler (``pet/trainer.py:697-717``:
@@ -175,6 +198,7 @@ class TrainStep:
         self.step_index = int(state["step_index"])
         self.total_steps = int(state["total_steps"])
         self.hypers.update(state["hypers"])
+        self._set_loss_spec()
         self.model.load_optimizer_state(state["optimizer"])
 
     def current_lr(self) -> float:
@@ -193,8 +217,21 @@ class TrainStep:
         stress, several blocks or properties), ``{name: {"values": [N|S, ...] or {block: [N|S, ...]}, "per_atom": bool
         (default True), "weight": float (default loss_weights[name]), "scales": optional {block: per-property scales}}}``; NaN target entries are dropped, a
         ``non_conservative_stress`` target needs ``cells``. ``target_energies`` may then be None (a model loaded with
-        ``target=None``). One forward and one backbone reverse sweep serve all targets."""
+        ``target=None``). One forward and one backbone reverse sweep serve all targets.
+
+        With a ``loss`` entry in the hypers (the reference's ``loss`` hyper, :func:`metatrain_amd.loss.expand_loss_hypers`)
+        every term is formed on the device by ``csrc/loss.hip``: MSE, MAE or Huber, mean or sum, NaN targets dropped in
+        every term, weights from the ``loss`` entry (``loss_weights`` and a spec's ``"weight"`` are refused beside it), a
+        ``masked_*`` type with ``spec["mask"]`` (the values' shape, or ``{block: ...}``; non-zero = counted). The result
+        then also holds ``"terms"``: per term a statistics block for :class:`metatrain_amd.loss.LossMetrics`. Without a
+        ``loss`` entry the step is the MSE / mean step it always was."""
         self.model.zero_grad()
+        if self.loss_spec is not None:
+            out = self._native([dict(graph=graph, fw=fw, target_energies=target_energies, n_atoms=n_atoms,
+                                     target_gradients=target_gradients, target_strain_gradients=target_strain_gradients,
+                                     positions=positions, cells=cells, extra_targets=extra_targets)])
+            out["grad_norm"] = self._finish(self._trained(target_energies is not None, [extra_targets]))
+            return out
         loss, energies = self._accumulate(graph, fw, target_energies, n_atoms, target_gradients, target_strain_gradients,
                                           positions, cells, 1.0, 1.0, 1.0, extra_targets)
         norm = self._finish(self._trained(target_energies is not None, [extra_targets]))
@@ -209,6 +246,12 @@ class TrainStep:
         (``utils/loss.py`` "mean" reduction over ALL structures / components), so the result equals the one-batch step up
         to fp32 summation order."""
         batches = list(batches)
+        if self.loss_spec is not None:  # every micro-batch is counted on the device first: the means are the whole step's
+            self.model.zero_grad()
+            out = self._native(batches)
+            out["grad_norm"] = self._finish(self._trained(any(b.get("target_energies") is not None for b in batches),
+                                                          [b.get("extra_targets") for b in batches]))
+            return out
         s_tot = float(sum(int(b["n_atoms"].numel()) for b in batches))
         n_tot = float(sum(int(b["graph"].n_nodes) for b in batches))
         counts = {}  # extra targets: the whole step's non-NaN entries (their MSE's denominator)
@@ -237,16 +280,24 @@ class TrainStep:
         :meth:`end` -- the next batch's neighbour lists and graph build, as the reference's DataLoader workers do beside
         ``loss.backward()`` (``pet/trainer.py:417-472``) -- overlaps the collective."""
         self.model.zero_grad()
-        self._pending = self._accumulate(graph, fw, target_energies, n_atoms, target_gradients, target_strain_gradients,
-                                         positions, cells, 1.0, 1.0, 1.0, extra_targets)
+        if self.loss_spec is not None:
+            self._pending = self._native([dict(graph=graph, fw=fw, target_energies=target_energies, n_atoms=n_atoms,
+                                               target_gradients=target_gradients,
+                                               target_strain_gradients=target_strain_gradients, positions=positions,
+                                               cells=cells, extra_targets=extra_targets)])
+        else:
+            self._pending = self._accumulate(graph, fw, target_energies, n_atoms, target_gradients, target_strain_gradients,
+                                             positions, cells, 1.0, 1.0, 1.0, extra_targets)
         self._pending_trained = self._trained(target_energies is not None, [extra_targets])
         self._reduce = D.all_reduce_gradients_async(self.model, self.comm_events)
 
     def end(self) -> Dict[str, torch.Tensor]:
         """Second half: wait for the reduced gradients (a stream dependency under RCCL), clip + AdamW + schedule."""
-        loss, energies = self._pending
+        pending, self._pending = self._pending, None
         norm = self._finish(self._pending_trained)
-        self._pending = None
+        if isinstance(pending, dict):  # the `loss` path
+            return dict(pending, grad_norm=norm)
+        loss, energies = pending
         return {"loss": loss, "grad_norm": norm, "energies": energies}
 
     def _trained(self, with_energy: bool, extra_list) -> Dict[str, Optional[set]]:
@@ -353,3 +404,138 @@ class TrainStep:
                 u = u + u_s
             fw.backward_train2(ones, seeds, u, u_cell=u_cell, seed_features=seed_features)
         return loss, energies
+
+    # ---- the `loss` hyper: every term on csrc/loss.hip (metatrain_amd/loss.py) ---------------------------------------------
+
+    def _term_arrays(self, b):
+        """(term key, loss node, target, mask) of every target array of one (micro-)batch, in the order the step runs
+        them; the keys are the reference's metric keys (``utils/metrics.py:149-156``)."""
+        spec, name = self.loss_spec, self.model.target
+        if b.get("target_energies") is not None:
+            yield name, spec[name], b["target_energies"], None
+            if b.get("target_gradients") is not None:
+                yield f"{name}_positions_gradients", spec[name]["gradients"]["positions"], b["target_gradients"], None
+            if b.get("target_strain_gradients") is not None:
+                yield f"{name}_strain_gradients", spec[name]["gradients"]["strain"], b["target_strain_gradients"], None
+        for x, xs in (b.get("extra_targets") or {}).items():
+            if x not in spec:
+                raise ValueError(f"no loss for the target '{x}': the model has no head of that name (loss entries: {sorted(spec)})")
+            if "weight" in xs:
+                raise ValueError(f"target '{x}': with a `loss` hyper the weight is the `weight` entry of its loss")
+            masks = xs.get("mask")
+            if spec[x]["type"].startswith("masked_"):
+                if masks is None:
+                    raise ValueError(f"Expected extra_data to contain TensorMap under '{x}_mask'")  # utils/loss.py:272-275
+                masks = masks if isinstance(masks, dict) else {x: masks}
+            else:
+                masks = {}  # (an unmasked type does not look at a mask, as in the reference)
+            for blk, t in _extra_blocks(x, xs).items():
+                yield x, spec[x], t, masks.get(blk)
+
+    def _run_term(self, key, node, pred, target, total, **kw):
+        kind = node["type"][len("masked_"):] if node["type"].startswith("masked_") else node["type"]
+        return self._terms[key](pred, target, kind=kind, delta=node.get("delta", 1.0), weight=node["weight"],
+                                reduction=node["reduction"], loss_out=total, **kw)[1]
+
+    def _native(self, batches) -> Dict[str, object]:
+        """The sweeps of one optimizer step over ``batches`` (dicts of :meth:`__call__`'s arguments) with every loss term
+        formed by :class:`metatrain_amd.loss.PointwiseLoss`: the valid entries of every term are counted over ALL batches
+        first, on the device, so a mean is over the step's valid entries (``utils/loss.py:203-217``) without a read-back.
+        Returns ``loss``, ``energies`` and ``terms = {key: statistics block}`` (fp64 ``[4]`` device tensors, zeroed per
+        step: what ``LossMetrics.update`` takes)."""
+        dev = batches[0]["n_atoms"].device
+        arrays = [list(self._term_arrays(b)) for b in batches]
+        keys = list(dict.fromkeys(k for a in arrays for k, _, _, _ in a))
+        state = torch.zeros((len(keys), STATE_WORDS), dtype=torch.int64, device=dev)
+        for i, k in enumerate(keys):
+            self._terms.setdefault(k, PointwiseLoss()).bind(state[i])
+        for a in arrays:
+            for k, _, t, m in a:
+                self._terms[k].count(t, t, m)
+        total = torch.zeros((), dtype=torch.float64, device=dev)
+        energies = [self._accumulate_native(total=total, **b) for b in batches]
+        return {"loss": total, "energies": None if energies[0] is None else (energies[0] if len(energies) == 1 else torch.cat(energies)),
+                "terms": {k: self._terms[k].stats() for k in keys}}
+
+    def _extra_native(self, graph, fw, inv_n, cells, extra_targets, total):
+        """:meth:`_extra` with the seeds from the kernel: dL/d(prediction) goes straight to ``train_predict_backward``;
+        torch's autograd is used only for what stands between a head's output and the loss's prediction (the
+        non-conservative stress's post-processing, the per-structure sum)."""
+        sys = graph.system_of_atom().long()
+        n_layers = self.model.num_readout_layers()
+        seed_features = None
+        for name, xs in extra_targets.items():
+            node = self.loss_spec[name]
+            per_atom = xs.get("per_atom", True)
+            scales = xs.get("scales") or {}
+            masks = xs.get("mask") if node["type"].startswith("masked_") else None
+            masks = masks if isinstance(masks, dict) else {name: masks}
+            grads = {}
+            for b, target in _extra_blocks(name, xs).items():
+                p = fw.train_predict(name, b)
+                for layer in range(1, n_layers):  # fixed order
+                    p = p + fw.train_predict(name, b, readout_layer=layer)
+                q = p
+                if name == "non_conservative_stress" or not per_atom:
+                    p.requires_grad_(True)
+                    if name == "non_conservative_stress":
+                        if cells is None:
+                            raise ValueError("a non_conservative_stress target needs `cells`")
+                        q = process_non_conservative_stress(p, cells, sys)
+                    if not per_atom:
+                        q = _SumOverAtoms.apply(q, fw, sys)
+                rs = inv_n if not per_atom and name not in self.hypers.get("per_structure_targets", ()) else None
+                seed = self._run_term(name, node, q.detach(), target, total, row_scale=rs, col_scale=scales.get(b),
+                                      mask=masks.get(b))
+                grads[b] = seed if q is p else torch.autograd.grad(q, p, seed)[0]
+            for layer in range(n_layers):
+                seed_features = fw.train_predict_backward(name, grads, readout_layer=layer, seed_features=seed_features)
+        return seed_features
+
+    def _accumulate_native(self, graph, fw, n_atoms, total, target_energies=None, target_gradients=None,
+                           target_strain_gradients=None, positions=None, cells=None, extra_targets=None):
+        """:meth:`_accumulate` on the `loss` path: the loss is added to ``total`` on the device; returns the energies."""
+        if fw.graph is not graph:  # micro-batches may share one workspace allocation
+            fw.rebind(graph)
+        name = self.model.target
+        inv_n = n_atoms.to(torch.float64).reciprocal()
+        if target_energies is None:
+            if target_gradients is not None or target_strain_gradients is not None:
+                raise ValueError("force / strain-gradient targets need the energy target")
+            if not extra_targets:
+                raise ValueError("no target to train")
+            fw.forward(want_atomic=False)
+            seeds, energies = None, None
+        else:
+            node = self.loss_spec[name]
+            atomic = fw.forward()
+            energies = fw.sum_over_atoms(atomic)
+            d_energy = self._run_term(name, node, energies, target_energies, total, row_scale=inv_n)  # dL/dE_s
+            seeds = d_energy[graph.system_of_atom().long()]
+        seed_features = None
+        if extra_targets:
+            seed_features = self._extra_native(graph, fw, inv_n, cells, extra_targets, total)
+        if target_gradients is None and target_strain_gradients is None:
+            fw.backward_train(seeds, seed_features=seed_features)
+            return energies
+        ones = torch.ones_like(atomic)
+        grad_positions, grad_cells = fw.backward(ones, want_cell_grad=True)
+        u, u_cell = None, None
+        if target_gradients is not None:
+            u = self._run_term(f"{name}_positions_gradients", node["gradients"]["positions"], grad_positions, target_gradients,
+                               total)
+        if target_strain_gradients is not None:
+            if positions is None or cells is None:
+                raise ValueError("a strain-gradient (stress) target needs `positions` and `cells`")
+            pos, cell, sys = positions.to(torch.float32), cells.to(torch.float32), graph.system_of_atom().long()
+            outer = (pos[:, :, None] * grad_positions[:, None, :]).reshape(-1, 9)
+            # the per-structure sum in a fixed order (index_add's float atomics would make the seeds vary run to run)
+            virial = torch.stack([fw.sum_over_atoms(outer[:, j].contiguous()) for j in range(9)], dim=1).reshape(-1, 3, 3)
+            virial = virial + cell.transpose(1, 2) @ grad_cells
+            g = self._run_term(f"{name}_strain_gradients", node["gradients"]["strain"], virial, target_strain_gradients,
+                               total)                              # dL/d(dE/deps)
+            u_s = (pos[:, None, :] @ g[sys]).squeeze(1)             # d(dE/deps_ab)/d(gR_ib) = R_ia
+            u = u_s if u is None else u + u_s
+            u_cell = cell @ g
+        fw.backward_train2(ones, seeds, u, u_cell=u_cell, seed_features=seed_features)
+        return energies

@@ -576,6 +576,44 @@ typedef struct pet_o3_array {
 int pet_o3_draw(uint64_t key, uint64_t counter, int32_t group, int64_t n_systems, float* d_matrices, void* stream);
 int pet_o3_apply(const float* d_matrices, int64_t n_systems, int32_t n_arrays, const pet_o3_array_t* h_arrays, void* stream);
 
+/* ---- Rotational augmentation of spherical targets (utils/augmentation.py:158-180, 97-124; utils/testing/output.py:940-944) ---
+ * Targets that are blocks of irreducible representations of O(3), {o3_lambda = l, o3_sigma = +-1}: rows [2l+1, P], P innermost.
+ * With positions x' = O x, Q = det(O) O the proper part, a block transforms as t'[m] = f sum_m' D^l(Q)[m,m'] t[m'], f = 1 for a
+ * proper O and o3_sigma (-1)^l for an improper one. D^l is defined by Y_l(Q u) = D^l(Q) Y_l(u) with the orthonormal real
+ * spherical harmonics in the order m = -l..l WITHOUT the Condon-Shortley phase (metatensor / sphericart):
+ * Y_1 = sqrt(3/4pi) (y, z, x), Y_2 = (sqrt(15/4pi) xy, sqrt(15/4pi) yz, sqrt(5/16pi) (3z^2 - 1), sqrt(15/4pi) xz,
+ * sqrt(15/16pi) (x^2 - y^2)).
+ *   pet_o3_wigner replaces augmentation.py:158-180 (the Wigner-D cache the reference sizes from its targets and fills on the
+ *     host through Euler angles): from d_matrices [n_systems,3,3] fp32 (what pet_o3_draw wrote, or the caller's own) it writes
+ *     d_parity [n_systems] fp32, the sign of the fp64 determinant as +-1, and d_wigner [n_systems, W(l_max)] fp32 with
+ *     W(L) = (L+1)(2L+1)(2L+3)/3: for l = 0..l_max the block D^l(Q) row-major [2l+1, 2l+1], block l at offset l (4 l^2 - 1) / 3.
+ *     The Ivanic-Ruedenberg recursion (D^l from D^(l-1) and D^1; every entry a polynomial of degree l in the entries of Q, so
+ *     a slightly non-orthogonal matrix gives a slightly non-orthogonal D), fp64 arithmetic, every entry rounded to fp32 once.
+ *     A matrix that is exactly +-identity gives exactly the identity blocks. A NaN or an infinity in a matrix makes that
+ *     system's whole table and its parity NaN, and no other system's. One workgroup per system.
+ *   pet_o3_apply_spherical replaces augmentation.py:97-124 (transform_tensormap for spherical targets): up to
+ *     PET_O3_MAX_ARRAYS arrays in one launch, each OUT OF PLACE (dst != src). Rows and system_of_row as in pet_o3_apply.
+ *     out[m,p] = f sum_m' D^l[m,m'] x[m',p] in fp32 fused multiply-adds over ALL m': a NaN anywhere in a (row, p) multiplet
+ *     makes that whole multiplet NaN, and only that one; a zero multiplet stays exactly zero; under +-identity the output is
+ *     exactly +-input. A system index outside [0, n_systems) is not followed: that row comes out NaN. o3_lambda = 0 with
+ *     o3_sigma = -1 (a pseudoscalar) multiplies by det; invariants (0, +1) need not be passed at all.
+ * No atomics, no allocation, no host read-back, no synchronisation: results are the same bits run to run, whatever the grid.
+ * PET_ERR_ARGUMENT: l_max or o3_lambda outside [0, PET_O3_MAX_L], o3_lambda above l_max, o3_sigma not +-1, a negative count,
+ * n_arrays above PET_O3_MAX_ARRAYS, dst == src, more rows than systems without system_of_row. Empty inputs launch nothing. */
+#define PET_O3_MAX_L 8
+typedef struct pet_o3_spherical_array {
+    const float* src;             /* device, rows x (2 o3_lambda + 1) x n_properties */
+    float* dst;                   /* device, same shape */
+    int64_t rows;
+    const int32_t* system_of_row; /* device [rows], or NULL: row r belongs to system r */
+    int32_t n_properties;         /* P, the innermost dimension */
+    int32_t o3_lambda;            /* l in [0, PET_O3_MAX_L], at most the table's l_max */
+    int32_t o3_sigma;             /* +1, or -1: the block changes sign under inversion relative to (-1)^l */
+} pet_o3_spherical_array_t;
+int pet_o3_wigner(const float* d_matrices, int64_t n_systems, int32_t l_max, float* d_wigner, float* d_parity, void* stream);
+int pet_o3_apply_spherical(const float* d_wigner, const float* d_parity, int32_t l_max, int64_t n_systems, int32_t n_arrays,
+                           const pet_o3_spherical_array_t* h_arrays, void* stream);
+
 /* ---- Composition baselines and target scales (composition/_base_composition.py; scaler/_base_scaler.py) ----------------------
  * What the reference fits on the training set before the first optimizer step, from the plain tensors of a collated batch:
  * species [N] i32 (atomic numbers), system_indices [N] i32 (non-decreasing, in [0, n_systems)) and targets. No model or graph

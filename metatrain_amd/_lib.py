@@ -25,6 +25,7 @@ PET_LLPR_MAX_ENSEMBLE = 16384
 PET_O3_GROUPS = {"O3": 0, "inversions": 1}
 PET_O3_KINDS = {"vector": 0, "tensor2": 1}
 PET_O3_MAX_ARRAYS = 8
+PET_O3_MAX_L = 8
 PET_TARGET_MAX_ARRAYS = 4
 PET_LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2}
 PET_LOSS_REDUCTIONS = {"mean": 0, "sum": 1}
@@ -53,7 +54,7 @@ SYMBOLS = [
     "pet_llpr_covariance_finalize", "pet_llpr_variance", "pet_llpr_ensemble",
     "pet_zbl_create", "pet_zbl_destroy", "pet_zbl_cutoff", "pet_zbl_pair_table", "pet_zbl_workspace_bytes",
     "pet_zbl_forward", "pet_zbl_backward", "pet_zbl_hessian_vector",
-    "pet_o3_draw", "pet_o3_apply",
+    "pet_o3_draw", "pet_o3_apply", "pet_o3_wigner", "pet_o3_apply_spherical",
     "pet_baseline_workspace_bytes", "pet_species_counts", "pet_composition_accumulate", "pet_target_moments",
     "pet_targets_remove",
     "pet_loss_workspace_bytes", "pet_loss_count", "pet_loss_pointwise",
@@ -101,6 +102,20 @@ class O3Array(ctypes.Structure):
         ("system_of_row", c_void_p),
         ("n_properties", c_int32),
         ("kind", c_int32),
+    ]
+
+
+class O3SphericalArray(ctypes.Structure):
+    """Mirror of ``pet_o3_spherical_array_t``."""
+
+    _fields_ = [
+        ("src", c_void_p),
+        ("dst", c_void_p),
+        ("rows", c_int64),
+        ("system_of_row", c_void_p),
+        ("n_properties", c_int32),
+        ("o3_lambda", c_int32),
+        ("o3_sigma", c_int32),
     ]
 
 
@@ -269,6 +284,8 @@ def load() -> ctypes.CDLL:
     lib.pet_zbl_hessian_vector.argtypes = [P, P, P, P, P, P, P, P, P, c_int64, P]
     lib.pet_o3_draw.argtypes = [c_uint64, c_uint64, c_int32, c_int64, P, P]
     lib.pet_o3_apply.argtypes = [P, c_int64, c_int32, POINTER(O3Array), P]
+    lib.pet_o3_wigner.argtypes = [P, c_int64, c_int32, P, P, P]
+    lib.pet_o3_apply_spherical.argtypes = [P, P, c_int32, c_int64, c_int32, POINTER(O3SphericalArray), P]
     lib.pet_baseline_workspace_bytes.argtypes = [c_int64, c_int32, c_int32]
     lib.pet_baseline_workspace_bytes.restype = c_int64
     lib.pet_species_counts.argtypes = [P, P, c_int64, c_int64, P, c_int32, c_int32, P, P, P, P]

@@ -8,6 +8,16 @@ cell_shift)`` list as the original: the batch is collated (neighbour search incl
 step only draws ``S`` matrices and transforms a few arrays (``csrc/augment.hip``: two launches, no synchronisation, no
 read-back). The reference rotates first and re-runs the neighbour search on every structure at every step.
 
+Spherical targets (``{"kind": "spherical", "o3_lambda": l, "o3_sigma": +-1}``, ``l <= 8``: multipoles, the irreducible parts
+of a polarisability, density coefficients) are rotated too. Where a batch holds one with ``l > 0`` or ``o3_sigma = -1``, a step
+adds two launches (``csrc/wigner.hip``): ``pet_o3_wigner`` builds the real Wigner-D matrices of every system's matrix up to the
+largest ``l`` among the kinds, and ``pet_o3_apply_spherical`` applies them, eight arrays per launch. The convention is the
+reference's (``utils/testing/output.py:940-944``): with ``x' = Q x`` a block transforms as ``t'[m] = sum_m' D^l[m,m'] t[m']``,
+``Y_l(Q u) = D^l(Q) Y_l(u)`` for the real harmonics in the order ``m = -l..l`` without the Condon-Shortley phase; an improper
+matrix ``O`` applies ``D^l(det O * O)`` times ``o3_sigma (-1)^l``. The table and the determinants travel with the batch under
+``"o3_wigner"`` and ``"o3_parity"`` (``runtime.o3_wigner_block`` views one ``l``). Without such a kind nothing changes: no
+extra launch, no extra key.
+
 Sequence of matrices. ``pet_o3_draw`` is counter based: the matrix of system ``s`` of the ``n``-th call is a function of
 ``(key, n, s)`` alone, with ``key = stream << 32 | seed`` (``seed`` and ``stream`` both below 2^32; ``stream`` is for the
 rank: two ranks with one seed hold different keys, and no counter value of one rank's sequence is another's).
@@ -18,11 +28,14 @@ from typing import Dict, Optional, Union
 import torch
 
 from . import runtime as rt
+from ._lib import PET_O3_MAX_L as MAX_L
 
 # what a collated batch holds besides targets: the first two are transformed, the others shared with the input by reference
 TRANSFORMED = ("positions", "cells")
 SHARED = ("centers", "neighbors", "cell_shifts", "species", "system_indices")
 MATRICES = "o3_matrices"
+WIGNER, PARITY = "o3_wigner", "o3_parity"  # present only where a spherical kind needs them
+ADDED = (MATRICES, WIGNER, PARITY)
 ORTHOGONALITY_TOLERANCE = 1e-4
 
 
@@ -31,11 +44,26 @@ def _normalise_kind(name: str, spec: Union[str, dict]) -> dict:
         spec = {"kind": spec}
     if not isinstance(spec, dict) or "kind" not in spec:
         raise ValueError(f"target '{name}': expected 'scalar', 'vector', 'tensor2' or a dict with a 'kind', got {spec!r}")
-    unknown = set(spec) - {"kind", "per_atom", "lambda", "sigma"}
+    unknown = set(spec) - {"kind", "per_atom", "lambda", "sigma", "o3_lambda", "o3_sigma"}
     if unknown:
         raise ValueError(f"target '{name}': unknown entries {sorted(unknown)}")
     kind = spec["kind"]
-    if kind == "spherical":
+    per_atom = spec.get("per_atom")
+    per_atom = None if per_atom is None else bool(per_atom)
+    if "o3_lambda" in spec or "o3_sigma" in spec:  # the reference's own key names: served
+        if kind != "spherical":
+            raise ValueError(f"target '{name}': 'o3_lambda' / 'o3_sigma' belong to the kind 'spherical'")
+        if "lambda" in spec or "sigma" in spec:
+            raise ValueError(f"target '{name}': give 'o3_lambda' / 'o3_sigma' or the short 'lambda' / 'sigma', not both")
+        lam, sigma = spec.get("o3_lambda", 0), spec.get("o3_sigma", 1)
+        if isinstance(lam, bool) or not isinstance(lam, int) or not 0 <= lam <= MAX_L:
+            raise ValueError(f"target '{name}': o3_lambda must be an integer in [0, {MAX_L}], got {lam!r}")
+        if isinstance(sigma, bool) or not isinstance(sigma, int) or sigma not in (1, -1):
+            raise ValueError(f"target '{name}': o3_sigma must be +1 or -1, got {sigma!r}")
+        if lam == 0 and sigma == 1:
+            return {"kind": "scalar", "per_atom": per_atom}
+        return {"kind": "spherical", "per_atom": per_atom, "o3_lambda": lam, "o3_sigma": sigma}
+    if kind == "spherical":  # the short spelling keeps its refusal: use 'o3_lambda' / 'o3_sigma'
         lam, sigma = int(spec.get("lambda", 0)), int(spec.get("sigma", 1))
         if lam > 0 or sigma != 1:
             raise ValueError(f"target '{name}': spherical targets with lambda > 0 (or sigma = -1) need Wigner-D matrices, which "
@@ -45,8 +73,7 @@ def _normalise_kind(name: str, spec: Union[str, dict]) -> dict:
         raise ValueError(f"target '{name}': 'lambda' / 'sigma' belong to the kind 'spherical'")
     if kind not in ("scalar", "vector", "tensor2"):
         raise ValueError(f"target '{name}': unknown kind '{kind}', expected 'scalar', 'vector' or 'tensor2'")
-    per_atom = spec.get("per_atom")
-    return {"kind": kind, "per_atom": None if per_atom is None else bool(per_atom)}
+    return {"kind": kind, "per_atom": per_atom}
 
 
 class O3Augmenter:
@@ -58,8 +85,12 @@ class O3Augmenter:
     ``reshape(n, 3, 3, p)`` layout of ``trainer.process_non_conservative_stress``). Scalars, entries whose name ends in
     ``_mask`` (``augmentation.py:118-120``) and entries that are no tensors pass through untouched. Every other tensor of a
     batch must be named in ``kinds``: an unnamed one raises, since leaving a Cartesian target unrotated is silent and wrong.
-    ``{"kind": "spherical", "lambda": l}`` is refused for ``l > 0``. float32 only; a NaN anywhere in a vector or tensor
-    makes that whole output vector or tensor NaN.
+    ``{"kind": "spherical", "o3_lambda": l, "o3_sigma": +-1, "per_atom": ...}`` with ``0 <= l <= 8`` (the reference's own
+    key names): trailing dimensions ``[2l+1, P]``, flattened or not; one entry per block, so a target of several irreps is
+    several entries. ``(0, +1)`` is a scalar and passes through; ``(0, -1)``, a pseudoscalar, is multiplied by the
+    determinant. The older short spelling ``{"kind": "spherical", "lambda": l, "sigma": s}`` is still refused for ``l > 0`` or
+    ``s = -1`` with the message it always had: write ``o3_lambda`` / ``o3_sigma`` instead. float32 only; a NaN anywhere in a
+    vector, tensor or ``(row, property)`` multiplet makes that whole output vector, tensor or multiplet NaN.
 
     ``group``: ``"O3"`` (Haar-uniform rotations, improper with probability 1/2) or ``"inversions"`` (+-identity).
     ``seed``, ``stream``: integers in ``[0, 2^32)``; ``stream`` is for the rank (see the module's text)."""
@@ -75,9 +106,11 @@ class O3Augmenter:
         self.counter = 0  # calls of apply_random_augmentations so far
         self.kinds = {}
         for name, spec in (kinds or {}).items():
-            if name in TRANSFORMED + SHARED or name == MATRICES:
+            if name in TRANSFORMED + SHARED + ADDED:
                 raise ValueError(f"'{name}' is part of the batch itself, not a target")
             self.kinds[name] = _normalise_kind(name, spec)
+        # the table of a step reaches the largest l among the kinds; None: no kind needs a table
+        self.l_max = max((k["o3_lambda"] for k in self.kinds.values() if k["kind"] == "spherical"), default=None)
         self._cell_rows: Dict[tuple, torch.Tensor] = {}  # (S, device) -> int32 [3 S], the system of every lattice vector
 
     @property
@@ -109,17 +142,23 @@ class O3Augmenter:
         n, s = int(pos.shape[0]), int(cells.shape[0])
         plan = [("positions", "vector", True), ("cells", "vector", "cells")]
         for name, v in batch.items():
-            if name in TRANSFORMED + SHARED or name == MATRICES or name.endswith("_mask") or not torch.is_tensor(v):
+            if name in TRANSFORMED + SHARED + ADDED or name.endswith("_mask") or not torch.is_tensor(v):
                 continue
             if name not in self.kinds:
                 raise ValueError(f"the batch holds '{name}', which the augmenter was not told the kind of: name it in `kinds` "
-                                 "('scalar', 'vector' or 'tensor2')")
+                                 "('scalar', 'vector', 'tensor2' or a spherical block)")
             kind, per_atom = self.kinds[name]["kind"], self.kinds[name]["per_atom"]
             if kind == "scalar":
                 continue
-            width = 3 if kind == "vector" else 9
-            if v.dim() < 2 or int(v.shape[1:].numel()) % width:
-                raise ValueError(f"target '{name}': a {kind} needs {width} x P values per row, got the shape {tuple(v.shape)}")
+            if kind == "spherical":
+                lam = self.kinds[name]["o3_lambda"]
+                if v.dim() < 2 or int(v.shape[1:].numel()) % (2 * lam + 1):
+                    raise ValueError(f"target '{name}': a spherical block of o3_lambda = {lam} needs (2l+1) x P = {2 * lam + 1} x P "
+                                     f"values per row, got the shape {tuple(v.shape)}")
+            else:
+                width = 3 if kind == "vector" else 9
+                if v.dim() < 2 or int(v.shape[1:].numel()) % width:
+                    raise ValueError(f"target '{name}': a {kind} needs {width} x P values per row, got the shape {tuple(v.shape)}")
             rows = int(v.shape[0])
             if per_atom is None:
                 if rows not in (n, s):
@@ -139,9 +178,12 @@ class O3Augmenter:
         sysidx = batch["system_indices"]
         if sysidx.dtype != torch.int32:
             raise ValueError(f"system_indices must be int32 (as collate makes them), got {sysidx.dtype}")
-        arrays = []
+        arrays, spherical = [], []
         for name, kind, owner in plan:
-            if owner == "cells":  # lattice vectors are the rows of a cell: [3 S] vectors, three per system
+            if kind == "spherical":
+                k = self.kinds[name]
+                spherical.append((batch[name], k["o3_lambda"], k["o3_sigma"], sysidx if owner else None))
+            elif owner == "cells":  # lattice vectors are the rows of a cell: [3 S] vectors, three per system
                 ck = (s, batch["cells"].device)
                 if ck not in self._cell_rows:
                     self._cell_rows[ck] = torch.arange(3 * s, dtype=torch.int32, device=ck[1]) // 3
@@ -150,9 +192,17 @@ class O3Augmenter:
                 arrays.append((batch[name], kind, sysidx if owner else None))
         outs = rt.o3_apply(matrices, arrays)
         new = dict(batch)  # everything else, the pair list first of all, is shared by reference
-        for (name, _, _), out in zip(plan, outs):
+        for (name, _, _), out in zip([e for e in plan if e[1] != "spherical"], outs):
             new[name] = out.reshape(batch[name].shape)
         new[MATRICES] = matrices
+        new.pop(WIGNER, None)  # (an augmented batch passed in again: the keys of another step's matrices)
+        new.pop(PARITY, None)
+        if spherical:
+            table, parity = rt.o3_wigner(matrices, self.l_max)
+            outs = rt.o3_apply_spherical(table, parity, self.l_max, spherical)
+            for (name, _, _), out in zip([e for e in plan if e[1] == "spherical"], outs):
+                new[name] = out.reshape(batch[name].shape)
+            new[WIGNER], new[PARITY] = table, parity
         return new
 
     def apply_random_augmentations(self, batch: Dict[str, object]) -> Dict[str, object]:

@@ -897,6 +897,94 @@ def o3_apply(matrices: torch.Tensor, arrays) -> List[torch.Tensor]:
     return outs
 
 
+def _wigner_offset(l: int) -> int:
+    return l * (4 * l * l - 1) // 3
+
+
+def o3_wigner(matrices: torch.Tensor, l_max: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Real Wigner-D matrices of ``matrices [S,3,3]`` (``pet_o3_wigner``): ``(table [S, W(l_max)], parity [S])``, both fp32.
+    ``parity`` is the sign of the determinant; ``table`` holds ``D^l`` of the proper part ``det * O`` for ``l = 0..l_max``,
+    row-major, block ``l`` at offset ``l (4 l^2 - 1) / 3`` (:func:`o3_wigner_block`), ``W(L) = (L+1)(2L+1)(2L+3)/3``.
+    Convention: ``Y_l(Q u) = D^l(Q) Y_l(u)`` with the real harmonics in the order ``m = -l..l`` without the Condon-Shortley
+    phase. fp64 arithmetic, one rounding. No synchronisation, no read-back."""
+    _require_cuda(matrices)
+    l_max = int(l_max)
+    if not 0 <= l_max <= _lib.PET_O3_MAX_L:
+        raise ValueError(f"l_max must be in [0, {_lib.PET_O3_MAX_L}], got {l_max}")
+    if matrices.dim() != 3 or tuple(matrices.shape[1:]) != (3, 3):
+        raise ValueError(f"matrices must be [S,3,3], got {tuple(matrices.shape)}")
+    mats = matrices.detach().to(torch.float32).contiguous()
+    n_sys = int(mats.shape[0])
+    table = torch.empty((n_sys, _wigner_offset(l_max + 1)), dtype=torch.float32, device=mats.device)
+    parity = torch.empty((n_sys,), dtype=torch.float32, device=mats.device)
+    with torch.cuda.device(mats.device):
+        check(_lib.load().pet_o3_wigner(_ptr(mats), n_sys, l_max, _ptr(table), _ptr(parity), _stream()))
+    return table, parity
+
+
+def o3_wigner_block(table: torch.Tensor, l: int) -> torch.Tensor:
+    """``D^l`` of every system as ``[S, 2l+1, 2l+1]``: a view of ``table`` (:func:`o3_wigner`)."""
+    l = int(l)
+    w = 2 * l + 1
+    if table.dim() != 2 or l < 0 or _wigner_offset(l + 1) > int(table.shape[1]):
+        raise ValueError(f"the table {tuple(table.shape)} holds no block of l = {l}")
+    return table[:, _wigner_offset(l):_wigner_offset(l + 1)].unflatten(1, (w, w))
+
+
+def o3_apply_spherical(table: torch.Tensor, parity: torch.Tensor, l_max: int, arrays) -> List[torch.Tensor]:
+    """Transform ``arrays = [(tensor [rows, ...], o3_lambda, o3_sigma, system_of_row), ...]`` by the Wigner-D ``table`` and
+    ``parity`` of :func:`o3_wigner` into fresh tensors of the same shapes (``pet_o3_apply_spherical``, eight arrays per
+    launch). Trailing dimensions ``[2l+1, P]``, flattened or not: ``out[m,p] = f sum_m' D^l[m,m'] x[m',p]`` with ``f = 1``
+    for a proper system and ``o3_sigma (-1)^l`` for an improper one. ``system_of_row``: int32 ``[rows]`` or None (row ``r``
+    belongs to system ``r``). The inputs are left alone. A NaN anywhere in a ``(row, p)`` multiplet makes that whole
+    multiplet NaN."""
+    arrays = list(arrays)
+    _require_cuda(table, parity, *[a[0] for a in arrays], *[a[3] for a in arrays if a[3] is not None])
+    l_max = int(l_max)
+    if not 0 <= l_max <= _lib.PET_O3_MAX_L:
+        raise ValueError(f"l_max must be in [0, {_lib.PET_O3_MAX_L}], got {l_max}")
+    n_sys = int(parity.numel())
+    if (table.dtype != torch.float32 or parity.dtype != torch.float32 or parity.dim() != 1
+            or tuple(table.shape) != (n_sys, _wigner_offset(l_max + 1))):
+        raise ValueError(f"table and parity must be fp32 [S, {_wigner_offset(l_max + 1)}] and [S] for l_max = {l_max}, got "
+                         f"{table.dtype} {tuple(table.shape)} and {parity.dtype} {tuple(parity.shape)}")
+    table, parity = table.detach().contiguous(), parity.detach().contiguous()
+    keep, descs, outs = [table, parity], [], []
+    for src, lam, sigma, sor in arrays:
+        lam, sigma = int(lam), int(sigma)
+        if not 0 <= lam <= l_max:
+            raise ValueError(f"o3_lambda must be in [0, l_max = {l_max}], got {lam}")
+        if sigma not in (1, -1):
+            raise ValueError(f"o3_sigma must be +1 or -1, got {sigma}")
+        width = 2 * lam + 1
+        rows = int(src.shape[0]) if src.dim() else 0
+        per_row = int(src.shape[1:].numel())
+        if src.dim() < 2 or per_row % width:
+            raise ValueError(f"a spherical block of o3_lambda = {lam} needs (2l+1) x P = {width} x P values per row, got the "
+                             f"shape {tuple(src.shape)}")
+        if src.dtype != torch.float32:
+            raise ValueError(f"the transformation kernels are float32, got {src.dtype}")
+        x = src.detach().contiguous()
+        out = torch.empty_like(x)
+        if sor is not None:
+            if sor.dtype != torch.int32 or sor.numel() != rows:
+                raise ValueError(f"system_of_row must be int32 [{rows}], got {sor.dtype} {tuple(sor.shape)}")
+            sor = sor.contiguous()
+        elif rows > n_sys:
+            raise ValueError(f"{rows} rows for {n_sys} systems and no system_of_row")
+        keep += [x, sor]
+        descs.append(_lib.O3SphericalArray(x.data_ptr(), out.data_ptr(), rows, None if sor is None else sor.data_ptr(),
+                                           per_row // width, lam, sigma))
+        outs.append(out)
+    lib = _lib.load()
+    with torch.cuda.device(table.device):
+        for i in range(0, len(descs), _lib.PET_O3_MAX_ARRAYS):
+            chunk = descs[i:i + _lib.PET_O3_MAX_ARRAYS]
+            check(lib.pet_o3_apply_spherical(_ptr(table), _ptr(parity), l_max, n_sys, len(chunk),
+                                             (_lib.O3SphericalArray * len(chunk))(*chunk), _stream()))
+    return outs
+
+
 def profile(enable: bool, stage: Optional[str] = None) -> None:
     """Bracket every stage (or only ``stage``) of forward/backward with HIP events."""
     lib = _lib.load()

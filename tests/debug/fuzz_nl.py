@@ -1,4 +1,9 @@
-"""One-off randomized sweep of the device neighbour list against the oracle (sorted (i, j, S) sets + vectors)."""
+"""One-off randomized sweep of the device neighbour list against the oracle (sorted (i, j, S) sets + vectors).
+
+Its in-suite successor is ``tests/test_gpu_nl_edges.py``: the structural edge cases of ``k_nlb_pairs`` and of the host set-up
+(image-count and tile-overflow flushes, more than 64 centres in a bin, halved and capped bin counts, mixed batches, the host's
+refusals) as a deterministic table in ``tests/nl_cases.py``, and -- what this sweep skips below -- pairs on the cutoff's last
+ulp. The sweep stays here for systems nobody thought of."""
 import sys
 import numpy as np
 import torch

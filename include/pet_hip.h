@@ -540,6 +540,64 @@ int pet_zbl_hessian_vector(const pet_zbl_t* z, const pet_graph_t* g, const float
                            const float* d_u_cell, float* d_hvp_positions, float* d_hvp_cells, float* d_tangent_atomic,
                            void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Long-range (Ewald) features of `long_range: {enable: true}` (utils/long_range.py:108-195, pet/model.py:505-518) ---------
+ * A periodic Coulomb sum over C channels of per-atom "charges" q [N, C], with its adjoints. torch-pme is not part of the
+ * reference tree: the operator is fixed HERE by definition (DESIGN section 18 holds the same convention table) and pinned to
+ * an independent fp64 oracle; parity with torch-pme is NOT pinned.
+ *   sigma = smearing, R = the model cutoff (exclusion radius), lambda = kspace_resolution, Omega = |det cell|, a = sqrt(2) sigma,
+ *   f(d) = (1 + cos(pi d / R)) / 2 for d < R, else 0,   G(k) = 4 pi exp(-sigma^2 k^2 / 2) / k^2,   P = 1/2 (prefactor).
+ * Periodic system (all three pbc):
+ *   V_i = P [ (1/Omega) sum_{k != 0, |k| <= 2 pi / lambda} G(k) Re(e^{-i k.r_i} S(k)) - q_i sqrt(2/pi)/sigma
+ *             - (2 pi sigma^2 / Omega) sum_j q_j - sum_{edges (i -> j, S) of the graph} q_j w(d) ],
+ *   S(k) = sum_j q_j e^{i k.r_j},  w(d) = erf(d/a) f(d) / d,  k over the reciprocal lattice 2 pi n cell^{-T} (a sphere).
+ * Non-periodic system (no pbc): V_i = P sum_{j != i} q_j K(d_ij) over ALL pairs of the system, K(d) = (1 - f(d)) / d.
+ * Mixed pbc: PET_ERR_UNSUPPORTED from pet_ewald_plan.
+ * Adjoints, for L with dL/dV = g [N, C] (the operator is symmetric in (i, j): the neighbour list is full):
+ *   dL/dq = the operator applied to g.
+ *   With T(k) = sum_i g_i e^{i k.r_i}, c_ik = cos k.r_i, s_ik = sin k.r_i (per channel, summed over channels below):
+ *   k-space:   F_i = (P/Omega) sum_k G k [ g_i (c_ik Im S - s_ik Re S) + q_i (c_ik Im T - s_ik Re T) ],  dL/dR_i += F_i
+ *              Z_k = Re(conj(T) S);  dL/dcell_bc += -sum_i s_ib F_ic          (s_i = r_i cell^{-1}: the phases through k)
+ *                                  + (P/Omega) sum_k G Z_k [ (sigma^2 + 2/k^2) (cell^{-T} k)_b k_c - (cell^{-T})_bc ]
+ *   background: dL/dcell_bc += (2 pi sigma^2 P / Omega) (sum_i g_i).(sum_j q_j) (cell^{-T})_bc
+ *   exclusion: per edge p = (i -> j, S), D = r_j - r_i + S.cell, B_p = g_i.q_j, B'_p = g_j.q_i, w' = dw/dd:
+ *              dL/dR_i += P sum_{row i, j != i} w'(d) (B_p + B'_p) D/d,   dL/dcell_ab += -P sum_p w'(d) B_p S_a D_b / d
+ *              (an edge from an atom to its own image moves with the cell only)
+ *   non-periodic: dL/dR_i = -P sum_{j != i} K'(d) (g_i.q_j + g_j.q_i) (r_j - r_i)/d.
+ * Kernels (csrc/ewald.hip): structure factors, the gather back to atoms and the all-pairs sum are GEMMs on the fp32 matrix
+ * core (v_mfma_f32_32x32x2_f32) with one operand GENERATED in registers -- phases as products of per-axis tables
+ * e^{2 pi i n s_a}, built in fp64 from fractional coordinates and rounded once; cos(k.r) of a large fp32 argument is never
+ * formed. Sums over atoms and over k run in fixed-order chunks relative to the system's first atom / first k-vector, the
+ * exclusion term is a CSR row sum; no float atomics: the same bits run to run, and a system gives the same bits alone as
+ * inside a batch.
+ *   pet_ewald_create(smearing, kspace_resolution, cutoff).
+ *   pet_ewald_kvectors_host: the k-set of one cell, host fp64, no GPU: returns the count and fills h_out [count, 3] when
+ *     capacity suffices (h_out may be NULL to count); -1 for a singular cell.
+ *   pet_ewald_plan: h_cells [S,3,3] fp64, h_pbc [S,3], h_first_atom [S+1] on the host. Builds the per-system k lists in fp64
+ *     and uploads them (allocations kept until the next plan / destroy; blocking host-to-device copies, no read-back). The
+ *     plan is valid while the cells and the batch layout do not change (every step of fixed-cell MD). Not inside a capture.
+ *   pet_ewald_num_kvectors: k-vectors of system s (0 for a non-periodic one); the kernels walk one of every pair (k, -k).
+ *   pet_ewald_potential: d_positions [N,3], d_charges [N,C] -> d_potential [N,C], any C >= 1.
+ *   pet_ewald_backward: d_grad_potential [N,C] -> d_grad_charges [N,C], d_grad_positions [N,3], d_grad_cells [S,3,3] (may be
+ *     NULL): dL/dcell at fixed Cartesian positions. Nothing is kept between the two calls.
+ *   d_workspace: pet_ewald_workspace_bytes(e, C) bytes (after the plan). No host synchronisation after the plan.
+ * PET_ERR_ARGUMENT: a pet_graph_from_batch handle, a graph built under an adaptive cutoff (it drops edges inside R), a graph
+ * of a model without nl_is_strict, a graph whose cutoff, atom or system count differ from the plan's.
+ * PET_ERR_UNSUPPORTED: mixed pbc; a cell with more than PET_EWALD_MAX_INDEX reciprocal indices along an axis. */
+#define PET_EWALD_MAX_INDEX 63
+typedef struct pet_ewald pet_ewald_t;
+int pet_ewald_create(double smearing, double kspace_resolution, double cutoff, pet_ewald_t** out);
+void pet_ewald_destroy(pet_ewald_t* e);
+int64_t pet_ewald_kvectors_host(const double* h_cell, double kspace_resolution, double* h_out, int64_t capacity);
+int pet_ewald_plan(pet_ewald_t* e, const double* h_cells, const int32_t* h_pbc, const int64_t* h_first_atom,
+                   int64_t n_systems);
+int64_t pet_ewald_num_kvectors(const pet_ewald_t* e, int64_t system);
+int64_t pet_ewald_workspace_bytes(const pet_ewald_t* e, int64_t n_channels);
+int pet_ewald_potential(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
+                        int32_t n_channels, float* d_potential, void* d_workspace, int64_t workspace_bytes, void* stream);
+int pet_ewald_backward(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
+                       const float* d_grad_potential, int32_t n_channels, float* d_grad_charges, float* d_grad_positions,
+                       float* d_grad_cells, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Rotational augmentation (utils/augmentation.py:O3Augmenter; pet/trainer.py:187-193, 288-303) -------------------------
  * A random element of O(3) per system of a collated batch, drawn and applied on the device. A rigid transformation of
  * positions and cell leaves fractional coordinates alone, so the batch's (center, neighbor, cell_shift) list stays valid:

@@ -54,6 +54,8 @@ SYMBOLS = [
     "pet_llpr_covariance_finalize", "pet_llpr_variance", "pet_llpr_ensemble",
     "pet_zbl_create", "pet_zbl_destroy", "pet_zbl_cutoff", "pet_zbl_pair_table", "pet_zbl_workspace_bytes",
     "pet_zbl_forward", "pet_zbl_backward", "pet_zbl_hessian_vector",
+    "pet_ewald_create", "pet_ewald_destroy", "pet_ewald_kvectors_host", "pet_ewald_plan", "pet_ewald_num_kvectors",
+    "pet_ewald_workspace_bytes", "pet_ewald_potential", "pet_ewald_backward",
     "pet_o3_draw", "pet_o3_apply", "pet_o3_wigner", "pet_o3_apply_spherical",
     "pet_baseline_workspace_bytes", "pet_species_counts", "pet_composition_accumulate", "pet_target_moments",
     "pet_targets_remove",
@@ -282,6 +284,18 @@ def load() -> ctypes.CDLL:
     lib.pet_zbl_forward.argtypes = [P, P, P, P]
     lib.pet_zbl_backward.argtypes = [P, P, P, P, P, P, P, c_int64, P]
     lib.pet_zbl_hessian_vector.argtypes = [P, P, P, P, P, P, P, P, P, c_int64, P]
+    lib.pet_ewald_create.argtypes = [c_double, c_double, c_double, POINTER(P)]
+    lib.pet_ewald_destroy.argtypes = [P]
+    lib.pet_ewald_destroy.restype = None
+    lib.pet_ewald_kvectors_host.argtypes = [POINTER(c_double), c_double, POINTER(c_double), c_int64]
+    lib.pet_ewald_kvectors_host.restype = c_int64
+    lib.pet_ewald_plan.argtypes = [P, POINTER(c_double), POINTER(c_int32), POINTER(c_int64), c_int64]
+    lib.pet_ewald_num_kvectors.argtypes = [P, c_int64]
+    lib.pet_ewald_num_kvectors.restype = c_int64
+    lib.pet_ewald_workspace_bytes.argtypes = [P, c_int64]
+    lib.pet_ewald_workspace_bytes.restype = c_int64
+    lib.pet_ewald_potential.argtypes = [P, P, P, P, c_int32, P, P, c_int64, P]
+    lib.pet_ewald_backward.argtypes = [P, P, P, P, P, c_int32, P, P, P, P, c_int64, P]
     lib.pet_o3_draw.argtypes = [c_uint64, c_uint64, c_int32, c_int64, P, P]
     lib.pet_o3_apply.argtypes = [P, c_int64, c_int32, POINTER(O3Array), P]
     lib.pet_o3_wigner.argtypes = [P, c_int64, c_int32, P, P, P]

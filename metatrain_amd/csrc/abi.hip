@@ -843,6 +843,7 @@ int pet_graph_build(const pet_model_t* pm, const float* d_positions, const float
                 "graph too large for int32 indices");
     pet_graph_t* pg = new pet_graph_t();
     pg->cutoff = pm->m.h.cutoff;
+    pg->strict = pm->m.h.nl_is_strict != 0;
     int rc = graph_build(pm->m, d_positions, d_cells, d_centers, d_neighbors, d_cell_shifts, d_species,
                          d_system_indices, n_nodes, n_edges_in, n_systems, d_workspace, workspace_bytes,
                          pg->g, (hipStream_t)stream);

@@ -441,4 +441,5 @@ struct ProfScope {
 struct pet_graph {
     pet::Graph g;
     float cutoff;
+    bool strict = false;  // built by a model with nl_is_strict (long_range.enable): every pair inside the cutoff is kept
 };

@@ -1,0 +1,324 @@
+"""Long-range (Ewald) features of a ``long_range: {enable: true}`` PET on the HIP path (``utils/long_range.py:108-195``,
+``pet/model.py:505-518, 664-695``).
+
+With ``L`` readout layers and node features ``h_l [N, d_node]`` the reference computes
+
+    x    = (sum_l h_l) / sqrt(L)
+    q    = charges_map(x)                        Linear(d_node, d_node)
+    V    = potential(q; positions, cell, NL)     per system, [n, d_node]
+    lr   = out_projection(V)                     Linear -> SiLU -> Linear
+    h_l <- (h_l + lr) / sqrt(2)   for every l,   then predict as usual
+
+``potential`` is torch-pme's ``CoulombPotential`` / ``EwaldCalculator``. torch-pme is not part of the reference tree and its
+tests pin no values, so the operator is fixed HERE by definition (the formulas are in ``include/pet_hip.h``, block
+``pet_ewald_*``, and DESIGN.md section 18) and pinned to an independent fp64 oracle (``tests/_ewald_oracle.py``). **Parity
+with torch-pme is not pinned.** Every convention constant of that definition is in :data:`CONVENTIONS` below (and, as the
+same table); the kernels hold them as ``EW_PREFACTOR``, the three coefficients ``pet_ewald_potential``
+passes to ``k_ew_finish`` and the weight ``pet_ewald_plan`` gives every k-vector (``csrc/ewald.hip``).
+
+:class:`EwaldHip` is the operator (``csrc/ewald.hip``: structure factors, the gather back to atoms and the open all-pairs sum
+as fp32 matrix-core GEMMs with a generated operand; fixed summation orders, no atomics), :class:`LongRangeFeaturizerHip` the
+featuriser under the reference's state-dict keys, :func:`energy_and_gradient` the whole model: energies, dE/dR and dE/dcell.
+
+``P3M`` is not built. The reference evaluates a ``use_ewald: false`` model with P3M, an approximation of this same sum: such a
+model loads only with an explicit ``p3m_as_ewald=True``.
+"""
+import logging
+import math
+from ctypes import byref, c_double, c_int32, c_int64, c_void_p
+from typing import Dict, List, Optional, Sequence
+
+import torch
+
+from . import _lib
+from . import runtime as rt
+from ._lib import PetHipError, check
+
+# The convention table (sigma = smearing, lambda = kspace_resolution, Omega = |det cell|, R = the model cutoff).
+CONVENTIONS = {
+    "prefactor": "P = 1/2 on every term (torch-pme's Calculator halves the pair sum)",
+    "kernel": "G(k) = 4 pi exp(-sigma^2 k^2 / 2) / k^2, summed over k != 0 and divided by Omega",
+    "self": "- q_i sqrt(2 / pi) / sigma",
+    "background": "- (2 pi sigma^2 / Omega) sum_j q_j  (= pi / (Omega a^2) with a = 1 / (sqrt(2) sigma))",
+    "k_set": "the sphere |k| <= 2 pi / lambda of the reciprocal lattice 2 pi n cell^{-T} (torch-pme: the box of a mesh)",
+    "exclusion": "- sum over the model's edges of q_j erf(d / (sqrt(2) sigma)) / d * (1 + cos(pi d / R)) / 2",
+    "open": "P sum_{j != i} q_j (1 - (1 + cos(pi d / R)) / 2 [d < R]) / d over all pairs of a system without pbc",
+}
+PREFACTOR = 0.5
+
+REFERENCE_KEYS = ("long_range_featurizer.charges_map.weight", "long_range_featurizer.charges_map.bias",
+                  "long_range_featurizer.out_projection.0.weight", "long_range_featurizer.out_projection.0.bias",
+                  "long_range_featurizer.out_projection.2.weight", "long_range_featurizer.out_projection.2.bias")
+
+_warned_kset = False
+
+
+def truncation_factor(smearing: float, kspace_resolution: float) -> float:
+    """``exp(-(sigma 2 pi / lambda)^2 / 2)``: the size of the first k-space terms left out, relative to the largest."""
+    return math.exp(-0.5 * (float(smearing) * 2.0 * math.pi / float(kspace_resolution)) ** 2)
+
+
+def resolve_hypers(hypers: dict, p3m_as_ewald: bool = False) -> dict:
+    """The ``long_range`` block of a model's hypers with the reference's defaults filled in, checked for what this package
+    serves. Raises for a model without ``long_range.enable``, for ``use_ewald: false`` without ``p3m_as_ewald=True`` and for
+    an adaptive cutoff together with long range."""
+    from .pet.hypers import long_range_hypers
+
+    lr = long_range_hypers(hypers)
+    if not lr["enable"]:
+        raise PetHipError("long_range.enable is false: this model has no long-range featuriser")
+    if not lr["use_ewald"] and not p3m_as_ewald:
+        raise PetHipError("long_range.use_ewald is false: the reference evaluates this model with P3M, which is not built. "
+                          "Ewald summation is the sum P3M approximates: pass p3m_as_ewald=True to evaluate with it")
+    if hypers.get("num_neighbors_adaptive"):
+        raise PetHipError("long_range together with num_neighbors_adaptive: the adaptive cutoff drops edges inside the "
+                          "exclusion radius, on which the long-range exclusion term relies")
+    return lr
+
+
+def kvectors(cell, kspace_resolution: float) -> torch.Tensor:
+    """The k-set ``[K, 3]`` (fp64, host) the plan builds for one ``cell [3, 3]``: every ``k = 2 pi n cell^{-T} != 0`` with
+    ``|k| <= 2 pi / kspace_resolution`` (``pet_ewald_kvectors_host``; the kernels walk one of every pair ``(k, -k)``).
+    Needs no GPU."""
+    lib = _lib.load()
+    flat = [float(x) for x in torch.as_tensor(cell, dtype=torch.float64).reshape(-1).tolist()]
+    if len(flat) != 9:
+        raise ValueError("cell must be [3, 3]")
+    h = (c_double * 9)(*flat)
+    n = int(lib.pet_ewald_kvectors_host(h, float(kspace_resolution), None, 0))
+    if n < 0:
+        raise PetHipError("singular cell or non-positive kspace_resolution")
+    buf = (c_double * (3 * max(n, 1)))()
+    lib.pet_ewald_kvectors_host(h, float(kspace_resolution), buf, n)
+    return torch.tensor(list(buf)[: 3 * n], dtype=torch.float64).reshape(n, 3)
+
+
+def _first_atoms(system_indices: torch.Tensor, n_systems: int) -> List[int]:
+    counts = torch.bincount(system_indices.long(), minlength=n_systems).cpu().tolist()
+    first = [0]
+    for c in counts:
+        first.append(first[-1] + int(c))
+    return first
+
+
+class EwaldHip:
+    """``pet_ewald_t``: the operator ``q [N, C] -> V [N, C]`` and its adjoints on device tensors."""
+
+    def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5):
+        global _warned_kset
+        self.lib = _lib.load()
+        self.smearing, self.kspace_resolution, self.cutoff = float(smearing), float(kspace_resolution), float(cutoff)
+        self._handle = c_void_p()
+        check(self.lib.pet_ewald_create(self.smearing, self.kspace_resolution, self.cutoff, byref(self._handle)))
+        t = truncation_factor(self.smearing, self.kspace_resolution)
+        if t > 1e-7 and not _warned_kset:
+            _warned_kset = True
+            logging.warning(f"long range: exp(-(smearing 2 pi / kspace_resolution)^2 / 2) = {t:.1e} exceeds 1e-7: the k-space "
+                            "sum has not converged inside the k-set, so the result depends on the SHAPE of the k-set (a "
+                            "sphere here, the box of a mesh in torch-pme), which is not pinned")
+        self.n_systems = -1
+        self._workspace: Optional[torch.Tensor] = None
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        try:
+            if h is not None and h.value:
+                self.lib.pet_ewald_destroy(h)
+                self._handle = c_void_p()
+        except Exception:
+            pass
+
+    @property
+    def handle(self) -> c_void_p:
+        return self._handle
+
+    def plan(self, cells, pbcs: Sequence[Sequence[bool]], first_atom: Sequence[int]) -> "EwaldHip":
+        """Build the per-system k-vector lists (host fp64) for ``cells [S, 3, 3]``, ``pbcs [S][3]`` and the batch layout
+        ``first_atom [S + 1]`` (``pet_ewald_plan``). Valid for as long as the cells do not change. Mixed ``pbc`` raises."""
+        cells_t = torch.as_tensor(cells).detach().to("cpu", torch.float64).reshape(-1, 3, 3)
+        n_sys = int(cells_t.shape[0])
+        if len(pbcs) != n_sys or len(first_atom) != n_sys + 1:
+            raise PetHipError(f"{n_sys} cells, {len(pbcs)} pbc entries and {len(first_atom)} first_atom entries do not "
+                              "describe one batch")
+        h_cells = (c_double * (9 * max(n_sys, 1)))(*[float(x) for x in cells_t.reshape(-1).tolist()])
+        h_pbc = (c_int32 * (3 * max(n_sys, 1)))(*[int(bool(x)) for p in pbcs for x in p])
+        h_first = (c_int64 * (n_sys + 1))(*[int(x) for x in first_atom])
+        check(self.lib.pet_ewald_plan(self._handle, h_cells, h_pbc, h_first, n_sys))
+        self.n_systems = n_sys
+        self._workspace = None
+        return self
+
+    def num_kvectors(self, system: int) -> int:
+        n = int(self.lib.pet_ewald_num_kvectors(self._handle, int(system)))
+        if n < 0:
+            raise PetHipError("no plan, or no such system")
+        return n
+
+    def _ws(self, channels: int, device) -> torch.Tensor:
+        nbytes = int(self.lib.pet_ewald_workspace_bytes(self._handle, channels))
+        if nbytes < 0:
+            raise PetHipError("pet_ewald_workspace_bytes failed: call plan() first")
+        if self._workspace is None or self._workspace.numel() < nbytes or self._workspace.device != device:
+            self._workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+        return self._workspace
+
+    def potential(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor) -> torch.Tensor:
+        """``V [N, C]`` for ``charges [N, C]`` (``pet_ewald_potential``)."""
+        rt._require_cuda(positions, charges)
+        pos = positions.detach().to(torch.float32).contiguous()
+        q = charges.detach().to(torch.float32).reshape(pos.shape[0], -1).contiguous()
+        out = torch.empty_like(q)
+        ws = self._ws(q.shape[1], q.device)
+        check(self.lib.pet_ewald_potential(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), int(q.shape[1]),
+                                           rt._ptr(out), rt._ptr(ws), ws.numel(), rt._stream()))
+        return out
+
+    def backward(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor, grad_potential: torch.Tensor,
+                 want_cell_grad: bool = False):
+        """``(dL/dq [N, C], dL/dR [N, 3])`` and on request ``dL/dcell [S, 3, 3]`` (fixed Cartesian positions) for
+        ``dL/dV = grad_potential`` (``pet_ewald_backward``)."""
+        rt._require_cuda(positions, charges, grad_potential)
+        pos = positions.detach().to(torch.float32).contiguous()
+        q = charges.detach().to(torch.float32).reshape(pos.shape[0], -1).contiguous()
+        g = grad_potential.detach().to(torch.float32).reshape(q.shape).contiguous()
+        gq = torch.empty_like(q)
+        gpos = torch.empty_like(pos)
+        gcell = torch.empty((graph.n_systems, 3, 3), dtype=torch.float32, device=q.device) if want_cell_grad else None
+        ws = self._ws(q.shape[1], q.device)
+        check(self.lib.pet_ewald_backward(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), rt._ptr(g), int(q.shape[1]),
+                                          rt._ptr(gq), rt._ptr(gpos), rt._ptr(gcell), rt._ptr(ws), ws.numel(), rt._stream()))
+        return (gq, gpos, gcell) if want_cell_grad else (gq, gpos)
+
+
+class _EwaldFn(torch.autograd.Function):
+    """The operator as an autograd node over the two HIP calls: gradients for charges, positions and cells."""
+
+    @staticmethod
+    def forward(ctx, charges, positions, cells, ewald, graph):
+        ctx.ewald, ctx.graph = ewald, graph
+        ctx.save_for_backward(charges, positions)
+        ctx.cell_shape = cells.shape
+        return ewald.potential(graph, positions, charges)
+
+    @staticmethod
+    def backward(ctx, grad):
+        charges, positions = ctx.saved_tensors
+        gq, gpos, gcell = ctx.ewald.backward(ctx.graph, positions, charges, grad, want_cell_grad=True)
+        return gq, gpos, gcell.reshape(ctx.cell_shape), None, None
+
+
+class LongRangeFeaturizerHip:
+    """``LongRangeFeaturizer`` (``utils/long_range.py``) on the device: ``charges_map`` and ``out_projection`` under the
+    reference's state-dict keys (fp32 torch ops on the device; there is no TF32 on gfx950) around :class:`EwaldHip`."""
+
+    def __init__(self, hypers: dict, device=None, p3m_as_ewald: bool = False):
+        self.long_range = resolve_hypers(hypers, p3m_as_ewald)
+        self.d = int(hypers["d_node"])
+        self.cutoff = float(hypers["cutoff"])
+        self.ewald = EwaldHip(self.long_range["smearing"], self.long_range["kspace_resolution"], self.cutoff)
+        dev = torch.device("cpu") if device is None else torch.device(device)
+        d = self.d
+        self.params: Dict[str, torch.Tensor] = {}
+        for name in ("charges_map", "out_projection.0", "out_projection.2"):
+            lin = torch.nn.Linear(d, d)
+            self.params[name + ".weight"] = lin.weight.detach().to(dev, torch.float32)
+            self.params[name + ".bias"] = lin.bias.detach().to(dev, torch.float32)
+
+    def state_dict(self, prefix: str = "long_range_featurizer.") -> Dict[str, torch.Tensor]:
+        return {prefix + k: v for k, v in self.params.items()}
+
+    def load_state_dict(self, state: Dict[str, torch.Tensor], prefix: str = "long_range_featurizer.") -> None:
+        d = self.d
+        dev = next(iter(self.params.values())).device
+        for k in list(self.params):
+            if prefix + k not in state:
+                raise PetHipError(f"the state dict has no '{prefix + k}': not a long-range checkpoint")
+            t = state[prefix + k].detach().to(dev, torch.float32).contiguous()
+            want = (d, d) if k.endswith("weight") else (d,)
+            if tuple(t.shape) != want:
+                raise PetHipError(f"'{prefix + k}' has shape {tuple(t.shape)}, expected {want}")
+            self.params[k] = t
+
+    @classmethod
+    def from_state_dict(cls, hypers: dict, state: Dict[str, torch.Tensor], device=None, p3m_as_ewald: bool = False,
+                        prefix: str = "long_range_featurizer.") -> "LongRangeFeaturizerHip":
+        self = cls(hypers, device, p3m_as_ewald)
+        self.load_state_dict(state, prefix)
+        return self
+
+    def to(self, device) -> "LongRangeFeaturizerHip":
+        self.params = {k: v.to(device) for k, v in self.params.items()}
+        return self
+
+    def plan(self, cells, pbcs, first_atom) -> "LongRangeFeaturizerHip":
+        self.ewald.plan(cells, pbcs, first_atom)
+        return self
+
+    def __call__(self, features: torch.Tensor, positions: torch.Tensor, cells: torch.Tensor, graph: rt.HipGraph):
+        """``out_projection(potential(charges_map(features)))`` ``[N, d_node]``, differentiable by torch autograd with
+        respect to ``features``, ``positions`` and ``cells``."""
+        rt._require_cuda(features, positions)
+        p = self.params
+        q = torch.nn.functional.linear(features, p["charges_map.weight"], p["charges_map.bias"])
+        v = _EwaldFn.apply(q, positions, cells, self.ewald, graph)
+        hid = torch.nn.functional.silu(torch.nn.functional.linear(v, p["out_projection.0.weight"], p["out_projection.0.bias"]))
+        return torch.nn.functional.linear(hid, p["out_projection.2.weight"], p["out_projection.2.bias"])
+
+
+def energy_and_gradient(model: rt.HipModel, featurizer: LongRangeFeaturizerHip, graph: rt.HipGraph, pbcs, target: str = "energy",
+                        want_cell_grad: bool = False, outputs: Sequence[str] = (), replan: bool = True):
+    """The whole long-range model on one batch: ``(per-atom energies [N], per-system energies [S], dE/dR [N, 3])`` and, on
+    request, ``dE/dcell [S, 3, 3]`` (fixed Cartesian positions) of the summed energy.
+
+    ``features_layers -> featuriser -> (h_l + lr) / sqrt(2) -> predict`` per readout layer, summed; back through
+    ``predict_backward``, the featuriser's adjoint (torch autograd over the HIP operator), ``backward_features_layers`` and
+    ``backward_geometry``, plus the operator's own position and cell gradients. ``pbcs [S][3]``: a graph does not record
+    them. ``replan=False`` reuses the featuriser's plan (fixed-cell MD: the k-vectors depend on the cells alone)."""
+    if outputs:
+        raise PetHipError(f"auxiliary outputs {list(outputs)} ('feature', last-layer features) of a long-range model are not "
+                          "built: the long-range entry point returns energies and their gradients")
+    if not bool((model.hypers.get("long_range") or {}).get("enable")):
+        raise PetHipError("this model has no long_range.enable: use the ordinary entry points")
+    if model.hypers.get("num_neighbors_adaptive"):
+        raise PetHipError("long_range together with num_neighbors_adaptive is not served (the adaptive cutoff drops edges "
+                          "inside the exclusion radius)")
+    if getattr(graph, "_sys", None) is None:
+        raise PetHipError("the long-range model needs a HipGraph built from positions (not from batch_data)")
+    dev = graph.workspace.device
+    if replan or featurizer.ewald.n_systems != graph.n_systems:
+        featurizer.plan(graph._cells, pbcs, _first_atoms(graph._sys, graph.n_systems))
+    fw = rt.HipForward(model, graph)
+    nfs, efs = fw.features_layers()
+    n_l = len(nfs)
+    leaves = [t.detach().requires_grad_(True) for t in nfs]
+    pos = graph._pos.detach().clone().requires_grad_(True)
+    cells = graph._cells.detach().clone().requires_grad_(True)
+    x = leaves[0]
+    for t in leaves[1:]:
+        x = x + t
+    lr = featurizer(x * (1.0 / math.sqrt(n_l)), pos, cells, graph)
+    mixed = [(t + lr) * math.sqrt(0.5) for t in leaves]
+    hs = [t.detach().contiguous() for t in mixed]
+    atomic = None
+    for l in range(n_l):
+        a = rt.predict(model, graph, hs[l], efs[l], target, readout_layer=l)
+        atomic = a if atomic is None else atomic + a
+    if atomic.shape[1] != 1:
+        raise PetHipError(f"target '{target}' has {atomic.shape[1]} properties: energies have one")
+    atomic = atomic.reshape(-1)
+    energies = torch.zeros(graph.n_systems, dtype=torch.float32, device=dev)
+    check(model.lib.pet_sum_over_atoms(graph.handle, rt._ptr(atomic), rt._ptr(energies), rt._stream()))
+    ones = torch.ones((graph.n_nodes, 1), dtype=torch.float32, device=dev)
+    g_h, g_ef, g_fc = [], [], None
+    for l in range(n_l):
+        a, b, c = rt.predict_backward(model, graph, hs[l], efs[l], ones, target, readout_layer=l)
+        g_h.append(a)
+        g_ef.append(b)
+        g_fc = c if g_fc is None else g_fc + c
+    torch.autograd.backward(mixed, g_h)
+    geo, gfc = fw.backward_features_layers([t.grad for t in leaves], g_ef)
+    out = fw.backward_geometry(geo, gfc + g_fc, want_cell_grad=want_cell_grad)
+    if want_cell_grad:
+        gpos, gcell = out
+        return atomic, energies, gpos + pos.grad, gcell + cells.grad
+    return atomic, energies, out + pos.grad

@@ -33,7 +33,9 @@ use -- ``normalization = "LayerNorm"``, ``transformer_type = "PostLN"``, ``featu
 (``pet/checkpoints.py:190-205``) --, both adaptive-cutoff methods ("solver" and the legacy "grid") and system conditioning
 (charge / spin multiplicity): inference, forces AND training (energy and force loss) for all of them, edge-free batches of
 isolated atoms and empty systems included. Not built (raise loudly): diagnostic capture, double backward through the three
-inference nodes, long-range features.
+inference nodes. Long-range models (``long_range.enable``) are refused by this mirror: their
+featuriser sits between ``calculate_features`` and ``predict``, and ``metatrain_amd.long_range`` evaluates it (energies,
+dE/dR, dE/dcell).
 """
 from math import prod
 from typing import Dict, List, Optional, Tuple
@@ -367,6 +369,7 @@ class PETBackend(torch.nn.Module):
 
     def __init__(self, hypers: dict, atomic_types: List[int]) -> None:
         super().__init__()
+        rt.refuse_long_range(hypers, "the three-node PETBackend mirror")
         h = rt.hypers_struct(hypers, atomic_types)  # validates; unsupported variants raise here
         fields = [float(getattr(h, name)) for name, _ in h._fields_]
         # PetHipBackend(hypers): the first 16 fields of pet_hypers_t, the SiLU flag, then the remaining fields (normalization,

@@ -21,11 +21,28 @@ DEFAULT_MODEL_HYPERS = {
     "transformer_type": "PreLN",
     "featurizer_type": "feedforward",
     "zbl": False,
-    "long_range": {"enable": False},
+    "long_range": {"enable": False},  # completed from DEFAULT_LONG_RANGE_HYPERS where the other keys are read
     "system_conditioning": False,
     "max_charge": 10,
     "max_spin_multiplicity": 10,
 }
+
+# ``LongRangeHypers`` (src/metatrain/utils/long_range.py:11-26). A model dictionary may carry only ``enable``: the other four
+# keys are filled in from here (``long_range_hypers``).
+DEFAULT_LONG_RANGE_HYPERS = {
+    "enable": False,
+    "use_ewald": False,
+    "smearing": 1.4,
+    "kspace_resolution": 1.33,
+    "interpolation_nodes": 5,
+}
+
+
+def long_range_hypers(hypers: dict) -> dict:
+    """The ``long_range`` block of ``hypers`` with the reference's defaults for the keys it leaves out."""
+    out = dict(DEFAULT_LONG_RANGE_HYPERS)
+    out.update(hypers.get("long_range") or {})
+    return out
 
 
 def default_hypers() -> dict:

@@ -206,6 +206,7 @@ class LLPRUncertainty:
 
     def __init__(self, model: rt.HipModel, params: Dict[str, torch.Tensor], targets: Dict[str, str],
                  num_ensemble_members: Optional[Dict[str, int]] = None):
+        rt.refuse_long_range(getattr(model, "hypers", None) or {}, "LLPR")
         self.model = model
         self.lib = model.lib
         self.F = int(self.lib.pet_llpr_feature_size(model.handle))

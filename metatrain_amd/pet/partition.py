@@ -56,6 +56,12 @@ def _zbl_of(model, zbl, what: str):
                               model.hypers.get("num_neighbors_adaptive") is not None, what)
 
 
+def _refuse_long_range(model, what: str = "the box partition") -> None:
+    from ..runtime import refuse_long_range
+
+    refuse_long_range(getattr(model, "hypers", None) or {}, what)
+
+
 def energy_and_gradient(model, positions: torch.Tensor, species: torch.Tensor, cell: torch.Tensor, pbc: Sequence[bool],
                         world: int, rank: int, all_reduce: Optional[Callable[[torch.Tensor], None]] = None,
                         neighbor_list: Optional[Callable] = None, runtime=None, hops: Optional[int] = None, zbl=None):
@@ -67,6 +73,7 @@ def energy_and_gradient(model, positions: torch.Tensor, species: torch.Tensor, c
     (default radii), ``False`` (the network alone) or None (``model.hypers["zbl"]`` decides): energy and gradient include
     the ZBL term; a model whose neighbour list cannot serve it (cutoff below the ZBL cutoff, adaptive cutoff) is refused.
     Returns ``(energy [1], gradient [N, 3], n_sub, n_owned)``."""
+    _refuse_long_range(model)
     z = _zbl_of(model, zbl, "the partitioned box")
     if runtime is None:
         from .. import runtime
@@ -152,6 +159,7 @@ def energy_and_gradient_exchange(model, positions: torch.Tensor, species: torch.
 
     from ..partition import slab_owner
 
+    _refuse_long_range(model, "the per-layer exchange")
     z = _zbl_of(model, zbl, "the per-layer exchange")
     if runtime is None:
         from .. import runtime

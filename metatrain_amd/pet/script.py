@@ -13,7 +13,7 @@ from typing import Dict, List, NamedTuple, Optional
 import torch
 
 from ..build import TORCH_LIB
-from ..runtime import hypers_struct
+from ..runtime import hypers_struct, refuse_long_range
 from .._lib import PetHipError
 
 _loaded = False
@@ -86,6 +86,7 @@ def make_core(hypers: dict, atomic_types: List[int], state_dict: Dict[str, torch
         raise PetHipError("this model has `zbl: true` and the core evaluates the network alone: build both parts with "
                           "make_core_and_zbl(...) and pass its table as ExportedEnergyModel(core, ..., zbl=table), or "
                           "pass zbl=False for the bare network")
+    refuse_long_range(hypers, "the scripted model (ExportedEnergyModel, csrc/torch_ops.cpp)")
     load_ops()
     block = block or target
     h = hypers_struct(hypers, atomic_types)

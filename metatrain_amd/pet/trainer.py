@@ -16,7 +16,7 @@ import torch
 
 from .. import distributed as D
 from ..loss import STATE_WORDS, PointwiseLoss, expand_loss_hypers
-from ..runtime import HipForward, HipGraph, HipModel
+from ..runtime import HipForward, HipGraph, HipModel, refuse_long_range
 
 DEFAULT_TRAINER_HYPERS = {  # pet/documentation.py TrainerHypers defaults that the step depends on
     "learning_rate": 1e-4,
@@ -159,6 +159,7 @@ class TrainStep:
     parameters, is not part of the loss graph and is added back at evaluation (``ExportedEnergyModel(..., zbl=...)``)."""
 
     def __init__(self, model: HipModel, hypers: Optional[dict] = None, steps_per_epoch: int = 1):
+        refuse_long_range(getattr(model, "hypers", None) or {}, "training (TrainStep)")
         self.model = model
         self.hypers = dict(DEFAULT_TRAINER_HYPERS)
         self.hypers.update(hypers or {})

@@ -29,6 +29,14 @@ def _require_cuda(*tensors: torch.Tensor) -> None:
             )
 
 
+def refuse_long_range(hypers: dict, what: str) -> None:
+    """Raise for a ``long_range.enable`` model at an entry point that does not evaluate the long-range featuriser: without
+    it the model would silently compute something else. ``metatrain_amd.long_range.energy_and_gradient`` evaluates it."""
+    if bool((hypers.get("long_range") or {}).get("enable")):
+        raise PetHipError(f"{what} of a long-range model (long_range.enable) is not built: it would leave the long-range "
+                          "features out. Energies, dE/dR and dE/dcell: metatrain_amd.long_range.energy_and_gradient")
+
+
 def hypers_struct(hypers: dict, atomic_types: List[int]) -> PetHypers:
     fn = hypers["cutoff_function"].lower()
     if fn not in ("bump", "cosine"):
@@ -714,6 +722,7 @@ def hessian_vector_product(model: HipModel, graph: HipGraph, u: torch.Tensor, u_
     ``[S,3,3]`` and the tangents ``e'_i [N]``. Needs no forward pass and touches no gradient slot; it runs on the
     size-generic dual pass for every model size. Adaptive-cutoff models and graphs with a per-layer exchange raise
     (``PET_ERR_UNSUPPORTED``). ``workspace``: a uint8 buffer of at least ``hvp_workspace_bytes(model, graph)`` to reuse."""
+    refuse_long_range(getattr(model, "hypers", None) or {}, "the Hessian-vector product")
     _require_cuda(u)
     dev = u.device
     n, s = graph.n_nodes, graph.n_systems

@@ -98,19 +98,29 @@ def potential_batch(pos, cells, pbcs, first_atom, q, centers, neighbors, shifts,
 def madelung_nacl(smearing: float) -> float:
     """The NaCl Madelung constant (nearest distance 1) from the no-exclusion mode: k-space + self + background of the
     definition plus the real-space ``erfc`` sum over images."""
-    a = 2.0
-    cell = torch.eye(3, dtype=torch.float64) * a
+    pos, cell, q = nacl_system()
+    v = kspace_self_background(pos, cell, q, smearing, None, kmax=9.0 / smearing)
+    return float((v + real_space_erfc(pos, cell, q, smearing))[0, 0])
+
+
+def nacl_system():
+    """Rock salt with nearest distance 1: ``(positions [8, 3], cell [3, 3], charges [8, 1])``, fp64, the atom at the origin
+    first and charged +1."""
+    cell = torch.eye(3, dtype=torch.float64) * 2.0
     pos = torch.tensor(list(itertools.product(range(2), repeat=3)), dtype=torch.float64)
     q = torch.tensor([[(-1.0) ** int(p.sum())] for p in pos], dtype=torch.float64)
-    v = kspace_self_background(pos, cell, q, smearing, None, kmax=9.0 / smearing)
+    return pos, cell, q
+
+
+def real_space_erfc(pos, cell, q, smearing):
+    """``sum over images j != i of q_j erfc(d / a) / d`` out to ``8 sigma``, without the prefactor (fp64)."""
     rc = 8.0 * smearing
-    m = int(math.ceil(rc / a))
+    m = int(math.ceil(rc / float(cell.diagonal().min())))
     S = torch.cartesian_prod(*[torch.arange(-m, m + 1)] * 3).double()
     D = pos[None, :, None, :] - pos[:, None, None, :] + (S @ cell)[None, None]
     d = D.norm(dim=-1)
     i, j, s = torch.nonzero((d > 1e-9) & (d < rc), as_tuple=True)
-    sr = torch.zeros_like(q).index_add(0, i, q[j] * (torch.erfc(d[i, j, s] / (math.sqrt(2.0) * smearing)) / d[i, j, s])[:, None])
-    return float((v + sr)[0, 0])
+    return torch.zeros_like(q).index_add(0, i, q[j] * (torch.erfc(d[i, j, s] / (math.sqrt(2.0) * smearing)) / d[i, j, s])[:, None])
 
 
 # ---- inputs ----------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import _ewald_oracle as eo
+import ewald_cases as ec
 import gen_shapes as gs
 from _memo import memo_oracle
 from oracle import pet as opet
@@ -36,10 +37,7 @@ def _check(case, names, got, ref, f32):
 
 
 def _lr_hypers(**extra):
-    h = dict(opet.DEFAULT_HYPERS, **extra)
-    h["long_range"] = {"enable": True, "use_ewald": True, "smearing": SMEARING, "kspace_resolution": RESOLUTION,
-                       "interpolation_nodes": 5}
-    return h
+    return ec.lr_hypers(SMEARING, RESOLUTION, **extra)
 
 
 @functools.lru_cache(maxsize=None)
@@ -59,34 +57,8 @@ def _reference(batch, q, gv, dtype):
     return eo.operator_reference(batch, q, gv, SMEARING, RESOLUTION, CUTOFF, dtype)
 
 
-def _graph(batch, dev, hypers=None, species=None):
-    """The model's strict graph of a batch (a weight-less model builds it: the operator reads rows and distances only)."""
-    from metatrain_amd import runtime as rt
-
-    model = rt.HipModel(hypers or _lr_hypers(), eo.TYPES)
-    model.load_species_table()
-    n = batch["positions"].shape[0]
-    z = torch.full((n,), 6, dtype=torch.int32) if species is None else species
-    graph = rt.HipGraph(model, batch["positions"].float().to(dev), batch["cells"].float().to(dev), batch["centers"].to(dev),
-                        batch["neighbors"].to(dev), batch["cell_shifts"].to(dev), z.to(dev),
-                        batch["system_indices"].int().to(dev))
-    return model, graph
-
-
-def _operator(batch, dev):
-    from metatrain_amd import long_range as lr
-
-    model, graph = _graph(batch, dev)
-    ew = lr.EwaldHip(SMEARING, RESOLUTION, CUTOFF).plan(batch["cells"], batch["pbcs"], batch["first_atom"])
-    return model, graph, ew
-
-
-def _run(ew, graph, batch, q, gv, dev):
-    pos = batch["positions"].float().to(dev)
-    qd, gd = q.float().to(dev), gv.float().to(dev)
-    v = ew.potential(graph, pos, qd)
-    gq, gp, gc = ew.backward(graph, pos, qd, gd, want_cell_grad=True)
-    return v, gq, gp, gc
+# the model's graph of a batch, the planned operator on it and one run of it: shared with test_gpu_long_range_edges.py
+_graph, _operator, _run = ec.graph, ec.operator, ec.run
 
 
 @pytest.mark.parametrize("channels", [1, 24, 256])

@@ -818,20 +818,28 @@ __global__ __launch_bounds__(256) void k_soap_ps_bwd_m(SoapDims d, const float* 
 // and their accumulators are summed through LDS. Per-atom results do not depend on tile mates, so the (atomic)
 // order inside a bucket does not show in the output.
 // ---------------------------------------------------------------------------------------------
-constexpr int SP_MAXSETS = 8;
-struct SpInfo {  // device-side bucket table
-    int count[SP_MAXSETS], cursor[SP_MAXSETS], offs[SP_MAXSETS + 1], tstart[SP_MAXSETS + 1];
+constexpr int SP_MAXSETS = 8;         // networks of the species-sorted tiles (soap_sorted_ok; m.NT is built up to 8)
+constexpr int SP_TRAIN_MAXSETS = 16;  // networks of the training pass's bucket table (soap_train.h; refused beyond)
+// The bucket table and the k_sp_* kernels are sized by MS at compile time: the forward keeps MS = 8 (eight ballots per
+// atom in k_sp_fill), the training pass of a model with more networks takes MS = 16. An atom of a network >= MS would
+// index every array here out of range, so each host path checks n_sets <= MS before the first launch.
+template <int MS>
+struct SpInfoT {  // device-side bucket table
+    int count[MS], cursor[MS], offs[MS + 1], tstart[MS + 1];
 };
-__global__ void k_sp_count(const int* __restrict__ sp, int legacy, int N, SpInfo* __restrict__ info) {
-    __shared__ int hist[SP_MAXSETS];
-    if (threadIdx.x < SP_MAXSETS) hist[threadIdx.x] = 0;
+using SpInfo = SpInfoT<SP_MAXSETS>;
+template <int MS>
+__global__ void k_sp_count(const int* __restrict__ sp, int legacy, int N, SpInfoT<MS>* __restrict__ info) {
+    __shared__ int hist[MS];
+    if (threadIdx.x < MS) hist[threadIdx.x] = 0;
     __syncthreads();
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < N) atomicAdd(&hist[legacy ? sp[i] : 0], 1);
     __syncthreads();
-    if (threadIdx.x < SP_MAXSETS && hist[threadIdx.x]) atomicAdd(&info->count[threadIdx.x], hist[threadIdx.x]);
+    if (threadIdx.x < MS && hist[threadIdx.x]) atomicAdd(&info->count[threadIdx.x], hist[threadIdx.x]);
 }
-__global__ void k_sp_scan(int n_sets, SpInfo* __restrict__ info) {
+template <int MS>
+__global__ void k_sp_scan(int n_sets, SpInfoT<MS>* __restrict__ info) {
     info->offs[0] = 0;
     info->tstart[0] = 0;
     for (int s = 0; s < n_sets; s++) {
@@ -840,22 +848,23 @@ __global__ void k_sp_scan(int n_sets, SpInfo* __restrict__ info) {
         info->cursor[s] = 0;
     }
 }
-__global__ __launch_bounds__(1024) void k_sp_fill(const int* __restrict__ sp, int legacy, int N, SpInfo* __restrict__ info,
+template <int MS>
+__global__ __launch_bounds__(1024) void k_sp_fill(const int* __restrict__ sp, int legacy, int N, SpInfoT<MS>* __restrict__ info,
                                                    int* __restrict__ perm) {
     // one atomic per (workgroup of 1 024 atoms, network) instead of one per atom: 100 k atoms on 4 cursors serialised in
     // L2 (0.63 ms per atom, 0.08 ms per wave)
-    __shared__ int wcount[SP_MAXSETS][16], wbase[SP_MAXSETS][16];
+    __shared__ int wcount[MS][16], wbase[MS][16];
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int s = i < N ? (legacy ? sp[i] : 0) : -1;
     int rank = 0;
-    for (int t = 0; t < SP_MAXSETS; t++) {
+    for (int t = 0; t < MS; t++) {
         const unsigned long long m = __ballot(s == t);
         if (lane == 0) wcount[t][wave] = __popcll(m);
         if (s == t) rank = __popcll(m & ((1ull << lane) - 1ull));
     }
     __syncthreads();
-    if (threadIdx.x < SP_MAXSETS) {
+    if (threadIdx.x < MS) {
         const int t = threadIdx.x;
         int tot = 0;
         for (int w = 0; w < 16; w++) { wbase[t][w] = tot; tot += wcount[t][w]; }
@@ -864,6 +873,18 @@ __global__ __launch_bounds__(1024) void k_sp_fill(const int* __restrict__ sp, in
     }
     __syncthreads();
     if (s >= 0) perm[info->offs[s] + wbase[s][wave] + rank] = i;
+}
+// atoms bucketed by network into perm, on a table of MS networks; *offs = the table's offs[n_sets + 1] (device pointer)
+template <int MS>
+static int sp_bucket(const int* sp, int legacy, int N, int n_sets, void* info_, int* perm, const int** offs, hipStream_t st) {
+    PET_REQUIRE(n_sets <= MS, PET_ERR_UNSUPPORTED, "more networks than the bucket table holds");
+    SpInfoT<MS>* info = static_cast<SpInfoT<MS>*>(info_);
+    PET_HIP_CHECK(hipMemsetAsync(info, 0, sizeof(SpInfoT<MS>), st));
+    k_sp_count<MS><<<cdiv(N, 256), 256, 0, st>>>(sp, legacy, N, info);
+    k_sp_scan<MS><<<1, 1, 0, st>>>(n_sets, info);
+    k_sp_fill<MS><<<cdiv(N, 1024), 1024, 0, st>>>(sp, legacy, N, info, perm);
+    if (offs) *offs = info->offs;
+    return PET_OK;
 }
 // tile -> (network, first slot in perm, number of atoms); false if the tile index is past the last bucket
 __device__ __forceinline__ bool sp_tile(const SpInfo* __restrict__ info, int n_sets, int t, int& s, int& base, int& cnt) {
@@ -1782,10 +1803,7 @@ static int soap_fwd(const SoapModel& m, const Graph& g, void* ws, int64_t ws_byt
         {
             ProfScope ps("soap_tail", st, 2.0 * (double)N * d.S * d.H, (double)N * (packed ? d.Sp : d.S) * 4);
             if (soap_sorted_ok(m)) {
-                PET_HIP_CHECK(hipMemsetAsync(w.info, 0, sizeof(SpInfo), st));
-                k_sp_count<<<cdiv(N, 256), 256, 0, st>>>(g.sp, d.legacy, N, w.info);
-                k_sp_scan<<<1, 1, 0, st>>>(m.n_sets, w.info);
-                k_sp_fill<<<cdiv(N, 1024), 1024, 0, st>>>(g.sp, d.legacy, N, w.info, w.perm);
+                if (int rc = sp_bucket<SP_MAXSETS>(g.sp, d.legacy, N, m.n_sets, w.info, w.perm, nullptr, st)) return rc;
                 const size_t lds = ((size_t)BM * lds_ld(128) + BM * 32 + BM) * 4;
                 SoapDims dt = d;
                 if (packed) dt.S = d.Sp;  // (the kernel uses S as the row pitch / length of the feature rows only)

@@ -278,14 +278,14 @@ __global__ __launch_bounds__(256) void k_soap_tail_train(SoapDims d, const float
 // out[(chunk, network)][H + 2][S]
 constexpr int WG_ATOMS = 32;
 __global__ __launch_bounds__(64) void k_soap_wgrad1(SoapDims d, const float* __restrict__ feats, const float* __restrict__ xd,
-                                                    const int* __restrict__ perm, const SpInfo* __restrict__ info,
+                                                    const int* __restrict__ perm, const int* __restrict__ offs,
                                                     const SoapSet* __restrict__ sets, const float* __restrict__ pack,
                                                     int n_chunks, float* __restrict__ out) {
     __shared__ float sv[WG_ATOMS][2 * MAXH + 4];
     __shared__ int sat[WG_ATOMS];
     const int s = blockIdx.y, chunk = blockIdx.z, k = blockIdx.x * 64 + threadIdx.x;
     const int H = d.H, PK = soap_pack_size(H, d.NH);
-    const int a0 = info->offs[s], a1 = info->offs[s + 1];
+    const int a0 = offs[s], a1 = offs[s + 1];   // the bucket table's offs[n_sets + 1]
     const int per = (a1 - a0 + n_chunks - 1) / n_chunks;
     const int lo = a0 + chunk * per, hi = min(a1, lo + per);
     const SoapSet W = sets[s];
@@ -359,13 +359,13 @@ __global__ void k_soap_wgrad1_reduce(SoapDims d, const float* __restrict__ part,
 // hidden layer kk (1 <= kk < NH) or the last layer (kk == NH): one workgroup per (network, layer), elements strided over the
 // threads, atoms in order
 //   dW_kk[j][q] = sum_i (abar_kk[i][j] h_{kk-1}[i][q] + adbar_kk[i][j] h'_{kk-1}[i][q]),  dw3[j] = sum_i (gA_i h_NH[i][j] + st h'_NH[i][j])
-__global__ __launch_bounds__(256) void k_soap_wgrad2(SoapDims d, const int* __restrict__ perm, const SpInfo* __restrict__ info,
+__global__ __launch_bounds__(256) void k_soap_wgrad2(SoapDims d, const int* __restrict__ perm, const int* __restrict__ offs,
                                                      const float* __restrict__ pack, const float* __restrict__ gA,
                                                      float seed_tangent, int s, int kk, float* __restrict__ gout) {
     extern __shared__ float sp_[];   // [WG_ATOMS][4 H + 1]: abar_kk | adbar_kk | h_{kk-1} | h'_{kk-1} | gA
     const int H = d.H, NH = d.NH, PK = soap_pack_size(H, NH), LD = 4 * H + 1;
     const bool last = kk == NH;
-    const int a0 = info->offs[s], a1 = info->offs[s + 1];
+    const int a0 = offs[s], a1 = offs[s + 1];   // the bucket table's offs[n_sets + 1]
     constexpr int MAXE = (MAXH * MAXH + 255) / 256;
     double acc[MAXE];
 #pragma unroll
@@ -633,7 +633,7 @@ struct SoapTrainWs {
     float *Cd, *xd, *pack, *part;
     float *NY, *LY, *NX, *LX, *NC, *LC, *q, *part2;   // legacy = False only (see k_soap_ybar)
     int* perm;
-    SpInfo* info;
+    void* info;   // SpInfoT<SP_MAXSETS> or, above 8 networks, SpInfoT<SP_TRAIN_MAXSETS> (soap_train_grads)
     int n_chunks;
     size_t bytes;
 };
@@ -650,7 +650,7 @@ static void carve_soap_train(const SoapModel& m, int64_t N, int64_t E, void* bas
     w.pack = c.take<float>(Na * soap_pack_size(d.H, d.NH));
     w.part = c.take<float>((size_t)w.n_chunks * m.n_sets * (d.H + 2) * d.S);
     w.perm = c.take<int>(Na);
-    w.info = reinterpret_cast<SpInfo*>(c.take<int>((sizeof(SpInfo) + 3) / 4));
+    w.info = c.take<int>((sizeof(SpInfoT<SP_TRAIN_MAXSETS>) + 3) / 4);
     const bool front = !d.legacy;
     const int64_t ns_s = front ? Na * d.S : 1, nc_s = front ? Na * d.NCOEF : 1;
     w.NY = c.take<float>(ns_s); w.LY = c.take<float>(ns_s);
@@ -694,6 +694,8 @@ static int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_b
     const SoapDims& d = m.d;
     PET_REQUIRE(d.legacy || d.ns * d.C <= 256, PET_ERR_UNSUPPORTED, "more than 64 species with the Alchemical embedding");
     PET_REQUIRE(d.H <= MAXH && d.NH <= MAXNH, PET_ERR_UNSUPPORTED, "tail size outside the compiled limits");
+    PET_REQUIRE(m.n_sets <= SP_TRAIN_MAXSETS, PET_ERR_UNSUPPORTED,
+                "training more than 16 per-species networks: the bucket table of the weight gradients holds 16");
     PET_REQUIRE(!m.grad.empty(), PET_ERR_ARGUMENT, "soap_model_zero_grad has not been called");
     SoapWs w;
     carve_soap(d, g.n_nodes, g.n_edges, ws, w);
@@ -729,12 +731,14 @@ static int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_b
     const float* xd = tangent ? t.xd : nullptr;
     const float seed_t = tangent ? 1.f : 0.f;
     k_soap_tail_train<<<N, 256, 0, st>>>(d, w.feats, xd, g.sp, m.sets, gA, seed_t, t.pack, tangent_atomic);
-    // atoms bucketed by network (the forward's own bucketing exists only on its MFMA path)
-    PET_HIP_CHECK(hipMemsetAsync(t.info, 0, sizeof(SpInfo), st));
-    k_sp_count<<<cdiv(N, 256), 256, 0, st>>>(g.sp, d.legacy, N, t.info);
-    k_sp_scan<<<1, 1, 0, st>>>(m.n_sets, t.info);
-    k_sp_fill<<<cdiv(N, 1024), 1024, 0, st>>>(g.sp, d.legacy, N, t.info, t.perm);
-    k_soap_wgrad1<<<dim3(cdiv(d.S, 64), m.n_sets, t.n_chunks), 64, 0, st>>>(d, w.feats, xd, t.perm, t.info, m.sets, t.pack,
+    // atoms bucketed by network (the forward's own bucketing exists only on its MFMA path, for at most SP_MAXSETS networks):
+    // the forward's 8-network table where it suffices, the 16-network one above
+    const int* offs = nullptr;
+    if (int rc = m.n_sets <= SP_MAXSETS
+                     ? sp_bucket<SP_MAXSETS>(g.sp, d.legacy, N, m.n_sets, t.info, t.perm, &offs, st)
+                     : sp_bucket<SP_TRAIN_MAXSETS>(g.sp, d.legacy, N, m.n_sets, t.info, t.perm, &offs, st))
+        return rc;
+    k_soap_wgrad1<<<dim3(cdiv(d.S, 64), m.n_sets, t.n_chunks), 64, 0, st>>>(d, w.feats, xd, t.perm, offs, m.sets, t.pack,
                                                                           t.n_chunks, t.part);
     for (int s = 0; s < m.n_sets; s++) {
         const std::string ss = std::to_string(s);
@@ -745,9 +749,9 @@ static int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_b
                                                                                gG, gB);
         const size_t lds2 = (size_t)WG_ATOMS * (4 * d.H + 1) * 4;
         for (int kk = 1; kk < d.NH; kk++)
-            k_soap_wgrad2<<<1, 256, lds2, st>>>(d, t.perm, t.info, t.pack, gA, seed_t, s, kk,
+            k_soap_wgrad2<<<1, 256, lds2, st>>>(d, t.perm, offs, t.pack, gA, seed_t, s, kk,
                                                 m.grad.at("bpnn." + ss + "." + std::to_string(2 * kk) + ".weight").first);
-        k_soap_wgrad2<<<1, 256, lds2, st>>>(d, t.perm, t.info, t.pack, gA, seed_t, s, d.NH,
+        k_soap_wgrad2<<<1, 256, lds2, st>>>(d, t.perm, offs, t.pack, gA, seed_t, s, d.NH,
                                             m.grad.at("last_layers.energy." + ss + ".weight").first);
     }
     if (!d.legacy) {   // centre encoding and species embedding (k_soap_ybar ...)

@@ -598,6 +598,63 @@ int pet_ewald_backward(const pet_ewald_t* e, const pet_graph_t* g, const float* 
                        const float* d_grad_potential, int32_t n_channels, float* d_grad_charges, float* d_grad_positions,
                        float* d_grad_cells, void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- P3M evaluation of the same operator (utils/long_range.py:71-79,153-170) ------------------------------------------------
+ * The reference takes its Ewald branch only under `use_ewald and training`: every evaluation of a periodic long-range model
+ * goes through torch-pme's P3MCalculator (mesh_spacing = kspace_resolution, interpolation_nodes). This block is a second
+ * implementation of the RECIPROCAL-SPACE sum of the block above; self, background, exclusion and the open all-pairs sum are
+ * the same kernels. torch-pme is not part of the reference tree: the mesh operator too is fixed HERE by definition (DESIGN
+ * section 19 and metatrain_amd.long_range.P3M_CONVENTIONS hold the same table) and pinned to an independent fp64 oracle
+ * (tests/_p3m_oracle.py); parity with torch-pme is NOT pinned.
+ *   h = kspace_resolution, p = interpolation_nodes in 1..5, N_a = the smallest power of two >= |cell row a| / h (at least 1),
+ *   u = s N with s = r cell^{-1} wrapped to [0, 1), W(x) = M_p(x + p/2) the order-p charge-assignment function (centred
+ *   cardinal B-spline), separable over the fractional axes. Nodes: odd p around floor(u + 1/2), offsets -(p-1)/2 .. (p-1)/2;
+ *   even p around floor(u), offsets -(p/2-1) .. p/2; indices mod N_a (with N_a < p several nodes fold onto one point and add).
+ *   G^(n) = sum_m U_m^2 G(|k_{n+mN}|) / (sum_m U_m^2)^2, G^(0) = 0, U_m = prod_a sinc^p((n_a + m_a N_a) / N_a), m in {-2..2}^3,
+ *   n_a in [-N_a/2, N_a/2), k_nu = 2 pi nu cell^{-T}.
+ *   Phi = (1/Omega) sum_n G^(n) rho^(n) e^{2 pi i n.j/N} (unnormalised transforms both ways: G^/Omega is the whole filter).
+ *   Periodic system: V_i = P [ sum_nodes W_i(node) Phi(node) - self - background - exclusion ]; open systems as above.
+ * Adjoints, for dL/dV = g: dL/dq = the operator applied to g. With Phi_q, Phi_g the mesh potentials of q and g and q^, g^ their
+ * unfiltered half spectra (per channel, summed over channels):
+ *   F_i = P sum_nodes grad_r W_i(node) [ g_i Phi_q + q_i Phi_g ](node),  dW/dr_b = sum_a N_a (cell^{-1})_{ba} dW/du_a,
+ *   dL/dcell_bc += -sum_i s_ib F_ic + P sum_n w_n Re(conj(g^_n) q^_n) d(G^_n/Omega)/dcell_bc,  w_n = 1 on the planes n_z = 0 and
+ *   n_z = N_z/2 of the half spectrum, 2 elsewhere; the derivative alias term by alias term with the bracket of the block above.
+ * The transforms are the CALLER's (torch.fft.rfftn / irfftn(norm="forward") over the last three axes, fp32, same stream): this
+ * library links no FFT. Layout, CHANNEL-FIRST: mesh of system s = [C, N_x, N_y, N_z] floats at offset mesh_off_s * C of the
+ * packed buffer, half spectrum [C, N_x, N_y, N_z/2 + 1] complex at spec_off_s * C; systems in batch order; non-periodic and
+ * empty systems have none (pet_p3m_mesh_shape gives 0 0 0).
+ *   pet_ewald_set_p3m(e, p): before pet_ewald_plan, which then builds mesh descriptors and G^/Omega (k_p3m_influence, fp64 ->
+ *     fp32; one device synchronisation) instead of k lists. On such a handle pet_ewald_potential / _backward /
+ *     _workspace_bytes / _num_kvectors fail (PET_ERR_ARGUMENT / -1), and pet_p3m_* fail on an Ewald-mode handle.
+ *   pet_p3m_mesh_shape_host / pet_p3m_influence_host: host fp64, no GPU: N[3] of one cell (0, or -1 for a singular cell), and
+ *     G^/Omega on the half spectrum [N_x, N_y, N_z/2 + 1] (returns the count; fills h_out when capacity suffices).
+ *   pet_p3m_spread: bins the atoms (k_p3m_bin_*: weights in fp64 from wrapped fractional coordinates, rounded once; stable
+ *     counting sort by stencil origin) and spreads d_charges [N, C] to d_mesh. The weights and bins stay in the workspace:
+ *     pet_p3m_finish and pet_p3m_backward read them, so they follow a pet_p3m_spread of the same positions.
+ *   pet_p3m_filter: d_spectrum *= G^/Omega in place.   pet_p3m_finish: gather of d_mesh_potential, open pairs, self,
+ *     background, exclusion -> d_out [N, C].   pet_p3m_backward: d_grad_positions [N, 3] and d_grad_cells [S, 3, 3] (may be
+ *     NULL, then the spectra may be too) from the mesh potentials and UNFILTERED spectra of q and g: mesh, exclusion and
+ *     open-system parts.
+ * PET_ERR_UNSUPPORTED: a mesh axis above PET_P3M_MAX_AXIS; mixed pbc. No float atomics; fixed orders (csrc/p3m.hip). */
+#define PET_P3M_MAX_AXIS 512
+int pet_ewald_set_p3m(pet_ewald_t* e, int32_t interpolation_nodes);
+int pet_p3m_mesh_shape_host(const double* h_cell, double spacing, int32_t* out);
+int64_t pet_p3m_influence_host(const double* h_cell, double smearing, double spacing, int32_t interpolation_nodes,
+                               double* h_out, int64_t capacity);
+int pet_p3m_mesh_shape(const pet_ewald_t* e, int64_t system, int32_t* out);
+int64_t pet_p3m_mesh_elements(const pet_ewald_t* e, int64_t n_channels);
+int64_t pet_p3m_spectrum_elements(const pet_ewald_t* e, int64_t n_channels);
+int64_t pet_p3m_workspace_bytes(const pet_ewald_t* e, int64_t n_channels);
+int pet_p3m_spread(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
+                   int32_t n_channels, float* d_mesh, void* d_workspace, int64_t workspace_bytes, void* stream);
+int pet_p3m_filter(const pet_ewald_t* e, int32_t n_channels, void* d_spectrum, void* stream);
+int pet_p3m_finish(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
+                   int32_t n_channels, const float* d_mesh_potential, float* d_out, void* d_workspace, int64_t workspace_bytes,
+                   void* stream);
+int pet_p3m_backward(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
+                     const float* d_grad_potential, int32_t n_channels, const float* d_phi_q, const float* d_phi_g,
+                     const void* d_spec_q, const void* d_spec_g, float* d_grad_positions, float* d_grad_cells,
+                     void* d_workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- Rotational augmentation (utils/augmentation.py:O3Augmenter; pet/trainer.py:187-193, 288-303) -------------------------
  * A random element of O(3) per system of a collated batch, drawn and applied on the device. A rigid transformation of
  * positions and cell leaves fractional coordinates alone, so the batch's (center, neighbor, cell_shift) list stays valid:

@@ -56,6 +56,9 @@ SYMBOLS = [
     "pet_zbl_forward", "pet_zbl_backward", "pet_zbl_hessian_vector",
     "pet_ewald_create", "pet_ewald_destroy", "pet_ewald_kvectors_host", "pet_ewald_plan", "pet_ewald_num_kvectors",
     "pet_ewald_workspace_bytes", "pet_ewald_potential", "pet_ewald_backward",
+    "pet_ewald_set_p3m", "pet_p3m_mesh_shape_host", "pet_p3m_influence_host", "pet_p3m_mesh_shape", "pet_p3m_mesh_elements",
+    "pet_p3m_spectrum_elements", "pet_p3m_workspace_bytes", "pet_p3m_spread", "pet_p3m_filter", "pet_p3m_finish",
+    "pet_p3m_backward",
     "pet_o3_draw", "pet_o3_apply", "pet_o3_wigner", "pet_o3_apply_spherical",
     "pet_baseline_workspace_bytes", "pet_species_counts", "pet_composition_accumulate", "pet_target_moments",
     "pet_targets_remove",
@@ -296,6 +299,18 @@ def load() -> ctypes.CDLL:
     lib.pet_ewald_workspace_bytes.restype = c_int64
     lib.pet_ewald_potential.argtypes = [P, P, P, P, c_int32, P, P, c_int64, P]
     lib.pet_ewald_backward.argtypes = [P, P, P, P, P, c_int32, P, P, P, P, c_int64, P]
+    lib.pet_ewald_set_p3m.argtypes = [P, c_int32]
+    lib.pet_p3m_mesh_shape_host.argtypes = [POINTER(c_double), c_double, POINTER(c_int32)]
+    lib.pet_p3m_influence_host.argtypes = [POINTER(c_double), c_double, c_double, c_int32, POINTER(c_double), c_int64]
+    lib.pet_p3m_influence_host.restype = c_int64
+    lib.pet_p3m_mesh_shape.argtypes = [P, c_int64, POINTER(c_int32)]
+    for name in ("pet_p3m_mesh_elements", "pet_p3m_spectrum_elements", "pet_p3m_workspace_bytes"):
+        getattr(lib, name).argtypes = [P, c_int64]
+        getattr(lib, name).restype = c_int64
+    lib.pet_p3m_spread.argtypes = [P, P, P, P, c_int32, P, P, c_int64, P]
+    lib.pet_p3m_filter.argtypes = [P, c_int32, P, P]
+    lib.pet_p3m_finish.argtypes = [P, P, P, P, c_int32, P, P, P, c_int64, P]
+    lib.pet_p3m_backward.argtypes = [P, P, P, P, P, c_int32, P, P, P, P, P, P, P, c_int64, P]
     lib.pet_o3_draw.argtypes = [c_uint64, c_uint64, c_int32, c_int64, P, P]
     lib.pet_o3_apply.argtypes = [P, c_int64, c_int32, POINTER(O3Array), P]
     lib.pet_o3_wigner.argtypes = [P, c_int64, c_int32, P, P, P]

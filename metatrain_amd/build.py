@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libpet_hip.so")
-SOURCES = ["abi.hip", "graph.hip", "nl.hip", "pet_plan.hip", "pet_fwd.hip", "pet_bwd.hip", "pet_trr.hip", "pet_attn.hip", "pet_ablk.hip", "pet_ablk_bwd1.hip", "pet_emlp_s.hip", "pet_head_s.hip", "pet_compress_s.hip", "pet_center_s.hip", "pet_comb.hip", "pet_comb_s.hip", "pet_comb_bwd.hip", "pet_comb_bwd_s.hip", "train.hip", "optim.hip", "so.hip", "so_rows_s.hip", "pet_node_s.hip", "soap.hip", "gen.hip", "gen_train.hip", "lora.hip", "llpr.hip", "zbl.hip", "ewald.hip", "augment.hip", "wigner.hip", "baseline.hip", "loss.hip"]
+SOURCES = ["abi.hip", "graph.hip", "nl.hip", "pet_plan.hip", "pet_fwd.hip", "pet_bwd.hip", "pet_trr.hip", "pet_attn.hip", "pet_ablk.hip", "pet_ablk_bwd1.hip", "pet_emlp_s.hip", "pet_head_s.hip", "pet_compress_s.hip", "pet_center_s.hip", "pet_comb.hip", "pet_comb_s.hip", "pet_comb_bwd.hip", "pet_comb_bwd_s.hip", "train.hip", "optim.hip", "so.hip", "so_rows_s.hip", "pet_node_s.hip", "soap.hip", "gen.hip", "gen_train.hip", "lora.hip", "llpr.hip", "zbl.hip", "ewald.hip", "p3m.hip", "augment.hip", "wigner.hip", "baseline.hip", "loss.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fgpu-rdc"]
 FLAGS += os.environ.get("PET_HIP_EXTRA_FLAGS", "").split()  # debugging builds, e.g. -DAB_PROFILE (pet_ablk.hip)
 # Translation units compiled on their own (no -fgpu-rdc: their device code is generated here, not at the link step) with the
@@ -18,7 +18,11 @@ VGPR_FORM_FLAGS = ["-fno-gpu-rdc", "-mllvm", "-amdgpu-mfma-vgpr-form"]
 # Translation units whose device code is generated per file, not at the link step (-fgpu-rdc generates it there, over all files, and
 # its register allocation of k_comb_bwd_s came out at 256 registers + 4 spilled -- scratch loads inside the ring's vmcnt window --
 # where the per-file code generation needs 229 and none)
-NO_RDC = {"pet_comb_bwd_s.hip", "so_rows_s.hip", "zbl.hip", "ewald.hip", "augment.hip", "wigner.hip", "baseline.hip", "loss.hip"}  # (zbl.hip, ewald.hip, augment.hip, wigner.hip, baseline.hip, loss.hip: self-contained; their register / scratch report is per file)
+NO_RDC = {"pet_comb_bwd_s.hip", "so_rows_s.hip", "zbl.hip", "ewald.hip", "p3m.hip", "augment.hip", "wigner.hip", "baseline.hip", "loss.hip"}  # (zbl.hip, ewald.hip, p3m.hip, augment.hip, wigner.hip, baseline.hip, loss.hip: self-contained; their register / scratch report is per file)
+
+
+# translation units that #include another one (p3m.hip compiles ewald.hip's shared kernels together with its own)
+INCLUDES = {"p3m.hip": ["ewald.hip"]}
 
 
 def _newer(a, b):
@@ -46,7 +50,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _newer(s, o) or hdr_time > os.path.getmtime(o):
+        if force or _newer(s, o) or hdr_time > os.path.getmtime(o) or any(_newer(os.path.join(CSRC, d), o) for d in INCLUDES.get(src, ())):
             cmd = ["hipcc", *FLAGS, *(VGPR_FORM_FLAGS if src in VGPR_FORM else []), *(["-fno-gpu-rdc"] if src in NO_RDC else []), "-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)

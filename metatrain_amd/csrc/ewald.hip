@@ -566,6 +566,7 @@ __global__ __launch_bounds__(256) void k_ew_cell(const EwSys* __restrict__ sys, 
     }
 }
 
+#ifndef PET_EWALD_SHARED_ONLY  // (p3m.hip compiles the kernels above together with its own and stops here)
 // the walked half of the k-set of one cell: n with the first non-zero index positive, 0 < |k| <= kmax
 int ew_half_kset(const double* cell, double lambda, double* inv, double* vol, std::vector<EwK>* out, int* nm) {
     const double* h = cell;
@@ -602,8 +603,16 @@ int ew_half_kset(const double* cell, double lambda, double* inv, double* vol, st
             }
     return 0;
 }
+#endif
 
 }  // namespace
+
+// P3M mode (csrc/p3m.hip): mesh descriptors and influence functions in place of k lists
+struct P3mPlan;
+void p3m_release(P3mPlan* p);
+// geometry [S][10] = cell^{-1} and Omega; has_mesh [S]; chunks [S][2] receives every system's (first, count) reduction chunks
+int p3m_plan_build(double sigma, double spacing, int nodes, const double* h_cells, const double* geometry, const int* has_mesh,
+                   int64_t n_systems, int* chunks, P3mPlan** out);
 
 }  // namespace pet
 
@@ -615,6 +624,8 @@ struct pet_ewald {
     int device = -1;
     int64_t n_atoms = 0, n_systems = 0, n_k = 0;
     int nm = 1;
+    int p3m_nodes = 0;         // 0: Ewald mode; 1..5: P3M mode (pet_ewald_set_p3m)
+    P3mPlan* p3m = nullptr;    // owned; rebuilt by every plan of a P3M-mode handle
     std::vector<EwSys> sys;
     std::vector<int2> ktiles, atiles_p, atiles_n;
     // device copies (made by pet_ewald_plan, kept until the next plan / destroy)
@@ -626,6 +637,8 @@ struct pet_ewald {
         (void)hipFree(d_sys); (void)hipFree(d_k); (void)hipFree(d_ksys);
         (void)hipFree(d_ktiles); (void)hipFree(d_atiles_p); (void)hipFree(d_atiles_n);
         d_sys = nullptr; d_k = nullptr; d_ksys = nullptr; d_ktiles = d_atiles_p = d_atiles_n = nullptr;
+        p3m_release(p3m);
+        p3m = nullptr;
         planned = false;
     }
 };
@@ -639,6 +652,37 @@ int ew_upload(T** dst, const std::vector<T>& src) {
     if (!src.empty()) PET_HIP_CHECK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return PET_OK;
 }
+
+
+// what both modes ask of the graph
+int ew_check_graph(const pet_ewald_t* e, const pet_graph_t* pg, int32_t C) {
+    PET_REQUIRE(e && pg, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(e->planned, PET_ERR_ARGUMENT, "pet_ewald_plan has not been called");
+    PET_REQUIRE(C >= 1, PET_ERR_ARGUMENT, "n_channels must be at least 1");
+    const Graph& g = pg->g;
+    PET_REQUIRE(g.sys && (g.n_edges == 0 || g.shift), PET_ERR_ARGUMENT,
+                "the long-range exclusion term needs a pet_graph_build handle (cell shifts, system indices): a "
+                "pet_graph_from_batch handle has none");
+    PET_REQUIRE(!g.adaptive, PET_ERR_ARGUMENT,
+                "long range on a graph built under an adaptive cutoff: it drops edges inside the exclusion radius");
+    PET_REQUIRE(pg->strict, PET_ERR_ARGUMENT,
+                "long range needs the graph of a model with nl_is_strict (long_range.enable): every pair inside the cutoff");
+    PET_REQUIRE(std::fabs((double)pg->cutoff - e->cutoff) <= 1e-5 * e->cutoff, PET_ERR_ARGUMENT,
+                "the graph's cutoff " + std::to_string(pg->cutoff) + " is not the exclusion radius " +
+                    std::to_string(e->cutoff) + " of this pet_ewald_t");
+    PET_REQUIRE(g.n_nodes == e->n_atoms && g.n_systems == e->n_systems, PET_ERR_ARGUMENT,
+                "the graph has " + std::to_string(g.n_nodes) + " atoms in " + std::to_string(g.n_systems) +
+                    " systems, the plan " + std::to_string(e->n_atoms) + " in " + std::to_string(e->n_systems));
+    int device = 0;
+    PET_HIP_CHECK(hipGetDevice(&device));
+    PET_REQUIRE(device == e->device, PET_ERR_ARGUMENT, "the plan was made on another device");
+    return PET_OK;
+}
+
+}  // namespace
+
+#ifndef PET_EWALD_SHARED_ONLY
+namespace {
 
 struct EwWs {
     float2* tab;
@@ -662,26 +706,11 @@ size_t ew_carve(const pet_ewald_t* e, int64_t C, void* base, EwWs& w) {
 }
 
 int ew_check(const pet_ewald_t* e, const pet_graph_t* pg, int32_t C, const void* ws, int64_t ws_bytes) {
-    PET_REQUIRE(e && pg, PET_ERR_ARGUMENT, "null argument");
-    PET_REQUIRE(e->planned, PET_ERR_ARGUMENT, "pet_ewald_plan has not been called");
-    PET_REQUIRE(C >= 1, PET_ERR_ARGUMENT, "n_channels must be at least 1");
-    const Graph& g = pg->g;
-    PET_REQUIRE(g.sys && (g.n_edges == 0 || g.shift), PET_ERR_ARGUMENT,
-                "the long-range exclusion term needs a pet_graph_build handle (cell shifts, system indices): a "
-                "pet_graph_from_batch handle has none");
-    PET_REQUIRE(!g.adaptive, PET_ERR_ARGUMENT,
-                "long range on a graph built under an adaptive cutoff: it drops edges inside the exclusion radius");
-    PET_REQUIRE(pg->strict, PET_ERR_ARGUMENT,
-                "long range needs the graph of a model with nl_is_strict (long_range.enable): every pair inside the cutoff");
-    PET_REQUIRE(std::fabs((double)pg->cutoff - e->cutoff) <= 1e-5 * e->cutoff, PET_ERR_ARGUMENT,
-                "the graph's cutoff " + std::to_string(pg->cutoff) + " is not the exclusion radius " +
-                    std::to_string(e->cutoff) + " of this pet_ewald_t");
-    PET_REQUIRE(g.n_nodes == e->n_atoms && g.n_systems == e->n_systems, PET_ERR_ARGUMENT,
-                "the graph has " + std::to_string(g.n_nodes) + " atoms in " + std::to_string(g.n_systems) +
-                    " systems, the plan " + std::to_string(e->n_atoms) + " in " + std::to_string(e->n_systems));
-    int device = 0;
-    PET_HIP_CHECK(hipGetDevice(&device));
-    PET_REQUIRE(device == e->device, PET_ERR_ARGUMENT, "the plan was made on another device");
+    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(e->p3m_nodes == 0, PET_ERR_ARGUMENT,
+                "a pet_ewald_* entry point on a P3M-mode handle (pet_ewald_set_p3m): use pet_p3m_spread / _filter / _finish / "
+                "_backward");
+    PET_TRY(ew_check_graph(e, pg, C));
     EwWs w;
     PET_REQUIRE(e->n_atoms == 0 || (ws && ws_bytes >= (int64_t)ew_carve(e, C, nullptr, w)), PET_ERR_ARGUMENT,
                 "Ewald workspace too small (pet_ewald_workspace_bytes)");
@@ -787,14 +816,19 @@ int pet_ewald_plan(pet_ewald_t* e, const double* h_cells, const int32_t* h_pbc, 
         y.first_k = (int)ks.size();
         y.n_k = 0;
         y.nm = 1;
-        if (y.periodic) {
+        if (y.periodic && e->p3m_nodes) {
+            // P3M mode: the inverse cell and the volume only; no k list and no limit on the cell's length
+            const int rc = ew_half_kset(h_cells + 9 * s, e->lambda, y.inv, &y.vol, nullptr, &y.nm);
+            PET_REQUIRE(rc != -1, PET_ERR_ARGUMENT, "the cell of periodic system " + std::to_string(s) + " is singular");
+            y.nm = 1;
+        } else if (y.periodic) {
             const size_t before = ks.size();
             const int rc = ew_half_kset(h_cells + 9 * s, e->lambda, y.inv, &y.vol, nullptr, &y.nm);
             PET_REQUIRE(rc != -1, PET_ERR_ARGUMENT, "the cell of periodic system " + std::to_string(s) + " is singular");
             PET_REQUIRE(rc == 0 && y.nm - 1 <= PET_EWALD_MAX_INDEX, PET_ERR_UNSUPPORTED,
                         "system " + std::to_string(s) + " needs reciprocal indices up to " + std::to_string(y.nm - 1) +
                             " at this kspace_resolution; at most " + std::to_string(PET_EWALD_MAX_INDEX) +
-                            " are served (the Ewald sum costs O(N K): large boxes are what P3M is for, which is not built)");
+                            " are served (the Ewald sum costs O(N K): large boxes are what P3M is for: pet_ewald_set_p3m)");
             (void)ew_half_kset(h_cells + 9 * s, e->lambda, y.inv, &y.vol, &ks, &y.nm);
             y.n_k = (int)(ks.size() - before);
             // by descending |k| (ties in enumeration order): the gather adds the small terms first
@@ -815,7 +849,25 @@ int pet_ewald_plan(pet_ewald_t* e, const double* h_cells, const int32_t* h_pbc, 
         for (int a = 0; a < y.n_atoms; a += 32) (y.periodic ? ap : an).push_back(make_int2((int)s, a));
     }
     PET_REQUIRE(ks.size() < (size_t(1) << 28), PET_ERR_UNSUPPORTED, "too many k-vectors in one batch");
+    P3mPlan* mesh_plan = nullptr;
+    if (e->p3m_nodes) {
+        std::vector<double> geometry((size_t)n_systems * 10);
+        std::vector<int> has_mesh((size_t)n_systems), chunks((size_t)n_systems * 2);
+        for (int64_t s = 0; s < n_systems; s++) {
+            for (int k = 0; k < 9; k++) geometry[(size_t)s * 10 + k] = sys[(size_t)s].inv[k];
+            geometry[(size_t)s * 10 + 9] = sys[(size_t)s].vol;
+            has_mesh[(size_t)s] = sys[(size_t)s].periodic && sys[(size_t)s].n_atoms > 0;
+        }
+        PET_TRY(p3m_plan_build(e->sigma, e->lambda, e->p3m_nodes, h_cells, geometry.data(), has_mesh.data(), n_systems,
+                               chunks.data(), &mesh_plan));
+        // k_ew_cell walks a system's reduction chunks where it walks k-vectors in Ewald mode
+        for (int64_t s = 0; s < n_systems; s++) {
+            sys[(size_t)s].first_k = chunks[(size_t)s * 2];
+            sys[(size_t)s].n_k = chunks[(size_t)s * 2 + 1];
+        }
+    }
     e->release();
+    e->p3m = mesh_plan;
     PET_HIP_CHECK(hipGetDevice(&e->device));
     PET_TRY(ew_upload(&e->d_sys, sys));
     PET_TRY(ew_upload(&e->d_k, ks));
@@ -836,12 +888,12 @@ int pet_ewald_plan(pet_ewald_t* e, const double* h_cells, const int32_t* h_pbc, 
 }
 
 int64_t pet_ewald_num_kvectors(const pet_ewald_t* e, int64_t system) {
-    if (!e || !e->planned || system < 0 || system >= e->n_systems) return -1;
+    if (!e || !e->planned || e->p3m_nodes || system < 0 || system >= e->n_systems) return -1;
     return 2 * (int64_t)e->sys[(size_t)system].n_k;
 }
 
 int64_t pet_ewald_workspace_bytes(const pet_ewald_t* e, int64_t n_channels) {
-    if (!e || !e->planned || n_channels < 1) return -1;
+    if (!e || !e->planned || e->p3m_nodes || n_channels < 1) return -1;
     EwWs w;
     return (int64_t)ew_carve(e, n_channels, nullptr, w);
 }
@@ -905,3 +957,4 @@ int pet_ewald_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float*
 }
 
 }  // extern "C"
+#endif  // PET_EWALD_SHARED_ONLY

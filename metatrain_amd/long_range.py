@@ -20,8 +20,13 @@ passes to ``k_ew_finish`` and the weight ``pet_ewald_plan`` gives every k-vector
 as fp32 matrix-core GEMMs with a generated operand; fixed summation orders, no atomics), :class:`LongRangeFeaturizerHip` the
 featuriser under the reference's state-dict keys, :func:`energy_and_gradient` the whole model: energies, dE/dR and dE/dcell.
 
-``P3M`` is not built. The reference evaluates a ``use_ewald: false`` model with P3M, an approximation of this same sum: such a
-model loads only with an explicit ``p3m_as_ewald=True``.
+The reference takes its Ewald branch only under ``use_ewald and training`` (``utils/long_range.py:153-170``): it EVALUATES every
+periodic long-range model with P3M. :class:`P3MHip` is that operator (``csrc/p3m.hip``: binning, spread, filter, gather and the
+adjoints as HIP kernels in stages around ``torch.fft.rfftn`` / ``irfftn``), fixed by definition like the Ewald one
+(:data:`P3M_CONVENTIONS`, DESIGN.md section 19, oracle ``tests/_p3m_oracle.py``; parity with torch-pme unpinned). It is an
+explicit opt-in: ``LongRangeFeaturizerHip(hypers, method="p3m")`` evaluates periodic systems with P3M whatever ``use_ewald``
+says, ``method="ewald"`` (the earlier ``p3m_as_ewald=True``) with the Ewald sum P3M approximates, and without either a
+``use_ewald: false`` model is refused.
 """
 import logging
 import math
@@ -46,6 +51,21 @@ CONVENTIONS = {
 }
 PREFACTOR = 0.5
 
+# The mesh operator's conventions (h = kspace_resolution, the reference's mesh_spacing; p = interpolation_nodes in 1..5). The
+# self, background, exclusion and open-system terms and the prefactor are those of CONVENTIONS.
+P3M_CONVENTIONS = {
+    "mesh": "N_a = 2^ceil(log2(|cell row a| / h)), at least 1 (believed to be torch-pme's get_ns_mesh; unpinned)",
+    "assignment": "the order-p P3M (Hockney-Eastwood) charge-assignment function: the centred cardinal B-spline "
+                  "W(x) = M_p(x + p/2), separable over the fractional axes, in mesh units u_a = s_a N_a, s = r cell^{-1} in [0, 1)",
+    "nodes": "odd p: around floor(u + 1/2), offsets -(p-1)/2 .. (p-1)/2; even p: around floor(u), offsets -(p/2-1) .. p/2; "
+             "indices mod N_a (N_a < p: several nodes fall on one mesh point and their weights add)",
+    "influence": "G^(n) = sum_m U_m^2 G(|k_{n+mN}|) / (sum_m U_m^2)^2, G^(0) = 0, G as in CONVENTIONS, k_nu = 2 pi nu cell^{-T}, "
+                 "U_m = prod_a sinc^p((n_a + m_a N_a) / N_a), aliases m in {-2..2}^3, n_a in [-N_a/2, N_a/2)",
+    "mesh_potential": "Phi = (1/Omega) sum_n G^(n) rho^(n) e^{2 pi i n.j/N}: unnormalised transforms, G^/Omega is the filter",
+    "gather": "sum over the same nodes of W_i(node) Phi(node)",
+}
+METHODS = (None, "ewald", "p3m")
+
 REFERENCE_KEYS = ("long_range_featurizer.charges_map.weight", "long_range_featurizer.charges_map.bias",
                   "long_range_featurizer.out_projection.0.weight", "long_range_featurizer.out_projection.0.bias",
                   "long_range_featurizer.out_projection.2.weight", "long_range_featurizer.out_projection.2.bias")
@@ -58,22 +78,65 @@ def truncation_factor(smearing: float, kspace_resolution: float) -> float:
     return math.exp(-0.5 * (float(smearing) * 2.0 * math.pi / float(kspace_resolution)) ** 2)
 
 
-def resolve_hypers(hypers: dict, p3m_as_ewald: bool = False) -> dict:
+def resolve_hypers(hypers: dict, p3m_as_ewald: bool = False, method: Optional[str] = None) -> dict:
     """The ``long_range`` block of a model's hypers with the reference's defaults filled in, checked for what this package
-    serves. Raises for a model without ``long_range.enable``, for ``use_ewald: false`` without ``p3m_as_ewald=True`` and for
-    an adaptive cutoff together with long range."""
+    serves. Raises for a model without ``long_range.enable``, for ``use_ewald: false`` without an explicit choice
+    (``method="p3m"``, ``method="ewald"`` or the earlier ``p3m_as_ewald=True``), for an unknown ``method``, for
+    ``interpolation_nodes`` outside 1..5 under ``method="p3m"`` and for an adaptive cutoff together with long range."""
     from .pet.hypers import long_range_hypers
 
+    if method not in METHODS:
+        raise PetHipError(f"method must be one of None, 'ewald', 'p3m': got {method!r}")
     lr = long_range_hypers(hypers)
     if not lr["enable"]:
         raise PetHipError("long_range.enable is false: this model has no long-range featuriser")
-    if not lr["use_ewald"] and not p3m_as_ewald:
-        raise PetHipError("long_range.use_ewald is false: the reference evaluates this model with P3M, which is not built. "
-                          "Ewald summation is the sum P3M approximates: pass p3m_as_ewald=True to evaluate with it")
+    if not lr["use_ewald"] and not p3m_as_ewald and method is None:
+        raise PetHipError("long_range.use_ewald is false: the reference evaluates this model with P3M, which is an explicit "
+                          "opt-in here: pass method='p3m' to evaluate with it. Ewald summation is the sum P3M approximates: "
+                          "pass p3m_as_ewald=True (or method='ewald') to evaluate with that")
+    if method == "p3m":
+        _check_nodes(lr["interpolation_nodes"])
     if hypers.get("num_neighbors_adaptive"):
         raise PetHipError("long_range together with num_neighbors_adaptive: the adaptive cutoff drops edges inside the "
                           "exclusion radius, on which the long-range exclusion term relies")
     return lr
+
+
+def _check_nodes(interpolation_nodes) -> int:
+    if isinstance(interpolation_nodes, bool) or int(interpolation_nodes) != interpolation_nodes or not 1 <= int(interpolation_nodes) <= 5:
+        raise PetHipError(f"interpolation_nodes must be an integer in 1..5: got {interpolation_nodes!r}")
+    return int(interpolation_nodes)
+
+
+def _cell9(cell):
+    flat = [float(x) for x in torch.as_tensor(cell, dtype=torch.float64).reshape(-1).tolist()]
+    if len(flat) != 9:
+        raise ValueError("cell must be [3, 3]")
+    return (c_double * 9)(*flat)
+
+
+def mesh_shape(cell, spacing: float) -> List[int]:
+    """The P3M mesh ``[N_0, N_1, N_2]`` of one ``cell [3, 3]`` at mesh spacing ``spacing`` (``pet_p3m_mesh_shape_host``).
+    Needs no GPU."""
+    out = (c_int32 * 3)()
+    if _lib.load().pet_p3m_mesh_shape_host(_cell9(cell), float(spacing), out) != 0:
+        raise PetHipError("singular cell or non-positive spacing")
+    return [int(x) for x in out]
+
+
+def influence(cell, smearing: float, spacing: float, interpolation_nodes: int = 5) -> torch.Tensor:
+    """The filter ``G^(n) / Omega`` (fp64, host) on the half spectrum ``[N_0, N_1, N_2 / 2 + 1]`` of one cell's mesh, from the
+    function the device evaluates at plan time (``pet_p3m_influence_host``). Needs no GPU."""
+    lib = _lib.load()
+    p = _check_nodes(interpolation_nodes)
+    h = _cell9(cell)
+    n = int(lib.pet_p3m_influence_host(h, float(smearing), float(spacing), p, None, 0))
+    if n < 0:
+        raise PetHipError("singular cell, or non-positive smearing or spacing")
+    buf = (c_double * n)()
+    lib.pet_p3m_influence_host(h, float(smearing), float(spacing), p, buf, n)
+    shape = mesh_shape(cell, spacing)
+    return torch.tensor(list(buf), dtype=torch.float64).reshape(shape[0], shape[1], shape[2] // 2 + 1)
 
 
 def kvectors(cell, kspace_resolution: float) -> torch.Tensor:
@@ -190,6 +253,116 @@ class EwaldHip:
         return (gq, gpos, gcell) if want_cell_grad else (gq, gpos)
 
 
+class P3MHip(EwaldHip):
+    """The same operator with the reciprocal-space sum on a mesh (a ``pet_ewald_t`` after ``pet_ewald_set_p3m``): ``plan``,
+    ``potential`` and ``backward`` as :class:`EwaldHip`, and ``mesh_shape(system)``. One application is
+    ``pet_p3m_spread -> torch.fft.rfftn -> pet_p3m_filter -> torch.fft.irfftn -> pet_p3m_finish`` on the current stream; the
+    meshes are channel-first ``[C, N_x, N_y, N_z]`` per periodic system, packed in batch order."""
+
+    def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5, interpolation_nodes: int = 5):
+        self.interpolation_nodes = _check_nodes(interpolation_nodes)
+        self.lib = _lib.load()
+        self.smearing, self.kspace_resolution, self.cutoff = float(smearing), float(kspace_resolution), float(cutoff)
+        self._handle = c_void_p()
+        check(self.lib.pet_ewald_create(self.smearing, self.kspace_resolution, self.cutoff, byref(self._handle)))
+        check(self.lib.pet_ewald_set_p3m(self._handle, self.interpolation_nodes))
+        self.n_systems = -1
+        self._workspace: Optional[torch.Tensor] = None
+        self._meshes: List[tuple] = []  # (shape, first mesh point, first half-spectrum point) per system with a mesh
+
+    def plan(self, cells, pbcs: Sequence[Sequence[bool]], first_atom: Sequence[int]) -> "P3MHip":
+        """Mesh descriptors and influence functions for the batch (``pet_ewald_plan`` in P3M mode). Valid while the cells and
+        the batch layout do not change. Mixed ``pbc`` and a mesh axis above 512 raise."""
+        super().plan(cells, pbcs, first_atom)
+        self._meshes = []
+        moff = soff = 0
+        out = (c_int32 * 3)()
+        for s in range(self.n_systems):
+            check(self.lib.pet_p3m_mesh_shape(self._handle, s, out))
+            n = (int(out[0]), int(out[1]), int(out[2]))
+            if n[0] == 0:
+                continue
+            self._meshes.append((n, moff, soff))
+            moff += n[0] * n[1] * n[2]
+            soff += n[0] * n[1] * (n[2] // 2 + 1)
+        self._mesh_points, self._spec_points = moff, soff
+        return self
+
+    def num_kvectors(self, system: int) -> int:
+        raise PetHipError("a P3M operator has no k-vector list: see mesh_shape(system)")
+
+    def mesh_shape(self, system: int) -> List[int]:
+        """``[N_0, N_1, N_2]`` of a planned system; zeros for a non-periodic or empty one, which has no mesh."""
+        out = (c_int32 * 3)()
+        check(self.lib.pet_p3m_mesh_shape(self._handle, int(system), out))
+        return [int(x) for x in out]
+
+    def _ws(self, channels: int, device) -> torch.Tensor:
+        nbytes = int(self.lib.pet_p3m_workspace_bytes(self._handle, channels))
+        if nbytes < 0:
+            raise PetHipError("pet_p3m_workspace_bytes failed: call plan() first")
+        if self._workspace is None or self._workspace.numel() < nbytes or self._workspace.device != device:
+            self._workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
+        return self._workspace
+
+    def _mesh_potential(self, graph, pos, x, ws, keep_spectrum: bool = False):
+        """spread -> rfftn -> filter -> irfftn of ``x [N, C]``: the mesh potential (packed, channel-first) and, on request, the
+        unfiltered half spectrum. Leaves the weights and bins of ``pos`` in the workspace."""
+        C = int(x.shape[1])
+        mesh = torch.empty(max(self._mesh_points * C, 1), dtype=torch.float32, device=x.device)
+        check(self.lib.pet_p3m_spread(self._handle, graph.handle, rt._ptr(pos), rt._ptr(x), C, rt._ptr(mesh), rt._ptr(ws),
+                                      ws.numel(), rt._stream()))
+        spec = torch.empty(max(self._spec_points * C, 1), dtype=torch.complex64, device=x.device)
+        views = []
+        for n, moff, soff in self._meshes:
+            m, mh = n[0] * n[1] * n[2], n[0] * n[1] * (n[2] // 2 + 1)
+            real = mesh[moff * C:(moff + m) * C].view(C, *n)
+            half = spec[soff * C:(soff + mh) * C].view(C, n[0], n[1], n[2] // 2 + 1)
+            torch.fft.rfftn(real, dim=(1, 2, 3), out=half)
+            views.append((n, real, half))
+        raw = spec.clone() if keep_spectrum else None
+        check(self.lib.pet_p3m_filter(self._handle, C, rt._ptr(spec), rt._stream()))
+        for n, real, half in views:
+            torch.fft.irfftn(half, s=n, dim=(1, 2, 3), norm="forward", out=real)
+        return mesh, raw
+
+    def _inputs(self, positions, *rows):
+        rt._require_cuda(positions, *rows)
+        pos = positions.detach().to(torch.float32).contiguous()
+        return (pos,) + tuple(r.detach().to(torch.float32).reshape(pos.shape[0], -1).contiguous() for r in rows)
+
+    def _finish(self, graph, pos, x, phi, ws):
+        out = torch.empty_like(x)
+        check(self.lib.pet_p3m_finish(self._handle, graph.handle, rt._ptr(pos), rt._ptr(x), int(x.shape[1]), rt._ptr(phi),
+                                      rt._ptr(out), rt._ptr(ws), ws.numel(), rt._stream()))
+        return out
+
+    def potential(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor) -> torch.Tensor:
+        """``V [N, C]`` for ``charges [N, C]``."""
+        pos, q = self._inputs(positions, charges)
+        ws = self._ws(q.shape[1], q.device)
+        phi, _ = self._mesh_potential(graph, pos, q, ws)
+        return self._finish(graph, pos, q, phi, ws)
+
+    def backward(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor, grad_potential: torch.Tensor,
+                 want_cell_grad: bool = False):
+        """``(dL/dq [N, C], dL/dR [N, 3])`` and on request ``dL/dcell [S, 3, 3]`` (fixed Cartesian positions) for
+        ``dL/dV = grad_potential``: the forward path applied to ``grad_potential`` (the operator is symmetric), then
+        ``pet_p3m_backward`` on the two mesh potentials and the two unfiltered spectra."""
+        pos, q, g = self._inputs(positions, charges, grad_potential)
+        C = int(q.shape[1])
+        ws = self._ws(C, q.device)
+        phi_q, spec_q = self._mesh_potential(graph, pos, q, ws, keep_spectrum=want_cell_grad)
+        phi_g, spec_g = self._mesh_potential(graph, pos, g, ws, keep_spectrum=want_cell_grad)
+        gq = self._finish(graph, pos, g, phi_g, ws)
+        gpos = torch.empty_like(pos)
+        gcell = torch.empty((graph.n_systems, 3, 3), dtype=torch.float32, device=q.device) if want_cell_grad else None
+        check(self.lib.pet_p3m_backward(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), rt._ptr(g), C, rt._ptr(phi_q),
+                                        rt._ptr(phi_g), rt._ptr(spec_q), rt._ptr(spec_g), rt._ptr(gpos), rt._ptr(gcell),
+                                        rt._ptr(ws), ws.numel(), rt._stream()))
+        return (gq, gpos, gcell) if want_cell_grad else (gq, gpos)
+
+
 class _EwaldFn(torch.autograd.Function):
     """The operator as an autograd node over the two HIP calls: gradients for charges, positions and cells."""
 
@@ -209,13 +382,19 @@ class _EwaldFn(torch.autograd.Function):
 
 class LongRangeFeaturizerHip:
     """``LongRangeFeaturizer`` (``utils/long_range.py``) on the device: ``charges_map`` and ``out_projection`` under the
-    reference's state-dict keys (fp32 torch ops on the device; there is no TF32 on gfx950) around :class:`EwaldHip`."""
+    reference's state-dict keys (fp32 torch ops on the device; there is no TF32 on gfx950) around :class:`EwaldHip` or, with
+    ``method="p3m"``, :class:`P3MHip` (``interpolation_nodes`` from the hypers). ``method=None`` follows the hypers and refuses
+    ``use_ewald: false``; ``method="ewald"`` is ``p3m_as_ewald=True``."""
 
-    def __init__(self, hypers: dict, device=None, p3m_as_ewald: bool = False):
-        self.long_range = resolve_hypers(hypers, p3m_as_ewald)
+    def __init__(self, hypers: dict, device=None, p3m_as_ewald: bool = False, method: Optional[str] = None):
+        self.long_range = resolve_hypers(hypers, p3m_as_ewald, method)
+        self.method = method
         self.d = int(hypers["d_node"])
         self.cutoff = float(hypers["cutoff"])
-        self.ewald = EwaldHip(self.long_range["smearing"], self.long_range["kspace_resolution"], self.cutoff)
+        lr = self.long_range
+        # (the attribute keeps its name: whichever operator evaluates the periodic systems)
+        self.ewald = (P3MHip(lr["smearing"], lr["kspace_resolution"], self.cutoff, lr["interpolation_nodes"]) if method == "p3m"
+                      else EwaldHip(lr["smearing"], lr["kspace_resolution"], self.cutoff))
         dev = torch.device("cpu") if device is None else torch.device(device)
         d = self.d
         self.params: Dict[str, torch.Tensor] = {}
@@ -241,8 +420,8 @@ class LongRangeFeaturizerHip:
 
     @classmethod
     def from_state_dict(cls, hypers: dict, state: Dict[str, torch.Tensor], device=None, p3m_as_ewald: bool = False,
-                        prefix: str = "long_range_featurizer.") -> "LongRangeFeaturizerHip":
-        self = cls(hypers, device, p3m_as_ewald)
+                        prefix: str = "long_range_featurizer.", method: Optional[str] = None) -> "LongRangeFeaturizerHip":
+        self = cls(hypers, device, p3m_as_ewald, method)
         self.load_state_dict(state, prefix)
         return self
 

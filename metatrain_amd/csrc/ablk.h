@@ -2,6 +2,7 @@
 // two-kernel adjoint). See pet_ablk.hip for the layout conventions (token form / feature form, planes of 64 x).
 #pragma once
 #include "common.h"
+#include "ablk_rows.h"  // (behind common.h: its __host__ __device__ come from the HIP runtime header)
 #include "model.h"
 #include "pet_ws.h"
 #include "trr.h"
@@ -108,40 +109,78 @@ extern __device__ unsigned long long ab_prof[32];  // defined in pet_ablk.hip
 // its neighbours = CSR rows startA ..) and, in a 32-slot tile, possibly a second atom B behind it (Graph::tile_desc; the
 // graph build pairs small atoms with partners that fit). Tokens attend within their own atom only. Slots past the last
 // token repeat it (their results are never stored and, as keys, are masked).
+// The slot -> row map is ablk_rows.h: the wave-uniform part (`rows`) is formed here, once per tile, and every row access of
+// the kernels is integer selects on it (slot(s)); addresses are byte offsets against the arrays' bases, never a choice
+// between two pointers. Row indices are 32-bit: the CSR starts are, and a token stream of 2^31 rows would be a terabyte.
 struct AbAtom {
     int atomA, startA, TA, atomB, startB, TB, T;
-    int64_t E;
-    __device__ __forceinline__ AbAtom(const int4* __restrict__ d, int64_t e) : E(e) {
+    int E;          // edge rows in front of the centre tokens of the token stream
+    int edge0, ne;  // the tile's first CSR row and the number of its neighbour slots (0: nothing of the edge arrays is the tile's)
+    AbTileRows rows;
+    __device__ __forceinline__ AbAtom(const int4* __restrict__ d, int64_t e) : E((int)e) {
         const int4 d0 = d[0], d1 = d[1];
         atomA = __builtin_amdgcn_readfirstlane(d0.x); startA = __builtin_amdgcn_readfirstlane(d0.y);
         TA = __builtin_amdgcn_readfirstlane(d0.z); atomB = __builtin_amdgcn_readfirstlane(d0.w);
         startB = __builtin_amdgcn_readfirstlane(d1.x); TB = __builtin_amdgcn_readfirstlane(d1.y);
         T = TA + TB;
+        ne = T - 1 - (TB > 0 ? 1 : 0);
+        edge0 = TA > 1 ? startA : startB;
+        rows = ab_tile_rows(atomA, startA, TA, atomB, startB, TB);
     }
-    __device__ __forceinline__ bool centre(int s) const { return s == 0 || s == TA; }
-    __device__ __forceinline__ int atom(int s) const { return s < TA ? atomA : atomB; }
-    __device__ __forceinline__ int64_t edge(int s) const {  // CSR row of a neighbour slot
-        return s < TA ? (int64_t)startA + s - 1 : (int64_t)startB + (s - TA) - 1;
-    }
-    __device__ __forceinline__ int64_t row(int s) const {  // row of the token stream [edges | centre tokens]
-        s = s < T ? s : T - 1;
-        return centre(s) ? E + atom(s) : edge(s);
-    }
+    __device__ __forceinline__ AbSlotRow slot(int s) const { return ab_slot_row(rows, s); }  // (s clamped to the last token)
+    // row of the token stream [edges | centre tokens]
+    __device__ __forceinline__ int row(int s) const { return ab_token_row(slot(s), E); }
+    // CSR row of a neighbour slot; of any other slot (`nb` false) the tile's first CSR row, which is always there to be read
+    // when the tile has a neighbour at all (ne > 0): unconditional loads of the edge arrays, selected afterwards
+    __device__ __forceinline__ int edge_or_first(const AbSlotRow& r, bool nb) const { return nb ? r.edge : edge0; }
 };
+
+// byte address of row `row` (512-B rows) of the array at `base`, plus `off` bytes
+// (pointer arithmetic, not integers: a pointer made from an integer is loaded from with flat_load instead of global_load)
+__device__ __forceinline__ const float* ab_row_ptr(const float* base, int row, unsigned off) {
+    return reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + ((uint64_t)(unsigned)row * 512u + off));
+}
+__device__ __forceinline__ float* ab_row_ptr(float* base, int row, unsigned off) {
+    return reinterpret_cast<float*>(reinterpret_cast<char*>(base) + ((uint64_t)(unsigned)row * 512u + off));
+}
+// byte offset of the 16-B piece this lane brings of row r = 2 j + (lane >> 5) of a DMA tile: 16 ((lane & 31) ^ (r & 15));
+// r & 15 = (2 j & 15) | (lane >> 5), so the lane's part is formed once (ab_piece0) and a request adds its constant
+__device__ __forceinline__ unsigned ab_piece0(const RowLane& L) { return 16u * (unsigned)((L.lane & 31) ^ (L.lane >> 5)); }
+__device__ __forceinline__ unsigned ab_piece(unsigned piece0, int j) { return piece0 ^ (32u * (unsigned)(j & 7)); }
 
 // whole-row LDS-DMA of the atom's token rows into the wave's tile(s): tile tq holds slots 32 tq .. 32 tq + 31 in the
 // layout of trr.h dma_tile128 (row r, 16-B piece p at byte 512 r + 16 (p ^ (r & 15)))
 template <int NQ>
 __device__ __forceinline__ void ab_dma_rows(const float* __restrict__ X, const AbAtom& a, unsigned lds_base,
                                             const RowLane& L) {
+    const unsigned piece0 = ab_piece0(L);
 #pragma unroll
     for (int tq = 0; tq < NQ; tq++)
 #pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const int r = 2 * j + (L.lane >> 5);
-            const int p = (L.lane & 31) ^ (r & 15);
-            glds16_trr(X + a.row(32 * tq + r) * D + 4 * p, lds_base + tq * 16384 + j * 1024);
-        }
+        for (int j = 0; j < 16; j++)
+            glds16_trr(ab_row_ptr(X, a.row(32 * tq + 2 * j + (L.lane >> 5)), ab_piece(piece0, j)),
+                       lds_base + tq * 16384 + j * 1024);
+}
+
+// 16 B / 4 B to global memory from the lanes where `on` holds, WITHOUT a branch: the exec mask is narrowed around the one
+// store (the compiler brackets every conditional memory access with s_cbranch_execz, sixteen times per epilogue)
+// The s_nop behind the 16-B store is not optional: on gfx940 and later a vector instruction must not write the data registers
+// of a store of more than 8 B within two wait states of it, the compiler's hazard recognizer does not look into inline assembly,
+// and it does reuse those registers in the very next instruction (without the s_nop a few rows per ten thousand came out wrong,
+// and only under load).
+typedef float ab_f32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void ab_store16_if(bool on, float* p, const float4& v) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(on);
+    const ab_f32x4 d = {v.x, v.y, v.z, v.w};
+    unsigned long long keep;
+    asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_dwordx4 %2, %3, off\n\ts_mov_b64 exec, %0\n\ts_nop 1"
+                 : "=&s"(keep) : "s"(m), "v"(p), "v"(d) : "memory", "scc");
+}
+__device__ __forceinline__ void ab_store4_if(bool on, float* p, float v) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(on);
+    unsigned long long keep;
+    asm volatile("s_and_saveexec_b64 %0, %1\n\tglobal_store_dword %2, %3, off\n\ts_mov_b64 exec, %0"
+                 : "=&s"(keep) : "s"(m), "v"(p), "v"(v) : "memory", "scc");
 }
 
 // planes of a normalised row tile in the wave's LDS: [kb 0..7][plane H, L][lane] f16x8
@@ -219,15 +258,32 @@ template <int NQ>
 __device__ __forceinline__ void ab_key_bias(float (&bias)[NQ][16], const AbAtom& a, const float* __restrict__ fc,
                                             const RowLane& L) {
     const bool qb = (L.r < a.T ? L.r : a.T - 1) >= a.TA;
+    // every lane loads for every key (a masked key reads the tile's first CSR row) and selects afterwards: the only branch
+    // is the wave-uniform one around the loads of a tile without a neighbour
+    float f[NQ][16];
+#pragma unroll
+    for (int tk = 0; tk < NQ; tk++)
+#pragma unroll
+        for (int i = 0; i < 16; i++) f[tk][i] = 1.f;
+    if (a.ne > 0) {
+#pragma unroll
+        for (int tk = 0; tk < NQ; tk++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int key = 32 * tk + 8 * (i >> 2) + 4 * L.h + (i & 3);
+                const AbSlotRow k = a.slot(key);
+                f[tk][i] = fc[a.edge_or_first(k, key < a.T && !k.centre)];
+            }
+    }
 #pragma unroll
     for (int tk = 0; tk < NQ; tk++)
 #pragma unroll
         for (int i = 0; i < 16; i++) {
             const int key = 32 * tk + 8 * (i >> 2) + 4 * L.h + (i & 3);
-            float b = -INFINITY;
-            if (key < a.T && (key >= a.TA) == qb)
-                b = a.centre(key) ? 0.f : __builtin_amdgcn_logf(fmaxf(fc[a.edge(key)], 1e-15f));
-            bias[tk][i] = b;
+            const bool on = key < a.T && (key >= a.TA) == qb;
+            float lg = __builtin_amdgcn_logf(fmaxf(f[tk][i], 1e-15f));
+            asm volatile("" : "+v"(lg));  // (taken by every lane: the compiler otherwise sinks the logarithm into a branch per key)
+            bias[tk][i] = on ? (a.slot(key).centre ? 0.f : lg) : -INFINITY;
         }
 }
 

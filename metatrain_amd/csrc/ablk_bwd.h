@@ -67,6 +67,9 @@ __global__ __launch_bounds__(256) void k_ablk_bwd(
     W2 wqkvt, const float* __restrict__ fc, const int4* __restrict__ desc, int n_list, int64_t E, float qscale, float scale,
     float* __restrict__ dXin, float* __restrict__ dbias) {
     extern __shared__ __attribute__((aligned(16))) char ab_smem[];
+    // the arguments that the row requests and what stands between them need are read with the first batch of argument loads:
+    // the compiler otherwise reads each where it is first used, with a scalar-cache wait of its own inside the request chain
+    asm volatile("" ::"s"(fc), "s"(wot.h), "s"(wot.l));
     const RowLane L;
     const unsigned lane16 = (unsigned)L.lane * 16u;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -83,18 +86,21 @@ __global__ __launch_bounds__(256) void k_ablk_bwd(
     const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
     AB_T0();
     ab_dma_rows<NQ>(X, a, tile_u, L);
-    // incoming adjoint: dX1 rows of the neighbours, dOC row of the centre token
+    // incoming adjoint: dX1 rows of the neighbours, dOC row of the centre token (one address = base + 512 index, both selected
+    // as integers)
+    {
+        const unsigned piece0 = ab_piece0(L);
+        const uintptr_t b_edge = reinterpret_cast<uintptr_t>(dX1), b_ctr = reinterpret_cast<uintptr_t>(dOC);
 #pragma unroll
-    for (int tq = 0; tq < NQ; tq++)
+        for (int tq = 0; tq < NQ; tq++)
 #pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const int r = 2 * j + (L.lane >> 5);
-            const int p = (L.lane & 31) ^ (r & 15);
-            int s = 32 * tq + r;
-            s = s < a.T ? s : a.T - 1;
-            const float* src = a.centre(s) ? dOC + (int64_t)a.atom(s) * D : dX1 + a.edge(s) * D;
-            glds16_trr(src + 4 * p, tile_u + NQ * 16384 + tq * 16384 + j * 1024);
-        }
+            for (int j = 0; j < 16; j++) {
+                const AbSlotRow r = a.slot(32 * tq + 2 * j + (L.lane >> 5));
+                const uintptr_t src = (r.centre ? b_ctr : b_edge) + ((uint64_t)(unsigned)(r.centre ? r.atom : r.edge) * 512u +
+                                                                     ab_piece(piece0, j));
+                glds16_trr(reinterpret_cast<const float*>(src), tile_u + NQ * 16384 + tq * 16384 + j * 1024);
+            }
+    }
     ab_bwd_request<NW>(0, wqkv, wot, wqkvt, ring_u, wave, lane16);
     float bias[NQ][16];
     ab_key_bias<NQ>(bias, a, fc, L);
@@ -415,7 +421,8 @@ __global__ __launch_bounds__(256) void k_ablk_bwd(
     for (int tk = 0; tk < NQ; tk++) {
         const float v = (db[tk] + __shfl_xor(db[tk], 32)) * (inv_sc * ABS_INV);  // the transposed planes held 64 dS
         const int key = 32 * tk + L.r;
-        if (live && L.h == 0 && key < a.T && !a.centre(key)) dbias[a.edge(key)] = v;
+        const AbSlotRow k = a.slot(key);
+        ab_store4_if(live && L.h == 0 && key < a.T && !k.centre, dbias + k.edge, v);
     }
     // ---- norm adjoint, residual, whole-line stores
     __builtin_amdgcn_wave_barrier();
@@ -433,15 +440,25 @@ __global__ __launch_bounds__(256) void k_ablk_bwd(
                 w[4 * t + j] = make_float4(dxn[tq][t][4 * j] * f, dxn[tq][t][4 * j + 1] * f, dxn[tq][t][4 * j + 2] * f,
                                            dxn[tq][t][4 * j + 3] * f);
         const int rr = L.lane >> 4, cc = 4 * (L.lane & 15);
-        float4 dr[2][8];  // the residual (dX1 rows) in the store's shape, requested before the norm adjoint's arithmetic
+        // the residual (dX1 rows) in the store's shape, requested before the norm adjoint's arithmetic: every lane reads (a
+        // centre or dead slot the tile's first CSR row) and the slots without a residual are zeroed where it is added
+        float4 dr[2][8];
+        AbSlotRow sr[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) sr[j] = a.slot(32 * tq + 4 * j + rr);
 #pragma unroll
         for (int c = 0; c < 2; c++)
 #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const int s = 32 * tq + 4 * j + rr;
-                dr[c][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (s < a.T && !a.centre(s)) dr[c][j] = *reinterpret_cast<const float4*>(dX1 + a.edge(s) * D + 64 * c + cc);
-            }
+            for (int j = 0; j < 8; j++) dr[c][j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.ne > 0) {
+#pragma unroll
+            for (int c = 0; c < 2; c++)
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const bool nb = 32 * tq + 4 * j + rr < a.T && !sr[j].centre;
+                    dr[c][j] = *reinterpret_cast<const float4*>(ab_row_ptr(dX1, a.edge_or_first(sr[j], nb), 256 * c + 4 * cc));
+                }
+        }
         ab_norm_adjoint_planes<LN>(w, tile + tq * 16384, rstd[tq], L);
 #pragma unroll
         for (int c = 0; c < 2; c++) {
@@ -452,12 +469,11 @@ __global__ __launch_bounds__(256) void k_ablk_bwd(
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const int r = 4 * j + rr, s = 32 * tq + r;
-                if (live && s < a.T) {
-                    float4 o4 = *reinterpret_cast<const float4*>(stg + r * TILE_LD + cc);
-                    o4.x += dr[c][j].x; o4.y += dr[c][j].y; o4.z += dr[c][j].z; o4.w += dr[c][j].w;
-                    float* dst = dXin + (a.centre(s) ? E + a.atom(s) : a.edge(s)) * D;
-                    *reinterpret_cast<float4*>(dst + 64 * c + cc) = o4;
-                }
+                const bool nb = s < a.T && !sr[j].centre;
+                float4 o4 = *reinterpret_cast<const float4*>(stg + r * TILE_LD + cc);
+                o4.x += nb ? dr[c][j].x : 0.f; o4.y += nb ? dr[c][j].y : 0.f;
+                o4.z += nb ? dr[c][j].z : 0.f; o4.w += nb ? dr[c][j].w : 0.f;
+                ab_store16_if(live && s < a.T, ab_row_ptr(dXin, ab_token_row(sr[j], a.E), 256 * c + 4 * cc), o4);
             }
             __builtin_amdgcn_wave_barrier();
         }

@@ -71,6 +71,13 @@ __device__ __forceinline__ void ab_fwd_request(int g, const W2& wqkv, const W2& 
 }
 // (the adjoint's ring stages and the adjoint kernel itself: ablk_bwd.h)
 
+// where a slot's output row goes: row `edge` of X1 (a neighbour) or row `atom` of OC (the centre token), plus `off` bytes;
+// base and index are selected as integers
+__device__ __forceinline__ float* ab_out_ptr(float* X1, float* OC, const AbSlotRow& sr, unsigned off) {
+    const uintptr_t base = sr.centre ? reinterpret_cast<uintptr_t>(OC) : reinterpret_cast<uintptr_t>(X1);
+    return reinterpret_cast<float*>(base + ((uint64_t)(unsigned)(sr.centre ? sr.atom : sr.edge) * 512u + off));
+}
+
 // ---------------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------------
@@ -232,15 +239,24 @@ __global__ __launch_bounds__(256) void k_ablk_fwd(
     const int rr = L.lane >> 4, cc = 4 * (L.lane & 15);
 #pragma unroll
     for (int c = 0; c < 2; c++) {  // 64 output features at a time
-        float4 xr[NQ][8];  // the residual rows of this half in the store's shape, requested before the products
+        // the residual rows of this half in the store's shape, requested before the products: every lane reads (a centre or
+        // dead slot the tile's first CSR row); the slots without a residual are zeroed where it is added
+        float4 xr[NQ][8];
 #pragma unroll
         for (int tq = 0; tq < NQ; tq++)
 #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const int s = 32 * tq + 4 * j + rr;
-                xr[tq][j] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (s < a.T && !a.centre(s)) xr[tq][j] = *reinterpret_cast<const float4*>(X + a.edge(s) * D + 64 * c + cc);
-            }
+            for (int j = 0; j < 8; j++) xr[tq][j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.ne > 0) {
+#pragma unroll
+            for (int tq = 0; tq < NQ; tq++)
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const int s = 32 * tq + 4 * j + rr;
+                    const AbSlotRow sr = a.slot(s);
+                    xr[tq][j] = *reinterpret_cast<const float4*>(
+                        ab_row_ptr(X, a.edge_or_first(sr, s < a.T && !sr.centre), 256 * c + 4 * cc));
+                }
+        }
         f32x16 y[NQ][2];
 #pragma unroll
         for (int tq = 0; tq < NQ; tq++) {
@@ -284,12 +300,12 @@ __global__ __launch_bounds__(256) void k_ablk_fwd(
 #pragma unroll
             for (int j = 0; j < 8; j++) {
                 const int r = 4 * j + rr, s = 32 * tq + r;
-                if (live && s < a.T) {
-                    float4 o4 = *reinterpret_cast<const float4*>(stg + r * TILE_LD + cc);
-                    o4.x += xr[tq][j].x; o4.y += xr[tq][j].y; o4.z += xr[tq][j].z; o4.w += xr[tq][j].w;
-                    float* dst = a.centre(s) ? OC + (int64_t)a.atom(s) * D : X1 + a.edge(s) * D;
-                    *reinterpret_cast<float4*>(dst + 64 * c + cc) = o4;
-                }
+                const AbSlotRow sr = a.slot(s);
+                const bool nb = s < a.T && !sr.centre;
+                float4 o4 = *reinterpret_cast<const float4*>(stg + r * TILE_LD + cc);
+                o4.x += nb ? xr[tq][j].x : 0.f; o4.y += nb ? xr[tq][j].y : 0.f;
+                o4.z += nb ? xr[tq][j].z : 0.f; o4.w += nb ? xr[tq][j].w : 0.f;
+                ab_store16_if(live && s < a.T, ab_out_ptr(X1, OC, sr, 256 * c + 4 * cc), o4);
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -481,12 +497,16 @@ __global__ __launch_bounds__(256, 2) void k_ablk_fwd4(
     const int rr = L.lane >> 4, cc = 4 * (L.lane & 15);
 #pragma unroll
     for (int c = 0; c < 2; c++) {
-        float4 xr[8];
+        float4 xr[8];  // (every lane reads; the slots without a residual are zeroed where it is added: k_ablk_fwd)
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const int sl = 4 * j + rr;
-            xr[j] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (sl < a.T && !a.centre(sl)) xr[j] = *reinterpret_cast<const float4*>(X + a.edge(sl) * D + 64 * c + cc);
+        for (int j = 0; j < 8; j++) xr[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.ne > 0) {
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const AbSlotRow sr = a.slot(4 * j + rr);
+                xr[j] = *reinterpret_cast<const float4*>(
+                    ab_row_ptr(X, a.edge_or_first(sr, 4 * j + rr < a.T && !sr.centre), 256 * c + 4 * cc));
+            }
         }
 #pragma unroll
         for (int t = 0; t < 2; t++)
@@ -499,12 +519,12 @@ __global__ __launch_bounds__(256, 2) void k_ablk_fwd4(
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             const int r = 4 * j + rr;
-            if (live && r < a.T) {
-                float4 o4 = *reinterpret_cast<const float4*>(stg + r * TILE_LD + cc);
-                o4.x += xr[j].x; o4.y += xr[j].y; o4.z += xr[j].z; o4.w += xr[j].w;
-                float* dst = a.centre(r) ? OC + (int64_t)a.atom(r) * D : X1 + a.edge(r) * D;
-                *reinterpret_cast<float4*>(dst + 64 * c + cc) = o4;
-            }
+            const AbSlotRow sr = a.slot(r);
+            const bool nb = r < a.T && !sr.centre;
+            float4 o4 = *reinterpret_cast<const float4*>(stg + r * TILE_LD + cc);
+            o4.x += nb ? xr[j].x : 0.f; o4.y += nb ? xr[j].y : 0.f;
+            o4.z += nb ? xr[j].z : 0.f; o4.w += nb ? xr[j].w : 0.f;
+            ab_store16_if(live && r < a.T, ab_out_ptr(X1, OC, sr, 256 * c + 4 * cc), o4);
         }
         __builtin_amdgcn_wave_barrier();
     }

@@ -563,7 +563,7 @@ int pet_zbl_hessian_vector(const pet_zbl_t* z, const pet_graph_t* g, const float
  *              dL/dR_i += P sum_{row i, j != i} w'(d) (B_p + B'_p) D/d,   dL/dcell_ab += -P sum_p w'(d) B_p S_a D_b / d
  *              (an edge from an atom to its own image moves with the cell only)
  *   non-periodic: dL/dR_i = -P sum_{j != i} K'(d) (g_i.q_j + g_j.q_i) (r_j - r_i)/d.
- * Kernels (csrc/ewald.hip): structure factors, the gather back to atoms and the all-pairs sum are GEMMs on the fp32 matrix
+ * Kernels (csrc/ewald.hip; the local terms, shared with P3M mode, in csrc/long_range.h): structure factors, the gather back to atoms and the all-pairs sum are GEMMs on the fp32 matrix
  * core (v_mfma_f32_32x32x2_f32) with one operand GENERATED in registers -- phases as products of per-axis tables
  * e^{2 pi i n s_a}, built in fp64 from fractional coordinates and rounded once; cos(k.r) of a large fp32 argument is never
  * formed. Sums over atoms and over k run in fixed-order chunks relative to the system's first atom / first k-vector, the
@@ -634,7 +634,8 @@ int pet_ewald_backward(const pet_ewald_t* e, const pet_graph_t* g, const float* 
  *     background, exclusion -> d_out [N, C].   pet_p3m_backward: d_grad_positions [N, 3] and d_grad_cells [S, 3, 3] (may be
  *     NULL, then the spectra may be too) from the mesh potentials and UNFILTERED spectra of q and g: mesh, exclusion and
  *     open-system parts.
- * PET_ERR_UNSUPPORTED: a mesh axis above PET_P3M_MAX_AXIS; mixed pbc. No float atomics; fixed orders (csrc/p3m.hip). */
+ * PET_ERR_UNSUPPORTED: a mesh axis above PET_P3M_MAX_AXIS; mixed pbc. No float atomics; fixed orders (csrc/p3m.hip, and
+ * csrc/long_range.h for the terms both modes launch). */
 #define PET_P3M_MAX_AXIS 512
 int pet_ewald_set_p3m(pet_ewald_t* e, int32_t interpolation_nodes);
 int pet_p3m_mesh_shape_host(const double* h_cell, double spacing, int32_t* out);

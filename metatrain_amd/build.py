@@ -21,10 +21,6 @@ VGPR_FORM_FLAGS = ["-fno-gpu-rdc", "-mllvm", "-amdgpu-mfma-vgpr-form"]
 NO_RDC = {"pet_comb_bwd_s.hip", "so_rows_s.hip", "zbl.hip", "ewald.hip", "p3m.hip", "augment.hip", "wigner.hip", "baseline.hip", "loss.hip"}  # (zbl.hip, ewald.hip, p3m.hip, augment.hip, wigner.hip, baseline.hip, loss.hip: self-contained; their register / scratch report is per file)
 
 
-# translation units that #include another one (p3m.hip compiles ewald.hip's shared kernels together with its own)
-INCLUDES = {"p3m.hip": ["ewald.hip"]}
-
-
 def _newer(a, b):
     return not os.path.exists(b) or os.path.getmtime(a) > os.path.getmtime(b)
 
@@ -50,7 +46,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _newer(s, o) or hdr_time > os.path.getmtime(o) or any(_newer(os.path.join(CSRC, d), o) for d in INCLUDES.get(src, ())):
+        if force or _newer(s, o) or hdr_time > os.path.getmtime(o):
             cmd = ["hipcc", *FLAGS, *(VGPR_FORM_FLAGS if src in VGPR_FORM else []), *(["-fno-gpu-rdc"] if src in NO_RDC else []), "-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)

@@ -1,13 +1,13 @@
 // P3M (particle-particle particle-mesh) evaluation of the long-range operator's reciprocal-space sum: the second implementation
 // of the k-space term of ewald.hip, O(N p^3 C + M log M) where the Ewald sum costs O(N K C). The definition, the convention
 // table and the adjoints are in include/pet_hip.h (block pet_p3m_*) and DESIGN.md section 19. The self, background, exclusion
-// and open-system terms are the kernels of ewald.hip, compiled into this translation unit as they stand (PET_EWALD_SHARED_ONLY).
+// and open-system terms, their adjoints and the handle are those of long_range.h, which this file shares with ewald.hip.
 // Stages (the transforms between them are the caller's: torch.fft on the same stream, no second FFT library in this one):
 //   pet_p3m_spread   k_p3m_bin_* (weights [N,3,p] in fp64 from wrapped fractional coordinates, rounded once; a stable counting
 //                    sort of the atoms by the mesh cell of their stencil origin) and k_p3m_spread in owner-computes form
 //   pet_p3m_filter   k_p3m_filter: half spectrum times G^/Omega (k_p3m_influence at plan time, fp64 -> fp32)
-//   pet_p3m_finish   k_p3m_gather, then k_ew_pairs / k_ew_colsum / k_ew_finish
-//   pet_p3m_backward k_p3m_force, k_ew_force<false>, k_ew_edge_bwd, k_p3m_cell, k_ew_cell
+//   pet_p3m_finish   k_p3m_gather, then ew_local_forward (k_ew_pairs / k_ew_colsum / k_ew_finish)
+//   pet_p3m_backward k_p3m_force, then ew_local_backward (k_ew_force<false>, k_ew_edge_bwd, k_ew_cell) with k_p3m_cell before k_ew_cell
 // Layout. CHANNEL-FIRST: the mesh of a system is [C, N_x, N_y, N_z] (z fastest), its half spectrum [C, N_x, N_y, N_z/2 + 1]
 // complex; the meshes of a batch's periodic, non-empty systems are packed one after another (system s starts at mesh_off_s * C).
 // The transforms run over contiguous planes with batch stride M and need no copy; the price is on this side: k_p3m_spread owns
@@ -17,8 +17,7 @@
 // p^3 nodes in the same order; channels are reduced by the butterfly of k_ew_force; per-point parts of dL/dcell are reduced per
 // chunk of 1024 half-spectrum points by a fixed tree and then in chunk order (k_ew_cell). The only atomics are integer counters
 // of the counting sort, whose result (a bin's atoms in atom order, after k_p3m_bin_sort) does not depend on their order.
-#define PET_EWALD_SHARED_ONLY
-#include "ewald.hip"
+#include "long_range.h"
 
 namespace pet {
 
@@ -126,17 +125,6 @@ __host__ __device__ inline double p3m_influence_point(const double* inv, double 
     if (grad)
         for (int k = 0; k < 9; k++) grad[k] *= d2;
     return num * d2;
-}
-
-// cell^{-1} (row-major) and |det|; false for a singular cell
-inline bool p3m_inverse(const double* h, double* inv, double* vol) {
-    const double det = h[0] * (h[4] * h[8] - h[5] * h[7]) - h[1] * (h[3] * h[8] - h[5] * h[6]) + h[2] * (h[3] * h[7] - h[4] * h[6]);
-    if (!(std::fabs(det) > 1e-12) || !std::isfinite(det)) return false;
-    inv[0] = (h[4] * h[8] - h[5] * h[7]) / det; inv[1] = (h[2] * h[7] - h[1] * h[8]) / det; inv[2] = (h[1] * h[5] - h[2] * h[4]) / det;
-    inv[3] = (h[5] * h[6] - h[3] * h[8]) / det; inv[4] = (h[0] * h[8] - h[2] * h[6]) / det; inv[5] = (h[2] * h[3] - h[0] * h[5]) / det;
-    inv[6] = (h[3] * h[7] - h[4] * h[6]) / det; inv[7] = (h[1] * h[6] - h[0] * h[7]) / det; inv[8] = (h[0] * h[4] - h[1] * h[3]) / det;
-    *vol = std::fabs(det);
-    return true;
 }
 
 __device__ __forceinline__ int p3m_wrap(int i, int n) {
@@ -464,8 +452,7 @@ struct P3mWs {
     float *wts, *dwts;
     int4* org;
     int *start, *fill, *order, *bsum;
-    float *sum1, *sum2, *F, *cell_part;
-    double* kpart;
+    EwLocalWs loc;  // kpart: one entry per reduction chunk
 };
 
 size_t p3m_carve(const pet_ewald_t* e, int64_t C, void* base, P3mWs& w) {
@@ -480,11 +467,11 @@ size_t p3m_carve(const pet_ewald_t* e, int64_t C, void* base, P3mWs& w) {
     w.fill = c.take<int>(M + 1);
     w.order = c.take<int>(N);
     w.bsum = c.take<int>((M + 1 + 1023) / 1024 + 1);
-    w.sum1 = c.take<float>(S * C);
-    w.sum2 = c.take<float>(S * C);
-    w.F = c.take<float>(N * 3);
-    w.cell_part = c.take<float>(N * 9);
-    w.kpart = c.take<double>(std::max<size_t>(mp->stiles.size(), 1) * 9);
+    w.loc.sum_q = c.take<float>(S * C);
+    w.loc.sum_g = c.take<float>(S * C);
+    w.loc.F = c.take<float>(N * 3);
+    w.loc.cell_part = c.take<float>(N * 9);
+    w.loc.kpart = c.take<double>(std::max<size_t>(mp->stiles.size(), 1) * 9);
     return c.off;
 }
 
@@ -518,28 +505,28 @@ int p3m_bin(const pet_ewald_t* e, const Graph& g, const float* pos, const P3mWs&
 
 }  // namespace
 
-// pet_ewald_plan of a P3M-mode handle: mesh descriptors and influence functions instead of k lists. geometry [S][10] = cell^{-1}
-// and Omega, has_mesh [S]; chunks [S][2] receives every system's range of reduction chunks (what k_ew_cell walks in place of
-// k-vectors).
-int p3m_plan_build(double sigma, double spacing, int nodes, const double* h_cells, const double* geometry, const int* has_mesh,
-                   int64_t n_systems, int* chunks, P3mPlan** out) {
+// pet_ewald_plan of a P3M-mode handle: mesh descriptors and influence functions instead of k lists, for the systems the shared
+// part of the plan has described in sys. A periodic system with atoms gets a mesh; every system's range of reduction chunks
+// (what k_ew_cell walks in this mode) goes into its first_k / n_k.
+int p3m_plan_build(double sigma, double spacing, int nodes, const double* h_cells, std::vector<EwSys>& sys, P3mPlan** out) {
     P3mPlan* mp = new P3mPlan();
     struct Guard {
         P3mPlan* p;
         ~Guard() { p3m_release(p); }
     } guard{mp};
-    mp->sys.resize((size_t)n_systems);
-    for (size_t s = 0; s < (size_t)n_systems; s++) {
+    const size_t n_systems = sys.size();
+    mp->sys.resize(n_systems);
+    for (size_t s = 0; s < n_systems; s++) {
         P3mSysD& m = mp->sys[s];
         m.n[0] = m.n[1] = m.n[2] = 0;
         m.nzh = 0;
         m.moff = mp->m_total;
         m.soff = mp->s_total;
-        for (int k = 0; k < 9; k++) m.inv[k] = geometry[10 * s + k];
-        m.vol = geometry[10 * s + 9];
-        chunks[2 * s] = (int)mp->stiles.size();
-        chunks[2 * s + 1] = 0;
-        if (!has_mesh[s]) continue;
+        for (int k = 0; k < 9; k++) m.inv[k] = sys[s].inv[k];
+        m.vol = sys[s].vol;
+        sys[s].first_k = (int)mp->stiles.size();
+        sys[s].n_k = 0;
+        if (!sys[s].periodic || sys[s].n_atoms == 0) continue;
         p3m_mesh_shape(h_cells + 9 * s, spacing, m.n);
         for (int a = 0; a < 3; a++)
             PET_REQUIRE(m.n[a] <= P3M_MAX_AXIS, PET_ERR_UNSUPPORTED,
@@ -550,7 +537,7 @@ int p3m_plan_build(double sigma, double spacing, int nodes, const double* h_cell
         const int64_t M = (int64_t)m.n[0] * m.n[1] * m.n[2], Mh = (int64_t)m.n[0] * m.n[1] * m.nzh;
         for (int64_t i = 0; i < M; i += 256) mp->mtiles.push_back(make_int2((int)s, (int)i));
         for (int64_t i = 0; i < Mh; i += P3M_CHUNK) mp->stiles.push_back(make_int2((int)s, (int)i));
-        chunks[2 * s + 1] = (int)mp->stiles.size() - chunks[2 * s];
+        sys[s].n_k = (int)mp->stiles.size() - sys[s].first_k;
         mp->m_total += M;
         mp->s_total += Mh;
         PET_REQUIRE(mp->m_total < (int64_t(1) << 30), PET_ERR_UNSUPPORTED, "the meshes of one batch hold more than 2^30 points");
@@ -587,7 +574,7 @@ int pet_ewald_set_p3m(pet_ewald_t* e, int32_t interpolation_nodes) {
 int pet_p3m_mesh_shape_host(const double* h_cell, double spacing, int32_t* out) {
     if (!h_cell || !out || !(spacing > 0.0) || !std::isfinite(spacing)) return -1;
     double inv[9], vol;
-    if (!p3m_inverse(h_cell, inv, &vol)) return -1;
+    if (!ew_cell_inverse(h_cell, inv, &vol)) return -1;
     int n[3];
     p3m_mesh_shape(h_cell, spacing, n);
     for (int a = 0; a < 3; a++) out[a] = n[a];
@@ -598,7 +585,7 @@ int64_t pet_p3m_influence_host(const double* h_cell, double smearing, double spa
                                double* h_out, int64_t capacity) {
     if (!h_cell || !(spacing > 0.0) || !(smearing > 0.0) || interpolation_nodes < 1 || interpolation_nodes > 5) return -1;
     double inv[9], vol;
-    if (!p3m_inverse(h_cell, inv, &vol)) return -1;
+    if (!ew_cell_inverse(h_cell, inv, &vol)) return -1;
     int N[3];
     p3m_mesh_shape(h_cell, spacing, N);
     const int nzh = N[2] / 2 + 1;
@@ -686,20 +673,10 @@ int pet_p3m_finish(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_p
     P3mWs w;
     p3m_carve(e, C, d_workspace, w);
     ProfScope ps("p3m_finish", st, 0.0, 0.0);
-    const unsigned cy = (unsigned)cdiv(C, 256);
     if (mp->m_total > 0)
         k_p3m_gather<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, e->p3m_nodes, d_mesh_potential,
                                                           (int)e->n_atoms, C, d_out);
-    if (!e->atiles_n.empty())
-        k_ew_pairs<<<dim3((unsigned)e->atiles_n.size(), cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, d_positions,
-                                                                          (float)(1.0 / e->cutoff), d_charges, C, d_out);
-    k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_charges, C, w.sum1);
-    k_ew_finish<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.geo, d_charges, w.sum1, (int)e->n_atoms, C,
-                                                     (float)(std::sqrt(2.0 / EW_PI) / e->sigma),
-                                                     (float)(2.0 * EW_PI * e->sigma * e->sigma),
-                                                     (float)(1.0 / (std::sqrt(2.0) * e->sigma)), (float)(1.0 / e->cutoff), d_out);
-    PET_HIP_CHECK(hipGetLastError());
-    return PET_OK;
+    return ew_local_forward(e, g, d_positions, d_charges, C, d_out, w.loc.sum_q, st);
 }
 
 int pet_p3m_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
@@ -709,11 +686,7 @@ int pet_p3m_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float* d
     if (int rc = p3m_check(e, pg, C, d_workspace, workspace_bytes)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Graph& g = pg->g;
-    if (e->n_atoms == 0) {
-        if (d_grad_cells && e->n_systems > 0)
-            PET_HIP_CHECK(hipMemsetAsync(d_grad_cells, 0, (size_t)e->n_systems * 9 * sizeof(float), st));
-        return PET_OK;
-    }
+    if (e->n_atoms == 0) return ew_backward_empty(e, d_grad_cells, st);
     PET_REQUIRE(d_positions && d_charges && d_grad_potential && d_grad_positions, PET_ERR_ARGUMENT, "null argument");
     const P3mPlan* mp = e->p3m;
     PET_REQUIRE(mp->m_total == 0 || (d_phi_q && d_phi_g), PET_ERR_ARGUMENT, "no mesh potentials (pet_p3m_mesh_elements)");
@@ -723,27 +696,16 @@ int pet_p3m_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float* d
     p3m_carve(e, C, d_workspace, w);
     ProfScope ps("p3m_bwd", st, 0.0, 0.0);
     const unsigned cy = (unsigned)cdiv(C, 256);
-    k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_charges, C, w.sum1);
-    k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_grad_potential, C, w.sum2);
-    const bool vec = C % 4 == 0 && ((uintptr_t)d_charges & 15) == 0 && ((uintptr_t)d_grad_potential & 15) == 0;
-    const float inv_R = (float)(1.0 / e->cutoff);
+    k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_charges, C, w.loc.sum_q);
+    k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_grad_potential, C, w.loc.sum_g);
     if (mp->m_total > 0)
         k_p3m_force<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, w.dwts, e->p3m_nodes, d_phi_q, d_phi_g,
-                                                         d_grad_potential, d_charges, (int)e->n_atoms, C, w.F);
-    if (!e->atiles_n.empty())
-        k_ew_force<false><<<(unsigned)e->atiles_n.size(), 256, 0, st>>>(e->d_atiles_n, e->d_sys, nullptr, nullptr, 1, d_positions,
-                                                                        inv_R, d_grad_potential, d_charges, nullptr, nullptr, C, vec, w.F);
-    k_ew_edge_bwd<<<(unsigned)e->n_atoms, 64, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.shift, g.geo, d_positions,
-                                                       d_grad_potential, d_charges, w.F, C, e->sigma, e->cutoff, d_grad_positions,
-                                                       d_grad_cells ? w.cell_part : nullptr);
-    if (d_grad_cells) {
+                                                         d_grad_potential, d_charges, (int)e->n_atoms, C, w.loc.F);
+    return ew_local_backward(e, g, d_positions, d_charges, d_grad_potential, C, w.loc, d_grad_positions, d_grad_cells, st, [&] {
         if (!mp->stiles.empty())
             k_p3m_cell<<<(unsigned)mp->stiles.size(), 256, 0, st>>>(mp->d_stiles, mp->d_sys, (const float2*)d_spec_q,
-                                                                   (const float2*)d_spec_g, C, e->sigma, e->p3m_nodes, w.kpart);
-        k_ew_cell<<<(unsigned)e->n_systems, 256, 0, st>>>(e->d_sys, w.cell_part, w.kpart, w.sum2, w.sum1, C, e->sigma, d_grad_cells);
-    }
-    PET_HIP_CHECK(hipGetLastError());
-    return PET_OK;
+                                                                   (const float2*)d_spec_g, C, e->sigma, e->p3m_nodes, w.loc.kpart);
+    });
 }
 
 }  // extern "C"

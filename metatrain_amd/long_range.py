@@ -13,8 +13,9 @@ With ``L`` readout layers and node features ``h_l [N, d_node]`` the reference co
 tests pin no values, so the operator is fixed HERE by definition (the formulas are in ``include/pet_hip.h``, block
 ``pet_ewald_*``, and DESIGN.md section 18) and pinned to an independent fp64 oracle (``tests/_ewald_oracle.py``). **Parity
 with torch-pme is not pinned.** Every convention constant of that definition is in :data:`CONVENTIONS` below (and, as the
-same table); the kernels hold them as ``EW_PREFACTOR``, the three coefficients ``pet_ewald_potential``
-passes to ``k_ew_finish`` and the weight ``pet_ewald_plan`` gives every k-vector (``csrc/ewald.hip``).
+same table); the kernels hold them as ``EW_PREFACTOR`` and the three coefficients ``ew_local_forward``
+passes to ``k_ew_finish`` (``csrc/long_range.h``: the local terms and their adjoints, which both operators below launch) and
+the weight ``pet_ewald_plan`` gives every k-vector (``csrc/ewald.hip``).
 
 :class:`EwaldHip` is the operator (``csrc/ewald.hip``: structure factors, the gather back to atoms and the open all-pairs sum
 as fp32 matrix-core GEMMs with a generated operand; fixed summation orders, no atomics), :class:`LongRangeFeaturizerHip` the
@@ -144,10 +145,7 @@ def kvectors(cell, kspace_resolution: float) -> torch.Tensor:
     ``|k| <= 2 pi / kspace_resolution`` (``pet_ewald_kvectors_host``; the kernels walk one of every pair ``(k, -k)``).
     Needs no GPU."""
     lib = _lib.load()
-    flat = [float(x) for x in torch.as_tensor(cell, dtype=torch.float64).reshape(-1).tolist()]
-    if len(flat) != 9:
-        raise ValueError("cell must be [3, 3]")
-    h = (c_double * 9)(*flat)
+    h = _cell9(cell)
     n = int(lib.pet_ewald_kvectors_host(h, float(kspace_resolution), None, 0))
     if n < 0:
         raise PetHipError("singular cell or non-positive kspace_resolution")
@@ -167,6 +165,9 @@ def _first_atoms(system_indices: torch.Tensor, n_systems: int) -> List[int]:
 class EwaldHip:
     """``pet_ewald_t``: the operator ``q [N, C] -> V [N, C]`` and its adjoints on device tensors."""
 
+    _warns_kset = True  # the k-set warning is the Ewald sum's: a mesh operator walks no k-set
+    _workspace_bytes = "pet_ewald_workspace_bytes"
+
     def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5):
         global _warned_kset
         self.lib = _lib.load()
@@ -174,7 +175,7 @@ class EwaldHip:
         self._handle = c_void_p()
         check(self.lib.pet_ewald_create(self.smearing, self.kspace_resolution, self.cutoff, byref(self._handle)))
         t = truncation_factor(self.smearing, self.kspace_resolution)
-        if t > 1e-7 and not _warned_kset:
+        if self._warns_kset and t > 1e-7 and not _warned_kset:
             _warned_kset = True
             logging.warning(f"long range: exp(-(smearing 2 pi / kspace_resolution)^2 / 2) = {t:.1e} exceeds 1e-7: the k-space "
                             "sum has not converged inside the k-set, so the result depends on the SHAPE of the k-set (a "
@@ -218,18 +219,21 @@ class EwaldHip:
         return n
 
     def _ws(self, channels: int, device) -> torch.Tensor:
-        nbytes = int(self.lib.pet_ewald_workspace_bytes(self._handle, channels))
+        nbytes = int(getattr(self.lib, self._workspace_bytes)(self._handle, channels))
         if nbytes < 0:
-            raise PetHipError("pet_ewald_workspace_bytes failed: call plan() first")
+            raise PetHipError(f"{self._workspace_bytes} failed: call plan() first")
         if self._workspace is None or self._workspace.numel() < nbytes or self._workspace.device != device:
             self._workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
         return self._workspace
 
+    def _inputs(self, positions, *rows):
+        rt._require_cuda(positions, *rows)
+        pos = positions.detach().to(torch.float32).contiguous()
+        return (pos,) + tuple(r.detach().to(torch.float32).reshape(pos.shape[0], -1).contiguous() for r in rows)
+
     def potential(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor) -> torch.Tensor:
         """``V [N, C]`` for ``charges [N, C]`` (``pet_ewald_potential``)."""
-        rt._require_cuda(positions, charges)
-        pos = positions.detach().to(torch.float32).contiguous()
-        q = charges.detach().to(torch.float32).reshape(pos.shape[0], -1).contiguous()
+        pos, q = self._inputs(positions, charges)
         out = torch.empty_like(q)
         ws = self._ws(q.shape[1], q.device)
         check(self.lib.pet_ewald_potential(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), int(q.shape[1]),
@@ -240,10 +244,7 @@ class EwaldHip:
                  want_cell_grad: bool = False):
         """``(dL/dq [N, C], dL/dR [N, 3])`` and on request ``dL/dcell [S, 3, 3]`` (fixed Cartesian positions) for
         ``dL/dV = grad_potential`` (``pet_ewald_backward``)."""
-        rt._require_cuda(positions, charges, grad_potential)
-        pos = positions.detach().to(torch.float32).contiguous()
-        q = charges.detach().to(torch.float32).reshape(pos.shape[0], -1).contiguous()
-        g = grad_potential.detach().to(torch.float32).reshape(q.shape).contiguous()
+        pos, q, g = self._inputs(positions, charges, grad_potential)
         gq = torch.empty_like(q)
         gpos = torch.empty_like(pos)
         gcell = torch.empty((graph.n_systems, 3, 3), dtype=torch.float32, device=q.device) if want_cell_grad else None
@@ -259,15 +260,13 @@ class P3MHip(EwaldHip):
     ``pet_p3m_spread -> torch.fft.rfftn -> pet_p3m_filter -> torch.fft.irfftn -> pet_p3m_finish`` on the current stream; the
     meshes are channel-first ``[C, N_x, N_y, N_z]`` per periodic system, packed in batch order."""
 
+    _warns_kset = False
+    _workspace_bytes = "pet_p3m_workspace_bytes"
+
     def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5, interpolation_nodes: int = 5):
         self.interpolation_nodes = _check_nodes(interpolation_nodes)
-        self.lib = _lib.load()
-        self.smearing, self.kspace_resolution, self.cutoff = float(smearing), float(kspace_resolution), float(cutoff)
-        self._handle = c_void_p()
-        check(self.lib.pet_ewald_create(self.smearing, self.kspace_resolution, self.cutoff, byref(self._handle)))
+        super().__init__(smearing, kspace_resolution, cutoff)
         check(self.lib.pet_ewald_set_p3m(self._handle, self.interpolation_nodes))
-        self.n_systems = -1
-        self._workspace: Optional[torch.Tensor] = None
         self._meshes: List[tuple] = []  # (shape, first mesh point, first half-spectrum point) per system with a mesh
 
     def plan(self, cells, pbcs: Sequence[Sequence[bool]], first_atom: Sequence[int]) -> "P3MHip":
@@ -297,14 +296,6 @@ class P3MHip(EwaldHip):
         check(self.lib.pet_p3m_mesh_shape(self._handle, int(system), out))
         return [int(x) for x in out]
 
-    def _ws(self, channels: int, device) -> torch.Tensor:
-        nbytes = int(self.lib.pet_p3m_workspace_bytes(self._handle, channels))
-        if nbytes < 0:
-            raise PetHipError("pet_p3m_workspace_bytes failed: call plan() first")
-        if self._workspace is None or self._workspace.numel() < nbytes or self._workspace.device != device:
-            self._workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
-        return self._workspace
-
     def _mesh_potential(self, graph, pos, x, ws, keep_spectrum: bool = False):
         """spread -> rfftn -> filter -> irfftn of ``x [N, C]``: the mesh potential (packed, channel-first) and, on request, the
         unfiltered half spectrum. Leaves the weights and bins of ``pos`` in the workspace."""
@@ -325,11 +316,6 @@ class P3MHip(EwaldHip):
         for n, real, half in views:
             torch.fft.irfftn(half, s=n, dim=(1, 2, 3), norm="forward", out=real)
         return mesh, raw
-
-    def _inputs(self, positions, *rows):
-        rt._require_cuda(positions, *rows)
-        pos = positions.detach().to(torch.float32).contiguous()
-        return (pos,) + tuple(r.detach().to(torch.float32).reshape(pos.shape[0], -1).contiguous() for r in rows)
 
     def _finish(self, graph, pos, x, phi, ws):
         out = torch.empty_like(x)

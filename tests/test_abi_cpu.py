@@ -148,3 +148,15 @@ def test_config_keys_are_the_documented_ones(lib):
     for key in sorted(documented):
         assert lib.pet_config_set(key.encode(), DOCUMENTED_SWITCHES.get(key, 0)) == 0, key
     assert lib.pet_config_set(b"undocumented_probe", 0) == -3
+
+
+def test_no_translation_unit_includes_another():
+    """No file under ``csrc/`` ``#include``s a ``.hip`` file: what two translation units share lives in a header
+    (``csrc/long_range.h`` for ``ewald.hip`` and ``p3m.hip``), which the build's staleness check covers by itself."""
+    csrc = os.path.join(ROOT, "metatrain_amd", "csrc")
+    bad = []
+    for name in sorted(os.listdir(csrc)):
+        for n, line in enumerate(open(os.path.join(csrc, name), errors="replace"), 1):
+            if re.match(r'\s*#\s*include\s*["<][^">]*\.hip[">]', line):
+                bad.append((name, n, line.strip()))
+    assert not bad, bad

@@ -142,3 +142,14 @@ def test_unconverged_kset_warns_once(caplog):
         lr.EwaldHip(1.4, 2.66)
         lr.EwaldHip(1.4, 2.66)
     assert len([r for r in caplog.records if "shape of the k-set" in r.getMessage().lower()]) == 1
+
+
+def test_a_mesh_operator_does_not_warn_about_the_kset(caplog):
+    """``P3MHip`` is built through ``EwaldHip.__init__`` and walks no k-set: it neither warns nor uses up the one warning."""
+    from metatrain_amd import long_range as lr
+
+    lr._warned_kset = False
+    with caplog.at_level("WARNING"):
+        op = lr.P3MHip(1.4, 2.66, 4.5, 3)
+    assert not caplog.records and lr._warned_kset is False
+    assert (op.smearing, op.kspace_resolution, op.cutoff, op.interpolation_nodes, op.n_systems) == (1.4, 2.66, 4.5, 3, -1)

@@ -1,6 +1,5 @@
-// The inference adjoint of the message-passing combination stage (backend.py:559-575; forward: pet_comb_s.hip) in the form of
-// k_emlp_s (rows_s.h): one-accumulator split-operand products, two desynchronised four-wave workgroups per CU, one weight stream per
-// workgroup through a four-slot LDS ring requested three stages ahead. Round 6. k_comb_bwd_p2 (pet_comb_bwd.hip: 440 + 184
+// The inference adjoint of the message-passing combination stage (backend.py:559-575; forward: pet_comb_s.hip) on the row ring
+// (rows_s.h). Round 6. k_comb_bwd_p2 (pet_comb_bwd.hip: 440 + 184
 // registers, one wave per SIMD, 40 KB of LDS per wave, its weights streamed per WAVE from L2) keeps serving small graphs and the
 // training pass (which exports da for the weight gradients).
 //   forward   a = W0g xhat + b0g (xhat = LayerNorm-hat([e ; e[rev]]), the affine part folded into W0g / b0g);  M' = M + e + W2 silu(a) + b2
@@ -26,37 +25,12 @@ constexpr int CBS_SPC = 12, CBS_NC = 2 * D / 32;
 //   s < 4:  W2^T tile hc (hidden units 32 hc ..), K blocks 2 s + (w >> 1) of the 128 message features, plane w & 1
 //   s >= 4: W0g^T output tile s - 4 (columns 32 (s - 4) .. of the 256), K blocks 2 hc + (w >> 1) of the hidden units, plane w & 1
 __device__ __forceinline__ void cbs_request(int hc, int s, const W2& w2b, const W2& w0b, unsigned ring_u, int wave, unsigned lane16) {
-    if (s >= CBS_SPC) { s -= CBS_SPC; hc += 1; }
-    if (hc >= CBS_NC) { hc = CBS_NC - 1; s = CBS_SPC - 1; }  // past the end: the last stage again (keeps vmcnt uniform)
-    const unsigned dst = ring_u + (unsigned)((CBS_SPC * hc + s) & (HS_NSLOT - 1)) * HS_SLOT + wave * 1024;
+    ring_clamp_chunk<CBS_SPC, CBS_NC>(hc, s);
+    const unsigned dst = RING_SLOT_DST(ring_u, wave, CBS_SPC * hc + s);
     const int pl = wave & 1, j = wave >> 1;
     if (s < 4) ab_dma_piece(pl ? w2b.l : w2b.h, hc * (D / 16) + 2 * s + j, lane16, dst);
     else ab_dma_piece(pl ? w0b.l : w0b.h, (s - 4) * (2 * D / 16) + 2 * hc + j, lane16, dst);
 }
-#define CBS_STAGE_SYNC(LEAD)                                                        \
-    do {                                                                            \
-        if (LEAD) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");      \
-        else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");            \
-        __syncthreads();                                                            \
-    } while (0)
-
-// whole rows of a [32 x 128] fp32 block (leading dimension ld) into the wave's tile: trr.h dma_tile128 with one wave-uniform base and
-// 32-bit lane offsets (so_rows_s.hip rs_dma_tile: the 64-bit row addresses of three call sites do not stay live across the loop)
-__device__ __forceinline__ void cbs_dma_rows(const float* __restrict__ X, int64_t r0, int64_t R, int ld, unsigned lds_base,
-                                             const RowLane& L) {
-    const float* base = X + r0 * ld;
-    const int rmax = (int)(R - 1 - r0 < 31 ? R - 1 - r0 : 31);
-    const int hi = L.lane >> 5, c = L.lane & 31;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int r = 2 * j + hi, rr = r < rmax ? r : rmax;
-        const unsigned off = ((unsigned)rr * (unsigned)ld + 4u * (unsigned)(c ^ (r & 15))) * 4u;
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(off), "s"(base), "s"(lds_base + j * 1024) : "memory");
-    }
-}
-
 // a [32 rows x 64 columns] slab of the [E, 256] pre-activations into 8 KB of LDS: instruction j brings rows 4 j .. 4 j + 3 (16 lanes x
 // 16 B per row); row r, 16-B piece c lands at byte 256 r + 16 (c ^ (r & 15))
 __device__ __forceinline__ void cbs_dma_slab(const float* __restrict__ X, int64_t r0, int64_t R, unsigned lds_base, const RowLane& L) {
@@ -87,20 +61,10 @@ __global__ __launch_bounds__(256, 2) void k_comb_bwd_s(const float* __restrict__
                                                       const int* __restrict__ rev, const float* __restrict__ LNS,
                                                       const float* __restrict__ CA, const float* __restrict__ b0g, W2 w2b, W2 w0b,
                                                       float* __restrict__ dcat, int64_t E) {
-    extern __shared__ __attribute__((aligned(16))) char cbs_smem[];
-    const RowLane L;
-    const unsigned lane16 = (unsigned)L.lane * 16u;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int64_t row0 = ((int64_t)blockIdx.x * HS_NW + wave) * WROWS;
-    const bool live = row0 < E;
-    if (!live) row0 = ((E - 1) / WROWS) * WROWS;  // run along on the last tile (same barriers), store nothing
-    char* tile = cbs_smem + wave * 16384;
-    const char* ring = cbs_smem + HS_NW * 16384;
-    const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);
-    const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+    RING_WAVE(E);
     // ---- rows: dM -> planes (the low plane parked in the first half of the consumed tile: every lane reads back what it wrote);
     // then the first slab (chunks 0, 1: 64 columns) of the saved pre-activations into the second half
-    cbs_dma_rows(dM, row0, E, D, tile_u, L);
+    ring_dma_rows(dM, row0, E, D, tile_u, L);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     f16x8 mh[8];
     float inv;
@@ -137,9 +101,9 @@ __global__ __launch_bounds__(256, 2) void k_comb_bwd_s(const float* __restrict__
         f32x16 t1 = ab_zero();
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            CBS_STAGE_SYNC(false);
+            ring_stage_sync();
             cbs_request(hc, s + 3, w2b, w0b, ring_u, wave, lane16p);
-            const char* slot = ring + ((CBS_SPC * hc + s) & (HS_NSLOT - 1)) * HS_SLOT + lane16p;
+            const char* slot = RING_SLOT_PTR(ring, CBS_SPC * hc + s, lane16p);
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const f16x8 wh = *reinterpret_cast<const f16x8*>(slot + (2 * j) * 1024);
@@ -176,15 +140,9 @@ __global__ __launch_bounds__(256, 2) void k_comb_bwd_s(const float* __restrict__
         ab_tile_planes(t1, uh, ul);
 #pragma unroll
         for (int s = 4; s < 12; s++) {
-            CBS_STAGE_SYNC(refill && s < 7);  // (the fragments of stages 4 .. 6 were requested before the refill)
+            ring_stage_sync<8>(refill && s < 7);  // (the fragments of stages 4 .. 6 were requested before the refill's 8 requests)
             cbs_request(hc, s + 3, w2b, w0b, ring_u, wave, lane16p);
-            const char* slot = ring + ((CBS_SPC * hc + s) & (HS_NSLOT - 1)) * HS_SLOT + lane16p;
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const f16x8 wh = *reinterpret_cast<const f16x8*>(slot + (2 * j) * 1024);
-                const f16x8 wl = *reinterpret_cast<const f16x8*>(slot + (2 * j + 1) * 1024);
-                AB_MFMA3(dl[s - 4], wh, wl, uh[j], ul[j]);
-            }
+            ring_stage_mfma(RING_SLOT_PTR(ring, CBS_SPC * hc + s, lane16p), dl[s - 4], uh[0], ul[0], dl[s - 4], uh[1], ul[1]);
         }
     }
     // ---- the LayerNorm adjoint. dl = 64 dxhat (row-scaled); the two sums, then one 128-column half of the result at a time
@@ -218,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void k_comb_bwd_s(const float* __restrict__
         CBS_ROW0(re);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
-        if (half == 0) cbs_dma_rows(XF, re, E, D, tile_u, Le);
+        if (half == 0) ring_dma_rows(XF, re, E, D, tile_u, Le);
         else {
 #pragma unroll
             for (int j = 0; j < 16; j++) {  // the e[rev] rows (pet_comb_s.hip)
@@ -251,28 +209,13 @@ __global__ __launch_bounds__(256, 2) void k_comb_bwd_s(const float* __restrict__
     }
 }
 
-static inline W2 cbs_w2(const void* base, int n_tiles_dim, int k_dim) {
-    const size_t n8 = (size_t)(n_tiles_dim / 32) * (k_dim / 16) * 64;
-    const f16x8* b = reinterpret_cast<const f16x8*>(base);
-    W2 w; w.h = b; w.l = b + n8;
-    return w;
-}
-
 // c0g = comb0 with the LayerNorm folded in
 int comb_bwd_s(const float* dM, const float* XF, const int* rev, const float* LNS, const float* CA, const Lin& c0g, const Lin& c2,
                float* dcat, int64_t E, bool add_dm, hipStream_t st) {
     PET_REQUIRE_PLANES(c0g.bwd2s && c2.bwd2s && c0g.b, "combination adjoint");
-    const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
-    // bwd2s operands: tiles over k_in, K = n_out
-    const W2 w2b = cbs_w2(c2.bwd2s, c2.k_in, c2.n_out), w0b = cbs_w2(c0g.bwd2s, c0g.k_in, c0g.n_out);
-    const int grid = (int)cdiv(E, HS_NW * WROWS);
-    if (add_dm) {
-        allow_big_lds(k_comb_bwd_s<true>, lds);
-        k_comb_bwd_s<true><<<grid, 256, lds, st>>>(dM, XF, rev, LNS, CA, c0g.b, w2b, w0b, dcat, E);
-    } else {
-        allow_big_lds(k_comb_bwd_s<false>, lds);
-        k_comb_bwd_s<false><<<grid, 256, lds, st>>>(dM, XF, rev, LNS, CA, c0g.b, w2b, w0b, dcat, E);
-    }
+    const W2 w2b = lin_planes(c2.bwd2s, c2), w0b = lin_planes(c0g.bwd2s, c0g);  // (bwd2s: tiles over k_in, K = n_out)
+    if (add_dm) launch_ring(k_comb_bwd_s<true>, E, st, dM, XF, rev, LNS, CA, c0g.b, w2b, w0b, dcat, E);
+    else launch_ring(k_comb_bwd_s<false>, E, st, dM, XF, rev, LNS, CA, c0g.b, w2b, w0b, dcat, E);
     return PET_OK;
 }
 

@@ -1,6 +1,5 @@
 // The message-passing combination stage (backend.py:559-575: M' = M + e + W2 silu(W0 LayerNorm([e ; e[rev]]) + b0) + b2), forward,
-// in the form of k_emlp_s (pet_emlp_s.hip, rows_s.h): one-accumulator split-operand products, two desynchronised four-wave
-// workgroups per CU, one weight stream per workgroup through a four-slot LDS ring requested three stages ahead. Round 5, second
+// on the row ring (rows_s.h). Round 5, second
 // attempt: the first one (tools/experiments/pet_comb_s.hip, 1.61 against k_comb_p2's 1.67 ms) loaded the LayerNorm's weight and
 // bias behind its first ring requests, gathered M and e[rev] as 32-byte pieces and stored the pre-activations as 32-byte pieces.
 // Here the LayerNorm's affine part is folded into W0 (Model comb0_g: W0 diag(gamma), b0 + W0 beta; abi.hip fold_norm_s), the rows
@@ -23,42 +22,21 @@ constexpr int CB_SPC = 12, CB_NC = 2 * D / 32;
 //   s < 8:  W0g tile hc, K blocks 2 s + j (j = w >> 1), plane w & 1
 //   s >= 8: W2 K block 2 hc + (s - 8) / 2, output tiles 2 th + (w >> 1) (th = (s - 8) % 2), plane w & 1
 __device__ __forceinline__ void cb_request(int hc, int s, const W2& w0, const W2& w2, unsigned ring_u, int wave, unsigned lane16) {
-    if (s >= CB_SPC) { s -= CB_SPC; hc += 1; }
-    if (hc >= CB_NC) { hc = CB_NC - 1; s = CB_SPC - 1; }  // past the end: the last stage again (identical bytes; keeps vmcnt uniform)
-    const unsigned dst = ring_u + (unsigned)((CB_SPC * hc + s) & (HS_NSLOT - 1)) * HS_SLOT + wave * 1024;
+    ring_clamp_chunk<CB_SPC, CB_NC>(hc, s);
+    const unsigned dst = RING_SLOT_DST(ring_u, wave, CB_SPC * hc + s);
     const int pl = wave & 1, j = wave >> 1;
     if (s < 8) ab_dma_piece(pl ? w0.l : w0.h, hc * (2 * D / 16) + 2 * s + j, lane16, dst);
     else ab_dma_piece(pl ? w2.l : w2.h, (2 * ((s - 8) & 1) + j) * (2 * D / 16) + 2 * hc + ((s - 8) >> 1), lane16, dst);
 }
 // (vmcnt retires in order, stores included: the chunk's four pre-activation store instructions are issued between the requests of
-// stages 12 hc + 10 and + 11, so the count is 2 + 4 for the stages 12 hc + 8 .. + 10; a partial tile skips store instructions)
-#define CB_STAGE_SYNC(AFTER_STORES)                                                          \
-    do {                                                                                     \
-        if ((AFTER_STORES) && !full) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");        \
-        else if (AFTER_STORES) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");              \
-        else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");                                \
-        __syncthreads();                                                                     \
-    } while (0)
-
+// stages 12 hc + 10 and + 11, so the count is 2 + 4 for the stages 12 hc + 8 .. + 10; a partial tile skips store instructions: drained)
 template <bool FIRST>
 __global__ __launch_bounds__(256, 2) void k_comb_s(const float* __restrict__ XF, const int* __restrict__ rev, W2 w0,
                                                   const float* __restrict__ b0, W2 w2, const float* __restrict__ b2,
                                                   const float* __restrict__ Min, const float* __restrict__ edge_emb,
                                                   const int* __restrict__ sp_nbr, float* __restrict__ CA,
                                                   float* __restrict__ LNS, float* __restrict__ Mout, int64_t E) {
-    extern __shared__ __attribute__((aligned(16))) char cb_smem[];
-    const RowLane L;
-    const unsigned lane16 = (unsigned)L.lane * 16u;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int64_t row0 = ((int64_t)blockIdx.x * HS_NW + wave) * WROWS;
-    const bool live = row0 < E;
-    if (!live) row0 = ((E - 1) / WROWS) * WROWS;
-    const int64_t row = row0 + L.r < E ? row0 + L.r : E - 1;
-    const bool valid = live && row0 + L.r < E;
-    char* tile = cb_smem + wave * 16384;
-    const char* ring = cb_smem + HS_NW * 16384;
-    const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);
-    const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+    RING_WAVE(E);
     // ---- the three row sets, all consumed before the ring starts
     dma_tile128(XF, row0, E, tile_u, L);
     int rv;
@@ -132,15 +110,7 @@ __global__ __launch_bounds__(256, 2) void k_comb_s(const float* __restrict__ XF,
     cb_request(0, 1, w0, w2, ring_u, wave, lane16);
     cb_request(0, 2, w0, w2, ring_u, wave, lane16);
     f16x8 xh[16], xl[16];  // planes of 64 xhat (the LayerNorm's weight and bias are in W0g / b0g)
-    {
-        const float f = rstd * ABS;
-#pragma unroll
-        for (int kb = 0; kb < 16; kb++) {
-            const float v8[8] = {x[2 * kb].x * f, x[2 * kb].y * f, x[2 * kb].z * f, x[2 * kb].w * f,
-                                 x[2 * kb + 1].x * f, x[2 * kb + 1].y * f, x[2 * kb + 1].z * f, x[2 * kb + 1].w * f};
-            ab_split8(v8, xh[kb], xl[kb]);
-        }
-    }
+    hs_planes(x, xh, xl, rstd * ABS);
     f32x16 out[4];
 #pragma unroll
     for (int t = 0; t < 4; t++)
@@ -164,15 +134,9 @@ __global__ __launch_bounds__(256, 2) void k_comb_s(const float* __restrict__ XF,
             for (int i = 0; i < 4; i++) aa[4 * j + i] = hs_vec_s(b0 + 32 * hc, 0, j, i, L.h) * ABQ;
 #pragma unroll
         for (int s = 0; s < 8; s++) {
-            CB_STAGE_SYNC(false);
+            ring_stage_sync();
             cb_request(hc, s + 3, w0, w2, ring_u, wave, lane16);
-            const char* slot = ring + ((CB_SPC * hc + s) & (HS_NSLOT - 1)) * HS_SLOT + lane16;
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const f16x8 wh = *reinterpret_cast<const f16x8*>(slot + (2 * j) * 1024);
-                const f16x8 wl = *reinterpret_cast<const f16x8*>(slot + (2 * j + 1) * 1024);
-                AB_MFMA3(aa, wh, wl, xh[2 * s + j], xl[2 * s + j]);
-            }
+            ring_stage_mfma(RING_SLOT_PTR(ring, CB_SPC * hc + s, lane16), aa, xh[2 * s], xl[2 * s], aa, xh[2 * s + 1], xl[2 * s + 1]);
         }
         f32x16 u;
 #pragma unroll
@@ -190,51 +154,27 @@ __global__ __launch_bounds__(256, 2) void k_comb_s(const float* __restrict__ XF,
         ab_tile_planes(u, uh, ul);
 #pragma unroll
         for (int s = 8; s < 12; s++) {
-            CB_STAGE_SYNC(s < 11 && stores);  // (the fragments of stages 8 .. 10 were requested before the stores)
+            ring_stage_sync<4>(s < 11 && stores, !full);  // (the fragments of stages 8 .. 10 were requested before the stores)
             cb_request(hc, s + 3, w0, w2, ring_u, wave, lane16);
-            const char* slot = ring + ((CB_SPC * hc + s) & (HS_NSLOT - 1)) * HS_SLOT + lane16;
             const int kb2 = (s - 8) >> 1, th = (s - 8) & 1;
-#pragma unroll
-            for (int t = 0; t < 2; t++) {
-                const f16x8 wh = *reinterpret_cast<const f16x8*>(slot + (2 * t) * 1024);
-                const f16x8 wl = *reinterpret_cast<const f16x8*>(slot + (2 * t + 1) * 1024);
-                AB_MFMA3(out[2 * th + t], wh, wl, uh[kb2], ul[kb2]);
-            }
+            ring_stage_mfma(RING_SLOT_PTR(ring, CB_SPC * hc + s, lane16), out[2 * th], uh[kb2], ul[kb2], out[2 * th + 1], uh[kb2], ul[kb2]);
         }
     }
     // ---- M' = out / 64: whole lines through the wave's own tile
     float4 y[16];
-#pragma unroll
-    for (int t = 0; t < 4; t++)
-#pragma unroll
-        for (int j = 0; j < 4; j++)
-            y[4 * t + j] = make_float4(out[t][4 * j] * ABS_INV, out[t][4 * j + 1] * ABS_INV, out[t][4 * j + 2] * ABS_INV, out[t][4 * j + 3] * ABS_INV);
+    hs_acc_rows<4>(y, out, ABS_INV);
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
     store_rows_lines<16>(y, reinterpret_cast<float*>(tile), L, [&](int r) { return live && row0 + r < E ? Mout + (row0 + r) * D : nullptr; });
-}
-
-static inline W2 cb_w2(const void* base, int n_out, int k_in) {
-    const size_t n8 = (size_t)(n_out / 32) * (k_in / 16) * 64;
-    const f16x8* b = reinterpret_cast<const f16x8*>(base);
-    W2 w; w.h = b; w.l = b + n8;
-    return w;
 }
 
 // c0g = comb0 with the LayerNorm folded in
 int comb_s(bool first, const float* XF, const int* rev, const Lin& c0g, const Lin& c2, const float* Min, const float* edge_emb,
            const int* sp_nbr, float* CA, float* LNS, float* Mout, int64_t E, hipStream_t st) {
     PET_REQUIRE_PLANES(c0g.fwd2s && c2.fwd2s, "combination stage");
-    const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
-    const W2 w0 = cb_w2(c0g.fwd2s, c0g.n_out, c0g.k_in), w2 = cb_w2(c2.fwd2s, c2.n_out, c2.k_in);
-    const int grid = (int)cdiv(E, HS_NW * WROWS);
-    if (first) {
-        allow_big_lds(k_comb_s<true>, lds);
-        k_comb_s<true><<<grid, 256, lds, st>>>(XF, rev, w0, c0g.b, w2, c2.b, nullptr, edge_emb, sp_nbr, CA, LNS, Mout, E);
-    } else {
-        allow_big_lds(k_comb_s<false>, lds);
-        k_comb_s<false><<<grid, 256, lds, st>>>(XF, rev, w0, c0g.b, w2, c2.b, Min, edge_emb, sp_nbr, CA, LNS, Mout, E);
-    }
+    const W2 w0 = lin_planes(c0g.fwd2s, c0g), w2 = lin_planes(c2.fwd2s, c2);
+    if (first) launch_ring(k_comb_s<true>, E, st, XF, rev, w0, c0g.b, w2, c2.b, nullptr, edge_emb, sp_nbr, CA, LNS, Mout, E);
+    else launch_ring(k_comb_s<false>, E, st, XF, rev, w0, c0g.b, w2, c2.b, Min, edge_emb, sp_nbr, CA, LNS, Mout, E);
     return PET_OK;
 }
 

@@ -1,4 +1,4 @@
-// The inference adjoint of the compress stage (transformer.py:499-521) in the form of k_emlp_s / k_head_s (rows_s.h): round 5.
+// The inference adjoint of the compress stage (transformer.py:499-521) on the row ring (rows_s.h): round 5.
 //   forward (k_compress_h, pet_trr.hip):  a0 = [v, d] Wc^T + Tbl[species] (+ M W0c^T);  e = SiLU(a0) W2^T + b2
 //   adjoint:  da0 = (dE W2) . silu'(a0);  dgeo += da0 Wc;  dM += da0 W0c
 // Same arithmetic as k_compress_bwd_h (pet_trr.hip), which keeps serving small graphs and the training passes; that kernel
@@ -27,23 +27,11 @@ template <bool FIRST>
 __global__ __launch_bounds__(256, 2) void k_compress_bwd_s(const float* __restrict__ dXe, const float* __restrict__ a0, W2 w2b,
                                                           W2 wcp /* Wc^T padded to [32][D], planes of 64 w */, W2 w0cb,
                                                           float* __restrict__ dgeo, float* __restrict__ dM, int64_t E) {
-    extern __shared__ __attribute__((aligned(16))) char cs_smem[];
-    const RowLane L;
-    const unsigned lane16 = (unsigned)L.lane * 16u;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int64_t row0 = ((int64_t)blockIdx.x * HS_NW + wave) * WROWS;
-    const bool live = row0 < E;
-    if (!live) row0 = ((E - 1) / WROWS) * WROWS;
-    const int64_t row = row0 + L.r < E ? row0 + L.r : E - 1;
-    const bool valid = live && row0 + L.r < E;
-    char* tile = cs_smem + wave * 16384;
-    const char* ring = cs_smem + HS_NW * 16384;
-    const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);
-    const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+    RING_WAVE(E);
     constexpr int NST = FIRST ? 20 : 36;
     auto req = [&](int g) {
-        g = g < NST ? g : NST - 1;
-        const unsigned dst = ring_u + (unsigned)(g & (HS_NSLOT - 1)) * HS_SLOT + wave * 1024;
+        g = ring_clamp(g, NST);
+        const unsigned dst = RING_SLOT_DST(ring_u, wave, g);
         if (g < 16) cs_piece(w2b, g, dst, wave, lane16);
         else if (g < 20) ab_dma_piece((wave & 1) ? wcp.l : wcp.h, 2 * (g - 16) + (wave >> 1), lane16, dst);  // K blocks 2 r, 2 r + 1
         else cs_piece(w0cb, g - 20, dst, wave, lane16);
@@ -89,15 +77,9 @@ __global__ __launch_bounds__(256, 2) void k_compress_bwd_s(const float* __restri
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int g = 16 + r;
-        HS_STAGE_SYNC();
+        ring_stage_sync();
         req(g + 3);
-        const char* slot = ring + (g & (HS_NSLOT - 1)) * HS_SLOT + lane16;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const f16x8 wh = *reinterpret_cast<const f16x8*>(slot + (2 * j) * 1024);
-            const f16x8 wl = *reinterpret_cast<const f16x8*>(slot + (2 * j + 1) * 1024);
-            AB_MFMA3(gt, wh, wl, xh[2 * r + j], xl[2 * r + j]);
-        }
+        ring_stage_mfma(RING_SLOT_PTR(ring, g, lane16), gt, xh[2 * r], xl[2 * r], gt, xh[2 * r + 1], xl[2 * r + 1]);
     }
     if (!FIRST) {
 #pragma unroll
@@ -115,11 +97,7 @@ __global__ __launch_bounds__(256, 2) void k_compress_bwd_s(const float* __restri
         auto rows = [&](int r) { return dM + (row0 + r < E ? row0 + r : E - 1) * D; };
         float4 old[16], y[16];
         request_rows_addend<16>(old, L, rows);
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                y[4 * t + j] = make_float4(acc[t][4 * j] * f, acc[t][4 * j + 1] * f, acc[t][4 * j + 2] * f, acc[t][4 * j + 3] * f);
+        hs_acc_rows<4>(y, acc, f);
         __builtin_amdgcn_wave_barrier();
         asm volatile("" ::: "memory");
         store_rows_lines_add<16>(y, old, reinterpret_cast<float*>(tile), L,
@@ -127,25 +105,12 @@ __global__ __launch_bounds__(256, 2) void k_compress_bwd_s(const float* __restri
     }
 }
 
-static inline W2 cs_w2(const void* base, int tiles, int kbs) {
-    const f16x8* b = reinterpret_cast<const f16x8*>(base);
-    W2 w; w.h = b; w.l = b + (size_t)tiles * kbs * 64;
-    return w;
-}
-
 int compress_bwd_s(bool first, const float* dXe, const float* a0, const GnnLayerW& G, float* dgeo, float* dM, int64_t E,
                    hipStream_t st) {
     PET_REQUIRE_PLANES(G.compress2.bwd2s && G.wc2s && (first || G.compress0_msg.bwd2s), "compress adjoint");
-    const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
-    const int grid = (int)cdiv(E, HS_NW * WROWS);
-    const W2 w2b = cs_w2(G.compress2.bwd2s, D / 32, D / 16), wcp = cs_w2(G.wc2s, 1, D / 16);
-    if (first) {
-        allow_big_lds(k_compress_bwd_s<true>, lds);
-        k_compress_bwd_s<true><<<grid, 256, lds, st>>>(dXe, a0, w2b, wcp, W2(), dgeo, nullptr, E);
-    } else {
-        allow_big_lds(k_compress_bwd_s<false>, lds);
-        k_compress_bwd_s<false><<<grid, 256, lds, st>>>(dXe, a0, w2b, wcp, cs_w2(G.compress0_msg.bwd2s, D / 32, D / 16), dgeo, dM, E);
-    }
+    const W2 w2b = w2_planes(G.compress2.bwd2s, D / 32, D / 16), wcp = w2_planes(G.wc2s, 1, D / 16);
+    if (first) launch_ring(k_compress_bwd_s<true>, E, st, dXe, a0, w2b, wcp, W2(), dgeo, nullptr, E);
+    else launch_ring(k_compress_bwd_s<false>, E, st, dXe, a0, w2b, wcp, w2_planes(G.compress0_msg.bwd2s, D / 32, D / 16), dgeo, dM, E);
     return PET_OK;
 }
 

@@ -9,9 +9,9 @@
 // step with each other (an eight-wave workgroup was tried first: its waves meet at every stage barrier, so the two waves of a
 // SIMD were in their matrix phase or in their vector phase at the same time -- SQ_VALU_MFMA_COEXEC_CYCLES 875 per wave against
 // 5 600 in k_emlp_p2 -- and it ran no faster than k_emlp_p2). The four waves of a workgroup share ONE stream of weight fragments
-// through a four-slot LDS ring (each weight byte is fetched once per four row tiles instead of once per tile), requested
-// three stages ahead (an LDS-DMA request takes ~1 us to land; a stage is 6 MFMAs per wave); the forward reads its fragments one
-// stage ahead of the stage that uses them and requests four ahead (ablk.h ring_turn).
+// through the row ring (rows_s.h; DESIGN 4.4: each weight byte is fetched once per four row tiles instead of once per tile; an
+// LDS-DMA request takes ~1 us to land, a stage is 6 MFMAs per wave); the forward reads its fragments one stage ahead of the stage
+// that uses them and requests four ahead (ablk.h ring_turn).
 //
 //   rows      32 per wave, LDS-DMA; residual + output bias = initial value of the out accumulators; RMSNorm / LayerNorm;
 //             planes of 64 xn parked over the rows
@@ -20,13 +20,10 @@
 //             out += W_out[:, chunk] u (2 stages of one K block x 4 tiles: 24 MFMAs)
 //   stores    whole lines through the wave's (dead) plane tile, as in k_ablk_fwd
 // Scales: W planes 64 x, xn planes 64 x -> [v; g] accumulators hold 4096 x; u planes 1 x -> out accumulators hold 64 x.
-#include "ablk.h"
+#include "rows_s.h"
 
 namespace pet {
 
-constexpr int ES_NW = 4;       // waves per workgroup
-constexpr int ES_SLOT = 4096;  // ring slot: 4 fragments, one per wave
-constexpr int ES_NSLOT = 4;
 constexpr int ES_SPC = 12;     // stages per hidden chunk: 8 of W_in, 4 of W_out
 constexpr int ES_NSTAGE = ES_SPC * (DFF / 32);
 
@@ -35,12 +32,11 @@ constexpr int ES_NSTAGE = ES_SPC * (DFF / 32);
 //   s >= 8: W_out K block 2 hc + (s - 8) / 2 of output tiles 2 th, 2 th + 1 (th = (s - 8) % 2): fragments 2 t + plane
 __device__ __forceinline__ void es_request(int hc, int s, const W2& win, const W2& wout, unsigned ring_u, int wave,
                                            unsigned lane16) {  // s may run past the chunk (s < 2 ES_SPC): the next chunk's stage
-    if (s >= ES_SPC) { s -= ES_SPC; hc += 1; }
-    if (hc >= DFF / 32) { hc = DFF / 32 - 1; s = ES_SPC - 1; }  // past the end: the last stage again (identical bytes; keeps vmcnt uniform)
+    ring_clamp_chunk<ES_SPC, DFF / 32>(hc, s);
 #ifdef AB_ABL_NODMA
     if (hc > 0 || s > 2) return;
 #endif
-    const unsigned dst = ring_u + (unsigned)((ES_SPC * hc + s) & (ES_NSLOT - 1)) * ES_SLOT + wave * 1024;
+    const unsigned dst = RING_SLOT_DST(ring_u, wave, ES_SPC * hc + s);
     if (s < 8) {
         const int tile = (wave >> 1) * (DFF / 32) + hc;
         ab_dma_piece((wave & 1) ? win.l : win.h, tile * (D / 16) + s, lane16, dst);
@@ -49,25 +45,13 @@ __device__ __forceinline__ void es_request(int hc, int s, const W2& win, const W
         ab_dma_piece((wave & 1) ? wout.l : wout.h, t * (DFF / 16) + 2 * hc + kb2, lane16, dst);
     }
 }
-// ES_STAGE_SYNC: this wave's fragment of the stage it waits for has landed (everything but its fragments of the two stages
-// requested after it) and its own fragment reads have returned, then the workgroup barrier. k_emlp_bwd_s reads a stage behind
-// the stage's own sync (requests three ahead: the stage waited for is the one about to be consumed); k_emlp_s reads one stage
-// ahead (ablk.h ring_turn, requests four ahead: the stage waited for is the NEXT one) -- the counts are the same.
-#ifdef AB_ABL_NOBAR
-#define ES_BARRIER()
-#else
-#define ES_BARRIER() __syncthreads()
-#endif
-// (vmcnt retires in order, stores included: behind the chunk's eight [v; g] store instructions -- issued between the requests of stages 12 hc + 11 and 12 hc + 12 -- the
-// count is 2 + 8 for the three stages whose fragments were requested before them and are waited for after them: 12 hc + 9 .. + 11,
-// at the syncs of stages 12 hc + 8 .. + 10)
-#define ES_STAGE_SYNC(AFTER_STORES)                                           \
-    do {                                                                      \
-        if ((AFTER_STORES) && !full) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");   /* a partial tile skips store instructions */ \
-        else if (AFTER_STORES) asm volatile("s_waitcnt vmcnt(10) lgkmcnt(0)" ::: "memory");        \
-        else asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");                 \
-        ES_BARRIER();                                                         \
-    } while (0)
+// The stage syncs (rows_s.h ring_stage_sync): k_emlp_bwd_s reads a stage behind the stage's own sync (requests three ahead: the
+// stage waited for is the one about to be consumed) and has no stores between its stages: every sync is the plain one; k_emlp_s
+// reads one stage ahead (ablk.h ring_turn, requests four ahead: the stage waited for is the NEXT one) -- the counts are the same.
+// k_emlp_s behind its stores: vmcnt retires in order, stores included: behind the chunk's eight [v; g] store instructions -- issued
+// between the requests of stages 12 hc + 11 and 12 hc + 12 -- the count is 2 + 8 for the three stages whose fragments were requested
+// before them and are waited for after them: 12 hc + 9 .. + 11, at the syncs of stages 12 hc + 8 .. + 10 (a partial tile skips
+// store instructions: drained instead)
 // accumulator tile initialised with 4096 x bias through the SCALAR cache (ablk.h ab_bias_tile_s): a vector load here would sit in
 // the in-order vmcnt queue behind the ring requests
 __device__ __forceinline__ void es_bias_tile(f32x16& acc, const float* __restrict__ b, int h) { ab_bias_tile_s(acc, b, h); }
@@ -77,17 +61,7 @@ __global__ __launch_bounds__(256, 2) void k_emlp_s(const float* __restrict__ X1,
                                                 const float* __restrict__ beta, W2 win, const float* __restrict__ bin, W2 wout,
                                                 const float* __restrict__ bout, float* __restrict__ VG, float* __restrict__ X2,
                                                 int64_t E) {
-    extern __shared__ __attribute__((aligned(16))) char es_smem[];
-    const RowLane L;
-    const unsigned lane16 = (unsigned)L.lane * 16u;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int64_t row0 = ((int64_t)blockIdx.x * ES_NW + wave) * WROWS;
-    const bool live = row0 < E;
-    if (!live) row0 = ((E - 1) / WROWS) * WROWS;  // run along on the last tile (same barriers), store nothing
-    char* tile = es_smem + wave * 16384;
-    const char* ring = es_smem + ES_NW * 16384;
-    const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);
-    const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+    RING_WAVE(E);
     dma_tile128(X1, row0, E, tile_u, L);
     es_request(0, 0, win, wout, ring_u, wave, lane16);
     es_request(0, 1, win, wout, ring_u, wave, lane16);
@@ -108,13 +82,9 @@ __global__ __launch_bounds__(256, 2) void k_emlp_s(const float* __restrict__ X1,
                 out[t][4 * j + 2] = (x[4 * t + j].z + b4.z) * ABS; out[t][4 * j + 3] = (x[4 * t + j].w + b4.w) * ABS;
             }
         norm_frag<16, LN>(x, gamma, beta, L.h);
-#pragma unroll
-        for (int kb = 0; kb < 8; kb++) {  // planes of 64 xn, kept in REGISTERS: every hidden chunk reads all of them (an eighth
-            // of the kernel's LDS reads), and the row tile becomes the staging tile of the whole-line [v; g] stores
-            const float v8[8] = {x[2 * kb].x * ABS, x[2 * kb].y * ABS, x[2 * kb].z * ABS, x[2 * kb].w * ABS,
-                                 x[2 * kb + 1].x * ABS, x[2 * kb + 1].y * ABS, x[2 * kb + 1].z * ABS, x[2 * kb + 1].w * ABS};
-            ab_split8(v8, xph[kb], xpl[kb]);
-        }
+        // planes of 64 xn, kept in REGISTERS: every hidden chunk reads all of them (an eighth of the kernel's LDS reads), and the
+        // row tile becomes the staging tile of the whole-line [v; g] stores
+        hs_planes(x, xph, xpl);
     }
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
@@ -132,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void k_emlp_s(const float* __restrict__ X1,
         es_bias_tile(ga, bin + DFF + 32 * hc, L.h);
 #pragma unroll
         for (int s = 0; s < 8; s++) {
-            ES_STAGE_SYNC(false);
+            ring_stage_sync();
             ring_turn(w, wn, s, true, req, ring, lane16);  // (12 hc is a multiple of the slot count)
             AB_MFMA3(va, w.f[0], w.f[1], xph[s], xpl[s]);
             AB_MFMA3(ga, w.f[2], w.f[3], xph[s], xpl[s]);
@@ -158,7 +128,7 @@ __global__ __launch_bounds__(256, 2) void k_emlp_s(const float* __restrict__ X1,
         ab_tile_planes(u, uh, ul);
 #pragma unroll
         for (int s = 8; s < 12; s++) {
-            ES_STAGE_SYNC(s < 11 && stores);  // (the fragments of stages 9 .. 11 were requested before the stores)
+            ring_stage_sync<8>(s < 11 && stores, !full);  // (the fragments of stages 9 .. 11 were requested before the stores)
             ring_turn(w, wn, s, true, req, ring, lane16);  // (behind the stream's last stage: a landed older stage, unused)
             const int kb2 = (s - 8) >> 1, th = (s - 8) & 1;
 #pragma unroll
@@ -209,12 +179,11 @@ __global__ __launch_bounds__(256, 2) void k_emlp_s(const float* __restrict__ X1,
 constexpr int EB_SPC = 20;
 __device__ __forceinline__ void eb_request(int hc, int s, const W2& win, const W2& woutT, const W2& winT, unsigned ring_u, int wave,
                                            unsigned lane16) {
-    if (s >= EB_SPC) { s -= EB_SPC; hc += 1; }
-    if (hc >= DFF / 32) { hc = DFF / 32 - 1; s = EB_SPC - 1; }
+    ring_clamp_chunk<EB_SPC, DFF / 32>(hc, s);
 #ifdef AB_ABL_NODMA
     if (hc > 0 || s > 2) return;
 #endif
-    const unsigned dst = ring_u + (unsigned)((EB_SPC * hc + s) & (ES_NSLOT - 1)) * ES_SLOT + wave * 1024;
+    const unsigned dst = RING_SLOT_DST(ring_u, wave, EB_SPC * hc + s);
     const int pl = wave & 1, j = wave >> 1;
     if (s < 8) {
         ab_dma_piece(pl ? win.l : win.h, (j * (DFF / 32) + hc) * (D / 16) + s, lane16, dst);
@@ -232,19 +201,7 @@ __global__ __launch_bounds__(256, 2) void k_emlp_bwd_s(const float* __restrict__
                                                        const float* __restrict__ bin, W2 woutT, W2 winT,
                                                        float* __restrict__ dX1, int64_t E, int ldy,
                                                        const float* __restrict__ dY2, const int* __restrict__ rev2) {
-    extern __shared__ __attribute__((aligned(16))) char es_smem[];
-    const RowLane L;
-    const unsigned lane16 = (unsigned)L.lane * 16u;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int64_t row0 = ((int64_t)blockIdx.x * ES_NW + wave) * WROWS;
-    const bool live = row0 < E;
-    if (!live) row0 = ((E - 1) / WROWS) * WROWS;
-    const int64_t row = row0 + L.r < E ? row0 + L.r : E - 1;
-    constexpr bool full = true;  // (ES_STAGE_SYNC: this kernel has no stores between its stages)
-    char* tile = es_smem + wave * 16384;
-    const char* ring = es_smem + ES_NW * 16384;
-    const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);
-    const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+    RING_WAVE(E);
     // the layer input by LDS-DMA, the adjoint rows as row fragments straight into registers, the first ring stages
     dma_tile128(X1, row0, E, tile_u, L);
     float4 dy[16];
@@ -279,13 +236,7 @@ __global__ __launch_bounds__(256, 2) void k_emlp_bwd_s(const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 16; k++) ss += x[k].x * x[k].x + x[k].y * x[k].y + x[k].z * x[k].z + x[k].w * x[k].w;
         rstd = rsqrtf(row_sum(ss) * (1.0f / 128.0f) + (LN ? 1e-5f : 1.1920928955078125e-07f));
-        const float f = rstd * ABS;
-#pragma unroll
-        for (int kb = 0; kb < 8; kb++) {
-            const float v8[8] = {x[2 * kb].x * f, x[2 * kb].y * f, x[2 * kb].z * f, x[2 * kb].w * f,
-                                 x[2 * kb + 1].x * f, x[2 * kb + 1].y * f, x[2 * kb + 1].z * f, x[2 * kb + 1].w * f};
-            ab_split8(v8, xph[kb], xpl[kb]);
-        }
+        hs_planes(x, xph, xpl, rstd * ABS);
     }
     float inv;
     {
@@ -308,9 +259,9 @@ __global__ __launch_bounds__(256, 2) void k_emlp_bwd_s(const float* __restrict__
         es_bias_tile(ga, bin + DFF + 32 * hc, L.h);
 #pragma unroll
         for (int s = 0; s < 8; s++) {
-            ES_STAGE_SYNC(false);
+            ring_stage_sync();
             eb_request(hc, s + 3, win, woutT, winT, ring_u, wave, lane16);
-            const char* slot = ring + ((EB_SPC * hc + s) & (ES_NSLOT - 1)) * ES_SLOT + lane16;
+            const char* slot = RING_SLOT_PTR(ring, EB_SPC * hc + s, lane16);
             const f16x8 wvh = *reinterpret_cast<const f16x8*>(slot + 0 * 1024);
             const f16x8 wvl = *reinterpret_cast<const f16x8*>(slot + 1 * 1024);
             const f16x8 wgh = *reinterpret_cast<const f16x8*>(slot + 2 * 1024);
@@ -321,9 +272,9 @@ __global__ __launch_bounds__(256, 2) void k_emlp_bwd_s(const float* __restrict__
         f32x16 du = ab_zero();
 #pragma unroll
         for (int s = 8; s < 12; s++) {
-            ES_STAGE_SYNC(false);
+            ring_stage_sync();
             eb_request(hc, s + 3, win, woutT, winT, ring_u, wave, lane16);
-            const char* slot = ring + ((EB_SPC * hc + s) & (ES_NSLOT - 1)) * ES_SLOT + lane16;
+            const char* slot = RING_SLOT_PTR(ring, EB_SPC * hc + s, lane16);
 #pragma unroll
             for (int j = 0; j < 2; j++) {
                 const int kb = 2 * (s - 8) + j;
@@ -352,16 +303,10 @@ __global__ __launch_bounds__(256, 2) void k_emlp_bwd_s(const float* __restrict__
         }
 #pragma unroll
         for (int s = 12; s < 20; s++) {
-            ES_STAGE_SYNC(false);
+            ring_stage_sync();
             eb_request(hc, s + 3, win, woutT, winT, ring_u, wave, lane16);
-            const char* slot = ring + ((EB_SPC * hc + s) & (ES_NSLOT - 1)) * ES_SLOT + lane16;
             const int kk = (s - 12) >> 1, th = (s - 12) & 1;
-#pragma unroll
-            for (int t = 0; t < 2; t++) {
-                const f16x8 wh = *reinterpret_cast<const f16x8*>(slot + (2 * t) * 1024);
-                const f16x8 wl = *reinterpret_cast<const f16x8*>(slot + (2 * t + 1) * 1024);
-                AB_MFMA3(dn[2 * th + t], wh, wl, dh[kk], dl[kk]);
-            }
+            ring_stage_mfma(RING_SLOT_PTR(ring, EB_SPC * hc + s, lane16), dn[2 * th], dh[kk], dl[kk], dn[2 * th + 1], dh[kk], dl[kk]);
         }
     }
     // ---- epilogue: the norm adjoint on (w = d xhat-space adjoint, xhat from the planes), the residual dY' from ITS planes
@@ -371,11 +316,7 @@ __global__ __launch_bounds__(256, 2) void k_emlp_bwd_s(const float* __restrict__
     {
         const float f = inv * ABS_INV;  // dn holds 64 x (W_in^T planes) of the scaled row
         float dot = 0.f, sw = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                w[4 * t + j] = make_float4(dn[t][4 * j] * f, dn[t][4 * j + 1] * f, dn[t][4 * j + 2] * f, dn[t][4 * j + 3] * f);
+        hs_acc_rows<4>(w, dn, f);
         float4 xh4[16];
 #pragma unroll
         for (int kb = 0; kb < 8; kb++) {
@@ -415,26 +356,12 @@ __global__ __launch_bounds__(256, 2) void k_emlp_bwd_s(const float* __restrict__
     store_rows_lines<16>(w, reinterpret_cast<float*>(tile), L, [&](int r) { return live && row0 + r < E ? dX1 + (row0 + r) * D : nullptr; });
 }
 
-static inline W2 es_w2(const void* base, int n_out, int k_in) {
-    const size_t n8 = (size_t)(n_out / 32) * (k_in / 16) * 64;
-    const f16x8* b = reinterpret_cast<const f16x8*>(base);
-    W2 w; w.h = b; w.l = b + n8;
-    return w;
-}
-
 int emlp_s(const float* X1, const float* gamma, const float* beta, const Lin& win, const Lin& wout, float* VG, float* X2,
            int64_t E, hipStream_t st) {
     PET_REQUIRE_PLANES(win.fwd2s && wout.fwd2s, "edge MLP");
-    const size_t lds = ES_NW * 16384 + ES_NSLOT * ES_SLOT;
-    const W2 wi = es_w2(win.fwd2s, win.n_out, win.k_in), wo = es_w2(wout.fwd2s, wout.n_out, wout.k_in);
-    const int grid = (int)cdiv(E, ES_NW * WROWS);
-    if (beta) {
-        allow_big_lds(k_emlp_s<true>, lds);
-        k_emlp_s<true><<<grid, 256, lds, st>>>(X1, gamma, beta, wi, win.b, wo, wout.b, VG, X2, E);
-    } else {
-        allow_big_lds(k_emlp_s<false>, lds);
-        k_emlp_s<false><<<grid, 256, lds, st>>>(X1, gamma, beta, wi, win.b, wo, wout.b, VG, X2, E);
-    }
+    const W2 wi = lin_planes(win.fwd2s, win), wo = lin_planes(wout.fwd2s, wout);
+    if (beta) launch_ring(k_emlp_s<true>, E, st, X1, gamma, beta, wi, win.b, wo, wout.b, VG, X2, E);
+    else launch_ring(k_emlp_s<false>, E, st, X1, gamma, beta, wi, win.b, wo, wout.b, VG, X2, E);
     return PET_OK;
 }
 
@@ -443,15 +370,8 @@ int emlp_bwd_s(const float* dY, const float* X1, bool ln, const Lin& win_g, cons
                hipStream_t st, int ldy, const float* dY2, const int* rev2) {
     PET_REQUIRE_PLANES(win_g.fwd2s && win_g.bwd2s && wout.bwd2s, "edge MLP adjoint");
     if (E <= 0) return PET_OK;
-    const size_t lds = ES_NW * 16384 + ES_NSLOT * ES_SLOT;
-    const W2 wi = es_w2(win_g.fwd2s, win_g.n_out, win_g.k_in), wot = es_w2(wout.bwd2s, wout.n_out, wout.k_in),
-             wit = es_w2(win_g.bwd2s, win_g.n_out, win_g.k_in);
-    const int grid = (int)cdiv(E, ES_NW * WROWS);
-#define PET_EB(LNF, GF)                                                                                        \
-    {                                                                                                          \
-        allow_big_lds(k_emlp_bwd_s<LNF, GF>, lds);                                                             \
-        k_emlp_bwd_s<LNF, GF><<<grid, 256, lds, st>>>(dY, X1, wi, win_g.b, wot, wit, dX1, E, ldy, dY2, rev2);  \
-    }
+    const W2 wi = lin_planes(win_g.fwd2s, win_g), wot = lin_planes(wout.bwd2s, wout), wit = lin_planes(win_g.bwd2s, win_g);
+#define PET_EB(LNF, GF) launch_ring(k_emlp_bwd_s<LNF, GF>, E, st, dY, X1, wi, win_g.b, wot, wit, dX1, E, ldy, dY2, rev2);
     if (ln) { if (dY2) PET_EB(true, true) else PET_EB(true, false) }
     else { if (dY2) PET_EB(false, true) else PET_EB(false, false) }
 #undef PET_EB

@@ -1,7 +1,5 @@
 // The edge head (backend.py:651-777: y = w_l . silu(W2 silu(W0 x + b0) + b2) + b_l per edge, times the cutoff factor, summed
-// per centre atom by k_atom_sum) and its adjoint in the form of k_emlp_s (pet_emlp_s.hip): one-accumulator split-operand
-// products, two desynchronised four-wave workgroups per CU, the four waves of a workgroup sharing ONE stream of weight
-// fragments through a four-slot LDS ring requested three stages ahead. Round 5.
+// per centre atom by k_atom_sum) and its adjoint on the row ring (rows_s.h). Round 5.
 //
 // k_head_h / k_head_bwd_h (pet_trr.hip) stream their weights per wave straight from L2 (64 KB per 128 x 128 product and wave):
 // with every weight block replaced by block 0 they run 25 % faster (tools/experiments/README.md), and the adjoint needs 492
@@ -25,8 +23,8 @@ namespace pet {
 #define HS_WARGS wa, wb, wc, wd
 template <int NM>
 __device__ __forceinline__ void hs_request(int g, HS_W, unsigned ring_u, int wave, unsigned lane16) {
-    g = g < 16 * NM ? g : 16 * NM - 1;
-    const unsigned dst = ring_u + (unsigned)(g & (HS_NSLOT - 1)) * HS_SLOT + wave * 1024;
+    g = ring_clamp(g, 16 * NM);
+    const unsigned dst = RING_SLOT_DST(ring_u, wave, g);
     const int mi = g >> 4, tp = (g >> 3) & 1, kb = g & 7;
     const int idx = (2 * tp + (wave >> 1)) * 8 + kb;
     // (g is a compile-time constant at every call)
@@ -45,19 +43,7 @@ __global__ __launch_bounds__(256, 2) void k_head_s(const float* __restrict__ Xin
                                                   const float* __restrict__ b2, const float* __restrict__ wl, float bl,
                                                   const float* __restrict__ fc, float* __restrict__ ypred,
                                                   float* __restrict__ yout, int64_t R) {
-    extern __shared__ __attribute__((aligned(16))) char hs_smem[];
-    const RowLane L;
-    const unsigned lane16 = (unsigned)L.lane * 16u;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int64_t row0 = ((int64_t)blockIdx.x * HS_NW + wave) * WROWS;
-    const bool live = row0 < R;
-    if (!live) row0 = ((R - 1) / WROWS) * WROWS;  // run along on the last tile (same barriers), store nothing
-    const int64_t row = row0 + L.r < R ? row0 + L.r : R - 1;
-    const bool valid = live && row0 + L.r < R;
-    char* tile = hs_smem + wave * 16384;
-    const char* ring = hs_smem + HS_NW * 16384;
-    const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);
-    const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+    RING_WAVE(R);
     dma_tile128(Xin, row0, R, tile_u, L);
     const float fcr = fc ? fc[row] : 1.0f;
     asm volatile("" ::"v"(fcr));
@@ -119,19 +105,7 @@ __global__ __launch_bounds__(256, 2) void k_head_bwd_s(const float* __restrict__
                                                       const float* __restrict__ gA, const int* __restrict__ ctr,
                                                       const float* __restrict__ fc, const float* __restrict__ ypred,
                                                       float* __restrict__ dfc, float* __restrict__ dXout, int64_t R) {
-    extern __shared__ __attribute__((aligned(16))) char hs_smem[];
-    const RowLane L;
-    const unsigned lane16 = (unsigned)L.lane * 16u;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int64_t row0 = ((int64_t)blockIdx.x * HS_NW + wave) * WROWS;
-    const bool live = row0 < R;
-    if (!live) row0 = ((R - 1) / WROWS) * WROWS;
-    const int64_t row = row0 + L.r < R ? row0 + L.r : R - 1;
-    const bool valid = live && row0 + L.r < R;
-    char* tile = hs_smem + wave * 16384;
-    const char* ring = hs_smem + HS_NW * 16384;
-    const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);
-    const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+    RING_WAVE(R);
     dma_tile128(Xin, row0, R, tile_u, L);
     float gy;  // dL/dy of this edge: the centre atom's seed times the cutoff factor
     {
@@ -217,42 +191,23 @@ __global__ __launch_bounds__(256, 2) void k_head_bwd_s(const float* __restrict__
     hs_gemm<4>(acc, xh, xl, 48, w0f, w2f, w2b, w0b, ring, ring_u, wave, lane16);
     // dx = W0^T da1: whole lines through the wave's tile (a1 is dead)
     float4 dx[16];
-    {
-        const float f = inv * ABQ_INV;
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                dx[4 * t + j] = make_float4(acc[t][4 * j] * f, acc[t][4 * j + 1] * f, acc[t][4 * j + 2] * f, acc[t][4 * j + 3] * f);
-    }
+    hs_acc_rows<4>(dx, acc, inv * ABQ_INV);
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
     store_rows_lines<16>(dx, reinterpret_cast<float*>(tile), L, [&](int r) { return live && row0 + r < R ? dXout + (row0 + r) * D : nullptr; });
 }
 
-static inline W2 hs_w2(const void* base, int n_out, int k_in) {
-    const size_t n8 = (size_t)(n_out / 32) * (k_in / 16) * 64;
-    const f16x8* b = reinterpret_cast<const f16x8*>(base);
-    W2 w; w.h = b; w.l = b + n8;
-    return w;
-}
-
 int head_edge_s(const Model& m, const float* Xin, const float* fc, float* ypred, float* yout, int64_t E, hipStream_t st) {
     PET_REQUIRE_PLANES(m.eh0.fwd2s && m.eh2.fwd2s, "edge head");
-    const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
-    allow_big_lds(k_head_s, lds);
-    k_head_s<<<(int)cdiv(E, HS_NW * WROWS), 256, lds, st>>>(Xin, hs_w2(m.eh0.fwd2s, DH, D), m.eh0.b, hs_w2(m.eh2.fwd2s, DH, DH), m.eh2.b,
-                                                             m.ell_w, m.ell_b, fc, ypred, yout, E);
+    launch_ring(k_head_s, E, st, Xin, lin_planes(m.eh0.fwd2s, m.eh0), m.eh0.b, lin_planes(m.eh2.fwd2s, m.eh2), m.eh2.b, m.ell_w, m.ell_b,
+                fc, ypred, yout, E);
     return PET_OK;
 }
 int head_edge_bwd_s(const Model& m, const float* Xin, const float* gA, const int* ctr, const float* fc, const float* ypred,
                     float* dfc, float* dXout, int64_t E, hipStream_t st) {
     PET_REQUIRE_PLANES(m.eh0.fwd2s && m.eh2.fwd2s && m.eh0.bwd2s && m.eh2.bwd2s, "edge head adjoint");
-    const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
-    allow_big_lds(k_head_bwd_s, lds);
-    k_head_bwd_s<<<(int)cdiv(E, HS_NW * WROWS), 256, lds, st>>>(Xin, hs_w2(m.eh0.fwd2s, DH, D), m.eh0.b, hs_w2(m.eh2.fwd2s, DH, DH),
-                                                                 m.eh2.b, hs_w2(m.eh2.bwd2s, DH, DH), hs_w2(m.eh0.bwd2s, DH, D), m.ell_w, gA,
-                                                                 ctr, fc, ypred, dfc, dXout, E);
+    launch_ring(k_head_bwd_s, E, st, Xin, lin_planes(m.eh0.fwd2s, m.eh0), m.eh0.b, lin_planes(m.eh2.fwd2s, m.eh2), m.eh2.b,
+                lin_planes(m.eh2.bwd2s, m.eh2), lin_planes(m.eh0.bwd2s, m.eh0), m.ell_w, gA, ctr, fc, ypred, dfc, dXout, E);
     return PET_OK;
 }
 

@@ -7,8 +7,7 @@
 namespace pet {
 
 // ---- policy ----------------------------------------------------------------------------------------------------------
-// pet_config_set("emlp_s", v): the ring kernels from switches().emlp_s_rows rows on (v > 1: the tests force small graphs through)
-static bool ring_serves(int64_t rows) { return switches().emlp_s && rows >= switches().emlp_s_rows; }
+// (the ring kernels' row policy: switches.h ring_serves)
 // the node chain's Linear layers as k_rowlin_s: large graphs (below, the 32-row node kernels fuse two of the three), or forced
 static bool ring_center_serves(int64_t N) {
     return ring_serves((int64_t)1 << 40) && (N >= NODE_ROWS32_MAX_ATOMS || switches().emlp_s_rows < EMLP_S_MIN_ROWS);

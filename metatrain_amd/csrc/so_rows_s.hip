@@ -1,6 +1,5 @@
-// The generic row GEMM of the training passes, Y[R, 128 nn] (=|+=) (X[R, 128 nk] * cs) W^T + bias, in the form of k_emlp_s
-// (rows_s.h): one-accumulator split-operand products, two desynchronised four-wave workgroups per CU, the four waves of a
-// workgroup sharing ONE stream of weight fragments through a four-slot LDS ring requested three stages ahead. Round 6.
+// The generic row GEMM of the training passes, Y[R, 128 nn] (=|+=) (X[R, 128 nk] * cs) W^T + bias, on the row ring (rows_s.h;
+// DESIGN 4.4). Round 6.
 //
 // k_rowgemm_k128 / k_rowgemm_n128 (so.hip) stream 64 KB of weight fragments per 128 x 128 product and WAVE from L2 -- 2 to 4 KB
 // per row against the 1.5 to 2.5 KB per row that the row operands move through HBM -- and the wide shapes take one launch per
@@ -23,79 +22,28 @@
 
 namespace pet {
 
-#define RS_STAGE_SYNC_LEAD()                                          \
-    do {                                                              \
-        asm volatile("s_waitcnt vmcnt(18) lgkmcnt(0)" ::: "memory");  \
-        __syncthreads();                                              \
-    } while (0)
-
-// dma_tile128 (trr.h) with the addresses as one wave-uniform base (the slice's first row) + a 32-bit lane offset: the 64-bit
-// row addresses of trr.h's form, three sets of sixteen, were kept across the product loop in spilled registers
-__device__ __forceinline__ void rs_dma_tile(const float* __restrict__ Xs, int64_t r0, int64_t R, int ldx, unsigned lds_base,
-                                            const RowLane& L) {
-    const float* base = Xs + r0 * ldx;
-    const int rmax = (int)(R - 1 - r0 < 31 ? R - 1 - r0 : 31);  // rows past the end: the last one again
-    const int hi = L.lane >> 5, c = L.lane & 31;
-#pragma unroll
-    for (int j = 0; j < 16; j++) {
-        const int r = 2 * j + hi, rr = r < rmax ? r : rmax;
-        const unsigned off = ((unsigned)rr * (unsigned)ldx + 4u * (unsigned)(c ^ (r & 15))) * 4u;
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(off), "s"(base), "s"(lds_base + j * 1024) : "memory");
-    }
-}
-
 // v[i] for the lanes of the low half, v[i + 4] for the others (the compiler folds the select into the address: one divergent
 // vector load per value, consumed before the product's first stage; pinning the two values to scalar registers does not
 // compile -- behind the ring's asm statements the loads are not provably unclobbered, so they are not scalar loads)
 __device__ __forceinline__ float rs_pick(const float* __restrict__ v, int i, int h) { return h ? v[i + 4] : v[i]; }
 
-// hs_gemm_r (rows_s.h) with `lead` (wave-uniform): 16 vector-memory operations of this wave that are younger than the ring
-// requests of the first three stages may stay in flight over those stages. req(s, slot): request stage s of THIS product
-// (s = 3 .. 18; 16 .. 18 are the first stages of the next one) into ring slot `slot`
-template <class Req>
-__device__ __forceinline__ void rs_gemm(f32x16 (&acc)[4], const f16x8 (&xh)[8], const f16x8 (&xl)[8], bool lead, Req req,
-                                        const char* ring, unsigned lane16) {
-#pragma unroll
-    for (int r = 0; r < 16; r++) {  // (a product starts at a stage that is a multiple of 16: ring slot = r & 3)
-        const int tp = r >> 3, kb = r & 7;
-        if (r < 3 && lead) RS_STAGE_SYNC_LEAD();
-        else HS_STAGE_SYNC();
-        req(r + 3, (r + 3) & (HS_NSLOT - 1));
-        const char* slot = ring + (r & (HS_NSLOT - 1)) * HS_SLOT + lane16;
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const f16x8 wh = *reinterpret_cast<const f16x8*>(slot + (2 * t) * 1024);
-            const f16x8 wl = *reinterpret_cast<const f16x8*>(slot + (2 * t + 1) * 1024);
-            AB_MFMA3(acc[2 * tp + t], wh, wl, xh[kb], xl[kb]);
-        }
-    }
-}
-
+// The products are rows_s.h hs_gemm_r<16> with `lead` (wave-uniform): the 16 vector-memory operations of this wave that are
+// younger than the ring requests of the first three stages (the next slice's requests, or a column block's stores) may stay in
+// flight over those stages: vmcnt(2 + 16). A product starts at a stage that is a multiple of 16, so its stage s is in ring slot
+// s mod 4: piece(nb, ks, s, g) requests stage s (0 .. 15) of product (nb, ks) into the slot of stage g.
 // w: planes of 64 W (k_pack2h with both scales 64: Lin::fwd2s / bwd2s), fragments [(tile * (K / 16) + kb) * 64 + lane]
 __global__ __launch_bounds__(256, 2) void k_rowgemm_s(const float* __restrict__ X, int ldx, int nk, const float* __restrict__ cs,
                                                      W2 w, const float* __restrict__ bias, float* __restrict__ Y, int ldy, int nn,
                                                      int64_t R, const float* __restrict__ A /* addend rows (ld = ldy), may be Y; or null */) {
-    extern __shared__ __attribute__((aligned(16))) char rs_smem[];
-    const RowLane L;
-    const unsigned lane16 = (unsigned)L.lane * 16u;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    int64_t row0 = ((int64_t)blockIdx.x * HS_NW + wave) * WROWS;
-    const bool live = row0 < R;
-    if (!live) row0 = ((R - 1) / WROWS) * WROWS;  // run along on the last tile (same barriers), store nothing
-    char* tile = rs_smem + wave * 16384;
-    const char* ring = rs_smem + HS_NW * 16384;
-    const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);
-    const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);
+    RING_WAVE(R);
     const int kbt = 8 * nk, np = nk * nn;
     // stage s (0 .. 15) of product (nb, ks): tile pair s / 8, K block s % 8; wave w brings tile 2 tp + (w >> 1), plane w & 1
     const f16x8* plane = (wave & 1) ? w.l : w.h;
-    auto piece = [=](int nb, int ks, int s, int slot) {
-        const unsigned dst = ring_u + (unsigned)slot * HS_SLOT + wave * 1024;
+    auto piece = [=](int nb, int ks, int s, int g) {
+        const unsigned dst = RING_SLOT_DST(ring_u, wave, g);
         ab_dma_piece(plane, (4 * nb + 2 * (s >> 3) + (wave >> 1)) * kbt + 8 * ks + (s & 7), lane16, dst);
     };
-    rs_dma_tile(X, row0, R, ldx, tile_u, L);
+    ring_dma_rows(X, row0, R, ldx, tile_u, L);
     piece(0, 0, 0, 0);
     piece(0, 0, 1, 1);
     piece(0, 0, 2, 2);
@@ -148,17 +96,17 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s(const float* __restrict__ 
         if (ks + 1 < nk) {  // the next slice into the tile while this product runs (the fragments above have been read)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
-            rs_dma_tile(X + 128 * (ks + 1), r0, R, ldx, tile_u, Lp);
+            ring_dma_rows(X + 128 * (ks + 1), r0, R, ldx, tile_u, Lp);
             lead = true;
         }
         {   // the product after this one (past the end: this product's last stage again -- keeps vmcnt uniform)
             const bool last = p + 1 == np;
             const int ksn = ks + 1 < nk ? ks + 1 : 0, nbn = ks + 1 < nk ? nb : nb + 1;
-            rs_gemm(acc, xh, xl, lead, [=](int s, int slot) {
-                if (s < 16) piece(nb, ks, s, slot);
-                else if (last) piece(nb, ks, 15, slot);
-                else piece(nbn, ksn, s - 16, slot);
-            }, ring, lane16);
+            hs_gemm_r<16>(acc, xh, xl, 0, [=](int s) {
+                if (s < 16) piece(nb, ks, s, s);
+                else if (last) piece(nb, ks, 15, s);
+                else piece(nbn, ksn, s - 16, s);
+            }, ring, lane16, lead);
         }
         if (ks + 1 < nk) continue;
         // ---- the column block is complete: scale back, bias, (addend), whole-line stores through the row tile
@@ -201,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s(const float* __restrict__ 
             __builtin_amdgcn_wave_barrier();
             int64_t r1 = row0;
             asm volatile("" : "+s"(r1));
-            rs_dma_tile(X, r1, R, ldx, tile_u, Lp);
+            ring_dma_rows(X, r1, R, ldx, tile_u, Lp);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
     }
@@ -219,19 +167,9 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s(const float* __restrict__ 
 // Both take an addend (Y = A + ...; A == Y accumulates in place). Same stream order convention as above: product p of the
 // stream = (column block, K slice) in the order the kernel consumes them.
 // ---------------------------------------------------------------------------------------------------------------------------
-#define RS_SETUP()                                                                                       \
-    extern __shared__ __attribute__((aligned(16))) char rs_smem[];                                       \
-    const RowLane L;                                                                                     \
-    const unsigned lane16 = (unsigned)L.lane * 16u;                                                      \
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                   \
-    int64_t row0 = ((int64_t)blockIdx.x * HS_NW + wave) * WROWS;                                         \
-    const bool live = row0 < R;                                                                          \
-    if (!live) row0 = ((R - 1) / WROWS) * WROWS;                                                         \
-    const bool full = live && row0 + WROWS <= R; /* every store instruction of the tile is issued */     \
-    char* tile = rs_smem + wave * 16384;                                                                 \
-    const char* ring = rs_smem + HS_NW * 16384;                                                          \
-    const unsigned tile_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)tile);                   \
-    const unsigned ring_u = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)ring);                   \
+// the wave's frame (rows_s.h) and the weight plane this wave requests from
+#define RS_SETUP() \
+    RING_WAVE(R);  \
     const f16x8* plane = (wave & 1) ? w.l : w.h
 #define RS_LANE(Lx)                            \
     RowLane Lx = L;                            \
@@ -353,12 +291,13 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s_k2(const float* __restrict
                                                         const float* __restrict__ cb, W2 w, const float* __restrict__ bias,
                                                         const float* __restrict__ A, float* __restrict__ Y, int ldy, int nn, int64_t R) {
     RS_SETUP();
+    const bool full = live && row0 + WROWS <= R;  // every store instruction of the tile is issued
     constexpr int nk = 2, kbt = 16;
-    auto piece = [=](int nb, int ks, int s, int slot) {
-        const unsigned dst = ring_u + (unsigned)slot * HS_SLOT + wave * 1024;
+    auto piece = [=](int nb, int ks, int s, int g) {
+        const unsigned dst = RING_SLOT_DST(ring_u, wave, g);
         ab_dma_piece(plane, (4 * nb + 2 * (s >> 3) + (wave >> 1)) * kbt + 8 * ks + (s & 7), lane16, dst);
     };
-    rs_dma_tile(X, row0, R, ldx, tile_u, L);
+    ring_dma_rows(X, row0, R, ldx, tile_u, L);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     f16x8 xh[2][8], xl[2][8];
     float inv;
@@ -367,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s_k2(const float* __restrict
         tile128_to_frag(x0, tile, L);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the reads have returned before the tile is requested again
         __builtin_amdgcn_wave_barrier();
-        rs_dma_tile(X + 128, row0, R, ldx, tile_u, L);
+        ring_dma_rows(X + 128, row0, R, ldx, tile_u, L);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         tile128_to_frag(x1, tile, L);
         if (NORM) {  // RMSNorm (eps 2^-23) or torch.nn.LayerNorm (eps 1e-5) over the 256 columns, then weight (and bias)
@@ -436,13 +375,13 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s_k2(const float* __restrict
         // (16 store instructions of the previous block may be in flight over the first three stages -- if all of them were issued)
         if (nb > 0 && !full) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (a partial tile skips store instructions: drained instead of counted)
         if (EPI == 1 && nb > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (32 stores per block there: drained, not budgeted)
-        rs_gemm(acc, xh[0], xl[0], EPI == 0 && nb > 0 && full, [=](int s, int slot) {
-            if (s < 16) piece(nb, 0, s, slot); else piece(nb, 1, s - 16, slot);
-        }, ring, lane16);
-        rs_gemm(acc, xh[1], xl[1], false, [=](int s, int slot) {
-            if (s < 16) piece(nb, 1, s, slot);
-            else if (last) piece(nb, 1, 15, slot);
-            else piece(nb + 1, 0, s - 16, slot);
+        hs_gemm_r<16>(acc, xh[0], xl[0], 0, [=](int s) {
+            if (s < 16) piece(nb, 0, s, s); else piece(nb, 1, s - 16, s);
+        }, ring, lane16, EPI == 0 && nb > 0 && full);
+        hs_gemm_r(acc, xh[1], xl[1], 0, [=](int s) {
+            if (s < 16) piece(nb, 1, s, s);
+            else if (last) piece(nb, 1, 15, s);
+            else piece(nb + 1, 0, s - 16, s);
         }, ring, lane16);
         RS_LANE(Lq);
         RS_ROW0(r0);
@@ -457,13 +396,12 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s_n2(const float* __restrict
                                                         float* __restrict__ Y, int ldy, int64_t R,
                                                         const float* __restrict__ xn = nullptr, int ln = 0) {
     RS_SETUP();
-    (void)full;
     const int kbt = 8 * nk;
-    auto piece = [=](int nb, int ks, int s, int slot) {
-        const unsigned dst = ring_u + (unsigned)slot * HS_SLOT + wave * 1024;
+    auto piece = [=](int nb, int ks, int s, int g) {
+        const unsigned dst = RING_SLOT_DST(ring_u, wave, g);
         ab_dma_piece(plane, (4 * nb + 2 * (s >> 3) + (wave >> 1)) * kbt + 8 * ks + (s & 7), lane16, dst);
     };
-    rs_dma_tile(X, row0, R, ldx, tile_u, L);
+    ring_dma_rows(X, row0, R, ldx, tile_u, L);
     piece(0, 0, 0, 0);
     piece(0, 0, 1, 1);
     piece(0, 0, 2, 2);
@@ -515,15 +453,15 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s_n2(const float* __restrict
         if (more) {  // the next slice into the tile while this slice's two products run
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_wave_barrier();
-            rs_dma_tile(X + 128 * (ks + 1), r0, R, ldx, tile_u, Lp);
+            ring_dma_rows(X + 128 * (ks + 1), r0, R, ldx, tile_u, Lp);
         }
-        rs_gemm(acc0, xh, xl, more, [=](int s, int slot) {
-            if (s < 16) piece(0, ks, s, slot); else piece(1, ks, s - 16, slot);
-        }, ring, lane16);
-        rs_gemm(acc1, xh, xl, false, [=](int s, int slot) {
-            if (s < 16) piece(1, ks, s, slot);
-            else if (!more) piece(1, ks, 15, slot);
-            else piece(0, ks + 1, s - 16, slot);
+        hs_gemm_r<16>(acc0, xh, xl, 0, [=](int s) {
+            if (s < 16) piece(0, ks, s, s); else piece(1, ks, s - 16, s);
+        }, ring, lane16, more);
+        hs_gemm_r(acc1, xh, xl, 0, [=](int s) {
+            if (s < 16) piece(1, ks, s, s);
+            else if (!more) piece(1, ks, 15, s);
+            else piece(0, ks + 1, s - 16, s);
         }, ring, lane16);
     }
     const float f = inv * ABQ_INV;
@@ -539,59 +477,34 @@ __global__ __launch_bounds__(256, 2) void k_rowgemm_s_n2(const float* __restrict
     rs_store_block(acc1, f, bias ? bias + 128 : nullptr, A, Y, ldy, 128, r0, R, live, tile, Lq);
 }
 
-// the ring kernels' row policy (pet_config_set("emlp_s"); the first-order pass states the same in pet_plan.hip)
-static bool rows_s_serves(int64_t R) { return switches().emlp_s && R >= switches().emlp_s_rows; }
-
 // false = not served: planes missing, shape not a multiple of 128 both ways, a small matrix of rows, or the row kernels'
 // switch is off (pet_config_set("emlp_s", 0); "emlp_s" = 2 serves the tests' small graphs too).
 // Y = [A +] (norm(X) | X * cs) W^T [+ bias]; A may be Y (accumulate in place); norm 1 / 2: RMSNorm / LayerNorm of the 256-wide rows
 // with weight cs (and bias cb) before the product (K == 256 only)
 bool rowgemm_s_ex(hipStream_t st, const float* X, int K, const float* cs, const void* planes, const float* bias, const float* A,
                   float* Y, int n_out, int64_t R, int norm, const float* cb) {
-    if (!planes || K % 128 || n_out % 128 || K > 1024 || n_out > 1024 || !rows_s_serves(R)) return false;
+    if (!planes || K % 128 || n_out % 128 || K > 1024 || n_out > 1024 || !ring_serves(R)) return false;
     if (norm && (K != 256 || !cs || (norm == 2 && !cb))) return false;
-    const size_t n8 = (size_t)(n_out / 32) * (K / 16) * 64;
-    const f16x8* b = reinterpret_cast<const f16x8*>(planes);
-    W2 w; w.h = b; w.l = b + n8;
-    const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
-    const int grid = (int)cdiv(R, HS_NW * WROWS);
-    if (norm == 1) {
-        allow_big_lds(k_rowgemm_s_k2<1>, lds);
-        k_rowgemm_s_k2<1><<<grid, 256, lds, st>>>(X, K, cs, cb, w, bias, A, Y, n_out, n_out / 128, R);
-    } else if (norm == 2) {
-        allow_big_lds(k_rowgemm_s_k2<2>, lds);
-        k_rowgemm_s_k2<2><<<grid, 256, lds, st>>>(X, K, cs, cb, w, bias, A, Y, n_out, n_out / 128, R);
-    } else if (K == 256 && n_out >= 256) {
-        allow_big_lds(k_rowgemm_s_k2<0>, lds);
-        k_rowgemm_s_k2<0><<<grid, 256, lds, st>>>(X, K, cs, nullptr, w, bias, A, Y, n_out, n_out / 128, R);
-    } else if (n_out == 256 && K >= 256 && !cs) {
-        allow_big_lds(k_rowgemm_s_n2<0>, lds);
-        k_rowgemm_s_n2<0><<<grid, 256, lds, st>>>(X, K, K / 128, w, bias, A, Y, n_out, R);
-    } else {
-        allow_big_lds(k_rowgemm_s, lds);
-        k_rowgemm_s<<<grid, 256, lds, st>>>(X, K, K / 128, cs, w, bias, Y, n_out, n_out / 128, R, A);
-    }
+    const W2 w = w2_planes(planes, n_out / 32, K / 16);
+    if (norm == 1) launch_ring(k_rowgemm_s_k2<1>, R, st, X, K, cs, cb, w, bias, A, Y, n_out, n_out / 128, R);
+    else if (norm == 2) launch_ring(k_rowgemm_s_k2<2>, R, st, X, K, cs, cb, w, bias, A, Y, n_out, n_out / 128, R);
+    else if (K == 256 && n_out >= 256) launch_ring(k_rowgemm_s_k2<0>, R, st, X, K, cs, nullptr, w, bias, A, Y, n_out, n_out / 128, R);
+    else if (n_out == 256 && K >= 256 && !cs) launch_ring(k_rowgemm_s_n2<0>, R, st, X, K, K / 128, w, bias, A, Y, n_out, R, nullptr, 0);
+    else launch_ring(k_rowgemm_s, R, st, X, K, K / 128, cs, w, bias, Y, n_out, n_out / 128, R, A);
     return true;
 }
 // dVG[R, 2 hid] = swiglu'(VG) ((X[R, 256]) W^T): the node update's adjoint, first half (hid a multiple of 128)
 bool rowgemm_s_swiglu_bwd(hipStream_t st, const float* X, const void* planes, const float* VG, float* dVG, int hid, int64_t R) {
-    if (!planes || hid % 128 || hid > 1024 || !rows_s_serves(R)) return false;
-    const f16x8* b = reinterpret_cast<const f16x8*>(planes);
-    W2 w; w.h = b; w.l = b + (size_t)(hid / 32) * (256 / 16) * 64;
-    const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
-    allow_big_lds(k_rowgemm_s_k2<0, 1>, lds);
-    k_rowgemm_s_k2<0, 1><<<(int)cdiv(R, HS_NW * WROWS), 256, lds, st>>>(X, 256, nullptr, nullptr, w, nullptr, VG, dVG, 2 * hid, hid / 128, R);
+    if (!planes || hid % 128 || hid > 1024 || !ring_serves(R)) return false;
+    launch_ring(k_rowgemm_s_k2<0, 1>, R, st, X, 256, nullptr, nullptr, w2_planes(planes, hid / 32, 256 / 16), nullptr, VG, dVG, 2 * hid,
+                hid / 128, R);
     return true;
 }
 // out[R, 256] = dres + norm^T((X[R, K]) W^T; xn): the node update's adjoint, second half (gamma: the norm's weight; ln: LayerNorm)
 bool rowgemm_s_norm_bwd(hipStream_t st, const float* X, int K, const void* planes, const float* xn, const float* gamma, int ln,
                         const float* dres, float* out, int64_t R) {
-    if (!planes || K % 128 || K < 256 || K > 1024 || !rows_s_serves(R)) return false;
-    const f16x8* b = reinterpret_cast<const f16x8*>(planes);
-    W2 w; w.h = b; w.l = b + (size_t)(256 / 32) * (K / 16) * 64;
-    const size_t lds = HS_NW * 16384 + HS_NSLOT * HS_SLOT;
-    allow_big_lds(k_rowgemm_s_n2<1>, lds);
-    k_rowgemm_s_n2<1><<<(int)cdiv(R, HS_NW * WROWS), 256, lds, st>>>(X, K, K / 128, w, gamma, dres, out, 256, R, xn, ln);
+    if (!planes || K % 128 || K < 256 || K > 1024 || !ring_serves(R)) return false;
+    launch_ring(k_rowgemm_s_n2<1>, R, st, X, K, K / 128, w2_planes(planes, 256 / 32, K / 16), gamma, dres, out, 256, R, xn, ln);
     return true;
 }
 bool rowgemm_s(hipStream_t st, const float* X, int K, const float* cs, const void* planes, const float* bias, float* Y, int n_out,

@@ -32,4 +32,8 @@ struct Switches {
 
 const Switches& switches();
 
+// the row policy of the ring kernels (rows_s.h), first-order plan and second-order GEMMs alike: pet_config_set("emlp_s", v) serves
+// row counts from emlp_s_rows on (v > 1: the tests force small graphs through)
+inline bool ring_serves(int64_t rows) { return switches().emlp_s && rows >= switches().emlp_s_rows; }
+
 }  // namespace pet

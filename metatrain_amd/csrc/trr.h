@@ -126,6 +126,13 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 struct W2 {  // weight fragments, high and (scaled) low plane, [(tile * kb_total + kb) * 64 + lane]
     const f16x8 *h = nullptr, *l = nullptr;
 };
+// the two planes of a packed matrix of `tiles` 32-row tiles x `kbs` 16-column K blocks (the low plane follows the high one)
+inline W2 w2_planes(const void* base, int tiles, int kbs) {
+    W2 w;
+    w.h = reinterpret_cast<const f16x8*>(base);
+    w.l = w.h + (size_t)tiles * kbs * 64;
+    return w;
+}
 typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
 // x - h with h read as the fp16 (low / high) half of a register: ONE mixed-precision fma instead of v_cvt_f32_f16 + v_sub
 // (the difference is exact in fp32 either way, so the result is the same bit for bit)

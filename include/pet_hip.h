@@ -580,6 +580,30 @@ int pet_zbl_hessian_vector(const pet_zbl_t* z, const pet_graph_t* g, const float
  *   pet_ewald_backward: d_grad_potential [N,C] -> d_grad_charges [N,C], d_grad_positions [N,3], d_grad_cells [S,3,3] (may be
  *     NULL): dL/dcell at fixed Cartesian positions. Nothing is kept between the two calls.
  *   d_workspace: pet_ewald_workspace_bytes(e, C) bytes (after the plan). No host synchronisation after the plan.
+ * Second derivatives (pet_ewald_second). Per system V = A(r) q with A symmetric, Phi(r; g, q) = sum_c g_c^T A q_c,
+ * and the adjoint above returns gq = A g, gpos = grad_r Phi. For cotangents u_q [N, C] of gq and u_r [N, 3] of gpos,
+ *   Psi = <u_q, A g> + <u_r, grad_r Phi(r; g, q)>, and the call returns
+ *   d_out_grad_potential = dPsi/dg = A u_q + (D_u A) q,     d_out_charges = dPsi/dq = (D_u A) g,
+ *   d_out_positions      = dPsi/dr = grad_r Phi(r; u_q, g) + H_Phi(r; g, q) u_r,
+ *   D_u A = sum_i u_r,i . grad_{r_i} A (the directional derivative of A along u_r), H_Phi the position Hessian of Phi.
+ *   The same outputs serve forward mode: d/dt (A q) = A q' + (D_r' A) q is d_out_grad_potential with u_q = q', u_r = r'.
+ *   With e_ij = u_j - u_i, n = D / d and M_phi = phi''(d) n n^T + (phi'(d) / d) (I - n n^T):
+ *   k-space (half the k-set, w = 2 G / Omega, c, s = cos, sin k.r_i, S'_X = w sum_j X_j e^{i k.r_j},
+ *            S'_{uX} = w sum_j (k.u_j) X_j e^{i k.r_j}):
+ *     (D_u A X)_i = -P sum_k [ (c Im S'_{uX} - s Re S'_{uX}) - (k.u_i) (c Im S'_X - s Re S'_X) ]
+ *     (H u)_i     =  P sum_k k { g_i . [ (c Re S'_{uq} + s Im S'_{uq}) - (k.u_i) (c Re S'_q + s Im S'_q) ]
+ *                              + q_i . [ the same with g in place of q ] }
+ *     (self and background do not depend on r: they enter through A u_q alone)
+ *   exclusion, edge p = (i -> j, S), phi = w:  (D_u A X)_i = -P sum_{row i} w'(d) (n.e) X_j,
+ *     (H u)_i = P sum_{row i, j != i} (B_p + B'_p) M_w e          (an edge to an atom's own image has e = 0)
+ *   non-periodic, phi = K, all pairs j != i:  (D_u A X)_i = P sum_j K'(d) (n.e) X_j,
+ *     (H u)_i = -P sum_j (g_i.q_j + g_j.q_i) M_K e                (f = 0 beyond R: f'' jumps at d = R)
+ *   grad_r Phi(r; u_q, g) is the first-order position adjoint with (g, q) := (u_q, g), from the same kernels.
+ *   d_u_charges / d_u_positions may each be NULL (zero; that part's work is skipped), both NULL: PET_ERR_ARGUMENT. All three
+ *   outputs are written in full. d_workspace: pet_ewald_second_workspace_bytes(e, C) bytes (-1 without a plan, on a P3M-mode
+ *   handle, for C < 1). No atoms: PET_OK, nothing touched. Nothing is kept between calls, no host synchronisation, same bits run
+ *   to run and alone as inside a batch. No cell tangent is taken and no cell result returned (mixed position / cell second
+ *   derivatives are not built); a P3M-mode handle: PET_ERR_ARGUMENT (second derivatives through P3M are not built).
  * PET_ERR_ARGUMENT: a pet_graph_from_batch handle, a graph built under an adaptive cutoff (it drops edges inside R), a graph
  * of a model without nl_is_strict, a graph whose cutoff, atom or system count differ from the plan's.
  * PET_ERR_UNSUPPORTED: mixed pbc; a cell with more than PET_EWALD_MAX_INDEX reciprocal indices along an axis. */
@@ -597,6 +621,11 @@ int pet_ewald_potential(const pet_ewald_t* e, const pet_graph_t* g, const float*
 int pet_ewald_backward(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
                        const float* d_grad_potential, int32_t n_channels, float* d_grad_charges, float* d_grad_positions,
                        float* d_grad_cells, void* d_workspace, int64_t workspace_bytes, void* stream);
+int64_t pet_ewald_second_workspace_bytes(const pet_ewald_t* e, int64_t n_channels);
+int pet_ewald_second(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
+                     const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions,
+                     int32_t n_channels, float* d_out_charges, float* d_out_grad_potential, float* d_out_positions,
+                     void* d_workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- P3M evaluation of the same operator (utils/long_range.py:71-79,153-170) ------------------------------------------------
  * The reference takes its Ewald branch only under `use_ewald and training`: every evaluation of a periodic long-range model

@@ -55,7 +55,8 @@ SYMBOLS = [
     "pet_zbl_create", "pet_zbl_destroy", "pet_zbl_cutoff", "pet_zbl_pair_table", "pet_zbl_workspace_bytes",
     "pet_zbl_forward", "pet_zbl_backward", "pet_zbl_hessian_vector",
     "pet_ewald_create", "pet_ewald_destroy", "pet_ewald_kvectors_host", "pet_ewald_plan", "pet_ewald_num_kvectors",
-    "pet_ewald_workspace_bytes", "pet_ewald_potential", "pet_ewald_backward",
+    "pet_ewald_workspace_bytes", "pet_ewald_potential", "pet_ewald_backward", "pet_ewald_second_workspace_bytes",
+    "pet_ewald_second",
     "pet_ewald_set_p3m", "pet_p3m_mesh_shape_host", "pet_p3m_influence_host", "pet_p3m_mesh_shape", "pet_p3m_mesh_elements",
     "pet_p3m_spectrum_elements", "pet_p3m_workspace_bytes", "pet_p3m_spread", "pet_p3m_filter", "pet_p3m_finish",
     "pet_p3m_backward",
@@ -299,6 +300,9 @@ def load() -> ctypes.CDLL:
     lib.pet_ewald_workspace_bytes.restype = c_int64
     lib.pet_ewald_potential.argtypes = [P, P, P, P, c_int32, P, P, c_int64, P]
     lib.pet_ewald_backward.argtypes = [P, P, P, P, P, c_int32, P, P, P, P, c_int64, P]
+    lib.pet_ewald_second_workspace_bytes.argtypes = [P, c_int64]
+    lib.pet_ewald_second_workspace_bytes.restype = c_int64
+    lib.pet_ewald_second.argtypes = [P, P, P, P, P, P, P, c_int32, P, P, P, P, c_int64, P]
     lib.pet_ewald_set_p3m.argtypes = [P, c_int32]
     lib.pet_p3m_mesh_shape_host.argtypes = [POINTER(c_double), c_double, POINTER(c_int32)]
     lib.pet_p3m_influence_host.argtypes = [POINTER(c_double), c_double, c_double, c_int32, POINTER(c_double), c_int64]

@@ -16,6 +16,10 @@
 // Each chunk of 32 contraction indices is summed on its own and then added to a total, and a system's k-vectors are listed by
 // descending |k| (small terms first): the k-space sum and the self term cancel to a few tenths of either, and one running
 // fp32 sum over 7 000 k-vectors left 8.9e-6 of the largest potential where this order leaves 3.5e-7.
+// Second derivatives (pet_ewald_second) are variants in the same form: k_ew_sfac<true> (the phase carries
+// k.u_j), k_ew_gather<true> (the directional derivative, a contraction of twice the length), k_ew_force2 (the position Hessian
+// applied to a direction: four product tiles per k tile, or M_K (u_j - u_i) for open systems), k_ew_pairs<true> (long_range.h) and
+// k_ew_edge_second (the exclusion rows, fp64); the <false> instantiations are the first-order kernels, bit for bit.
 // Here: the k-space part (k_ew_tables, k_ew_sfac, k_ew_gather, k_ew_force<true>, k_ew_zk, the k list) and pet_ewald_*, among
 // them the plan of both modes. The handle, k_ew_force and the local terms' kernels are in long_range.h, shared with p3m.hip.
 #include "long_range.h"
@@ -43,18 +47,25 @@ __global__ void k_ew_tables(const float* __restrict__ pos, const int* __restrict
     tab[idx] = out;
 }
 
+// DIR: the structure factor weighted by the direction U [N, 3], S'_{uX} = w sum_j (k.u_j) X_j e^{i k.r_j} (pet_ewald_second):
+// u of the chunk's 32 atoms is staged next to the tables, k is the row's
+template <bool DIR>
 __global__ __launch_bounds__(256) void k_ew_sfac(const int2* __restrict__ tiles, const EwSys* __restrict__ sys,
                                                  const EwK* __restrict__ klist, const float2* __restrict__ tab, int NM,
-                                                 const float* __restrict__ X, int C, float* __restrict__ S) {
+                                                 const float* __restrict__ X, int C, float* __restrict__ S,
+                                                 const float* __restrict__ U) {
     extern __shared__ float2 T[];
+    __shared__ float4 us[DIR ? 32 : 1];
     const int2 tile = tiles[blockIdx.x];
     const EwSys s = sys[tile.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, r = lane & 31;
     const int kidx = tile.y + r;
     int n0 = 0, n1 = 0, n2 = 0;
+    float kx = 0.f, ky = 0.f, kz = 0.f;
     if (kidx < s.n_k) {
         const EwK k = klist[s.first_k + kidx];
         n0 = k.n0; n1 = k.n1; n2 = k.n2;
+        if (DIR) { kx = k.kx; ky = k.ky; kz = k.kz; }
     }
     const int c0 = blockIdx.y * 256 + wave * 64;
     const bool active = c0 < C;
@@ -67,6 +78,14 @@ __global__ __launch_bounds__(256) void k_ew_sfac(const int2* __restrict__ tiles,
     for (int j0 = 0; j0 < s.n_atoms; j0 += 32) {
         __syncthreads();
         ew_stage_tables(T, tab, NM, s.first_atom + j0, s.n_atoms - j0);
+        if (DIR && threadIdx.x < 32) {
+            float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (j0 + (int)threadIdx.x < s.n_atoms) {
+                const float* p = U + 3 * (int64_t)(s.first_atom + j0 + threadIdx.x);
+                u = make_float4(p[0], p[1], p[2], 0.f);
+            }
+            us[threadIdx.x] = u;
+        }
         __syncthreads();
         if (!active) continue;
 #pragma unroll
@@ -76,6 +95,11 @@ __global__ __launch_bounds__(256) void k_ew_sfac(const int2* __restrict__ tiles,
             const int jj = 2 * s2 + half;
             float c, sn;
             ew_phase(T + jj * 3 * NM, NM, n0, n1, n2, c, sn);
+            if (DIR) {
+                const float4 u = us[jj];
+                const float ku = kx * u.x + ky * u.y + kz * u.z;
+                c *= ku; sn *= ku;
+            }
             const bool jin = j0 + jj < s.n_atoms;
             const float* row = X + (int64_t)(s.first_atom + j0 + jj) * C + c0 + r;
             const float b0 = jin && in0 ? row[0] : 0.f, b1 = jin && in1 ? row[32] : 0.f;
@@ -99,11 +123,17 @@ __global__ __launch_bounds__(256) void k_ew_sfac(const int2* __restrict__ tiles,
     }
 }
 
+// DIR: the directional derivative of the k-space sum along U [N, 3] (pet_ewald_second), ADDED to V with the prefactor:
+//   V[i][c] -= P sum_k [ (c Im S'_{uX} - s Re S'_{uX}) - (k.u_i) (c Im S'_X - s Re S'_X) ],  S = S'_X, Su = S'_{uX}:
+// the generated operand is (-s, c) against Su and -(k.u_i) (-s, c) against S, one contraction of twice the length
+template <bool DIR>
 __global__ __launch_bounds__(256) void k_ew_gather(const int2* __restrict__ tiles, const EwSys* __restrict__ sys,
                                                    const EwK* __restrict__ klist, const float2* __restrict__ tab, int NM,
-                                                   const float* __restrict__ S, int C, float* __restrict__ V) {
+                                                   const float* __restrict__ S, int C, float* __restrict__ V,
+                                                   const float* __restrict__ Su, const float* __restrict__ U) {
     extern __shared__ float2 T[];
     __shared__ int4 kn[32];
+    __shared__ float4 kv[DIR ? 32 : 1];
     const int2 tile = tiles[blockIdx.x];
     const EwSys s = sys[tile.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, r = lane & 31;
@@ -113,6 +143,11 @@ __global__ __launch_bounds__(256) void k_ew_gather(const int2* __restrict__ tile
     const bool active = c0 < C;
     const bool in0 = c0 + r < C, in1 = c0 + 32 + r < C;
     const float2* Tr = T + r * 3 * NM;
+    float3 ui = make_float3(0.f, 0.f, 0.f);
+    if (DIR && a0 + r < s.n_atoms) {
+        const float* p = U + 3 * (int64_t)(s.first_atom + a0 + r);
+        ui = make_float3(p[0], p[1], p[2]);
+    }
     // chunks of 32 k-vectors are summed on their own and then added to the totals; the plan lists a system's k-vectors by
     // descending |k|, so the small terms come first
     f32x16 v0, v1, t0, t1;
@@ -122,11 +157,14 @@ __global__ __launch_bounds__(256) void k_ew_gather(const int2* __restrict__ tile
         __syncthreads();
         if (threadIdx.x < 32) {
             int4 n = make_int4(0, 0, 0, 0);
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (k0 + (int)threadIdx.x < s.n_k) {
                 const EwK k = klist[s.first_k + k0 + threadIdx.x];
                 n = make_int4(k.n0, k.n1, k.n2, 1);
+                v = make_float4(k.kx, k.ky, k.kz, 0.f);
             }
             kn[threadIdx.x] = n;
+            if (DIR) kv[threadIdx.x] = v;
         }
         __syncthreads();
         if (!active) continue;
@@ -142,6 +180,23 @@ __global__ __launch_bounds__(256) void k_ew_gather(const int2* __restrict__ tile
             const bool kin = n.w != 0;
             const float br0 = kin && in0 ? row[0] : 0.f, bi0 = kin && in0 ? row[C] : 0.f;
             const float br1 = kin && in1 ? row[32] : 0.f, bi1 = kin && in1 ? row[C + 32] : 0.f;
+            if (DIR) {
+                const float* urow = Su + (int64_t)(s.first_k + k0 + kk) * 2 * C + c0 + r;
+                const float ur0 = kin && in0 ? urow[0] : 0.f, ui0 = kin && in0 ? urow[C] : 0.f;
+                const float ur1 = kin && in1 ? urow[32] : 0.f, ui1 = kin && in1 ? urow[C + 32] : 0.f;
+                const float4 k = kv[kk];
+                const float ku = k.x * ui.x + k.y * ui.y + k.z * ui.z;
+                const float pr = ku * sn, pi = -ku * c;
+                v0 = __builtin_amdgcn_mfma_f32_32x32x2f32(-sn, ur0, v0, 0, 0, 0);
+                v0 = __builtin_amdgcn_mfma_f32_32x32x2f32(c, ui0, v0, 0, 0, 0);
+                v0 = __builtin_amdgcn_mfma_f32_32x32x2f32(pr, br0, v0, 0, 0, 0);
+                v0 = __builtin_amdgcn_mfma_f32_32x32x2f32(pi, bi0, v0, 0, 0, 0);
+                v1 = __builtin_amdgcn_mfma_f32_32x32x2f32(-sn, ur1, v1, 0, 0, 0);
+                v1 = __builtin_amdgcn_mfma_f32_32x32x2f32(c, ui1, v1, 0, 0, 0);
+                v1 = __builtin_amdgcn_mfma_f32_32x32x2f32(pr, br1, v1, 0, 0, 0);
+                v1 = __builtin_amdgcn_mfma_f32_32x32x2f32(pi, bi1, v1, 0, 0, 0);
+                continue;
+            }
             v0 = __builtin_amdgcn_mfma_f32_32x32x2f32(c, br0, v0, 0, 0, 0);
             v0 = __builtin_amdgcn_mfma_f32_32x32x2f32(sn, bi0, v0, 0, 0, 0);
             v1 = __builtin_amdgcn_mfma_f32_32x32x2f32(c, br1, v1, 0, 0, 0);
@@ -155,6 +210,11 @@ __global__ __launch_bounds__(256) void k_ew_gather(const int2* __restrict__ tile
         const int a = a0 + (i & 3) + 8 * (i >> 2) + 4 * half;
         if (a >= s.n_atoms) continue;
         float* o = V + (int64_t)(s.first_atom + a) * C + c0 + r;
+        if (DIR) {
+            if (in0) o[0] -= (float)EW_PREFACTOR * t0[i];
+            if (in1) o[32] -= (float)EW_PREFACTOR * t1[i];
+            continue;
+        }
         if (in0) o[0] = t0[i];
         if (in1) o[32] = t1[i];
     }
@@ -181,6 +241,227 @@ __global__ __launch_bounds__(256) void k_ew_zk(const EwSys* __restrict__ sys, co
         const double co = EW_PREFACTOR * (double)z / (double)kk.w;
         kpart[9 * (int64_t)k + lane] = co * ((sigma * sigma + 2.0 / (double)kk.k2) * m * kv[cc] - s.inv[3 * cc + bb]);
     }
+}
+
+// The position Hessian of Phi = sum_c g^T A q applied to the direction U [N, 3] (pet_ewald_second), k-space (PER) / open
+// all-pairs part, in the form of k_ew_force: F[i] = P sum_col gen(i, col) . [product tiles], rows [g_i | q_i] over 2 C channels.
+// PER: four tiles per column tile of 32 k-vectors, against [Re S'_q | Re S'_g], [Im S'_q | Im S'_g] and the same of the
+// weighted structure factors S'_{uq} | S'_{ug}: gen = k [ (c Re_u + s Im_u) - (k.u_i) (c Re + s Im) ].
+// Open: one tile against [q_j | g_j], gen = -M_K (u_j - u_i), M_K = K'' n n^T + (K'/d) (I - n n^T), n = (r_j - r_i) / d.
+template <bool PER>
+__global__ __launch_bounds__(256) void k_ew_force2(const int2* __restrict__ tiles, const EwSys* __restrict__ sys,
+                                                   const EwK* __restrict__ klist, const float2* __restrict__ tab, int NM,
+                                                   const float* __restrict__ pos, float inv_R, const float* __restrict__ G,
+                                                   const float* __restrict__ Q, const float* __restrict__ Sq,
+                                                   const float* __restrict__ Sg, const float* __restrict__ Suq,
+                                                   const float* __restrict__ Sug, const float* __restrict__ U, int C, bool vec,
+                                                   float* __restrict__ F) {
+    extern __shared__ float2 T[];
+    __shared__ float4 ps[32];
+    __shared__ float4 us[32];
+    __shared__ float red[4 * 32 * 3];
+    const int2 tile = tiles[blockIdx.x];
+    const EwSys s = sys[tile.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, r = lane & 31;
+    const int a0 = tile.y;
+    if (PER) ew_stage_tables(T, tab, NM, s.first_atom + a0, s.n_atoms - a0);
+    if (threadIdx.x < 32) {
+        float4 p = make_float4(0.f, 0.f, 0.f, 0.f), u = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a0 + (int)threadIdx.x < s.n_atoms) {
+            const float* q = pos + 3 * (int64_t)(s.first_atom + a0 + threadIdx.x);
+            const float* v = U + 3 * (int64_t)(s.first_atom + a0 + threadIdx.x);
+            p = make_float4(q[0], q[1], q[2], 1.f);
+            u = make_float4(v[0], v[1], v[2], 0.f);
+        }
+        ps[threadIdx.x] = p;
+        us[threadIdx.x] = u;
+    }
+    __syncthreads();
+    const bool vi = a0 + r < s.n_atoms;
+    const float* gi = G + (int64_t)(s.first_atom + a0 + r) * C;
+    const float* qi = Q + (int64_t)(s.first_atom + a0 + r) * C;
+    const int ncols = PER ? s.n_k : s.n_atoms;
+    const int nsteps = (2 * C + 7) / 8;
+    float f[16][3];
+#pragma unroll
+    for (int i = 0; i < 16; i++) f[i][0] = f[i][1] = f[i][2] = 0.f;
+    for (int col0 = wave * 32; col0 < ncols; col0 += 128) {
+        const int col = col0 + r;
+        const bool vc = col < ncols;
+        f32x16 acc_r, acc_i, acu_r, acu_i;  // (open: acc_r alone)
+#pragma unroll
+        for (int i = 0; i < 16; i++) acc_r[i] = acc_i[i] = acu_r[i] = acu_i[i] = 0.f;
+        if (PER) {
+            const int64_t kabs = s.first_k + col;
+            const float *re1 = Sq + kabs * 2 * C, *re2 = Sg + kabs * 2 * C, *ur1 = Suq + kabs * 2 * C, *ur2 = Sug + kabs * 2 * C;
+            for (int t = 0; t < nsteps; t++) {
+                const int ch = 8 * t + 4 * half;
+                const f32x4 A = ew_load4(vi, gi, qi, ch, C, vec);
+                const f32x4 Br = ew_load4(vc, re1, re2, ch, C, vec), Bi = ew_load4(vc, re1 + C, re2 + C, ch, C, vec);
+                const f32x4 Ur = ew_load4(vc, ur1, ur2, ch, C, vec), Ui = ew_load4(vc, ur1 + C, ur2 + C, ch, C, vec);
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Br[u], acc_r, 0, 0, 0);
+                    acc_i = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Bi[u], acc_i, 0, 0, 0);
+                    acu_r = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Ur[u], acu_r, 0, 0, 0);
+                    acu_i = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Ui[u], acu_i, 0, 0, 0);
+                }
+            }
+            int n0 = 0, n1 = 0, n2 = 0;
+            float kx = 0.f, ky = 0.f, kz = 0.f;
+            if (vc) {
+                const EwK k = klist[s.first_k + col];
+                n0 = k.n0; n1 = k.n1; n2 = k.n2; kx = k.kx; ky = k.ky; kz = k.kz;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
+                float c, sn;
+                ew_phase(T + row * 3 * NM, NM, n0, n1, n2, c, sn);
+                const float4 u = us[row];
+                const float ku = kx * u.x + ky * u.y + kz * u.z;
+                const float x = (c * acu_r[i] + sn * acu_i[i]) - ku * (c * acc_r[i] + sn * acc_i[i]);
+                f[i][0] += kx * x; f[i][1] += ky * x; f[i][2] += kz * x;
+            }
+        } else {
+            const float* a1 = Q + (int64_t)(s.first_atom + col) * C;
+            const float* a2 = G + (int64_t)(s.first_atom + col) * C;
+            for (int t = 0; t < nsteps; t++) {
+                const int ch = 8 * t + 4 * half;
+                const f32x4 A = ew_load4(vi, gi, qi, ch, C, vec);
+                const f32x4 Ba = ew_load4(vc, a1, a2, ch, C, vec);
+#pragma unroll
+                for (int u = 0; u < 4; u++) acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Ba[u], acc_r, 0, 0, 0);
+            }
+            float3 pj = make_float3(0.f, 0.f, 0.f), uj = make_float3(0.f, 0.f, 0.f);
+            if (vc) {
+                const float* q = pos + 3 * (int64_t)(s.first_atom + col);
+                const float* v = U + 3 * (int64_t)(s.first_atom + col);
+                pj = make_float3(q[0], q[1], q[2]);
+                uj = make_float3(v[0], v[1], v[2]);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
+                const float4 pi = ps[row];
+                if (!vc || pi.w == 0.f || col == a0 + row) continue;
+                const float4 u = us[row];
+                const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+                const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+                const float nx = dx / d, ny = dy / d, nz = dz / d;
+                const float ex = uj.x - u.x, ey = uj.y - u.y, ez = uj.z - u.z;
+                const float nd = nx * ex + ny * ey + nz * ez;
+                const float kd = ew_open_kernel_d(d, inv_R) / d, kdd = ew_open_kernel_dd(d, inv_R);
+                const float along = (kdd - kd) * nd;  // M_K e = (K'' - K'/d) (n.e) n + (K'/d) e
+                f[i][0] -= acc_r[i] * (along * nx + kd * ex);
+                f[i][1] -= acc_r[i] * (along * ny + kd * ey);
+                f[i][2] -= acc_r[i] * (along * nz + kd * ez);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            float v = f[i][a];
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            if (r == 0) red[(wave * 32 + row) * 3 + a] = v;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 96) {
+        const int row = threadIdx.x / 3, a = threadIdx.x % 3;
+        if (a0 + row < s.n_atoms) {
+            float v = red[row * 3 + a];
+            for (int w = 1; w < 4; w++) v += red[(w * 32 + row) * 3 + a];
+            F[3 * (int64_t)(s.first_atom + a0 + row) + a] = (float)EW_PREFACTOR * v;
+        }
+    }
+}
+
+// The exclusion rows' share of all three results of pet_ewald_second, one wave per atom, fp64 like k_ew_edge_bwd. Per edge
+// p = (i -> j, S) with e = u_j - u_i, n = D / d:  out_g[i] -= P w'(d) (n.e) q_j,  out_q[i] -= P w'(d) (n.e) g_j  and
+// out_r[i] += P (B_p + B'_p) M_w e,  M_w = w'' n n^T + (w'/d) (I - n n^T). Lanes take one edge each of a chunk of 64 for w', w''
+// and M_w e, then all lanes walk the chunk's edges for the channel sums. Adds F2 (k_ew_force2) into out_r for every atom.
+__global__ __launch_bounds__(64) void k_ew_edge_second(const EwSys* __restrict__ sys, const int* __restrict__ gsys,
+                                                       const int* __restrict__ rowptr, const int* __restrict__ nbr,
+                                                       const float4* __restrict__ geo, const float* __restrict__ G,
+                                                       const float* __restrict__ Q, const float* __restrict__ U,
+                                                       const float* __restrict__ F2, int C, double sigma, double Rcut,
+                                                       float* __restrict__ out_g, float* __restrict__ out_q,
+                                                       float* __restrict__ out_r) {
+    __shared__ int sj[64];
+    __shared__ double sco[64], sm[64][3];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const EwSys& s = sys[gsys[i]];
+    double fp[3] = {0.0, 0.0, 0.0};
+    if (s.periodic) {
+        const double inv_a = 1.0 / (sqrt(2.0) * sigma);
+        const float* gi = G + (int64_t)i * C;
+        const float* qi = Q + (int64_t)i * C;
+        const double ui[3] = {(double)U[3 * (int64_t)i], (double)U[3 * (int64_t)i + 1], (double)U[3 * (int64_t)i + 2]};
+        const int p1 = rowptr[i + 1];
+        for (int p0 = rowptr[i]; p0 < p1; p0 += 64) {
+            __syncthreads();
+            const int p = p0 + lane;
+            int j = i;
+            double co = 0.0, m[3] = {0.0, 0.0, 0.0};
+            if (p < p1) {
+                j = nbr[p];
+                const float4 g4 = geo[p];
+                const double d = (double)g4.w;
+                if (d < Rcut && j != i) {
+                    const double x = d * inv_a, er = erf(x), der = 2.0 / sqrt(EW_PI) * inv_a * exp(-x * x), dder = -2.0 * x * inv_a * der;
+                    const double cutf = 0.5 * (1.0 + cos(EW_PI * d / Rcut)), dcut = -0.5 * EW_PI / Rcut * sin(EW_PI * d / Rcut);
+                    const double ddcut = -0.5 * (EW_PI / Rcut) * (EW_PI / Rcut) * cos(EW_PI * d / Rcut);
+                    const double n0 = er * cutf, n1 = der * cutf + er * dcut, n2 = dder * cutf + 2.0 * der * dcut + er * ddcut;
+                    const double dw = n1 / d - n0 / (d * d), ddw = n2 / d - 2.0 * n1 / (d * d) + 2.0 * n0 / (d * d * d);
+                    const double n[3] = {(double)g4.x / d, (double)g4.y / d, (double)g4.z / d};
+                    double e[3], nd = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 3; a++) {
+                        e[a] = (double)U[3 * (int64_t)j + a] - ui[a];
+                        nd += n[a] * e[a];
+                    }
+                    co = -EW_PREFACTOR * dw * nd;
+#pragma unroll
+                    for (int a = 0; a < 3; a++) m[a] = EW_PREFACTOR * ((ddw - dw / d) * nd * n[a] + dw / d * e[a]);
+                }
+            }
+            sj[lane] = j;
+            sco[lane] = co;
+            sm[lane][0] = m[0]; sm[lane][1] = m[1]; sm[lane][2] = m[2];
+            __syncthreads();
+            const int ne = min(64, p1 - p0);
+            for (int q = 0; q < ne; q++) {
+                const int jq = sj[q];
+                if (jq == i) continue;
+                const float* gj = G + (int64_t)jq * C;
+                const float* qj = Q + (int64_t)jq * C;
+                float b = 0.f, bp = 0.f;
+                for (int c = lane; c < C; c += 64) {
+                    b += gi[c] * qj[c];
+                    bp += gj[c] * qi[c];
+                }
+                const double bb = (double)wsum(b) + (double)wsum(bp);
+#pragma unroll
+                for (int a = 0; a < 3; a++) fp[a] += bb * sm[q][a];
+            }
+            for (int c = lane; c < C; c += 64) {
+                double ag = 0.0, aq = 0.0;
+                for (int q = 0; q < ne; q++) {
+                    const int64_t o = (int64_t)sj[q] * C + c;
+                    ag += sco[q] * (double)Q[o];
+                    aq += sco[q] * (double)G[o];
+                }
+                out_g[(int64_t)i * C + c] += (float)ag;
+                out_q[(int64_t)i * C + c] += (float)aq;
+            }
+        }
+    }
+    if (lane < 3) out_r[3 * (int64_t)i + lane] += (float)((double)F2[3 * (int64_t)i + lane] + fp[lane]);
 }
 
 // the largest reciprocal index along every axis of a cell inside |k| <= 2 pi / lambda; false where one is beyond 1e6
@@ -314,11 +595,28 @@ int ew_apply(const pet_ewald_t* e, const Graph& g, const float* pos, const float
     const unsigned cy = (unsigned)cdiv(C, 256);
     const size_t lds = ew_table_lds(e);
     if (!e->ktiles.empty())
-        k_ew_sfac<<<dim3((unsigned)e->ktiles.size(), cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, X, C, Sbuf);
+        k_ew_sfac<false><<<dim3((unsigned)e->ktiles.size(), cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, X, C,
+                                                                                 Sbuf, nullptr);
     if (!e->atiles_p.empty())
-        k_ew_gather<<<dim3((unsigned)e->atiles_p.size(), cy), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, Sbuf,
-                                                                            C, out);
+        k_ew_gather<false><<<dim3((unsigned)e->atiles_p.size(), cy), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm,
+                                                                                   Sbuf, C, out, nullptr, nullptr);
     return ew_local_forward(e, g, pos, X, C, out, sums, st);
+}
+
+// the workspace of pet_ewald_second: that of the other entry points, then S'(u_q) and the two weighted structure factors
+struct EwWs2 {
+    EwWs w;
+    float *S3, *Su1, *Su2;
+};
+
+size_t ew_carve2(const pet_ewald_t* e, int64_t C, void* base, EwWs2& w2) {
+    Carver c(base);
+    c.off = ew_carve(e, C, base, w2.w);
+    const size_t K = (size_t)std::max<int64_t>(e->n_k, 1);
+    w2.S3 = c.take<float>(K * 2 * C);
+    w2.Su1 = c.take<float>(K * 2 * C);
+    w2.Su2 = c.take<float>(K * 2 * C);
+    return c.off;
 }
 
 }  // namespace
@@ -453,8 +751,8 @@ int pet_ewald_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float*
     const unsigned cy = (unsigned)cdiv(C, 256);
     const size_t lds = ew_table_lds(e);
     if (!e->ktiles.empty())
-        k_ew_sfac<<<dim3((unsigned)e->ktiles.size(), cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, d_charges,
-                                                                          C, w.S1);
+        k_ew_sfac<false><<<dim3((unsigned)e->ktiles.size(), cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm,
+                                                                                 d_charges, C, w.S1, nullptr);
     k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_charges, C, w.loc.sum_q);
     if (!e->atiles_p.empty())
         k_ew_force<true><<<(unsigned)e->atiles_p.size(), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, d_positions,
@@ -464,6 +762,82 @@ int pet_ewald_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float*
         if (e->n_k > 0)
             k_ew_zk<<<cdiv(e->n_k, 4), 256, 0, st>>>(e->d_sys, e->d_ksys, e->d_k, w.S1, w.S2, C, (int)e->n_k, e->sigma, w.loc.kpart);
     });
+}
+
+int64_t pet_ewald_second_workspace_bytes(const pet_ewald_t* e, int64_t n_channels) {
+    if (!e || !e->planned || e->p3m_nodes || n_channels < 1) return -1;
+    EwWs2 w;
+    return (int64_t)ew_carve2(e, n_channels, nullptr, w);
+}
+
+int pet_ewald_second(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
+                     const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions, int32_t C,
+                     float* d_out_charges, float* d_out_grad_potential, float* d_out_positions, void* d_workspace,
+                     int64_t workspace_bytes, void* stream) {
+    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(e->p3m_nodes == 0, PET_ERR_ARGUMENT,
+                "pet_ewald_second on a P3M-mode handle (pet_ewald_set_p3m): second derivatives through P3M are not built (the "
+                "reference trains with Ewald summation)");
+    if (int rc = ew_check(e, pg, C, d_workspace, workspace_bytes)) return rc;
+    PET_REQUIRE(d_u_charges || d_u_positions, PET_ERR_ARGUMENT, "d_u_charges and d_u_positions are both NULL");
+    if (e->n_atoms == 0) return PET_OK;
+    EwWs2 w2;
+    PET_REQUIRE(d_workspace && workspace_bytes >= (int64_t)ew_carve2(e, C, nullptr, w2), PET_ERR_ARGUMENT,
+                "Ewald workspace too small (pet_ewald_second_workspace_bytes)");
+    PET_REQUIRE(d_positions && d_charges && d_grad_potential && d_out_charges && d_out_grad_potential && d_out_positions,
+                PET_ERR_ARGUMENT, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const Graph& g = pg->g;
+    ew_carve2(e, C, d_workspace, w2);
+    const EwWs& w = w2.w;
+    const float *Q = d_charges, *G = d_grad_potential, *Uq = d_u_charges, *Ur = d_u_positions;
+    const int64_t N = e->n_atoms;
+    const unsigned cy = (unsigned)cdiv(C, 256), nk = (unsigned)e->ktiles.size(), np = (unsigned)e->atiles_p.size(),
+                   nn = (unsigned)e->atiles_n.size();
+    const size_t lds = ew_table_lds(e);
+    const float inv_R = (float)(1.0 / e->cutoff);
+    ProfScope ps("ewald_second", st, 0.0, 0.0);
+    PET_TRY(ew_tables(e, g, d_positions, w, st));
+    // S'(g) serves both halves
+    if (nk) k_ew_sfac<false><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, G, C, w.S2, nullptr);
+    if (Uq) {
+        // out_g = A u_q (leaves S'(u_q) in S3), out_r = grad_r Phi(r; u_q, g): the first-order adjoint with (g, q) := (u_q, g)
+        PET_TRY(ew_apply(e, g, d_positions, Uq, C, d_out_grad_potential, w, w2.S3, w.loc.sum_g, st));
+        if (np)
+            k_ew_force<true><<<np, 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, d_positions, inv_R, Uq, G, w.S2,
+                                                   w2.S3, C, ew_vec_loads(C, G, Uq), w.loc.F);
+        PET_TRY(ew_local_backward(e, g, d_positions, G, Uq, C, w.loc, d_out_positions, nullptr, st, [] {}));
+    } else {
+        PET_HIP_CHECK(hipMemsetAsync(d_out_grad_potential, 0, (size_t)N * C * sizeof(float), st));
+        PET_HIP_CHECK(hipMemsetAsync(d_out_positions, 0, (size_t)N * 3 * sizeof(float), st));
+    }
+    PET_HIP_CHECK(hipMemsetAsync(d_out_charges, 0, (size_t)N * C * sizeof(float), st));
+    if (Ur) {
+        // out_g += (D_u A) q, out_q = (D_u A) g, out_r += H u_r: k-space and open parts, then the exclusion rows
+        if (nk) {
+            k_ew_sfac<false><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Q, C, w.S1, nullptr);
+            k_ew_sfac<true><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Q, C, w2.Su1, Ur);
+            k_ew_sfac<true><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, G, C, w2.Su2, Ur);
+        }
+        if (np) {
+            k_ew_gather<true><<<dim3(np, cy), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, w.S1, C,
+                                                              d_out_grad_potential, w2.Su1, Ur);
+            k_ew_gather<true><<<dim3(np, cy), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, w.S2, C, d_out_charges,
+                                                              w2.Su2, Ur);
+            k_ew_force2<true><<<np, 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, d_positions, inv_R, G, Q, w.S1, w.S2,
+                                                    w2.Su1, w2.Su2, Ur, C, ew_vec_loads(C, Q, G), w.loc.F);
+        }
+        if (nn) {
+            k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, d_positions, inv_R, Q, C, d_out_grad_potential, Ur);
+            k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, d_positions, inv_R, G, C, d_out_charges, Ur);
+            k_ew_force2<false><<<nn, 256, 0, st>>>(e->d_atiles_n, e->d_sys, nullptr, nullptr, 1, d_positions, inv_R, G, Q, nullptr,
+                                                   nullptr, nullptr, nullptr, Ur, C, ew_vec_loads(C, Q, G), w.loc.F);
+        }
+        k_ew_edge_second<<<(unsigned)N, 64, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.geo, G, Q, Ur, w.loc.F, C, e->sigma, e->cutoff,
+                                                     d_out_grad_potential, d_out_charges, d_out_positions);
+    }
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
 }
 
 }  // extern "C"

@@ -4,6 +4,8 @@
 // sum) with their adjoints: kernels and the two host functions that launch them. The operator's convention constants
 // (include/pet_hip.h) are EW_PREFACTOR and the three coefficients of ew_local_forward; a mode adds only
 // its weight 2 G(k) / Omega (ewald.hip: ew_plan_klist) or G^(n) / Omega (p3m.hip: p3m_influence_point).
+// k_ew_pairs<true> and ew_open_kernel_dd serve the Ewald mode's second derivatives (ewald.hip: pet_ewald_second); P3M mode
+// instantiates k_ew_pairs<false> alone.
 // Kernels and functions have internal linkage: each translation unit is compiled on its own (build.py: NO_RDC) with its own
 // copy of what it launches. Only the two record types and the P3M plan's entry points have names that cross objects.
 #pragma once
@@ -88,10 +90,23 @@ __device__ __forceinline__ float ew_open_kernel_d(float d, float inv_R) {
     return (0.5f * (float)EW_PI * inv_R * sinpif(d * inv_R) - sn * sn / d) / d;
 }
 
+// K''(d), with A = sin^2(pi d / 2R): K = A / d, K'' = A''/d - 2 A'/d^2 + 2 A/d^3 (f = 0 beyond R: f'' jumps there)
+__device__ __forceinline__ float ew_open_kernel_dd(float d, float inv_R) {
+    if (d * inv_R >= 1.f) return 2.f / (d * d * d);
+    const float sn = sinpif(0.5f * d * inv_R);
+    const float a1 = 0.5f * (float)EW_PI * inv_R * sinpif(d * inv_R);
+    const float a2 = 0.5f * (float)(EW_PI * EW_PI) * inv_R * inv_R * cospif(d * inv_R);
+    return (a2 - 2.f * (a1 - sn * sn / d) / d) / d;
+}
+
+// DIR: the directional derivative along U [N, 3] in place of the sum itself, V[i][c] += P sum_{j != i} K'(d) (n . (u_j - u_i))
+// X[j][c] with n = (r_j - r_i) / d, ADDED to V (pet_ewald_second)
+template <bool DIR>
 __global__ __launch_bounds__(256) void k_ew_pairs(const int2* __restrict__ tiles, const EwSys* __restrict__ sys,
                                                   const float* __restrict__ pos, float inv_R, const float* __restrict__ X,
-                                                  int C, float* __restrict__ V) {
+                                                  int C, float* __restrict__ V, const float* __restrict__ U) {
     __shared__ float4 ps[32];
+    __shared__ float4 us[DIR ? 32 : 1];
     const int2 tile = tiles[blockIdx.x];
     const EwSys s = sys[tile.x];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, r = lane & 31;
@@ -101,6 +116,11 @@ __global__ __launch_bounds__(256) void k_ew_pairs(const int2* __restrict__ tiles
     if (i < s.n_atoms) {
         const float* p = pos + 3 * (int64_t)(s.first_atom + i);
         ri = make_float3(p[0], p[1], p[2]);
+    }
+    float3 ui = make_float3(0.f, 0.f, 0.f);
+    if (DIR && i < s.n_atoms) {
+        const float* p = U + 3 * (int64_t)(s.first_atom + i);
+        ui = make_float3(p[0], p[1], p[2]);
     }
     const int c0 = blockIdx.y * 256 + wave * 64;
     const bool active = c0 < C;
@@ -118,6 +138,15 @@ __global__ __launch_bounds__(256) void k_ew_pairs(const int2* __restrict__ tiles
             }
             ps[threadIdx.x] = p;
         }
+        if (DIR && threadIdx.x >= 64 && threadIdx.x < 96) {
+            const int jj = threadIdx.x - 64;
+            float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (j0 + jj < s.n_atoms) {
+                const float* q = U + 3 * (int64_t)(s.first_atom + j0 + jj);
+                u = make_float4(q[0], q[1], q[2], 0.f);
+            }
+            us[jj] = u;
+        }
         __syncthreads();
         if (!active) continue;
 #pragma unroll
@@ -128,7 +157,16 @@ __global__ __launch_bounds__(256) void k_ew_pairs(const int2* __restrict__ tiles
             const float4 pj = ps[jj];
             const float dx = pj.x - ri.x, dy = pj.y - ri.y, dz = pj.z - ri.z;
             const bool pair = pj.w != 0.f && i < s.n_atoms && j0 + jj != i;
-            const float kern = pair ? ew_open_kernel(sqrtf(dx * dx + dy * dy + dz * dz), inv_R) : 0.f;
+            float kern = 0.f;
+            if (DIR) {
+                if (pair) {
+                    const float4 uj = us[jj];
+                    const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+                    kern = ew_open_kernel_d(d, inv_R) * (dx * (uj.x - ui.x) + dy * (uj.y - ui.y) + dz * (uj.z - ui.z)) / d;
+                }
+            } else {
+                kern = pair ? ew_open_kernel(sqrtf(dx * dx + dy * dy + dz * dz), inv_R) : 0.f;
+            }
             const float* row = X + (int64_t)(s.first_atom + j0 + jj) * C + c0 + r;
             const bool jin = pj.w != 0.f;
             const float b0 = jin && in0 ? row[0] : 0.f, b1 = jin && in1 ? row[32] : 0.f;
@@ -143,8 +181,13 @@ __global__ __launch_bounds__(256) void k_ew_pairs(const int2* __restrict__ tiles
         const int a = a0 + (q & 3) + 8 * (q >> 2) + 4 * half;
         if (a >= s.n_atoms) continue;
         float* o = V + (int64_t)(s.first_atom + a) * C + c0 + r;
-        if (in0) o[0] = (float)EW_PREFACTOR * t0[q];
-        if (in1) o[32] = (float)EW_PREFACTOR * t1[q];
+        if (DIR) {
+            if (in0) o[0] += (float)EW_PREFACTOR * t0[q];
+            if (in1) o[32] += (float)EW_PREFACTOR * t1[q];
+        } else {
+            if (in0) o[0] = (float)EW_PREFACTOR * t0[q];
+            if (in1) o[32] = (float)EW_PREFACTOR * t1[q];
+        }
     }
 }
 
@@ -492,8 +535,8 @@ int ew_local_forward(const pet_ewald_t* e, const Graph& g, const float* pos, con
                      hipStream_t st) {
     const unsigned cy = (unsigned)cdiv(C, 256);
     if (!e->atiles_n.empty())
-        k_ew_pairs<<<dim3((unsigned)e->atiles_n.size(), cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, (float)(1.0 / e->cutoff),
-                                                                          X, C, out);
+        k_ew_pairs<false><<<dim3((unsigned)e->atiles_n.size(), cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos,
+                                                                                 (float)(1.0 / e->cutoff), X, C, out, nullptr);
     k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, X, C, sums);
     k_ew_finish<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.geo, X, sums, (int)e->n_atoms, C,
                                                      (float)(std::sqrt(2.0 / EW_PI) / e->sigma),

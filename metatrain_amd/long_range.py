@@ -21,6 +21,13 @@ the weight ``pet_ewald_plan`` gives every k-vector (``csrc/ewald.hip``).
 as fp32 matrix-core GEMMs with a generated operand; fixed summation orders, no atomics), :class:`LongRangeFeaturizerHip` the
 featuriser under the reference's state-dict keys, :func:`energy_and_gradient` the whole model: energies, dE/dR and dE/dcell.
 
+Second derivatives are built at the OPERATOR level for the Ewald sum: :meth:`EwaldHip.second`
+(``pet_ewald_second``) differentiates the adjoint -- ``dL/dq`` and ``dL/dR`` -- with respect to charges, ``dL/dV`` and positions,
+and torch double backward (``create_graph=True``) through :class:`LongRangeFeaturizerHip` runs on it, which is what a force loss
+and a Hessian-vector product need from the operator. Not built, each raising by name: cell tangents and cell results of that
+operation (cells that require grad in a double backward), second derivatives through P3M (the reference trains with Ewald
+summation), and the model-level training step and ``pet_hessian_vector`` of a long-range model.
+
 The reference takes its Ewald branch only under ``use_ewald and training`` (``utils/long_range.py:153-170``): it EVALUATES every
 periodic long-range model with P3M. :class:`P3MHip` is that operator (``csrc/p3m.hip``: binning, spread, filter, gather and the
 adjoints as HIP kernels in stages around ``torch.fft.rfftn`` / ``irfftn``), fixed by definition like the Ewald one
@@ -182,6 +189,7 @@ class EwaldHip:
                             "sphere here, the box of a mesh in torch-pme), which is not pinned")
         self.n_systems = -1
         self._workspace: Optional[torch.Tensor] = None
+        self._second_workspaces: Dict[int, torch.Tensor] = {}  # by channel count (``second``)
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -210,6 +218,7 @@ class EwaldHip:
         check(self.lib.pet_ewald_plan(self._handle, h_cells, h_pbc, h_first, n_sys))
         self.n_systems = n_sys
         self._workspace = None
+        self._second_workspaces = {}
         return self
 
     def num_kvectors(self, system: int) -> int:
@@ -253,6 +262,31 @@ class EwaldHip:
                                           rt._ptr(gq), rt._ptr(gpos), rt._ptr(gcell), rt._ptr(ws), ws.numel(), rt._stream()))
         return (gq, gpos, gcell) if want_cell_grad else (gq, gpos)
 
+    def second(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor, grad_potential: torch.Tensor,
+               u_charges: Optional[torch.Tensor] = None, u_positions: Optional[torch.Tensor] = None):
+        """The derivative of the adjoint (``pet_ewald_second``): for cotangents ``u_charges [N, C]`` of ``dL/dq`` and
+        ``u_positions [N, 3]`` of ``dL/dR`` as :meth:`backward` returns them, the gradient of
+        ``<u_charges, dL/dq> + <u_positions, dL/dR>`` with respect to ``(charges, grad_potential, positions)``:
+        ``(out_charges [N, C], out_grad_potential [N, C], out_positions [N, 3])``. Either cotangent may be ``None`` (zero; its
+        work is skipped), not both. No cell tangent is taken and no cell result returned."""
+        if u_charges is None and u_positions is None:
+            raise PetHipError("second: u_charges and u_positions are both None")
+        rt._require_cuda(*[t for t in (u_charges, u_positions) if t is not None])
+        pos, q, g = self._inputs(positions, charges, grad_potential)
+        uq = None if u_charges is None else u_charges.detach().to(torch.float32).reshape(q.shape).contiguous()
+        ur = None if u_positions is None else u_positions.detach().to(torch.float32).reshape(pos.shape).contiguous()
+        C = int(q.shape[1])
+        nbytes = int(self.lib.pet_ewald_second_workspace_bytes(self._handle, C))
+        if nbytes < 0:
+            raise PetHipError("pet_ewald_second_workspace_bytes failed: call plan() first")
+        ws = self._second_workspaces.get(C)
+        if ws is None or ws.numel() < nbytes or ws.device != q.device:
+            ws = self._second_workspaces[C] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=q.device)
+        out_q, out_g, out_r = torch.empty_like(q), torch.empty_like(q), torch.empty_like(pos)
+        check(self.lib.pet_ewald_second(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), rt._ptr(g), rt._ptr(uq), rt._ptr(ur),
+                                        C, rt._ptr(out_q), rt._ptr(out_g), rt._ptr(out_r), rt._ptr(ws), ws.numel(), rt._stream()))
+        return out_q, out_g, out_r
+
 
 class P3MHip(EwaldHip):
     """The same operator with the reciprocal-space sum on a mesh (a ``pet_ewald_t`` after ``pet_ewald_set_p3m``): ``plan``,
@@ -295,6 +329,11 @@ class P3MHip(EwaldHip):
         out = (c_int32 * 3)()
         check(self.lib.pet_p3m_mesh_shape(self._handle, int(system), out))
         return [int(x) for x in out]
+
+    def second(self, *args, **kwargs):
+        raise PetHipError("second derivatives through P3M are not built: the reference trains long-range models with Ewald "
+                          "summation and evaluates them with P3M; use EwaldHip (method='ewald') for training and "
+                          "Hessian-vector products")
 
     def _mesh_potential(self, graph, pos, x, ws, keep_spectrum: bool = False):
         """spread -> rfftn -> filter -> irfftn of ``x [N, C]``: the mesh potential (packed, channel-first) and, on request, the
@@ -349,21 +388,51 @@ class P3MHip(EwaldHip):
         return (gq, gpos, gcell) if want_cell_grad else (gq, gpos)
 
 
+_MIXED_SECOND = ("mixed position / cell second derivatives of the long-range operator are not built: the second-order "
+                 "operation (pet_ewald_second) takes no cell tangent and returns no cell result (a stress loss needs them); "
+                 "differentiate the first-order gradients with respect to charges, dL/dV and positions only, with cells that "
+                 "do not require grad")
+
+
+class _EwaldAdjointFn(torch.autograd.Function):
+    """The operator's adjoint as an autograd node of its own: ``forward`` is the first-order ``backward`` call, ``backward`` the
+    second-order operation (:meth:`EwaldHip.second`), with respect to charges, positions and the incoming gradient."""
+
+    @staticmethod
+    def forward(ctx, charges, positions, cells, grad, ewald, graph):
+        ctx.set_materialize_grads(False)
+        ctx.ewald, ctx.graph = ewald, graph
+        ctx.save_for_backward(charges, positions, grad)
+        gq, gpos, gcell = ewald.backward(graph, positions, charges, grad, want_cell_grad=True)
+        return gq, gpos, gcell.reshape(cells.shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable  # (third derivatives are not built)
+    def backward(ctx, u_charges, u_positions, u_cells):
+        if u_cells is not None or ctx.needs_input_grad[2]:
+            raise PetHipError(_MIXED_SECOND)
+        if u_charges is None and u_positions is None:
+            return None, None, None, None, None, None
+        charges, positions, grad = ctx.saved_tensors
+        out_q, out_g, out_r = ctx.ewald.second(ctx.graph, positions, charges, grad, u_charges, u_positions)
+        return out_q, out_r, None, out_g, None, None
+
+
 class _EwaldFn(torch.autograd.Function):
-    """The operator as an autograd node over the two HIP calls: gradients for charges, positions and cells."""
+    """The operator as an autograd node over the HIP calls: gradients for charges, positions and cells, and (Ewald only, no
+    cells) their derivatives once more under ``create_graph`` through :class:`_EwaldAdjointFn`."""
 
     @staticmethod
     def forward(ctx, charges, positions, cells, ewald, graph):
         ctx.ewald, ctx.graph = ewald, graph
-        ctx.save_for_backward(charges, positions)
-        ctx.cell_shape = cells.shape
+        ctx.save_for_backward(charges, positions, cells)
         return ewald.potential(graph, positions, charges)
 
     @staticmethod
     def backward(ctx, grad):
-        charges, positions = ctx.saved_tensors
-        gq, gpos, gcell = ctx.ewald.backward(ctx.graph, positions, charges, grad, want_cell_grad=True)
-        return gq, gpos, gcell.reshape(ctx.cell_shape), None, None
+        charges, positions, cells = ctx.saved_tensors
+        gq, gpos, gcell = _EwaldAdjointFn.apply(charges, positions, cells, grad, ctx.ewald, ctx.graph)
+        return gq, gpos, gcell, None, None
 
 
 class LongRangeFeaturizerHip:
@@ -421,7 +490,9 @@ class LongRangeFeaturizerHip:
 
     def __call__(self, features: torch.Tensor, positions: torch.Tensor, cells: torch.Tensor, graph: rt.HipGraph):
         """``out_projection(potential(charges_map(features)))`` ``[N, d_node]``, differentiable by torch autograd with
-        respect to ``features``, ``positions`` and ``cells``."""
+        respect to ``features``, ``positions`` and ``cells``, and with the Ewald operator twice (``create_graph=True``) with
+        respect to ``features``, ``positions`` and the six parameter tensors once a caller sets ``requires_grad_`` on them;
+        a P3M featuriser and cells that require grad are refused there."""
         rt._require_cuda(features, positions)
         p = self.params
         q = torch.nn.functional.linear(features, p["charges_map.weight"], p["charges_map.bias"])

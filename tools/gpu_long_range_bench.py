@@ -2,6 +2,9 @@
 256, next to the same box without long range. A record, not a gate: writes ``profiles/long_range_bench.json``.
 
     python tools/gpu_long_range_bench.py [--atoms 1000] [--repeats 10] [--out profiles/long_range_bench.json]
+
+``--leg second`` times the operator's second-order call (``EwaldHip.second``) next to its first-order adjoint (``backward``
+without cell gradients) on the same box in one process, alternating the two, and writes ``profiles/long_range_second_bench.json``.
 """
 import argparse
 import json
@@ -35,12 +38,64 @@ def timed(fn, repeats):
     return out
 
 
+def second_leg(args):
+    """``second`` (both cotangents) against ``backward`` on the box at C = d_node: samples of ``--calls`` calls each, the two
+    alternating, after a warm-up of both."""
+    dev = torch.device("cuda:0")
+    hypers = default_hypers()
+    hypers["long_range"] = {"enable": True, "use_ewald": True, "smearing": 1.4, "kspace_resolution": 1.33, "interpolation_nodes": 5}
+    pos, z, cell = synthetic.random_box(args.atoms, seed=11)
+    n, c = args.atoms, hypers["d_node"]
+    model = rt.HipModel(hypers, TYPES)
+    model.load_species_table()
+    pairs, _ = rt.neighbor_list(pos.to(dev), cell, [True] * 3, hypers["cutoff"])
+    graph = rt.HipGraph(model, pos.to(dev), cell[None].to(dev), pairs[:, 0], pairs[:, 1], pairs[:, 2:5], z.to(dev),
+                        torch.zeros(n, dtype=torch.int32, device=dev))
+    ew = lr.EwaldHip(1.4, 1.33, hypers["cutoff"]).plan(cell[None], [[True] * 3], [0, n])
+    gen = torch.Generator(device=dev).manual_seed(0)
+    q, g, uq = (torch.randn(n, c, device=dev, generator=gen) for _ in range(3))
+    ur = torch.randn(n, 3, device=dev, generator=gen)
+    p32 = pos.to(dev)
+    legs = {"backward": lambda: ew.backward(graph, p32, q, g), "second": lambda: ew.second(graph, p32, q, g, uq, ur),
+            "second_u_positions_only": lambda: ew.second(graph, p32, q, g, None, ur),
+            "second_u_charges_only": lambda: ew.second(graph, p32, q, g, uq, None)}
+    for fn in legs.values():
+        fn()
+    torch.cuda.synchronize()
+    samples = {k: [] for k in legs}
+    for _ in range(args.repeats):
+        for name, fn in legs.items():
+            t0 = time.perf_counter()
+            for _ in range(args.calls):
+                fn()
+            torch.cuda.synchronize()
+            samples[name].append(1e3 * (time.perf_counter() - t0) / args.calls)
+    med = {k: statistics.median(v) for k, v in samples.items()}
+    result = {"workload": f"{n}-atom synthetic periodic box, C = {c}, {ew.num_kvectors(0)} k-vectors, {graph.n_edges} edges; ms per "
+                          f"call on the host clock around {args.calls} calls and a synchronise, median of {args.repeats} samples, "
+                          "the legs alternating, after one warm-up call each",
+              "atoms": n, "channels": c, "kvectors": ew.num_kvectors(0), "graph_edges": graph.n_edges, "ms": samples,
+              "ms_median": med, "ms_min": {k: min(v) for k, v in samples.items()}, "ms_max": {k: max(v) for k, v in samples.items()},
+              "second_over_backward": med["second"] / med["backward"],
+              "gemm_count": {"second": {"structure_factors": 5, "gathers": 3, "force_type_products": 3},
+                             "backward": {"structure_factors": 2, "gathers": 1, "force_type_products": 1}}}
+    os.makedirs(os.path.dirname(args.second_out), exist_ok=True)
+    with open(args.second_out, "w") as fh:
+        json.dump(result, fh)
+    print(json.dumps({k: v for k, v in result.items() if k != "ms"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--atoms", type=int, default=1000)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "long_range_bench.json"))
+    ap.add_argument("--leg", choices=("model", "second"), default="model")
+    ap.add_argument("--calls", type=int, default=20, help="calls per timed sample of --leg second")
+    ap.add_argument("--second-out", default=os.path.join(ROOT, "profiles", "long_range_second_bench.json"))
     args = ap.parse_args()
+    if args.leg == "second":
+        return second_leg(args)
     dev = torch.device("cuda:0")
     pos, z, cell = synthetic.random_box(args.atoms, seed=11)
     n = args.atoms

@@ -627,6 +627,38 @@ int pet_ewald_second(const pet_ewald_t* e, const pet_graph_t* g, const float* d_
                      int32_t n_channels, float* d_out_charges, float* d_out_grad_potential, float* d_out_positions,
                      void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- Long-range PET: the force-loss training sweep and Hessian-vector products -----------------------
+ * The long-range forms of pet_backward_train2 and pet_hessian_vector for a long_range.enable model: the size-generic dual
+ * pass (for EVERY model size, the default included, as pet_hessian_vector) with the featuriser between the backbone and the
+ * heads,  x = sum_l h_l / sqrt(L),  q = charges_map(x),  V = A(r) q,  y = out_projection(V),  m_l = (h_l + y) / sqrt(2),  the
+ * node heads reading m_l. `e` is a planned Ewald-mode handle for the batch of `g`; d_positions [N,3] the positions the graph
+ * was built from. The six featuriser tensors are read from the MODEL's parameter table, under the reference's keys
+ * long_range_featurizer.{charges_map,out_projection.0,out_projection.2}.{weight,bias} (pet_model_set_param; each d_node x
+ * d_node / d_node), and their gradients go to their slots: clipping, Adam, pet_model_set_trainable and the flat gradient
+ * cover them like any other parameter. A missing tensor: PET_ERR_ARGUMENT naming the key.
+ *   pet_backward_train2_long_range: ADDS dJ/dtheta, J = sum_i (nu_i e_i + lambda_i e'_i), e'_i = d/d eps e_i(R + eps u), to the
+ *     gradient slots (pet_model_zero_grad first); d_tangent_atomic [N] (may be NULL) receives e'_i. d_u NULL: first order
+ *     (an energy-only loss), d_nu_atomic is then required and d_lambda_atomic ignored; with d_u, d_lambda_atomic is
+ *     required and d_nu_atomic may be NULL. Needs no forward pass before it.
+ *   pet_hessian_vector_long_range: d_hvp_positions [N,3] = grad_R sum_i lambda_i e'_i (d_lambda_atomic NULL = ones: H u of the
+ *     total energy), d_tangent_atomic [N] (may be NULL) = e'_i. Touches no gradient slot.
+ *   d_workspace: ONE buffer of pet_train2_long_range_workspace_bytes / pet_hvp_long_range_workspace_bytes (-1 for what the
+ *     entry point itself refuses). A batch WITHOUT ANY EDGE is computed like any other: open systems interact through the
+ *     operator beyond the cutoff, so it has forces, a Hessian and featuriser gradients.
+ * Neither takes a cell tangent, seeds of further targets or returns a cell result: they have no such argument (a stress
+ * loss needs the operator's cell tangents, which are not built). Same bits run to run (no float atomics).
+ * PET_ERR_UNSUPPORTED: a P3M-mode handle; an adaptive-cutoff model or graph; a graph with a per-layer exchange.
+ * PET_ERR_ARGUMENT: a handle without a plan or planned for another batch (atom / system counts, cutoff, device), a
+ * pet_graph_from_batch handle, a model without the fused single-property target, a workspace that is too small. */
+int64_t pet_train2_long_range_workspace_bytes(const pet_model_t* m, const pet_graph_t* g, const pet_ewald_t* e);
+int pet_backward_train2_long_range(const pet_model_t* m, const pet_graph_t* g, const pet_ewald_t* e, const float* d_positions,
+                                   void* d_workspace, int64_t workspace_bytes, const float* d_lambda_atomic,
+                                   const float* d_nu_atomic, const float* d_u, float* d_tangent_atomic, void* stream);
+int64_t pet_hvp_long_range_workspace_bytes(const pet_model_t* m, const pet_graph_t* g, const pet_ewald_t* e);
+int pet_hessian_vector_long_range(const pet_model_t* m, const pet_graph_t* g, const pet_ewald_t* e, const float* d_positions,
+                                  void* d_workspace, int64_t workspace_bytes, const float* d_lambda_atomic, const float* d_u,
+                                  float* d_hvp_positions, float* d_tangent_atomic, void* stream);
+
 /* ---- P3M evaluation of the same operator (utils/long_range.py:71-79,153-170) ------------------------------------------------
  * The reference takes its Ewald branch only under `use_ewald and training`: every evaluation of a periodic long-range model
  * goes through torch-pme's P3MCalculator (mesh_spacing = kspace_resolution, interpolation_nodes). This block is a second

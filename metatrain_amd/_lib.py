@@ -57,6 +57,8 @@ SYMBOLS = [
     "pet_ewald_create", "pet_ewald_destroy", "pet_ewald_kvectors_host", "pet_ewald_plan", "pet_ewald_num_kvectors",
     "pet_ewald_workspace_bytes", "pet_ewald_potential", "pet_ewald_backward", "pet_ewald_second_workspace_bytes",
     "pet_ewald_second",
+    "pet_train2_long_range_workspace_bytes", "pet_backward_train2_long_range", "pet_hvp_long_range_workspace_bytes",
+    "pet_hessian_vector_long_range",
     "pet_ewald_set_p3m", "pet_p3m_mesh_shape_host", "pet_p3m_influence_host", "pet_p3m_mesh_shape", "pet_p3m_mesh_elements",
     "pet_p3m_spectrum_elements", "pet_p3m_workspace_bytes", "pet_p3m_spread", "pet_p3m_filter", "pet_p3m_finish",
     "pet_p3m_backward",
@@ -303,6 +305,11 @@ def load() -> ctypes.CDLL:
     lib.pet_ewald_second_workspace_bytes.argtypes = [P, c_int64]
     lib.pet_ewald_second_workspace_bytes.restype = c_int64
     lib.pet_ewald_second.argtypes = [P, P, P, P, P, P, P, c_int32, P, P, P, P, c_int64, P]
+    for name in ("pet_train2_long_range_workspace_bytes", "pet_hvp_long_range_workspace_bytes"):
+        getattr(lib, name).argtypes = [P, P, P]
+        getattr(lib, name).restype = c_int64
+    lib.pet_backward_train2_long_range.argtypes = [P, P, P, P, P, c_int64, P, P, P, P, P]
+    lib.pet_hessian_vector_long_range.argtypes = [P, P, P, P, P, c_int64, P, P, P, P, P]
     lib.pet_ewald_set_p3m.argtypes = [P, c_int32]
     lib.pet_p3m_mesh_shape_host.argtypes = [POINTER(c_double), c_double, POINTER(c_int32)]
     lib.pet_p3m_influence_host.argtypes = [POINTER(c_double), c_double, c_double, c_int32, POINTER(c_double), c_int64]

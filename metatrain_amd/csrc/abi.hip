@@ -804,6 +804,60 @@ int pet_hessian_vector(const pet_model_t* pm, const pet_graph_t* pg, void* d_wor
                    d_tangent_atomic, (hipStream_t)stream);
 }
 
+// ---- the long-range forms: the dual pass with the featuriser stage between the backbone and the heads ----
+// what both refuse, by name, before anything is launched
+static int long_range_check(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e, const char* who) {
+    PET_REQUIRE(pm && pg && e, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(pm->m.finalized, PET_ERR_ARGUMENT, "pet_model_finalize has not been called");
+    PET_REQUIRE(pm->m.h.num_neighbors_adaptive <= 0.f && !pg->g.adaptive, PET_ERR_UNSUPPORTED,
+                std::string(who) + ": long range together with an adaptive cutoff is not served (it drops edges inside the "
+                "exclusion radius)");
+    PET_REQUIRE(!pg->g.x_fn, PET_ERR_UNSUPPORTED,
+                std::string(who) + " on a graph with a per-layer exchange (pet_graph_set_exchange) is not built");
+    return lr_check(e, pg, pm->m.h.d_node, who);
+}
+
+int64_t pet_train2_long_range_workspace_bytes(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e) {
+    if (long_range_check(pm, pg, e, "pet_backward_train2_long_range")) return -1;
+    return gen_train2_lr_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges);
+}
+
+int pet_backward_train2_long_range(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e,
+                                   const float* d_positions, void* d_workspace, int64_t workspace_bytes,
+                                   const float* d_lambda_atomic, const float* d_nu_atomic, const float* d_u,
+                                   float* d_tangent_atomic, void* stream) {
+    if (int rc = long_range_check(pm, pg, e, "pet_backward_train2_long_range")) return rc;
+    if (pg->g.n_nodes == 0) return PET_OK;  // an empty batch: nothing to compute, zero-sized buffers may be null
+    PET_REQUIRE(d_positions && d_workspace, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(d_u ? d_lambda_atomic != nullptr : d_nu_atomic != nullptr, PET_ERR_ARGUMENT,
+                "a direction d_u needs the seeds d_lambda_atomic its gradient was taken with; without one (first order, "
+                "energy only) d_nu_atomic is the loss' seed");
+    Model& m = const_cast<Model&>(pm->m);  // the gradient slots (and LoRA scratch) are the model's mutable state
+    const hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = lora_begin(m, st))) return rc;
+    if ((rc = gen_train2_lr(m, pg->g, e, d_positions, d_workspace, workspace_bytes, d_u ? d_lambda_atomic : nullptr,
+                            d_nu_atomic, d_u, d_tangent_atomic, st)))
+        return rc;
+    return lora_end(m, st);
+}
+
+int64_t pet_hvp_long_range_workspace_bytes(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e) {
+    if (long_range_check(pm, pg, e, "pet_hessian_vector_long_range")) return -1;
+    return gen_hvp_lr_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges);
+}
+
+int pet_hessian_vector_long_range(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e,
+                                  const float* d_positions, void* d_workspace, int64_t workspace_bytes,
+                                  const float* d_lambda_atomic, const float* d_u, float* d_hvp_positions,
+                                  float* d_tangent_atomic, void* stream) {
+    if (int rc = long_range_check(pm, pg, e, "pet_hessian_vector_long_range")) return rc;
+    if (pg->g.n_nodes == 0) return PET_OK;
+    PET_REQUIRE(d_positions && d_workspace && d_u && d_hvp_positions, PET_ERR_ARGUMENT, "null argument");
+    return gen_hvp_lr(pm->m, pg->g, e, d_positions, d_workspace, workspace_bytes, d_lambda_atomic, d_u, d_hvp_positions,
+                      d_tangent_atomic, (hipStream_t)stream);
+}
+
 int64_t pet_nl_workspace_bytes(int64_t n_atoms) { return nl_workspace_bytes(n_atoms); }
 
 int pet_nl_build(const float* d_positions, const float* h_cell, const int32_t* h_pbc, int64_t n_atoms,

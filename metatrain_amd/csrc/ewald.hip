@@ -385,6 +385,8 @@ __global__ __launch_bounds__(256) void k_ew_force2(const int2* __restrict__ tile
 // p = (i -> j, S) with e = u_j - u_i, n = D / d:  out_g[i] -= P w'(d) (n.e) q_j,  out_q[i] -= P w'(d) (n.e) g_j  and
 // out_r[i] += P (B_p + B'_p) M_w e,  M_w = w'' n n^T + (w'/d) (I - n n^T). Lanes take one edge each of a chunk of 64 for w', w''
 // and M_w e, then all lanes walk the chunk's edges for the channel sums. Adds F2 (k_ew_force2) into out_r for every atom.
+// A null result is not formed (ew_second_run): without out_r neither F2 nor the channel products are read, without out_g
+// (out_q) Q (G) is not read in the channel sums; each sum is its own accumulator, so the others keep their bits.
 __global__ __launch_bounds__(64) void k_ew_edge_second(const EwSys* __restrict__ sys, const int* __restrict__ gsys,
                                                        const int* __restrict__ rowptr, const int* __restrict__ nbr,
                                                        const float4* __restrict__ geo, const float* __restrict__ G,
@@ -399,8 +401,8 @@ __global__ __launch_bounds__(64) void k_ew_edge_second(const EwSys* __restrict__
     double fp[3] = {0.0, 0.0, 0.0};
     if (s.periodic) {
         const double inv_a = 1.0 / (sqrt(2.0) * sigma);
-        const float* gi = G + (int64_t)i * C;
-        const float* qi = Q + (int64_t)i * C;
+        const float* gi = out_r ? G + (int64_t)i * C : nullptr;
+        const float* qi = out_r ? Q + (int64_t)i * C : nullptr;
         const double ui[3] = {(double)U[3 * (int64_t)i], (double)U[3 * (int64_t)i + 1], (double)U[3 * (int64_t)i + 2]};
         const int p1 = rowptr[i + 1];
         for (int p0 = rowptr[i]; p0 < p1; p0 += 64) {
@@ -435,7 +437,7 @@ __global__ __launch_bounds__(64) void k_ew_edge_second(const EwSys* __restrict__
             sm[lane][0] = m[0]; sm[lane][1] = m[1]; sm[lane][2] = m[2];
             __syncthreads();
             const int ne = min(64, p1 - p0);
-            for (int q = 0; q < ne; q++) {
+            for (int q = 0; out_r && q < ne; q++) {
                 const int jq = sj[q];
                 if (jq == i) continue;
                 const float* gj = G + (int64_t)jq * C;
@@ -453,15 +455,15 @@ __global__ __launch_bounds__(64) void k_ew_edge_second(const EwSys* __restrict__
                 double ag = 0.0, aq = 0.0;
                 for (int q = 0; q < ne; q++) {
                     const int64_t o = (int64_t)sj[q] * C + c;
-                    ag += sco[q] * (double)Q[o];
-                    aq += sco[q] * (double)G[o];
+                    if (out_g) ag += sco[q] * (double)Q[o];
+                    if (out_q) aq += sco[q] * (double)G[o];
                 }
-                out_g[(int64_t)i * C + c] += (float)ag;
-                out_q[(int64_t)i * C + c] += (float)aq;
+                if (out_g) out_g[(int64_t)i * C + c] += (float)ag;
+                if (out_q) out_q[(int64_t)i * C + c] += (float)aq;
             }
         }
     }
-    if (lane < 3) out_r[3 * (int64_t)i + lane] += (float)((double)F2[3 * (int64_t)i + lane] + fp[lane]);
+    if (out_r && lane < 3) out_r[3 * (int64_t)i + lane] += (float)((double)F2[3 * (int64_t)i + lane] + fp[lane]);
 }
 
 // the largest reciprocal index along every axis of a cell inside |k| <= 2 pi / lambda; false where one is beyond 1e6
@@ -619,7 +621,132 @@ size_t ew_carve2(const pet_ewald_t* e, int64_t C, void* base, EwWs2& w2) {
     return c.off;
 }
 
+// pet_ewald_second with selectable results: a null out_q / out_g / out_r is not formed and the launches that serve it alone
+// are skipped. With all three it is the launch list pet_ewald_second always had. Q may be null where only out_q is asked
+// for (it is a function of (G, Ur) alone), G where only out_g is (a function of (Q, Uq, Ur)).
+int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                  const float* Ur, int C, float* out_q, float* out_g, float* out_r, const EwWs2& w2, hipStream_t st) {
+    const EwWs& w = w2.w;
+    const int64_t N = e->n_atoms;
+    const unsigned cy = (unsigned)cdiv(C, 256), nk = (unsigned)e->ktiles.size(), np = (unsigned)e->atiles_p.size(),
+                   nn = (unsigned)e->atiles_n.size();
+    const size_t lds = ew_table_lds(e);
+    const float inv_R = (float)(1.0 / e->cutoff);
+    // (the profiler's stage names tell the selections apart: all three results, the dual forward's, the two reverses')
+    ProfScope ps(out_q && out_g && out_r ? "ewald_second" : out_g ? "ewald_second_g" : out_r ? "ewald_second_qr" : "ewald_second_q",
+                 st, 0.0, 0.0);
+    PET_TRY(ew_tables(e, g, pos, w, st));
+    // S'(g) serves out_r of both halves and out_q
+    if (nk && (out_r || (out_q && Ur)))
+        k_ew_sfac<false><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, G, C, w.S2, nullptr);
+    if (Uq) {
+        // out_g = A u_q (leaves S'(u_q) in S3), out_r = grad_r Phi(r; u_q, g): the first-order adjoint with (g, q) := (u_q, g)
+        if (out_g) PET_TRY(ew_apply(e, g, pos, Uq, C, out_g, w, w2.S3, w.loc.sum_g, st));
+        else if (out_r && nk)
+            k_ew_sfac<false><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Uq, C, w2.S3, nullptr);
+        if (out_r) {
+            if (np)
+                k_ew_force<true><<<np, 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, pos, inv_R, Uq, G, w.S2, w2.S3,
+                                                       C, ew_vec_loads(C, G, Uq), w.loc.F);
+            PET_TRY(ew_local_backward(e, g, pos, G, Uq, C, w.loc, out_r, nullptr, st, [] {}));
+        }
+    } else {
+        if (out_g) PET_HIP_CHECK(hipMemsetAsync(out_g, 0, (size_t)N * C * sizeof(float), st));
+        if (out_r) PET_HIP_CHECK(hipMemsetAsync(out_r, 0, (size_t)N * 3 * sizeof(float), st));
+    }
+    if (out_q) PET_HIP_CHECK(hipMemsetAsync(out_q, 0, (size_t)N * C * sizeof(float), st));
+    if (Ur) {
+        // out_g += (D_u A) q, out_q = (D_u A) g, out_r += H u_r: k-space and open parts, then the exclusion rows
+        if (nk) {
+            if (out_g || out_r) {
+                k_ew_sfac<false><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Q, C, w.S1, nullptr);
+                k_ew_sfac<true><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Q, C, w2.Su1, Ur);
+            }
+            if (out_q || out_r)
+                k_ew_sfac<true><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, G, C, w2.Su2, Ur);
+        }
+        if (np) {
+            if (out_g)
+                k_ew_gather<true><<<dim3(np, cy), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, w.S1, C, out_g,
+                                                                  w2.Su1, Ur);
+            if (out_q)
+                k_ew_gather<true><<<dim3(np, cy), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, w.S2, C, out_q,
+                                                                  w2.Su2, Ur);
+            if (out_r)
+                k_ew_force2<true><<<np, 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, pos, inv_R, G, Q, w.S1, w.S2,
+                                                        w2.Su1, w2.Su2, Ur, C, ew_vec_loads(C, Q, G), w.loc.F);
+        }
+        if (nn) {
+            if (out_g) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, Q, C, out_g, Ur);
+            if (out_q) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, G, C, out_q, Ur);
+            if (out_r)
+                k_ew_force2<false><<<nn, 256, 0, st>>>(e->d_atiles_n, e->d_sys, nullptr, nullptr, 1, pos, inv_R, G, Q, nullptr, nullptr,
+                                                       nullptr, nullptr, Ur, C, ew_vec_loads(C, Q, G), w.loc.F);
+        }
+        k_ew_edge_second<<<(unsigned)N, 64, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.geo, G, Q, Ur, w.loc.F, C, e->sigma, e->cutoff,
+                                                     out_g, out_q, out_r);
+    }
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
+}
+
 }  // namespace
+
+// ---- what the long-range stage of the dual training pass (gen_train.hip) calls: the operator on device rows of a planned
+// Ewald-mode handle, on ONE workspace of lr_ewald_workspace_bytes (that of pet_ewald_second). The caller has checked the
+// handle against the graph (lr_check); every call rebuilds the phase tables (positions do not change inside a sweep, but
+// the tables are a fraction of one structure-factor launch).
+int lr_check(const pet_ewald_t* e, const pet_graph_t* pg, int C, const char* who) {
+    PET_REQUIRE(e && pg, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(e->p3m_nodes == 0, PET_ERR_UNSUPPORTED,
+                std::string(who) + " on a P3M-mode handle (pet_ewald_set_p3m): second derivatives through P3M are not built "
+                "(the reference trains with Ewald summation)");
+    return ew_check_graph(e, pg, C);
+}
+
+int64_t lr_ewald_workspace_bytes(const pet_ewald_t* e, int C) {
+    EwWs2 w;
+    return (int64_t)ew_carve2(e, C, nullptr, w);
+}
+
+// out = A X
+int lr_potential(const pet_ewald_t* e, const Graph& g, const float* pos, const float* X, int C, float* out, void* ws,
+                 hipStream_t st) {
+    EwWs2 w2;
+    ew_carve2(e, C, ws, w2);
+    ProfScope ps("ewald_fwd", st, 0.0, 0.0);
+    PET_TRY(ew_tables(e, g, pos, w2.w, st));
+    return ew_apply(e, g, pos, X, C, out, w2.w, w2.w.S1, w2.w.loc.sum_q, st);
+}
+
+// gq = A G and gpos = grad_r Phi(r; G, Q): pet_ewald_backward without the cell gradient
+int lr_backward(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, int C, float* gq,
+                float* gpos, void* ws, hipStream_t st) {
+    EwWs2 w2;
+    ew_carve2(e, C, ws, w2);
+    const EwWs& w = w2.w;
+    ProfScope ps("ewald_bwd", st, 0.0, 0.0);
+    PET_TRY(ew_tables(e, g, pos, w, st));
+    PET_TRY(ew_apply(e, g, pos, G, C, gq, w, w.S2, w.loc.sum_g, st));
+    const unsigned cy = (unsigned)cdiv(C, 256);
+    const size_t lds = ew_table_lds(e);
+    if (!e->ktiles.empty())
+        k_ew_sfac<false><<<dim3((unsigned)e->ktiles.size(), cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Q, C,
+                                                                                 w.S1, nullptr);
+    if (!e->atiles_p.empty())
+        k_ew_force<true><<<(unsigned)e->atiles_p.size(), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, pos,
+                                                                         (float)(1.0 / e->cutoff), G, Q, w.S1, w.S2, C,
+                                                                         ew_vec_loads(C, Q, G), w.loc.F);
+    return ew_local_backward(e, g, pos, Q, G, C, w.loc, gpos, nullptr, st, [] {});
+}
+
+// pet_ewald_second's results by choice (ew_second_run): null results are skipped
+int lr_second(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+              const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st) {
+    EwWs2 w2;
+    ew_carve2(e, C, ws, w2);
+    return ew_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, out_r, w2, st);
+}
 
 }  // namespace pet
 
@@ -786,58 +913,9 @@ int pet_ewald_second(const pet_ewald_t* e, const pet_graph_t* pg, const float* d
                 "Ewald workspace too small (pet_ewald_second_workspace_bytes)");
     PET_REQUIRE(d_positions && d_charges && d_grad_potential && d_out_charges && d_out_grad_potential && d_out_positions,
                 PET_ERR_ARGUMENT, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    const Graph& g = pg->g;
     ew_carve2(e, C, d_workspace, w2);
-    const EwWs& w = w2.w;
-    const float *Q = d_charges, *G = d_grad_potential, *Uq = d_u_charges, *Ur = d_u_positions;
-    const int64_t N = e->n_atoms;
-    const unsigned cy = (unsigned)cdiv(C, 256), nk = (unsigned)e->ktiles.size(), np = (unsigned)e->atiles_p.size(),
-                   nn = (unsigned)e->atiles_n.size();
-    const size_t lds = ew_table_lds(e);
-    const float inv_R = (float)(1.0 / e->cutoff);
-    ProfScope ps("ewald_second", st, 0.0, 0.0);
-    PET_TRY(ew_tables(e, g, d_positions, w, st));
-    // S'(g) serves both halves
-    if (nk) k_ew_sfac<false><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, G, C, w.S2, nullptr);
-    if (Uq) {
-        // out_g = A u_q (leaves S'(u_q) in S3), out_r = grad_r Phi(r; u_q, g): the first-order adjoint with (g, q) := (u_q, g)
-        PET_TRY(ew_apply(e, g, d_positions, Uq, C, d_out_grad_potential, w, w2.S3, w.loc.sum_g, st));
-        if (np)
-            k_ew_force<true><<<np, 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, d_positions, inv_R, Uq, G, w.S2,
-                                                   w2.S3, C, ew_vec_loads(C, G, Uq), w.loc.F);
-        PET_TRY(ew_local_backward(e, g, d_positions, G, Uq, C, w.loc, d_out_positions, nullptr, st, [] {}));
-    } else {
-        PET_HIP_CHECK(hipMemsetAsync(d_out_grad_potential, 0, (size_t)N * C * sizeof(float), st));
-        PET_HIP_CHECK(hipMemsetAsync(d_out_positions, 0, (size_t)N * 3 * sizeof(float), st));
-    }
-    PET_HIP_CHECK(hipMemsetAsync(d_out_charges, 0, (size_t)N * C * sizeof(float), st));
-    if (Ur) {
-        // out_g += (D_u A) q, out_q = (D_u A) g, out_r += H u_r: k-space and open parts, then the exclusion rows
-        if (nk) {
-            k_ew_sfac<false><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Q, C, w.S1, nullptr);
-            k_ew_sfac<true><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Q, C, w2.Su1, Ur);
-            k_ew_sfac<true><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, G, C, w2.Su2, Ur);
-        }
-        if (np) {
-            k_ew_gather<true><<<dim3(np, cy), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, w.S1, C,
-                                                              d_out_grad_potential, w2.Su1, Ur);
-            k_ew_gather<true><<<dim3(np, cy), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, w.S2, C, d_out_charges,
-                                                              w2.Su2, Ur);
-            k_ew_force2<true><<<np, 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, d_positions, inv_R, G, Q, w.S1, w.S2,
-                                                    w2.Su1, w2.Su2, Ur, C, ew_vec_loads(C, Q, G), w.loc.F);
-        }
-        if (nn) {
-            k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, d_positions, inv_R, Q, C, d_out_grad_potential, Ur);
-            k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, d_positions, inv_R, G, C, d_out_charges, Ur);
-            k_ew_force2<false><<<nn, 256, 0, st>>>(e->d_atiles_n, e->d_sys, nullptr, nullptr, 1, d_positions, inv_R, G, Q, nullptr,
-                                                   nullptr, nullptr, nullptr, Ur, C, ew_vec_loads(C, Q, G), w.loc.F);
-        }
-        k_ew_edge_second<<<(unsigned)N, 64, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.geo, G, Q, Ur, w.loc.F, C, e->sigma, e->cutoff,
-                                                     d_out_grad_potential, d_out_charges, d_out_positions);
-    }
-    PET_HIP_CHECK(hipGetLastError());
-    return PET_OK;
+    return ew_second_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, C, d_out_charges,
+                         d_out_grad_potential, d_out_positions, w2, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -601,6 +601,39 @@ __global__ void k_gt_last_rev(const float* __restrict__ gA, const int* __restric
 }
 
 // ---------------------------------------------------------------------------------------------
+// long-range stage: the layer sum, the mix and their adjoints (one half of a dual row set per launch)
+// ---------------------------------------------------------------------------------------------
+constexpr int LR_MAX_LAYERS = 16;
+struct LrRows {
+    const float* p[LR_MAX_LAYERS];
+    int n;
+};
+// Y = scale * sum_l X_l, the layers added in layer order by one thread per element: x = sum_l h_l / sqrt(NR) forward, and
+// the adjoint of y from those of the m_l, sum_l / sqrt(2), in reverse
+__global__ void k_lr_layer_sum(LrRows X, float scale, float* __restrict__ Y, int64_t n) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    float s = X.p[0][idx];
+    for (int l = 1; l < X.n; l++) s += X.p[l][idx];
+    Y[idx] = scale * s;
+}
+// m_l = (h_l + y) / sqrt(2)
+__global__ void k_lr_mix(const float* __restrict__ H, const float* __restrict__ Y, float* __restrict__ M, int64_t n) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n) M[idx] = (H[idx] + Y[idx]) * 0.70710678118654752f;
+}
+// the adjoint of h_l from that of m_l (in place) and that of x: dH = dM / sqrt(2) + dX * sx, sx = 1 / sqrt(NR)
+__global__ void k_lr_mix_rev(float* __restrict__ dH, const float* __restrict__ dX, float sx, int64_t n) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n) dH[idx] = fmaf(dX[idx], sx, dH[idx] * 0.70710678118654752f);
+}
+// nu_q = A nu_V + (D_u A) lambda_V: the second term added where there is a direction
+__global__ void k_lr_add(float* __restrict__ Y, const float* __restrict__ X, int64_t n) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx < n) Y[idx] += X[idx];
+}
+
+// ---------------------------------------------------------------------------------------------
 // workspace of the pass
 // ---------------------------------------------------------------------------------------------
 using TAttn = WAttn<D2>;
@@ -903,6 +936,118 @@ struct TOps {
     }
 };
 
+// ---------------------------------------------------------------------------------------------
+// The long-range stage (LrStage, model.h): between the backbone and the heads,
+//     x = sum_l h_l / sqrt(NR),  q = C x + c,  V = A(r) q,  a = P0 V + p0,  s = silu(a),  y = P2 s + p2,  m_l = (h_l + y) / sqrt(2)
+// on dual rows [N, d_node] (every Linear of the featuriser is d_node x d_node), with V' = A q' + (D_u A) q from the
+// operator's second-order entry (out_grad_potential at u_q = q', u_r = u). The heads read m_l.
+// ---------------------------------------------------------------------------------------------
+const char* const LR_KEYS[3] = {"long_range_featurizer.charges_map", "long_range_featurizer.out_projection.0",
+                                "long_range_featurizer.out_projection.2"};
+struct LrWs {
+    void* ew;                             // the operator's workspace (lr_ewald_workspace_bytes at d_node channels)
+    D2 x, q, V, a, s, y, dy, dV, dq, dx;  // values and adjoints [N, d_node]
+    float *dqu, *r1, *r2;                 // (D_u A) lambda_V [N, d_node]; the operator's two position adjoints [N, 3]
+    std::vector<D2> ml;
+    size_t bytes;
+};
+static void lr_carve(const Model& m, const pet_ewald_t* e, int64_t N, void* base, LrWs& w) {
+    const GD d = dims_of(m);
+    Carver c(base);
+    w.ew = base;
+    c.off = ((size_t)lr_ewald_workspace_bytes(e, d.DN) + 255) & ~size_t(255);
+    const size_t n = (size_t)(N > 0 ? N : 1) * d.DN;
+    for (D2* v : {&w.x, &w.q, &w.V, &w.a, &w.s, &w.y, &w.dy, &w.dV, &w.dq, &w.dx}) take(c, n, *v);
+    w.dqu = c.take<float>(n);
+    w.r1 = c.take<float>((size_t)(N > 0 ? N : 1) * 3);
+    w.r2 = c.take<float>((size_t)(N > 0 ? N : 1) * 3);
+    w.ml.resize(m.num_readout_layers());
+    for (auto& v : w.ml) take(c, n, v);
+    w.bytes = c.off;
+}
+// the three Linears from the model's own parameter table; a missing (or mis-sized) tensor is an error by key
+static int lr_linears(const Model& m, int DN, Lin* L) {
+    for (int i = 0; i < 3; i++) {
+        const std::string k(LR_KEYS[i]);
+        auto wi = m.raw.find(k + ".weight"), bi = m.raw.find(k + ".bias");
+        PET_REQUIRE(wi != m.raw.end() && wi->second.second == (int64_t)DN * DN, PET_ERR_ARGUMENT,
+                    "the model holds no '" + k + ".weight' of d_node x d_node elements: load the long-range checkpoint's "
+                    "featuriser tensors with the model (HipModel.load uploads every key of a state dict)");
+        PET_REQUIRE(bi != m.raw.end() && bi->second.second == (int64_t)DN, PET_ERR_ARGUMENT,
+                    "the model holds no '" + k + ".bias' of d_node elements: load the long-range checkpoint's featuriser "
+                    "tensors with the model (HipModel.load uploads every key of a state dict)");
+        L[i] = Lin();
+        L[i].w = wi->second.first;
+        L[i].b = bi->second.first;
+        L[i].n_out = L[i].k_in = DN;
+    }
+    return PET_OK;
+}
+static LrRows lr_rows(const std::vector<D2>& v, bool tangent) {
+    LrRows r;
+    r.n = (int)v.size();
+    for (int l = 0; l < r.n; l++) r.p[l] = tangent ? v[l].t : v[l].p;
+    return r;
+}
+// sweep 1: h_l (the backbone's node features per readout layer) -> m_l. Without a direction every tangent row is zero.
+static int lr_forward(TOps& t, const LrStage& lr, const Lin* L, const std::vector<D2>& h, const float* u, LrWs& w) {
+    const int64_t N = t.N, n = t.N * t.d.DN;
+    const int DN = t.d.DN;
+    const float sx = 1.0f / sqrtf((float)h.size());
+    k_lr_layer_sum<<<g1(n), 256, 0, t.st>>>(lr_rows(h, false), sx, w.x.p, n);
+    k_lr_layer_sum<<<g1(n), 256, 0, t.st>>>(lr_rows(h, true), sx, w.x.t, n);
+    t.linf(w.x, DN, L[0], w.q, DN, N);
+    PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.q.p, DN, w.V.p, w.ew, t.st));
+    if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, nullptr, w.q.t, u, DN, nullptr, w.V.t, nullptr, w.ew, t.st));
+    else t.o.zero(w.V.t, n);
+    t.linf(w.V, DN, L[1], w.a, DN, N);
+    t.silu(w.a, w.s, n);
+    t.linf(w.s, DN, L[2], w.y, DN, N);
+    for (size_t l = 0; l < h.size(); l++) {
+        k_lr_mix<<<g1(n), 256, 0, t.st>>>(h[l].p, w.y.p, w.ml[l].p, n);
+        k_lr_mix<<<g1(n), 256, 0, t.st>>>(h[l].t, w.y.t, w.ml[l].t, n);
+    }
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
+}
+// sweep 2: t.dHl holds the heads' adjoint pairs of (m_l, m_l'); on return those of (h_l, h_l'). The six gradients go to
+// their slots; in Hessian-vector mode none is formed and lr.rbar receives the operator's share of dJ/dR instead:
+//     grad_r Phi(r; nu_V, q) + grad_r Phi(r; q', lambda_V) + H_Phi(r; lambda_V, q) u.
+static int lr_reverse(TOps& t, const LrStage& lr, const Lin* L, const float* u, LrWs& w) {
+    const int64_t N = t.N, n = t.N * t.d.DN;
+    const int DN = t.d.DN;
+    k_lr_layer_sum<<<g1(n), 256, 0, t.st>>>(lr_rows(t.dHl, false), 0.70710678118654752f, w.dy.p, n);
+    k_lr_layer_sum<<<g1(n), 256, 0, t.st>>>(lr_rows(t.dHl, true), 0.70710678118654752f, w.dy.t, n);
+    t.wgrad(L[2], w.dy, DN, w.s, DN, N);
+    t.linb(w.dy, DN, L[2], w.s, DN, N);     // (nu, lambda) of s, then of a
+    t.silu_rev(w.a, w.s, n);
+    t.wgrad(L[1], w.s, DN, w.V, DN, N);
+    t.linb(w.s, DN, L[1], w.dV, DN, N);     // (nu_V, lambda_V)
+    // lambda_q' = A lambda_V, nu_q = A nu_V + (D_u A) lambda_V (A and D_u A are symmetric)
+    if (t.hv) {
+        PET_TRY(lr_backward(lr.e, t.g, lr.pos, w.q.p, w.dV.p, DN, w.dq.p, w.r1, w.ew, t.st));
+        PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, w.dV.t, w.q.t, u, DN, w.dqu, nullptr, w.r2, w.ew, t.st));
+        t.o.axpby(1.f, w.r1, 3, 1.f, w.r2, 3, nullptr, lr.rbar, 3, false, N, 3);
+    } else {
+        PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.p, DN, w.dq.p, w.ew, t.st));
+        if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, nullptr, w.dV.t, nullptr, u, DN, w.dqu, nullptr, nullptr, w.ew, t.st));
+    }
+    if (u) {
+        PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.t, DN, w.dq.t, w.ew, t.st));
+        k_lr_add<<<g1(n), 256, 0, t.st>>>(w.dq.p, w.dqu, n);
+    } else
+        t.o.zero(w.dq.t, n);
+    t.wgrad(L[0], w.dq, DN, w.x, DN, N);
+    t.linb(w.dq, DN, L[0], w.dx, DN, N);
+    const float sx = 1.0f / sqrtf((float)t.dHl.size());
+    for (auto& dh : t.dHl) {
+        k_lr_mix_rev<<<g1(n), 256, 0, t.st>>>(dh.p, w.dx.p, sx, n);
+        k_lr_mix_rev<<<g1(n), 256, 0, t.st>>>(dh.t, w.dx.t, sx, n);
+    }
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
+}
+
 }  // namespace
 
 // (nu_x, lambda_x) = adjoint of (y, y') = norm(x, x') on rows of any width (k_gt_norm_rev) for another caller: the
@@ -932,7 +1077,9 @@ int64_t gen_train_workspace_bytes(const Model& m, int64_t N, int64_t E) {
 // (nu, lambda) pair -- and k_hvp_geo folds them into hv->dv = dJ/dv [E, 4]. Needs u and a static cutoff.
 int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, const float* lA, const float* nA, const float* u,
                const float* ucell, float* tangent_atomic, hipStream_t st, const float* const* seed_node,
-               const float* const* seed_edge, int n_seed, const HvpTaps* hv) {
+               const float* const* seed_edge, int n_seed, const HvpTaps* hv, const LrStage* lr) {
+    PET_REQUIRE(!lr || ((lA || nA) && !ucell && n_seed == 0 && !g.adaptive), PET_ERR_ARGUMENT,
+                "the long-range stage: the fused target's seeds, no cell tangent, no seeds of further targets, a static cutoff");
     PET_REQUIRE(hv || m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
     PET_REQUIRE(!hv || (u && !g.adaptive && n_seed == 0), PET_ERR_ARGUMENT, "Hessian-vector mode: a direction, a static cutoff, no seeds");
     PET_REQUIRE(n_seed == 0 || n_seed == m.num_readout_layers(), PET_ERR_ARGUMENT, "expected one seed pair per readout layer");
@@ -992,6 +1139,18 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
         PET_HIP_CHECK(hipMemsetAsync(w.bd, 0, E * sizeof(float), st));
     }
     gen_walk_forward(t, w);
+    // ---------------- the long-range stage, forward: the heads' node inputs become m_l ----------------
+    LrWs lw;
+    Lin lrl[3];
+    if (lr) {
+        PET_REQUIRE(NR <= LR_MAX_LAYERS, PET_ERR_UNSUPPORTED, "the long-range stage serves at most 16 readout layers");
+        if (int rc = lr_linears(m, DN, lrl)) return rc;
+        lr_carve(m, lr->e, N, lr->ws, lw);
+        PET_REQUIRE((int64_t)lw.bytes <= lr->ws_bytes, PET_ERR_ARGUMENT, "long-range stage workspace too small");
+        std::vector<D2> hl(NR);
+        for (int l = 0; l < NR; l++) hl[l] = (res ? w.gnn[l] : w.gnn.back()).Hout;
+        if (int rc = lr_forward(t, *lr, lrl, hl, u, lw)) return rc;
+    }
     // ---------------- heads: tangent energies and the seeds of sweep 2 ----------------
     // adjoints entering the backbone from the heads, per readout layer: kept apart for the residual featuriser
     t.dHl.resize(NR);
@@ -1020,7 +1179,7 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
     }
     for (int l = 0; fused && l < NR; l++) {
         const TGnn& Bl = res ? w.gnn[l] : w.gnn.back();
-        const D2 Hf = Bl.Hout, Mf = res ? Bl.XF : Bl.Mout;
+        const D2 Hf = lr ? lw.ml[l] : Bl.Hout, Mf = res ? Bl.XF : Bl.Mout;
         const HeadW& H = *heads[l];
         const LastW& Lw = *lasts[l];
         Lin ln; ln.w = Lw.nw; ln.b = Lw.nb; ln.n_out = 1; ln.k_in = DH;
@@ -1041,6 +1200,9 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
         if (seed_node && seed_node[l]) t.o.axpby(1.f, seed_node[l], DN, 0.f, nullptr, 0, nullptr, t.dHl[l].p, DN, true, N, DN);
         if (seed_edge && seed_edge[l]) t.o.axpby(1.f, seed_edge[l], D, 0.f, nullptr, 0, nullptr, t.dMl[l].p, D, true, E, D);
     }
+    // ---------------- the long-range stage, reverse: the adjoints of m_l become those of h_l ----------------
+    if (lr)
+        if (int rc = lr_reverse(t, *lr, lrl, u, lw)) return rc;
     // ---------------- sweep 2: joint reverse through the backbone ----------------
     gen_walk_reverse(t, w);
     if (conditioned && !hv) {
@@ -1115,6 +1277,71 @@ int gen_hvp(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const fl
     if (rc) return rc;
     // (h.ngeo is spent: it serves as the scatter's d/d(edge vector) scratch)
     return backward_geometry_generic(m, g, h.ngeo, h.dv, nullptr, nullptr, hvp_pos, hvp_cell, st);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The long-range forms (pet_backward_train2_long_range, pet_hessian_vector_long_range): ONE workspace, the dual pass'
+// (and the Hessian-vector taps) first, the stage's behind. No edge-free exit: open systems interact through the operator
+// beyond the cutoff, so a batch without an edge still has forces, a Hessian and featuriser gradients.
+// ---------------------------------------------------------------------------------------------
+static size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
+
+int64_t lr_stage_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N) {
+    LrWs w;
+    lr_carve(m, e, N, nullptr, w);
+    return (int64_t)w.bytes;
+}
+
+int64_t gen_train2_lr_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, int64_t E) {
+    return (int64_t)align256((size_t)gen_train_workspace_bytes(m, N, E)) + lr_stage_workspace_bytes(m, e, N);
+}
+
+int gen_train2_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
+                  const float* lA, const float* nA, const float* u, float* tangent_atomic, hipStream_t st) {
+    const int64_t N = g.n_nodes, E = g.n_edges;
+    const size_t train_bytes = align256((size_t)gen_train_workspace_bytes(m, N, E));
+    const int64_t stage_bytes = lr_stage_workspace_bytes(m, e, N);
+    PET_REQUIRE((int64_t)train_bytes + stage_bytes <= ws_bytes, PET_ERR_ARGUMENT,
+                "workspace too small (pet_train2_long_range_workspace_bytes)");
+    LrStage lr{e, pos, static_cast<char*>(ws) + train_bytes, stage_bytes, nullptr};
+    return gen_train2(m, g, ws, (int64_t)train_bytes, lA, nA, u, nullptr, tangent_atomic, st, nullptr, nullptr, 0, nullptr, &lr);
+}
+
+int64_t gen_hvp_lr_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, int64_t E) {
+    return (int64_t)align256((size_t)gen_hvp_workspace_bytes(m, N, E)) + (int64_t)align256((size_t)(N > 0 ? N : 1) * 3 * sizeof(float)) +
+           lr_stage_workspace_bytes(m, e, N);
+}
+
+// hvp_pos [N, 3] = grad_R of sum_i lambda_i e'_i of the long-range model: the backbone's share through the scatter of the
+// geometry adjoint (none without an edge), the operator's own from the stage
+int gen_hvp_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
+               const float* lA, const float* u, float* hvp_pos, float* tangent_atomic, hipStream_t st) {
+    const int64_t N = g.n_nodes, E = g.n_edges;
+    if (N == 0) return PET_OK;
+    HvpTaps h;
+    float* ones;
+    const size_t train_bytes = (size_t)gen_train_workspace_bytes(m, N, E);
+    const size_t hvp_bytes = align256(hvp_carve(m, N, E, ws, train_bytes, h, &ones));
+    const size_t rbar_bytes = align256((size_t)N * 3 * sizeof(float));
+    const int64_t stage_bytes = lr_stage_workspace_bytes(m, e, N);
+    PET_REQUIRE((int64_t)(hvp_bytes + rbar_bytes) + stage_bytes <= ws_bytes, PET_ERR_ARGUMENT,
+                "workspace too small (pet_hvp_long_range_workspace_bytes)");
+    float* rbar = reinterpret_cast<float*>(static_cast<char*>(ws) + hvp_bytes);
+    LrStage lr{e, pos, static_cast<char*>(ws) + hvp_bytes + rbar_bytes, stage_bytes, rbar};
+    if (!lA) {
+        k_hvp_fill<<<g1(N), 256, 0, st>>>(ones, 1.f, N);
+        lA = ones;
+    }
+    int rc = gen_train2(m, g, ws, (int64_t)train_bytes, lA, nullptr, u, nullptr, tangent_atomic, st, nullptr, nullptr, 0, &h, &lr);
+    if (rc) return rc;
+    if (E > 0) {
+        // (h.ngeo is spent: it serves as the scatter's d/d(edge vector) scratch)
+        if ((rc = backward_geometry_generic(m, g, h.ngeo, h.dv, nullptr, nullptr, hvp_pos, nullptr, st))) return rc;
+    } else
+        PET_HIP_CHECK(hipMemsetAsync(hvp_pos, 0, (size_t)N * 3 * sizeof(float), st));
+    k_lr_add<<<g1(N * 3), 256, 0, st>>>(hvp_pos, rbar, N * 3);
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
 }
 
 // Adjoint of gen_train_predict for `n_blocks` blocks of one (target, readout layer), seeds gA[b] [N, P_b]: dL/dtheta of the

@@ -24,9 +24,13 @@ featuriser under the reference's state-dict keys, :func:`energy_and_gradient` th
 Second derivatives are built at the OPERATOR level for the Ewald sum: :meth:`EwaldHip.second`
 (``pet_ewald_second``) differentiates the adjoint -- ``dL/dq`` and ``dL/dR`` -- with respect to charges, ``dL/dV`` and positions,
 and torch double backward (``create_graph=True``) through :class:`LongRangeFeaturizerHip` runs on it, which is what a force loss
-and a Hessian-vector product need from the operator. Not built, each raising by name: cell tangents and cell results of that
-operation (cells that require grad in a double backward), second derivatives through P3M (the reference trains with Ewald
-summation), and the model-level training step and ``pet_hessian_vector`` of a long-range model.
+and a Hessian-vector product need from the operator. At the MODEL level the size-generic dual pass
+carries the featuriser between the backbone and the heads (``pet_backward_train2_long_range``,
+``pet_hessian_vector_long_range``): :class:`LongRangeForward` and :class:`LongRangeTrainStep` are the training step on
+energies and forces, :func:`hessian_vector_product` is ``H u``. The six featuriser tensors then live in the model's own
+parameter table (:meth:`LongRangeFeaturizerHip.bind`). Not built, each raising by name: cell tangents and cell results
+(a stress / strain-gradient loss, cell directions of a Hessian-vector product), second derivatives through P3M (the
+reference trains with Ewald summation), further targets in the long-range step.
 
 The reference takes its Ewald branch only under ``use_ewald and training`` (``utils/long_range.py:153-170``): it EVALUATES every
 periodic long-range model with P3M. :class:`P3MHip` is that operator (``csrc/p3m.hip``: binning, spread, filter, gather and the
@@ -480,6 +484,27 @@ class LongRangeFeaturizerHip:
         self.load_state_dict(state, prefix)
         return self
 
+    def bind(self, model: rt.HipModel, prefix: str = "long_range_featurizer.") -> "LongRangeFeaturizerHip":
+        """Make ``model``'s parameter table the single source of the six tensors (training: the model holds their storage,
+        gradient slots and Adam moments; ``HipModel.load`` uploads them with every other key of a long-range checkpoint).
+        ``params`` become copies of the model's and :meth:`refresh` renews them after an optimizer step, so that
+        ``state_dict()`` of model and featuriser agree to the bit. A tensor the model was loaded without raises by key."""
+        keys = getattr(model, "_ckeys", {})
+        for k in self.params:
+            if prefix + k not in keys:
+                raise PetHipError(f"the model was loaded without '{prefix + k}': load the long-range checkpoint's featuriser "
+                                  "tensors with the model (one state dict) to train them")
+        self._bound = (model, prefix)
+        return self.refresh()
+
+    def refresh(self) -> "LongRangeFeaturizerHip":
+        """Copy the six tensors from the bound model (six small device copies); a no-op without :meth:`bind`."""
+        bound = getattr(self, "_bound", None)
+        if bound is not None:
+            model, prefix = bound
+            self.params = {k: model.param(prefix + k) for k in self.params}
+        return self
+
     def to(self, device) -> "LongRangeFeaturizerHip":
         self.params = {k: v.to(device) for k, v in self.params.items()}
         return self
@@ -558,3 +583,192 @@ def energy_and_gradient(model: rt.HipModel, featurizer: LongRangeFeaturizerHip, 
         gpos, gcell = out
         return atomic, energies, gpos + pos.grad, gcell + cells.grad
     return atomic, energies, out + pos.grad
+
+
+# ---- training on energies and forces, Hessian-vector products --------------------------------------------
+def _check_trainable(model, featurizer, what: str) -> None:
+    """What the long-range sweeps refuse before anything is launched, by name."""
+    hypers = getattr(model, "hypers", None) or {}
+    if not bool((hypers.get("long_range") or {}).get("enable")):
+        raise PetHipError(f"{what}: this model has no long_range.enable: use the ordinary entry points")
+    if hypers.get("num_neighbors_adaptive"):
+        raise PetHipError(f"{what}: long_range together with num_neighbors_adaptive is not served (the adaptive cutoff drops "
+                          "edges inside the exclusion radius)")
+    if isinstance(getattr(featurizer, "ewald", None), P3MHip):
+        raise PetHipError(f"{what} with a P3M featuriser is not built: second derivatives through P3M are not built (the "
+                          "reference trains long-range models with Ewald summation). Build the featuriser with "
+                          "method='ewald'; a use_ewald: false model needs the explicit p3m_as_ewald=True to train by Ewald "
+                          "summation")
+
+
+class LongRangeForward:
+    """What :class:`metatrain_amd.pet.trainer.TrainStep` calls on a ``HipForward``, for a long-range model: ``forward``,
+    ``sum_over_atoms``, ``backward(ones, want_cell_grad=True)``, ``backward_train(seeds)``, ``backward_train2(ones, seeds, u)``
+    and ``rebind``. The first-order pair is :func:`energy_and_gradient` (``forward`` runs it and keeps dE/dR and dE/dcell of
+    the summed energy for ``backward``, whose seeds are therefore ones); the two training calls are
+    ``pet_backward_train2_long_range``, which needs no forward. ``pbcs [S][3]``: a graph does not record them."""
+
+    train = True
+
+    def __init__(self, model: rt.HipModel, featurizer: LongRangeFeaturizerHip, graph: rt.HipGraph, pbcs, target: str = "energy"):
+        _check_trainable(model, featurizer, "LongRangeForward")
+        self.model, self.featurizer, self.graph, self.pbcs, self.target = model, featurizer, graph, pbcs, target
+        self.lib = model.lib
+        self._first = None
+        self._planned_for = None
+        self.workspace2: Optional[torch.Tensor] = None
+
+    def rebind(self, graph: rt.HipGraph, pbcs=None) -> "LongRangeForward":
+        """Another batch (``pbcs``: its periodicities, unchanged if None); the plan follows at the next call."""
+        self.graph = graph
+        self.pbcs = self.pbcs if pbcs is None else pbcs
+        self._first = None
+        return self
+
+    def _plan(self) -> None:
+        g = self.graph
+        if getattr(g, "_sys", None) is None:
+            raise PetHipError("the long-range model needs a HipGraph built from positions (not from batch_data)")
+        if self._planned_for is not g or self.featurizer.ewald.n_systems != g.n_systems:
+            self.featurizer.plan(g._cells, self.pbcs, _first_atoms(g._sys, g.n_systems))
+            self._planned_for = g
+
+    def forward(self, want_features: bool = False, want_atomic: bool = True):
+        if want_features or not want_atomic:
+            raise PetHipError("LongRangeForward.forward returns the per-atom energies of the fused target only (features and a "
+                              "model without a fused target belong to further targets, which the long-range step does not serve)")
+        self._plan()
+        atomic, _, gpos, gcell = energy_and_gradient(self.model, self.featurizer, self.graph, self.pbcs, self.target,
+                                                     want_cell_grad=True, replan=False)
+        self._first = (gpos, gcell)
+        return atomic
+
+    def sum_over_atoms(self, atomic: torch.Tensor) -> torch.Tensor:
+        out = torch.zeros(self.graph.n_systems, dtype=torch.float32, device=atomic.device)
+        check(self.lib.pet_sum_over_atoms(self.graph.handle, rt._ptr(atomic), rt._ptr(out), rt._stream()))
+        return out
+
+    def backward(self, grad_atomic: torch.Tensor, want_cell_grad: bool = False):
+        """dE/dR (and dE/dcell) of the summed energy from the last :meth:`forward`: ``grad_atomic`` is ones by contract."""
+        if self._first is None:
+            raise PetHipError("LongRangeForward.backward follows forward() on the same graph")
+        if grad_atomic is not None and not bool((grad_atomic == 1).all()):
+            raise PetHipError("LongRangeForward.backward returns the gradients of the summed energy: grad_atomic must be ones "
+                              "(weighted sums: hessian_vector_product / backward_train2 take lambda_atomic)")
+        return self._first if want_cell_grad else self._first[0]
+
+    def _sweep(self, lam, nu, u, want_tangent):
+        self._plan()
+        g, dev = self.graph, self.graph.workspace.device
+        need = int(self.lib.pet_train2_long_range_workspace_bytes(self.model.handle, g.handle, self.featurizer.ewald.handle))
+        if need < 0:
+            raise PetHipError(self.lib.pet_last_error().decode(errors="replace") or "pet_train2_long_range_workspace_bytes failed")
+        if self.workspace2 is None or self.workspace2.numel() < need:
+            self.workspace2 = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
+        lam, nu, u = f32(lam), f32(nu), f32(u)
+        pos = g._pos.detach().to(torch.float32).contiguous()
+        tan = torch.empty(g.n_nodes, dtype=torch.float32, device=dev) if want_tangent else None
+        check(self.lib.pet_backward_train2_long_range(self.model.handle, g.handle, self.featurizer.ewald.handle, rt._ptr(pos),
+                                                      rt._ptr(self.workspace2), self.workspace2.numel(), rt._ptr(lam),
+                                                      rt._ptr(nu), rt._ptr(u), rt._ptr(tan), rt._stream()))
+        return tan
+
+    def backward_train(self, grad_atomic: Optional[torch.Tensor], want_position_grad: bool = False, want_cell_grad: bool = False,
+                       seed_features=None):
+        """Energy-only loss: ADDS dL/dtheta for ``dL/de = grad_atomic`` to the model's gradient slots, the six featuriser
+        tensors' among them."""
+        if seed_features is not None:
+            raise PetHipError("seed_features (further targets) in the long-range training step are not built")
+        if want_position_grad or want_cell_grad:
+            raise PetHipError("LongRangeForward.backward_train forms parameter gradients only: dE/dR and dE/dcell come from "
+                              "forward() / backward()")
+        if grad_atomic is None:
+            raise PetHipError("the long-range training step trains the fused energy target: grad_atomic is None")
+        self._sweep(None, grad_atomic, None, False)
+        return None
+
+    def backward_train2(self, lambda_atomic: torch.Tensor, nu_atomic: Optional[torch.Tensor], u: torch.Tensor,
+                        want_tangent: bool = False, u_cell: Optional[torch.Tensor] = None, seed_features=None):
+        """Force loss: ADDS d/dtheta ``[sum_i nu_i e_i + <u, dE/dR>]`` (gradient taken with seeds ``lambda_atomic``) to the
+        gradient slots; on request returns ``e'_i`` along ``u``."""
+        if u_cell is not None:
+            raise PetHipError("u_cell (a cell tangent: the stress / strain-gradient loss) of a long-range model is not built: "
+                              "the operator's second-order entry takes no cell tangent")
+        if seed_features is not None:
+            raise PetHipError("seed_features (further targets) in the long-range training step are not built")
+        return self._sweep(lambda_atomic, nu_atomic, u, want_tangent)
+
+
+from .pet.trainer import TrainStep  # noqa: E402  (trainer imports runtime only: no cycle)
+
+
+class LongRangeTrainStep(TrainStep):
+    """:class:`TrainStep` for a long-range model: energy and position-gradient terms, by ``loss_weights`` (MSE) or the
+    ``loss`` hyper (MSE / MAE / Huber), with a :class:`LongRangeForward` in place of the ``HipForward``. ``featurizer`` is
+    bound to the model (:meth:`LongRangeFeaturizerHip.bind`): the model's table holds the six tensors, the optimizer step
+    updates them there and the featuriser's copies are refreshed after it. Refused by name: ``target_strain_gradients``,
+    ``extra_targets``, a P3M featuriser."""
+
+    _serves_long_range = True
+
+    def __init__(self, model: rt.HipModel, featurizer: LongRangeFeaturizerHip, hypers: Optional[dict] = None,
+                 steps_per_epoch: int = 1):
+        _check_trainable(model, featurizer, "LongRangeTrainStep")
+        super().__init__(model, hypers, steps_per_epoch)
+        self.featurizer = featurizer.bind(model)
+
+    @staticmethod
+    def _refuse(fw, target_strain_gradients, extra_targets) -> None:
+        if target_strain_gradients is not None:
+            raise PetHipError("target_strain_gradients (the stress loss) of a long-range model are not built: the operator's "
+                              "second-order entry takes no cell tangent")
+        if extra_targets:
+            raise PetHipError(f"extra_targets {sorted(extra_targets)} in the long-range training step are not built")
+        if not isinstance(fw, LongRangeForward):
+            raise PetHipError("LongRangeTrainStep needs a LongRangeForward (a HipForward leaves the long-range features out)")
+
+    def _accumulate(self, graph, fw, target_energies, n_atoms, target_gradients, target_strain_gradients, positions, cells,
+                    share_e, share_f, share_s, extra_targets=None, extra_counts=None):
+        self._refuse(fw, target_strain_gradients, extra_targets)
+        return super()._accumulate(graph, fw, target_energies, n_atoms, target_gradients, None, positions, cells, share_e,
+                                   share_f, share_s, None, extra_counts)
+
+    def _term_arrays(self, b):
+        self._refuse(b["fw"], b.get("target_strain_gradients"), b.get("extra_targets"))
+        return super()._term_arrays(b)
+
+    def _finish(self, trained=None):
+        norm = super()._finish(trained)
+        self.featurizer.refresh()
+        return norm
+
+
+def hessian_vector_product(model: rt.HipModel, featurizer: LongRangeFeaturizerHip, graph: rt.HipGraph, pbcs, u: torch.Tensor,
+                           lambda_atomic: Optional[torch.Tensor] = None, want_tangent: bool = False, replan: bool = True,
+                           workspace: Optional[torch.Tensor] = None):
+    """``H u`` of a long-range model (``pet_hessian_vector_long_range``): ``grad_R sum_i lambda_i e'_i`` ``[N, 3]`` with ``e'_i``
+    the derivative of the per-atom energies along ``dR = u [N, 3]`` (``lambda_atomic = None``: ones, the total energy's
+    Hessian), then on request ``e'_i [N]``. The model holds the six featuriser tensors (one state dict); ``featurizer``
+    supplies the planned operator. Needs no forward pass and touches no gradient slot. No cell direction and no cell result."""
+    _check_trainable(model, featurizer, "the long-range Hessian-vector product")
+    rt._require_cuda(u)
+    if getattr(graph, "_sys", None) is None:
+        raise PetHipError("the long-range model needs a HipGraph built from positions (not from batch_data)")
+    if replan or featurizer.ewald.n_systems != graph.n_systems:
+        featurizer.plan(graph._cells, pbcs, _first_atoms(graph._sys, graph.n_systems))
+    dev, n = u.device, graph.n_nodes
+    need = int(model.lib.pet_hvp_long_range_workspace_bytes(model.handle, graph.handle, featurizer.ewald.handle))
+    if need < 0:
+        raise PetHipError(model.lib.pet_last_error().decode(errors="replace") or "pet_hvp_long_range_workspace_bytes failed")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    uu = u.detach().to(torch.float32).reshape(n, 3).contiguous()
+    lam = None if lambda_atomic is None else lambda_atomic.detach().to(dev, torch.float32).reshape(n).contiguous()
+    pos = graph._pos.detach().to(torch.float32).contiguous()
+    hp = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    tan = torch.empty(n, dtype=torch.float32, device=dev) if want_tangent else None
+    check(model.lib.pet_hessian_vector_long_range(model.handle, graph.handle, featurizer.ewald.handle, rt._ptr(pos),
+                                                  rt._ptr(workspace), workspace.numel(), rt._ptr(lam), rt._ptr(uu), rt._ptr(hp),
+                                                  rt._ptr(tan), rt._stream()))
+    return (hp, tan) if want_tangent else hp

@@ -158,8 +158,11 @@ class TrainStep:
     targets (``metatrain_amd/zbl.py``), as the reference's ``get_remove_additive_transform`` does: the ZBL term has no
     parameters, is not part of the loss graph and is added back at evaluation (``ExportedEnergyModel(..., zbl=...)``)."""
 
+    _serves_long_range = False  # a subclass that evaluates the long-range featuriser (long_range.LongRangeTrainStep) sets it
+
     def __init__(self, model: HipModel, hypers: Optional[dict] = None, steps_per_epoch: int = 1):
-        refuse_long_range(getattr(model, "hypers", None) or {}, "training (TrainStep)")
+        if not self._serves_long_range:
+            refuse_long_range(getattr(model, "hypers", None) or {}, "training (TrainStep)")
         self.model = model
         self.hypers = dict(DEFAULT_TRAINER_HYPERS)
         self.hypers.update(hypers or {})

@@ -34,7 +34,8 @@ def refuse_long_range(hypers: dict, what: str) -> None:
     it the model would silently compute something else. ``metatrain_amd.long_range.energy_and_gradient`` evaluates it."""
     if bool((hypers.get("long_range") or {}).get("enable")):
         raise PetHipError(f"{what} of a long-range model (long_range.enable) is not built: it would leave the long-range "
-                          "features out. Energies, dE/dR and dE/dcell: metatrain_amd.long_range.energy_and_gradient")
+                          "features out. Energies, dE/dR and dE/dcell: metatrain_amd.long_range.energy_and_gradient; training on "
+                          "energies and forces: long_range.LongRangeTrainStep; H u: long_range.hessian_vector_product")
 
 
 def hypers_struct(hypers: dict, atomic_types: List[int]) -> PetHypers:

@@ -1,0 +1,143 @@
+"""Cost of the long-range PET's force-loss training sweep on the 1 000-atom synthetic box of ``profiles/long_range_bench.json``
+at the default size, next to the same model without long range. A record, not a gate: writes
+``profiles/long_range_train_bench.json``.
+
+    python tools/gpu_long_range_train_bench.py [--atoms 1000] [--repeats 10] [--calls 20]
+
+Legs, alternating in one process (host clock around ``--calls`` calls and a synchronise, median of ``--repeats`` samples, spread
+reported): the second-order call and the whole optimizer step, each with long range (``LongRangeForward`` /
+``LongRangeTrainStep``) and without (``HipForward(train=True)`` / ``TrainStep``: the tuned pass serves the default size there);
+the operator's full second-order call (``EwaldHip.second``: all three results, what the parent commit had) next to the sweep's
+own operator calls, which are read from the library's event profiler in a pass of their own (``ewald_second_g``: the dual
+forward's tangent alone; ``ewald_second_q``: the training reverse's ``(D_u A) lambda_V`` alone; ``ewald_fwd``: ``A x``).
+Kernel shares: ``rocprofv3 --kernel-trace --stats -- python tools/gpu_long_range_train_bench.py --profile-sweeps 5``, a run
+of its own."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from metatrain_amd import long_range as lr  # noqa: E402
+from metatrain_amd import runtime as rt  # noqa: E402
+from metatrain_amd import synthetic  # noqa: E402
+from metatrain_amd.pet.hypers import default_hypers  # noqa: E402
+from metatrain_amd.pet.trainer import TrainStep  # noqa: E402
+
+TYPES = [1, 6, 7, 8]
+LR = {"enable": True, "use_ewald": True, "smearing": 1.4, "kspace_resolution": 1.33, "interpolation_nodes": 5}
+
+
+def build(enable, pos, z, cell, dev):
+    hypers = default_hypers()
+    if enable:
+        hypers["long_range"] = dict(LR)
+    params = dict(synthetic.synthetic_params(hypers, TYPES, {"energy": 1}, 0, torch.float32))
+    feat = None
+    if enable:
+        feat = lr.LongRangeFeaturizerHip(hypers, device=dev)
+        params.update({k: v.cpu() for k, v in feat.state_dict().items()})
+    model = rt.HipModel(hypers, TYPES)
+    model.load({k: v.to(dev) for k, v in params.items()}, "energy")
+    n = pos.shape[0]
+    pairs, _ = rt.neighbor_list(pos.to(dev), cell, [True] * 3, hypers["cutoff"])
+    graph = rt.HipGraph(model, pos.to(dev), cell[None].to(dev), pairs[:, 0], pairs[:, 1], pairs[:, 2:5], z.to(dev),
+                        torch.zeros(n, dtype=torch.int32, device=dev))
+    return hypers, model, graph, feat
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--atoms", type=int, default=1000)
+    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "long_range_train_bench.json"))
+    ap.add_argument("--profile-sweeps", type=int, default=0,
+                    help="run only this many long-range second-order sweeps after one warm-up and exit: the command to put "
+                         "under rocprofv3 --kernel-trace --stats (profiles/long_range_train_kernel_stats.csv)")
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    n = args.atoms
+    pos, z, cell = synthetic.random_box(n, seed=11)
+    pbcs = [[True] * 3]
+    gen = torch.Generator(device=dev).manual_seed(0)
+    nu = torch.rand(n, device=dev, generator=gen) - 0.5
+    u = torch.randn(n, 3, device=dev, generator=gen)
+    ones = torch.ones(n, device=dev)
+    te = torch.zeros(1, device=dev)
+    tg = torch.zeros(n, 3, device=dev)
+    n_atoms = torch.full((1,), float(n), device=dev)
+    hyp_l, model_l, graph_l, feat = build(True, pos, z, cell, dev)
+    hyp_s, model_s, graph_s, _ = build(False, pos, z, cell, dev)
+    fw_l = lr.LongRangeForward(model_l, feat, graph_l, pbcs)
+    fw_s = rt.HipForward(model_s, graph_s, train=True)
+    train = {"learning_rate": 1e-6, "warmup_fraction": 0.0, "num_epochs": 10**9}
+    step_l = lr.LongRangeTrainStep(model_l, feat, train)
+    step_s = TrainStep(model_s, train)
+    ew = feat.ewald
+    c = hyp_l["d_node"]
+    q, g, uq = (torch.randn(n, c, device=dev, generator=gen) for _ in range(3))
+    p32 = pos.to(dev)
+
+    def sweep_l():
+        model_l.zero_grad()
+        fw_l.backward_train2(ones, nu, u)
+
+    def sweep_s():
+        model_s.zero_grad()
+        fw_s.forward()
+        fw_s.backward_train2(ones, nu, u)
+
+    if args.profile_sweeps:
+        for _ in range(args.profile_sweeps + 1):
+            sweep_l()
+        torch.cuda.synchronize()
+        return
+    legs = {"second_order_long_range": sweep_l, "forward_and_second_order_short_range": sweep_s,
+            "step_long_range": lambda: step_l(graph_l, fw_l, te, n_atoms, tg),
+            "step_short_range": lambda: step_s(graph_s, fw_s, te, n_atoms, tg),
+            "operator_second_all_results": lambda: ew.second(graph_l, p32, q, g, uq, u),
+            "energy_and_forces_long_range": lambda: lr.energy_and_gradient(model_l, feat, graph_l, pbcs, replan=False)}
+    for fn in legs.values():
+        fn()
+    torch.cuda.synchronize()
+    samples = {k: [] for k in legs}
+    for _ in range(args.repeats):
+        for name, fn in legs.items():
+            t0 = time.perf_counter()
+            for _ in range(args.calls):
+                fn()
+            torch.cuda.synchronize()
+            samples[name].append(1e3 * (time.perf_counter() - t0) / args.calls)
+    med = {k: statistics.median(v) for k, v in samples.items()}
+    # the sweep's own operator calls, from the event profiler (a pass of its own: the events serialise nothing on one stream,
+    # but they are not part of the timed legs)
+    rt.profile(True)
+    for _ in range(args.calls):
+        sweep_l()
+    torch.cuda.synchronize()
+    stages = {r["name"]: {"ms_per_call": r["total_ms"] / max(r["calls"], 1), "calls_per_sweep": r["calls"] / args.calls}
+              for r in rt.profile_report() if r["name"].startswith("ewald")}
+    rt.profile(False)
+    ewald_ms = sum(s["ms_per_call"] * s["calls_per_sweep"] for s in stages.values())
+    result = {"workload": f"{n}-atom synthetic periodic box, default PET (d_node = {c}), {ew.num_kvectors(0)} k-vectors, "
+                          f"{graph_l.n_edges} edges; ms per call on the host clock around {args.calls} calls and a synchronise, "
+                          f"median of {args.repeats} samples, the legs alternating, after one warm-up call each",
+              "atoms": n, "channels": c, "kvectors": ew.num_kvectors(0), "graph_edges": graph_l.n_edges, "ms": samples,
+              "ms_median": med, "ms_min": {k: min(v) for k, v in samples.items()}, "ms_max": {k: max(v) for k, v in samples.items()},
+              "sweep_operator_stages": stages, "sweep_operator_ms": ewald_ms,
+              "sweep_operator_share": ewald_ms / med["second_order_long_range"]}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(result, fh)
+    print(json.dumps({k: v for k, v in result.items() if k != "ms"}))
+
+
+if __name__ == "__main__":
+    main()

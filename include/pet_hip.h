@@ -603,7 +603,7 @@ int pet_zbl_hessian_vector(const pet_zbl_t* z, const pet_graph_t* g, const float
  *   outputs are written in full. d_workspace: pet_ewald_second_workspace_bytes(e, C) bytes (-1 without a plan, on a P3M-mode
  *   handle, for C < 1). No atoms: PET_OK, nothing touched. Nothing is kept between calls, no host synchronisation, same bits run
  *   to run and alone as inside a batch. No cell tangent is taken and no cell result returned (mixed position / cell second
- *   derivatives are not built); a P3M-mode handle: PET_ERR_ARGUMENT (second derivatives through P3M are not built).
+ *   derivatives are not built); a P3M-mode handle: PET_ERR_ARGUMENT (the mesh operator's are pet_p3m_second's, below).
  * PET_ERR_ARGUMENT: a pet_graph_from_batch handle, a graph built under an adaptive cutoff (it drops edges inside R), a graph
  * of a model without nl_is_strict, a graph whose cutoff, atom or system count differ from the plan's.
  * PET_ERR_UNSUPPORTED: mixed pbc; a cell with more than PET_EWALD_MAX_INDEX reciprocal indices along an axis. */
@@ -631,7 +631,7 @@ int pet_ewald_second(const pet_ewald_t* e, const pet_graph_t* g, const float* d_
  * The long-range forms of pet_backward_train2 and pet_hessian_vector for a long_range.enable model: the size-generic dual
  * pass (for EVERY model size, the default included, as pet_hessian_vector) with the featuriser between the backbone and the
  * heads,  x = sum_l h_l / sqrt(L),  q = charges_map(x),  V = A(r) q,  y = out_projection(V),  m_l = (h_l + y) / sqrt(2),  the
- * node heads reading m_l. `e` is a planned Ewald-mode handle for the batch of `g`; d_positions [N,3] the positions the graph
+ * node heads reading m_l. `e` is a planned handle for the batch of `g` (Ewald mode, or P3M mode with a transform hook: below); d_positions [N,3] the positions the graph
  * was built from. The six featuriser tensors are read from the MODEL's parameter table, under the reference's keys
  * long_range_featurizer.{charges_map,out_projection.0,out_projection.2}.{weight,bias} (pet_model_set_param; each d_node x
  * d_node / d_node), and their gradients go to their slots: clipping, Adam, pet_model_set_trainable and the flat gradient
@@ -647,7 +647,7 @@ int pet_ewald_second(const pet_ewald_t* e, const pet_graph_t* g, const float* d_
  *     operator beyond the cutoff, so it has forces, a Hessian and featuriser gradients.
  * Neither takes a cell tangent, seeds of further targets or returns a cell result: they have no such argument (a stress
  * loss needs the operator's cell tangents, which are not built). Same bits run to run (no float atomics).
- * PET_ERR_UNSUPPORTED: a P3M-mode handle; an adaptive-cutoff model or graph; a graph with a per-layer exchange.
+ * PET_ERR_UNSUPPORTED: a P3M-mode handle without a transform hook (pet_p3m_set_transform); an adaptive-cutoff model or graph; a graph with a per-layer exchange.
  * PET_ERR_ARGUMENT: a handle without a plan or planned for another batch (atom / system counts, cutoff, device), a
  * pet_graph_from_batch handle, a model without the fused single-property target, a workspace that is too small. */
 int64_t pet_train2_long_range_workspace_bytes(const pet_model_t* m, const pet_graph_t* g, const pet_ewald_t* e);
@@ -716,6 +716,36 @@ int pet_p3m_backward(const pet_ewald_t* e, const pet_graph_t* g, const float* d_
                      const float* d_grad_potential, int32_t n_channels, const float* d_phi_q, const float* d_phi_g,
                      const void* d_spec_q, const void* d_spec_g, float* d_grad_positions, float* d_grad_cells,
                      void* d_workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- Second derivatives of the mesh operator, and P3M in the dual pass ---------------------------------
+ * pet_p3m_second is pet_ewald_second (same arguments, same three results, same contract) on a P3M-mode handle. Positions
+ * enter the mesh sum A_mesh = W^T K W (W the spread, K = irfftn . (G^/Omega) . rfftn) through W alone: with the per-atom
+ * direction du_i = N (.) (u_r,i cell^{-1}) in mesh units and the tangent weight (D_u W)_i = sum_a (d_a W) du_a,
+ *   (D_u A) x = (D_u W)^T K W x + W^T K (D_u W) x,
+ *   H_Phi(g, q) u_r = per atom sum_c sum_nodes [ (grad grad W . du)(g phi_q + q phi_g) + grad W (g phi_dq + q phi_dg) ],
+ *   phi_x = K W x, phi_dx = K (D_u W) x; d^2W/du^2 = M_{p-2}(x) - 2 M_{p-2}(x-1) + M_{p-2}(x-2) (fp64, rounded once).
+ * The self, background, exclusion and open-system terms are the kernels pet_ewald_second launches. A NULL result is not
+ * formed and what serves it alone is skipped (all three NULL: PET_ERR_ARGUMENT). Pairs of transforms per call, both
+ * cotangents given: d_out_grad_potential alone 2, d_out_charges alone 2, d_out_positions or all three 4.
+ * The library links no FFT: the transforms inside the call are the caller's, through a HOOK. pet_p3m_set_transform(e, fn,
+ * user) (fn NULL removes it; it survives pet_ewald_plan): fn(user, inverse, mesh_byte_offset, spectrum_byte_offset, C) runs
+ * rfftn (inverse = 0) or irfftn with norm = "forward" (inverse = 1) of the plan's packed channel-first meshes (layout of the
+ * block above) between a mesh buffer and a half-spectrum buffer at those byte offsets (multiples of 256) of the d_workspace
+ * of the entry point that is running, on the stream that entry point was given. It is called on the host while the entry
+ * point enqueues its launches and must not synchronise; non-zero fails the entry point with PET_ERR_ARGUMENT naming the hook.
+ * The hook is the opt-in: with one, pet_backward_train2_long_range / pet_hessian_vector_long_range and their workspace
+ * functions take a P3M-mode handle (their single workspace then holds four meshes and a half spectrum at d_node channels);
+ * without one they refuse it as before, and pet_p3m_second returns PET_ERR_ARGUMENT naming pet_p3m_set_transform.
+ * pet_p3m_second_workspace_bytes: -1 without a plan, on an Ewald-mode handle, for C < 1. pet_ewald_second* refuse a
+ * P3M-mode handle as before. No cell tangent and no cell result. No float atomics; same bits run to run and alone as in a batch. */
+typedef int (*pet_p3m_transform_fn)(void* user, int32_t inverse, int64_t mesh_byte_offset, int64_t spectrum_byte_offset,
+                                    int32_t n_channels);
+int pet_p3m_set_transform(pet_ewald_t* e, pet_p3m_transform_fn fn, void* user);
+int64_t pet_p3m_second_workspace_bytes(const pet_ewald_t* e, int64_t n_channels);
+int pet_p3m_second(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
+                   const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions, int32_t n_channels,
+                   float* d_out_charges, float* d_out_grad_potential, float* d_out_positions, void* d_workspace,
+                   int64_t workspace_bytes, void* stream);
 
 /* ---- Rotational augmentation (utils/augmentation.py:O3Augmenter; pet/trainer.py:187-193, 288-303) -------------------------
  * A random element of O(3) per system of a collated batch, drawn and applied on the device. A rigid transformation of

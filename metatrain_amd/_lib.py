@@ -28,6 +28,8 @@ PET_O3_MAX_ARRAYS = 8
 PET_O3_MAX_L = 8
 PET_TARGET_MAX_ARRAYS = 4
 PET_LOSS_KINDS = {"mse": 0, "mae": 1, "huber": 2}
+# pet_p3m_transform_fn: (user, inverse, mesh_byte_offset, spectrum_byte_offset, n_channels) -> 0, or non-zero on failure
+P3M_TRANSFORM_FN = ctypes.CFUNCTYPE(c_int, c_void_p, c_int32, c_int64, c_int64, c_int32)
 PET_LOSS_REDUCTIONS = {"mean": 0, "sum": 1}
 
 # every symbol include/pet_hip.h declares (tests check the library exports them all)
@@ -61,7 +63,7 @@ SYMBOLS = [
     "pet_hessian_vector_long_range",
     "pet_ewald_set_p3m", "pet_p3m_mesh_shape_host", "pet_p3m_influence_host", "pet_p3m_mesh_shape", "pet_p3m_mesh_elements",
     "pet_p3m_spectrum_elements", "pet_p3m_workspace_bytes", "pet_p3m_spread", "pet_p3m_filter", "pet_p3m_finish",
-    "pet_p3m_backward",
+    "pet_p3m_backward", "pet_p3m_set_transform", "pet_p3m_second_workspace_bytes", "pet_p3m_second",
     "pet_o3_draw", "pet_o3_apply", "pet_o3_wigner", "pet_o3_apply_spherical",
     "pet_baseline_workspace_bytes", "pet_species_counts", "pet_composition_accumulate", "pet_target_moments",
     "pet_targets_remove",
@@ -322,6 +324,10 @@ def load() -> ctypes.CDLL:
     lib.pet_p3m_filter.argtypes = [P, c_int32, P, P]
     lib.pet_p3m_finish.argtypes = [P, P, P, P, c_int32, P, P, P, c_int64, P]
     lib.pet_p3m_backward.argtypes = [P, P, P, P, P, c_int32, P, P, P, P, P, P, P, c_int64, P]
+    lib.pet_p3m_set_transform.argtypes = [P, P3M_TRANSFORM_FN, P]
+    lib.pet_p3m_second_workspace_bytes.argtypes = [P, c_int64]
+    lib.pet_p3m_second_workspace_bytes.restype = c_int64
+    lib.pet_p3m_second.argtypes = [P, P, P, P, P, P, P, c_int32, P, P, P, P, c_int64, P]
     lib.pet_o3_draw.argtypes = [c_uint64, c_uint64, c_int32, c_int64, P, P]
     lib.pet_o3_apply.argtypes = [P, c_int64, c_int32, POINTER(O3Array), P]
     lib.pet_o3_wigner.argtypes = [P, c_int64, c_int32, P, P, P]

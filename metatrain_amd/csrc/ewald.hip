@@ -18,10 +18,12 @@
 // fp32 sum over 7 000 k-vectors left 8.9e-6 of the largest potential where this order leaves 3.5e-7.
 // Second derivatives (pet_ewald_second) are variants in the same form: k_ew_sfac<true> (the phase carries
 // k.u_j), k_ew_gather<true> (the directional derivative, a contraction of twice the length), k_ew_force2 (the position Hessian
-// applied to a direction: four product tiles per k tile, or M_K (u_j - u_i) for open systems), k_ew_pairs<true> (long_range.h) and
-// k_ew_edge_second (the exclusion rows, fp64); the <false> instantiations are the first-order kernels, bit for bit.
+// applied to a direction: four product tiles per k tile, or M_K (u_j - u_i) for open systems), k_ew_pairs<true> and
+// k_ew_edge_second (the exclusion rows, fp64); the <false> instantiations are the first-order kernels, bit for bit. k_ew_force2,
+// k_ew_pairs and k_ew_edge_second are in long_range.h: pet_p3m_second launches them for the same local terms.
 // Here: the k-space part (k_ew_tables, k_ew_sfac, k_ew_gather, k_ew_force<true>, k_ew_zk, the k list) and pet_ewald_*, among
-// them the plan of both modes. The handle, k_ew_force and the local terms' kernels are in long_range.h, shared with p3m.hip.
+// them the plan of both modes, and lr_* (what the dual pass calls, dispatching on the handle's mode). The handle, k_ew_force
+// and the local terms' kernels are in long_range.h, shared with p3m.hip.
 #include "long_range.h"
 
 namespace pet {
@@ -241,229 +243,6 @@ __global__ __launch_bounds__(256) void k_ew_zk(const EwSys* __restrict__ sys, co
         const double co = EW_PREFACTOR * (double)z / (double)kk.w;
         kpart[9 * (int64_t)k + lane] = co * ((sigma * sigma + 2.0 / (double)kk.k2) * m * kv[cc] - s.inv[3 * cc + bb]);
     }
-}
-
-// The position Hessian of Phi = sum_c g^T A q applied to the direction U [N, 3] (pet_ewald_second), k-space (PER) / open
-// all-pairs part, in the form of k_ew_force: F[i] = P sum_col gen(i, col) . [product tiles], rows [g_i | q_i] over 2 C channels.
-// PER: four tiles per column tile of 32 k-vectors, against [Re S'_q | Re S'_g], [Im S'_q | Im S'_g] and the same of the
-// weighted structure factors S'_{uq} | S'_{ug}: gen = k [ (c Re_u + s Im_u) - (k.u_i) (c Re + s Im) ].
-// Open: one tile against [q_j | g_j], gen = -M_K (u_j - u_i), M_K = K'' n n^T + (K'/d) (I - n n^T), n = (r_j - r_i) / d.
-template <bool PER>
-__global__ __launch_bounds__(256) void k_ew_force2(const int2* __restrict__ tiles, const EwSys* __restrict__ sys,
-                                                   const EwK* __restrict__ klist, const float2* __restrict__ tab, int NM,
-                                                   const float* __restrict__ pos, float inv_R, const float* __restrict__ G,
-                                                   const float* __restrict__ Q, const float* __restrict__ Sq,
-                                                   const float* __restrict__ Sg, const float* __restrict__ Suq,
-                                                   const float* __restrict__ Sug, const float* __restrict__ U, int C, bool vec,
-                                                   float* __restrict__ F) {
-    extern __shared__ float2 T[];
-    __shared__ float4 ps[32];
-    __shared__ float4 us[32];
-    __shared__ float red[4 * 32 * 3];
-    const int2 tile = tiles[blockIdx.x];
-    const EwSys s = sys[tile.x];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, r = lane & 31;
-    const int a0 = tile.y;
-    if (PER) ew_stage_tables(T, tab, NM, s.first_atom + a0, s.n_atoms - a0);
-    if (threadIdx.x < 32) {
-        float4 p = make_float4(0.f, 0.f, 0.f, 0.f), u = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (a0 + (int)threadIdx.x < s.n_atoms) {
-            const float* q = pos + 3 * (int64_t)(s.first_atom + a0 + threadIdx.x);
-            const float* v = U + 3 * (int64_t)(s.first_atom + a0 + threadIdx.x);
-            p = make_float4(q[0], q[1], q[2], 1.f);
-            u = make_float4(v[0], v[1], v[2], 0.f);
-        }
-        ps[threadIdx.x] = p;
-        us[threadIdx.x] = u;
-    }
-    __syncthreads();
-    const bool vi = a0 + r < s.n_atoms;
-    const float* gi = G + (int64_t)(s.first_atom + a0 + r) * C;
-    const float* qi = Q + (int64_t)(s.first_atom + a0 + r) * C;
-    const int ncols = PER ? s.n_k : s.n_atoms;
-    const int nsteps = (2 * C + 7) / 8;
-    float f[16][3];
-#pragma unroll
-    for (int i = 0; i < 16; i++) f[i][0] = f[i][1] = f[i][2] = 0.f;
-    for (int col0 = wave * 32; col0 < ncols; col0 += 128) {
-        const int col = col0 + r;
-        const bool vc = col < ncols;
-        f32x16 acc_r, acc_i, acu_r, acu_i;  // (open: acc_r alone)
-#pragma unroll
-        for (int i = 0; i < 16; i++) acc_r[i] = acc_i[i] = acu_r[i] = acu_i[i] = 0.f;
-        if (PER) {
-            const int64_t kabs = s.first_k + col;
-            const float *re1 = Sq + kabs * 2 * C, *re2 = Sg + kabs * 2 * C, *ur1 = Suq + kabs * 2 * C, *ur2 = Sug + kabs * 2 * C;
-            for (int t = 0; t < nsteps; t++) {
-                const int ch = 8 * t + 4 * half;
-                const f32x4 A = ew_load4(vi, gi, qi, ch, C, vec);
-                const f32x4 Br = ew_load4(vc, re1, re2, ch, C, vec), Bi = ew_load4(vc, re1 + C, re2 + C, ch, C, vec);
-                const f32x4 Ur = ew_load4(vc, ur1, ur2, ch, C, vec), Ui = ew_load4(vc, ur1 + C, ur2 + C, ch, C, vec);
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Br[u], acc_r, 0, 0, 0);
-                    acc_i = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Bi[u], acc_i, 0, 0, 0);
-                    acu_r = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Ur[u], acu_r, 0, 0, 0);
-                    acu_i = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Ui[u], acu_i, 0, 0, 0);
-                }
-            }
-            int n0 = 0, n1 = 0, n2 = 0;
-            float kx = 0.f, ky = 0.f, kz = 0.f;
-            if (vc) {
-                const EwK k = klist[s.first_k + col];
-                n0 = k.n0; n1 = k.n1; n2 = k.n2; kx = k.kx; ky = k.ky; kz = k.kz;
-            }
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
-                float c, sn;
-                ew_phase(T + row * 3 * NM, NM, n0, n1, n2, c, sn);
-                const float4 u = us[row];
-                const float ku = kx * u.x + ky * u.y + kz * u.z;
-                const float x = (c * acu_r[i] + sn * acu_i[i]) - ku * (c * acc_r[i] + sn * acc_i[i]);
-                f[i][0] += kx * x; f[i][1] += ky * x; f[i][2] += kz * x;
-            }
-        } else {
-            const float* a1 = Q + (int64_t)(s.first_atom + col) * C;
-            const float* a2 = G + (int64_t)(s.first_atom + col) * C;
-            for (int t = 0; t < nsteps; t++) {
-                const int ch = 8 * t + 4 * half;
-                const f32x4 A = ew_load4(vi, gi, qi, ch, C, vec);
-                const f32x4 Ba = ew_load4(vc, a1, a2, ch, C, vec);
-#pragma unroll
-                for (int u = 0; u < 4; u++) acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Ba[u], acc_r, 0, 0, 0);
-            }
-            float3 pj = make_float3(0.f, 0.f, 0.f), uj = make_float3(0.f, 0.f, 0.f);
-            if (vc) {
-                const float* q = pos + 3 * (int64_t)(s.first_atom + col);
-                const float* v = U + 3 * (int64_t)(s.first_atom + col);
-                pj = make_float3(q[0], q[1], q[2]);
-                uj = make_float3(v[0], v[1], v[2]);
-            }
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
-                const float4 pi = ps[row];
-                if (!vc || pi.w == 0.f || col == a0 + row) continue;
-                const float4 u = us[row];
-                const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
-                const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-                const float nx = dx / d, ny = dy / d, nz = dz / d;
-                const float ex = uj.x - u.x, ey = uj.y - u.y, ez = uj.z - u.z;
-                const float nd = nx * ex + ny * ey + nz * ez;
-                const float kd = ew_open_kernel_d(d, inv_R) / d, kdd = ew_open_kernel_dd(d, inv_R);
-                const float along = (kdd - kd) * nd;  // M_K e = (K'' - K'/d) (n.e) n + (K'/d) e
-                f[i][0] -= acc_r[i] * (along * nx + kd * ex);
-                f[i][1] -= acc_r[i] * (along * ny + kd * ey);
-                f[i][2] -= acc_r[i] * (along * nz + kd * ez);
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-            float v = f[i][a];
-#pragma unroll
-            for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
-            if (r == 0) red[(wave * 32 + row) * 3 + a] = v;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 96) {
-        const int row = threadIdx.x / 3, a = threadIdx.x % 3;
-        if (a0 + row < s.n_atoms) {
-            float v = red[row * 3 + a];
-            for (int w = 1; w < 4; w++) v += red[(w * 32 + row) * 3 + a];
-            F[3 * (int64_t)(s.first_atom + a0 + row) + a] = (float)EW_PREFACTOR * v;
-        }
-    }
-}
-
-// The exclusion rows' share of all three results of pet_ewald_second, one wave per atom, fp64 like k_ew_edge_bwd. Per edge
-// p = (i -> j, S) with e = u_j - u_i, n = D / d:  out_g[i] -= P w'(d) (n.e) q_j,  out_q[i] -= P w'(d) (n.e) g_j  and
-// out_r[i] += P (B_p + B'_p) M_w e,  M_w = w'' n n^T + (w'/d) (I - n n^T). Lanes take one edge each of a chunk of 64 for w', w''
-// and M_w e, then all lanes walk the chunk's edges for the channel sums. Adds F2 (k_ew_force2) into out_r for every atom.
-// A null result is not formed (ew_second_run): without out_r neither F2 nor the channel products are read, without out_g
-// (out_q) Q (G) is not read in the channel sums; each sum is its own accumulator, so the others keep their bits.
-__global__ __launch_bounds__(64) void k_ew_edge_second(const EwSys* __restrict__ sys, const int* __restrict__ gsys,
-                                                       const int* __restrict__ rowptr, const int* __restrict__ nbr,
-                                                       const float4* __restrict__ geo, const float* __restrict__ G,
-                                                       const float* __restrict__ Q, const float* __restrict__ U,
-                                                       const float* __restrict__ F2, int C, double sigma, double Rcut,
-                                                       float* __restrict__ out_g, float* __restrict__ out_q,
-                                                       float* __restrict__ out_r) {
-    __shared__ int sj[64];
-    __shared__ double sco[64], sm[64][3];
-    const int i = blockIdx.x, lane = threadIdx.x;
-    const EwSys& s = sys[gsys[i]];
-    double fp[3] = {0.0, 0.0, 0.0};
-    if (s.periodic) {
-        const double inv_a = 1.0 / (sqrt(2.0) * sigma);
-        const float* gi = out_r ? G + (int64_t)i * C : nullptr;
-        const float* qi = out_r ? Q + (int64_t)i * C : nullptr;
-        const double ui[3] = {(double)U[3 * (int64_t)i], (double)U[3 * (int64_t)i + 1], (double)U[3 * (int64_t)i + 2]};
-        const int p1 = rowptr[i + 1];
-        for (int p0 = rowptr[i]; p0 < p1; p0 += 64) {
-            __syncthreads();
-            const int p = p0 + lane;
-            int j = i;
-            double co = 0.0, m[3] = {0.0, 0.0, 0.0};
-            if (p < p1) {
-                j = nbr[p];
-                const float4 g4 = geo[p];
-                const double d = (double)g4.w;
-                if (d < Rcut && j != i) {
-                    const double x = d * inv_a, er = erf(x), der = 2.0 / sqrt(EW_PI) * inv_a * exp(-x * x), dder = -2.0 * x * inv_a * der;
-                    const double cutf = 0.5 * (1.0 + cos(EW_PI * d / Rcut)), dcut = -0.5 * EW_PI / Rcut * sin(EW_PI * d / Rcut);
-                    const double ddcut = -0.5 * (EW_PI / Rcut) * (EW_PI / Rcut) * cos(EW_PI * d / Rcut);
-                    const double n0 = er * cutf, n1 = der * cutf + er * dcut, n2 = dder * cutf + 2.0 * der * dcut + er * ddcut;
-                    const double dw = n1 / d - n0 / (d * d), ddw = n2 / d - 2.0 * n1 / (d * d) + 2.0 * n0 / (d * d * d);
-                    const double n[3] = {(double)g4.x / d, (double)g4.y / d, (double)g4.z / d};
-                    double e[3], nd = 0.0;
-#pragma unroll
-                    for (int a = 0; a < 3; a++) {
-                        e[a] = (double)U[3 * (int64_t)j + a] - ui[a];
-                        nd += n[a] * e[a];
-                    }
-                    co = -EW_PREFACTOR * dw * nd;
-#pragma unroll
-                    for (int a = 0; a < 3; a++) m[a] = EW_PREFACTOR * ((ddw - dw / d) * nd * n[a] + dw / d * e[a]);
-                }
-            }
-            sj[lane] = j;
-            sco[lane] = co;
-            sm[lane][0] = m[0]; sm[lane][1] = m[1]; sm[lane][2] = m[2];
-            __syncthreads();
-            const int ne = min(64, p1 - p0);
-            for (int q = 0; out_r && q < ne; q++) {
-                const int jq = sj[q];
-                if (jq == i) continue;
-                const float* gj = G + (int64_t)jq * C;
-                const float* qj = Q + (int64_t)jq * C;
-                float b = 0.f, bp = 0.f;
-                for (int c = lane; c < C; c += 64) {
-                    b += gi[c] * qj[c];
-                    bp += gj[c] * qi[c];
-                }
-                const double bb = (double)wsum(b) + (double)wsum(bp);
-#pragma unroll
-                for (int a = 0; a < 3; a++) fp[a] += bb * sm[q][a];
-            }
-            for (int c = lane; c < C; c += 64) {
-                double ag = 0.0, aq = 0.0;
-                for (int q = 0; q < ne; q++) {
-                    const int64_t o = (int64_t)sj[q] * C + c;
-                    if (out_g) ag += sco[q] * (double)Q[o];
-                    if (out_q) aq += sco[q] * (double)G[o];
-                }
-                if (out_g) out_g[(int64_t)i * C + c] += (float)ag;
-                if (out_q) out_q[(int64_t)i * C + c] += (float)aq;
-            }
-        }
-    }
-    if (out_r && lane < 3) out_r[3 * (int64_t)i + lane] += (float)((double)F2[3 * (int64_t)i + lane] + fp[lane]);
 }
 
 // the largest reciprocal index along every axis of a cell inside |k| <= 2 pi / lambda; false where one is beyond 1e6
@@ -693,25 +472,29 @@ int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const 
 }  // namespace
 
 // ---- what the long-range stage of the dual training pass (gen_train.hip) calls: the operator on device rows of a planned
-// Ewald-mode handle, on ONE workspace of lr_ewald_workspace_bytes (that of pet_ewald_second). The caller has checked the
+// handle, on ONE workspace of lr_ewald_workspace_bytes (that of pet_ewald_second / pet_p3m_second). The caller has checked the
 // handle against the graph (lr_check); every call rebuilds the phase tables (positions do not change inside a sweep, but
-// the tables are a fraction of one structure-factor launch).
+// the tables are a fraction of one structure-factor launch). A P3M-mode handle that has a transform hook goes to the mesh
+// operator (p3m.hip: p3m_lr_*), whose workspace begins at the same address; ws_offset (the bytes of ws into the entry point's
+// d_workspace) is what that one's transform hook needs and the Ewald sum ignores.
 int lr_check(const pet_ewald_t* e, const pet_graph_t* pg, int C, const char* who) {
     PET_REQUIRE(e && pg, PET_ERR_ARGUMENT, "null argument");
-    PET_REQUIRE(e->p3m_nodes == 0, PET_ERR_UNSUPPORTED,
-                std::string(who) + " on a P3M-mode handle (pet_ewald_set_p3m): second derivatives through P3M are not built "
-                "(the reference trains with Ewald summation)");
+    PET_REQUIRE(e->p3m_nodes == 0 || e->p3m_transform, PET_ERR_UNSUPPORTED,
+                std::string(who) + " on a P3M-mode handle (pet_ewald_set_p3m) without a transform hook: second derivatives "
+                "through P3M need the caller's transforms (pet_p3m_set_transform)");
     return ew_check_graph(e, pg, C);
 }
 
 int64_t lr_ewald_workspace_bytes(const pet_ewald_t* e, int C) {
+    if (e->p3m_nodes) return p3m_lr_workspace_bytes(e, C);
     EwWs2 w;
     return (int64_t)ew_carve2(e, C, nullptr, w);
 }
 
 // out = A X
 int lr_potential(const pet_ewald_t* e, const Graph& g, const float* pos, const float* X, int C, float* out, void* ws,
-                 hipStream_t st) {
+                 hipStream_t st, int64_t ws_offset) {
+    if (e->p3m_nodes) return p3m_lr_potential(e, g, pos, X, C, out, ws, st, ws_offset);
     EwWs2 w2;
     ew_carve2(e, C, ws, w2);
     ProfScope ps("ewald_fwd", st, 0.0, 0.0);
@@ -721,7 +504,8 @@ int lr_potential(const pet_ewald_t* e, const Graph& g, const float* pos, const f
 
 // gq = A G and gpos = grad_r Phi(r; G, Q): pet_ewald_backward without the cell gradient
 int lr_backward(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, int C, float* gq,
-                float* gpos, void* ws, hipStream_t st) {
+                float* gpos, void* ws, hipStream_t st, int64_t ws_offset) {
+    if (e->p3m_nodes) return p3m_lr_backward(e, g, pos, Q, G, C, gq, gpos, ws, st, ws_offset);
     EwWs2 w2;
     ew_carve2(e, C, ws, w2);
     const EwWs& w = w2.w;
@@ -742,7 +526,8 @@ int lr_backward(const pet_ewald_t* e, const Graph& g, const float* pos, const fl
 
 // pet_ewald_second's results by choice (ew_second_run): null results are skipped
 int lr_second(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-              const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st) {
+              const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st, int64_t ws_offset) {
+    if (e->p3m_nodes) return p3m_lr_second(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, out_r, ws, st, ws_offset);
     EwWs2 w2;
     ew_carve2(e, C, ws, w2);
     return ew_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, out_r, w2, st);
@@ -903,8 +688,8 @@ int pet_ewald_second(const pet_ewald_t* e, const pet_graph_t* pg, const float* d
                      int64_t workspace_bytes, void* stream) {
     PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
     PET_REQUIRE(e->p3m_nodes == 0, PET_ERR_ARGUMENT,
-                "pet_ewald_second on a P3M-mode handle (pet_ewald_set_p3m): second derivatives through P3M are not built (the "
-                "reference trains with Ewald summation)");
+                "pet_ewald_second on a P3M-mode handle (pet_ewald_set_p3m): the mesh operator's second derivatives are "
+                "pet_p3m_second's");
     if (int rc = ew_check(e, pg, C, d_workspace, workspace_bytes)) return rc;
     PET_REQUIRE(d_u_charges || d_u_positions, PET_ERR_ARGUMENT, "d_u_charges and d_u_positions are both NULL");
     if (e->n_atoms == 0) return PET_OK;

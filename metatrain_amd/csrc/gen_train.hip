@@ -997,8 +997,8 @@ static int lr_forward(TOps& t, const LrStage& lr, const Lin* L, const std::vecto
     k_lr_layer_sum<<<g1(n), 256, 0, t.st>>>(lr_rows(h, false), sx, w.x.p, n);
     k_lr_layer_sum<<<g1(n), 256, 0, t.st>>>(lr_rows(h, true), sx, w.x.t, n);
     t.linf(w.x, DN, L[0], w.q, DN, N);
-    PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.q.p, DN, w.V.p, w.ew, t.st));
-    if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, nullptr, w.q.t, u, DN, nullptr, w.V.t, nullptr, w.ew, t.st));
+    PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.q.p, DN, w.V.p, w.ew, t.st, lr.ws_offset));
+    if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, nullptr, w.q.t, u, DN, nullptr, w.V.t, nullptr, w.ew, t.st, lr.ws_offset));
     else t.o.zero(w.V.t, n);
     t.linf(w.V, DN, L[1], w.a, DN, N);
     t.silu(w.a, w.s, n);
@@ -1025,15 +1025,15 @@ static int lr_reverse(TOps& t, const LrStage& lr, const Lin* L, const float* u, 
     t.linb(w.s, DN, L[1], w.dV, DN, N);     // (nu_V, lambda_V)
     // lambda_q' = A lambda_V, nu_q = A nu_V + (D_u A) lambda_V (A and D_u A are symmetric)
     if (t.hv) {
-        PET_TRY(lr_backward(lr.e, t.g, lr.pos, w.q.p, w.dV.p, DN, w.dq.p, w.r1, w.ew, t.st));
-        PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, w.dV.t, w.q.t, u, DN, w.dqu, nullptr, w.r2, w.ew, t.st));
+        PET_TRY(lr_backward(lr.e, t.g, lr.pos, w.q.p, w.dV.p, DN, w.dq.p, w.r1, w.ew, t.st, lr.ws_offset));
+        PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, w.dV.t, w.q.t, u, DN, w.dqu, nullptr, w.r2, w.ew, t.st, lr.ws_offset));
         t.o.axpby(1.f, w.r1, 3, 1.f, w.r2, 3, nullptr, lr.rbar, 3, false, N, 3);
     } else {
-        PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.p, DN, w.dq.p, w.ew, t.st));
-        if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, nullptr, w.dV.t, nullptr, u, DN, w.dqu, nullptr, nullptr, w.ew, t.st));
+        PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.p, DN, w.dq.p, w.ew, t.st, lr.ws_offset));
+        if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, nullptr, w.dV.t, nullptr, u, DN, w.dqu, nullptr, nullptr, w.ew, t.st, lr.ws_offset));
     }
     if (u) {
-        PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.t, DN, w.dq.t, w.ew, t.st));
+        PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.t, DN, w.dq.t, w.ew, t.st, lr.ws_offset));
         k_lr_add<<<g1(n), 256, 0, t.st>>>(w.dq.p, w.dqu, n);
     } else
         t.o.zero(w.dq.t, n);
@@ -1303,7 +1303,7 @@ int gen_train2_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const fl
     const int64_t stage_bytes = lr_stage_workspace_bytes(m, e, N);
     PET_REQUIRE((int64_t)train_bytes + stage_bytes <= ws_bytes, PET_ERR_ARGUMENT,
                 "workspace too small (pet_train2_long_range_workspace_bytes)");
-    LrStage lr{e, pos, static_cast<char*>(ws) + train_bytes, stage_bytes, nullptr};
+    LrStage lr{e, pos, static_cast<char*>(ws) + train_bytes, stage_bytes, nullptr, (int64_t)train_bytes};
     return gen_train2(m, g, ws, (int64_t)train_bytes, lA, nA, u, nullptr, tangent_atomic, st, nullptr, nullptr, 0, nullptr, &lr);
 }
 
@@ -1327,7 +1327,7 @@ int gen_hvp_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const float
     PET_REQUIRE((int64_t)(hvp_bytes + rbar_bytes) + stage_bytes <= ws_bytes, PET_ERR_ARGUMENT,
                 "workspace too small (pet_hvp_long_range_workspace_bytes)");
     float* rbar = reinterpret_cast<float*>(static_cast<char*>(ws) + hvp_bytes);
-    LrStage lr{e, pos, static_cast<char*>(ws) + hvp_bytes + rbar_bytes, stage_bytes, rbar};
+    LrStage lr{e, pos, static_cast<char*>(ws) + hvp_bytes + rbar_bytes, stage_bytes, rbar, (int64_t)(hvp_bytes + rbar_bytes)};
     if (!lA) {
         k_hvp_fill<<<g1(N), 256, 0, st>>>(ones, 1.f, N);
         lA = ones;

@@ -4,8 +4,8 @@
 // sum) with their adjoints: kernels and the two host functions that launch them. The operator's convention constants
 // (include/pet_hip.h) are EW_PREFACTOR and the three coefficients of ew_local_forward; a mode adds only
 // its weight 2 G(k) / Omega (ewald.hip: ew_plan_klist) or G^(n) / Omega (p3m.hip: p3m_influence_point).
-// k_ew_pairs<true> and ew_open_kernel_dd serve the Ewald mode's second derivatives (ewald.hip: pet_ewald_second); P3M mode
-// instantiates k_ew_pairs<false> alone.
+// k_ew_pairs<true>, k_ew_force2, k_ew_edge_second and ew_open_kernel_dd serve both modes' second derivatives (ewald.hip:
+// pet_ewald_second; p3m.hip: pet_p3m_second, which has no k tiles and instantiates k_ew_force2<false> alone).
 // Kernels and functions have internal linkage: each translation unit is compiled on its own (build.py: NO_RDC) with its own
 // copy of what it launches. Only the two record types and the P3M plan's entry points have names that cross objects.
 #pragma once
@@ -455,6 +455,229 @@ __global__ __launch_bounds__(256) void k_ew_cell(const EwSys* __restrict__ sys, 
     }
 }
 
+// The position Hessian of Phi = sum_c g^T A q applied to the direction U [N, 3] (pet_ewald_second), k-space (PER) / open
+// all-pairs part, in the form of k_ew_force: F[i] = P sum_col gen(i, col) . [product tiles], rows [g_i | q_i] over 2 C channels.
+// PER: four tiles per column tile of 32 k-vectors, against [Re S'_q | Re S'_g], [Im S'_q | Im S'_g] and the same of the
+// weighted structure factors S'_{uq} | S'_{ug}: gen = k [ (c Re_u + s Im_u) - (k.u_i) (c Re + s Im) ].
+// Open: one tile against [q_j | g_j], gen = -M_K (u_j - u_i), M_K = K'' n n^T + (K'/d) (I - n n^T), n = (r_j - r_i) / d.
+template <bool PER>
+__global__ __launch_bounds__(256) void k_ew_force2(const int2* __restrict__ tiles, const EwSys* __restrict__ sys,
+                                                   const EwK* __restrict__ klist, const float2* __restrict__ tab, int NM,
+                                                   const float* __restrict__ pos, float inv_R, const float* __restrict__ G,
+                                                   const float* __restrict__ Q, const float* __restrict__ Sq,
+                                                   const float* __restrict__ Sg, const float* __restrict__ Suq,
+                                                   const float* __restrict__ Sug, const float* __restrict__ U, int C, bool vec,
+                                                   float* __restrict__ F) {
+    extern __shared__ float2 T[];
+    __shared__ float4 ps[32];
+    __shared__ float4 us[32];
+    __shared__ float red[4 * 32 * 3];
+    const int2 tile = tiles[blockIdx.x];
+    const EwSys s = sys[tile.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, r = lane & 31;
+    const int a0 = tile.y;
+    if (PER) ew_stage_tables(T, tab, NM, s.first_atom + a0, s.n_atoms - a0);
+    if (threadIdx.x < 32) {
+        float4 p = make_float4(0.f, 0.f, 0.f, 0.f), u = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a0 + (int)threadIdx.x < s.n_atoms) {
+            const float* q = pos + 3 * (int64_t)(s.first_atom + a0 + threadIdx.x);
+            const float* v = U + 3 * (int64_t)(s.first_atom + a0 + threadIdx.x);
+            p = make_float4(q[0], q[1], q[2], 1.f);
+            u = make_float4(v[0], v[1], v[2], 0.f);
+        }
+        ps[threadIdx.x] = p;
+        us[threadIdx.x] = u;
+    }
+    __syncthreads();
+    const bool vi = a0 + r < s.n_atoms;
+    const float* gi = G + (int64_t)(s.first_atom + a0 + r) * C;
+    const float* qi = Q + (int64_t)(s.first_atom + a0 + r) * C;
+    const int ncols = PER ? s.n_k : s.n_atoms;
+    const int nsteps = (2 * C + 7) / 8;
+    float f[16][3];
+#pragma unroll
+    for (int i = 0; i < 16; i++) f[i][0] = f[i][1] = f[i][2] = 0.f;
+    for (int col0 = wave * 32; col0 < ncols; col0 += 128) {
+        const int col = col0 + r;
+        const bool vc = col < ncols;
+        f32x16 acc_r, acc_i, acu_r, acu_i;  // (open: acc_r alone)
+#pragma unroll
+        for (int i = 0; i < 16; i++) acc_r[i] = acc_i[i] = acu_r[i] = acu_i[i] = 0.f;
+        if (PER) {
+            const int64_t kabs = s.first_k + col;
+            const float *re1 = Sq + kabs * 2 * C, *re2 = Sg + kabs * 2 * C, *ur1 = Suq + kabs * 2 * C, *ur2 = Sug + kabs * 2 * C;
+            for (int t = 0; t < nsteps; t++) {
+                const int ch = 8 * t + 4 * half;
+                const f32x4 A = ew_load4(vi, gi, qi, ch, C, vec);
+                const f32x4 Br = ew_load4(vc, re1, re2, ch, C, vec), Bi = ew_load4(vc, re1 + C, re2 + C, ch, C, vec);
+                const f32x4 Ur = ew_load4(vc, ur1, ur2, ch, C, vec), Ui = ew_load4(vc, ur1 + C, ur2 + C, ch, C, vec);
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Br[u], acc_r, 0, 0, 0);
+                    acc_i = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Bi[u], acc_i, 0, 0, 0);
+                    acu_r = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Ur[u], acu_r, 0, 0, 0);
+                    acu_i = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Ui[u], acu_i, 0, 0, 0);
+                }
+            }
+            int n0 = 0, n1 = 0, n2 = 0;
+            float kx = 0.f, ky = 0.f, kz = 0.f;
+            if (vc) {
+                const EwK k = klist[s.first_k + col];
+                n0 = k.n0; n1 = k.n1; n2 = k.n2; kx = k.kx; ky = k.ky; kz = k.kz;
+            }
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
+                float c, sn;
+                ew_phase(T + row * 3 * NM, NM, n0, n1, n2, c, sn);
+                const float4 u = us[row];
+                const float ku = kx * u.x + ky * u.y + kz * u.z;
+                const float x = (c * acu_r[i] + sn * acu_i[i]) - ku * (c * acc_r[i] + sn * acc_i[i]);
+                f[i][0] += kx * x; f[i][1] += ky * x; f[i][2] += kz * x;
+            }
+        } else {
+            const float* a1 = Q + (int64_t)(s.first_atom + col) * C;
+            const float* a2 = G + (int64_t)(s.first_atom + col) * C;
+            for (int t = 0; t < nsteps; t++) {
+                const int ch = 8 * t + 4 * half;
+                const f32x4 A = ew_load4(vi, gi, qi, ch, C, vec);
+                const f32x4 Ba = ew_load4(vc, a1, a2, ch, C, vec);
+#pragma unroll
+                for (int u = 0; u < 4; u++) acc_r = __builtin_amdgcn_mfma_f32_32x32x2f32(A[u], Ba[u], acc_r, 0, 0, 0);
+            }
+            float3 pj = make_float3(0.f, 0.f, 0.f), uj = make_float3(0.f, 0.f, 0.f);
+            if (vc) {
+                const float* q = pos + 3 * (int64_t)(s.first_atom + col);
+                const float* v = U + 3 * (int64_t)(s.first_atom + col);
+                pj = make_float3(q[0], q[1], q[2]);
+                uj = make_float3(v[0], v[1], v[2]);
+            }
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
+                const float4 pi = ps[row];
+                if (!vc || pi.w == 0.f || col == a0 + row) continue;
+                const float4 u = us[row];
+                const float dx = pj.x - pi.x, dy = pj.y - pi.y, dz = pj.z - pi.z;
+                const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+                const float nx = dx / d, ny = dy / d, nz = dz / d;
+                const float ex = uj.x - u.x, ey = uj.y - u.y, ez = uj.z - u.z;
+                const float nd = nx * ex + ny * ey + nz * ez;
+                const float kd = ew_open_kernel_d(d, inv_R) / d, kdd = ew_open_kernel_dd(d, inv_R);
+                const float along = (kdd - kd) * nd;  // M_K e = (K'' - K'/d) (n.e) n + (K'/d) e
+                f[i][0] -= acc_r[i] * (along * nx + kd * ex);
+                f[i][1] -= acc_r[i] * (along * ny + kd * ey);
+                f[i][2] -= acc_r[i] * (along * nz + kd * ez);
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const int row = (i & 3) + 8 * (i >> 2) + 4 * half;
+#pragma unroll
+        for (int a = 0; a < 3; a++) {
+            float v = f[i][a];
+#pragma unroll
+            for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            if (r == 0) red[(wave * 32 + row) * 3 + a] = v;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 96) {
+        const int row = threadIdx.x / 3, a = threadIdx.x % 3;
+        if (a0 + row < s.n_atoms) {
+            float v = red[row * 3 + a];
+            for (int w = 1; w < 4; w++) v += red[(w * 32 + row) * 3 + a];
+            F[3 * (int64_t)(s.first_atom + a0 + row) + a] = (float)EW_PREFACTOR * v;
+        }
+    }
+}
+
+// The exclusion rows' share of all three results of pet_ewald_second, one wave per atom, fp64 like k_ew_edge_bwd. Per edge
+// p = (i -> j, S) with e = u_j - u_i, n = D / d:  out_g[i] -= P w'(d) (n.e) q_j,  out_q[i] -= P w'(d) (n.e) g_j  and
+// out_r[i] += P (B_p + B'_p) M_w e,  M_w = w'' n n^T + (w'/d) (I - n n^T). Lanes take one edge each of a chunk of 64 for w', w''
+// and M_w e, then all lanes walk the chunk's edges for the channel sums. Adds F2 (k_ew_force2) into out_r for every atom.
+// A null result is not formed (ew_second_run): without out_r neither F2 nor the channel products are read, without out_g
+// (out_q) Q (G) is not read in the channel sums; each sum is its own accumulator, so the others keep their bits.
+__global__ __launch_bounds__(64) void k_ew_edge_second(const EwSys* __restrict__ sys, const int* __restrict__ gsys,
+                                                       const int* __restrict__ rowptr, const int* __restrict__ nbr,
+                                                       const float4* __restrict__ geo, const float* __restrict__ G,
+                                                       const float* __restrict__ Q, const float* __restrict__ U,
+                                                       const float* __restrict__ F2, int C, double sigma, double Rcut,
+                                                       float* __restrict__ out_g, float* __restrict__ out_q,
+                                                       float* __restrict__ out_r) {
+    __shared__ int sj[64];
+    __shared__ double sco[64], sm[64][3];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const EwSys& s = sys[gsys[i]];
+    double fp[3] = {0.0, 0.0, 0.0};
+    if (s.periodic) {
+        const double inv_a = 1.0 / (sqrt(2.0) * sigma);
+        const float* gi = out_r ? G + (int64_t)i * C : nullptr;
+        const float* qi = out_r ? Q + (int64_t)i * C : nullptr;
+        const double ui[3] = {(double)U[3 * (int64_t)i], (double)U[3 * (int64_t)i + 1], (double)U[3 * (int64_t)i + 2]};
+        const int p1 = rowptr[i + 1];
+        for (int p0 = rowptr[i]; p0 < p1; p0 += 64) {
+            __syncthreads();
+            const int p = p0 + lane;
+            int j = i;
+            double co = 0.0, m[3] = {0.0, 0.0, 0.0};
+            if (p < p1) {
+                j = nbr[p];
+                const float4 g4 = geo[p];
+                const double d = (double)g4.w;
+                if (d < Rcut && j != i) {
+                    const double x = d * inv_a, er = erf(x), der = 2.0 / sqrt(EW_PI) * inv_a * exp(-x * x), dder = -2.0 * x * inv_a * der;
+                    const double cutf = 0.5 * (1.0 + cos(EW_PI * d / Rcut)), dcut = -0.5 * EW_PI / Rcut * sin(EW_PI * d / Rcut);
+                    const double ddcut = -0.5 * (EW_PI / Rcut) * (EW_PI / Rcut) * cos(EW_PI * d / Rcut);
+                    const double n0 = er * cutf, n1 = der * cutf + er * dcut, n2 = dder * cutf + 2.0 * der * dcut + er * ddcut;
+                    const double dw = n1 / d - n0 / (d * d), ddw = n2 / d - 2.0 * n1 / (d * d) + 2.0 * n0 / (d * d * d);
+                    const double n[3] = {(double)g4.x / d, (double)g4.y / d, (double)g4.z / d};
+                    double e[3], nd = 0.0;
+#pragma unroll
+                    for (int a = 0; a < 3; a++) {
+                        e[a] = (double)U[3 * (int64_t)j + a] - ui[a];
+                        nd += n[a] * e[a];
+                    }
+                    co = -EW_PREFACTOR * dw * nd;
+#pragma unroll
+                    for (int a = 0; a < 3; a++) m[a] = EW_PREFACTOR * ((ddw - dw / d) * nd * n[a] + dw / d * e[a]);
+                }
+            }
+            sj[lane] = j;
+            sco[lane] = co;
+            sm[lane][0] = m[0]; sm[lane][1] = m[1]; sm[lane][2] = m[2];
+            __syncthreads();
+            const int ne = min(64, p1 - p0);
+            for (int q = 0; out_r && q < ne; q++) {
+                const int jq = sj[q];
+                if (jq == i) continue;
+                const float* gj = G + (int64_t)jq * C;
+                const float* qj = Q + (int64_t)jq * C;
+                float b = 0.f, bp = 0.f;
+                for (int c = lane; c < C; c += 64) {
+                    b += gi[c] * qj[c];
+                    bp += gj[c] * qi[c];
+                }
+                const double bb = (double)wsum(b) + (double)wsum(bp);
+#pragma unroll
+                for (int a = 0; a < 3; a++) fp[a] += bb * sm[q][a];
+            }
+            for (int c = lane; c < C; c += 64) {
+                double ag = 0.0, aq = 0.0;
+                for (int q = 0; q < ne; q++) {
+                    const int64_t o = (int64_t)sj[q] * C + c;
+                    if (out_g) ag += sco[q] * (double)Q[o];
+                    if (out_q) aq += sco[q] * (double)G[o];
+                }
+                if (out_g) out_g[(int64_t)i * C + c] += (float)ag;
+                if (out_q) out_q[(int64_t)i * C + c] += (float)aq;
+            }
+        }
+    }
+    if (out_r && lane < 3) out_r[3 * (int64_t)i + lane] += (float)((double)F2[3 * (int64_t)i + lane] + fp[lane]);
+}
+
 }  // namespace
 
 // P3M mode (csrc/p3m.hip): mesh descriptors and influence functions in place of k lists
@@ -462,6 +685,23 @@ struct P3mPlan;
 void p3m_release(P3mPlan* p);
 // reads every system's cell^{-1}, Omega, pbc and atom count from sys and leaves its range of reduction chunks in first_k / n_k
 int p3m_plan_build(double sigma, double spacing, int nodes, const double* h_cells, std::vector<EwSys>& sys, P3mPlan** out);
+
+}  // namespace pet
+
+struct pet_ewald;
+
+namespace pet {
+struct Graph;
+// the mesh operator behind lr_potential / lr_backward / lr_second (ewald.hip dispatches on the handle's mode): a planned
+// P3M-mode handle WITH a transform hook, on one workspace of p3m_lr_workspace_bytes that lies ws_offset bytes into the running
+// entry point's d_workspace (the hook's offsets count from there)
+int64_t p3m_lr_workspace_bytes(const pet_ewald* e, int C);
+int p3m_lr_potential(const pet_ewald* e, const Graph& g, const float* pos, const float* X, int C, float* out, void* ws,
+                     hipStream_t st, int64_t ws_offset);
+int p3m_lr_backward(const pet_ewald* e, const Graph& g, const float* pos, const float* Q, const float* G, int C, float* gq,
+                    float* gpos, void* ws, hipStream_t st, int64_t ws_offset);
+int p3m_lr_second(const pet_ewald* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                  const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st, int64_t ws_offset);
 
 }  // namespace pet
 
@@ -475,6 +715,10 @@ struct pet_ewald {
     int nm = 1;
     int p3m_nodes = 0;         // 0: Ewald mode; 1..5: P3M mode (pet_ewald_set_p3m)
     P3mPlan* p3m = nullptr;    // owned; rebuilt by every plan of a P3M-mode handle
+    // the caller's rfftn / irfftn between two offsets of the running entry point's workspace (pet_p3m_set_transform); kept
+    // across plans. Without one a P3M-mode handle has no second-order entry and no place in the dual pass.
+    int (*p3m_transform)(void*, int32_t, int64_t, int64_t, int32_t) = nullptr;
+    void* p3m_transform_user = nullptr;
     std::vector<EwSys> sys;
     std::vector<int2> ktiles, atiles_p, atiles_n;
     // device copies (made by pet_ewald_plan, kept until the next plan / destroy)

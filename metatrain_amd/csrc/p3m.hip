@@ -8,6 +8,10 @@
 //   pet_p3m_filter   k_p3m_filter: half spectrum times G^/Omega (k_p3m_influence at plan time, fp64 -> fp32)
 //   pet_p3m_finish   k_p3m_gather, then ew_local_forward (k_ew_pairs / k_ew_colsum / k_ew_finish)
 //   pet_p3m_backward k_p3m_force, then ew_local_backward (k_ew_force<false>, k_ew_edge_bwd, k_ew_cell) with k_p3m_cell before k_ew_cell
+// Second order (pet_p3m_second) and the dual pass (p3m_lr_*) run the whole operator inside ONE call: the
+// transforms come back through the handle's hook (pet_p3m_set_transform), between a mesh and a half spectrum inside the call's
+// own workspace. k_p3m_spread2 / k_p3m_gather2 / k_p3m_force2 are the three mesh kernels with the tangent and Hessian weights
+// beside the plain ones; the local terms are long_range.h's (k_ew_pairs<true>, k_ew_force2<false>, k_ew_edge_second).
 // Layout. CHANNEL-FIRST: the mesh of a system is [C, N_x, N_y, N_z] (z fastest), its half spectrum [C, N_x, N_y, N_z/2 + 1]
 // complex; the meshes of a batch's periodic, non-empty systems are packed one after another (system s starts at mesh_off_s * C).
 // The transforms run over contiguous planes with batch stride M and need no copy; the price is on this side: k_p3m_spread owns
@@ -148,11 +152,15 @@ __global__ __launch_bounds__(256) void k_p3m_influence(P3mSysD m, double sigma, 
 }
 
 // ---- binning ------------------------------------------------------------------------------------------------------------------
-// per atom of a periodic system: weights and their derivatives by u (fp64, rounded once), the wrapped stencil origin and its bin
+// per atom of a periodic system: weights and their derivatives by u (fp64, rounded once), the wrapped stencil origin and its bin.
+// With d2wts (pet_p3m_second): the second derivatives M_{p-2}(x) - 2 M_{p-2}(x-1) + M_{p-2}(x-2) as well, and with a direction
+// Ur [N, 3] the atom's du = N (.) (u_r cell^{-1}) in mesh units (zero without one, and on atoms of open systems).
 __global__ __launch_bounds__(256) void k_p3m_bin_count(const float* __restrict__ pos, const int* __restrict__ gsys,
                                                        const EwSys* __restrict__ sys, const P3mSysD* __restrict__ msys, int N,
                                                        int p, float* __restrict__ wts, float* __restrict__ dwts,
-                                                       int4* __restrict__ org, int* __restrict__ start) {
+                                                       int4* __restrict__ org, int* __restrict__ start,
+                                                       float* __restrict__ d2wts, const float* __restrict__ Ur,
+                                                       float* __restrict__ du) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
     const int si = gsys[i];
@@ -162,8 +170,11 @@ __global__ __launch_bounds__(256) void k_p3m_bin_count(const float* __restrict__
     for (int ax = 0; ax < 3; ax++) {
         float* w = wts + ((int64_t)i * 3 + ax) * p;
         float* dw = dwts + ((int64_t)i * 3 + ax) * p;
+        float* d2w = d2wts ? d2wts + ((int64_t)i * 3 + ax) * p : nullptr;
         if (!s.periodic) {
             for (int t = 0; t < p; t++) w[t] = dw[t] = 0.f;
+            for (int t = 0; d2w && t < p; t++) d2w[t] = 0.f;
+            if (du) du[3 * (int64_t)i + ax] = 0.f;
             continue;
         }
         double f = (double)pos[3 * (int64_t)i] * s.inv[ax] + (double)pos[3 * (int64_t)i + 1] * s.inv[3 + ax] +
@@ -175,7 +186,13 @@ __global__ __launch_bounds__(256) void k_p3m_bin_count(const float* __restrict__
             const double x = u - (base + (double)t) + 0.5 * (double)p;
             w[t] = (float)p3m_bspline(p, x);
             dw[t] = (float)(p3m_bspline(p - 1, x) - p3m_bspline(p - 1, x - 1.0));
+            if (d2w) d2w[t] = (float)(p3m_bspline(p - 2, x) - 2.0 * p3m_bspline(p - 2, x - 1.0) + p3m_bspline(p - 2, x - 2.0));
         }
+        if (du)
+            du[3 * (int64_t)i + ax] =
+                Ur ? (float)((double)m.n[ax] * ((double)Ur[3 * (int64_t)i] * s.inv[ax] + (double)Ur[3 * (int64_t)i + 1] * s.inv[3 + ax] +
+                                                (double)Ur[3 * (int64_t)i + 2] * s.inv[6 + ax]))
+                   : 0.f;
         o[ax] = p3m_wrap((int)base, m.n[ax]);
     }
     int key = -1;
@@ -404,6 +421,163 @@ __global__ __launch_bounds__(256) void k_p3m_force(const int* __restrict__ gsys,
     }
 }
 
+// ---- second order (pet_p3m_second) -----------------------------------------------------------------------
+// Positions enter the mesh sum A = W^T K W through W alone. Along a direction u_r, with du_i = N (.) (u_r,i cell^{-1}) per atom,
+//   (D_u W)_i(node) = dW_x du_x W_y W_z + W_x dW_y du_y W_z + W_x W_y dW_z du_z                  (the TANGENT weight)
+//   (grad grad W . du)_a = d/du_a of the tangent weight                                          (the Hessian weight)
+// The three kernels below are k_p3m_spread, k_p3m_gather and k_p3m_force with those weights beside the plain ones, in the same
+// walks and orders.
+
+// k_p3m_spread with two operands: mesh = W X1 + (D_u W) X2, either may be null (not both)
+__global__ __launch_bounds__(256) void k_p3m_spread2(const int2* __restrict__ tiles, const P3mSysD* __restrict__ msys,
+                                                     const int* __restrict__ start, const int* __restrict__ order,
+                                                     const float* __restrict__ wts, const float* __restrict__ dwts,
+                                                     const float* __restrict__ du, int p, const float* __restrict__ X1,
+                                                     const float* __restrict__ X2, int C, float* __restrict__ mesh) {
+    const int2 tile = tiles[blockIdx.x];
+    const P3mSysD& m = msys[tile.x];
+    const int M = m.n[0] * m.n[1] * m.n[2];
+    const int idx = tile.y + threadIdx.x;
+    if (idx >= M) return;
+    const int z = idx % m.n[2], y = (idx / m.n[2]) % m.n[1], x = idx / (m.n[2] * m.n[1]);
+    const int c0 = blockIdx.y * P3M_CH;
+    float acc[P3M_CH];
+#pragma unroll
+    for (int u = 0; u < P3M_CH; u++) acc[u] = 0.f;
+    for (int tx = 0; tx < p; tx++) {
+        const int bx = p3m_wrap(x - tx, m.n[0]);
+        for (int ty = 0; ty < p; ty++) {
+            const int by = p3m_wrap(y - ty, m.n[1]);
+            for (int tz = 0; tz < p; tz++) {
+                const int bz = p3m_wrap(z - tz, m.n[2]);
+                const int64_t bin = m.moff + ((int64_t)bx * m.n[1] + by) * m.n[2] + bz;
+                const int lo = start[bin], hi = start[bin + 1];
+                for (int a = lo; a < hi; a++) {
+                    const int j = order[a];
+                    const float* wj = wts + (int64_t)j * 3 * p;
+                    const float wx = wj[tx], wy = wj[p + ty], wz = wj[2 * p + tz];
+                    if (X1) {
+                        const float w = wx * wy * wz;
+                        const float* row = X1 + (int64_t)j * C + c0;
+#pragma unroll
+                        for (int u = 0; u < P3M_CH; u++)
+                            if (c0 + u < C) acc[u] += w * row[u];
+                    }
+                    if (X2) {
+                        const float* dj = dwts + (int64_t)j * 3 * p;
+                        const float* uj = du + 3 * (int64_t)j;
+                        const float tw = dj[tx] * uj[0] * wy * wz + wx * (dj[p + ty] * uj[1]) * wz + wx * wy * (dj[2 * p + tz] * uj[2]);
+                        const float* row = X2 + (int64_t)j * C + c0;
+#pragma unroll
+                        for (int u = 0; u < P3M_CH; u++)
+                            if (c0 + u < C) acc[u] += tw * row[u];
+                    }
+                }
+            }
+        }
+    }
+    float* out = mesh + m.moff * C + idx;
+#pragma unroll
+    for (int u = 0; u < P3M_CH; u++)
+        if (c0 + u < C) out[(int64_t)(c0 + u) * M] = acc[u];
+}
+
+// k_p3m_gather of two mesh potentials in one stencil walk: V[i][c] = scale sum_nodes [ W phi_a + (D_u W) phi_b ], phi_b may be null.
+// The tangent weights of an atom add up to zero, so on an atom whose surroundings are symmetric (a one-atom cell) the result
+// is what is left of terms 1e4 times its size: the products and the two sums are fp64, which keeps the kernel's own rounding
+// out of that residue (the walk waits for its node loads, not for these).
+__global__ __launch_bounds__(256) void k_p3m_gather2(const int* __restrict__ gsys, const P3mSysD* __restrict__ msys,
+                                                     const int4* __restrict__ org, const float* __restrict__ wts,
+                                                     const float* __restrict__ dwts, const float* __restrict__ du, int p,
+                                                     const float* __restrict__ phi_a, const float* __restrict__ phi_b, int N,
+                                                     int C, float scale, float* __restrict__ V) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= N) return;
+    const int4 o = org[i];
+    if (o.w < 0) return;
+    const P3mSysD& m = msys[gsys[i]];
+    const int M = m.n[0] * m.n[1] * m.n[2];
+    const float* wi = wts + (int64_t)i * 3 * p;
+    const float* di = dwts + (int64_t)i * 3 * p;
+    const double u0 = du[3 * (int64_t)i], u1 = du[3 * (int64_t)i + 1], u2 = du[3 * (int64_t)i + 2];
+    for (int c = lane; c < C; c += 64) {
+        const float* pa = phi_a + m.moff * C + (int64_t)c * M;
+        const float* pb = phi_b ? phi_b + m.moff * C + (int64_t)c * M : nullptr;
+        double acc_a = 0.0, acc_b = 0.0;
+        for (int tx = 0; tx < p; tx++) {
+            const int ix = p3m_wrap(o.x + tx, m.n[0]);
+            for (int ty = 0; ty < p; ty++) {
+                const int iy = p3m_wrap(o.y + ty, m.n[1]);
+                const double wxy = (double)wi[tx] * (double)wi[p + ty];
+                const double txy = (double)di[tx] * u0 * (double)wi[p + ty] + (double)wi[tx] * ((double)di[p + ty] * u1);
+                for (int tz = 0; tz < p; tz++) {
+                    const int iz = p3m_wrap(o.z + tz, m.n[2]);
+                    const int64_t node = ((int64_t)ix * m.n[1] + iy) * m.n[2] + iz;
+                    const double wz = wi[2 * p + tz];
+                    acc_a += wxy * wz * (double)pa[node];
+                    if (pb) acc_b += (txy * wz + wxy * ((double)di[2 * p + tz] * u2)) * (double)pb[node];
+                }
+            }
+        }
+        V[(int64_t)i * C + c] = (float)((double)scale * (acc_a + acc_b));
+    }
+}
+
+// k_p3m_force with the second-order terms, from four mesh potentials in one walk (phi_q = K W q, phi_g = K W g,
+// phi_a = K (W u_q + (D_u W) q), phi_dg = K (D_u W) g):
+//   F_i = P sum_c sum_nodes { grad W [ u_q phi_g + g phi_a + q phi_dg ] + (grad grad W . du) [ g phi_q + q phi_g ] }
+// = the mesh part of grad_r Phi(r; u_q, g) + H_Phi(r; g, q) u_r. Uq may be null (zero). fp64 products and per-lane sums, as
+// k_p3m_gather2 (the gradient weights add up to zero as well); the butterfly over channels is the fp32 one of k_ew_force.
+__global__ __launch_bounds__(256) void k_p3m_force2(const int* __restrict__ gsys, const P3mSysD* __restrict__ msys,
+                                                    const int4* __restrict__ org, const float* __restrict__ wts,
+                                                    const float* __restrict__ dwts, const float* __restrict__ d2wts,
+                                                    const float* __restrict__ du, int p, const float* __restrict__ phi_q,
+                                                    const float* __restrict__ phi_g, const float* __restrict__ phi_a,
+                                                    const float* __restrict__ phi_dg, const float* __restrict__ G,
+                                                    const float* __restrict__ Q, const float* __restrict__ Uq, int N, int C,
+                                                    float* __restrict__ F) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= N) return;
+    const int4 o = org[i];
+    if (o.w < 0) return;
+    const P3mSysD& m = msys[gsys[i]];
+    const int M = m.n[0] * m.n[1] * m.n[2];
+    const float* wi = wts + (int64_t)i * 3 * p;
+    const float* di = dwts + (int64_t)i * 3 * p;
+    const float* ei = d2wts + (int64_t)i * 3 * p;
+    const double u0 = du[3 * (int64_t)i], u1 = du[3 * (int64_t)i + 1], u2 = du[3 * (int64_t)i + 2];
+    double f0 = 0.0, f1 = 0.0, f2 = 0.0;
+    for (int c = lane; c < C; c += 64) {
+        const int64_t plane = m.moff * C + (int64_t)c * M;
+        const float *pq = phi_q + plane, *pg = phi_g + plane, *pa = phi_a + plane, *pd = phi_dg + plane;
+        const double gi = G[(int64_t)i * C + c], qi = Q[(int64_t)i * C + c], ui = Uq ? Uq[(int64_t)i * C + c] : 0.f;
+        for (int tx = 0; tx < p; tx++) {
+            const int ix = p3m_wrap(o.x + tx, m.n[0]);
+            const double wx = wi[tx], dx = di[tx], bx = dx * u0, ex = (double)ei[tx] * u0;
+            for (int ty = 0; ty < p; ty++) {
+                const int iy = p3m_wrap(o.y + ty, m.n[1]);
+                const double wy = wi[p + ty], dy = di[p + ty], by = dy * u1, ey = (double)ei[p + ty] * u1;
+                for (int tz = 0; tz < p; tz++) {
+                    const int iz = p3m_wrap(o.z + tz, m.n[2]);
+                    const double wz = wi[2 * p + tz], dz = di[2 * p + tz], bz = dz * u2, ez = (double)ei[2 * p + tz] * u2;
+                    const int64_t node = ((int64_t)ix * m.n[1] + iy) * m.n[2] + iz;
+                    const double vq = pq[node], vg = pg[node];
+                    const double v1 = ui * vg + gi * (double)pa[node] + qi * (double)pd[node];
+                    const double v2 = gi * vq + qi * vg;
+                    f0 += dx * wy * wz * v1 + (ex * wy * wz + dx * (by * wz + wy * bz)) * v2;
+                    f1 += wx * dy * wz * v1 + (ey * wx * wz + dy * (bx * wz + wx * bz)) * v2;
+                    f2 += wx * wy * dz * v1 + (ez * wx * wy + dz * (bx * wy + wx * by)) * v2;
+                }
+            }
+        }
+    }
+    const float s0 = wsum((float)f0), s1 = wsum((float)f1), s2 = wsum((float)f2);
+    if (lane < 3) {
+        const double a0 = (double)s0 * m.n[0], a1 = (double)s1 * m.n[1], a2 = (double)s2 * m.n[2];
+        F[3 * (int64_t)i + lane] = (float)(EW_PREFACTOR * (m.inv[3 * lane] * a0 + m.inv[3 * lane + 1] * a1 + m.inv[3 * lane + 2] * a2));
+    }
+}
+
 // the reciprocal part of dL/dcell through G^/Omega: per chunk of P3M_CHUNK half-spectrum points of one system,
 // kpart[chunk][9] = P sum_n w_n Re(conj(g^_n) q^_n) d(G^_n/Omega)/dcell (fp64, points in index order per thread, then a fixed
 // tree over the block); k_ew_cell adds a system's chunks in order
@@ -487,12 +661,14 @@ int p3m_check(const pet_ewald_t* e, const pet_graph_t* pg, int32_t C, const void
 }
 
 // weights, origins and the stable counting sort of the atoms by origin bin
-int p3m_bin(const pet_ewald_t* e, const Graph& g, const float* pos, const P3mWs& w, hipStream_t st) {
+int p3m_bin(const pet_ewald_t* e, const Graph& g, const float* pos, const P3mWs& w, hipStream_t st, float* d2wts = nullptr,
+            const float* Ur = nullptr, float* du = nullptr) {
     const P3mPlan* mp = e->p3m;
     const int N = (int)e->n_atoms, nb = (int)mp->m_total + 1;
     PET_HIP_CHECK(hipMemsetAsync(w.start, 0, (size_t)nb * sizeof(int), st));
     PET_HIP_CHECK(hipMemsetAsync(w.fill, 0, (size_t)nb * sizeof(int), st));
-    k_p3m_bin_count<<<cdiv(N, 256), 256, 0, st>>>(pos, g.sys, e->d_sys, mp->d_sys, N, e->p3m_nodes, w.wts, w.dwts, w.org, w.start);
+    k_p3m_bin_count<<<cdiv(N, 256), 256, 0, st>>>(pos, g.sys, e->d_sys, mp->d_sys, N, e->p3m_nodes, w.wts, w.dwts, w.org, w.start,
+                                                      d2wts, Ur, du);
     const int blocks = cdiv(nb, 1024);
     k_p3m_bin_scan1<<<blocks, 256, 0, st>>>(w.start, nb, w.bsum);
     k_p3m_bin_scan2<<<1, 256, 0, st>>>(w.bsum, blocks);
@@ -503,7 +679,185 @@ int p3m_bin(const pet_ewald_t* e, const Graph& g, const float* pos, const P3mWs&
     return PET_OK;
 }
 
+// The workspace of pet_p3m_second and of the dual pass: that of the staged entry points, then the second-derivative weights,
+// the per-atom directions, FOUR packed meshes and ONE packed half spectrum (the transforms of an entry point run one after
+// another on its stream). The byte offsets are what the transform hook is given: they count from the d_workspace of the entry
+// point that is running, ws_offset bytes before this workspace (the dual pass keeps its own rows in front of the operator's).
+enum { MESH_Q = 0, MESH_G = 1, MESH_A = 2, MESH_DG = 3 };
+struct P3mWs2 {
+    P3mWs w;
+    float *d2wts, *du;
+    float* mesh[4];
+    float2* spec;
+    int64_t mesh_off[4], spec_off;
+};
+
+size_t p3m_carve2(const pet_ewald_t* e, int64_t C, void* base, P3mWs2& w2, int64_t ws_offset = 0) {
+    Carver c(base);
+    c.off = p3m_carve(e, C, base, w2.w);
+    const P3mPlan* mp = e->p3m;
+    const size_t N = (size_t)std::max<int64_t>(e->n_atoms, 1), p = (size_t)e->p3m_nodes;
+    w2.d2wts = c.take<float>(N * 3 * p);
+    w2.du = c.take<float>(N * 3);
+    for (int k = 0; k < 4; k++) {
+        w2.mesh_off[k] = ws_offset + (int64_t)c.off;
+        w2.mesh[k] = c.take<float>((size_t)std::max<int64_t>(mp->m_total, 1) * C);
+    }
+    w2.spec_off = ws_offset + (int64_t)c.off;
+    w2.spec = c.take<float2>((size_t)std::max<int64_t>(mp->s_total, 1) * C);
+    return c.off;
+}
+
+// mesh[slot] <- K mesh[slot]: the hook's rfftn into the half spectrum, the filter, the hook's irfftn back
+int p3m_solve(const pet_ewald_t* e, int C, const P3mWs2& w2, int slot, hipStream_t st) {
+    const P3mPlan* mp = e->p3m;
+    if (mp->stiles.empty()) return PET_OK;
+    for (int inverse = 0; inverse < 2; inverse++) {
+        const int rc = e->p3m_transform(e->p3m_transform_user, inverse, w2.mesh_off[slot], w2.spec_off, C);
+        PET_REQUIRE(rc == 0, PET_ERR_ARGUMENT,
+                    "the transform hook (pet_p3m_set_transform) returned " + std::to_string(rc) + " for the " +
+                        (inverse ? "inverse" : "forward") + " transform");
+        if (!inverse)
+            k_p3m_filter<<<dim3((unsigned)mp->stiles.size(), (unsigned)std::min(C, 256)), 256, 0, st>>>(
+                mp->d_stiles, mp->d_sys, mp->d_infl, C, w2.spec);
+    }
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
+}
+
+// mesh[slot] <- K W X with the kernels of the staged entry points (the dual pass' first-order calls keep their bits)
+int p3m_potential_mesh(const pet_ewald_t* e, const float* X, int C, const P3mWs2& w2, int slot, hipStream_t st) {
+    const P3mPlan* mp = e->p3m;
+    if (mp->mtiles.empty()) return PET_OK;
+    const bool vec = C % P3M_CH == 0 && ((uintptr_t)X & 15) == 0;
+    k_p3m_spread<<<dim3((unsigned)mp->mtiles.size(), (unsigned)cdiv(C, P3M_CH)), 256, 0, st>>>(
+        mp->d_mtiles, mp->d_sys, w2.w.start, w2.w.order, w2.w.wts, e->p3m_nodes, X, C, vec, w2.mesh[slot]);
+    return p3m_solve(e, C, w2, slot, st);
+}
+
+// pet_p3m_second with selectable results, as ew_second_run: a null out_q / out_g / out_r is not formed, and the meshes,
+// transform pairs and launches that serve it alone are skipped. Q may be null where only out_q is asked for, G where only
+// out_g is. Transform pairs with both cotangents: out_g alone 2 (phi_q, phi_a), out_q alone 2 (phi_g, phi_dg), out_r or all
+// three 4; with u_q alone 1 / 0 / 2, with u_r alone as with both.
+int p3m_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                   const float* Ur, int C, float* out_q, float* out_g, float* out_r, const P3mWs2& w2, hipStream_t st) {
+    const P3mPlan* mp = e->p3m;
+    const P3mWs& w = w2.w;
+    const int N = (int)e->n_atoms, p = e->p3m_nodes;
+    const bool per = mp->m_total > 0;
+    const unsigned cy = (unsigned)cdiv(C, 256), nn = (unsigned)e->atiles_n.size(), na = (unsigned)cdiv(N, 4);
+    const float inv_R = (float)(1.0 / e->cutoff);
+    ProfScope ps(out_q && out_g && out_r ? "p3m_second" : out_g ? "p3m_second_g" : out_r ? "p3m_second_qr" : "p3m_second_q", st,
+                 0.0, 0.0);
+    PET_TRY(p3m_bin(e, g, pos, w, st, w2.d2wts, Ur, w2.du));
+    auto mesh_of = [&](int slot, const float* X1, const float* X2) -> int {
+        if (!per) return PET_OK;
+        k_p3m_spread2<<<dim3((unsigned)mp->mtiles.size(), (unsigned)cdiv(C, P3M_CH)), 256, 0, st>>>(
+            mp->d_mtiles, mp->d_sys, w.start, w.order, w.wts, w.dwts, w2.du, p, X1, X2, C, w2.mesh[slot]);
+        return p3m_solve(e, C, w2, slot, st);
+    };
+    auto gather = [&](const float* phi_a, const float* phi_b, float scale, float* out) {
+        if (per)
+            k_p3m_gather2<<<na, 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, w.dwts, w2.du, p, phi_a, phi_b, N, C, scale, out);
+    };
+    if (Ur && (out_g || out_r)) PET_TRY(mesh_of(MESH_Q, Q, nullptr));
+    if (out_r || (Ur && out_q)) PET_TRY(mesh_of(MESH_G, G, nullptr));
+    if (out_g || out_r) PET_TRY(mesh_of(MESH_A, Uq, Ur ? Q : nullptr));  // W u_q + (D_u W) q as ONE mesh
+    if (Ur && (out_q || out_r)) PET_TRY(mesh_of(MESH_DG, nullptr, G));
+    if (Uq) {
+        // out_g = A u_q + (D_u A) q on the mesh, then the local terms of A u_q; out_r = grad_r Phi(r; u_q, g): the first-order
+        // adjoint with (g, q) := (u_q, g), whose mesh part waits for k_p3m_force2 where there is a direction
+        if (out_g) {
+            gather(w2.mesh[MESH_A], Ur ? w2.mesh[MESH_Q] : nullptr, 1.f, out_g);
+            PET_TRY(ew_local_forward(e, g, pos, Uq, C, out_g, w.loc.sum_g, st));
+        }
+        if (out_r) {
+            if (Ur) PET_HIP_CHECK(hipMemsetAsync(w.loc.F, 0, (size_t)N * 3 * sizeof(float), st));
+            else if (per)
+                k_p3m_force<<<na, 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, w.dwts, p, w2.mesh[MESH_G], w2.mesh[MESH_A], Uq, G, N,
+                                                C, w.loc.F);
+            PET_TRY(ew_local_backward(e, g, pos, G, Uq, C, w.loc, out_r, nullptr, st, [] {}));
+        }
+    } else {
+        if (out_g) {
+            PET_HIP_CHECK(hipMemsetAsync(out_g, 0, (size_t)N * C * sizeof(float), st));
+            gather(w2.mesh[MESH_A], w2.mesh[MESH_Q], (float)EW_PREFACTOR, out_g);
+        }
+        if (out_r) PET_HIP_CHECK(hipMemsetAsync(out_r, 0, (size_t)N * 3 * sizeof(float), st));
+    }
+    if (out_q) PET_HIP_CHECK(hipMemsetAsync(out_q, 0, (size_t)N * C * sizeof(float), st));
+    if (Ur) {
+        // out_q = (D_u A) g, out_r += H u_r: mesh and open parts, then the exclusion rows (which add w.loc.F into out_r)
+        if (out_q) gather(w2.mesh[MESH_DG], w2.mesh[MESH_G], (float)EW_PREFACTOR, out_q);
+        if (out_r && per)
+            k_p3m_force2<<<na, 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, w.dwts, w2.d2wts, w2.du, p, w2.mesh[MESH_Q],
+                                             w2.mesh[MESH_G], w2.mesh[MESH_A], w2.mesh[MESH_DG], G, Q, Uq, N, C, w.loc.F);
+        if (nn) {
+            if (out_g) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, Q, C, out_g, Ur);
+            if (out_q) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, G, C, out_q, Ur);
+            if (out_r)
+                k_ew_force2<false><<<nn, 256, 0, st>>>(e->d_atiles_n, e->d_sys, nullptr, nullptr, 1, pos, inv_R, G, Q, nullptr, nullptr,
+                                                       nullptr, nullptr, Ur, C, ew_vec_loads(C, Q, G), w.loc.F);
+        }
+        k_ew_edge_second<<<(unsigned)N, 64, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.geo, G, Q, Ur, w.loc.F, C, e->sigma, e->cutoff,
+                                                     out_g, out_q, out_r);
+    }
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
+}
+
+const char* const P3M_NO_HOOK =
+    "a P3M-mode handle without a transform hook: the mesh operator's second derivatives and its place in the dual pass need "
+    "the caller's transforms (pet_p3m_set_transform)";
+
 }  // namespace
+
+// ---- the mesh operator for the long-range stage of the dual pass (lr_potential / lr_backward / lr_second of ewald.hip) -----
+// Every call bins anew (six small launches; the positions do not change inside a sweep, but neither do the calls share more
+// than that) and nothing is kept between calls.
+int64_t p3m_lr_workspace_bytes(const pet_ewald_t* e, int C) {
+    P3mWs2 w2;
+    return (int64_t)p3m_carve2(e, C, nullptr, w2);
+}
+
+int p3m_lr_potential(const pet_ewald_t* e, const Graph& g, const float* pos, const float* X, int C, float* out, void* ws,
+                     hipStream_t st, int64_t ws_offset) {
+    P3mWs2 w2;
+    p3m_carve2(e, C, ws, w2, ws_offset);
+    ProfScope ps("p3m_fwd", st, 0.0, 0.0);
+    PET_TRY(p3m_bin(e, g, pos, w2.w, st));
+    PET_TRY(p3m_potential_mesh(e, X, C, w2, MESH_Q, st));
+    if (e->p3m->m_total > 0)
+        k_p3m_gather<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, e->p3m->d_sys, w2.w.org, w2.w.wts, e->p3m_nodes, w2.mesh[MESH_Q],
+                                                          (int)e->n_atoms, C, out);
+    return ew_local_forward(e, g, pos, X, C, out, w2.w.loc.sum_q, st);
+}
+
+int p3m_lr_backward(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, int C, float* gq,
+                    float* gpos, void* ws, hipStream_t st, int64_t ws_offset) {
+    P3mWs2 w2;
+    p3m_carve2(e, C, ws, w2, ws_offset);
+    const P3mWs& w = w2.w;
+    ProfScope ps("p3m_bwd", st, 0.0, 0.0);
+    PET_TRY(p3m_bin(e, g, pos, w, st));
+    PET_TRY(p3m_potential_mesh(e, G, C, w2, MESH_G, st));
+    PET_TRY(p3m_potential_mesh(e, Q, C, w2, MESH_Q, st));
+    if (e->p3m->m_total > 0) {
+        k_p3m_gather<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, e->p3m->d_sys, w.org, w.wts, e->p3m_nodes, w2.mesh[MESH_G],
+                                                          (int)e->n_atoms, C, gq);
+        k_p3m_force<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, e->p3m->d_sys, w.org, w.wts, w.dwts, e->p3m_nodes, w2.mesh[MESH_Q],
+                                                         w2.mesh[MESH_G], G, Q, (int)e->n_atoms, C, w.loc.F);
+    }
+    PET_TRY(ew_local_forward(e, g, pos, G, C, gq, w.loc.sum_g, st));
+    return ew_local_backward(e, g, pos, Q, G, C, w.loc, gpos, nullptr, st, [] {});
+}
+
+int p3m_lr_second(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                  const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st, int64_t ws_offset) {
+    P3mWs2 w2;
+    p3m_carve2(e, C, ws, w2, ws_offset);
+    return p3m_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, out_r, w2, st);
+}
 
 // pet_ewald_plan of a P3M-mode handle: mesh descriptors and influence functions instead of k lists, for the systems the shared
 // part of the plan has described in sys. A periodic system with atoms gets a mesh; every system's range of reduction chunks
@@ -706,6 +1060,42 @@ int pet_p3m_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float* d
             k_p3m_cell<<<(unsigned)mp->stiles.size(), 256, 0, st>>>(mp->d_stiles, mp->d_sys, (const float2*)d_spec_q,
                                                                    (const float2*)d_spec_g, C, e->sigma, e->p3m_nodes, w.loc.kpart);
     });
+}
+
+int pet_p3m_set_transform(pet_ewald_t* e, pet_p3m_transform_fn fn, void* user) {
+    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(e->p3m_nodes != 0, PET_ERR_ARGUMENT,
+                "a pet_p3m_* entry point on an Ewald-mode handle: call pet_ewald_set_p3m before pet_ewald_plan");
+    e->p3m_transform = fn;
+    e->p3m_transform_user = fn ? user : nullptr;
+    return PET_OK;
+}
+
+int64_t pet_p3m_second_workspace_bytes(const pet_ewald_t* e, int64_t n_channels) {
+    if (!e || !e->planned || !e->p3m || n_channels < 1) return -1;
+    P3mWs2 w2;
+    return (int64_t)p3m_carve2(e, n_channels, nullptr, w2);
+}
+
+int pet_p3m_second(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
+                   const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions, int32_t C,
+                   float* d_out_charges, float* d_out_grad_potential, float* d_out_positions, void* d_workspace,
+                   int64_t workspace_bytes, void* stream) {
+    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(e->p3m_nodes != 0, PET_ERR_ARGUMENT,
+                "a pet_p3m_* entry point on an Ewald-mode handle: call pet_ewald_set_p3m before pet_ewald_plan");
+    PET_TRY(ew_check_graph(e, pg, C));
+    PET_REQUIRE(e->p3m_transform, PET_ERR_ARGUMENT, std::string("pet_p3m_second on ") + P3M_NO_HOOK);
+    PET_REQUIRE(d_u_charges || d_u_positions, PET_ERR_ARGUMENT, "d_u_charges and d_u_positions are both NULL");
+    if (e->n_atoms == 0) return PET_OK;
+    P3mWs2 w2;
+    PET_REQUIRE(d_workspace && workspace_bytes >= (int64_t)p3m_carve2(e, C, nullptr, w2), PET_ERR_ARGUMENT,
+                "P3M workspace missing or too small (pet_p3m_second_workspace_bytes)");
+    PET_REQUIRE(d_positions && d_charges && d_grad_potential, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(d_out_charges || d_out_grad_potential || d_out_positions, PET_ERR_ARGUMENT, "all three results are NULL");
+    p3m_carve2(e, C, d_workspace, w2);
+    return p3m_second_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, C, d_out_charges,
+                          d_out_grad_potential, d_out_positions, w2, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -29,19 +29,26 @@ carries the featuriser between the backbone and the heads (``pet_backward_train2
 ``pet_hessian_vector_long_range``): :class:`LongRangeForward` and :class:`LongRangeTrainStep` are the training step on
 energies and forces, :func:`hessian_vector_product` is ``H u``. The six featuriser tensors then live in the model's own
 parameter table (:meth:`LongRangeFeaturizerHip.bind`). Not built, each raising by name: cell tangents and cell results
-(a stress / strain-gradient loss, cell directions of a Hessian-vector product), second derivatives through P3M (the
-reference trains with Ewald summation), further targets in the long-range step.
+(a stress / strain-gradient loss, cell directions of a Hessian-vector product), further targets in the long-range step.
 
-The reference takes its Ewald branch only under ``use_ewald and training`` (``utils/long_range.py:153-170``): it EVALUATES every
-periodic long-range model with P3M. :class:`P3MHip` is that operator (``csrc/p3m.hip``: binning, spread, filter, gather and the
+The reference takes its Ewald branch only under ``use_ewald and training`` (``utils/long_range.py:153-170``): with its default
+hypers (``use_ewald: false``) a periodic long-range model goes through P3M in training and in evaluation alike.
+:class:`P3MHip` is that operator (``csrc/p3m.hip``: binning, spread, filter, gather and the
 adjoints as HIP kernels in stages around ``torch.fft.rfftn`` / ``irfftn``), fixed by definition like the Ewald one
 (:data:`P3M_CONVENTIONS`, DESIGN.md section 19, oracle ``tests/_p3m_oracle.py``; parity with torch-pme unpinned). It is an
 explicit opt-in: ``LongRangeFeaturizerHip(hypers, method="p3m")`` evaluates periodic systems with P3M whatever ``use_ewald``
 says, ``method="ewald"`` (the earlier ``p3m_as_ewald=True``) with the Ewald sum P3M approximates, and without either a
 ``use_ewald: false`` model is refused.
+
+Second derivatives through the mesh operator are a further opt-in, ``second_order=True`` on
+:class:`P3MHip` and on a ``method="p3m"`` :class:`LongRangeFeaturizerHip`: the operator's stages run around ``torch.fft``, which
+this library does not link, so ``pet_p3m_second`` and the dual pass call the transforms back through a hook the operator
+installs (``pet_p3m_set_transform``). With it :meth:`P3MHip.second`, torch double backward, :class:`LongRangeTrainStep`,
+:class:`LongRangeForward` and :func:`hessian_vector_product` serve a P3M featuriser; without it they raise as before.
 """
 import logging
 import math
+import weakref
 from ctypes import byref, c_double, c_int32, c_int64, c_void_p
 from typing import Dict, List, Optional, Sequence
 
@@ -178,6 +185,7 @@ class EwaldHip:
 
     _warns_kset = True  # the k-set warning is the Ewald sum's: a mesh operator walks no k-set
     _workspace_bytes = "pet_ewald_workspace_bytes"
+    _second_entry = ("pet_ewald_second_workspace_bytes", "pet_ewald_second")
 
     def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5):
         global _warned_kset
@@ -273,6 +281,13 @@ class EwaldHip:
         ``<u_charges, dL/dq> + <u_positions, dL/dR>`` with respect to ``(charges, grad_potential, positions)``:
         ``(out_charges [N, C], out_grad_potential [N, C], out_positions [N, 3])``. Either cotangent may be ``None`` (zero; its
         work is skipped), not both. No cell tangent is taken and no cell result returned."""
+        return self._second(graph, positions, charges, grad_potential, u_charges, u_positions, (True, True, True))
+
+    def _with_hook(self, workspace: Optional[torch.Tensor], call) -> None:
+        """``check(call())`` for an entry point that runs on ``workspace``; :class:`P3MHip` serves its transform hook there."""
+        check(call())
+
+    def _second(self, graph, positions, charges, grad_potential, u_charges, u_positions, results):
         if u_charges is None and u_positions is None:
             raise PetHipError("second: u_charges and u_positions are both None")
         rt._require_cuda(*[t for t in (u_charges, u_positions) if t is not None])
@@ -280,32 +295,94 @@ class EwaldHip:
         uq = None if u_charges is None else u_charges.detach().to(torch.float32).reshape(q.shape).contiguous()
         ur = None if u_positions is None else u_positions.detach().to(torch.float32).reshape(pos.shape).contiguous()
         C = int(q.shape[1])
-        nbytes = int(self.lib.pet_ewald_second_workspace_bytes(self._handle, C))
+        bytes_name, entry_name = self._second_entry
+        nbytes = int(getattr(self.lib, bytes_name)(self._handle, C))
         if nbytes < 0:
-            raise PetHipError("pet_ewald_second_workspace_bytes failed: call plan() first")
+            raise PetHipError(f"{bytes_name} failed: call plan() first")
         ws = self._second_workspaces.get(C)
         if ws is None or ws.numel() < nbytes or ws.device != q.device:
             ws = self._second_workspaces[C] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=q.device)
-        out_q, out_g, out_r = torch.empty_like(q), torch.empty_like(q), torch.empty_like(pos)
-        check(self.lib.pet_ewald_second(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), rt._ptr(g), rt._ptr(uq), rt._ptr(ur),
-                                        C, rt._ptr(out_q), rt._ptr(out_g), rt._ptr(out_r), rt._ptr(ws), ws.numel(), rt._stream()))
-        return out_q, out_g, out_r
+        outs = tuple(torch.empty_like(t) if want else None for t, want in zip((q, q, pos), results))
+        entry = getattr(self.lib, entry_name)
+        self._with_hook(ws, lambda: entry(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), rt._ptr(g), rt._ptr(uq), rt._ptr(ur),
+                                          C, rt._ptr(outs[0]), rt._ptr(outs[1]), rt._ptr(outs[2]), rt._ptr(ws), ws.numel(),
+                                          rt._stream()))
+        return outs
 
 
 class P3MHip(EwaldHip):
     """The same operator with the reciprocal-space sum on a mesh (a ``pet_ewald_t`` after ``pet_ewald_set_p3m``): ``plan``,
     ``potential`` and ``backward`` as :class:`EwaldHip`, and ``mesh_shape(system)``. One application is
     ``pet_p3m_spread -> torch.fft.rfftn -> pet_p3m_filter -> torch.fft.irfftn -> pet_p3m_finish`` on the current stream; the
-    meshes are channel-first ``[C, N_x, N_y, N_z]`` per periodic system, packed in batch order."""
+    meshes are channel-first ``[C, N_x, N_y, N_z]`` per periodic system, packed in batch order.
+
+    ``second_order=True`` installs the TRANSFORM HOOK (``pet_p3m_set_transform``): a ctypes callback that
+    runs the same ``torch.fft`` calls between two offsets of the workspace of whichever entry point is running. That enables
+    :meth:`second` (``pet_p3m_second``), torch double backward through a P3M featuriser, and the handle's place in the
+    long-range training sweep and Hessian-vector product. Without it all of those raise as before."""
 
     _warns_kset = False
     _workspace_bytes = "pet_p3m_workspace_bytes"
+    _second_entry = ("pet_p3m_second_workspace_bytes", "pet_p3m_second")
 
-    def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5, interpolation_nodes: int = 5):
+    def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5, interpolation_nodes: int = 5,
+                 second_order: bool = False):
         self.interpolation_nodes = _check_nodes(interpolation_nodes)
         super().__init__(smearing, kspace_resolution, cutoff)
         check(self.lib.pet_ewald_set_p3m(self._handle, self.interpolation_nodes))
         self._meshes: List[tuple] = []  # (shape, first mesh point, first half-spectrum point) per system with a mesh
+        self._mesh_points = self._spec_points = 0
+        self.second_order = bool(second_order)
+        self.transform_calls = 0  # hook invocations (a batch without a mesh makes none)
+        self._hook = self._hook_error = self._hook_workspace = None
+        if self.second_order:
+            self._install_hook()
+
+    def _install_hook(self) -> None:
+        me = weakref.ref(self)  # (the callback must not keep the handle's owner alive)
+
+        def hook(user, inverse, mesh_byte_offset, spectrum_byte_offset, n_channels):
+            # ctypes swallows an exception raised here: keep it for _with_hook and tell the C side by the return value
+            op = me()
+            try:
+                op._transform(op._hook_workspace, int(inverse), int(mesh_byte_offset), int(spectrum_byte_offset), int(n_channels))
+                return 0
+            except BaseException as exc:  # noqa: BLE001
+                if op is not None:
+                    op._hook_error = exc
+                return 1
+
+        self._hook = _lib.P3M_TRANSFORM_FN(hook)  # (kept: the handle holds the raw pointer)
+        check(self.lib.pet_p3m_set_transform(self._handle, self._hook, None))
+
+    def _transform(self, ws: Optional[torch.Tensor], inverse: int, mesh_off: int, spec_off: int, C: int) -> None:
+        """``rfftn`` (``inverse = 0``) / ``irfftn(norm="forward")`` of every mesh of the plan between the packed mesh buffer at
+        byte ``mesh_off`` and the packed half spectrum at byte ``spec_off`` of ``ws`` (uint8), on the current stream, without a
+        copy: the calls of :meth:`_mesh_potential`."""
+        if ws is None:
+            raise PetHipError("the P3M transform hook ran outside an entry point that named its workspace (P3MHip._with_hook)")
+        self.transform_calls += 1
+        for n, moff, soff in self._meshes:
+            m, mh = n[0] * n[1] * n[2], n[0] * n[1] * (n[2] // 2 + 1)
+            real = ws[mesh_off + 4 * moff * C:mesh_off + 4 * (moff + m) * C].view(torch.float32).view(C, *n)
+            half = ws[spec_off + 8 * soff * C:spec_off + 8 * (soff + mh) * C].view(torch.complex64).view(C, n[0], n[1], n[2] // 2 + 1)
+            if inverse:
+                torch.fft.irfftn(half, s=n, dim=(1, 2, 3), norm="forward", out=real)
+            else:
+                torch.fft.rfftn(real, dim=(1, 2, 3), out=half)
+
+    def _with_hook(self, workspace: Optional[torch.Tensor], call) -> None:
+        """Run an entry point whose transforms come back through the hook on ``workspace``; an exception raised inside the hook
+        is re-raised here, in place of the C side's error that names the hook."""
+        self._hook_workspace, self._hook_error = workspace, None
+        try:
+            rc = call()
+        finally:
+            self._hook_workspace = None
+        err, self._hook_error = self._hook_error, None
+        if err is not None:
+            raise err
+        check(rc)
 
     def plan(self, cells, pbcs: Sequence[Sequence[bool]], first_atom: Sequence[int]) -> "P3MHip":
         """Mesh descriptors and influence functions for the batch (``pet_ewald_plan`` in P3M mode). Valid while the cells and
@@ -334,10 +411,22 @@ class P3MHip(EwaldHip):
         check(self.lib.pet_p3m_mesh_shape(self._handle, int(system), out))
         return [int(x) for x in out]
 
-    def second(self, *args, **kwargs):
-        raise PetHipError("second derivatives through P3M are not built: the reference trains long-range models with Ewald "
-                          "summation and evaluates them with P3M; use EwaldHip (method='ewald') for training and "
-                          "Hessian-vector products")
+    def second(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor, grad_potential: torch.Tensor,
+               u_charges: Optional[torch.Tensor] = None, u_positions: Optional[torch.Tensor] = None,
+               results: Sequence[bool] = (True, True, True)):
+        """:meth:`EwaldHip.second` through the mesh operator (``pet_p3m_second``), for an operator built with
+        ``second_order=True``. ``results``: which of ``(out_charges, out_grad_potential, out_positions)`` to form; the others
+        come back ``None`` and the meshes, transforms and launches that serve them alone are skipped (the ones formed have the
+        bits of the full call)."""
+        if not self.second_order:
+            raise PetHipError("second derivatives through P3M are not built on this operator: second_order=True "
+                              "(P3MHip(..., second_order=True), LongRangeFeaturizerHip(..., method='p3m', second_order=True)) "
+                              "installs the transform hook they need and trains through the mesh operator; method='ewald' "
+                              "trains by Ewald summation")
+        results = tuple(bool(x) for x in results)
+        if len(results) != 3 or not any(results):
+            raise PetHipError("second: results names three flags (out_charges, out_grad_potential, out_positions), at least one set")
+        return self._second(graph, positions, charges, grad_potential, u_charges, u_positions, results)
 
     def _mesh_potential(self, graph, pos, x, ws, keep_spectrum: bool = False):
         """spread -> rfftn -> filter -> irfftn of ``x [N, C]``: the mesh potential (packed, channel-first) and, on request, the
@@ -423,8 +512,8 @@ class _EwaldAdjointFn(torch.autograd.Function):
 
 
 class _EwaldFn(torch.autograd.Function):
-    """The operator as an autograd node over the HIP calls: gradients for charges, positions and cells, and (Ewald only, no
-    cells) their derivatives once more under ``create_graph`` through :class:`_EwaldAdjointFn`."""
+    """The operator as an autograd node over the HIP calls: gradients for charges, positions and cells, and (no cells; P3M
+    under ``second_order=True``) their derivatives once more under ``create_graph`` through :class:`_EwaldAdjointFn`."""
 
     @staticmethod
     def forward(ctx, charges, positions, cells, ewald, graph):
@@ -445,14 +534,19 @@ class LongRangeFeaturizerHip:
     ``method="p3m"``, :class:`P3MHip` (``interpolation_nodes`` from the hypers). ``method=None`` follows the hypers and refuses
     ``use_ewald: false``; ``method="ewald"`` is ``p3m_as_ewald=True``."""
 
-    def __init__(self, hypers: dict, device=None, p3m_as_ewald: bool = False, method: Optional[str] = None):
+    def __init__(self, hypers: dict, device=None, p3m_as_ewald: bool = False, method: Optional[str] = None,
+                 second_order: bool = False):
         self.long_range = resolve_hypers(hypers, p3m_as_ewald, method)
+        if second_order and method != "p3m":
+            raise PetHipError("second_order=True is the switch of the P3M operator (method='p3m'): the Ewald operator has its "
+                              f"second derivatives without it, got method={method!r}")
         self.method = method
         self.d = int(hypers["d_node"])
         self.cutoff = float(hypers["cutoff"])
         lr = self.long_range
         # (the attribute keeps its name: whichever operator evaluates the periodic systems)
-        self.ewald = (P3MHip(lr["smearing"], lr["kspace_resolution"], self.cutoff, lr["interpolation_nodes"]) if method == "p3m"
+        self.ewald = (P3MHip(lr["smearing"], lr["kspace_resolution"], self.cutoff, lr["interpolation_nodes"], second_order)
+                      if method == "p3m"
                       else EwaldHip(lr["smearing"], lr["kspace_resolution"], self.cutoff))
         dev = torch.device("cpu") if device is None else torch.device(device)
         d = self.d
@@ -479,8 +573,9 @@ class LongRangeFeaturizerHip:
 
     @classmethod
     def from_state_dict(cls, hypers: dict, state: Dict[str, torch.Tensor], device=None, p3m_as_ewald: bool = False,
-                        prefix: str = "long_range_featurizer.", method: Optional[str] = None) -> "LongRangeFeaturizerHip":
-        self = cls(hypers, device, p3m_as_ewald, method)
+                        prefix: str = "long_range_featurizer.", method: Optional[str] = None,
+                        second_order: bool = False) -> "LongRangeFeaturizerHip":
+        self = cls(hypers, device, p3m_as_ewald, method, second_order)
         self.load_state_dict(state, prefix)
         return self
 
@@ -517,7 +612,7 @@ class LongRangeFeaturizerHip:
         """``out_projection(potential(charges_map(features)))`` ``[N, d_node]``, differentiable by torch autograd with
         respect to ``features``, ``positions`` and ``cells``, and with the Ewald operator twice (``create_graph=True``) with
         respect to ``features``, ``positions`` and the six parameter tensors once a caller sets ``requires_grad_`` on them;
-        a P3M featuriser and cells that require grad are refused there."""
+        a P3M featuriser without ``second_order=True`` and cells that require grad are refused there."""
         rt._require_cuda(features, positions)
         p = self.params
         q = torch.nn.functional.linear(features, p["charges_map.weight"], p["charges_map.bias"])
@@ -594,11 +689,12 @@ def _check_trainable(model, featurizer, what: str) -> None:
     if hypers.get("num_neighbors_adaptive"):
         raise PetHipError(f"{what}: long_range together with num_neighbors_adaptive is not served (the adaptive cutoff drops "
                           "edges inside the exclusion radius)")
-    if isinstance(getattr(featurizer, "ewald", None), P3MHip):
-        raise PetHipError(f"{what} with a P3M featuriser is not built: second derivatives through P3M are not built (the "
-                          "reference trains long-range models with Ewald summation). Build the featuriser with "
-                          "method='ewald'; a use_ewald: false model needs the explicit p3m_as_ewald=True to train by Ewald "
-                          "summation")
+    op = getattr(featurizer, "ewald", None)
+    if isinstance(op, P3MHip) and not op.second_order:
+        raise PetHipError(f"{what} with a P3M featuriser is not built without second_order=True: second derivatives through "
+                          "P3M are not built on an operator without the transform hook. Build the featuriser with "
+                          "method='p3m', second_order=True to train through the mesh operator, or with method='ewald' "
+                          "(p3m_as_ewald=True) to train by Ewald summation")
 
 
 class LongRangeForward:
@@ -669,9 +765,10 @@ class LongRangeForward:
         lam, nu, u = f32(lam), f32(nu), f32(u)
         pos = g._pos.detach().to(torch.float32).contiguous()
         tan = torch.empty(g.n_nodes, dtype=torch.float32, device=dev) if want_tangent else None
-        check(self.lib.pet_backward_train2_long_range(self.model.handle, g.handle, self.featurizer.ewald.handle, rt._ptr(pos),
-                                                      rt._ptr(self.workspace2), self.workspace2.numel(), rt._ptr(lam),
-                                                      rt._ptr(nu), rt._ptr(u), rt._ptr(tan), rt._stream()))
+        op, ws = self.featurizer.ewald, self.workspace2
+        op._with_hook(ws, lambda: self.lib.pet_backward_train2_long_range(
+            self.model.handle, g.handle, op.handle, rt._ptr(pos), rt._ptr(ws), ws.numel(), rt._ptr(lam), rt._ptr(nu), rt._ptr(u),
+            rt._ptr(tan), rt._stream()))
         return tan
 
     def backward_train(self, grad_atomic: Optional[torch.Tensor], want_position_grad: bool = False, want_cell_grad: bool = False,
@@ -708,7 +805,7 @@ class LongRangeTrainStep(TrainStep):
     ``loss`` hyper (MSE / MAE / Huber), with a :class:`LongRangeForward` in place of the ``HipForward``. ``featurizer`` is
     bound to the model (:meth:`LongRangeFeaturizerHip.bind`): the model's table holds the six tensors, the optimizer step
     updates them there and the featuriser's copies are refreshed after it. Refused by name: ``target_strain_gradients``,
-    ``extra_targets``, a P3M featuriser."""
+    ``extra_targets``, a P3M featuriser built without ``second_order=True``."""
 
     _serves_long_range = True
 
@@ -768,7 +865,8 @@ def hessian_vector_product(model: rt.HipModel, featurizer: LongRangeFeaturizerHi
     pos = graph._pos.detach().to(torch.float32).contiguous()
     hp = torch.empty((n, 3), dtype=torch.float32, device=dev)
     tan = torch.empty(n, dtype=torch.float32, device=dev) if want_tangent else None
-    check(model.lib.pet_hessian_vector_long_range(model.handle, graph.handle, featurizer.ewald.handle, rt._ptr(pos),
-                                                  rt._ptr(workspace), workspace.numel(), rt._ptr(lam), rt._ptr(uu), rt._ptr(hp),
-                                                  rt._ptr(tan), rt._stream()))
+    op = featurizer.ewald
+    op._with_hook(workspace, lambda: model.lib.pet_hessian_vector_long_range(
+        model.handle, graph.handle, op.handle, rt._ptr(pos), rt._ptr(workspace), workspace.numel(), rt._ptr(lam), rt._ptr(uu),
+        rt._ptr(hp), rt._ptr(tan), rt._stream()))
     return (hp, tan) if want_tangent else hp

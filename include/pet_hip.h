@@ -747,6 +747,50 @@ int pet_p3m_second(const pet_ewald_t* e, const pet_graph_t* g, const float* d_po
                    float* d_out_charges, float* d_out_grad_potential, float* d_out_positions, void* d_workspace,
                    int64_t workspace_bytes, void* stream);
 
+/* ---- Cell tangents of the second-order operation: the stress term of a loss ----------------------------
+ * With a cotangent u_c [S, 3, 3] of dL/dcell (what pet_ewald_backward returns, at fixed Cartesian positions) beside u_q and u_r,
+ *   Psi = <u_q, A g> + <u_r, grad_r Phi> + <u_c, grad_cell Phi>, and pet_ewald_second_cell / pet_p3m_second_cell return
+ *   d_out_grad_potential = A u_q + (D A) q,   d_out_charges = (D A) g,   D A = d/dt A(r + t u_r, cell + t u_c) at t = 0,
+ * the plan's k-index set and mesh shape held fixed (as the first-order dL/dcell holds them). These two feed parameter
+ * gradients; the position and cell results (mixed and second cell derivatives) are not built and have no argument here.
+ * Per periodic system U = cell^{-1} u_c and u'_i = u_r,i - r_i U (fp64, rounded once): fractional coordinates move by
+ * u' cell^{-1} alone, so every phase k.r and every mesh stencil moves as under the position direction u'. With k = 2 pi n cell^{-T}:
+ *   (D A) X = (D_{u'} A) X                                          the position tangent of the blocks above, k / the mesh fixed
+ *           + P sum_k w_k f_k Re(e^{-i k.r_i} S_X(k)),  f_k = (sigma^2 + 2/k^2)(k U k^T) - tr U      (Ewald: the weights)
+ *             P3M: W^T K' W X, K' the filter sum_bc d(G^/Omega)/dcell_bc u_c,bc in place of G^/Omega
+ *           + P (2 pi sigma^2 / Omega) tr U sum_j X_j                                                 (background)
+ *           - P sum_{row i} w'(d) (n.dD) X_j,  dD = u_j - u_i + S u_c, edges to an atom's own image included   (exclusion)
+ * Ewald: f_k S'_X is folded into the weighted structure factor S'_{u'X} before the one tangent gather (k_ew_wdot): no gather is
+ * added. P3M: K' W X shares the forward transform of K W X and is added to the spectrum of the mesh the tangent gather reads
+ * before that one's inverse transform: no transform is added. HOOK CALLS per pet_p3m_second_cell call with d_u_cells: 4 per
+ * result formed (two pairs), 8 for both, whichever of u_q / u_r are given; without d_u_cells those of pet_p3m_second without
+ * d_out_positions. Rows of d_u_cells that belong to open systems are ignored (u' = u_r there).
+ * Arguments of pet_*_second plus d_u_cells, without d_out_positions. Any of the three cotangents may be NULL (zero), all
+ * three: PET_ERR_ARGUMENT. A NULL result is not formed; both NULL: PET_ERR_ARGUMENT. d_u_cells NULL: the launches and bits of
+ * pet_*_second with d_out_positions NULL. *_second_cell_workspace_bytes: -1 without a plan, on the other mode's handle, for
+ * C < 1 (the second-order workspace, then u' [N, 3]; P3M: also K' per half-spectrum point and one more half spectrum).
+ * pet_p3m_second_cell needs the transform hook. Same bits run to run and alone as in a batch; no float atomics.
+ *   pet_backward_train2_long_range_cell: pet_backward_train2_long_range with d_u_cell [S, 3, 3] = dL/d(dE/dcell) beside d_u:
+ *     e'_i = d/d eps e_i(R + eps u, cell + eps u_cell). Either direction may be NULL when the other is given (d_lambda_atomic is
+ *     then required); d_u_cell NULL: the launches and bits of pet_backward_train2_long_range. Both handle modes; the refusals
+ *     of that entry point, and PET_ERR_ARGUMENT for a graph without cell shifts (the backbone's cell tangent needs them).
+ *     pet_hessian_vector_long_range takes no cell direction. */
+int64_t pet_ewald_second_cell_workspace_bytes(const pet_ewald_t* e, int64_t n_channels);
+int pet_ewald_second_cell(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
+                          const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions,
+                          const float* d_u_cells, int32_t n_channels, float* d_out_charges, float* d_out_grad_potential,
+                          void* d_workspace, int64_t workspace_bytes, void* stream);
+int64_t pet_p3m_second_cell_workspace_bytes(const pet_ewald_t* e, int64_t n_channels);
+int pet_p3m_second_cell(const pet_ewald_t* e, const pet_graph_t* g, const float* d_positions, const float* d_charges,
+                        const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions,
+                        const float* d_u_cells, int32_t n_channels, float* d_out_charges, float* d_out_grad_potential,
+                        void* d_workspace, int64_t workspace_bytes, void* stream);
+int64_t pet_train2_long_range_cell_workspace_bytes(const pet_model_t* m, const pet_graph_t* g, const pet_ewald_t* e);
+int pet_backward_train2_long_range_cell(const pet_model_t* m, const pet_graph_t* g, const pet_ewald_t* e,
+                                        const float* d_positions, void* d_workspace, int64_t workspace_bytes,
+                                        const float* d_lambda_atomic, const float* d_nu_atomic, const float* d_u,
+                                        const float* d_u_cell, float* d_tangent_atomic, void* stream);
+
 /* ---- Rotational augmentation (utils/augmentation.py:O3Augmenter; pet/trainer.py:187-193, 288-303) -------------------------
  * A random element of O(3) per system of a collated batch, drawn and applied on the device. A rigid transformation of
  * positions and cell leaves fractional coordinates alone, so the batch's (center, neighbor, cell_shift) list stays valid:

@@ -58,7 +58,8 @@ SYMBOLS = [
     "pet_zbl_forward", "pet_zbl_backward", "pet_zbl_hessian_vector",
     "pet_ewald_create", "pet_ewald_destroy", "pet_ewald_kvectors_host", "pet_ewald_plan", "pet_ewald_num_kvectors",
     "pet_ewald_workspace_bytes", "pet_ewald_potential", "pet_ewald_backward", "pet_ewald_second_workspace_bytes",
-    "pet_ewald_second",
+    "pet_ewald_second", "pet_ewald_second_cell_workspace_bytes", "pet_ewald_second_cell", "pet_p3m_second_cell_workspace_bytes",
+    "pet_p3m_second_cell", "pet_train2_long_range_cell_workspace_bytes", "pet_backward_train2_long_range_cell",
     "pet_train2_long_range_workspace_bytes", "pet_backward_train2_long_range", "pet_hvp_long_range_workspace_bytes",
     "pet_hessian_vector_long_range",
     "pet_ewald_set_p3m", "pet_p3m_mesh_shape_host", "pet_p3m_influence_host", "pet_p3m_mesh_shape", "pet_p3m_mesh_elements",
@@ -328,6 +329,13 @@ def load() -> ctypes.CDLL:
     lib.pet_p3m_second_workspace_bytes.argtypes = [P, c_int64]
     lib.pet_p3m_second_workspace_bytes.restype = c_int64
     lib.pet_p3m_second.argtypes = [P, P, P, P, P, P, P, c_int32, P, P, P, P, c_int64, P]
+    for name in ("pet_ewald_second_cell", "pet_p3m_second_cell"):
+        getattr(lib, name + "_workspace_bytes").argtypes = [P, c_int64]
+        getattr(lib, name + "_workspace_bytes").restype = c_int64
+        getattr(lib, name).argtypes = [P, P, P, P, P, P, P, P, c_int32, P, P, P, c_int64, P]
+    lib.pet_train2_long_range_cell_workspace_bytes.argtypes = [P, P, P]
+    lib.pet_train2_long_range_cell_workspace_bytes.restype = c_int64
+    lib.pet_backward_train2_long_range_cell.argtypes = [P, P, P, P, P, c_int64, P, P, P, P, P, P]
     lib.pet_o3_draw.argtypes = [c_uint64, c_uint64, c_int32, c_int64, P, P]
     lib.pet_o3_apply.argtypes = [P, c_int64, c_int32, POINTER(O3Array), P]
     lib.pet_o3_wigner.argtypes = [P, c_int64, c_int32, P, P, P]

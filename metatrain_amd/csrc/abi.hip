@@ -842,6 +842,34 @@ int pet_backward_train2_long_range(const pet_model_t* pm, const pet_graph_t* pg,
     return lora_end(m, st);
 }
 
+int64_t pet_train2_long_range_cell_workspace_bytes(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e) {
+    if (long_range_check(pm, pg, e, "pet_backward_train2_long_range_cell")) return -1;
+    return gen_train2_lr_cell_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges);
+}
+
+int pet_backward_train2_long_range_cell(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e,
+                                        const float* d_positions, void* d_workspace, int64_t workspace_bytes,
+                                        const float* d_lambda_atomic, const float* d_nu_atomic, const float* d_u,
+                                        const float* d_u_cell, float* d_tangent_atomic, void* stream) {
+    if (int rc = long_range_check(pm, pg, e, "pet_backward_train2_long_range_cell")) return rc;
+    PET_REQUIRE(!d_u_cell || pg->g.n_edges == 0 || pg->g.shift, PET_ERR_ARGUMENT,
+                "pet_backward_train2_long_range_cell: the backbone's cell tangent needs a pet_graph_build handle (cell shifts)");
+    if (pg->g.n_nodes == 0) return PET_OK;
+    PET_REQUIRE(d_positions && d_workspace, PET_ERR_ARGUMENT, "null argument");
+    const bool dir = d_u || d_u_cell;
+    PET_REQUIRE(dir ? d_lambda_atomic != nullptr : d_nu_atomic != nullptr, PET_ERR_ARGUMENT,
+                "a direction (d_u, d_u_cell) needs the seeds d_lambda_atomic its gradient was taken with; without one (first "
+                "order, energy only) d_nu_atomic is the loss' seed");
+    Model& m = const_cast<Model&>(pm->m);
+    const hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if ((rc = lora_begin(m, st))) return rc;
+    if ((rc = gen_train2_lr_cell(m, pg->g, e, d_positions, d_workspace, workspace_bytes, dir ? d_lambda_atomic : nullptr,
+                                 d_nu_atomic, d_u, d_u_cell, d_tangent_atomic, st)))
+        return rc;
+    return lora_end(m, st);
+}
+
 int64_t pet_hvp_long_range_workspace_bytes(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e) {
     if (long_range_check(pm, pg, e, "pet_hessian_vector_long_range")) return -1;
     return gen_hvp_lr_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges);

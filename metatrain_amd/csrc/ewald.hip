@@ -21,6 +21,10 @@
 // applied to a direction: four product tiles per k tile, or M_K (u_j - u_i) for open systems), k_ew_pairs<true> and
 // k_ew_edge_second (the exclusion rows, fp64); the <false> instantiations are the first-order kernels, bit for bit. k_ew_force2,
 // k_ew_pairs and k_ew_edge_second are in long_range.h: pet_p3m_second launches them for the same local terms.
+// Cell tangents (pet_ewald_second_cell): k_ew_uprime (long_range.h) turns (u, u_c) into the position
+// direction u' that moves the phases alike, k_ew_wdot folds the weights' tangent into the weighted structure factors before
+// the one k_ew_gather<true>, and ew_local_cell (k_ew_edge_cell) takes the place of k_ew_edge_second. New kernels and launches
+// only: every instantiation above is what it was.
 // Here: the k-space part (k_ew_tables, k_ew_sfac, k_ew_gather, k_ew_force<true>, k_ew_zk, the k list) and pet_ewald_*, among
 // them the plan of both modes, and lr_* (what the dual pass calls, dispatching on the handle's mode). The handle, k_ew_force
 // and the local terms' kernels are in long_range.h, shared with p3m.hip.
@@ -245,6 +249,40 @@ __global__ __launch_bounds__(256) void k_ew_zk(const EwSys* __restrict__ sys, co
     }
 }
 
+// The weights' share of the cell tangent (pet_ewald_second_cell), folded into the weighted structure factor that k_ew_gather<true>
+// reads: with f_k = w_k' / w_k = (sigma^2 + 2 / k^2) (k U k^T) - tr U along u_c (U = cell^{-1} u_c; fp64 from the integer triple
+// and the plan's inverse cell, rounded once), Su[k] += f_k (Im S'[k], -Re S'[k]), which that gather turns into
+// + P sum_k f_k Re(e^{-i k.r_i} S'_X(k)). One block per k-vector, threads over channels.
+__global__ __launch_bounds__(256) void k_ew_wdot(const EwSys* __restrict__ sys, const int* __restrict__ ksys,
+                                                 const EwK* __restrict__ klist, const float* __restrict__ ucell,
+                                                 const float* __restrict__ S, int C, double sigma, float* __restrict__ Su) {
+    __shared__ float fs;
+    const int64_t k = blockIdx.x;
+    if (threadIdx.x == 0) {
+        const int si = ksys[k];
+        const EwSys& s = sys[si];
+        const EwK kk = klist[k];
+        double U[9], kv[3], k2 = 0.0, kuk = 0.0;
+        ew_cell_U(s.inv, ucell + 9 * (int64_t)si, U);
+        for (int a = 0; a < 3; a++) {
+            kv[a] = 2.0 * EW_PI * (s.inv[3 * a] * kk.n0 + s.inv[3 * a + 1] * kk.n1 + s.inv[3 * a + 2] * kk.n2);
+            k2 += kv[a] * kv[a];
+        }
+        for (int a = 0; a < 3; a++)
+            for (int b = 0; b < 3; b++) kuk += kv[a] * U[3 * a + b] * kv[b];
+        fs = (float)((sigma * sigma + 2.0 / k2) * kuk - (U[0] + U[4] + U[8]));
+    }
+    __syncthreads();
+    const float f = fs;
+    const float* re = S + k * 2 * C;
+    float* ure = Su + k * 2 * C;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const float a = re[c], b = re[C + c];
+        ure[c] += f * b;
+        ure[C + c] -= f * a;
+    }
+}
+
 // the largest reciprocal index along every axis of a cell inside |k| <= 2 pi / lambda; false where one is beyond 1e6
 bool ew_index_bounds(const double* h, double lambda, int* nmax) {
     const double kmax = 2.0 * EW_PI / lambda;
@@ -400,11 +438,32 @@ size_t ew_carve2(const pet_ewald_t* e, int64_t C, void* base, EwWs2& w2) {
     return c.off;
 }
 
+// the workspace of pet_ewald_second_cell: that of pet_ewald_second, then u' [N, 3]
+struct EwWs3 {
+    EwWs2 w2;
+    float* up;
+};
+
+size_t ew_carve3(const pet_ewald_t* e, int64_t C, void* base, EwWs3& w3) {
+    Carver c(base);
+    c.off = ew_carve2(e, C, base, w3.w2);
+    w3.up = c.take<float>((size_t)std::max<int64_t>(e->n_atoms, 1) * 3);
+    return c.off;
+}
+
+// a cell tangent of ew_second_run: the caller's position direction u [N, 3] (may be null) and u_c [S, 3, 3]; Ur is then u'
+struct EwCellDir {
+    const float *u, *ucell;
+};
+
 // pet_ewald_second with selectable results: a null out_q / out_g / out_r is not formed and the launches that serve it alone
 // are skipped. With all three it is the launch list pet_ewald_second always had. Q may be null where only out_q is asked
 // for (it is a function of (G, Ur) alone), G where only out_g is (a function of (Q, Uq, Ur)).
+// With `cell` (pet_ewald_second_cell; Ur = u' of k_ew_uprime, no out_r): k_ew_wdot folds the weights' tangent into the two weighted
+// structure factors and ew_local_cell takes the place of k_ew_edge_second; nothing else differs.
 int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                  const float* Ur, int C, float* out_q, float* out_g, float* out_r, const EwWs2& w2, hipStream_t st) {
+                  const float* Ur, int C, float* out_q, float* out_g, float* out_r, const EwWs2& w2, hipStream_t st,
+                  const EwCellDir* cell = nullptr) {
     const EwWs& w = w2.w;
     const int64_t N = e->n_atoms;
     const unsigned cy = (unsigned)cdiv(C, 256), nk = (unsigned)e->ktiles.size(), np = (unsigned)e->atiles_p.size(),
@@ -412,7 +471,8 @@ int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const 
     const size_t lds = ew_table_lds(e);
     const float inv_R = (float)(1.0 / e->cutoff);
     // (the profiler's stage names tell the selections apart: all three results, the dual forward's, the two reverses')
-    ProfScope ps(out_q && out_g && out_r ? "ewald_second" : out_g ? "ewald_second_g" : out_r ? "ewald_second_qr" : "ewald_second_q",
+    ProfScope ps(cell ? (out_g && out_q ? "ewald_second_cell" : out_g ? "ewald_second_cell_g" : "ewald_second_cell_q")
+                 : out_q && out_g && out_r ? "ewald_second" : out_g ? "ewald_second_g" : out_r ? "ewald_second_qr" : "ewald_second_q",
                  st, 0.0, 0.0);
     PET_TRY(ew_tables(e, g, pos, w, st));
     // S'(g) serves out_r of both halves and out_q
@@ -443,6 +503,8 @@ int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const 
             }
             if (out_q || out_r)
                 k_ew_sfac<true><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, G, C, w2.Su2, Ur);
+            if (cell && out_g) k_ew_wdot<<<(unsigned)e->n_k, 256, 0, st>>>(e->d_sys, e->d_ksys, e->d_k, cell->ucell, w.S1, C, e->sigma, w2.Su1);
+            if (cell && out_q) k_ew_wdot<<<(unsigned)e->n_k, 256, 0, st>>>(e->d_sys, e->d_ksys, e->d_k, cell->ucell, w.S2, C, e->sigma, w2.Su2);
         }
         if (np) {
             if (out_g)
@@ -462,11 +524,22 @@ int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const 
                 k_ew_force2<false><<<nn, 256, 0, st>>>(e->d_atiles_n, e->d_sys, nullptr, nullptr, 1, pos, inv_R, G, Q, nullptr, nullptr,
                                                        nullptr, nullptr, Ur, C, ew_vec_loads(C, Q, G), w.loc.F);
         }
-        k_ew_edge_second<<<(unsigned)N, 64, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.geo, G, Q, Ur, w.loc.F, C, e->sigma, e->cutoff,
-                                                     out_g, out_q, out_r);
+        if (cell) PET_TRY(ew_local_cell(e, g, Q, G, cell->u, cell->ucell, C, w.loc, out_g, out_q, st));
+        else
+            k_ew_edge_second<<<(unsigned)N, 64, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.geo, G, Q, Ur, w.loc.F, C, e->sigma,
+                                                         e->cutoff, out_g, out_q, out_r);
     }
     PET_HIP_CHECK(hipGetLastError());
     return PET_OK;
+}
+
+// pet_ewald_second_cell: u' = u - r U, then ew_second_run along (u_q, u') with the cell tangent's two additions
+int ew_second_cell_run(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                       const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, const EwWs3& w3, hipStream_t st) {
+    if (!Ucell) return ew_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, nullptr, w3.w2, st);
+    k_ew_uprime<<<cdiv(e->n_atoms, 256), 256, 0, st>>>(pos, g.sys, e->d_sys, Ur, Ucell, (int)e->n_atoms, w3.up);
+    const EwCellDir cell{Ur, Ucell};
+    return ew_second_run(e, g, pos, Q, G, Uq, w3.up, C, out_q, out_g, nullptr, w3.w2, st, &cell);
 }
 
 }  // namespace
@@ -531,6 +604,23 @@ int lr_second(const pet_ewald_t* e, const Graph& g, const float* pos, const floa
     EwWs2 w2;
     ew_carve2(e, C, ws, w2);
     return ew_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, out_r, w2, st);
+}
+
+// lr_ewald_workspace_bytes / lr_second with a cell tangent Ucell [S, 3, 3] (pet_ewald_second_cell / pet_p3m_second_cell): the two
+// results that feed parameter gradients. Ur or Ucell may be null.
+int64_t lr_ewald_cell_workspace_bytes(const pet_ewald_t* e, int C) {
+    if (e->p3m_nodes) return p3m_lr_cell_workspace_bytes(e, C);
+    EwWs3 w;
+    return (int64_t)ew_carve3(e, C, nullptr, w);
+}
+
+int lr_second_cell(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                   const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, void* ws, hipStream_t st,
+                   int64_t ws_offset) {
+    if (e->p3m_nodes) return p3m_lr_second_cell(e, g, pos, Q, G, Uq, Ur, Ucell, C, out_q, out_g, ws, st, ws_offset);
+    EwWs3 w3;
+    ew_carve3(e, C, ws, w3);
+    return ew_second_cell_run(e, g, pos, Q, G, Uq, Ur, Ucell, C, out_q, out_g, w3, st);
 }
 
 }  // namespace pet
@@ -701,6 +791,34 @@ int pet_ewald_second(const pet_ewald_t* e, const pet_graph_t* pg, const float* d
     ew_carve2(e, C, d_workspace, w2);
     return ew_second_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, C, d_out_charges,
                          d_out_grad_potential, d_out_positions, w2, (hipStream_t)stream);
+}
+
+int64_t pet_ewald_second_cell_workspace_bytes(const pet_ewald_t* e, int64_t n_channels) {
+    if (!e || !e->planned || e->p3m_nodes || n_channels < 1) return -1;
+    EwWs3 w;
+    return (int64_t)ew_carve3(e, n_channels, nullptr, w);
+}
+
+int pet_ewald_second_cell(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
+                          const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions,
+                          const float* d_u_cells, int32_t C, float* d_out_charges, float* d_out_grad_potential, void* d_workspace,
+                          int64_t workspace_bytes, void* stream) {
+    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(e->p3m_nodes == 0, PET_ERR_ARGUMENT,
+                "pet_ewald_second_cell on a P3M-mode handle (pet_ewald_set_p3m): the mesh operator's cell tangents are "
+                "pet_p3m_second_cell's");
+    if (int rc = ew_check(e, pg, C, d_workspace, workspace_bytes)) return rc;
+    PET_REQUIRE(d_u_charges || d_u_positions || d_u_cells, PET_ERR_ARGUMENT,
+                "d_u_charges, d_u_positions and d_u_cells are all NULL");
+    if (e->n_atoms == 0) return PET_OK;
+    EwWs3 w3;
+    PET_REQUIRE(d_workspace && workspace_bytes >= (int64_t)ew_carve3(e, C, nullptr, w3), PET_ERR_ARGUMENT,
+                "Ewald workspace too small (pet_ewald_second_cell_workspace_bytes)");
+    PET_REQUIRE(d_positions && d_charges && d_grad_potential, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(d_out_charges || d_out_grad_potential, PET_ERR_ARGUMENT, "both results are NULL");
+    ew_carve3(e, C, d_workspace, w3);
+    return ew_second_cell_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, d_u_cells, C,
+                              d_out_charges, d_out_grad_potential, w3, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -951,11 +951,11 @@ struct LrWs {
     std::vector<D2> ml;
     size_t bytes;
 };
-static void lr_carve(const Model& m, const pet_ewald_t* e, int64_t N, void* base, LrWs& w) {
+static void lr_carve(const Model& m, const pet_ewald_t* e, int64_t N, void* base, LrWs& w, bool cell = false) {
     const GD d = dims_of(m);
     Carver c(base);
     w.ew = base;
-    c.off = ((size_t)lr_ewald_workspace_bytes(e, d.DN) + 255) & ~size_t(255);
+    c.off = ((size_t)(cell ? lr_ewald_cell_workspace_bytes(e, d.DN) : lr_ewald_workspace_bytes(e, d.DN)) + 255) & ~size_t(255);
     const size_t n = (size_t)(N > 0 ? N : 1) * d.DN;
     for (D2* v : {&w.x, &w.q, &w.V, &w.a, &w.s, &w.y, &w.dy, &w.dV, &w.dq, &w.dx}) take(c, n, *v);
     w.dqu = c.take<float>(n);
@@ -998,7 +998,9 @@ static int lr_forward(TOps& t, const LrStage& lr, const Lin* L, const std::vecto
     k_lr_layer_sum<<<g1(n), 256, 0, t.st>>>(lr_rows(h, true), sx, w.x.t, n);
     t.linf(w.x, DN, L[0], w.q, DN, N);
     PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.q.p, DN, w.V.p, w.ew, t.st, lr.ws_offset));
-    if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, nullptr, w.q.t, u, DN, nullptr, w.V.t, nullptr, w.ew, t.st, lr.ws_offset));
+    if (u && lr.ucell)   // V' = A q' + (D A) q along (u, ucell)
+        PET_TRY(lr_second_cell(lr.e, t.g, lr.pos, w.q.p, nullptr, w.q.t, u, lr.ucell, DN, nullptr, w.V.t, w.ew, t.st, lr.ws_offset));
+    else if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, nullptr, w.q.t, u, DN, nullptr, w.V.t, nullptr, w.ew, t.st, lr.ws_offset));
     else t.o.zero(w.V.t, n);
     t.linf(w.V, DN, L[1], w.a, DN, N);
     t.silu(w.a, w.s, n);
@@ -1030,7 +1032,9 @@ static int lr_reverse(TOps& t, const LrStage& lr, const Lin* L, const float* u, 
         t.o.axpby(1.f, w.r1, 3, 1.f, w.r2, 3, nullptr, lr.rbar, 3, false, N, 3);
     } else {
         PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.p, DN, w.dq.p, w.ew, t.st, lr.ws_offset));
-        if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, nullptr, w.dV.t, nullptr, u, DN, w.dqu, nullptr, nullptr, w.ew, t.st, lr.ws_offset));
+        if (u && lr.ucell)
+            PET_TRY(lr_second_cell(lr.e, t.g, lr.pos, nullptr, w.dV.t, nullptr, u, lr.ucell, DN, w.dqu, nullptr, w.ew, t.st, lr.ws_offset));
+        else if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, nullptr, w.dV.t, nullptr, u, DN, w.dqu, nullptr, nullptr, w.ew, t.st, lr.ws_offset));
     }
     if (u) {
         PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.t, DN, w.dq.t, w.ew, t.st, lr.ws_offset));
@@ -1078,8 +1082,11 @@ int64_t gen_train_workspace_bytes(const Model& m, int64_t N, int64_t E) {
 int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, const float* lA, const float* nA, const float* u,
                const float* ucell, float* tangent_atomic, hipStream_t st, const float* const* seed_node,
                const float* const* seed_edge, int n_seed, const HvpTaps* hv, const LrStage* lr) {
-    PET_REQUIRE(!lr || ((lA || nA) && !ucell && n_seed == 0 && !g.adaptive), PET_ERR_ARGUMENT,
-                "the long-range stage: the fused target's seeds, no cell tangent, no seeds of further targets, a static cutoff");
+    PET_REQUIRE(!lr || ((lA || nA) && (!ucell || (lr->ucell && !hv)) && n_seed == 0 && !g.adaptive), PET_ERR_ARGUMENT,
+                "the long-range stage: the fused target's seeds, no cell tangent (but pet_backward_train2_long_range_cell's), no "
+                "seeds of further targets, a static cutoff");
+    PET_REQUIRE(!lr || !lr->ucell || lr->ucell == ucell, PET_ERR_ARGUMENT,
+                "the long-range stage and the backbone take one cell tangent: LrStage::ucell is gen_train2's ucell");
     PET_REQUIRE(hv || m.grad_flat, PET_ERR_ARGUMENT, "pet_model_zero_grad has not been called");
     PET_REQUIRE(!hv || (u && !g.adaptive && n_seed == 0), PET_ERR_ARGUMENT, "Hessian-vector mode: a direction, a static cutoff, no seeds");
     PET_REQUIRE(n_seed == 0 || n_seed == m.num_readout_layers(), PET_ERR_ARGUMENT, "expected one seed pair per readout layer");
@@ -1145,7 +1152,7 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
     if (lr) {
         PET_REQUIRE(NR <= LR_MAX_LAYERS, PET_ERR_UNSUPPORTED, "the long-range stage serves at most 16 readout layers");
         if (int rc = lr_linears(m, DN, lrl)) return rc;
-        lr_carve(m, lr->e, N, lr->ws, lw);
+        lr_carve(m, lr->e, N, lr->ws, lw, lr->ucell != nullptr);
         PET_REQUIRE((int64_t)lw.bytes <= lr->ws_bytes, PET_ERR_ARGUMENT, "long-range stage workspace too small");
         std::vector<D2> hl(NR);
         for (int l = 0; l < NR; l++) hl[l] = (res ? w.gnn[l] : w.gnn.back()).Hout;
@@ -1286,9 +1293,9 @@ int gen_hvp(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const fl
 // ---------------------------------------------------------------------------------------------
 static size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
-int64_t lr_stage_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N) {
+int64_t lr_stage_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, bool cell) {
     LrWs w;
-    lr_carve(m, e, N, nullptr, w);
+    lr_carve(m, e, N, nullptr, w, cell);
     return (int64_t)w.bytes;
 }
 
@@ -1305,6 +1312,33 @@ int gen_train2_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const fl
                 "workspace too small (pet_train2_long_range_workspace_bytes)");
     LrStage lr{e, pos, static_cast<char*>(ws) + train_bytes, stage_bytes, nullptr, (int64_t)train_bytes};
     return gen_train2(m, g, ws, (int64_t)train_bytes, lA, nA, u, nullptr, tangent_atomic, st, nullptr, nullptr, 0, nullptr, &lr);
+}
+
+// With a cell tangent (pet_backward_train2_long_range_cell): the dual pass' workspace, a zero direction [N, 3] for the call
+// that has ucell alone (the backbone's geometry tangent and the operator read one direction, not a null), the stage's with
+// the operator's cell workspace. Without ucell it is gen_train2_lr, launch for launch.
+int64_t gen_train2_lr_cell_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, int64_t E) {
+    return (int64_t)align256((size_t)gen_train_workspace_bytes(m, N, E)) + (int64_t)align256((size_t)(N > 0 ? N : 1) * 3 * sizeof(float)) +
+           lr_stage_workspace_bytes(m, e, N, true);
+}
+
+int gen_train2_lr_cell(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
+                       const float* lA, const float* nA, const float* u, const float* ucell, float* tangent_atomic,
+                       hipStream_t st) {
+    if (!ucell) return gen_train2_lr(m, g, e, pos, ws, ws_bytes, lA, nA, u, tangent_atomic, st);
+    const int64_t N = g.n_nodes, E = g.n_edges;
+    const size_t train_bytes = align256((size_t)gen_train_workspace_bytes(m, N, E));
+    const size_t zero_bytes = align256((size_t)(N > 0 ? N : 1) * 3 * sizeof(float));
+    const int64_t stage_bytes = lr_stage_workspace_bytes(m, e, N, true);
+    PET_REQUIRE((int64_t)(train_bytes + zero_bytes) + stage_bytes <= ws_bytes, PET_ERR_ARGUMENT,
+                "workspace too small (pet_train2_long_range_cell_workspace_bytes)");
+    if (!u) {
+        float* zeros = reinterpret_cast<float*>(static_cast<char*>(ws) + train_bytes);
+        PET_HIP_CHECK(hipMemsetAsync(zeros, 0, (size_t)(N > 0 ? N : 1) * 3 * sizeof(float), st));
+        u = zeros;
+    }
+    LrStage lr{e, pos, static_cast<char*>(ws) + train_bytes + zero_bytes, stage_bytes, nullptr, (int64_t)(train_bytes + zero_bytes), ucell};
+    return gen_train2(m, g, ws, (int64_t)train_bytes, lA, nA, u, ucell, tangent_atomic, st, nullptr, nullptr, 0, nullptr, &lr);
 }
 
 int64_t gen_hvp_lr_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, int64_t E) {

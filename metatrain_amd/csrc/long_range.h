@@ -6,6 +6,7 @@
 // its weight 2 G(k) / Omega (ewald.hip: ew_plan_klist) or G^(n) / Omega (p3m.hip: p3m_influence_point).
 // k_ew_pairs<true>, k_ew_force2, k_ew_edge_second and ew_open_kernel_dd serve both modes' second derivatives (ewald.hip:
 // pet_ewald_second; p3m.hip: pet_p3m_second, which has no k tiles and instantiates k_ew_force2<false> alone).
+// k_ew_uprime, k_ew_edge_cell and ew_local_cell serve both modes' cell tangents (pet_ewald_second_cell, pet_p3m_second_cell).
 // Kernels and functions have internal linkage: each translation unit is compiled on its own (build.py: NO_RDC) with its own
 // copy of what it launches. Only the two record types and the P3M plan's entry points have names that cross objects.
 #pragma once
@@ -678,6 +679,111 @@ __global__ __launch_bounds__(64) void k_ew_edge_second(const EwSys* __restrict__
     if (out_r && lane < 3) out_r[3 * (int64_t)i + lane] += (float)((double)F2[3 * (int64_t)i + lane] + fp[lane]);
 }
 
+// ---- cell tangents of the second-order operation (pet_ewald_second_cell / pet_p3m_second_cell) ----------
+// U = cell^{-1} u_c of one periodic system (fp64), u_c [3, 3] one row of d_u_cells
+__device__ __forceinline__ void ew_cell_U(const double* inv, const float* uc, double* U) {
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++)
+            U[3 * a + b] = inv[3 * a] * (double)uc[b] + inv[3 * a + 1] * (double)uc[3 + b] + inv[3 * a + 2] * (double)uc[6 + b];
+}
+
+// u'_i = u_i - r_i U on the atoms of periodic systems (the direction that moves the fractional coordinates as (u, u_c) does),
+// u_i elsewhere; formed in fp64 and rounded once. u may be null (zero).
+__global__ __launch_bounds__(256) void k_ew_uprime(const float* __restrict__ pos, const int* __restrict__ gsys,
+                                                   const EwSys* __restrict__ sys, const float* __restrict__ u,
+                                                   const float* __restrict__ ucell, int N, float* __restrict__ up) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    const int si = gsys[i];
+    const EwSys& s = sys[si];
+    double v[3] = {0.0, 0.0, 0.0};
+    if (u)
+        for (int b = 0; b < 3; b++) v[b] = (double)u[3 * (int64_t)i + b];
+    if (s.periodic) {
+        double U[9];
+        ew_cell_U(s.inv, ucell + 9 * (int64_t)si, U);
+        const double r[3] = {(double)pos[3 * (int64_t)i], (double)pos[3 * (int64_t)i + 1], (double)pos[3 * (int64_t)i + 2]};
+        for (int b = 0; b < 3; b++) v[b] -= r[0] * U[b] + r[1] * U[3 + b] + r[2] * U[6 + b];
+    }
+    for (int b = 0; b < 3; b++) up[3 * (int64_t)i + b] = (float)v[b];
+}
+
+// The local terms' share of (D A) X along (u, u_c), in place of k_ew_edge_second where there is a cell tangent: one wave per
+// atom of a periodic system, fp64, the chunk walk of k_ew_edge_second. Per edge p = (i -> j, S), self-image edges included,
+// the edge vector moves by dD = u_j - u_i + S u_c:  out_g[i] -= P w'(d) (n.dD) q_j,  out_q[i] -= P w'(d) (n.dD) g_j;  then the
+// background, out_g[i] += P (2 pi sigma^2 / Omega) tr(U) sum_j q_j (sum_q, sum_g: k_ew_colsum of Q and of G). U may be null.
+__global__ __launch_bounds__(64) void k_ew_edge_cell(const EwSys* __restrict__ sys, const int* __restrict__ gsys,
+                                                     const int* __restrict__ rowptr, const int* __restrict__ nbr,
+                                                     const int* __restrict__ shift, const float4* __restrict__ geo,
+                                                     const float* __restrict__ G, const float* __restrict__ Q,
+                                                     const float* __restrict__ U, const float* __restrict__ ucell,
+                                                     const float* __restrict__ sum_q, const float* __restrict__ sum_g, int C,
+                                                     double sigma, double Rcut, float* __restrict__ out_g,
+                                                     float* __restrict__ out_q) {
+    __shared__ int sj[64];
+    __shared__ double sco[64];
+    const int i = blockIdx.x, lane = threadIdx.x;
+    const int si = gsys[i];
+    const EwSys& s = sys[si];
+    if (!s.periodic) return;
+    const float* uc = ucell + 9 * (int64_t)si;
+    const double inv_a = 1.0 / (sqrt(2.0) * sigma);
+    double ui[3] = {0.0, 0.0, 0.0};
+    if (U)
+        for (int a = 0; a < 3; a++) ui[a] = (double)U[3 * (int64_t)i + a];
+    const int p1 = rowptr[i + 1];
+    for (int p0 = rowptr[i]; p0 < p1; p0 += 64) {
+        __syncthreads();
+        const int p = p0 + lane;
+        int j = i;
+        double co = 0.0;
+        if (p < p1) {
+            j = nbr[p];
+            const float4 g4 = geo[p];
+            const double d = (double)g4.w;
+            if (d < Rcut) {
+                const double x = d * inv_a, er = erf(x), der = 2.0 / sqrt(EW_PI) * inv_a * exp(-x * x);
+                const double cutf = 0.5 * (1.0 + cos(EW_PI * d / Rcut)), dcut = -0.5 * EW_PI / Rcut * sin(EW_PI * d / Rcut);
+                const double n0 = er * cutf, n1 = der * cutf + er * dcut;
+                const double dw = n1 / d - n0 / (d * d);
+                const double n[3] = {(double)g4.x / d, (double)g4.y / d, (double)g4.z / d};
+                double nd = 0.0;
+#pragma unroll
+                for (int a = 0; a < 3; a++) {
+                    double e = U ? (double)U[3 * (int64_t)j + a] - ui[a] : 0.0;
+#pragma unroll
+                    for (int b = 0; b < 3; b++) e += (double)shift[3 * (int64_t)p + b] * (double)uc[3 * b + a];
+                    nd += n[a] * e;
+                }
+                co = -EW_PREFACTOR * dw * nd;
+            }
+        }
+        sj[lane] = j;
+        sco[lane] = co;
+        __syncthreads();
+        const int ne = min(64, p1 - p0);
+        for (int c = lane; c < C; c += 64) {
+            double ag = 0.0, aq = 0.0;
+            for (int q = 0; q < ne; q++) {
+                const int64_t o = (int64_t)sj[q] * C + c;
+                if (out_g) ag += sco[q] * (double)Q[o];
+                if (out_q) aq += sco[q] * (double)G[o];
+            }
+            if (out_g) out_g[(int64_t)i * C + c] += (float)ag;
+            if (out_q) out_q[(int64_t)i * C + c] += (float)aq;
+        }
+    }
+    double Um[9];
+    ew_cell_U(s.inv, uc, Um);
+    const double bg = EW_PREFACTOR * 2.0 * EW_PI * sigma * sigma / s.vol * (Um[0] + Um[4] + Um[8]);
+    for (int c = lane; c < C; c += 64) {
+        if (out_g) out_g[(int64_t)i * C + c] += (float)(bg * (double)sum_q[(int64_t)si * C + c]);
+        if (out_q) out_q[(int64_t)i * C + c] += (float)(bg * (double)sum_g[(int64_t)si * C + c]);
+    }
+}
+
 }  // namespace
 
 // P3M mode (csrc/p3m.hip): mesh descriptors and influence functions in place of k lists
@@ -702,6 +808,11 @@ int p3m_lr_backward(const pet_ewald* e, const Graph& g, const float* pos, const 
                     float* gpos, void* ws, hipStream_t st, int64_t ws_offset);
 int p3m_lr_second(const pet_ewald* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
                   const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st, int64_t ws_offset);
+// the same with a cell tangent Ucell [S, 3, 3] (pet_p3m_second_cell), on one workspace of p3m_lr_cell_workspace_bytes
+int64_t p3m_lr_cell_workspace_bytes(const pet_ewald* e, int C);
+int p3m_lr_second_cell(const pet_ewald* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                       const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, void* ws, hipStream_t st,
+                       int64_t ws_offset);
 
 }  // namespace pet
 
@@ -818,6 +929,19 @@ int ew_local_backward(const pet_ewald_t* e, const Graph& g, const float* pos, co
         kspace_cell();
         k_ew_cell<<<(unsigned)e->n_systems, 256, 0, st>>>(e->d_sys, w.cell_part, w.kpart, w.sum_g, w.sum_q, C, e->sigma, d_grad_cells);
     }
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
+}
+
+// The cell tangent's local terms (section 23) ADDED to out_g / out_q (a null one is not formed): the column sums of Q / of G,
+// then k_ew_edge_cell. U [N, 3] is the caller's position direction (may be null), not u'.
+int ew_local_cell(const pet_ewald_t* e, const Graph& g, const float* Q, const float* G, const float* U, const float* ucell, int C,
+                  const EwLocalWs& w, float* out_g, float* out_q, hipStream_t st) {
+    const unsigned cy = (unsigned)cdiv(C, 256);
+    if (out_g) k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, Q, C, w.sum_q);
+    if (out_q) k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, G, C, w.sum_g);
+    k_ew_edge_cell<<<(unsigned)e->n_atoms, 64, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.shift, g.geo, G, Q, U, ucell, w.sum_q,
+                                                        w.sum_g, C, e->sigma, e->cutoff, out_g, out_q);
     PET_HIP_CHECK(hipGetLastError());
     return PET_OK;
 }

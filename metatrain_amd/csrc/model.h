@@ -270,14 +270,22 @@ struct LrStage {
     int64_t ws_bytes;
     float* rbar;
     int64_t ws_offset;
+    // pet_backward_train2_long_range_cell: the cell tangent [S, 3, 3] of the operator (the backbone's is gen_train2's ucell);
+    // ws then holds lr_stage_workspace_bytes(..., true), with the operator's cell workspace in front
+    const float* ucell = nullptr;
 };
 int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, const float* lA, const float* nA, const float* u,
                const float* ucell, float* tangent_atomic, hipStream_t st, const float* const* seed_node = nullptr,
                const float* const* seed_edge = nullptr, int n_seed = 0, const HvpTaps* hv = nullptr,
                const LrStage* lr = nullptr);
 // the long-range forms of pet_backward_train2 and pet_hessian_vector (abi.hip checks and refuses; these carve and run)
-int64_t lr_stage_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes);
+int64_t lr_stage_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes, bool cell = false);
 int64_t gen_train2_lr_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes, int64_t n_edges);
+// with a cell tangent ucell [S, 3, 3] beside u (either may be null, not both): the stress term of a loss
+int64_t gen_train2_lr_cell_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes, int64_t n_edges);
+int gen_train2_lr_cell(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
+                       const float* lA, const float* nA, const float* u, const float* ucell, float* tangent_atomic,
+                       hipStream_t st);
 int gen_train2_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
                   const float* lA, const float* nA, const float* u, float* tangent_atomic, hipStream_t st);
 int64_t gen_hvp_lr_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes, int64_t n_edges);
@@ -293,6 +301,12 @@ int lr_backward(const pet_ewald_t* e, const Graph& g, const float* pos, const fl
                 float* gpos, void* ws, hipStream_t st, int64_t ws_offset);
 int lr_second(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
               const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st, int64_t ws_offset);
+// the same along (Ur, Ucell [S, 3, 3]) for the two results that feed parameter gradients, on one workspace of
+// lr_ewald_cell_workspace_bytes (pet_ewald_second_cell / pet_p3m_second_cell; Ur or Ucell may be null)
+int64_t lr_ewald_cell_workspace_bytes(const pet_ewald_t* e, int C);
+int lr_second_cell(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                   const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, void* ws, hipStream_t st,
+                   int64_t ws_offset);
 // Hessian-vector product of the fused single-property target on the size-generic dual pass (pet_hessian_vector)
 int64_t gen_hvp_workspace_bytes(const Model& m, int64_t n_nodes, int64_t n_edges);
 int gen_hvp(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* lA, const float* u, const float* ucell,

@@ -12,6 +12,9 @@
 // transforms come back through the handle's hook (pet_p3m_set_transform), between a mesh and a half spectrum inside the call's
 // own workspace. k_p3m_spread2 / k_p3m_gather2 / k_p3m_force2 are the three mesh kernels with the tangent and Hessian weights
 // beside the plain ones; the local terms are long_range.h's (k_ew_pairs<true>, k_ew_force2<false>, k_ew_edge_second).
+// Cell tangents (pet_p3m_second_cell): the position tangent at u' (k_ew_uprime), and the filter's tangent
+// K' = sum_bc d(G^/Omega)/dcell_bc u_c,bc (k_p3m_gdot) applied to the spectrum that p3m_solve_cell has in hand anyway
+// (k_p3m_filter_dot keeps it aside, k_p3m_spec_add adds it to the mesh the tangent gather reads): no transform is added.
 // Layout. CHANNEL-FIRST: the mesh of a system is [C, N_x, N_y, N_z] (z fastest), its half spectrum [C, N_x, N_y, N_z/2 + 1]
 // complex; the meshes of a batch's periodic, non-empty systems are packed one after another (system s starts at mesh_off_s * C).
 // The transforms run over contiguous planes with batch stride M and need no copy; the price is on this side: k_p3m_spread owns
@@ -621,6 +624,68 @@ __global__ __launch_bounds__(256) void k_p3m_cell(const int2* __restrict__ tiles
     if (threadIdx.x < 9) kpart[9 * (int64_t)blockIdx.x + threadIdx.x] = EW_PREFACTOR * red[0][threadIdx.x];
 }
 
+// ---- cell tangents (pet_p3m_second_cell) -----------------------------------------------------------------
+// At fixed fractional coordinates the mesh sum A = W^T K W depends on the cell through the filter alone: along u_c it is
+// W^T K' W with G^/Omega replaced by gdot = sum_bc d(G^/Omega)/dcell_bc u_c,bc (p3m_influence_point's gradient, fp64, rounded
+// once). K' X shares X's forward transform with K X: k_p3m_filter_dot keeps gdot (.) spectrum aside before the filter runs, and
+// k_p3m_spec_add adds it to the filtered spectrum of the mesh that the tangent gather reads, before that one's inverse
+// transform. No transform is added.
+__global__ __launch_bounds__(256) void k_p3m_gdot(const int2* __restrict__ tiles, const P3mSysD* __restrict__ msys,
+                                                  const float* __restrict__ ucell, double sigma, int p,
+                                                  float* __restrict__ gdot) {
+    const int2 tile = tiles[blockIdx.x];
+    const P3mSysD& m = msys[tile.x];
+    const int Mh = m.n[0] * m.n[1] * m.nzh;
+    const float* uc = ucell + 9 * (int64_t)tile.x;
+    for (int r = 0; r < P3M_CHUNK / 256; r++) {
+        const int idx = tile.y + r * 256 + threadIdx.x;
+        if (idx >= Mh) return;
+        int n[3];
+        p3m_spec_index(m, idx, n);
+        double grad[9], acc = 0.0;
+        (void)p3m_influence_point(m.inv, m.vol, m.n, n, sigma, p, grad);
+#pragma unroll
+        for (int k = 0; k < 9; k++) acc += grad[k] * (double)uc[k];
+        gdot[m.soff + idx] = (float)acc;
+    }
+}
+
+// side[c][n] = gdot(n) spectrum[c][n] (the unfiltered spectrum), in the tiling of k_p3m_filter
+__global__ __launch_bounds__(256) void k_p3m_filter_dot(const int2* __restrict__ tiles, const P3mSysD* __restrict__ msys,
+                                                        const float* __restrict__ gdot, int C, const float2* __restrict__ spec,
+                                                        float2* __restrict__ side) {
+    const int2 tile = tiles[blockIdx.x];
+    const P3mSysD& m = msys[tile.x];
+    const int Mh = m.n[0] * m.n[1] * m.nzh;
+    for (int r = 0; r < P3M_CHUNK / 256; r++) {
+        const int idx = tile.y + r * 256 + threadIdx.x;
+        if (idx >= Mh) return;
+        const float g = gdot[m.soff + idx];
+        for (int c = blockIdx.y; c < C; c += gridDim.y) {
+            const int64_t at = m.soff * C + (int64_t)c * Mh + idx;
+            const float2 a = spec[at];
+            side[at] = make_float2(a.x * g, a.y * g);
+        }
+    }
+}
+
+// spectrum[c][n] += side[c][n]
+__global__ __launch_bounds__(256) void k_p3m_spec_add(const int2* __restrict__ tiles, const P3mSysD* __restrict__ msys, int C,
+                                                      const float2* __restrict__ side, float2* __restrict__ spec) {
+    const int2 tile = tiles[blockIdx.x];
+    const P3mSysD& m = msys[tile.x];
+    const int Mh = m.n[0] * m.n[1] * m.nzh;
+    for (int r = 0; r < P3M_CHUNK / 256; r++) {
+        const int idx = tile.y + r * 256 + threadIdx.x;
+        if (idx >= Mh) return;
+        for (int c = blockIdx.y; c < C; c += gridDim.y) {
+            const int64_t at = m.soff * C + (int64_t)c * Mh + idx;
+            const float2 a = spec[at], b = side[at];
+            spec[at] = make_float2(a.x + b.x, a.y + b.y);
+        }
+    }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------
 struct P3mWs {
     float *wts, *dwts;
@@ -806,6 +871,100 @@ int p3m_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const
     return PET_OK;
 }
 
+// The workspace of pet_p3m_second_cell: that of pet_p3m_second (the hook's offsets are its), then u' [N, 3], gdot per
+// half-spectrum point and the side spectrum.
+struct P3mWs3 {
+    P3mWs2 w2;
+    float *up, *gdot;
+    float2* side;
+};
+
+size_t p3m_carve3(const pet_ewald_t* e, int64_t C, void* base, P3mWs3& w3, int64_t ws_offset = 0) {
+    Carver c(base);
+    c.off = p3m_carve2(e, C, base, w3.w2, ws_offset);
+    const size_t Sp = (size_t)std::max<int64_t>(e->p3m->s_total, 1);
+    w3.up = c.take<float>((size_t)std::max<int64_t>(e->n_atoms, 1) * 3);
+    w3.gdot = c.take<float>(Sp);
+    w3.side = c.take<float2>(Sp * C);
+    return c.off;
+}
+
+// p3m_solve with the cell tangent's fold: keep (gdot . the unfiltered spectrum) in the side spectrum, or add the side spectrum
+// to the filtered one. Two hook calls, as p3m_solve.
+enum { CELL_KEEP = 0, CELL_ADD = 1 };
+int p3m_solve_cell(const pet_ewald_t* e, int C, const P3mWs3& w3, int slot, int what, hipStream_t st) {
+    const P3mPlan* mp = e->p3m;
+    const P3mWs2& w2 = w3.w2;
+    if (mp->stiles.empty()) return PET_OK;
+    const dim3 grid((unsigned)mp->stiles.size(), (unsigned)std::min(C, 256));
+    for (int inverse = 0; inverse < 2; inverse++) {
+        const int rc = e->p3m_transform(e->p3m_transform_user, inverse, w2.mesh_off[slot], w2.spec_off, C);
+        PET_REQUIRE(rc == 0, PET_ERR_ARGUMENT,
+                    "the transform hook (pet_p3m_set_transform) returned " + std::to_string(rc) + " for the " +
+                        (inverse ? "inverse" : "forward") + " transform");
+        if (inverse) continue;
+        if (what == CELL_KEEP) k_p3m_filter_dot<<<grid, 256, 0, st>>>(mp->d_stiles, mp->d_sys, w3.gdot, C, w2.spec, w3.side);
+        k_p3m_filter<<<grid, 256, 0, st>>>(mp->d_stiles, mp->d_sys, mp->d_infl, C, w2.spec);
+        if (what == CELL_ADD) k_p3m_spec_add<<<grid, 256, 0, st>>>(mp->d_stiles, mp->d_sys, C, w3.side, w2.spec);
+    }
+    PET_HIP_CHECK(hipGetLastError());
+    return PET_OK;
+}
+
+// pet_p3m_second_cell: out_g = A u_q + (D A) q, out_q = (D A) g along (u_r, u_c); a null result is not formed. The position
+// tangent is p3m_second_run's at u' = u_r - r U; the filter's tangent rides on the same transforms (above); the local terms are
+// k_ew_pairs<true> at u' and ew_local_cell. Transform pairs: 2 per result formed (4 hook calls), whatever the cotangents.
+// Without Ucell it is p3m_second_run without out_r.
+int p3m_second_cell_run(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                        const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, const P3mWs3& w3, hipStream_t st) {
+    const P3mWs2& w2 = w3.w2;
+    if (!Ucell) return p3m_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, nullptr, w2, st);
+    const P3mPlan* mp = e->p3m;
+    const P3mWs& w = w2.w;
+    const int N = (int)e->n_atoms, p = e->p3m_nodes;
+    const bool per = mp->m_total > 0;
+    const unsigned cy = (unsigned)cdiv(C, 256), nn = (unsigned)e->atiles_n.size(), na = (unsigned)cdiv(N, 4);
+    const float inv_R = (float)(1.0 / e->cutoff);
+    ProfScope ps(out_g && out_q ? "p3m_second_cell" : out_g ? "p3m_second_cell_g" : "p3m_second_cell_q", st, 0.0, 0.0);
+    k_ew_uprime<<<cdiv(N, 256), 256, 0, st>>>(pos, g.sys, e->d_sys, Ur, Ucell, N, w3.up);
+    PET_TRY(p3m_bin(e, g, pos, w, st, nullptr, w3.up, w2.du));
+    if (!mp->stiles.empty())
+        k_p3m_gdot<<<(unsigned)mp->stiles.size(), 256, 0, st>>>(mp->d_stiles, mp->d_sys, Ucell, e->sigma, p, w3.gdot);
+    auto mesh_of = [&](int slot, const float* X1, const float* X2, int what) -> int {
+        if (!per) return PET_OK;
+        k_p3m_spread2<<<dim3((unsigned)mp->mtiles.size(), (unsigned)cdiv(C, P3M_CH)), 256, 0, st>>>(
+            mp->d_mtiles, mp->d_sys, w.start, w.order, w.wts, w.dwts, w2.du, p, X1, X2, C, w2.mesh[slot]);
+        return p3m_solve_cell(e, C, w3, slot, what, st);
+    };
+    auto gather = [&](const float* phi_a, const float* phi_b, float scale, float* out) {
+        if (per)
+            k_p3m_gather2<<<na, 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, w.dwts, w2.du, p, phi_a, phi_b, N, C, scale, out);
+    };
+    if (out_g) {
+        // phi_q = K W q, then K (W u_q + (D_u' W) q) + K' W q as ONE mesh
+        PET_TRY(mesh_of(MESH_Q, Q, nullptr, CELL_KEEP));
+        PET_TRY(mesh_of(MESH_A, Uq, Q, CELL_ADD));
+        if (Uq) {
+            gather(w2.mesh[MESH_A], w2.mesh[MESH_Q], 1.f, out_g);
+            PET_TRY(ew_local_forward(e, g, pos, Uq, C, out_g, w.loc.sum_g, st));
+        } else {
+            PET_HIP_CHECK(hipMemsetAsync(out_g, 0, (size_t)N * C * sizeof(float), st));
+            gather(w2.mesh[MESH_A], w2.mesh[MESH_Q], (float)EW_PREFACTOR, out_g);
+        }
+    }
+    if (out_q) {
+        PET_TRY(mesh_of(MESH_G, G, nullptr, CELL_KEEP));
+        PET_TRY(mesh_of(MESH_DG, nullptr, G, CELL_ADD));
+        PET_HIP_CHECK(hipMemsetAsync(out_q, 0, (size_t)N * C * sizeof(float), st));
+        gather(w2.mesh[MESH_DG], w2.mesh[MESH_G], (float)EW_PREFACTOR, out_q);
+    }
+    if (nn) {
+        if (out_g) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, Q, C, out_g, w3.up);
+        if (out_q) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, G, C, out_q, w3.up);
+    }
+    return ew_local_cell(e, g, Q, G, Ur, Ucell, C, w.loc, out_g, out_q, st);
+}
+
 const char* const P3M_NO_HOOK =
     "a P3M-mode handle without a transform hook: the mesh operator's second derivatives and its place in the dual pass need "
     "the caller's transforms (pet_p3m_set_transform)";
@@ -857,6 +1016,19 @@ int p3m_lr_second(const pet_ewald_t* e, const Graph& g, const float* pos, const 
     P3mWs2 w2;
     p3m_carve2(e, C, ws, w2, ws_offset);
     return p3m_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, out_r, w2, st);
+}
+
+int64_t p3m_lr_cell_workspace_bytes(const pet_ewald_t* e, int C) {
+    P3mWs3 w3;
+    return (int64_t)p3m_carve3(e, C, nullptr, w3);
+}
+
+int p3m_lr_second_cell(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
+                       const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, void* ws, hipStream_t st,
+                       int64_t ws_offset) {
+    P3mWs3 w3;
+    p3m_carve3(e, C, ws, w3, ws_offset);
+    return p3m_second_cell_run(e, g, pos, Q, G, Uq, Ur, Ucell, C, out_q, out_g, w3, st);
 }
 
 // pet_ewald_plan of a P3M-mode handle: mesh descriptors and influence functions instead of k lists, for the systems the shared
@@ -1096,6 +1268,34 @@ int pet_p3m_second(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_p
     p3m_carve2(e, C, d_workspace, w2);
     return p3m_second_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, C, d_out_charges,
                           d_out_grad_potential, d_out_positions, w2, (hipStream_t)stream);
+}
+
+int64_t pet_p3m_second_cell_workspace_bytes(const pet_ewald_t* e, int64_t n_channels) {
+    if (!e || !e->planned || !e->p3m || n_channels < 1) return -1;
+    P3mWs3 w3;
+    return (int64_t)p3m_carve3(e, n_channels, nullptr, w3);
+}
+
+int pet_p3m_second_cell(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
+                        const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions,
+                        const float* d_u_cells, int32_t C, float* d_out_charges, float* d_out_grad_potential, void* d_workspace,
+                        int64_t workspace_bytes, void* stream) {
+    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(e->p3m_nodes != 0, PET_ERR_ARGUMENT,
+                "a pet_p3m_* entry point on an Ewald-mode handle: call pet_ewald_set_p3m before pet_ewald_plan");
+    PET_TRY(ew_check_graph(e, pg, C));
+    PET_REQUIRE(e->p3m_transform, PET_ERR_ARGUMENT, std::string("pet_p3m_second_cell on ") + P3M_NO_HOOK);
+    PET_REQUIRE(d_u_charges || d_u_positions || d_u_cells, PET_ERR_ARGUMENT,
+                "d_u_charges, d_u_positions and d_u_cells are all NULL");
+    if (e->n_atoms == 0) return PET_OK;
+    P3mWs3 w3;
+    PET_REQUIRE(d_workspace && workspace_bytes >= (int64_t)p3m_carve3(e, C, nullptr, w3), PET_ERR_ARGUMENT,
+                "P3M workspace missing or too small (pet_p3m_second_cell_workspace_bytes)");
+    PET_REQUIRE(d_positions && d_charges && d_grad_potential, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(d_out_charges || d_out_grad_potential, PET_ERR_ARGUMENT, "both results are NULL");
+    p3m_carve3(e, C, d_workspace, w3);
+    return p3m_second_cell_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, d_u_cells, C,
+                               d_out_charges, d_out_grad_potential, w3, (hipStream_t)stream);
 }
 
 }  // extern "C"

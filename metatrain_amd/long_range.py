@@ -28,8 +28,11 @@ and a Hessian-vector product need from the operator. At the MODEL level (DESIGN.
 carries the featuriser between the backbone and the heads (``pet_backward_train2_long_range``,
 ``pet_hessian_vector_long_range``): :class:`LongRangeForward` and :class:`LongRangeTrainStep` are the training step on
 energies and forces, :func:`hessian_vector_product` is ``H u``. The six featuriser tensors then live in the model's own
-parameter table (:meth:`LongRangeFeaturizerHip.bind`). Not built, each raising by name: cell tangents and cell results
-(a stress / strain-gradient loss, cell directions of a Hessian-vector product), further targets in the long-range step.
+parameter table (:meth:`LongRangeFeaturizerHip.bind`). Behind ``LongRangeFeaturizerHip(...,
+cell_tangents=True)`` the loss may hold a stress term (``EwaldHip.second_cell`` / ``P3MHip.second_cell``,
+``pet_backward_train2_long_range_cell``). Not built, each raising by name: a stress / strain-gradient loss without that
+opt-in, the position result under a cell tangent and every cell result of the second-order operation (cell directions of a
+Hessian-vector product, cells that require grad in a double backward), further targets in the long-range step.
 
 The reference takes its Ewald branch only under ``use_ewald and training`` (``utils/long_range.py:153-170``): with its default
 hypers (``use_ewald: false``) a periodic long-range model goes through P3M in training and in evaluation alike.
@@ -186,6 +189,7 @@ class EwaldHip:
     _warns_kset = True  # the k-set warning is the Ewald sum's: a mesh operator walks no k-set
     _workspace_bytes = "pet_ewald_workspace_bytes"
     _second_entry = ("pet_ewald_second_workspace_bytes", "pet_ewald_second")
+    _second_cell_entry = ("pet_ewald_second_cell_workspace_bytes", "pet_ewald_second_cell")
 
     def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5):
         global _warned_kset
@@ -202,6 +206,7 @@ class EwaldHip:
         self.n_systems = -1
         self._workspace: Optional[torch.Tensor] = None
         self._second_workspaces: Dict[int, torch.Tensor] = {}  # by channel count (``second``)
+        self._cell_workspaces: Dict[int, torch.Tensor] = {}  # by channel count (``second_cell``)
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -231,6 +236,7 @@ class EwaldHip:
         self.n_systems = n_sys
         self._workspace = None
         self._second_workspaces = {}
+        self._cell_workspaces = {}
         return self
 
     def num_kvectors(self, system: int) -> int:
@@ -283,6 +289,39 @@ class EwaldHip:
         work is skipped), not both. No cell tangent is taken and no cell result returned."""
         return self._second(graph, positions, charges, grad_potential, u_charges, u_positions, (True, True, True))
 
+    def second_cell(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor, grad_potential: torch.Tensor,
+                    u_charges: Optional[torch.Tensor] = None, u_positions: Optional[torch.Tensor] = None,
+                    u_cells: Optional[torch.Tensor] = None, results: Sequence[bool] = (True, True)):
+        """:meth:`second` with a cotangent ``u_cells [S, 3, 3]`` of ``dL/dcell`` beside the other two (``pet_ewald_second_cell``;
+        DESIGN.md section 23): ``(out_charges, out_grad_potential)``, the gradient of ``<u_charges, dL/dq> + <u_positions, dL/dR>
+        + <u_cells, dL/dcell>`` with respect to ``(charges, grad_potential)`` -- the two results that feed parameter gradients.
+        Any cotangent may be ``None`` (zero), not all three; rows of ``u_cells`` of open systems are ignored. ``results``: which
+        of the two to form (the other comes back ``None``, the one formed has the bits of the full call). The position and
+        cell results (mixed and second cell derivatives) are not built."""
+        if u_charges is None and u_positions is None and u_cells is None:
+            raise PetHipError("second_cell: u_charges, u_positions and u_cells are all None")
+        results = tuple(bool(x) for x in results)
+        if len(results) != 2 or not any(results):
+            raise PetHipError("second_cell: results names two flags (out_charges, out_grad_potential), at least one set")
+        rt._require_cuda(*[t for t in (u_charges, u_positions, u_cells) if t is not None])
+        pos, q, g = self._inputs(positions, charges, grad_potential)
+        uq = None if u_charges is None else u_charges.detach().to(torch.float32).reshape(q.shape).contiguous()
+        ur = None if u_positions is None else u_positions.detach().to(torch.float32).reshape(pos.shape).contiguous()
+        uc = None if u_cells is None else u_cells.detach().to(torch.float32).reshape(graph.n_systems, 3, 3).contiguous()
+        C = int(q.shape[1])
+        bytes_name, entry_name = self._second_cell_entry
+        nbytes = int(getattr(self.lib, bytes_name)(self._handle, C))
+        if nbytes < 0:
+            raise PetHipError(f"{bytes_name} failed: call plan() first")
+        ws = self._cell_workspaces.get(C)
+        if ws is None or ws.numel() < nbytes or ws.device != q.device:
+            ws = self._cell_workspaces[C] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=q.device)
+        outs = tuple(torch.empty_like(q) if want else None for want in results)
+        entry = getattr(self.lib, entry_name)
+        self._with_hook(ws, lambda: entry(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), rt._ptr(g), rt._ptr(uq), rt._ptr(ur),
+                                          rt._ptr(uc), C, rt._ptr(outs[0]), rt._ptr(outs[1]), rt._ptr(ws), ws.numel(), rt._stream()))
+        return outs
+
     def _with_hook(self, workspace: Optional[torch.Tensor], call) -> None:
         """``check(call())`` for an entry point that runs on ``workspace``; :class:`P3MHip` serves its transform hook there."""
         check(call())
@@ -324,6 +363,7 @@ class P3MHip(EwaldHip):
     _warns_kset = False
     _workspace_bytes = "pet_p3m_workspace_bytes"
     _second_entry = ("pet_p3m_second_workspace_bytes", "pet_p3m_second")
+    _second_cell_entry = ("pet_p3m_second_cell_workspace_bytes", "pet_p3m_second_cell")
 
     def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5, interpolation_nodes: int = 5,
                  second_order: bool = False):
@@ -427,6 +467,17 @@ class P3MHip(EwaldHip):
         if len(results) != 3 or not any(results):
             raise PetHipError("second: results names three flags (out_charges, out_grad_potential, out_positions), at least one set")
         return self._second(graph, positions, charges, grad_potential, u_charges, u_positions, results)
+
+    def second_cell(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor, grad_potential: torch.Tensor,
+                    u_charges: Optional[torch.Tensor] = None, u_positions: Optional[torch.Tensor] = None,
+                    u_cells: Optional[torch.Tensor] = None, results: Sequence[bool] = (True, True)):
+        """:meth:`EwaldHip.second_cell` through the mesh operator (``pet_p3m_second_cell``), for an operator built with
+        ``second_order=True``: the filter's cell tangent rides on the transforms of the position tangent, four hook calls per
+        result formed."""
+        if not self.second_order:
+            raise PetHipError("cell tangents through P3M are not built on this operator: second_order=True "
+                              "(P3MHip(..., second_order=True)) installs the transform hook they need")
+        return super().second_cell(graph, positions, charges, grad_potential, u_charges, u_positions, u_cells, results)
 
     def _mesh_potential(self, graph, pos, x, ws, keep_spectrum: bool = False):
         """spread -> rfftn -> filter -> irfftn of ``x [N, C]``: the mesh potential (packed, channel-first) and, on request, the
@@ -535,11 +586,17 @@ class LongRangeFeaturizerHip:
     ``use_ewald: false``; ``method="ewald"`` is ``p3m_as_ewald=True``."""
 
     def __init__(self, hypers: dict, device=None, p3m_as_ewald: bool = False, method: Optional[str] = None,
-                 second_order: bool = False):
+                 second_order: bool = False, cell_tangents: bool = False):
         self.long_range = resolve_hypers(hypers, p3m_as_ewald, method)
         if second_order and method != "p3m":
             raise PetHipError("second_order=True is the switch of the P3M operator (method='p3m'): the Ewald operator has its "
                               f"second derivatives without it, got method={method!r}")
+        if cell_tangents and method == "p3m" and not second_order:
+            raise PetHipError("cell_tangents=True with method='p3m' needs second_order=True as well: the mesh operator's cell "
+                              "tangents run their transforms through the hook that second_order=True installs")
+        # the opt-in of the stress term (DESIGN.md section 23): LongRangeForward.backward_train2(u_cell=...) and
+        # LongRangeTrainStep(target_strain_gradients=...) run the cell-tangent sweep; without it they refuse as before
+        self.cell_tangents = bool(cell_tangents)
         self.method = method
         self.d = int(hypers["d_node"])
         self.cutoff = float(hypers["cutoff"])
@@ -574,8 +631,8 @@ class LongRangeFeaturizerHip:
     @classmethod
     def from_state_dict(cls, hypers: dict, state: Dict[str, torch.Tensor], device=None, p3m_as_ewald: bool = False,
                         prefix: str = "long_range_featurizer.", method: Optional[str] = None,
-                        second_order: bool = False) -> "LongRangeFeaturizerHip":
-        self = cls(hypers, device, p3m_as_ewald, method, second_order)
+                        second_order: bool = False, cell_tangents: bool = False) -> "LongRangeFeaturizerHip":
+        self = cls(hypers, device, p3m_as_ewald, method, second_order, cell_tangents)
         self.load_state_dict(state, prefix)
         return self
 
@@ -753,12 +810,13 @@ class LongRangeForward:
                               "(weighted sums: hessian_vector_product / backward_train2 take lambda_atomic)")
         return self._first if want_cell_grad else self._first[0]
 
-    def _sweep(self, lam, nu, u, want_tangent):
+    def _sweep(self, lam, nu, u, want_tangent, u_cell=None):
         self._plan()
         g, dev = self.graph, self.graph.workspace.device
-        need = int(self.lib.pet_train2_long_range_workspace_bytes(self.model.handle, g.handle, self.featurizer.ewald.handle))
+        bytes_name = "pet_train2_long_range_workspace_bytes" if u_cell is None else "pet_train2_long_range_cell_workspace_bytes"
+        need = int(getattr(self.lib, bytes_name)(self.model.handle, g.handle, self.featurizer.ewald.handle))
         if need < 0:
-            raise PetHipError(self.lib.pet_last_error().decode(errors="replace") or "pet_train2_long_range_workspace_bytes failed")
+            raise PetHipError(self.lib.pet_last_error().decode(errors="replace") or f"{bytes_name} failed")
         if self.workspace2 is None or self.workspace2.numel() < need:
             self.workspace2 = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
         f32 = lambda t: None if t is None else t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
@@ -766,6 +824,12 @@ class LongRangeForward:
         pos = g._pos.detach().to(torch.float32).contiguous()
         tan = torch.empty(g.n_nodes, dtype=torch.float32, device=dev) if want_tangent else None
         op, ws = self.featurizer.ewald, self.workspace2
+        if u_cell is not None:
+            uc = f32(u_cell).reshape(g.n_systems, 3, 3)
+            op._with_hook(ws, lambda: self.lib.pet_backward_train2_long_range_cell(
+                self.model.handle, g.handle, op.handle, rt._ptr(pos), rt._ptr(ws), ws.numel(), rt._ptr(lam), rt._ptr(nu),
+                rt._ptr(u), rt._ptr(uc), rt._ptr(tan), rt._stream()))
+            return tan
         op._with_hook(ws, lambda: self.lib.pet_backward_train2_long_range(
             self.model.handle, g.handle, op.handle, rt._ptr(pos), rt._ptr(ws), ws.numel(), rt._ptr(lam), rt._ptr(nu), rt._ptr(u),
             rt._ptr(tan), rt._stream()))
@@ -788,13 +852,15 @@ class LongRangeForward:
     def backward_train2(self, lambda_atomic: torch.Tensor, nu_atomic: Optional[torch.Tensor], u: torch.Tensor,
                         want_tangent: bool = False, u_cell: Optional[torch.Tensor] = None, seed_features=None):
         """Force loss: ADDS d/dtheta ``[sum_i nu_i e_i + <u, dE/dR>]`` (gradient taken with seeds ``lambda_atomic``) to the
-        gradient slots; on request returns ``e'_i`` along ``u``."""
-        if u_cell is not None:
+        gradient slots; on request returns ``e'_i`` along ``u``. With a featuriser built under ``cell_tangents=True``, ``u_cell
+        [S, 3, 3] = dL/d(dE/dcell)`` adds ``<u_cell, dE/dcell>`` (``pet_backward_train2_long_range_cell``; ``u`` may then be
+        ``None``)."""
+        if u_cell is not None and not getattr(self.featurizer, "cell_tangents", False):
             raise PetHipError("u_cell (a cell tangent: the stress / strain-gradient loss) of a long-range model is not built: "
                               "the operator's second-order entry takes no cell tangent")
         if seed_features is not None:
             raise PetHipError("seed_features (further targets) in the long-range training step are not built")
-        return self._sweep(lambda_atomic, nu_atomic, u, want_tangent)
+        return self._sweep(lambda_atomic, nu_atomic, u, want_tangent, u_cell)
 
 
 from .pet.trainer import TrainStep  # noqa: E402  (trainer imports runtime only: no cycle)
@@ -804,7 +870,10 @@ class LongRangeTrainStep(TrainStep):
     """:class:`TrainStep` for a long-range model: energy and position-gradient terms, by ``loss_weights`` (MSE) or the
     ``loss`` hyper (MSE / MAE / Huber), with a :class:`LongRangeForward` in place of the ``HipForward``. ``featurizer`` is
     bound to the model (:meth:`LongRangeFeaturizerHip.bind`): the model's table holds the six tensors, the optimizer step
-    updates them there and the featuriser's copies are refreshed after it. Refused by name: ``target_strain_gradients``,
+    updates them there and the featuriser's copies are refreshed after it. With a featuriser built under ``cell_tangents=True``
+    the step takes ``target_strain_gradients`` (with ``positions`` and ``cells``) on both loss paths, in ``microbatched`` and in
+    ``begin`` / ``end``: the seeds are the base class's (``strain_loss_and_seeds``; ``u_cell = cell @ g``), the sweep is
+    ``pet_backward_train2_long_range_cell``. Refused by name: ``target_strain_gradients`` without that opt-in,
     ``extra_targets``, a P3M featuriser built without ``second_order=True``."""
 
     _serves_long_range = True
@@ -817,7 +886,7 @@ class LongRangeTrainStep(TrainStep):
 
     @staticmethod
     def _refuse(fw, target_strain_gradients, extra_targets) -> None:
-        if target_strain_gradients is not None:
+        if target_strain_gradients is not None and not getattr(getattr(fw, "featurizer", None), "cell_tangents", False):
             raise PetHipError("target_strain_gradients (the stress loss) of a long-range model are not built: the operator's "
                               "second-order entry takes no cell tangent")
         if extra_targets:
@@ -828,8 +897,8 @@ class LongRangeTrainStep(TrainStep):
     def _accumulate(self, graph, fw, target_energies, n_atoms, target_gradients, target_strain_gradients, positions, cells,
                     share_e, share_f, share_s, extra_targets=None, extra_counts=None):
         self._refuse(fw, target_strain_gradients, extra_targets)
-        return super()._accumulate(graph, fw, target_energies, n_atoms, target_gradients, None, positions, cells, share_e,
-                                   share_f, share_s, None, extra_counts)
+        return super()._accumulate(graph, fw, target_energies, n_atoms, target_gradients, target_strain_gradients, positions,
+                                   cells, share_e, share_f, share_s, None, extra_counts)
 
     def _term_arrays(self, b):
         self._refuse(b["fw"], b.get("target_strain_gradients"), b.get("extra_targets"))

@@ -20,7 +20,15 @@ the Ewald legs above alternated in the same run where the Ewald plan serves the 
 indices per axis: the 10 000-atom box has no Ewald legs). Legs: the sweep, the whole step, ``P3MHip.second`` with all three
 results and with each result alone, energies and forces; the sweep's own operator stages (``p3m_*`` / ``ewald_*``) from the
 event profiler. Calls per sample scale down with the box (``--calls`` at 1 000 atoms). Writes
-``profiles/long_range_p3m_train_bench.json``."""
+``profiles/long_range_p3m_train_bench.json``.
+
+    python tools/gpu_long_range_train_bench.py --stress [--atoms 1000]
+
+The cost of the CELL tangent (``cell_tangents=True``), by Ewald summation and through P3M on one box: the
+sweep with ``(u, u_cell)`` against the same sweep with ``u`` alone on the same build, the whole step with and without the strain
+term, and ``second_cell`` against ``second`` without its position result; all legs alternating. The sweeps' operator stages from
+the event profiler in a pass of their own. ``--profile-sweeps K --stress [--p3m]`` runs K sweeps with ``(u, u_cell)`` alone, for a
+kernel trace. Writes ``profiles/long_range_stress_train_bench.json``."""
 import argparse
 import json
 import os
@@ -43,7 +51,7 @@ TYPES = [1, 6, 7, 8]
 LR = {"enable": True, "use_ewald": True, "smearing": 1.4, "kspace_resolution": 1.33, "interpolation_nodes": 5}
 
 
-def build(enable, pos, z, cell, dev, method=None):
+def build(enable, pos, z, cell, dev, method=None, cell_tangents=False):
     hypers = default_hypers()
     if enable:
         hypers["long_range"] = dict(LR)
@@ -51,7 +59,8 @@ def build(enable, pos, z, cell, dev, method=None):
     feat = None
     if enable:
         torch.manual_seed(0)  # (the featuriser draws its six tensors: the same ones for either operator)
-        feat = lr.LongRangeFeaturizerHip(hypers, device=dev, method=method, second_order=method == "p3m")
+        feat = lr.LongRangeFeaturizerHip(hypers, device=dev, method=method, second_order=method == "p3m",
+                                         cell_tangents=cell_tangents)
         params.update({k: v.cpu() for k, v in feat.state_dict().items()})
     model = rt.HipModel(hypers, TYPES)
     model.load({k: v.to(dev) for k, v in params.items()}, "energy")
@@ -137,6 +146,94 @@ def p3m_box(n, args, dev):
             "transform_hook_calls_per_sweep": None if "p3m" not in ops else _hook_calls(ops["p3m"], sweeps["p3m"])}
 
 
+def stress_main(args):
+    dev = torch.device("cuda:0")
+    n = (args.atoms or [1000])[0]
+    pos, z, cell = synthetic.random_box(n, seed=11)
+    pbcs = [[True] * 3]
+    gen = torch.Generator(device=dev).manual_seed(0)
+    nu = torch.rand(n, device=dev, generator=gen) - 0.5
+    u = torch.randn(n, 3, device=dev, generator=gen)
+    u_cell = cell.to(dev)[None] @ (0.1 * torch.randn(1, 3, 3, device=dev, generator=gen))
+    ones = torch.ones(n, device=dev)
+    te, tg, n_atoms = torch.zeros(1, device=dev), torch.zeros(n, 3, device=dev), torch.full((1,), float(n), device=dev)
+    ts = torch.zeros(1, 3, 3, device=dev)
+    train = {"learning_rate": 1e-6, "warmup_fraction": 0.0, "num_epochs": 10**9}
+    p32, c32 = pos.to(dev), cell[None].to(dev)
+    legs, sweeps, info = {}, {}, {}
+    for tag, method in (("ewald", None), ("p3m", "p3m")):
+        if args.profile_sweeps and (tag == "p3m") != args.p3m:
+            continue
+        hyp, model, graph, feat = build(True, pos, z, cell, dev, method, cell_tangents=True)
+        fw = lr.LongRangeForward(model, feat, graph, pbcs)
+        step = lr.LongRangeTrainStep(model, feat, train)
+        c = hyp["d_node"]
+        q, g, uq = (torch.randn(n, c, device=dev, generator=gen) for _ in range(3))
+        op = feat.ewald
+
+        def sweep(model=model, fw=fw, uc=None):
+            model.zero_grad()
+            fw.backward_train2(ones, nu, u, u_cell=uc)
+
+        sweeps[tag] = (sweep, lambda sweep=sweep: sweep(uc=u_cell))
+        legs[f"sweep_u_{tag}"] = sweeps[tag][0]
+        legs[f"sweep_u_and_u_cell_{tag}"] = sweeps[tag][1]
+        legs[f"step_energy_forces_{tag}"] = lambda step=step, graph=graph, fw=fw: step(graph, fw, te, n_atoms, tg)
+        legs[f"step_energy_forces_strain_{tag}"] = lambda step=step, graph=graph, fw=fw: step(
+            graph, fw, te, n_atoms, tg, target_strain_gradients=ts, positions=p32, cells=c32)
+        if tag == "p3m":
+            legs["operator_second_two_results_p3m"] = lambda op=op, graph=graph, q=q, g=g, uq=uq: op.second(
+                graph, p32, q, g, uq, u, results=(True, True, False))
+        legs[f"operator_second_cell_{tag}"] = lambda op=op, graph=graph, q=q, g=g, uq=uq: op.second_cell(graph, p32, q, g, uq, u, u_cell)
+        info[tag] = {"graph_edges": graph.n_edges, "channels": c, "op": op}
+    if args.profile_sweeps:
+        for fn in sweeps.values():
+            for _ in range(args.profile_sweeps + 1):
+                fn[1]()
+        torch.cuda.synchronize()
+        return
+    for fn in legs.values():
+        fn()
+    torch.cuda.synchronize()
+    for tag, v in info.items():   # (the plan exists after the first sweep)
+        op = v.pop("op")
+        v.update(kvectors=op.num_kvectors(0) if tag == "ewald" else None, mesh=op.mesh_shape(0) if tag == "p3m" else None)
+    samples = {k: [] for k in legs}
+    for _ in range(args.repeats):
+        for name, fn in legs.items():
+            t0 = time.perf_counter()
+            for _ in range(args.calls):
+                fn()
+            torch.cuda.synchronize()
+            samples[name].append(1e3 * (time.perf_counter() - t0) / args.calls)
+    med = {k: statistics.median(v) for k, v in samples.items()}
+    stages = {}
+    for tag, pair in sweeps.items():
+        for which, fn in zip(("u", "u_and_u_cell"), pair):
+            rt.profile(True)
+            for _ in range(args.calls):
+                fn()
+            torch.cuda.synchronize()
+            stages[f"{which}_{tag}"] = {r["name"]: {"ms_per_call": r["total_ms"] / max(r["calls"], 1),
+                                                   "calls_per_sweep": r["calls"] / args.calls}
+                                        for r in rt.profile_report() if r["name"].startswith(("ewald", "p3m"))}
+            rt.profile(False)
+    result = {"workload": f"{n}-atom synthetic periodic box, default PET, long-range featuriser with cell_tangents=True by Ewald "
+                          "summation and through P3M (interpolation_nodes 5, mesh spacing 1.33); ms per call on the host clock "
+                          f"around {args.calls} calls and a synchronise, median of {args.repeats} samples, all legs alternating, "
+                          "after one warm-up call each; operator stages from device events in passes of their own",
+              "atoms": n, "info": info, "ms": samples, "ms_median": med, "ms_min": {k: min(v) for k, v in samples.items()},
+              "ms_max": {k: max(v) for k, v in samples.items()},
+              "cell_tangent_ms": {t: med[f"sweep_u_and_u_cell_{t}"] - med[f"sweep_u_{t}"] for t in sweeps},
+              "strain_term_ms": {t: med[f"step_energy_forces_strain_{t}"] - med[f"step_energy_forces_{t}"] for t in sweeps},
+              "sweep_operator_stages": stages}
+    out = args.out or os.path.join(ROOT, "profiles", "long_range_stress_train_bench.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as fh:
+        json.dump(result, fh)
+    print(json.dumps({k: v for k, v in result.items() if k != "ms"}))
+
+
 def _hook_calls(op, sweep):
     before = op.transform_calls
     sweep()
@@ -170,7 +267,11 @@ def main():
     ap.add_argument("--profile-sweeps", type=int, default=0,
                     help="run only this many long-range second-order sweeps after one warm-up and exit: the command to put "
                          "under rocprofv3 --kernel-trace --stats (profiles/long_range_train_kernel_stats.csv)")
+    ap.add_argument("--stress", action="store_true",
+                    help="the cost of the cell tangent and of the strain term (profiles/long_range_stress_train_bench.json)")
     args = ap.parse_args()
+    if args.stress:
+        return stress_main(args)
     if args.p3m:
         args.atoms = args.atoms or [1000, 10000]
         return p3m_main(args)

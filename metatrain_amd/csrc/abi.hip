@@ -7,6 +7,7 @@
 
 #include "common.h"
 #include "model.h"
+#include "long_range.h"
 
 namespace pet {
 
@@ -819,7 +820,7 @@ static int long_range_check(const pet_model_t* pm, const pet_graph_t* pg, const 
 
 int64_t pet_train2_long_range_workspace_bytes(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e) {
     if (long_range_check(pm, pg, e, "pet_backward_train2_long_range")) return -1;
-    return gen_train2_lr_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges);
+    return lr_sweep_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges, LR_TRAIN);
 }
 
 int pet_backward_train2_long_range(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e,
@@ -837,14 +838,14 @@ int pet_backward_train2_long_range(const pet_model_t* pm, const pet_graph_t* pg,
     int rc;
     if ((rc = lora_begin(m, st))) return rc;
     if ((rc = gen_train2_lr(m, pg->g, e, d_positions, d_workspace, workspace_bytes, d_u ? d_lambda_atomic : nullptr,
-                            d_nu_atomic, d_u, d_tangent_atomic, st)))
+                            d_nu_atomic, d_u, nullptr, d_tangent_atomic, st)))
         return rc;
     return lora_end(m, st);
 }
 
 int64_t pet_train2_long_range_cell_workspace_bytes(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e) {
     if (long_range_check(pm, pg, e, "pet_backward_train2_long_range_cell")) return -1;
-    return gen_train2_lr_cell_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges);
+    return lr_sweep_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges, LR_TRAIN_CELL);
 }
 
 int pet_backward_train2_long_range_cell(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e,
@@ -864,15 +865,15 @@ int pet_backward_train2_long_range_cell(const pet_model_t* pm, const pet_graph_t
     const hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = lora_begin(m, st))) return rc;
-    if ((rc = gen_train2_lr_cell(m, pg->g, e, d_positions, d_workspace, workspace_bytes, dir ? d_lambda_atomic : nullptr,
-                                 d_nu_atomic, d_u, d_u_cell, d_tangent_atomic, st)))
+    if ((rc = gen_train2_lr(m, pg->g, e, d_positions, d_workspace, workspace_bytes, dir ? d_lambda_atomic : nullptr, d_nu_atomic,
+                            d_u, d_u_cell, d_tangent_atomic, st)))
         return rc;
     return lora_end(m, st);
 }
 
 int64_t pet_hvp_long_range_workspace_bytes(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e) {
     if (long_range_check(pm, pg, e, "pet_hessian_vector_long_range")) return -1;
-    return gen_hvp_lr_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges);
+    return lr_sweep_workspace_bytes(pm->m, e, pg->g.n_nodes, pg->g.n_edges, LR_HVP);
 }
 
 int pet_hessian_vector_long_range(const pet_model_t* pm, const pet_graph_t* pg, const pet_ewald_t* e,

@@ -26,8 +26,10 @@
 // the one k_ew_gather<true>, and ew_local_cell (k_ew_edge_cell) takes the place of k_ew_edge_second. New kernels and launches
 // only: every instantiation above is what it was.
 // Here: the k-space part (k_ew_tables, k_ew_sfac, k_ew_gather, k_ew_force<true>, k_ew_zk, the k list) and pet_ewald_*, among
-// them the plan of both modes, and lr_* (what the dual pass calls, dispatching on the handle's mode). The handle, k_ew_force
-// and the local terms' kernels are in long_range.h, shared with p3m.hip.
+// them the plan of both modes, and lr_* (the operator's interface of long_range.h, where the handle's mode is decided: the
+// dual pass calls it, pet_ewald_* run its Ewald half). The handle, k_ew_force and the local terms' kernels are in
+// long_range.h, shared with p3m.hip.
+#define LONG_RANGE_SHARED_PART
 #include "long_range.h"
 
 namespace pet {
@@ -422,56 +424,93 @@ int ew_apply(const pet_ewald_t* e, const Graph& g, const float* pos, const float
     return ew_local_forward(e, g, pos, X, C, out, sums, st);
 }
 
-// the workspace of pet_ewald_second: that of the other entry points, then S'(u_q) and the two weighted structure factors
+// the workspace of the second-order operation: that of the first-order entry points, then S'(u_q) and the two weighted
+// structure factors, then (cell: pet_ewald_second_cell) u' [N, 3]
 struct EwWs2 {
     EwWs w;
     float *S3, *Su1, *Su2;
+    float* up;
 };
 
-size_t ew_carve2(const pet_ewald_t* e, int64_t C, void* base, EwWs2& w2) {
+size_t ew_carve2(const pet_ewald_t* e, int64_t C, void* base, EwWs2& w2, bool cell) {
     Carver c(base);
     c.off = ew_carve(e, C, base, w2.w);
     const size_t K = (size_t)std::max<int64_t>(e->n_k, 1);
     w2.S3 = c.take<float>(K * 2 * C);
     w2.Su1 = c.take<float>(K * 2 * C);
     w2.Su2 = c.take<float>(K * 2 * C);
+    w2.up = cell ? c.take<float>((size_t)std::max<int64_t>(e->n_atoms, 1) * 3) : nullptr;
     return c.off;
 }
 
-// the workspace of pet_ewald_second_cell: that of pet_ewald_second, then u' [N, 3]
-struct EwWs3 {
-    EwWs2 w2;
-    float* up;
-};
-
-size_t ew_carve3(const pet_ewald_t* e, int64_t C, void* base, EwWs3& w3) {
-    Carver c(base);
-    c.off = ew_carve2(e, C, base, w3.w2);
-    w3.up = c.take<float>((size_t)std::max<int64_t>(e->n_atoms, 1) * 3);
-    return c.off;
+// ---- the Ewald sum's half of the interface (long_range.h). Every call rebuilds the phase tables (positions do not change inside
+// a sweep of the dual pass, but the tables are a fraction of one structure-factor launch). The first-order pair touches the
+// first-order workspace alone, which every workspace of this mode begins with.
+// out = A X
+int ew_potential(const LrCall& c, const float* X, float* out) {
+    EwWs w;
+    ew_carve(c.e, c.C, c.ws, w);
+    ProfScope ps("ewald_fwd", c.st, 0.0, 0.0);
+    PET_TRY(ew_tables(c.e, *c.g, c.pos, w, c.st));
+    return ew_apply(c.e, *c.g, c.pos, X, c.C, out, w, w.S1, w.loc.sum_q, c.st);
 }
 
-// a cell tangent of ew_second_run: the caller's position direction u [N, 3] (may be null) and u_c [S, 3, 3]; Ur is then u'
-struct EwCellDir {
-    const float *u, *ucell;
-};
+// gq = A G, gpos = grad_r Phi(r; G, Q) and, with gcell, dL/dcell: the column sums of Q and the k-vectors' parts (k_ew_zk) are
+// the cell gradient's alone
+int ew_backward(const LrCall& c, const float* Q, const float* G, float* gq, float* gpos, float* gcell) {
+    const pet_ewald_t* e = c.e;
+    const int C = c.C;
+    hipStream_t st = c.st;
+    EwWs w;
+    ew_carve(e, C, c.ws, w);
+    ProfScope ps("ewald_bwd", st, 0.0, 0.0);
+    PET_TRY(ew_tables(e, *c.g, c.pos, w, st));
+    // dL/dq = the operator applied to g: leaves S'(g) in S2 and the column sums of g in sum_g
+    PET_TRY(ew_apply(e, *c.g, c.pos, G, C, gq, w, w.S2, w.loc.sum_g, st));
+    const unsigned cy = (unsigned)cdiv(C, 256);
+    const size_t lds = ew_table_lds(e);
+    if (!e->ktiles.empty())
+        k_ew_sfac<false><<<dim3((unsigned)e->ktiles.size(), cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Q, C,
+                                                                                 w.S1, nullptr);
+    if (gcell) k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, Q, C, w.loc.sum_q);
+    if (!e->atiles_p.empty())
+        k_ew_force<true><<<(unsigned)e->atiles_p.size(), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, c.pos,
+                                                                         (float)(1.0 / e->cutoff), G, Q, w.S1, w.S2, C,
+                                                                         ew_vec_loads(C, Q, G), w.loc.F);
+    return ew_local_backward(e, *c.g, c.pos, Q, G, C, w.loc, gpos, gcell, st, [&] {
+        if (e->n_k > 0)
+            k_ew_zk<<<cdiv(e->n_k, 4), 256, 0, st>>>(e->d_sys, e->d_ksys, e->d_k, w.S1, w.S2, C, (int)e->n_k, e->sigma, w.loc.kpart);
+    });
+}
 
-// pet_ewald_second with selectable results: a null out_q / out_g / out_r is not formed and the launches that serve it alone
-// are skipped. With all three it is the launch list pet_ewald_second always had. Q may be null where only out_q is asked
+// The second-order operation with selectable results: a null out_q / out_g / out_r is not formed and the launches that serve it
+// alone are skipped. With all three it is the launch list pet_ewald_second always had. Q may be null where only out_q is asked
 // for (it is a function of (G, Ur) alone), G where only out_g is (a function of (Q, Uq, Ur)).
-// With `cell` (pet_ewald_second_cell; Ur = u' of k_ew_uprime, no out_r): k_ew_wdot folds the weights' tangent into the two weighted
-// structure factors and ew_local_cell takes the place of k_ew_edge_second; nothing else differs.
-int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                  const float* Ur, int C, float* out_q, float* out_g, float* out_r, const EwWs2& w2, hipStream_t st,
-                  const EwCellDir* cell = nullptr) {
+// With Ucell (pet_ewald_second_cell; no out_r): the position direction becomes u' = u - r U (k_ew_uprime), k_ew_wdot folds the
+// weights' tangent into the two weighted structure factors and ew_local_cell takes the place of k_ew_edge_second; nothing
+// else differs.
+int ew_second(const LrCall& c, const float* Q, const float* G, const float* Uq, const float* U, const float* Ucell, float* out_q,
+              float* out_g, float* out_r) {
+    const pet_ewald_t* e = c.e;
+    const Graph& g = *c.g;
+    const float* pos = c.pos;
+    const int C = c.C;
+    hipStream_t st = c.st;
+    EwWs2 w2;
+    ew_carve2(e, C, c.ws, w2, Ucell != nullptr);
     const EwWs& w = w2.w;
     const int64_t N = e->n_atoms;
     const unsigned cy = (unsigned)cdiv(C, 256), nk = (unsigned)e->ktiles.size(), np = (unsigned)e->atiles_p.size(),
                    nn = (unsigned)e->atiles_n.size();
     const size_t lds = ew_table_lds(e);
     const float inv_R = (float)(1.0 / e->cutoff);
+    const float* Ur = U;  // the direction of the position tangent: the caller's, or u' under a cell tangent
+    if (Ucell) {
+        k_ew_uprime<<<cdiv(N, 256), 256, 0, st>>>(pos, g.sys, e->d_sys, U, Ucell, (int)N, w2.up);
+        Ur = w2.up;
+    }
     // (the profiler's stage names tell the selections apart: all three results, the dual forward's, the two reverses')
-    ProfScope ps(cell ? (out_g && out_q ? "ewald_second_cell" : out_g ? "ewald_second_cell_g" : "ewald_second_cell_q")
+    ProfScope ps(Ucell ? (out_g && out_q ? "ewald_second_cell" : out_g ? "ewald_second_cell_g" : "ewald_second_cell_q")
                  : out_q && out_g && out_r ? "ewald_second" : out_g ? "ewald_second_g" : out_r ? "ewald_second_qr" : "ewald_second_q",
                  st, 0.0, 0.0);
     PET_TRY(ew_tables(e, g, pos, w, st));
@@ -503,8 +542,8 @@ int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const 
             }
             if (out_q || out_r)
                 k_ew_sfac<true><<<dim3(nk, cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, G, C, w2.Su2, Ur);
-            if (cell && out_g) k_ew_wdot<<<(unsigned)e->n_k, 256, 0, st>>>(e->d_sys, e->d_ksys, e->d_k, cell->ucell, w.S1, C, e->sigma, w2.Su1);
-            if (cell && out_q) k_ew_wdot<<<(unsigned)e->n_k, 256, 0, st>>>(e->d_sys, e->d_ksys, e->d_k, cell->ucell, w.S2, C, e->sigma, w2.Su2);
+            if (Ucell && out_g) k_ew_wdot<<<(unsigned)e->n_k, 256, 0, st>>>(e->d_sys, e->d_ksys, e->d_k, Ucell, w.S1, C, e->sigma, w2.Su1);
+            if (Ucell && out_q) k_ew_wdot<<<(unsigned)e->n_k, 256, 0, st>>>(e->d_sys, e->d_ksys, e->d_k, Ucell, w.S2, C, e->sigma, w2.Su2);
         }
         if (np) {
             if (out_g)
@@ -524,7 +563,7 @@ int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const 
                 k_ew_force2<false><<<nn, 256, 0, st>>>(e->d_atiles_n, e->d_sys, nullptr, nullptr, 1, pos, inv_R, G, Q, nullptr, nullptr,
                                                        nullptr, nullptr, Ur, C, ew_vec_loads(C, Q, G), w.loc.F);
         }
-        if (cell) PET_TRY(ew_local_cell(e, g, Q, G, cell->u, cell->ucell, C, w.loc, out_g, out_q, st));
+        if (Ucell) PET_TRY(ew_local_cell(e, g, Q, G, U, Ucell, C, w.loc, out_g, out_q, st));
         else
             k_ew_edge_second<<<(unsigned)N, 64, 0, st>>>(e->d_sys, g.sys, g.rowptr, g.nbr, g.geo, G, Q, Ur, w.loc.F, C, e->sigma,
                                                          e->cutoff, out_g, out_q, out_r);
@@ -533,23 +572,14 @@ int ew_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const 
     return PET_OK;
 }
 
-// pet_ewald_second_cell: u' = u - r U, then ew_second_run along (u_q, u') with the cell tangent's two additions
-int ew_second_cell_run(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                       const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, const EwWs3& w3, hipStream_t st) {
-    if (!Ucell) return ew_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, nullptr, w3.w2, st);
-    k_ew_uprime<<<cdiv(e->n_atoms, 256), 256, 0, st>>>(pos, g.sys, e->d_sys, Ur, Ucell, (int)e->n_atoms, w3.up);
-    const EwCellDir cell{Ur, Ucell};
-    return ew_second_run(e, g, pos, Q, G, Uq, w3.up, C, out_q, out_g, nullptr, w3.w2, st, &cell);
+// the context of an extern "C" entry point's own call: its d_workspace is the operator's
+LrCall ew_entry_call(const pet_ewald_t* e, const pet_graph_t* pg, const float* pos, int C, void* ws, void* stream) {
+    return LrCall{e, &pg->g, pos, C, ws, 0, (hipStream_t)stream};
 }
 
 }  // namespace
 
-// ---- what the long-range stage of the dual training pass (gen_train.hip) calls: the operator on device rows of a planned
-// handle, on ONE workspace of lr_ewald_workspace_bytes (that of pet_ewald_second / pet_p3m_second). The caller has checked the
-// handle against the graph (lr_check); every call rebuilds the phase tables (positions do not change inside a sweep, but
-// the tables are a fraction of one structure-factor launch). A P3M-mode handle that has a transform hook goes to the mesh
-// operator (p3m.hip: p3m_lr_*), whose workspace begins at the same address; ws_offset (the bytes of ws into the entry point's
-// d_workspace) is what that one's transform hook needs and the Ewald sum ignores.
+// ---- the interface (long_range.h): the handle's mode is decided here and nowhere else --------------------------------------------
 int lr_check(const pet_ewald_t* e, const pet_graph_t* pg, int C, const char* who) {
     PET_REQUIRE(e && pg, PET_ERR_ARGUMENT, "null argument");
     PET_REQUIRE(e->p3m_nodes == 0 || e->p3m_transform, PET_ERR_UNSUPPORTED,
@@ -558,69 +588,32 @@ int lr_check(const pet_ewald_t* e, const pet_graph_t* pg, int C, const char* who
     return ew_check_graph(e, pg, C);
 }
 
-int64_t lr_ewald_workspace_bytes(const pet_ewald_t* e, int C) {
-    if (e->p3m_nodes) return p3m_lr_workspace_bytes(e, C);
+int64_t lr_workspace_bytes(const pet_ewald_t* e, int C, bool cell) {
+    if (e->p3m_nodes) return p3m_workspace_bytes(e, C, cell);
     EwWs2 w;
-    return (int64_t)ew_carve2(e, C, nullptr, w);
+    return (int64_t)ew_carve2(e, C, nullptr, w, cell);
 }
 
-// out = A X
-int lr_potential(const pet_ewald_t* e, const Graph& g, const float* pos, const float* X, int C, float* out, void* ws,
-                 hipStream_t st, int64_t ws_offset) {
-    if (e->p3m_nodes) return p3m_lr_potential(e, g, pos, X, C, out, ws, st, ws_offset);
-    EwWs2 w2;
-    ew_carve2(e, C, ws, w2);
-    ProfScope ps("ewald_fwd", st, 0.0, 0.0);
-    PET_TRY(ew_tables(e, g, pos, w2.w, st));
-    return ew_apply(e, g, pos, X, C, out, w2.w, w2.w.S1, w2.w.loc.sum_q, st);
+int lr_potential(const LrCall& c, const float* X, float* out) {
+    if (c.e->p3m_nodes) return p3m_potential(c, X, out);
+    return ew_potential(c, X, out);
 }
 
-// gq = A G and gpos = grad_r Phi(r; G, Q): pet_ewald_backward without the cell gradient
-int lr_backward(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, int C, float* gq,
-                float* gpos, void* ws, hipStream_t st, int64_t ws_offset) {
-    if (e->p3m_nodes) return p3m_lr_backward(e, g, pos, Q, G, C, gq, gpos, ws, st, ws_offset);
-    EwWs2 w2;
-    ew_carve2(e, C, ws, w2);
-    const EwWs& w = w2.w;
-    ProfScope ps("ewald_bwd", st, 0.0, 0.0);
-    PET_TRY(ew_tables(e, g, pos, w, st));
-    PET_TRY(ew_apply(e, g, pos, G, C, gq, w, w.S2, w.loc.sum_g, st));
-    const unsigned cy = (unsigned)cdiv(C, 256);
-    const size_t lds = ew_table_lds(e);
-    if (!e->ktiles.empty())
-        k_ew_sfac<false><<<dim3((unsigned)e->ktiles.size(), cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm, Q, C,
-                                                                                 w.S1, nullptr);
-    if (!e->atiles_p.empty())
-        k_ew_force<true><<<(unsigned)e->atiles_p.size(), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, pos,
-                                                                         (float)(1.0 / e->cutoff), G, Q, w.S1, w.S2, C,
-                                                                         ew_vec_loads(C, Q, G), w.loc.F);
-    return ew_local_backward(e, g, pos, Q, G, C, w.loc, gpos, nullptr, st, [] {});
+int lr_backward(const LrCall& c, const float* Q, const float* G, float* gq, float* gpos, float* gcell) {
+    if (!c.e->p3m_nodes) return ew_backward(c, Q, G, gq, gpos, gcell);
+    PET_REQUIRE(!gcell, PET_ERR_UNSUPPORTED,
+                "dL/dcell of the mesh operator inside an entry point is not built: it needs the unfiltered spectra of q and of "
+                "dL/dV, which the staged entry point pet_p3m_backward is given");
+    return p3m_backward(c, Q, G, gq, gpos);
 }
 
-// pet_ewald_second's results by choice (ew_second_run): null results are skipped
-int lr_second(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-              const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st, int64_t ws_offset) {
-    if (e->p3m_nodes) return p3m_lr_second(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, out_r, ws, st, ws_offset);
-    EwWs2 w2;
-    ew_carve2(e, C, ws, w2);
-    return ew_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, out_r, w2, st);
-}
-
-// lr_ewald_workspace_bytes / lr_second with a cell tangent Ucell [S, 3, 3] (pet_ewald_second_cell / pet_p3m_second_cell): the two
-// results that feed parameter gradients. Ur or Ucell may be null.
-int64_t lr_ewald_cell_workspace_bytes(const pet_ewald_t* e, int C) {
-    if (e->p3m_nodes) return p3m_lr_cell_workspace_bytes(e, C);
-    EwWs3 w;
-    return (int64_t)ew_carve3(e, C, nullptr, w);
-}
-
-int lr_second_cell(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                   const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, void* ws, hipStream_t st,
-                   int64_t ws_offset) {
-    if (e->p3m_nodes) return p3m_lr_second_cell(e, g, pos, Q, G, Uq, Ur, Ucell, C, out_q, out_g, ws, st, ws_offset);
-    EwWs3 w3;
-    ew_carve3(e, C, ws, w3);
-    return ew_second_cell_run(e, g, pos, Q, G, Uq, Ur, Ucell, C, out_q, out_g, w3, st);
+int lr_second(const LrCall& c, const float* Q, const float* G, const float* Uq, const float* Ur, const float* Ucell, float* out_q,
+              float* out_g, float* out_r) {
+    PET_REQUIRE(!(Ucell && out_r), PET_ERR_UNSUPPORTED,
+                "the position result of the second-order operation under a cell tangent (mixed position / cell second "
+                "derivatives) is not built");
+    if (c.e->p3m_nodes) return p3m_second(c, Q, G, Uq, Ur, Ucell, out_q, out_g, out_r);
+    return ew_second(c, Q, G, Uq, Ur, Ucell, out_q, out_g, out_r);
 }
 
 }  // namespace pet
@@ -727,98 +720,54 @@ int pet_ewald_potential(const pet_ewald_t* e, const pet_graph_t* pg, const float
     if (int rc = ew_check(e, pg, C, d_workspace, workspace_bytes)) return rc;
     if (e->n_atoms == 0) return PET_OK;
     PET_REQUIRE(d_positions && d_charges && d_potential, PET_ERR_ARGUMENT, "null argument");
-    hipStream_t st = (hipStream_t)stream;
-    EwWs w;
-    ew_carve(e, C, d_workspace, w);
-    ProfScope ps("ewald_fwd", st, 0.0, 0.0);
-    PET_TRY(ew_tables(e, pg->g, d_positions, w, st));
-    return ew_apply(e, pg->g, d_positions, d_charges, C, d_potential, w, w.S1, w.loc.sum_q, st);
+    return ew_potential(ew_entry_call(e, pg, d_positions, C, d_workspace, stream), d_charges, d_potential);
 }
 
 int pet_ewald_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
                        const float* d_grad_potential, int32_t C, float* d_grad_charges, float* d_grad_positions,
                        float* d_grad_cells, void* d_workspace, int64_t workspace_bytes, void* stream) {
     if (int rc = ew_check(e, pg, C, d_workspace, workspace_bytes)) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    const Graph& g = pg->g;
-    if (e->n_atoms == 0) return ew_backward_empty(e, d_grad_cells, st);
+    if (e->n_atoms == 0) return ew_backward_empty(e, d_grad_cells, (hipStream_t)stream);
     PET_REQUIRE(d_positions && d_charges && d_grad_potential && d_grad_charges && d_grad_positions, PET_ERR_ARGUMENT,
                 "null argument");
-    EwWs w;
-    ew_carve(e, C, d_workspace, w);
-    ProfScope ps("ewald_bwd", st, 0.0, 0.0);
-    PET_TRY(ew_tables(e, g, d_positions, w, st));
-    // dL/dq = the operator applied to g: leaves S'(g) in S2 and the column sums of g in sum_g
-    PET_TRY(ew_apply(e, g, d_positions, d_grad_potential, C, d_grad_charges, w, w.S2, w.loc.sum_g, st));
-    const unsigned cy = (unsigned)cdiv(C, 256);
-    const size_t lds = ew_table_lds(e);
-    if (!e->ktiles.empty())
-        k_ew_sfac<false><<<dim3((unsigned)e->ktiles.size(), cy), 256, lds, st>>>(e->d_ktiles, e->d_sys, e->d_k, w.tab, e->nm,
-                                                                                 d_charges, C, w.S1, nullptr);
-    k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_charges, C, w.loc.sum_q);
-    if (!e->atiles_p.empty())
-        k_ew_force<true><<<(unsigned)e->atiles_p.size(), 256, lds, st>>>(e->d_atiles_p, e->d_sys, e->d_k, w.tab, e->nm, d_positions,
-                                                                         (float)(1.0 / e->cutoff), d_grad_potential, d_charges, w.S1,
-                                                                         w.S2, C, ew_vec_loads(C, d_charges, d_grad_potential), w.loc.F);
-    return ew_local_backward(e, g, d_positions, d_charges, d_grad_potential, C, w.loc, d_grad_positions, d_grad_cells, st, [&] {
-        if (e->n_k > 0)
-            k_ew_zk<<<cdiv(e->n_k, 4), 256, 0, st>>>(e->d_sys, e->d_ksys, e->d_k, w.S1, w.S2, C, (int)e->n_k, e->sigma, w.loc.kpart);
-    });
+    return ew_backward(ew_entry_call(e, pg, d_positions, C, d_workspace, stream), d_charges, d_grad_potential, d_grad_charges,
+                       d_grad_positions, d_grad_cells);
 }
 
 int64_t pet_ewald_second_workspace_bytes(const pet_ewald_t* e, int64_t n_channels) {
     if (!e || !e->planned || e->p3m_nodes || n_channels < 1) return -1;
-    EwWs2 w;
-    return (int64_t)ew_carve2(e, n_channels, nullptr, w);
+    return lr_workspace_bytes(e, (int)n_channels, false);
 }
 
 int pet_ewald_second(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
                      const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions, int32_t C,
                      float* d_out_charges, float* d_out_grad_potential, float* d_out_positions, void* d_workspace,
                      int64_t workspace_bytes, void* stream) {
-    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
-    PET_REQUIRE(e->p3m_nodes == 0, PET_ERR_ARGUMENT,
-                "pet_ewald_second on a P3M-mode handle (pet_ewald_set_p3m): the mesh operator's second derivatives are "
-                "pet_p3m_second's");
-    if (int rc = ew_check(e, pg, C, d_workspace, workspace_bytes)) return rc;
-    PET_REQUIRE(d_u_charges || d_u_positions, PET_ERR_ARGUMENT, "d_u_charges and d_u_positions are both NULL");
-    if (e->n_atoms == 0) return PET_OK;
-    EwWs2 w2;
-    PET_REQUIRE(d_workspace && workspace_bytes >= (int64_t)ew_carve2(e, C, nullptr, w2), PET_ERR_ARGUMENT,
-                "Ewald workspace too small (pet_ewald_second_workspace_bytes)");
-    PET_REQUIRE(d_positions && d_charges && d_grad_potential && d_out_charges && d_out_grad_potential && d_out_positions,
-                PET_ERR_ARGUMENT, "null argument");
-    ew_carve2(e, C, d_workspace, w2);
-    return ew_second_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, C, d_out_charges,
-                         d_out_grad_potential, d_out_positions, w2, (hipStream_t)stream);
+    bool run;
+    PET_TRY(ew_second_check(e, pg, C, "pet_ewald_second", false, false, d_u_charges || d_u_positions, d_workspace, workspace_bytes,
+                            d_positions && d_charges && d_grad_potential,
+                            d_out_charges && d_out_grad_potential && d_out_positions, "null argument", &run));
+    if (!run) return PET_OK;
+    return ew_second(ew_entry_call(e, pg, d_positions, C, d_workspace, stream), d_charges, d_grad_potential, d_u_charges,
+                     d_u_positions, nullptr, d_out_charges, d_out_grad_potential, d_out_positions);
 }
 
 int64_t pet_ewald_second_cell_workspace_bytes(const pet_ewald_t* e, int64_t n_channels) {
     if (!e || !e->planned || e->p3m_nodes || n_channels < 1) return -1;
-    EwWs3 w;
-    return (int64_t)ew_carve3(e, n_channels, nullptr, w);
+    return lr_workspace_bytes(e, (int)n_channels, true);
 }
 
 int pet_ewald_second_cell(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
                           const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions,
                           const float* d_u_cells, int32_t C, float* d_out_charges, float* d_out_grad_potential, void* d_workspace,
                           int64_t workspace_bytes, void* stream) {
-    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
-    PET_REQUIRE(e->p3m_nodes == 0, PET_ERR_ARGUMENT,
-                "pet_ewald_second_cell on a P3M-mode handle (pet_ewald_set_p3m): the mesh operator's cell tangents are "
-                "pet_p3m_second_cell's");
-    if (int rc = ew_check(e, pg, C, d_workspace, workspace_bytes)) return rc;
-    PET_REQUIRE(d_u_charges || d_u_positions || d_u_cells, PET_ERR_ARGUMENT,
-                "d_u_charges, d_u_positions and d_u_cells are all NULL");
-    if (e->n_atoms == 0) return PET_OK;
-    EwWs3 w3;
-    PET_REQUIRE(d_workspace && workspace_bytes >= (int64_t)ew_carve3(e, C, nullptr, w3), PET_ERR_ARGUMENT,
-                "Ewald workspace too small (pet_ewald_second_cell_workspace_bytes)");
-    PET_REQUIRE(d_positions && d_charges && d_grad_potential, PET_ERR_ARGUMENT, "null argument");
-    PET_REQUIRE(d_out_charges || d_out_grad_potential, PET_ERR_ARGUMENT, "both results are NULL");
-    ew_carve3(e, C, d_workspace, w3);
-    return ew_second_cell_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, d_u_cells, C,
-                              d_out_charges, d_out_grad_potential, w3, (hipStream_t)stream);
+    bool run;
+    PET_TRY(ew_second_check(e, pg, C, "pet_ewald_second_cell", false, true, d_u_charges || d_u_positions || d_u_cells, d_workspace,
+                            workspace_bytes, d_positions && d_charges && d_grad_potential, d_out_charges || d_out_grad_potential,
+                            "both results are NULL", &run));
+    if (!run) return PET_OK;
+    return ew_second(ew_entry_call(e, pg, d_positions, C, d_workspace, stream), d_charges, d_grad_potential, d_u_charges,
+                     d_u_positions, d_u_cells, d_out_charges, d_out_grad_potential, nullptr);
 }
 
 }  // extern "C"

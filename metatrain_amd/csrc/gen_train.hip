@@ -17,6 +17,7 @@
 
 #include "gen_walk.h"
 #include "cutoff.h"
+#include "long_range.h"
 
 namespace pet {
 
@@ -945,7 +946,8 @@ struct TOps {
 const char* const LR_KEYS[3] = {"long_range_featurizer.charges_map", "long_range_featurizer.out_projection.0",
                                 "long_range_featurizer.out_projection.2"};
 struct LrWs {
-    void* ew;                             // the operator's workspace (lr_ewald_workspace_bytes at d_node channels)
+    void* ew;                             // the operator's workspace (lr_workspace_bytes at d_node channels)
+    LrCall op;                            // the operator's call context on it (gen_train2 fills it once per stage)
     D2 x, q, V, a, s, y, dy, dV, dq, dx;  // values and adjoints [N, d_node]
     float *dqu, *r1, *r2;                 // (D_u A) lambda_V [N, d_node]; the operator's two position adjoints [N, 3]
     std::vector<D2> ml;
@@ -955,7 +957,7 @@ static void lr_carve(const Model& m, const pet_ewald_t* e, int64_t N, void* base
     const GD d = dims_of(m);
     Carver c(base);
     w.ew = base;
-    c.off = ((size_t)(cell ? lr_ewald_cell_workspace_bytes(e, d.DN) : lr_ewald_workspace_bytes(e, d.DN)) + 255) & ~size_t(255);
+    c.off = ((size_t)lr_workspace_bytes(e, d.DN, cell) + 255) & ~size_t(255);
     const size_t n = (size_t)(N > 0 ? N : 1) * d.DN;
     for (D2* v : {&w.x, &w.q, &w.V, &w.a, &w.s, &w.y, &w.dy, &w.dV, &w.dq, &w.dx}) take(c, n, *v);
     w.dqu = c.take<float>(n);
@@ -997,10 +999,8 @@ static int lr_forward(TOps& t, const LrStage& lr, const Lin* L, const std::vecto
     k_lr_layer_sum<<<g1(n), 256, 0, t.st>>>(lr_rows(h, false), sx, w.x.p, n);
     k_lr_layer_sum<<<g1(n), 256, 0, t.st>>>(lr_rows(h, true), sx, w.x.t, n);
     t.linf(w.x, DN, L[0], w.q, DN, N);
-    PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.q.p, DN, w.V.p, w.ew, t.st, lr.ws_offset));
-    if (u && lr.ucell)   // V' = A q' + (D A) q along (u, ucell)
-        PET_TRY(lr_second_cell(lr.e, t.g, lr.pos, w.q.p, nullptr, w.q.t, u, lr.ucell, DN, nullptr, w.V.t, w.ew, t.st, lr.ws_offset));
-    else if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, nullptr, w.q.t, u, DN, nullptr, w.V.t, nullptr, w.ew, t.st, lr.ws_offset));
+    PET_TRY(lr_potential(w.op, w.q.p, w.V.p));
+    if (u) PET_TRY(lr_second(w.op, w.q.p, nullptr, w.q.t, u, lr.ucell, nullptr, w.V.t, nullptr));  // V' = A q' + (D A) q along (u, ucell)
     else t.o.zero(w.V.t, n);
     t.linf(w.V, DN, L[1], w.a, DN, N);
     t.silu(w.a, w.s, n);
@@ -1027,17 +1027,15 @@ static int lr_reverse(TOps& t, const LrStage& lr, const Lin* L, const float* u, 
     t.linb(w.s, DN, L[1], w.dV, DN, N);     // (nu_V, lambda_V)
     // lambda_q' = A lambda_V, nu_q = A nu_V + (D_u A) lambda_V (A and D_u A are symmetric)
     if (t.hv) {
-        PET_TRY(lr_backward(lr.e, t.g, lr.pos, w.q.p, w.dV.p, DN, w.dq.p, w.r1, w.ew, t.st, lr.ws_offset));
-        PET_TRY(lr_second(lr.e, t.g, lr.pos, w.q.p, w.dV.t, w.q.t, u, DN, w.dqu, nullptr, w.r2, w.ew, t.st, lr.ws_offset));
+        PET_TRY(lr_backward(w.op, w.q.p, w.dV.p, w.dq.p, w.r1));
+        PET_TRY(lr_second(w.op, w.q.p, w.dV.t, w.q.t, u, nullptr, w.dqu, nullptr, w.r2));
         t.o.axpby(1.f, w.r1, 3, 1.f, w.r2, 3, nullptr, lr.rbar, 3, false, N, 3);
     } else {
-        PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.p, DN, w.dq.p, w.ew, t.st, lr.ws_offset));
-        if (u && lr.ucell)
-            PET_TRY(lr_second_cell(lr.e, t.g, lr.pos, nullptr, w.dV.t, nullptr, u, lr.ucell, DN, w.dqu, nullptr, w.ew, t.st, lr.ws_offset));
-        else if (u) PET_TRY(lr_second(lr.e, t.g, lr.pos, nullptr, w.dV.t, nullptr, u, DN, w.dqu, nullptr, nullptr, w.ew, t.st, lr.ws_offset));
+        PET_TRY(lr_potential(w.op, w.dV.p, w.dq.p));
+        if (u) PET_TRY(lr_second(w.op, nullptr, w.dV.t, nullptr, u, lr.ucell, w.dqu, nullptr, nullptr));
     }
     if (u) {
-        PET_TRY(lr_potential(lr.e, t.g, lr.pos, w.dV.t, DN, w.dq.t, w.ew, t.st, lr.ws_offset));
+        PET_TRY(lr_potential(w.op, w.dV.t, w.dq.t));
         k_lr_add<<<g1(n), 256, 0, t.st>>>(w.dq.p, w.dqu, n);
     } else
         t.o.zero(w.dq.t, n);
@@ -1154,6 +1152,7 @@ int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, con
         if (int rc = lr_linears(m, DN, lrl)) return rc;
         lr_carve(m, lr->e, N, lr->ws, lw, lr->ucell != nullptr);
         PET_REQUIRE((int64_t)lw.bytes <= lr->ws_bytes, PET_ERR_ARGUMENT, "long-range stage workspace too small");
+        lw.op = LrCall{lr->e, &g, lr->pos, DN, lw.ew, lr->ws_offset, st};
         std::vector<D2> hl(NR);
         for (int l = 0; l < NR; l++) hl[l] = (res ? w.gnn[l] : w.gnn.back()).Hout;
         if (int rc = lr_forward(t, *lr, lrl, hl, u, lw)) return rc;
@@ -1293,57 +1292,44 @@ int gen_hvp(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const fl
 // ---------------------------------------------------------------------------------------------
 static size_t align256(size_t n) { return (n + 255) & ~size_t(255); }
 
-int64_t lr_stage_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, bool cell) {
+// The one layout of the three forms' workspace, for the size query and the runs alike: [pass | block | stage].
+//   pass   the dual pass' workspace (gen_train_workspace_bytes; LR_HVP: with the Hessian-vector taps behind it)
+//   block  one [N, 3] block: LR_TRAIN_CELL the zero direction of a call that has ucell alone (the backbone's geometry tangent and
+//          the operator read one direction, not a null), LR_HVP rbar; LR_TRAIN has none
+//   stage  the long-range stage's (lr_carve), LR_TRAIN_CELL with the operator's cell workspace in front
+struct LrLayout {
+    size_t train;               // gen_train_workspace_bytes, unaligned (what hvp_carve continues from)
+    size_t block, stage, total; // byte offsets of the block and of the stage; the whole
+};
+static LrLayout lr_layout(const Model& m, const pet_ewald_t* e, int64_t N, int64_t E, LrSweep form) {
+    LrLayout l;
+    l.train = (size_t)gen_train_workspace_bytes(m, N, E);
+    l.block = align256(form == LR_HVP ? (size_t)gen_hvp_workspace_bytes(m, N, E) : l.train);
+    l.stage = l.block + (form == LR_TRAIN ? 0 : align256((size_t)(N > 0 ? N : 1) * 3 * sizeof(float)));
     LrWs w;
-    lr_carve(m, e, N, nullptr, w, cell);
-    return (int64_t)w.bytes;
+    lr_carve(m, e, N, nullptr, w, form == LR_TRAIN_CELL);
+    l.total = l.stage + w.bytes;
+    return l;
 }
 
-int64_t gen_train2_lr_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, int64_t E) {
-    return (int64_t)align256((size_t)gen_train_workspace_bytes(m, N, E)) + lr_stage_workspace_bytes(m, e, N);
+int64_t lr_sweep_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, int64_t E, LrSweep form) {
+    return (int64_t)lr_layout(m, e, N, E, form).total;
 }
 
 int gen_train2_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
-                  const float* lA, const float* nA, const float* u, float* tangent_atomic, hipStream_t st) {
+                  const float* lA, const float* nA, const float* u, const float* ucell, float* tangent_atomic, hipStream_t st) {
     const int64_t N = g.n_nodes, E = g.n_edges;
-    const size_t train_bytes = align256((size_t)gen_train_workspace_bytes(m, N, E));
-    const int64_t stage_bytes = lr_stage_workspace_bytes(m, e, N);
-    PET_REQUIRE((int64_t)train_bytes + stage_bytes <= ws_bytes, PET_ERR_ARGUMENT,
-                "workspace too small (pet_train2_long_range_workspace_bytes)");
-    LrStage lr{e, pos, static_cast<char*>(ws) + train_bytes, stage_bytes, nullptr, (int64_t)train_bytes};
-    return gen_train2(m, g, ws, (int64_t)train_bytes, lA, nA, u, nullptr, tangent_atomic, st, nullptr, nullptr, 0, nullptr, &lr);
-}
-
-// With a cell tangent (pet_backward_train2_long_range_cell): the dual pass' workspace, a zero direction [N, 3] for the call
-// that has ucell alone (the backbone's geometry tangent and the operator read one direction, not a null), the stage's with
-// the operator's cell workspace. Without ucell it is gen_train2_lr, launch for launch.
-int64_t gen_train2_lr_cell_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, int64_t E) {
-    return (int64_t)align256((size_t)gen_train_workspace_bytes(m, N, E)) + (int64_t)align256((size_t)(N > 0 ? N : 1) * 3 * sizeof(float)) +
-           lr_stage_workspace_bytes(m, e, N, true);
-}
-
-int gen_train2_lr_cell(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
-                       const float* lA, const float* nA, const float* u, const float* ucell, float* tangent_atomic,
-                       hipStream_t st) {
-    if (!ucell) return gen_train2_lr(m, g, e, pos, ws, ws_bytes, lA, nA, u, tangent_atomic, st);
-    const int64_t N = g.n_nodes, E = g.n_edges;
-    const size_t train_bytes = align256((size_t)gen_train_workspace_bytes(m, N, E));
-    const size_t zero_bytes = align256((size_t)(N > 0 ? N : 1) * 3 * sizeof(float));
-    const int64_t stage_bytes = lr_stage_workspace_bytes(m, e, N, true);
-    PET_REQUIRE((int64_t)(train_bytes + zero_bytes) + stage_bytes <= ws_bytes, PET_ERR_ARGUMENT,
-                "workspace too small (pet_train2_long_range_cell_workspace_bytes)");
-    if (!u) {
-        float* zeros = reinterpret_cast<float*>(static_cast<char*>(ws) + train_bytes);
+    const LrLayout l = lr_layout(m, e, N, E, ucell ? LR_TRAIN_CELL : LR_TRAIN);
+    PET_REQUIRE((int64_t)l.total <= ws_bytes, PET_ERR_ARGUMENT,
+                std::string("workspace too small (pet_train2_long_range_") + (ucell ? "cell_" : "") + "workspace_bytes)");
+    char* base = static_cast<char*>(ws);
+    if (ucell && !u) {
+        float* zeros = reinterpret_cast<float*>(base + l.block);
         PET_HIP_CHECK(hipMemsetAsync(zeros, 0, (size_t)(N > 0 ? N : 1) * 3 * sizeof(float), st));
         u = zeros;
     }
-    LrStage lr{e, pos, static_cast<char*>(ws) + train_bytes + zero_bytes, stage_bytes, nullptr, (int64_t)(train_bytes + zero_bytes), ucell};
-    return gen_train2(m, g, ws, (int64_t)train_bytes, lA, nA, u, ucell, tangent_atomic, st, nullptr, nullptr, 0, nullptr, &lr);
-}
-
-int64_t gen_hvp_lr_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t N, int64_t E) {
-    return (int64_t)align256((size_t)gen_hvp_workspace_bytes(m, N, E)) + (int64_t)align256((size_t)(N > 0 ? N : 1) * 3 * sizeof(float)) +
-           lr_stage_workspace_bytes(m, e, N);
+    LrStage lr{e, pos, base + l.stage, (int64_t)(l.total - l.stage), nullptr, (int64_t)l.stage, ucell};
+    return gen_train2(m, g, ws, (int64_t)l.block, lA, nA, u, ucell, tangent_atomic, st, nullptr, nullptr, 0, nullptr, &lr);
 }
 
 // hvp_pos [N, 3] = grad_R of sum_i lambda_i e'_i of the long-range model: the backbone's share through the scatter of the
@@ -1354,19 +1340,16 @@ int gen_hvp_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const float
     if (N == 0) return PET_OK;
     HvpTaps h;
     float* ones;
-    const size_t train_bytes = (size_t)gen_train_workspace_bytes(m, N, E);
-    const size_t hvp_bytes = align256(hvp_carve(m, N, E, ws, train_bytes, h, &ones));
-    const size_t rbar_bytes = align256((size_t)N * 3 * sizeof(float));
-    const int64_t stage_bytes = lr_stage_workspace_bytes(m, e, N);
-    PET_REQUIRE((int64_t)(hvp_bytes + rbar_bytes) + stage_bytes <= ws_bytes, PET_ERR_ARGUMENT,
-                "workspace too small (pet_hvp_long_range_workspace_bytes)");
-    float* rbar = reinterpret_cast<float*>(static_cast<char*>(ws) + hvp_bytes);
-    LrStage lr{e, pos, static_cast<char*>(ws) + hvp_bytes + rbar_bytes, stage_bytes, rbar, (int64_t)(hvp_bytes + rbar_bytes)};
+    const LrLayout l = lr_layout(m, e, N, E, LR_HVP);
+    PET_REQUIRE((int64_t)l.total <= ws_bytes, PET_ERR_ARGUMENT, "workspace too small (pet_hvp_long_range_workspace_bytes)");
+    hvp_carve(m, N, E, ws, l.train, h, &ones);
+    float* rbar = reinterpret_cast<float*>(static_cast<char*>(ws) + l.block);
+    LrStage lr{e, pos, static_cast<char*>(ws) + l.stage, (int64_t)(l.total - l.stage), rbar, (int64_t)l.stage};
     if (!lA) {
         k_hvp_fill<<<g1(N), 256, 0, st>>>(ones, 1.f, N);
         lA = ones;
     }
-    int rc = gen_train2(m, g, ws, (int64_t)train_bytes, lA, nullptr, u, nullptr, tangent_atomic, st, nullptr, nullptr, 0, &h, &lr);
+    int rc = gen_train2(m, g, ws, (int64_t)l.train, lA, nullptr, u, nullptr, tangent_atomic, st, nullptr, nullptr, 0, &h, &lr);
     if (rc) return rc;
     if (E > 0) {
         // (h.ngeo is spent: it serves as the scatter's d/d(edge vector) scratch)

@@ -1,14 +1,21 @@
-// What the two evaluations of the long-range operator share: ewald.hip (the reciprocal-space sum over a k list) and p3m.hip
-// (the same sum on a mesh) include this header and nothing of each other. Here are the handle (pet_ewald), its per-system
-// record, the one cell inverse, what both ask of a graph, and the LOCAL terms (self, background, exclusion, the open all-pairs
-// sum) with their adjoints: kernels and the two host functions that launch them. The operator's convention constants
-// (include/pet_hip.h) are EW_PREFACTOR and the three coefficients of ew_local_forward; a mode adds only
-// its weight 2 G(k) / Omega (ewald.hip: ew_plan_klist) or G^(n) / Omega (p3m.hip: p3m_influence_point).
-// k_ew_pairs<true>, k_ew_force2, k_ew_edge_second and ew_open_kernel_dd serve both modes' second derivatives (ewald.hip:
-// pet_ewald_second; p3m.hip: pet_p3m_second, which has no k tiles and instantiates k_ew_force2<false> alone).
-// k_ew_uprime, k_ew_edge_cell and ew_local_cell serve both modes' cell tangents (pet_ewald_second_cell, pet_p3m_second_cell).
-// Kernels and functions have internal linkage: each translation unit is compiled on its own (build.py: NO_RDC) with its own
-// copy of what it launches. Only the two record types and the P3M plan's entry points have names that cross objects.
+// The long-range operator (q [N, C] -> V [N, C], its adjoint and its second-order operation) behind ONE internal interface, and
+// what its two evaluations share: ewald.hip (the reciprocal-space sum over a k list) and p3m.hip (the same sum on a mesh).
+//
+// THE INTERFACE is the first part of this header, which gen_train.hip and abi.hip include as it is: a
+// call context (LrCall) and four functions that decide the handle's mode in one place (ewald.hip). The extern "C" entry
+// points of a mode run the functions that the interface dispatches to, so every launch list is stated once.
+//
+// THE SHARED PART, for the two translation units that define LONG_RANGE_SHARED_PART before they include this header (they
+// include nothing of each other): the handle (pet_ewald), its per-system record, the one cell inverse, what both ask of a
+// graph and of a second-order call, and the LOCAL terms (self, background, exclusion, the open all-pairs sum) with their
+// adjoints: kernels and the host functions that launch them. The operator's convention constants (include/pet_hip.h, DESIGN.md
+// section 18) are EW_PREFACTOR and the three coefficients of ew_local_forward; a mode adds only its weight 2 G(k) / Omega
+// (ewald.hip: ew_plan_klist) or G^(n) / Omega (p3m.hip: p3m_influence_point).
+// k_ew_pairs<true>, k_ew_force2, k_ew_edge_second and ew_open_kernel_dd serve both modes' second derivatives (p3m.hip has no k
+// tiles and instantiates k_ew_force2<false> alone); k_ew_uprime, k_ew_edge_cell and ew_local_cell both modes' cell tangents.
+// Kernels and functions of the shared part have internal linkage: each translation unit is compiled on its own (build.py:
+// NO_RDC) with its own copy of what it launches. Only the two record types, the P3M plan's entry points and a mode's half of
+// the interface (p3m_*) have names that cross objects.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -16,6 +23,41 @@
 
 #include "common.h"
 #include "model.h"
+
+struct pet_ewald;
+
+namespace pet {
+
+// One call of the operator from inside a running entry point: a planned handle that the caller has checked against the graph
+// (lr_check, or a mode's own entry check), at C channels, on a workspace of lr_workspace_bytes(e, C, cell) that lies ws_offset
+// bytes into that entry point's d_workspace (what a P3M handle's transform hook counts its offsets from; the Ewald sum
+// ignores it). A call without a cell tangent runs on either size: the cell workspace begins with the other.
+struct LrCall {
+    const pet_ewald* e;
+    const Graph* g;
+    const float* pos;
+    int C;
+    void* ws;
+    int64_t ws_offset;
+    hipStream_t st;
+};
+// Ewald mode, or P3M mode with a transform hook (pet_p3m_set_transform); then what both modes ask of the graph
+int lr_check(const pet_ewald* e, const pet_graph_t* pg, int C, const char* who);
+int64_t lr_workspace_bytes(const pet_ewald* e, int C, bool cell);
+// out = A X
+int lr_potential(const LrCall& c, const float* X, float* out);
+// gq = A G and gpos = grad_r Phi(r; G, Q); with gcell also dL/dcell [S, 3, 3] (Ewald mode: the mesh operator's needs the two
+// unfiltered spectra that its staged entry point pet_p3m_backward is given)
+int lr_backward(const LrCall& c, const float* Q, const float* G, float* gq, float* gpos, float* gcell = nullptr);
+// The second-order operation along (Uq [N, C], Ur [N, 3], Ucell [S, 3, 3]; each may be null, not all): a null result is not
+// formed and the launches that serve it alone are skipped; Q may be null where only out_q is asked for, G where only out_g is.
+// out_r together with Ucell is not built (mixed position / cell second derivatives).
+int lr_second(const LrCall& c, const float* Q, const float* G, const float* Uq, const float* Ur, const float* Ucell, float* out_q,
+              float* out_g, float* out_r);
+
+}  // namespace pet
+
+#ifdef LONG_RANGE_SHARED_PART
 
 namespace pet {
 
@@ -598,7 +640,7 @@ __global__ __launch_bounds__(256) void k_ew_force2(const int2* __restrict__ tile
 // p = (i -> j, S) with e = u_j - u_i, n = D / d:  out_g[i] -= P w'(d) (n.e) q_j,  out_q[i] -= P w'(d) (n.e) g_j  and
 // out_r[i] += P (B_p + B'_p) M_w e,  M_w = w'' n n^T + (w'/d) (I - n n^T). Lanes take one edge each of a chunk of 64 for w', w''
 // and M_w e, then all lanes walk the chunk's edges for the channel sums. Adds F2 (k_ew_force2) into out_r for every atom.
-// A null result is not formed (ew_second_run): without out_r neither F2 nor the channel products are read, without out_g
+// A null result is not formed (ew_second, p3m_second): without out_r neither F2 nor the channel products are read, without out_g
 // (out_q) Q (G) is not read in the channel sums; each sum is its own accumulator, so the others keep their bits.
 __global__ __launch_bounds__(64) void k_ew_edge_second(const EwSys* __restrict__ sys, const int* __restrict__ gsys,
                                                        const int* __restrict__ rowptr, const int* __restrict__ nbr,
@@ -791,28 +833,13 @@ struct P3mPlan;
 void p3m_release(P3mPlan* p);
 // reads every system's cell^{-1}, Omega, pbc and atom count from sys and leaves its range of reduction chunks in first_k / n_k
 int p3m_plan_build(double sigma, double spacing, int nodes, const double* h_cells, std::vector<EwSys>& sys, P3mPlan** out);
-
-}  // namespace pet
-
-struct pet_ewald;
-
-namespace pet {
-struct Graph;
-// the mesh operator behind lr_potential / lr_backward / lr_second (ewald.hip dispatches on the handle's mode): a planned
-// P3M-mode handle WITH a transform hook, on one workspace of p3m_lr_workspace_bytes that lies ws_offset bytes into the running
-// entry point's d_workspace (the hook's offsets count from there)
-int64_t p3m_lr_workspace_bytes(const pet_ewald* e, int C);
-int p3m_lr_potential(const pet_ewald* e, const Graph& g, const float* pos, const float* X, int C, float* out, void* ws,
-                     hipStream_t st, int64_t ws_offset);
-int p3m_lr_backward(const pet_ewald* e, const Graph& g, const float* pos, const float* Q, const float* G, int C, float* gq,
-                    float* gpos, void* ws, hipStream_t st, int64_t ws_offset);
-int p3m_lr_second(const pet_ewald* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                  const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st, int64_t ws_offset);
-// the same with a cell tangent Ucell [S, 3, 3] (pet_p3m_second_cell), on one workspace of p3m_lr_cell_workspace_bytes
-int64_t p3m_lr_cell_workspace_bytes(const pet_ewald* e, int C);
-int p3m_lr_second_cell(const pet_ewald* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                       const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, void* ws, hipStream_t st,
-                       int64_t ws_offset);
+// the mesh operator's half of the interface above (ewald.hip holds the other half and the `if` between them): a planned
+// P3M-mode handle WITH a transform hook
+int64_t p3m_workspace_bytes(const pet_ewald_t* e, int C, bool cell);
+int p3m_potential(const LrCall& c, const float* X, float* out);
+int p3m_backward(const LrCall& c, const float* Q, const float* G, float* gq, float* gpos);
+int p3m_second(const LrCall& c, const float* Q, const float* G, const float* Uq, const float* Ur, const float* Ucell, float* out_q,
+               float* out_g, float* out_r);
 
 }  // namespace pet
 
@@ -882,6 +909,37 @@ int ew_check_graph(const pet_ewald_t* e, const pet_graph_t* pg, int32_t C) {
     return PET_OK;
 }
 
+// What the four second-order entry points (`entry`: pet_ewald_second, pet_ewald_second_cell, pet_p3m_second,
+// pet_p3m_second_cell) check before they run lr_second's half of their mode, in this order: the handle and its mode, the graph,
+// the transform hook (`mesh`), the cotangents, an empty plan (PET_OK with *run false: nothing to launch, and zero-sized buffers
+// may be null), the workspace, the inputs, the results (`no_results`: what to say where `results` is false).
+int ew_second_check(const pet_ewald_t* e, const pet_graph_t* pg, int32_t C, const char* entry, bool mesh, bool cell, bool cotangent,
+                    const void* ws, int64_t ws_bytes, bool inputs, bool results, const char* no_results, bool* run) {
+    *run = false;
+    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
+    if (mesh)
+        PET_REQUIRE(e->p3m_nodes != 0, PET_ERR_ARGUMENT,
+                    "a pet_p3m_* entry point on an Ewald-mode handle: call pet_ewald_set_p3m before pet_ewald_plan");
+    else
+        PET_REQUIRE(e->p3m_nodes == 0, PET_ERR_ARGUMENT,
+                    std::string(entry) + " on a P3M-mode handle (pet_ewald_set_p3m): the mesh operator's " +
+                        (cell ? "cell tangents are pet_p3m_second_cell's" : "second derivatives are pet_p3m_second's"));
+    PET_TRY(ew_check_graph(e, pg, C));
+    PET_REQUIRE(!mesh || e->p3m_transform, PET_ERR_ARGUMENT,
+                std::string(entry) + " on a P3M-mode handle without a transform hook: the mesh operator's second derivatives "
+                "and its place in the dual pass need the caller's transforms (pet_p3m_set_transform)");
+    PET_REQUIRE(cotangent, PET_ERR_ARGUMENT,
+                cell ? "d_u_charges, d_u_positions and d_u_cells are all NULL" : "d_u_charges and d_u_positions are both NULL");
+    if (e->n_atoms == 0) return PET_OK;
+    PET_REQUIRE(ws && ws_bytes >= lr_workspace_bytes(e, C, cell), PET_ERR_ARGUMENT,
+                std::string(mesh ? "P3M workspace missing or too small (" : "Ewald workspace too small (") + entry +
+                    "_workspace_bytes)");
+    PET_REQUIRE(inputs, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(results, PET_ERR_ARGUMENT, no_results);
+    *run = true;
+    return PET_OK;
+}
+
 // ---- the local terms, launched by both modes around their reciprocal-space part ------------------------------------------------
 // Forward. out holds a mode's reciprocal-space sum on the atoms of periodic systems; this adds the rest of the operator on
 // X [N, C]: the open all-pairs sum, then V <- P (V - self - background - exclusion), the column sums of X left in sums. The three
@@ -907,7 +965,8 @@ inline bool ew_vec_loads(int C, const float* q, const float* g) {
 }
 
 // Workspace of the adjoint that both modes carve: F [N, 3] (a mode's reciprocal-space forces on periodic atoms, written before
-// ew_local_backward), cell_part [N, 9], kpart [parts, 9] and the column sums of q and of dL/dV
+// ew_local_backward), cell_part [N, 9], kpart [parts, 9] and the column sums of q and of dL/dV (read by k_ew_cell alone: the
+// adjoint fills them where it has a cell gradient to form)
 struct EwLocalWs {
     float *F, *cell_part, *sum_q, *sum_g;
     double* kpart;
@@ -954,3 +1013,5 @@ int ew_backward_empty(const pet_ewald_t* e, float* d_grad_cells, hipStream_t st)
 }
 
 }  // namespace
+
+#endif  // LONG_RANGE_SHARED_PART

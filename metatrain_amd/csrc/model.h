@@ -259,10 +259,11 @@ struct HvpTaps {
 // seed_node / seed_edge [n_seed] (n_seed = 0 or num_readout_layers(); NULL entries = 0): first-order feature adjoints of
 // further targets, added to the nu half of every readout layer's adjoint. lA and nA both NULL: no fused target in the loss
 // The long-range stage of gen_train2: the featuriser between the backbone and the heads, on a planned
-// handle the caller has checked against the graph (lr_check: Ewald mode, or P3M mode with a transform hook). `ws` holds
-// lr_stage_workspace_bytes: the operator's second-order workspace at d_node channels, then the stage's dual rows; it lies
+// handle the caller has checked against the graph (long_range.h: lr_check). `ws` holds what gen_train.hip's lr_carve lays out: the
+// operator's workspace at d_node channels (lr_workspace_bytes; with `ucell` its cell form), then the stage's dual rows; it lies
 // ws_offset bytes into the d_workspace of the entry point (what a P3M handle's transform hook counts its offsets from).
-// rbar [N, 3] (Hessian-vector mode only) receives the operator's own share of dJ/dR.
+// rbar [N, 3] (Hessian-vector mode only) receives the operator's own share of dJ/dR; ucell [S, 3, 3] is the operator's cell
+// tangent (pet_backward_train2_long_range_cell; the backbone's is gen_train2's ucell).
 struct LrStage {
     const pet_ewald_t* e;
     const float* pos;
@@ -270,43 +271,22 @@ struct LrStage {
     int64_t ws_bytes;
     float* rbar;
     int64_t ws_offset;
-    // pet_backward_train2_long_range_cell: the cell tangent [S, 3, 3] of the operator (the backbone's is gen_train2's ucell);
-    // ws then holds lr_stage_workspace_bytes(..., true), with the operator's cell workspace in front
     const float* ucell = nullptr;
 };
 int gen_train2(const Model& m, const Graph& g, void* ws2, int64_t ws2_bytes, const float* lA, const float* nA, const float* u,
                const float* ucell, float* tangent_atomic, hipStream_t st, const float* const* seed_node = nullptr,
                const float* const* seed_edge = nullptr, int n_seed = 0, const HvpTaps* hv = nullptr,
                const LrStage* lr = nullptr);
-// the long-range forms of pet_backward_train2 and pet_hessian_vector (abi.hip checks and refuses; these carve and run)
-int64_t lr_stage_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes, bool cell = false);
-int64_t gen_train2_lr_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes, int64_t n_edges);
-// with a cell tangent ucell [S, 3, 3] beside u (either may be null, not both): the stress term of a loss
-int64_t gen_train2_lr_cell_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes, int64_t n_edges);
-int gen_train2_lr_cell(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
-                       const float* lA, const float* nA, const float* u, const float* ucell, float* tangent_atomic,
-                       hipStream_t st);
+// The long-range forms of pet_backward_train2 and pet_hessian_vector (abi.hip checks and refuses; these carve and run), on ONE
+// workspace whose layout LrSweep states for all three: the training sweep, the same with a cell tangent ucell [S, 3, 3]
+// beside u (either may be null, not both: the stress term of a loss) and the Hessian-vector product.
+enum LrSweep { LR_TRAIN, LR_TRAIN_CELL, LR_HVP };
+int64_t lr_sweep_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes, int64_t n_edges, LrSweep form);
+// (without ucell the sweep is the one without a cell tangent, launch for launch, on either workspace)
 int gen_train2_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
-                  const float* lA, const float* nA, const float* u, float* tangent_atomic, hipStream_t st);
-int64_t gen_hvp_lr_workspace_bytes(const Model& m, const pet_ewald_t* e, int64_t n_nodes, int64_t n_edges);
+                  const float* lA, const float* nA, const float* u, const float* ucell, float* tangent_atomic, hipStream_t st);
 int gen_hvp_lr(const Model& m, const Graph& g, const pet_ewald_t* e, const float* pos, void* ws, int64_t ws_bytes,
                const float* lA, const float* u, float* hvp_pos, float* tangent_atomic, hipStream_t st);
-// ewald.hip: the operator on device rows for that stage (one workspace of lr_ewald_workspace_bytes, ws_offset bytes into the
-// entry point's d_workspace; null results skipped)
-int lr_check(const pet_ewald_t* e, const pet_graph_t* pg, int C, const char* who);
-int64_t lr_ewald_workspace_bytes(const pet_ewald_t* e, int C);
-int lr_potential(const pet_ewald_t* e, const Graph& g, const float* pos, const float* X, int C, float* out, void* ws,
-                 hipStream_t st, int64_t ws_offset);
-int lr_backward(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, int C, float* gq,
-                float* gpos, void* ws, hipStream_t st, int64_t ws_offset);
-int lr_second(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-              const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st, int64_t ws_offset);
-// the same along (Ur, Ucell [S, 3, 3]) for the two results that feed parameter gradients, on one workspace of
-// lr_ewald_cell_workspace_bytes (pet_ewald_second_cell / pet_p3m_second_cell; Ur or Ucell may be null)
-int64_t lr_ewald_cell_workspace_bytes(const pet_ewald_t* e, int C);
-int lr_second_cell(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                   const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, void* ws, hipStream_t st,
-                   int64_t ws_offset);
 // Hessian-vector product of the fused single-property target on the size-generic dual pass (pet_hessian_vector)
 int64_t gen_hvp_workspace_bytes(const Model& m, int64_t n_nodes, int64_t n_edges);
 int gen_hvp(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* lA, const float* u, const float* ucell,

@@ -8,12 +8,13 @@
 //   pet_p3m_filter   k_p3m_filter: half spectrum times G^/Omega (k_p3m_influence at plan time, fp64 -> fp32)
 //   pet_p3m_finish   k_p3m_gather, then ew_local_forward (k_ew_pairs / k_ew_colsum / k_ew_finish)
 //   pet_p3m_backward k_p3m_force, then ew_local_backward (k_ew_force<false>, k_ew_edge_bwd, k_ew_cell) with k_p3m_cell before k_ew_cell
-// Second order (pet_p3m_second) and the dual pass (p3m_lr_*) run the whole operator inside ONE call: the
+// Second order (pet_p3m_second) and the dual pass (the mesh operator's half of long_range.h's interface:
+// p3m_potential / p3m_backward / p3m_second) run the whole operator inside ONE call: the
 // transforms come back through the handle's hook (pet_p3m_set_transform), between a mesh and a half spectrum inside the call's
 // own workspace. k_p3m_spread2 / k_p3m_gather2 / k_p3m_force2 are the three mesh kernels with the tangent and Hessian weights
 // beside the plain ones; the local terms are long_range.h's (k_ew_pairs<true>, k_ew_force2<false>, k_ew_edge_second).
 // Cell tangents (pet_p3m_second_cell): the position tangent at u' (k_ew_uprime), and the filter's tangent
-// K' = sum_bc d(G^/Omega)/dcell_bc u_c,bc (k_p3m_gdot) applied to the spectrum that p3m_solve_cell has in hand anyway
+// K' = sum_bc d(G^/Omega)/dcell_bc u_c,bc (k_p3m_gdot) applied to the spectrum that p3m_solve has in hand anyway
 // (k_p3m_filter_dot keeps it aside, k_p3m_spec_add adds it to the mesh the tangent gather reads): no transform is added.
 // Layout. CHANNEL-FIRST: the mesh of a system is [C, N_x, N_y, N_z] (z fastest), its half spectrum [C, N_x, N_y, N_z/2 + 1]
 // complex; the meshes of a batch's periodic, non-empty systems are packed one after another (system s starts at mesh_off_s * C).
@@ -24,6 +25,7 @@
 // p^3 nodes in the same order; channels are reduced by the butterfly of k_ew_force; per-point parts of dL/dcell are reduced per
 // chunk of 1024 half-spectrum points by a fixed tree and then in chunk order (k_ew_cell). The only atomics are integer counters
 // of the counting sort, whose result (a bin's atoms in atom order, after k_p3m_bin_sort) does not depend on their order.
+#define LONG_RANGE_SHARED_PART
 #include "long_range.h"
 
 namespace pet {
@@ -744,9 +746,10 @@ int p3m_bin(const pet_ewald_t* e, const Graph& g, const float* pos, const P3mWs&
     return PET_OK;
 }
 
-// The workspace of pet_p3m_second and of the dual pass: that of the staged entry points, then the second-derivative weights,
-// the per-atom directions, FOUR packed meshes and ONE packed half spectrum (the transforms of an entry point run one after
-// another on its stream). The byte offsets are what the transform hook is given: they count from the d_workspace of the entry
+// The workspace of the second-order operation and of the dual pass: that of the staged entry points, then the
+// second-derivative weights, the per-atom directions, FOUR packed meshes and ONE packed half spectrum (the transforms of an
+// entry point run one after another on its stream); then (cell: pet_p3m_second_cell) u' [N, 3], gdot per half-spectrum point
+// and the side spectrum. The byte offsets are what the transform hook is given: they count from the d_workspace of the entry
 // point that is running, ws_offset bytes before this workspace (the dual pass keeps its own rows in front of the operator's).
 enum { MESH_Q = 0, MESH_G = 1, MESH_A = 2, MESH_DG = 3 };
 struct P3mWs2 {
@@ -755,9 +758,11 @@ struct P3mWs2 {
     float* mesh[4];
     float2* spec;
     int64_t mesh_off[4], spec_off;
+    float *up, *gdot;
+    float2* side;
 };
 
-size_t p3m_carve2(const pet_ewald_t* e, int64_t C, void* base, P3mWs2& w2, int64_t ws_offset = 0) {
+size_t p3m_carve2(const pet_ewald_t* e, int64_t C, void* base, P3mWs2& w2, bool cell, int64_t ws_offset = 0) {
     Carver c(base);
     c.off = p3m_carve(e, C, base, w2.w);
     const P3mPlan* mp = e->p3m;
@@ -770,61 +775,172 @@ size_t p3m_carve2(const pet_ewald_t* e, int64_t C, void* base, P3mWs2& w2, int64
     }
     w2.spec_off = ws_offset + (int64_t)c.off;
     w2.spec = c.take<float2>((size_t)std::max<int64_t>(mp->s_total, 1) * C);
+    w2.up = w2.gdot = nullptr;
+    w2.side = nullptr;
+    if (cell) {
+        const size_t Sp = (size_t)std::max<int64_t>(mp->s_total, 1);
+        w2.up = c.take<float>(N * 3);
+        w2.gdot = c.take<float>(Sp);
+        w2.side = c.take<float2>(Sp * C);
+    }
     return c.off;
 }
 
-// mesh[slot] <- K mesh[slot]: the hook's rfftn into the half spectrum, the filter, the hook's irfftn back
-int p3m_solve(const pet_ewald_t* e, int C, const P3mWs2& w2, int slot, hipStream_t st) {
+// mesh[slot] <- K mesh[slot]: the hook's rfftn into the half spectrum, the filter, the hook's irfftn back. Under a cell tangent
+// the filter's tangent rides on the same transforms: CELL_KEEP keeps (gdot . the unfiltered spectrum) in the side spectrum,
+// CELL_ADD adds the side spectrum to the filtered one. Two hook calls either way.
+enum { CELL_NONE = -1, CELL_KEEP = 0, CELL_ADD = 1 };
+int p3m_solve(const pet_ewald_t* e, int C, const P3mWs2& w2, int slot, hipStream_t st, int what = CELL_NONE) {
     const P3mPlan* mp = e->p3m;
     if (mp->stiles.empty()) return PET_OK;
+    const dim3 grid((unsigned)mp->stiles.size(), (unsigned)std::min(C, 256));
     for (int inverse = 0; inverse < 2; inverse++) {
         const int rc = e->p3m_transform(e->p3m_transform_user, inverse, w2.mesh_off[slot], w2.spec_off, C);
         PET_REQUIRE(rc == 0, PET_ERR_ARGUMENT,
                     "the transform hook (pet_p3m_set_transform) returned " + std::to_string(rc) + " for the " +
                         (inverse ? "inverse" : "forward") + " transform");
-        if (!inverse)
-            k_p3m_filter<<<dim3((unsigned)mp->stiles.size(), (unsigned)std::min(C, 256)), 256, 0, st>>>(
-                mp->d_stiles, mp->d_sys, mp->d_infl, C, w2.spec);
+        if (inverse) continue;
+        if (what == CELL_KEEP) k_p3m_filter_dot<<<grid, 256, 0, st>>>(mp->d_stiles, mp->d_sys, w2.gdot, C, w2.spec, w2.side);
+        k_p3m_filter<<<grid, 256, 0, st>>>(mp->d_stiles, mp->d_sys, mp->d_infl, C, w2.spec);
+        if (what == CELL_ADD) k_p3m_spec_add<<<grid, 256, 0, st>>>(mp->d_stiles, mp->d_sys, C, w2.side, w2.spec);
     }
     PET_HIP_CHECK(hipGetLastError());
     return PET_OK;
 }
 
-// mesh[slot] <- K W X with the kernels of the staged entry points (the dual pass' first-order calls keep their bits)
-int p3m_potential_mesh(const pet_ewald_t* e, const float* X, int C, const P3mWs2& w2, int slot, hipStream_t st) {
+// ---- the three launches that the staged entry points (pet_p3m_spread / _finish / _backward) share with the interface ----------
+// mesh <- W X on the bins that p3m_bin left in w
+void p3m_spread(const pet_ewald_t* e, const float* X, int C, const P3mWs& w, float* mesh, hipStream_t st) {
     const P3mPlan* mp = e->p3m;
-    if (mp->mtiles.empty()) return PET_OK;
+    if (mp->mtiles.empty()) return;
     const bool vec = C % P3M_CH == 0 && ((uintptr_t)X & 15) == 0;
     k_p3m_spread<<<dim3((unsigned)mp->mtiles.size(), (unsigned)cdiv(C, P3M_CH)), 256, 0, st>>>(
-        mp->d_mtiles, mp->d_sys, w2.w.start, w2.w.order, w2.w.wts, e->p3m_nodes, X, C, vec, w2.mesh[slot]);
+        mp->d_mtiles, mp->d_sys, w.start, w.order, w.wts, e->p3m_nodes, X, C, vec, mesh);
+}
+// out <- W^T phi on the atoms of periodic systems
+void p3m_gather(const pet_ewald_t* e, const Graph& g, const P3mWs& w, const float* phi, int C, float* out, hipStream_t st) {
+    if (e->p3m->m_total > 0)
+        k_p3m_gather<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, e->p3m->d_sys, w.org, w.wts, e->p3m_nodes, phi, (int)e->n_atoms, C, out);
+}
+// w.loc.F <- the mesh part of grad_r Phi(r; G, Q) from the two mesh potentials
+void p3m_force(const pet_ewald_t* e, const Graph& g, const P3mWs& w, const float* phi_q, const float* phi_g, const float* G,
+               const float* Q, int C, hipStream_t st) {
+    if (e->p3m->m_total > 0)
+        k_p3m_force<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, e->p3m->d_sys, w.org, w.wts, w.dwts, e->p3m_nodes, phi_q, phi_g, G, Q,
+                                                         (int)e->n_atoms, C, w.loc.F);
+}
+// out = W^T phi, then the local terms of the operator on X: what follows the mesh potential of X
+int p3m_finish(const pet_ewald_t* e, const Graph& g, const float* pos, const float* X, int C, const float* phi, float* out,
+               const P3mWs& w, hipStream_t st) {
+    p3m_gather(e, g, w, phi, C, out, st);
+    return ew_local_forward(e, g, pos, X, C, out, w.loc.sum_q, st);
+}
+
+// mesh[slot] <- K W X with the kernels of the staged entry points (the dual pass' first-order calls keep their bits)
+int p3m_potential_mesh(const pet_ewald_t* e, const float* X, int C, const P3mWs2& w2, int slot, hipStream_t st) {
+    if (e->p3m->mtiles.empty()) return PET_OK;
+    p3m_spread(e, X, C, w2.w, w2.mesh[slot], st);
     return p3m_solve(e, C, w2, slot, st);
 }
 
-// pet_p3m_second with selectable results, as ew_second_run: a null out_q / out_g / out_r is not formed, and the meshes,
+}  // namespace
+
+// ---- the mesh operator's half of the interface (long_range.h). Every call bins anew (six small launches; the positions do not
+// change inside a sweep, but neither do the calls share more than that) and nothing is kept between calls. -------------------
+int64_t p3m_workspace_bytes(const pet_ewald_t* e, int C, bool cell) {
+    P3mWs2 w2;
+    return (int64_t)p3m_carve2(e, C, nullptr, w2, cell);
+}
+
+int p3m_potential(const LrCall& c, const float* X, float* out) {
+    P3mWs2 w2;
+    p3m_carve2(c.e, c.C, c.ws, w2, false, c.ws_offset);
+    ProfScope ps("p3m_fwd", c.st, 0.0, 0.0);
+    PET_TRY(p3m_bin(c.e, *c.g, c.pos, w2.w, c.st));
+    PET_TRY(p3m_potential_mesh(c.e, X, c.C, w2, MESH_Q, c.st));
+    return p3m_finish(c.e, *c.g, c.pos, X, c.C, w2.mesh[MESH_Q], out, w2.w, c.st);
+}
+
+int p3m_backward(const LrCall& c, const float* Q, const float* G, float* gq, float* gpos) {
+    const pet_ewald_t* e = c.e;
+    P3mWs2 w2;
+    p3m_carve2(e, c.C, c.ws, w2, false, c.ws_offset);
+    const P3mWs& w = w2.w;
+    ProfScope ps("p3m_bwd", c.st, 0.0, 0.0);
+    PET_TRY(p3m_bin(e, *c.g, c.pos, w, c.st));
+    PET_TRY(p3m_potential_mesh(e, G, c.C, w2, MESH_G, c.st));
+    PET_TRY(p3m_potential_mesh(e, Q, c.C, w2, MESH_Q, c.st));
+    p3m_gather(e, *c.g, w, w2.mesh[MESH_G], c.C, gq, c.st);
+    p3m_force(e, *c.g, w, w2.mesh[MESH_Q], w2.mesh[MESH_G], G, Q, c.C, c.st);
+    PET_TRY(ew_local_forward(e, *c.g, c.pos, G, c.C, gq, w.loc.sum_g, c.st));
+    return ew_local_backward(e, *c.g, c.pos, Q, G, c.C, w.loc, gpos, nullptr, c.st, [] {});
+}
+
+// The second-order operation with selectable results, as ew_second: a null out_q / out_g / out_r is not formed, and the meshes,
 // transform pairs and launches that serve it alone are skipped. Q may be null where only out_q is asked for, G where only
 // out_g is. Transform pairs with both cotangents: out_g alone 2 (phi_q, phi_a), out_q alone 2 (phi_g, phi_dg), out_r or all
 // three 4; with u_q alone 1 / 0 / 2, with u_r alone as with both.
-int p3m_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                   const float* Ur, int C, float* out_q, float* out_g, float* out_r, const P3mWs2& w2, hipStream_t st) {
+// With Ucell (pet_p3m_second_cell; no out_r): out_g = A u_q + (D A) q, out_q = (D A) g along (u_r, u_c). The position tangent is
+// taken at u' = u_r - r U; the filter's tangent rides on the same transforms (p3m_solve); the local terms are k_ew_pairs<true> at
+// u' and ew_local_cell. Transform pairs: 2 per result formed (4 hook calls), whatever the cotangents.
+int p3m_second(const LrCall& c, const float* Q, const float* G, const float* Uq, const float* Ur, const float* Ucell, float* out_q,
+               float* out_g, float* out_r) {
+    const pet_ewald_t* e = c.e;
+    const Graph& g = *c.g;
+    const float* pos = c.pos;
+    const int C = c.C;
+    hipStream_t st = c.st;
+    P3mWs2 w2;
+    p3m_carve2(e, C, c.ws, w2, Ucell != nullptr, c.ws_offset);
     const P3mPlan* mp = e->p3m;
     const P3mWs& w = w2.w;
     const int N = (int)e->n_atoms, p = e->p3m_nodes;
     const bool per = mp->m_total > 0;
     const unsigned cy = (unsigned)cdiv(C, 256), nn = (unsigned)e->atiles_n.size(), na = (unsigned)cdiv(N, 4);
     const float inv_R = (float)(1.0 / e->cutoff);
-    ProfScope ps(out_q && out_g && out_r ? "p3m_second" : out_g ? "p3m_second_g" : out_r ? "p3m_second_qr" : "p3m_second_q", st,
-                 0.0, 0.0);
-    PET_TRY(p3m_bin(e, g, pos, w, st, w2.d2wts, Ur, w2.du));
-    auto mesh_of = [&](int slot, const float* X1, const float* X2) -> int {
+    ProfScope ps(Ucell ? (out_g && out_q ? "p3m_second_cell" : out_g ? "p3m_second_cell_g" : "p3m_second_cell_q")
+                 : out_q && out_g && out_r ? "p3m_second" : out_g ? "p3m_second_g" : out_r ? "p3m_second_qr" : "p3m_second_q",
+                 st, 0.0, 0.0);
+    auto mesh_of = [&](int slot, const float* X1, const float* X2, int what = CELL_NONE) -> int {
         if (!per) return PET_OK;
         k_p3m_spread2<<<dim3((unsigned)mp->mtiles.size(), (unsigned)cdiv(C, P3M_CH)), 256, 0, st>>>(
             mp->d_mtiles, mp->d_sys, w.start, w.order, w.wts, w.dwts, w2.du, p, X1, X2, C, w2.mesh[slot]);
-        return p3m_solve(e, C, w2, slot, st);
+        return p3m_solve(e, C, w2, slot, st, what);
     };
     auto gather = [&](const float* phi_a, const float* phi_b, float scale, float* out) {
         if (per)
             k_p3m_gather2<<<na, 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, w.dwts, w2.du, p, phi_a, phi_b, N, C, scale, out);
     };
+    if (Ucell) {
+        k_ew_uprime<<<cdiv(N, 256), 256, 0, st>>>(pos, g.sys, e->d_sys, Ur, Ucell, N, w2.up);
+        PET_TRY(p3m_bin(e, g, pos, w, st, nullptr, w2.up, w2.du));
+        if (!mp->stiles.empty())
+            k_p3m_gdot<<<(unsigned)mp->stiles.size(), 256, 0, st>>>(mp->d_stiles, mp->d_sys, Ucell, e->sigma, p, w2.gdot);
+        if (out_g) {
+            // phi_q = K W q, then K (W u_q + (D_u' W) q) + K' W q as ONE mesh
+            PET_TRY(mesh_of(MESH_Q, Q, nullptr, CELL_KEEP));
+            PET_TRY(mesh_of(MESH_A, Uq, Q, CELL_ADD));
+            if (Uq) {
+                gather(w2.mesh[MESH_A], w2.mesh[MESH_Q], 1.f, out_g);
+                PET_TRY(ew_local_forward(e, g, pos, Uq, C, out_g, w.loc.sum_g, st));
+            } else {
+                PET_HIP_CHECK(hipMemsetAsync(out_g, 0, (size_t)N * C * sizeof(float), st));
+                gather(w2.mesh[MESH_A], w2.mesh[MESH_Q], (float)EW_PREFACTOR, out_g);
+            }
+        }
+        if (out_q) {
+            PET_TRY(mesh_of(MESH_G, G, nullptr, CELL_KEEP));
+            PET_TRY(mesh_of(MESH_DG, nullptr, G, CELL_ADD));
+            PET_HIP_CHECK(hipMemsetAsync(out_q, 0, (size_t)N * C * sizeof(float), st));
+            gather(w2.mesh[MESH_DG], w2.mesh[MESH_G], (float)EW_PREFACTOR, out_q);
+        }
+        if (nn) {
+            if (out_g) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, Q, C, out_g, w2.up);
+            if (out_q) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, G, C, out_q, w2.up);
+        }
+        return ew_local_cell(e, g, Q, G, Ur, Ucell, C, w.loc, out_g, out_q, st);
+    }
+    PET_TRY(p3m_bin(e, g, pos, w, st, w2.d2wts, Ur, w2.du));
     if (Ur && (out_g || out_r)) PET_TRY(mesh_of(MESH_Q, Q, nullptr));
     if (out_r || (Ur && out_q)) PET_TRY(mesh_of(MESH_G, G, nullptr));
     if (out_g || out_r) PET_TRY(mesh_of(MESH_A, Uq, Ur ? Q : nullptr));  // W u_q + (D_u W) q as ONE mesh
@@ -838,9 +954,7 @@ int p3m_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const
         }
         if (out_r) {
             if (Ur) PET_HIP_CHECK(hipMemsetAsync(w.loc.F, 0, (size_t)N * 3 * sizeof(float), st));
-            else if (per)
-                k_p3m_force<<<na, 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, w.dwts, p, w2.mesh[MESH_G], w2.mesh[MESH_A], Uq, G, N,
-                                                C, w.loc.F);
+            else p3m_force(e, g, w, w2.mesh[MESH_G], w2.mesh[MESH_A], Uq, G, C, st);
             PET_TRY(ew_local_backward(e, g, pos, G, Uq, C, w.loc, out_r, nullptr, st, [] {}));
         }
     } else {
@@ -869,166 +983,6 @@ int p3m_second_run(const pet_ewald_t* e, const Graph& g, const float* pos, const
     }
     PET_HIP_CHECK(hipGetLastError());
     return PET_OK;
-}
-
-// The workspace of pet_p3m_second_cell: that of pet_p3m_second (the hook's offsets are its), then u' [N, 3], gdot per
-// half-spectrum point and the side spectrum.
-struct P3mWs3 {
-    P3mWs2 w2;
-    float *up, *gdot;
-    float2* side;
-};
-
-size_t p3m_carve3(const pet_ewald_t* e, int64_t C, void* base, P3mWs3& w3, int64_t ws_offset = 0) {
-    Carver c(base);
-    c.off = p3m_carve2(e, C, base, w3.w2, ws_offset);
-    const size_t Sp = (size_t)std::max<int64_t>(e->p3m->s_total, 1);
-    w3.up = c.take<float>((size_t)std::max<int64_t>(e->n_atoms, 1) * 3);
-    w3.gdot = c.take<float>(Sp);
-    w3.side = c.take<float2>(Sp * C);
-    return c.off;
-}
-
-// p3m_solve with the cell tangent's fold: keep (gdot . the unfiltered spectrum) in the side spectrum, or add the side spectrum
-// to the filtered one. Two hook calls, as p3m_solve.
-enum { CELL_KEEP = 0, CELL_ADD = 1 };
-int p3m_solve_cell(const pet_ewald_t* e, int C, const P3mWs3& w3, int slot, int what, hipStream_t st) {
-    const P3mPlan* mp = e->p3m;
-    const P3mWs2& w2 = w3.w2;
-    if (mp->stiles.empty()) return PET_OK;
-    const dim3 grid((unsigned)mp->stiles.size(), (unsigned)std::min(C, 256));
-    for (int inverse = 0; inverse < 2; inverse++) {
-        const int rc = e->p3m_transform(e->p3m_transform_user, inverse, w2.mesh_off[slot], w2.spec_off, C);
-        PET_REQUIRE(rc == 0, PET_ERR_ARGUMENT,
-                    "the transform hook (pet_p3m_set_transform) returned " + std::to_string(rc) + " for the " +
-                        (inverse ? "inverse" : "forward") + " transform");
-        if (inverse) continue;
-        if (what == CELL_KEEP) k_p3m_filter_dot<<<grid, 256, 0, st>>>(mp->d_stiles, mp->d_sys, w3.gdot, C, w2.spec, w3.side);
-        k_p3m_filter<<<grid, 256, 0, st>>>(mp->d_stiles, mp->d_sys, mp->d_infl, C, w2.spec);
-        if (what == CELL_ADD) k_p3m_spec_add<<<grid, 256, 0, st>>>(mp->d_stiles, mp->d_sys, C, w3.side, w2.spec);
-    }
-    PET_HIP_CHECK(hipGetLastError());
-    return PET_OK;
-}
-
-// pet_p3m_second_cell: out_g = A u_q + (D A) q, out_q = (D A) g along (u_r, u_c); a null result is not formed. The position
-// tangent is p3m_second_run's at u' = u_r - r U; the filter's tangent rides on the same transforms (above); the local terms are
-// k_ew_pairs<true> at u' and ew_local_cell. Transform pairs: 2 per result formed (4 hook calls), whatever the cotangents.
-// Without Ucell it is p3m_second_run without out_r.
-int p3m_second_cell_run(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                        const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, const P3mWs3& w3, hipStream_t st) {
-    const P3mWs2& w2 = w3.w2;
-    if (!Ucell) return p3m_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, nullptr, w2, st);
-    const P3mPlan* mp = e->p3m;
-    const P3mWs& w = w2.w;
-    const int N = (int)e->n_atoms, p = e->p3m_nodes;
-    const bool per = mp->m_total > 0;
-    const unsigned cy = (unsigned)cdiv(C, 256), nn = (unsigned)e->atiles_n.size(), na = (unsigned)cdiv(N, 4);
-    const float inv_R = (float)(1.0 / e->cutoff);
-    ProfScope ps(out_g && out_q ? "p3m_second_cell" : out_g ? "p3m_second_cell_g" : "p3m_second_cell_q", st, 0.0, 0.0);
-    k_ew_uprime<<<cdiv(N, 256), 256, 0, st>>>(pos, g.sys, e->d_sys, Ur, Ucell, N, w3.up);
-    PET_TRY(p3m_bin(e, g, pos, w, st, nullptr, w3.up, w2.du));
-    if (!mp->stiles.empty())
-        k_p3m_gdot<<<(unsigned)mp->stiles.size(), 256, 0, st>>>(mp->d_stiles, mp->d_sys, Ucell, e->sigma, p, w3.gdot);
-    auto mesh_of = [&](int slot, const float* X1, const float* X2, int what) -> int {
-        if (!per) return PET_OK;
-        k_p3m_spread2<<<dim3((unsigned)mp->mtiles.size(), (unsigned)cdiv(C, P3M_CH)), 256, 0, st>>>(
-            mp->d_mtiles, mp->d_sys, w.start, w.order, w.wts, w.dwts, w2.du, p, X1, X2, C, w2.mesh[slot]);
-        return p3m_solve_cell(e, C, w3, slot, what, st);
-    };
-    auto gather = [&](const float* phi_a, const float* phi_b, float scale, float* out) {
-        if (per)
-            k_p3m_gather2<<<na, 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, w.dwts, w2.du, p, phi_a, phi_b, N, C, scale, out);
-    };
-    if (out_g) {
-        // phi_q = K W q, then K (W u_q + (D_u' W) q) + K' W q as ONE mesh
-        PET_TRY(mesh_of(MESH_Q, Q, nullptr, CELL_KEEP));
-        PET_TRY(mesh_of(MESH_A, Uq, Q, CELL_ADD));
-        if (Uq) {
-            gather(w2.mesh[MESH_A], w2.mesh[MESH_Q], 1.f, out_g);
-            PET_TRY(ew_local_forward(e, g, pos, Uq, C, out_g, w.loc.sum_g, st));
-        } else {
-            PET_HIP_CHECK(hipMemsetAsync(out_g, 0, (size_t)N * C * sizeof(float), st));
-            gather(w2.mesh[MESH_A], w2.mesh[MESH_Q], (float)EW_PREFACTOR, out_g);
-        }
-    }
-    if (out_q) {
-        PET_TRY(mesh_of(MESH_G, G, nullptr, CELL_KEEP));
-        PET_TRY(mesh_of(MESH_DG, nullptr, G, CELL_ADD));
-        PET_HIP_CHECK(hipMemsetAsync(out_q, 0, (size_t)N * C * sizeof(float), st));
-        gather(w2.mesh[MESH_DG], w2.mesh[MESH_G], (float)EW_PREFACTOR, out_q);
-    }
-    if (nn) {
-        if (out_g) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, Q, C, out_g, w3.up);
-        if (out_q) k_ew_pairs<true><<<dim3(nn, cy), 256, 0, st>>>(e->d_atiles_n, e->d_sys, pos, inv_R, G, C, out_q, w3.up);
-    }
-    return ew_local_cell(e, g, Q, G, Ur, Ucell, C, w.loc, out_g, out_q, st);
-}
-
-const char* const P3M_NO_HOOK =
-    "a P3M-mode handle without a transform hook: the mesh operator's second derivatives and its place in the dual pass need "
-    "the caller's transforms (pet_p3m_set_transform)";
-
-}  // namespace
-
-// ---- the mesh operator for the long-range stage of the dual pass (lr_potential / lr_backward / lr_second of ewald.hip) -----
-// Every call bins anew (six small launches; the positions do not change inside a sweep, but neither do the calls share more
-// than that) and nothing is kept between calls.
-int64_t p3m_lr_workspace_bytes(const pet_ewald_t* e, int C) {
-    P3mWs2 w2;
-    return (int64_t)p3m_carve2(e, C, nullptr, w2);
-}
-
-int p3m_lr_potential(const pet_ewald_t* e, const Graph& g, const float* pos, const float* X, int C, float* out, void* ws,
-                     hipStream_t st, int64_t ws_offset) {
-    P3mWs2 w2;
-    p3m_carve2(e, C, ws, w2, ws_offset);
-    ProfScope ps("p3m_fwd", st, 0.0, 0.0);
-    PET_TRY(p3m_bin(e, g, pos, w2.w, st));
-    PET_TRY(p3m_potential_mesh(e, X, C, w2, MESH_Q, st));
-    if (e->p3m->m_total > 0)
-        k_p3m_gather<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, e->p3m->d_sys, w2.w.org, w2.w.wts, e->p3m_nodes, w2.mesh[MESH_Q],
-                                                          (int)e->n_atoms, C, out);
-    return ew_local_forward(e, g, pos, X, C, out, w2.w.loc.sum_q, st);
-}
-
-int p3m_lr_backward(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, int C, float* gq,
-                    float* gpos, void* ws, hipStream_t st, int64_t ws_offset) {
-    P3mWs2 w2;
-    p3m_carve2(e, C, ws, w2, ws_offset);
-    const P3mWs& w = w2.w;
-    ProfScope ps("p3m_bwd", st, 0.0, 0.0);
-    PET_TRY(p3m_bin(e, g, pos, w, st));
-    PET_TRY(p3m_potential_mesh(e, G, C, w2, MESH_G, st));
-    PET_TRY(p3m_potential_mesh(e, Q, C, w2, MESH_Q, st));
-    if (e->p3m->m_total > 0) {
-        k_p3m_gather<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, e->p3m->d_sys, w.org, w.wts, e->p3m_nodes, w2.mesh[MESH_G],
-                                                          (int)e->n_atoms, C, gq);
-        k_p3m_force<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, e->p3m->d_sys, w.org, w.wts, w.dwts, e->p3m_nodes, w2.mesh[MESH_Q],
-                                                         w2.mesh[MESH_G], G, Q, (int)e->n_atoms, C, w.loc.F);
-    }
-    PET_TRY(ew_local_forward(e, g, pos, G, C, gq, w.loc.sum_g, st));
-    return ew_local_backward(e, g, pos, Q, G, C, w.loc, gpos, nullptr, st, [] {});
-}
-
-int p3m_lr_second(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                  const float* Ur, int C, float* out_q, float* out_g, float* out_r, void* ws, hipStream_t st, int64_t ws_offset) {
-    P3mWs2 w2;
-    p3m_carve2(e, C, ws, w2, ws_offset);
-    return p3m_second_run(e, g, pos, Q, G, Uq, Ur, C, out_q, out_g, out_r, w2, st);
-}
-
-int64_t p3m_lr_cell_workspace_bytes(const pet_ewald_t* e, int C) {
-    P3mWs3 w3;
-    return (int64_t)p3m_carve3(e, C, nullptr, w3);
-}
-
-int p3m_lr_second_cell(const pet_ewald_t* e, const Graph& g, const float* pos, const float* Q, const float* G, const float* Uq,
-                       const float* Ur, const float* Ucell, int C, float* out_q, float* out_g, void* ws, hipStream_t st,
-                       int64_t ws_offset) {
-    P3mWs3 w3;
-    p3m_carve3(e, C, ws, w3, ws_offset);
-    return p3m_second_cell_run(e, g, pos, Q, G, Uq, Ur, Ucell, C, out_q, out_g, w3, st);
 }
 
 // pet_ewald_plan of a P3M-mode handle: mesh descriptors and influence functions instead of k lists, for the systems the shared
@@ -1162,11 +1116,7 @@ int pet_p3m_spread(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_p
     p3m_carve(e, C, d_workspace, w);
     ProfScope ps("p3m_spread", st, 0.0, 0.0);
     PET_TRY(p3m_bin(e, pg->g, d_positions, w, st));
-    if (!mp->mtiles.empty()) {
-        const bool vec = C % P3M_CH == 0 && ((uintptr_t)d_charges & 15) == 0;
-        k_p3m_spread<<<dim3((unsigned)mp->mtiles.size(), (unsigned)cdiv(C, P3M_CH)), 256, 0, st>>>(
-            mp->d_mtiles, mp->d_sys, w.start, w.order, w.wts, e->p3m_nodes, d_charges, C, vec, d_mesh);
-    }
+    p3m_spread(e, d_charges, C, w, d_mesh, st);
     PET_HIP_CHECK(hipGetLastError());
     return PET_OK;
 }
@@ -1195,14 +1145,10 @@ int pet_p3m_finish(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_p
     const P3mPlan* mp = e->p3m;
     PET_REQUIRE(d_mesh_potential || mp->m_total == 0, PET_ERR_ARGUMENT, "no mesh buffer (pet_p3m_mesh_elements)");
     hipStream_t st = (hipStream_t)stream;
-    const Graph& g = pg->g;
     P3mWs w;
     p3m_carve(e, C, d_workspace, w);
     ProfScope ps("p3m_finish", st, 0.0, 0.0);
-    if (mp->m_total > 0)
-        k_p3m_gather<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, e->p3m_nodes, d_mesh_potential,
-                                                          (int)e->n_atoms, C, d_out);
-    return ew_local_forward(e, g, d_positions, d_charges, C, d_out, w.loc.sum_q, st);
+    return p3m_finish(e, pg->g, d_positions, d_charges, C, d_mesh_potential, d_out, w, st);
 }
 
 int pet_p3m_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
@@ -1221,12 +1167,12 @@ int pet_p3m_backward(const pet_ewald_t* e, const pet_graph_t* pg, const float* d
     P3mWs w;
     p3m_carve(e, C, d_workspace, w);
     ProfScope ps("p3m_bwd", st, 0.0, 0.0);
-    const unsigned cy = (unsigned)cdiv(C, 256);
-    k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_charges, C, w.loc.sum_q);
-    k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_grad_potential, C, w.loc.sum_g);
-    if (mp->m_total > 0)
-        k_p3m_force<<<cdiv(e->n_atoms, 4), 256, 0, st>>>(g.sys, mp->d_sys, w.org, w.wts, w.dwts, e->p3m_nodes, d_phi_q, d_phi_g,
-                                                         d_grad_potential, d_charges, (int)e->n_atoms, C, w.loc.F);
+    if (d_grad_cells) {  // (k_ew_cell alone reads the column sums)
+        const unsigned cy = (unsigned)cdiv(C, 256);
+        k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_charges, C, w.loc.sum_q);
+        k_ew_colsum<<<dim3((unsigned)e->n_systems, cy), 256, 0, st>>>(e->d_sys, d_grad_potential, C, w.loc.sum_g);
+    }
+    p3m_force(e, g, w, d_phi_q, d_phi_g, d_grad_potential, d_charges, C, st);
     return ew_local_backward(e, g, d_positions, d_charges, d_grad_potential, C, w.loc, d_grad_positions, d_grad_cells, st, [&] {
         if (!mp->stiles.empty())
             k_p3m_cell<<<(unsigned)mp->stiles.size(), 256, 0, st>>>(mp->d_stiles, mp->d_sys, (const float2*)d_spec_q,
@@ -1245,57 +1191,38 @@ int pet_p3m_set_transform(pet_ewald_t* e, pet_p3m_transform_fn fn, void* user) {
 
 int64_t pet_p3m_second_workspace_bytes(const pet_ewald_t* e, int64_t n_channels) {
     if (!e || !e->planned || !e->p3m || n_channels < 1) return -1;
-    P3mWs2 w2;
-    return (int64_t)p3m_carve2(e, n_channels, nullptr, w2);
+    return p3m_workspace_bytes(e, (int)n_channels, false);
 }
 
 int pet_p3m_second(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
                    const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions, int32_t C,
                    float* d_out_charges, float* d_out_grad_potential, float* d_out_positions, void* d_workspace,
                    int64_t workspace_bytes, void* stream) {
-    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
-    PET_REQUIRE(e->p3m_nodes != 0, PET_ERR_ARGUMENT,
-                "a pet_p3m_* entry point on an Ewald-mode handle: call pet_ewald_set_p3m before pet_ewald_plan");
-    PET_TRY(ew_check_graph(e, pg, C));
-    PET_REQUIRE(e->p3m_transform, PET_ERR_ARGUMENT, std::string("pet_p3m_second on ") + P3M_NO_HOOK);
-    PET_REQUIRE(d_u_charges || d_u_positions, PET_ERR_ARGUMENT, "d_u_charges and d_u_positions are both NULL");
-    if (e->n_atoms == 0) return PET_OK;
-    P3mWs2 w2;
-    PET_REQUIRE(d_workspace && workspace_bytes >= (int64_t)p3m_carve2(e, C, nullptr, w2), PET_ERR_ARGUMENT,
-                "P3M workspace missing or too small (pet_p3m_second_workspace_bytes)");
-    PET_REQUIRE(d_positions && d_charges && d_grad_potential, PET_ERR_ARGUMENT, "null argument");
-    PET_REQUIRE(d_out_charges || d_out_grad_potential || d_out_positions, PET_ERR_ARGUMENT, "all three results are NULL");
-    p3m_carve2(e, C, d_workspace, w2);
-    return p3m_second_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, C, d_out_charges,
-                          d_out_grad_potential, d_out_positions, w2, (hipStream_t)stream);
+    bool run;
+    PET_TRY(ew_second_check(e, pg, C, "pet_p3m_second", true, false, d_u_charges || d_u_positions, d_workspace, workspace_bytes,
+                            d_positions && d_charges && d_grad_potential,
+                            d_out_charges || d_out_grad_potential || d_out_positions, "all three results are NULL", &run));
+    if (!run) return PET_OK;
+    return p3m_second(LrCall{e, &pg->g, d_positions, C, d_workspace, 0, (hipStream_t)stream}, d_charges, d_grad_potential,
+                      d_u_charges, d_u_positions, nullptr, d_out_charges, d_out_grad_potential, d_out_positions);
 }
 
 int64_t pet_p3m_second_cell_workspace_bytes(const pet_ewald_t* e, int64_t n_channels) {
     if (!e || !e->planned || !e->p3m || n_channels < 1) return -1;
-    P3mWs3 w3;
-    return (int64_t)p3m_carve3(e, n_channels, nullptr, w3);
+    return p3m_workspace_bytes(e, (int)n_channels, true);
 }
 
 int pet_p3m_second_cell(const pet_ewald_t* e, const pet_graph_t* pg, const float* d_positions, const float* d_charges,
                         const float* d_grad_potential, const float* d_u_charges, const float* d_u_positions,
                         const float* d_u_cells, int32_t C, float* d_out_charges, float* d_out_grad_potential, void* d_workspace,
                         int64_t workspace_bytes, void* stream) {
-    PET_REQUIRE(e, PET_ERR_ARGUMENT, "null argument");
-    PET_REQUIRE(e->p3m_nodes != 0, PET_ERR_ARGUMENT,
-                "a pet_p3m_* entry point on an Ewald-mode handle: call pet_ewald_set_p3m before pet_ewald_plan");
-    PET_TRY(ew_check_graph(e, pg, C));
-    PET_REQUIRE(e->p3m_transform, PET_ERR_ARGUMENT, std::string("pet_p3m_second_cell on ") + P3M_NO_HOOK);
-    PET_REQUIRE(d_u_charges || d_u_positions || d_u_cells, PET_ERR_ARGUMENT,
-                "d_u_charges, d_u_positions and d_u_cells are all NULL");
-    if (e->n_atoms == 0) return PET_OK;
-    P3mWs3 w3;
-    PET_REQUIRE(d_workspace && workspace_bytes >= (int64_t)p3m_carve3(e, C, nullptr, w3), PET_ERR_ARGUMENT,
-                "P3M workspace missing or too small (pet_p3m_second_cell_workspace_bytes)");
-    PET_REQUIRE(d_positions && d_charges && d_grad_potential, PET_ERR_ARGUMENT, "null argument");
-    PET_REQUIRE(d_out_charges || d_out_grad_potential, PET_ERR_ARGUMENT, "both results are NULL");
-    p3m_carve3(e, C, d_workspace, w3);
-    return p3m_second_cell_run(e, pg->g, d_positions, d_charges, d_grad_potential, d_u_charges, d_u_positions, d_u_cells, C,
-                               d_out_charges, d_out_grad_potential, w3, (hipStream_t)stream);
+    bool run;
+    PET_TRY(ew_second_check(e, pg, C, "pet_p3m_second_cell", true, true, d_u_charges || d_u_positions || d_u_cells, d_workspace,
+                            workspace_bytes, d_positions && d_charges && d_grad_potential, d_out_charges || d_out_grad_potential,
+                            "both results are NULL", &run));
+    if (!run) return PET_OK;
+    return p3m_second(LrCall{e, &pg->g, d_positions, C, d_workspace, 0, (hipStream_t)stream}, d_charges, d_grad_potential,
+                      d_u_charges, d_u_positions, d_u_cells, d_out_charges, d_out_grad_potential, nullptr);
 }
 
 }  // extern "C"

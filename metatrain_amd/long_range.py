@@ -187,9 +187,7 @@ class EwaldHip:
     """``pet_ewald_t``: the operator ``q [N, C] -> V [N, C]`` and its adjoints on device tensors."""
 
     _warns_kset = True  # the k-set warning is the Ewald sum's: a mesh operator walks no k-set
-    _workspace_bytes = "pet_ewald_workspace_bytes"
-    _second_entry = ("pet_ewald_second_workspace_bytes", "pet_ewald_second")
-    _second_cell_entry = ("pet_ewald_second_cell_workspace_bytes", "pet_ewald_second_cell")
+    _entry = "pet_ewald"  # the prefix of this mode's entry points
 
     def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5):
         global _warned_kset
@@ -204,9 +202,8 @@ class EwaldHip:
                             "sum has not converged inside the k-set, so the result depends on the SHAPE of the k-set (a "
                             "sphere here, the box of a mesh in torch-pme), which is not pinned")
         self.n_systems = -1
-        self._workspace: Optional[torch.Tensor] = None
-        self._second_workspaces: Dict[int, torch.Tensor] = {}  # by channel count (``second``)
-        self._cell_workspaces: Dict[int, torch.Tensor] = {}  # by channel count (``second_cell``)
+        self._workspace: Optional[torch.Tensor] = None  # first order: one buffer that only grows
+        self._workspaces: Dict[str, Dict[int, torch.Tensor]] = {}  # second order: by size-query name, then by channel count
 
     def __del__(self):
         h = getattr(self, "_handle", None)
@@ -235,8 +232,7 @@ class EwaldHip:
         check(self.lib.pet_ewald_plan(self._handle, h_cells, h_pbc, h_first, n_sys))
         self.n_systems = n_sys
         self._workspace = None
-        self._second_workspaces = {}
-        self._cell_workspaces = {}
+        self._workspaces = {}
         return self
 
     def num_kvectors(self, system: int) -> int:
@@ -246,9 +242,9 @@ class EwaldHip:
         return n
 
     def _ws(self, channels: int, device) -> torch.Tensor:
-        nbytes = int(getattr(self.lib, self._workspace_bytes)(self._handle, channels))
+        nbytes = int(getattr(self.lib, self._entry + "_workspace_bytes")(self._handle, channels))
         if nbytes < 0:
-            raise PetHipError(f"{self._workspace_bytes} failed: call plan() first")
+            raise PetHipError(f"{self._entry}_workspace_bytes failed: call plan() first")
         if self._workspace is None or self._workspace.numel() < nbytes or self._workspace.device != device:
             self._workspace = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device)
         return self._workspace
@@ -287,7 +283,7 @@ class EwaldHip:
         ``<u_charges, dL/dq> + <u_positions, dL/dR>`` with respect to ``(charges, grad_potential, positions)``:
         ``(out_charges [N, C], out_grad_potential [N, C], out_positions [N, 3])``. Either cotangent may be ``None`` (zero; its
         work is skipped), not both. No cell tangent is taken and no cell result returned."""
-        return self._second(graph, positions, charges, grad_potential, u_charges, u_positions, (True, True, True))
+        return self._second_order("second", graph, positions, charges, grad_potential, (u_charges, u_positions), (True, True, True))
 
     def second_cell(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor, grad_potential: torch.Tensor,
                     u_charges: Optional[torch.Tensor] = None, u_positions: Optional[torch.Tensor] = None,
@@ -298,54 +294,45 @@ class EwaldHip:
         Any cotangent may be ``None`` (zero), not all three; rows of ``u_cells`` of open systems are ignored. ``results``: which
         of the two to form (the other comes back ``None``, the one formed has the bits of the full call). The position and
         cell results (mixed and second cell derivatives) are not built."""
-        if u_charges is None and u_positions is None and u_cells is None:
-            raise PetHipError("second_cell: u_charges, u_positions and u_cells are all None")
-        results = tuple(bool(x) for x in results)
-        if len(results) != 2 or not any(results):
-            raise PetHipError("second_cell: results names two flags (out_charges, out_grad_potential), at least one set")
-        rt._require_cuda(*[t for t in (u_charges, u_positions, u_cells) if t is not None])
-        pos, q, g = self._inputs(positions, charges, grad_potential)
-        uq = None if u_charges is None else u_charges.detach().to(torch.float32).reshape(q.shape).contiguous()
-        ur = None if u_positions is None else u_positions.detach().to(torch.float32).reshape(pos.shape).contiguous()
-        uc = None if u_cells is None else u_cells.detach().to(torch.float32).reshape(graph.n_systems, 3, 3).contiguous()
-        C = int(q.shape[1])
-        bytes_name, entry_name = self._second_cell_entry
-        nbytes = int(getattr(self.lib, bytes_name)(self._handle, C))
-        if nbytes < 0:
-            raise PetHipError(f"{bytes_name} failed: call plan() first")
-        ws = self._cell_workspaces.get(C)
-        if ws is None or ws.numel() < nbytes or ws.device != q.device:
-            ws = self._cell_workspaces[C] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=q.device)
-        outs = tuple(torch.empty_like(q) if want else None for want in results)
-        entry = getattr(self.lib, entry_name)
-        self._with_hook(ws, lambda: entry(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), rt._ptr(g), rt._ptr(uq), rt._ptr(ur),
-                                          rt._ptr(uc), C, rt._ptr(outs[0]), rt._ptr(outs[1]), rt._ptr(ws), ws.numel(), rt._stream()))
-        return outs
+        return self._second_order("second_cell", graph, positions, charges, grad_potential, (u_charges, u_positions, u_cells), results)
 
     def _with_hook(self, workspace: Optional[torch.Tensor], call) -> None:
         """``check(call())`` for an entry point that runs on ``workspace``; :class:`P3MHip` serves its transform hook there."""
         check(call())
 
-    def _second(self, graph, positions, charges, grad_potential, u_charges, u_positions, results):
-        if u_charges is None and u_positions is None:
-            raise PetHipError("second: u_charges and u_positions are both None")
-        rt._require_cuda(*[t for t in (u_charges, u_positions) if t is not None])
+    @property
+    def _second_workspaces(self) -> Dict[int, torch.Tensor]:
+        """The workspaces of :meth:`second` by channel count: its part of the one cache."""
+        return self._workspaces.setdefault(self._entry + "_second_workspace_bytes", {})
+
+    def _second_order(self, what: str, graph, positions, charges, grad_potential, cotangents, results):
+        """Behind :meth:`second` (``what = "second"``: two cotangents, three results) and :meth:`second_cell` (three and two): the
+        cotangents as fp32 device rows, the results asked for, the cached workspace of the entry's size query, the call."""
+        cell = what == "second_cell"
+        if all(t is None for t in cotangents):
+            raise PetHipError("second_cell: u_charges, u_positions and u_cells are all None" if cell
+                              else "second: u_charges and u_positions are both None")
+        results = tuple(bool(x) for x in results)
+        if len(results) != (2 if cell else 3) or not any(results):
+            raise PetHipError("second_cell: results names two flags (out_charges, out_grad_potential), at least one set" if cell
+                              else "second: results names three flags (out_charges, out_grad_potential, out_positions), at least one set")
+        rt._require_cuda(*[t for t in cotangents if t is not None])
         pos, q, g = self._inputs(positions, charges, grad_potential)
-        uq = None if u_charges is None else u_charges.detach().to(torch.float32).reshape(q.shape).contiguous()
-        ur = None if u_positions is None else u_positions.detach().to(torch.float32).reshape(pos.shape).contiguous()
+        shapes = (q.shape, pos.shape, (graph.n_systems, 3, 3))
+        us = [None if t is None else t.detach().to(torch.float32).reshape(shape).contiguous() for t, shape in zip(cotangents, shapes)]
         C = int(q.shape[1])
-        bytes_name, entry_name = self._second_entry
-        nbytes = int(getattr(self.lib, bytes_name)(self._handle, C))
+        entry_name = f"{self._entry}_{what}"
+        nbytes = int(getattr(self.lib, entry_name + "_workspace_bytes")(self._handle, C))
         if nbytes < 0:
-            raise PetHipError(f"{bytes_name} failed: call plan() first")
-        ws = self._second_workspaces.get(C)
+            raise PetHipError(f"{entry_name}_workspace_bytes failed: call plan() first")
+        cache = self._workspaces.setdefault(entry_name + "_workspace_bytes", {})
+        ws = cache.get(C)
         if ws is None or ws.numel() < nbytes or ws.device != q.device:
-            ws = self._second_workspaces[C] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=q.device)
+            ws = cache[C] = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=q.device)
         outs = tuple(torch.empty_like(t) if want else None for t, want in zip((q, q, pos), results))
         entry = getattr(self.lib, entry_name)
-        self._with_hook(ws, lambda: entry(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), rt._ptr(g), rt._ptr(uq), rt._ptr(ur),
-                                          C, rt._ptr(outs[0]), rt._ptr(outs[1]), rt._ptr(outs[2]), rt._ptr(ws), ws.numel(),
-                                          rt._stream()))
+        self._with_hook(ws, lambda: entry(self._handle, graph.handle, rt._ptr(pos), rt._ptr(q), rt._ptr(g), *[rt._ptr(u) for u in us],
+                                          C, *[rt._ptr(t) for t in outs], rt._ptr(ws), ws.numel(), rt._stream()))
         return outs
 
 
@@ -361,9 +348,7 @@ class P3MHip(EwaldHip):
     long-range training sweep and Hessian-vector product. Without it all of those raise as before."""
 
     _warns_kset = False
-    _workspace_bytes = "pet_p3m_workspace_bytes"
-    _second_entry = ("pet_p3m_second_workspace_bytes", "pet_p3m_second")
-    _second_cell_entry = ("pet_p3m_second_cell_workspace_bytes", "pet_p3m_second_cell")
+    _entry = "pet_p3m"
 
     def __init__(self, smearing: float = 1.4, kspace_resolution: float = 1.33, cutoff: float = 4.5, interpolation_nodes: int = 5,
                  second_order: bool = False):
@@ -463,10 +448,7 @@ class P3MHip(EwaldHip):
                               "(P3MHip(..., second_order=True), LongRangeFeaturizerHip(..., method='p3m', second_order=True)) "
                               "installs the transform hook they need and trains through the mesh operator; method='ewald' "
                               "trains by Ewald summation")
-        results = tuple(bool(x) for x in results)
-        if len(results) != 3 or not any(results):
-            raise PetHipError("second: results names three flags (out_charges, out_grad_potential, out_positions), at least one set")
-        return self._second(graph, positions, charges, grad_potential, u_charges, u_positions, results)
+        return self._second_order("second", graph, positions, charges, grad_potential, (u_charges, u_positions), results)
 
     def second_cell(self, graph: rt.HipGraph, positions: torch.Tensor, charges: torch.Tensor, grad_potential: torch.Tensor,
                     u_charges: Optional[torch.Tensor] = None, u_positions: Optional[torch.Tensor] = None,
@@ -813,7 +795,8 @@ class LongRangeForward:
     def _sweep(self, lam, nu, u, want_tangent, u_cell=None):
         self._plan()
         g, dev = self.graph, self.graph.workspace.device
-        bytes_name = "pet_train2_long_range_workspace_bytes" if u_cell is None else "pet_train2_long_range_cell_workspace_bytes"
+        cell = "" if u_cell is None else "_cell"  # the entry with a cell tangent has one argument more
+        bytes_name = f"pet_train2_long_range{cell}_workspace_bytes"
         need = int(getattr(self.lib, bytes_name)(self.model.handle, g.handle, self.featurizer.ewald.handle))
         if need < 0:
             raise PetHipError(self.lib.pet_last_error().decode(errors="replace") or f"{bytes_name} failed")
@@ -824,15 +807,10 @@ class LongRangeForward:
         pos = g._pos.detach().to(torch.float32).contiguous()
         tan = torch.empty(g.n_nodes, dtype=torch.float32, device=dev) if want_tangent else None
         op, ws = self.featurizer.ewald, self.workspace2
-        if u_cell is not None:
-            uc = f32(u_cell).reshape(g.n_systems, 3, 3)
-            op._with_hook(ws, lambda: self.lib.pet_backward_train2_long_range_cell(
-                self.model.handle, g.handle, op.handle, rt._ptr(pos), rt._ptr(ws), ws.numel(), rt._ptr(lam), rt._ptr(nu),
-                rt._ptr(u), rt._ptr(uc), rt._ptr(tan), rt._stream()))
-            return tan
-        op._with_hook(ws, lambda: self.lib.pet_backward_train2_long_range(
-            self.model.handle, g.handle, op.handle, rt._ptr(pos), rt._ptr(ws), ws.numel(), rt._ptr(lam), rt._ptr(nu), rt._ptr(u),
-            rt._ptr(tan), rt._stream()))
+        uc = () if u_cell is None else (rt._ptr(f32(u_cell).reshape(g.n_systems, 3, 3)),)
+        entry = getattr(self.lib, f"pet_backward_train2_long_range{cell}")
+        op._with_hook(ws, lambda: entry(self.model.handle, g.handle, op.handle, rt._ptr(pos), rt._ptr(ws), ws.numel(), rt._ptr(lam),
+                                        rt._ptr(nu), rt._ptr(u), *uc, rt._ptr(tan), rt._stream()))
         return tan
 
     def backward_train(self, grad_atomic: Optional[torch.Tensor], want_position_grad: bool = False, want_cell_grad: bool = False,

@@ -8,6 +8,7 @@
 
 #include "../../include/pet_hip.h"
 #include "pet_plan.h"
+#include "soap_plan.h"
 
 namespace pet {
 
@@ -84,8 +85,8 @@ struct FwdRecord {
     const void* ws = nullptr;
     bool generic = false;
     int save = -1;              // the forward's save level (0 = nothing kept for an adjoint: pet_backward must refuse)
-    bool soap_packed = false;   // SOAP-BPNN: the feature buffer holds the packed power spectrum (upper triangles only)
     StagePlan plan;             // tuned path only (a record of another path has no layers)
+    SoapPlan soap_plan;         // SOAP-BPNN (soap_plan.h): the feature layout its forward stored, whether it bucketed the atoms
 };
 
 constexpr int GRID_MAX_PROBES = 64;  // adaptive_cutoff_method = "grid": probe cutoffs 0.5, 0.5 + w/4, .. < cutoff

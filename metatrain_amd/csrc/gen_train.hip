@@ -1053,7 +1053,7 @@ static int lr_reverse(TOps& t, const LrStage& lr, const Lin* L, const float* u, 
 }  // namespace
 
 // (nu_x, lambda_x) = adjoint of (y, y') = norm(x, x') on rows of any width (k_gt_norm_rev) for another caller: the
-// SOAP-BPNN training pass of legacy = False models takes its LayerNorm adjoints here (soap_train.h)
+// SOAP-BPNN training pass of legacy = False models takes its LayerNorm adjoints here (soap_train.hip)
 int norm_rev_rows(const float* Xp, const float* Xt, const float* gamma, int ln, float eps, const float* NYp, const float* NYt,
                   float* NXp, float* NXt, int64_t R, int W, hipStream_t st) {
     if (R <= 0) return PET_OK;

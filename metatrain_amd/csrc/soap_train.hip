@@ -1,6 +1,6 @@
 // SOAP-BPNN training step (reference loop body soap_bpnn/trainer.py:344-391:
 // zero_grad -> evaluate_model(is_training=True) -> MSE(E/atom) + MSE(dE/dR) -> loss.backward() -> Adam).
-// Included by soap.hip inside namespace pet (same translation unit: the kernels below reuse its per-pair building blocks).
+// A translation unit of its own: the kernels below reuse the per-pair building blocks of soap.h.
 //
 // What the reference obtains from autograd's double backward is computed here as FORWARD-OVER-REVERSE, like the PET
 // training pass (so.hip): with u = dL_F/d(dE/dR) and v'_p = u_j - u_i the tangent of every edge vector,
@@ -16,7 +16,11 @@
 // parameter of the default (legacy = True) model -- and, for legacy = False models, the centre encoding and the
 // Alchemical species embedding, which sit in FRONT of the tail: J is carried back through LayerNorm, the encoding, the
 // power spectrum and the expansion (k_soap_ybar ... k_soap_embed_reduce below).
-#pragma once
+#include <algorithm>
+
+#include "soap.h"
+
+namespace pet {
 
 // ---------------------------------------------------------------------------------------------
 // tangent sweep through the descriptor
@@ -661,12 +665,18 @@ static void carve_soap_train(const SoapModel& m, int64_t N, int64_t E, void* bas
     w.bytes = c.off;
 }
 
+int64_t soap_train_ws_bytes(const SoapModel& m, int64_t n_nodes, int64_t n_edges) {
+    SoapTrainWs w;
+    carve_soap_train(m, n_nodes, n_edges, nullptr, w);
+    return (int64_t)w.bytes;
+}
+
 static bool soap_trainable_key(const SoapModel& m, const std::string& key) {
     if (!m.d.legacy && (key == "species_embedding.weight" || key == "center_encoding.weight")) return true;
     return key.rfind("layernorm.", 0) == 0 || key.rfind("bpnn.", 0) == 0 || key.rfind("last_layers.", 0) == 0;
 }
 
-static int soap_zero_grad(SoapModel& m, hipStream_t st) {
+int soap_zero_grad(SoapModel& m, hipStream_t st) {
     for (auto& kv : m.raw) {
         if (!soap_trainable_key(m, kv.first)) continue;
         auto it = m.grad.find(kv.first);
@@ -689,8 +699,8 @@ static int soap_zero_grad(SoapModel& m, hipStream_t st) {
 
 // Parameter gradients of  J = sum_i gA_i e_i + <u, dE/dR>  ADDED to the slots; tangent_atomic [N] = e'_i (sum = <u, dE/dR>).
 // `ws` is the workspace soap_forward ran on (spherical expansion and power spectrum are read from it).
-static int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_bytes, void* tws, int64_t tws_bytes,
-                            const float* gA, const float* u, float* tangent_atomic, hipStream_t st) {
+int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_bytes, void* tws, int64_t tws_bytes, const float* gA,
+                     const float* u, float* tangent_atomic, hipStream_t st) {
     const SoapDims& d = m.d;
     PET_REQUIRE(d.legacy || d.ns * d.C <= 256, PET_ERR_UNSUPPORTED, "more than 64 species with the Alchemical embedding");
     PET_REQUIRE(d.H <= MAXH && d.NH <= MAXNH, PET_ERR_UNSUPPORTED, "tail size outside the compiled limits");
@@ -706,12 +716,13 @@ static int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_b
     const int N = (int)g.n_nodes;
     if (N == 0) return PET_OK;
     Graph::FwdRecord* rec = g.fwd_record(ws);
-    PET_REQUIRE(rec, PET_ERR_ARGUMENT, SOAP_NO_FORWARD);
-    if (rec->soap_packed) {  // the inference forward stored the packed power spectrum: this pass reads the full layout,
+    SoapTrainPlan plan;
+    PET_TRY(soap_plan_train(m, rec, plan));
+    if (plan.rebuild_full) {  // the inference forward stored the packed power spectrum: this pass reads the full layout,
         // rebuilt from the expansion coefficients the same forward left in the workspace (the LayerNorm statistics stay)
-        allow_big_lds(k_soap_ps_m<false>, (size_t)4 * d.NCOEF * 4);
-        k_soap_ps_m<false><<<cdiv(N, 4), 256, (size_t)4 * d.NCOEF * 4, st>>>(d, w.Cf, g.sp, m.enc, w.feats, w.tail, N);
-        rec->soap_packed = false;
+        soap_ps_full(m, g, w, st);
+        rec->soap_plan.packed = false;
+        rec->soap_plan.ps = SoapPlan::PowerSpectrum::Mfma;
     }
     const bool tangent = u != nullptr && g.n_edges > 0;
     if (!tangent && !d.legacy) {   // the front-of-the-tail pass reads the tangents: zeros for an energy-only loss
@@ -731,13 +742,10 @@ static int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_b
     const float* xd = tangent ? t.xd : nullptr;
     const float seed_t = tangent ? 1.f : 0.f;
     k_soap_tail_train<<<N, 256, 0, st>>>(d, w.feats, xd, g.sp, m.sets, gA, seed_t, t.pack, tangent_atomic);
-    // atoms bucketed by network (the forward's own bucketing exists only on its MFMA path, for at most SP_MAXSETS networks):
+    // atoms bucketed by network (the forward's own bucketing exists only on its sorted path, for at most SP_MAXSETS networks):
     // the forward's 8-network table where it suffices, the 16-network one above
     const int* offs = nullptr;
-    if (int rc = m.n_sets <= SP_MAXSETS
-                     ? sp_bucket<SP_MAXSETS>(g.sp, d.legacy, N, m.n_sets, t.info, t.perm, &offs, st)
-                     : sp_bucket<SP_TRAIN_MAXSETS>(g.sp, d.legacy, N, m.n_sets, t.info, t.perm, &offs, st))
-        return rc;
+    PET_TRY(soap_bucket(plan.wide_table, g.sp, d.legacy, N, m.n_sets, t.info, t.perm, &offs, st));
     k_soap_wgrad1<<<dim3(cdiv(d.S, 64), m.n_sets, t.n_chunks), 64, 0, st>>>(d, w.feats, xd, t.perm, offs, m.sets, t.pack,
                                                                           t.n_chunks, t.part);
     for (int s = 0; s < m.n_sets; s++) {
@@ -785,7 +793,7 @@ static int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_b
     return PET_OK;
 }
 
-static int soap_adam(SoapModel& m, float lr, float b1, float b2, float eps, int64_t step, hipStream_t st) {
+int soap_adam(SoapModel& m, float lr, float b1, float b2, float eps, int64_t step, hipStream_t st) {
     PET_REQUIRE(!m.grad.empty(), PET_ERR_ARGUMENT, "soap_model_zero_grad has not been called");
     PET_REQUIRE(step >= 1, PET_ERR_ARGUMENT, "Adam steps are counted from 1");
     const float c1 = 1.f - powf(b1, (float)step), c2 = 1.f - powf(b2, (float)step);
@@ -798,3 +806,5 @@ static int soap_adam(SoapModel& m, float lr, float b1, float b2, float eps, int6
     PET_HIP_CHECK(hipGetLastError());
     return soap_finalize(m, st);   // re-derive the packed / folded forms the forward kernels read
 }
+
+}  // namespace pet

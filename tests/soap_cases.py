@@ -1,4 +1,5 @@
-"""Inputs that drive the SOAP-BPNN pass (``metatrain_amd/csrc/soap.hip``, ``soap_train.h``) into the kernels and branches its
+"""Inputs that drive the SOAP-BPNN pass (``metatrain_amd/csrc/soap.hip`` and its stage files ``soap_expand.hip``, ``soap_ps.hip``,
+``soap_tail.hip``, ``soap_train.hip``; the plan is ``soap_plan.h``) into the kernels and branches its
 host code selects by the model's dimensions and by the batch (DESIGN.md "SOAP-BPNN dispatch and its edge cases"), which the one
 input shape of ``test_gpu_soap.py`` -- a cubic four-type box at 0.05 atoms / A^3 -- never reaches. Shared by
 ``test_soap_cases_cpu.py`` (the premises: each case is what it says) and ``test_gpu_soap_edges.py`` (the device against the fp64

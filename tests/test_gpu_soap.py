@@ -363,7 +363,7 @@ def test_power_spectrum_features_against_the_reference_module(legacy):
 def test_packed_power_spectrum_layout_against_the_full_layout_and_the_oracle(layernorm, layers):
     """Round 6: p_l[a][b] = p_l[b][a], so an inference step of the legacy (per-species networks) model stores the upper
     triangle of every l block only (2 360 floats per atom instead of 4 544), with the LayerNorm statistics weighted and the
-    first Linear folded accordingly (``soap.hip k_soap_prep_wallp``). Per-atom energies and dE/dR -- incl. dE/dcell -- against
+    first Linear folded accordingly (``soap_tail.hip k_soap_prep_wallp``). Per-atom energies and dE/dR -- incl. dE/dcell -- against
     the fp64 oracle at the 1e-5 bar and against the full layout (``pet_config_set("soap_packed", 0)``); seed linearity of the
     packed adjoint; an Alchemical model (per-feature centre encoding) keeps the full layout and is unaffected by the switch."""
     from metatrain_amd import runtime as rt

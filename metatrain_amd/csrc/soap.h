@@ -2,7 +2,7 @@
 // building blocks (spherical harmonics, radial splines, cutoff) and block reductions that more than one file uses, and the
 // host entry points of each file. soap.hip has the model, the plan (soap_plan.h) and the two drivers; soap_expand.hip,
 // soap_ps.hip and soap_tail.hip one stage each, both generations and the adjoints, with the stage's launchers;
-// soap_train.hip the training pass.
+// soap_train.hip the training pass; soap_hvp.hip the Hessian-vector product.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -59,6 +59,7 @@ struct SoapModel {
     std::map<std::string, float*> adam_m, adam_v;
     std::vector<void*> owned;
     float* table = nullptr;      // [n_grid][F][2]
+    float* curv = nullptr;       // [n_grid][F][2] curvature slopes of the radial spline (radial_two), or null: no second order
     float* shnorm = nullptr;     // [(L+1)*(L+1)] normalisation (sqrt 2 folded in for m > 0)
     int* coef_lut = nullptr;     // [NCOEF] lm | rn << 8 | a << 16
     int* item_lut = nullptr;     // [ITEMS] lm | rn << 8 | base << 16
@@ -174,6 +175,101 @@ __device__ __forceinline__ float shifted_cosine(float r, float rc, float w, floa
     return 0.5f * (1.0f + cosf(3.14159274f * s));
 }
 
+// ---------------------------------------------------------------------------------------------
+// second-order forms (soap_hvp.hip): the same blocks with their derivative along a direction v' of the pair vector
+// ---------------------------------------------------------------------------------------------
+// sh_chain in forward mode along v': besides Y and G = grad Y (w.r.t. the pair vector v, through u = v / r) it returns
+// Y' = G . v' and G' = (grad grad Y) v', the derivative of G along v' -- three tangent components per lm, never the 3 x 3
+// Hessian of Y. (xd, yd, zd) = u' = (v' - u (u . v')) / r and ird = (1 / r)' = -(u . v') / r^2 are the tangents of the
+// chain's inputs; every recurrence of sh_chain is carried as a (value, tangent) pair, and the polynomial Q_l^m gets its
+// second z derivative by differentiating the recurrence once more. r = 0: ir = 0 and all tangents 0 (the caller's guard).
+__device__ __forceinline__ void sh_chain2(float x, float y, float z, float xd, float yd, float zd, int m, int L,
+                                          const float* __restrict__ shn, float* Y, float* Yd, float* Gx, float* Gy,
+                                          float* Gz, float* Gxd, float* Gyd, float* Gzd, float ir, float ird) {
+    float cm = 1.f, sm = 0.f, cp = 1.f, sp_ = 0.f;      // (c_m, s_m) and (c_{m-1}, s_{m-1})
+    float cmd = 0.f, smd = 0.f, cpd = 0.f, spd = 0.f;   // their tangents
+    float qmm = 1.f;
+    for (int k = 1; k <= m; k++) {
+        cp = cm; sp_ = sm; cpd = cmd; spd = smd;
+        cm = x * cp - y * sp_;
+        sm = x * sp_ + y * cp;
+        cmd = xd * cp + x * cpd - yd * sp_ - y * spd;
+        smd = xd * sp_ + x * spd + yd * cp + y * cpd;
+        qmm *= -(2 * k - 1);
+    }
+    float q2 = 0.f, dq2 = 0.f, ddq2 = 0.f, q1 = qmm, dq1 = 0.f, ddq1 = 0.f;
+    for (int l = m; l <= L; l++) {
+        float q, dq, ddq;
+        if (l == m) { q = qmm; dq = 0.f; ddq = 0.f; }
+        else if (l == m + 1) { q = (2 * m + 1) * z * q1; dq = (2 * m + 1) * q1; ddq = 0.f; }
+        else {
+            const float inv = 1.0f / (l - m);
+            q = ((2 * l - 1) * z * q1 - (l + m - 1) * q2) * inv;
+            dq = ((2 * l - 1) * (q1 + z * dq1) - (l + m - 1) * dq2) * inv;
+            ddq = ((2 * l - 1) * (2.f * dq1 + z * ddq1) - (l + m - 1) * ddq2) * inv;
+        }
+        const float qt = dq * zd, dqt = ddq * zd;   // tangents of q and dq: both depend on z alone
+        const float f = shn[l * (L + 1) + m];
+        const int ip = l * l + l + m, im = l * l + l - m;
+        float yv[2], gx[2], gy[2], gz[2], yt[2], gxt[2], gyt[2], gzt[2];
+        if (m == 0) {
+            yv[0] = f * q; gx[0] = 0.f; gy[0] = 0.f; gz[0] = f * dq;
+            yt[0] = f * qt; gxt[0] = 0.f; gyt[0] = 0.f; gzt[0] = f * dqt;
+        } else {
+            const float fm = f * q * m, fmt = f * qt * m;
+            yv[0] = f * q * cm; gx[0] = fm * cp;  gy[0] = -fm * sp_; gz[0] = f * dq * cm;
+            yv[1] = f * q * sm; gx[1] = fm * sp_; gy[1] = fm * cp;   gz[1] = f * dq * sm;
+            yt[0] = f * (qt * cm + q * cmd); gxt[0] = fmt * cp + fm * cpd;  gyt[0] = -(fmt * sp_ + fm * spd);
+            yt[1] = f * (qt * sm + q * smd); gxt[1] = fmt * sp_ + fm * spd; gyt[1] = fmt * cp + fm * cpd;
+            gzt[0] = f * (dqt * cm + dq * cmd);
+            gzt[1] = f * (dqt * sm + dq * smd);
+        }
+        for (int k = 0; k < (m == 0 ? 1 : 2); k++) {
+            const int idx = k == 0 ? ip : im;
+            Y[idx] = yv[k];
+            Yd[idx] = yt[k];
+            // G = (g - u (u . g)) / r and its tangent
+            const float dot = x * gx[k] + y * gy[k] + z * gz[k];
+            const float dott = xd * gx[k] + yd * gy[k] + zd * gz[k] + x * gxt[k] + y * gyt[k] + z * gzt[k];
+            const float px = gx[k] - x * dot, py = gy[k] - y * dot, pz = gz[k] - z * dot;
+            Gx[idx] = px * ir; Gy[idx] = py * ir; Gz[idx] = pz * ir;
+            Gxd[idx] = (gxt[k] - xd * dot - x * dott) * ir + px * ird;
+            Gyd[idx] = (gyt[k] - yd * dot - y * dott) * ir + py * ird;
+            Gzd[idx] = (gzt[k] - zd * dot - z * dott) * ir + pz * ird;
+        }
+        if (l > m) { q2 = q1; dq2 = dq1; ddq2 = ddq1; }
+        q1 = q; dq1 = dq; ddq1 = ddq;
+        if (l == m) { q2 = 0.f; dq2 = 0.f; ddq2 = 0.f; }
+    }
+}
+
+// second derivative of the cutoff factor: fc'' = -(pi^2 / 2 w^2) cos(pi s) inside the taper, 0 outside
+__device__ __forceinline__ float shifted_cosine_dd(float r, float rc, float w) {
+    const float s = (r - (rc - w)) / w;
+    if (r >= rc || s <= 0.f) return 0.f;
+    return -0.5f * 3.14159274f * 3.14159274f * cosf(3.14159274f * s) / (w * w);
+}
+
+// radial_one to second order: R fc, (R fc)' and (R fc)'' = p'' fc + 2 p' fc' + p fc''. p and p' are radial_one's own
+// arithmetic (fc = 1, fc' = 0 hands them out unscaled); p''(s) = (4 - 6 s) d0 + (6 s - 2) d1 is the exact derivative of that
+// p', with the interval's curvature slopes d0 = (chord - m_k) / h, d1 = (m_{k+1} - chord) / h from the second table
+// [n_grid][F][2], which the host forms in fp64 (radial.curvature_table: formed from the fp32 table they would be rounding
+// noise divided by h twice).
+__device__ __forceinline__ void radial_two(const SoapDims& d, const float* __restrict__ table, const float* __restrict__ curv,
+                                           int f, float r, float fc, float dfc, float ddfc, float* R, float* dR, float* ddR) {
+    float p, dp;
+    radial_one(d, table, f, r, 1.f, 0.f, &p, &dp);
+    const float t = r * d.inv_h;
+    int k = (int)t;
+    if (k > d.n_grid - 2) k = d.n_grid - 2;
+    const float s = t - k;
+    const float2 c = reinterpret_cast<const float2*>(curv)[(size_t)k * d.F + f];
+    const float ddp = (4.f - 6.f * s) * c.x + (6.f * s - 2.f) * c.y;
+    *R = p * fc;
+    *dR = dp * fc + p * dfc;
+    *ddR = ddp * fc + 2.f * dp * dfc + p * ddfc;
+}
+
 constexpr int MAXK = 12;  // coefficients per thread (NCOEF <= 256 * MAXK)
 constexpr int MAXI = 8;   // (lm, n) items per lane of the wave expansion (ITEMS <= 64 * MAXI)
 
@@ -262,7 +358,31 @@ int soap_finalize(SoapModel& m, hipStream_t st);
 int64_t soap_train_ws_bytes(const SoapModel& m, int64_t n_nodes, int64_t n_edges);
 int soap_zero_grad(SoapModel& m, hipStream_t st);
 int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_bytes, void* tws, int64_t tws_bytes, const float* gA,
-                     const float* u, float* tangent_atomic, hipStream_t st);
+                     const float* u, const float* ucell, float* tangent_atomic, hipStream_t st);
 int soap_adam(SoapModel& m, float lr, float b1, float b2, float eps, int64_t step, hipStream_t st);
+// kernels of the training pass that the Hessian-vector product launches too (the same sweep with gA = 0, carried on to the pairs)
+__global__ void k_edge_tangent(const float* __restrict__ u, const int* __restrict__ ctr, const int* __restrict__ nbr,
+                               const int* __restrict__ shift, const int* __restrict__ sys, const float* __restrict__ ucell,
+                               float4* __restrict__ vd, int64_t E);
+__global__ __launch_bounds__(256) void k_soap_expand_jvp(SoapDims d, const float4* __restrict__ geo, const float4* __restrict__ vdot,
+                                  const int* __restrict__ rowptr, const int* __restrict__ sp_nbr,
+                                  const float* __restrict__ table, const float* __restrict__ shn,
+                                  const int* __restrict__ lut, const float* __restrict__ spw, float* __restrict__ Cd);
+__global__ __launch_bounds__(256) void k_soap_ps_jvp(SoapDims d, const float* __restrict__ Cf, const float* __restrict__ Cd,
+                              const int* __restrict__ sp, const float* __restrict__ enc, const int2* __restrict__ flut,
+                              float* __restrict__ xd);
+__host__ __device__ inline int soap_pack_size(int H, int NH) { return 4 + 4 * H * NH; }
+__global__ __launch_bounds__(256) void k_soap_tail_train(SoapDims d, const float* __restrict__ feats, const float* __restrict__ xd /* may be null */,
+                                  const int* __restrict__ sp, const SoapSet* __restrict__ sets,
+                                  const float* __restrict__ gA /* null: zeros */, float seed_tangent,
+                                  float* __restrict__ pack, float* __restrict__ edot);
+__global__ __launch_bounds__(256) void k_soap_ps_rev2(SoapDims d, const float* __restrict__ Cf, const float* __restrict__ Cd,
+                               const float* __restrict__ NP, const float* __restrict__ LP, float* __restrict__ NC,
+                               float* __restrict__ LC);
+
+// soap_hvp.hip
+int64_t soap_hvp_ws_bytes(const SoapModel& m, int64_t n_nodes, int64_t n_edges);
+int soap_hvp(const SoapModel& m, const Graph& g, void* ws, int64_t ws_bytes, void* hws, int64_t hws_bytes, const float* u,
+             const float* ucell, float* hvp_pos, float* hvp_cell, float* tangent_atomic, hipStream_t st);
 
 }  // namespace pet

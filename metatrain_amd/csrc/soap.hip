@@ -6,7 +6,8 @@
 //   e_i = w3 . silu(W2 silu(W1 LN(ps_i * enc[s_i])))                           model.py:553-595, 1204-1219
 //
 // This file: the model (soap_finalize), the plan (soap_plan.h: which kernel serves each stage), the two drivers and the
-// extern "C" entries. The stages and their launchers: soap_expand.hip, soap_ps.hip, soap_tail.hip; training: soap_train.hip.
+// extern "C" entries. The stages and their launchers: soap_expand.hip, soap_ps.hip, soap_tail.hip; training: soap_train.hip;
+// Hessian-vector product: soap_hvp.hip.
 #include "soap.h"
 
 namespace pet {
@@ -348,7 +349,21 @@ int soap_model_set_radial_table(soap_model_t* sm, const float* d_table, int32_t 
     PET_HIP_CHECK(hipMemcpyAsync(m.table, d_table, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     m.d.n_grid = n_grid;
     m.d.inv_h = (float)(n_grid - 1) / m.d.rc;
+    m.curv = nullptr;  // the curvature slopes belong to the table they were formed from
     m.finalized = false;
+    return PET_OK;
+}
+
+int soap_model_set_radial_curvature(soap_model_t* sm, const float* d_table, int32_t n_grid, void* stream) {
+    PET_REQUIRE(sm && d_table, PET_ERR_ARGUMENT, "bad argument");
+    SoapModel& m = sm->m;
+    PET_REQUIRE(m.table != nullptr && n_grid == m.d.n_grid, PET_ERR_ARGUMENT,
+                "the curvature table follows soap_model_set_radial_table, on the same grid");
+    const size_t bytes = (size_t)n_grid * m.d.F * 2 * sizeof(float);
+    m.curv = nullptr;
+    int rc = salloc(m, (void**)&m.curv, bytes);
+    if (rc) return rc;
+    PET_HIP_CHECK(hipMemcpyAsync(m.curv, d_table, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PET_OK;
 }
 
@@ -410,15 +425,38 @@ int64_t soap_train_workspace_bytes(const soap_model_t* sm, int64_t n_nodes, int6
     return soap_train_ws_bytes(sm->m, n_nodes, n_edges);
 }
 
-int soap_train_gradients(soap_model_t* sm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
-                         void* d_train_workspace, int64_t train_workspace_bytes, const float* d_grad_atomic,
-                         const float* d_u, float* d_tangent_atomic, void* stream) {
+int soap_train_gradients_cell(soap_model_t* sm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
+                              void* d_train_workspace, int64_t train_workspace_bytes, const float* d_grad_atomic,
+                              const float* d_u, const float* d_u_cell, float* d_tangent_atomic, void* stream) {
     PET_REQUIRE(sm && pg, PET_ERR_ARGUMENT, "null argument");
     PET_REQUIRE(sm->m.finalized, PET_ERR_ARGUMENT, "soap_model_finalize has not been called");
     if (pg->g.n_nodes == 0) return PET_OK;
     PET_REQUIRE(d_workspace && d_train_workspace && d_grad_atomic && d_tangent_atomic, PET_ERR_ARGUMENT, "null argument");
     return soap_train_grads(sm->m, pg->g, d_workspace, workspace_bytes, d_train_workspace, train_workspace_bytes,
-                            d_grad_atomic, d_u, d_tangent_atomic, (hipStream_t)stream);
+                            d_grad_atomic, d_u, d_u_cell, d_tangent_atomic, (hipStream_t)stream);
+}
+
+int soap_train_gradients(soap_model_t* sm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
+                         void* d_train_workspace, int64_t train_workspace_bytes, const float* d_grad_atomic,
+                         const float* d_u, float* d_tangent_atomic, void* stream) {
+    return soap_train_gradients_cell(sm, pg, d_workspace, workspace_bytes, d_train_workspace, train_workspace_bytes,
+                                     d_grad_atomic, d_u, nullptr, d_tangent_atomic, stream);
+}
+
+int64_t soap_hvp_workspace_bytes(const soap_model_t* sm, int64_t n_nodes, int64_t n_edges) {
+    if (!sm) return -1;
+    return soap_hvp_ws_bytes(sm->m, n_nodes, n_edges);
+}
+
+int soap_hessian_vector(const soap_model_t* sm, const pet_graph_t* pg, void* d_workspace, int64_t workspace_bytes,
+                        void* d_hvp_workspace, int64_t hvp_workspace_bytes, const float* d_u, const float* d_u_cell,
+                        float* d_hvp_positions, float* d_hvp_cells, float* d_tangent_atomic, void* stream) {
+    PET_REQUIRE(sm && pg, PET_ERR_ARGUMENT, "null argument");
+    PET_REQUIRE(sm->m.finalized, PET_ERR_ARGUMENT, "soap_model_finalize has not been called");
+    if (pg->g.n_nodes == 0) return PET_OK;
+    PET_REQUIRE(d_workspace && d_hvp_workspace && d_u && d_hvp_positions, PET_ERR_ARGUMENT, "null argument");
+    return soap_hvp(sm->m, pg->g, d_workspace, workspace_bytes, d_hvp_workspace, hvp_workspace_bytes, d_u, d_u_cell,
+                    d_hvp_positions, d_hvp_cells, d_tangent_atomic, (hipStream_t)stream);
 }
 
 static int soap_copy_out(const std::map<std::string, std::pair<float*, int64_t>>& table, const char* key, float* d_out,

@@ -25,12 +25,23 @@ namespace pet {
 // ---------------------------------------------------------------------------------------------
 // tangent sweep through the descriptor
 // ---------------------------------------------------------------------------------------------
+// v'_p = u_j - u_i (+ shift_p . u_cell[system], the cell tangent of the stress term and of the Hessian-vector product:
+// v = r_j - r_i + S cell, as k_gt_geo in gen_train.hip; ucell null: the arithmetic of the force-only pass, unchanged)
 __global__ void k_edge_tangent(const float* __restrict__ u, const int* __restrict__ ctr, const int* __restrict__ nbr,
+                               const int* __restrict__ shift, const int* __restrict__ sys, const float* __restrict__ ucell,
                                float4* __restrict__ vd, int64_t E) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= E) return;
     const int i = ctr[p], j = nbr[p];
-    vd[p] = make_float4(u[3 * j] - u[3 * i], u[3 * j + 1] - u[3 * i + 1], u[3 * j + 2] - u[3 * i + 2], 0.f);
+    float vx = u[3 * j] - u[3 * i], vy = u[3 * j + 1] - u[3 * i + 1], vz = u[3 * j + 2] - u[3 * i + 2];
+    if (ucell) {
+        const float* c = ucell + 9 * (int64_t)sys[i];
+        const float sa = (float)shift[3 * p], sb = (float)shift[3 * p + 1], sc = (float)shift[3 * p + 2];
+        vx += sa * c[0] + sb * c[3] + sc * c[6];
+        vy += sa * c[1] + sb * c[4] + sc * c[7];
+        vz += sa * c[2] + sb * c[5] + sc * c[8];
+    }
+    vd[p] = make_float4(vx, vy, vz, 0.f);
 }
 
 // C'_i[lm n a] = sum_p (Y'_lm R_n + Y_lm R'_n)(p) w_a(species of the neighbour), Y' = grad Y . v', R' = d(R fc)/dr (u . v').
@@ -154,8 +165,7 @@ __device__ __forceinline__ double block_sum_d(double v, double* red /*[4]*/) {
 }
 
 // pack[i] = {mu, rstd, mu', m = mean(xhat c'),  then per hidden layer k: abar_k[H], adbar_k[H], h_k[H], h'_k[H]}
-__host__ __device__ inline int soap_pack_size(int H, int NH) { return 4 + 4 * H * NH; }
-
+// (soap_pack_size: soap.h)
 __global__ __launch_bounds__(256) void k_soap_tail_train(SoapDims d, const float* __restrict__ feats,
                                                          const float* __restrict__ xd /* may be null */,
                                                          const int* __restrict__ sp, const SoapSet* __restrict__ sets,
@@ -248,7 +258,7 @@ __global__ __launch_bounds__(256) void k_soap_tail_train(SoapDims d, const float
         edot[i] = e1;
         pk[0] = mu; pk[1] = rstd; pk[2] = mud; pk[3] = mm;
     }
-    const float eb = gA[i], edb = seed_tangent;
+    const float eb = gA ? gA[i] : 0.f, edb = seed_tangent;
     if (j < H) { hbar[j] = eb * W.w3[j]; hbar[MAXH + j] = edb * W.w3[j]; }
     __builtin_amdgcn_wave_barrier();
     for (int k = NH - 1; k >= 0; k--) {
@@ -697,16 +707,19 @@ int soap_zero_grad(SoapModel& m, hipStream_t st) {
     return PET_OK;
 }
 
-// Parameter gradients of  J = sum_i gA_i e_i + <u, dE/dR>  ADDED to the slots; tangent_atomic [N] = e'_i (sum = <u, dE/dR>).
+// Parameter gradients of  J = sum_i gA_i e_i + <u, dE/dR> + <ucell, dE/dcell>  ADDED to the slots; tangent_atomic [N] = e'_i
+// (sum = <u, dE/dR> + <ucell, dE/dcell>). ucell (null: none) needs u: the stress seeds travel with the force seeds.
 // `ws` is the workspace soap_forward ran on (spherical expansion and power spectrum are read from it).
 int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_bytes, void* tws, int64_t tws_bytes, const float* gA,
-                     const float* u, float* tangent_atomic, hipStream_t st) {
+                     const float* u, const float* ucell, float* tangent_atomic, hipStream_t st) {
     const SoapDims& d = m.d;
     PET_REQUIRE(d.legacy || d.ns * d.C <= 256, PET_ERR_UNSUPPORTED, "more than 64 species with the Alchemical embedding");
     PET_REQUIRE(d.H <= MAXH && d.NH <= MAXNH, PET_ERR_UNSUPPORTED, "tail size outside the compiled limits");
     PET_REQUIRE(m.n_sets <= SP_TRAIN_MAXSETS, PET_ERR_UNSUPPORTED,
                 "training more than 16 per-species networks: the bucket table of the weight gradients holds 16");
     PET_REQUIRE(!m.grad.empty(), PET_ERR_ARGUMENT, "soap_model_zero_grad has not been called");
+    PET_REQUIRE(!ucell || u, PET_ERR_ARGUMENT, "d_u_cell without d_u: the stress seeds travel with the force seeds");
+    PET_REQUIRE(!ucell || g.shift, PET_ERR_ARGUMENT, "d_u_cell: a cell tangent needs a pet_graph_build handle (cell shifts)");
     SoapWs w;
     carve_soap(d, g.n_nodes, g.n_edges, ws, w);
     PET_REQUIRE((int64_t)w.bytes <= ws_bytes, PET_ERR_ARGUMENT, "soap workspace too small");
@@ -731,7 +744,7 @@ int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_bytes, v
         PET_HIP_CHECK(hipMemsetAsync(t.xd, 0, (size_t)N * d.S * 4, st));
     }
     if (tangent) {
-        k_edge_tangent<<<cdiv(g.n_edges, 256), 256, 0, st>>>(u, g.ctr, g.nbr, t.vd, g.n_edges);
+        k_edge_tangent<<<cdiv(g.n_edges, 256), 256, 0, st>>>(u, g.ctr, g.nbr, g.shift, g.sys, ucell, t.vd, g.n_edges);
         const size_t lds = (size_t)PC * (5 * d.NLM + 2 * d.F + 12 + 1) * 4;
         allow_big_lds(k_soap_expand_jvp, lds);
         k_soap_expand_jvp<<<N, 256, lds, st>>>(d, g.geo, t.vd, g.rowptr, g.sp_nbr, m.table, m.shnorm, m.coef_lut,

@@ -5,6 +5,7 @@ and the scalar last layer ``:1204-1219``): power spectrum -> (centre encoding) -
 bias-free linear last layer, per centre species when ``legacy``; dE/dR through the hand-written reverse pass.
 **Parity unpinned** against torch-spex (not shipped with the reference); checked against ``oracle/soap.py``.
 """
+import weakref
 from ctypes import byref, c_void_p
 from typing import Dict, List, Optional
 
@@ -64,6 +65,9 @@ class SoapBpnnHip:
         self.feature_size = int(self.lib.soap_model_feature_size(self._handle))
         table = torch.from_numpy(radial.spline_table(self.cutoff, zeros, norms, n_grid)).cuda().contiguous()
         check(self.lib.soap_model_set_radial_table(self._handle, rt._ptr(table), n_grid, rt._stream()))
+        # the spline's curvature slopes (second derivatives: the Hessian-vector product), a table of their own next to it
+        curv = torch.from_numpy(radial.curvature_table(self.cutoff, zeros, norms, n_grid)).cuda().contiguous()
+        check(self.lib.soap_model_set_radial_curvature(self._handle, rt._ptr(curv), n_grid, rt._stream()))
         torch.cuda.current_stream().synchronize()
         # the graph (CSR order, edge vectors, ij->ji map) is the PET path's, built with the SOAP cutoff
         gh = pet_default_hypers()
@@ -95,6 +99,7 @@ class SoapBpnnHip:
             check(self.lib.soap_model_set_param(self._handle, key.encode(), rt._ptr(src), src.numel(), rt._stream()))
             torch.cuda.current_stream().synchronize()
         check(self.lib.soap_model_finalize(self._handle, rt._stream()))
+        self._fwd_of = None  # (the workspace's forward is of the old parameters)
 
     def graph(self, positions, cells, centers, neighbors, cell_shifts, species, system_indices) -> rt.HipGraph:
         return rt.HipGraph(self._graph_model, positions, cells, centers, neighbors, cell_shifts, species,
@@ -115,6 +120,7 @@ class SoapBpnnHip:
         feats = torch.empty((g.n_nodes, self.feature_size), dtype=torch.float32, device=dev) if want_features else None
         check(self.lib.soap_forward(self._handle, g.handle, rt._ptr(ws), ws.numel(), rt._ptr(atomic), rt._ptr(feats),
                                     rt._stream()))
+        self._fwd_of = (weakref.ref(g), ws.data_ptr())  # (hessian_vector_product: whose expansion the workspace holds)
         return (atomic, feats) if want_features else atomic
 
     def backward(self, g: rt.HipGraph, grad_atomic: torch.Tensor, want_cell_grad: bool = False):
@@ -151,9 +157,11 @@ class SoapBpnnHip:
     def zero_grad(self) -> None:
         check(self.lib.soap_model_zero_grad(self._handle, rt._stream()))
 
-    def train_gradients(self, g: rt.HipGraph, grad_atomic: torch.Tensor, u: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """ADDS ``d/d theta [sum_i grad_atomic_i e_i + <u, dE/dR>]`` to the gradient slots (``soap_train_gradients``;
-        ``forward(g)`` must have run) and returns the tangent of the atomic energies along ``u`` ``[N]``."""
+    def train_gradients(self, g: rt.HipGraph, grad_atomic: torch.Tensor, u: Optional[torch.Tensor] = None,
+                        u_cell: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """ADDS ``d/d theta [sum_i grad_atomic_i e_i + <u, dE/dR> + <u_cell, dE/dcell>]`` to the gradient slots
+        (``soap_train_gradients`` / ``soap_train_gradients_cell``; ``forward(g)`` must have run) and returns the tangent of the
+        atomic energies along ``(u, u_cell)`` ``[N]``. ``u_cell [S,3,3]`` (the stress term's seeds) needs ``u``."""
         ws = self._workspace(g)
         n = int(self.lib.soap_train_workspace_bytes(self._handle, g.n_nodes, g.n_edges))
         if n < 0:
@@ -163,9 +171,54 @@ class SoapBpnnHip:
         ga = grad_atomic.detach().to(torch.float32).contiguous()
         uu = None if u is None else u.detach().to(torch.float32).contiguous()
         tangent = torch.zeros(g.n_nodes, dtype=torch.float32, device=ws.device)
-        check(self.lib.soap_train_gradients(self._handle, g.handle, rt._ptr(ws), ws.numel(), rt._ptr(self._tws),
-                                            self._tws.numel(), rt._ptr(ga), rt._ptr(uu), rt._ptr(tangent), rt._stream()))
+        if u_cell is None:
+            check(self.lib.soap_train_gradients(self._handle, g.handle, rt._ptr(ws), ws.numel(), rt._ptr(self._tws),
+                                                self._tws.numel(), rt._ptr(ga), rt._ptr(uu), rt._ptr(tangent), rt._stream()))
+            return tangent
+        uc = u_cell.detach().to(ws.device, torch.float32).reshape(g.n_systems, 3, 3).contiguous()
+        check(self.lib.soap_train_gradients_cell(self._handle, g.handle, rt._ptr(ws), ws.numel(), rt._ptr(self._tws),
+                                                 self._tws.numel(), rt._ptr(ga), rt._ptr(uu), rt._ptr(uc), rt._ptr(tangent),
+                                                 rt._stream()))
         return tangent
+
+    # ---- second derivatives ------------------------------------------------------------------------
+    def hessian_vector_product(self, g: rt.HipGraph, u: torch.Tensor, u_cell: Optional[torch.Tensor] = None,
+                               want_cells: bool = False, want_tangent: bool = False):
+        """Hessian-vector product of the network's energy (``soap_hessian_vector``), in the convention of
+        :func:`metatrain_amd.runtime.hessian_vector_product` without ``weights``: with ``e'_i`` the derivative of the
+        per-atom energies along ``(dR, dcell) = (u [N,3], u_cell [S,3,3])``, returns ``grad_R sum_i e'_i`` ``[N,3]`` -- ``H u``
+        -- then, if asked for, ``grad_cell`` of the same, i.e. of ``<u, dE/dR> + <u_cell, dE/dcell>``, ``[S,3,3]`` and the
+        tangents ``e'_i [N]``. Reads the expansion and the power spectrum of ``forward(g)``, which it runs itself unless this
+        graph's forward was the last one on the model's workspace; touches no gradient slot."""
+        rt._require_cuda(u)
+        ws = self._workspace(g)
+        dev = ws.device
+        n, s = g.n_nodes, g.n_systems
+        if getattr(self, "_fwd_of", None) is None or self._fwd_of[0]() is not g or self._fwd_of[1] != ws.data_ptr():
+            self.forward(g)
+        nbytes = int(self.lib.soap_hvp_workspace_bytes(self._handle, n, g.n_edges))
+        if nbytes < 0:
+            raise PetHipError("soap_hvp_workspace_bytes failed")
+        if getattr(self, "_hws", None) is None or self._hws.numel() < nbytes:
+            self._hws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        uu = u.detach().to(torch.float32).reshape(n, 3).contiguous()
+        uc = None if u_cell is None else u_cell.detach().to(dev, torch.float32).reshape(-1, 3, 3).contiguous()
+        hp = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        hc = torch.empty((s, 3, 3), dtype=torch.float32, device=dev) if want_cells else None
+        tan = torch.empty(n, dtype=torch.float32, device=dev) if want_tangent else None
+        check(self.lib.soap_hessian_vector(self._handle, g.handle, rt._ptr(ws), ws.numel(), rt._ptr(self._hws),
+                                           self._hws.numel(), rt._ptr(uu), rt._ptr(uc), rt._ptr(hp), rt._ptr(hc), rt._ptr(tan),
+                                           rt._stream()))
+        out = (hp,) + ((hc,) if want_cells else ()) + ((tan,) if want_tangent else ())
+        return out[0] if len(out) == 1 else out
+
+    def hessian_vector_product_total(self, g: rt.HipGraph, u: torch.Tensor, pbcs=None) -> torch.Tensor:
+        """:meth:`evaluate`'s sibling: ``H u`` of the network plus, for a model with ``zbl``, of the ZBL term on the same
+        graph (or on a second one at the ZBL cutoff when this graph's is shorter: ``pbcs`` as in ``ZBLHip.graph_for``)."""
+        out = self.hessian_vector_product(g, u)
+        if self.zbl is not None:
+            out = out + self.zbl.hessian_vector_product(self.zbl.graph_for(g, pbcs), u)
+        return out
 
     def _copy_out(self, fn, keys_shapes) -> Dict[str, torch.Tensor]:
         out = {}
@@ -200,6 +253,7 @@ class SoapBpnnHip:
 
     def adam_step(self, lr: float, step: int, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
         check(self.lib.soap_adam_step(self._handle, lr, betas[0], betas[1], eps, step, rt._stream()))
+        self._fwd_of = None
 
 
 class SoapTrainStep:
@@ -220,7 +274,7 @@ class SoapTrainStep:
         self.hypers = dict(self.DEFAULTS)
         self.hypers.update(hypers or {})
         self.total_steps = int(self.hypers["num_epochs"]) * int(steps_per_epoch)
-        self.weights = {"energy": 1.0, "forces": 1.0, **(loss_weights or {})}
+        self.weights = {"energy": 1.0, "forces": 1.0, "strain": 1.0, **(loss_weights or {})}
         self.step_index = 0  # optimizer steps taken so far (LambdaLR's last_epoch)
 
     def current_lr(self) -> float:
@@ -238,20 +292,36 @@ class SoapTrainStep:
         self.hypers.update(state["hypers"])
 
     def __call__(self, g: rt.HipGraph, target_energies: torch.Tensor, n_atoms: torch.Tensor,
-                 target_gradients: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
-        from ..pet.trainer import energy_loss_and_seeds, force_loss_and_seeds
+                 target_gradients: Optional[torch.Tensor] = None, target_strain_gradients: Optional[torch.Tensor] = None,
+                 positions: Optional[torch.Tensor] = None, cells: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+        """``target_strain_gradients [S,3,3]`` (dE/d strain, ``utils/evaluate_model.py:305-321``) adds the stress term
+        ``MSE(dE/dstrain)`` weighted by ``loss_weights["strain"]``; it needs the batch's ``positions`` and ``cells``."""
+        from ..pet.trainer import energy_loss_and_seeds, force_loss_and_seeds, strain_loss_and_seeds
+
+        strain = target_strain_gradients is not None
+        if strain and (positions is None or cells is None):
+            raise ValueError("a strain-gradient (stress) target (target_strain_gradients) needs `positions` and `cells`")
 
         m = self.model
         m.zero_grad()
         atomic = m.forward(g)
         energies = m.sum_over_atoms(g, atomic)
         loss, seeds = energy_loss_and_seeds(energies, target_energies, n_atoms, g.system_of_atom(), self.weights["energy"])
-        u = None
+        u = u_cell = None
+        if target_gradients is not None or strain:
+            # evaluate_model: autograd.grad(E.sum(), R | strain, create_graph)
+            res = m.backward(g, torch.ones_like(atomic), want_cell_grad=strain)
+            grad_positions, grad_cells = res if strain else (res, None)
         if target_gradients is not None:
-            grad_positions = m.backward(g, torch.ones_like(atomic))   # evaluate_model: autograd.grad(E.sum(), R, create_graph)
             loss_f, u = force_loss_and_seeds(grad_positions, target_gradients, self.weights["forces"])
             loss = loss + loss_f
-        tangent = m.train_gradients(g, seeds, u)
+        if strain:
+            loss_s, u_s, u_cell = strain_loss_and_seeds(
+                positions.to(torch.float32), cells.to(torch.float32), g.system_of_atom().long(), grad_positions, grad_cells,
+                target_strain_gradients, self.weights["strain"])
+            loss = loss + loss_s
+            u = u_s if u is None else u + u_s
+        tangent = m.train_gradients(g, seeds, u, u_cell)
         lr = self.current_lr()  # the rate the scheduler set after the previous step
         self.step_index += 1
         m.adam_step(lr, self.step_index)

@@ -46,3 +46,27 @@ def spline_table(cutoff: float, zeros, norms, n_grid: int = 2049) -> np.ndarray:
             cols.append(np.stack([val, nn * k * special.spherical_jn(l, k * r, derivative=True), chord,
                                   np.zeros_like(val)], axis=1))
     return np.stack(cols, axis=1).astype(np.float32)
+
+
+def curvature_table(cutoff: float, zeros, norms, n_grid: int = 2049) -> np.ndarray:
+    """``[n_grid, F, 2]`` float32: the curvature slopes ``(d0_k, d1_k) = ((c_k - m_k) / h, (m_{k+1} - c_k) / h)`` of every
+    interval of :func:`spline_table`'s grid, ``c_k`` its chord slope and ``m_k`` its node derivatives, zeros at the last
+    node. On interval ``k`` the device's first derivative is the chord-form quadratic
+    ``p'(s) = c + (1 - 4 s + 3 s^2)(m_k - c) + (3 s^2 - 2 s)(m_{k+1} - c)``, whose exact derivative is
+    ``p''(s) = (4 - 6 s) d0 + (6 s - 2) d1``. The slopes are formed here in fp64, like the chord: from the fp32 table they
+    would be fp32 rounding divided by ``h`` (1e-5 of the Hessian-vector product at 2049 nodes, worse on a finer grid)."""
+    r = np.linspace(0.0, cutoff, n_grid)
+    h = cutoff / (n_grid - 1)
+    cols = []
+    for l, (zl, nl) in enumerate(zip(zeros, norms)):
+        for zn, nn in zip(zl, nl):
+            k = zn / cutoff
+            val = nn * special.spherical_jn(l, k * r)
+            der = nn * k * special.spherical_jn(l, k * r, derivative=True)
+            chord = (val[1:] - val[:-1]) / h
+            d0 = np.concatenate([(chord - der[:-1]) / h, [0.0]])
+            d1 = np.concatenate([(der[1:] - chord) / h, [0.0]])
+            cols.append(np.stack([d0, d1], axis=1))
+    if not cols:
+        return np.zeros((n_grid, 0, 2), dtype=np.float32)
+    return np.stack(cols, axis=1).astype(np.float32)

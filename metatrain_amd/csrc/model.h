@@ -361,60 +361,9 @@ int geometry_backward(const Model& m, const Graph& g, const float* g_geo, const 
 int backward_geometry_abi(const Model& m, const Graph& g, void* ws, int64_t ws_bytes, const float* g_geo,
                           const float* g_fc, float* grad_pos, float* grad_cells, hipStream_t st);
 
-// ---- launchers of the tuned first-order pass, by file. Which of them serves a stage is the plan's decision (pet_plan.h); a launcher
-// launches, and returns an error only when it is called without the weight planes of its kernel.
+// ---- the stage launchers of the tuned first-order pass are declared in pet_stages.h. Which of them serves a stage is the plan's decision
+// (pet_plan.h).
 bool use_trr();  // abi.hip: pet_config_set("trr") / PET_HIP_TRR (0 selects the LDS-tile kernels)
-// pet_trr.hip: software-pipelined register-resident row kernels on f16x3 planes. beta: the LayerNorm bias of the layer's norm,
-// nullptr = RMSNorm; t_*: the operands the weight-gradient GEMMs need (training), nullptr otherwise
-int trr_compress(bool first, const Graph& g, const GnnLayerW& G, const float* Min, float* a0_out, float* Xout, int64_t E,
-                 hipStream_t st);
-int trr_compress_bwd(bool first, const float* dXe, const float* a0, const GnnLayerW& G, float* dgeo, float* dM, int64_t E,
-                     float* t_da0, hipStream_t st);
-int trr_head_edge(const Model& m, const float* Xin, const float* fc, float* ypred, float* yout, int64_t E, hipStream_t st);
-int trr_head_edge_bwd(const Model& m, const float* Xin, const float* gA, const int* ctr, const float* fc, const float* ypred,
-                      float* dfc, float* dXout, int64_t E, float* t_s1, float* t_da2, float* t_da1, float* t_s2y, hipStream_t st);
-void trr_qkv(const float* X, const float* gamma, const float* beta, const Lin& qkv, float* QKV, int64_t R, hipStream_t st);
-void trr_qkv_bwd(const float* dQKV, const float* X, const float* gamma, bool layer_norm, const Lin& qkv, const float* dX1,
-                 float* dXin, int64_t E, int64_t R, hipStream_t st);
-void trr_oproj(const float* AO, const float* X, const Lin& out, float* X1, float* OC, int64_t E, int64_t R, hipStream_t st);
-void trr_oproj_bwd(const float* dX1, const float* dOC, const Lin& out, float* dAO, int64_t E, int64_t R, hipStream_t st);
-void trr_emlp(const float* X1, const float* gamma, const float* beta, const Lin& win, const Lin& wout, float* VG, float* X2,
-              int64_t E, hipStream_t st);
-void trr_emlp_bwd(const float* dY, const float* X1, const float* VG, const float* gamma, const float* beta, const Lin& win,
-                  const Lin& wout, float* dX1, int64_t E, hipStream_t st, float* t_dvg = nullptr, int ldy = 128,
-                  const float* dY2 = nullptr, const int* rev2 = nullptr);  // dY2: dY = dY[p] + dY2[rev2[p]], rows of ldy floats
-// pet_comb.hip / pet_comb_bwd.hip: the combination stage and its adjoint, pipelined. add_dm: dcat[p][:D] += dM[p]
-int trr_comb(bool first, const float* XF, const Graph& g, const GnnLayerW& G, const float* Min, const float* edge_emb, float* CA,
-             float* LNS, float* Mout, int64_t E, hipStream_t st);
-int trr_comb_bwd(const float* dM, const float* XF, const Graph& g, const GnnLayerW& G, const float* LNS, const float* CA,
-                 float* dcat, int64_t E, float* t_da, hipStream_t st, bool add_dm = false);
-// pet_emlp_s.hip, pet_head_s.hip, pet_compress_s.hip, pet_comb_s.hip, pet_comb_bwd_s.hip, pet_center_s.hip: the same stages (inference)
-// with a workgroup-shared weight ring, two workgroups per CU; emlp_bwd_s recomputes [v; g]
-int emlp_s(const float* X1, const float* gamma, const float* beta, const Lin& win, const Lin& wout, float* VG, float* X2,
-           int64_t E, hipStream_t st);
-int emlp_bwd_s(const float* dY, const float* X1, bool ln, const Lin& win_g, const Lin& wout, float* dX1, int64_t E,
-               hipStream_t st, int ldy, const float* dY2, const int* rev2);
-int head_edge_s(const Model& m, const float* Xin, const float* fc, float* ypred, float* yout, int64_t E, hipStream_t st);
-int head_edge_bwd_s(const Model& m, const float* Xin, const float* gA, const int* ctr, const float* fc, const float* ypred,
-                    float* dfc, float* dXout, int64_t E, hipStream_t st);
-int compress_bwd_s(bool first, const float* dXe, const float* a0, const GnnLayerW& G, float* dgeo, float* dM, int64_t E, hipStream_t st);
-int comb_s(bool first, const float* XF, const int* rev, const Lin& c0g, const Lin& c2, const float* Min, const float* edge_emb,
-           const int* sp_nbr, float* CA, float* LNS, float* Mout, int64_t E, hipStream_t st);
-int comb_bwd_s(const float* dM, const float* XF, const int* rev, const float* LNS, const float* CA, const Lin& c0g, const Lin& c2,
-               float* dcat, int64_t E, bool add_dm, hipStream_t st);
-int center_s(const Lin& cc, const float* H, float* Xc, int64_t N, hipStream_t st);
-int expand_bwd_s(const Lin& ce, const float* dH1, float* dOC, int64_t N, hipStream_t st);
-int center_bwd_s(const Lin& cc, const float* dC, const float* dH1, float* dHin, int64_t N, hipStream_t st);
-// pet_node_s.hip: the node update of large graphs as ring row GEMMs (every kernel fits beside an edge kernel's workgroup)
-int node_fwd_s(const AttnLayerW& A, const float* H, const float* OC, float* H1, float* VGn, float* Hn, float* tmp, int64_t N,
-               hipStream_t st);
-int node_bwd_s(const AttnLayerW& A, const float* dHn, const float* H1, const float* VGn, float* dH1, float* tmp, int64_t N, bool ln,
-               hipStream_t st);
-// pet_ablk.hip: the per-atom fused attention block (norm -> QKV -> attention -> output projection in one kernel, the adjoint
-// recomputing Q, K, V)
-int ablk_fwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* X, float* X1, float* OC, float scale, hipStream_t st);
-int ablk_bwd(const Model& m, const Graph& g, const AttnLayerW& A, const float* X, const float* dX1, const float* dOC, float* dXin,
-             float* dbias, float scale, hipStream_t st);
 void ablk_prof_dump();  // debugging aid: per-phase cycle sums of the fused kernels (library built with -DAB_PROFILE)
 // so_rows_s.hip: the generic row GEMM of the training passes with a workgroup-shared weight ring; false = not served (planes
 // missing, a shape it does not tile, or fewer rows than the ring kernels' threshold)
@@ -426,11 +375,6 @@ bool rowgemm_s_ex(hipStream_t st, const float* X, int K, const float* cs, const 
 bool rowgemm_s_swiglu_bwd(hipStream_t st, const float* X, const void* planes, const float* VG, float* dVG, int hid, int64_t R);
 bool rowgemm_s_norm_bwd(hipStream_t st, const float* X, int K, const void* planes, const float* xn, const float* gamma, int ln,
                         const float* dres, float* out, int64_t R);
-
-// pet_attn.hip: preload variants of the attention kernels (NT <= 4); return false if not handled
-bool attn_fwd_preload(int nt, const float* QKV, const Graph& g, float* AO, float scale, hipStream_t st);
-bool attn_bwd_preload(int nt, const float* QKV, const float* dAO, const Graph& g, float* dQKV, float* dbias_h,
-                      float scale, hipStream_t st);
 
 // second-order attention on MFMA (training pass); false if the tile count is not served
 bool attn_jvp_mfma(int nt, const float* QKV, const float* QKVd, const Graph& g, const float* Tkb, float* AOd,

@@ -1,13 +1,15 @@
 // Per-atom attention, forward and adjoint, "preload" variants for up to 63 neighbours (NT <= 4).
 //
-// Same math and same operand-layout trick as k_attn_fwd / k_attn_bwd in pet_fwd.hip / pet_bwd.hip
+// Same math and same operand-layout trick as k_attn_fwd / k_attn_bwd further down
 // (one wave per (atom, head), transposed score tiles on v_mfma_f32_16x16x4_f32, no LDS), but every
 // global operand -- Q, K, V, dO fragments and the scalar re-reads used as A operands -- is loaded
 // into registers up front in ONE burst, so the wave pays one memory round trip instead of a chain
 // of dependent ones (the first version was latency-bound: MFMA busy 19 %, 58 % of wave time in
 // s_waitcnt). Reference: pet/modules/transformer.py:86-152, 565-589.
+#include <type_traits>
+
 #include "common.h"
-#include "model.h"
+#include "pet_stages.h"
 
 namespace pet {
 
@@ -827,15 +829,310 @@ __global__ __launch_bounds__(512) void k_attn_bwd_a(const float* __restrict__ QK
     }
 }
 
+// ---------------------------------------------------------------------------------
+// attention: one wave per (atom, head); 16x16x4 fp32 MFMA, no LDS.
+// Scores are produced transposed (keys x queries) so that the soft-maxed tile is
+// already in the B-operand layout of the PV product.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t token_row(int t, int T, int64_t E, int atom, int start) {
+    // token 0 = centre, token t >= 1 = edge start + t - 1; out-of-range tokens alias token 0
+    return (t == 0 || t >= T) ? E + atom : (int64_t)start + t - 1;
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void k_attn_fwd(const float* __restrict__ QKV, const int* __restrict__ rowptr,
+                                                   const float* __restrict__ fc, float* __restrict__ AO,
+                                                   int64_t E, int N, float scale) {
+    const int lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int atom = gw / NHEAD, head = gw % NHEAD;
+    if (atom >= N) return;
+    const int start = rowptr[atom];
+    const int T = rowptr[atom + 1] - start + 1;
+    const int nt = (T + 15) >> 4;
+    const int c16 = lane & 15, g4 = lane >> 4;
+    // key fragments (A operand of S^T = K Q^T): K[key = 16 kt + c16][4 g4 .. 4 g4 + 3]
+    float4 kf[NT];
+    float bias[NT][4];
+#pragma unroll
+    for (int kt = 0; kt < NT; kt++) {
+        if (kt < nt) {
+            const int64_t row = token_row(16 * kt + c16, T, E, atom, start);
+            kf[kt] = *reinterpret_cast<const float4*>(QKV + row * (3 * D) + D + HD * head + 4 * g4);
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int key = 16 * kt + 4 * g4 + r;  // C-layout row of the S^T tile
+                float b = 0.0f;
+                if (key >= T) b = -INFINITY;
+                else if (key > 0) b = logf(fmaxf(fc[start + key - 1], 1e-15f));  // transformer.py:109-110
+                bias[kt][r] = b;
+            }
+        }
+    }
+#pragma unroll 1
+    for (int qt = 0; qt < nt; qt++) {
+        const int q = 16 * qt + c16;
+        const int64_t qrow = token_row(q, T, E, atom, start);
+        float4 qf = *reinterpret_cast<const float4*>(QKV + qrow * (3 * D) + HD * head + 4 * g4);
+        qf.x *= scale; qf.y *= scale; qf.z *= scale; qf.w *= scale;
+        f32x4 s[NT];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < NT; kt++) {
+            if (kt < nt) {
+                f32x4 a = {0.f, 0.f, 0.f, 0.f};
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt].x, qf.x, a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt].y, qf.y, a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt].z, qf.z, a, 0, 0, 0);
+                a = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt].w, qf.w, a, 0, 0, 0);
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    a[r] += bias[kt][r];
+                    mx = fmaxf(mx, a[r]);
+                }
+                s[kt] = a;
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        float sum = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < NT; kt++) {
+            if (kt < nt) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    float p = expf(s[kt][r] - mx);
+                    s[kt][r] = p;
+                    sum += p;
+                }
+            }
+        }
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        const float inv = 1.0f / sum;
+        // O^T[d][q] = sum_key V^T[d][key] P^T[key][q]
+        f32x4 o = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kt = 0; kt < NT; kt++) {
+            if (kt < nt) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int64_t vrow = token_row(16 * kt + 4 * g4 + r, T, E, atom, start);
+                    const float vv = QKV[vrow * (3 * D) + 2 * D + HD * head + c16];
+                    o = __builtin_amdgcn_mfma_f32_16x16x4f32(vv, s[kt][r], o, 0, 0, 0);
+                }
+            }
+        }
+        if (q < T) {
+            float4 ov = make_float4(o[0] * inv, o[1] * inv, o[2] * inv, o[3] * inv);
+            *reinterpret_cast<float4*>(AO + qrow * D + HD * head + 4 * g4) = ov;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------
+// attention adjoint: one wave per (atom, head). Pass A (query tiles, transposed scores)
+// gives dQ, delta, lse and the key-bias gradient; pass B (key tiles, plain scores)
+// gives dK and dV. 16x16x4 fp32 MFMA, no LDS, no atomics.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t token_row_b(int t, int T, int64_t E, int atom, int start) {
+    return (t == 0 || t >= T) ? E + atom : (int64_t)start + t - 1;
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void k_attn_bwd(const float* __restrict__ QKV, const float* __restrict__ dAO,
+                                                   const int* __restrict__ rowptr, const float* __restrict__ fc,
+                                                   float* __restrict__ dQKV, float* __restrict__ dbias_h,
+                                                   int64_t E, int N, float scale) {
+    const int lane = threadIdx.x & 63;
+    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int atom = gw / NHEAD, head = gw % NHEAD;
+    if (atom >= N) return;
+    const int start = rowptr[atom];
+    const int T = rowptr[atom + 1] - start + 1;
+    const int nt = (T + 15) >> 4;
+    const int c16 = lane & 15, g4 = lane >> 4;
+    const int qo = HD * head, ko = D + HD * head, vo = 2 * D + HD * head;
+    float4 kf[NT], vf[NT];
+    float bias_r[NT][4];  // bias of key 16kt + 4g4 + r (rows of the transposed tile)
+    float bias_c[NT];     // bias of key 16kt + c16   (columns of the plain tile)
+    float db[NT][4];
+    float lse[NT], delta[NT];
+#pragma unroll
+    for (int kt = 0; kt < NT; kt++) {
+        lse[kt] = 0.f;
+        delta[kt] = 0.f;
+        if (kt < nt) {
+            const int64_t row = token_row_b(16 * kt + c16, T, E, atom, start);
+            kf[kt] = *reinterpret_cast<const float4*>(QKV + row * (3 * D) + ko + 4 * g4);
+            vf[kt] = *reinterpret_cast<const float4*>(QKV + row * (3 * D) + vo + 4 * g4);
+            const int kc = 16 * kt + c16;
+            bias_c[kt] = kc >= T ? -INFINITY : (kc == 0 ? 0.f : logf(fmaxf(fc[start + kc - 1], 1e-15f)));
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int key = 16 * kt + 4 * g4 + r;
+                bias_r[kt][r] = key >= T ? -INFINITY : (key == 0 ? 0.f : logf(fmaxf(fc[start + key - 1], 1e-15f)));
+                db[kt][r] = 0.f;
+            }
+        }
+    }
+    // ------------------------------ pass A ------------------------------
+#pragma unroll
+    for (int qt = 0; qt < NT; qt++) {
+        if (qt < nt) {
+            const int q = 16 * qt + c16;
+            const int64_t qrow = token_row_b(q, T, E, atom, start);
+            float4 qf = *reinterpret_cast<const float4*>(QKV + qrow * (3 * D) + qo + 4 * g4);
+            qf.x *= scale; qf.y *= scale; qf.z *= scale; qf.w *= scale;
+            float4 dof = make_float4(0, 0, 0, 0);
+            if (q < T) dof = *reinterpret_cast<const float4*>(dAO + qrow * D + qo + 4 * g4);
+            f32x4 s[NT], dp[NT];
+            float mx = -INFINITY;
+#pragma unroll
+            for (int kt = 0; kt < NT; kt++) {
+                if (kt < nt) {
+                    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt].x, qf.x, a, 0, 0, 0);
+                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt].y, qf.y, a, 0, 0, 0);
+                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt].z, qf.z, a, 0, 0, 0);
+                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[kt].w, qf.w, a, 0, 0, 0);
+                    f32x4 b = {0.f, 0.f, 0.f, 0.f};
+                    b = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[kt].x, dof.x, b, 0, 0, 0);
+                    b = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[kt].y, dof.y, b, 0, 0, 0);
+                    b = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[kt].z, dof.z, b, 0, 0, 0);
+                    b = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[kt].w, dof.w, b, 0, 0, 0);
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        a[r] += bias_r[kt][r];
+                        mx = fmaxf(mx, a[r]);
+                    }
+                    s[kt] = a;
+                    dp[kt] = b;
+                }
+            }
+            mx = fmaxf(mx, __shfl_xor(mx, 16));
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            float sum = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < NT; kt++)
+                if (kt < nt)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        float p = expf(s[kt][r] - mx);
+                        s[kt][r] = p;
+                        sum += p;
+                    }
+            sum += __shfl_xor(sum, 16);
+            sum += __shfl_xor(sum, 32);
+            const float inv = 1.0f / sum;
+            float dl = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < NT; kt++)
+                if (kt < nt)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        s[kt][r] *= inv;
+                        dl += s[kt][r] * dp[kt][r];
+                    }
+            dl += __shfl_xor(dl, 16);
+            dl += __shfl_xor(dl, 32);
+            lse[qt] = mx + logf(sum);
+            delta[qt] = dl;
+            f32x4 dq = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int kt = 0; kt < NT; kt++)
+                if (kt < nt)
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const float ds = s[kt][r] * (dp[kt][r] - dl);  // dS^T[key][q]
+                        db[kt][r] += ds;  // padded queries have dO = 0 => dp = dl = 0 => ds = 0
+                        const int64_t krow = token_row_b(16 * kt + 4 * g4 + r, T, E, atom, start);
+                        const float kk = QKV[krow * (3 * D) + ko + c16];
+                        dq = __builtin_amdgcn_mfma_f32_16x16x4f32(kk, ds, dq, 0, 0, 0);
+                    }
+            if (q < T)
+                *reinterpret_cast<float4*>(dQKV + qrow * (3 * D) + qo + 4 * g4) =
+                    make_float4(dq[0] * scale, dq[1] * scale, dq[2] * scale, dq[3] * scale);
+        }
+    }
+    // key-bias gradient: sum over the 16 query columns; lanes c16 < 4 write one key each into the attention
+    // layer's head-major slice [NHEAD, E] (one writer per (layer, head, edge): plain stores, k_dfc_attn sums)
+#pragma unroll
+    for (int kt = 0; kt < NT; kt++)
+        if (kt < nt) {
+            float v4[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                float v = db[kt][r];
+                v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4); v += __shfl_xor(v, 8);
+                v4[r] = v;
+            }
+            const float v = c16 == 0 ? v4[0] : c16 == 1 ? v4[1] : c16 == 2 ? v4[2] : v4[3];
+            const int key = 16 * kt + 4 * g4 + c16;
+            if (c16 < 4 && key >= 1 && key < T) dbias_h[(int64_t)head * E + start + key - 1] = v;
+        }
+    // ------------------------------ pass B ------------------------------
+#pragma unroll
+    for (int kt = 0; kt < NT; kt++) {
+        if (kt < nt) {
+            f32x4 dk = {0.f, 0.f, 0.f, 0.f}, dvv = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int qt = 0; qt < NT; qt++) {
+                if (qt < nt) {
+                    const int64_t qrow_c = token_row_b(16 * qt + c16, T, E, atom, start);
+                    float4 qf = *reinterpret_cast<const float4*>(QKV + qrow_c * (3 * D) + qo + 4 * g4);
+                    qf.x *= scale; qf.y *= scale; qf.z *= scale; qf.w *= scale;
+                    float4 dof = make_float4(0, 0, 0, 0);
+                    if (16 * qt + c16 < T) dof = *reinterpret_cast<const float4*>(dAO + qrow_c * D + qo + 4 * g4);
+                    // S[q][key]: A = Q (rows q), B = K (cols key)
+                    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(qf.x, kf[kt].x, a, 0, 0, 0);
+                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(qf.y, kf[kt].y, a, 0, 0, 0);
+                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(qf.z, kf[kt].z, a, 0, 0, 0);
+                    a = __builtin_amdgcn_mfma_f32_16x16x4f32(qf.w, kf[kt].w, a, 0, 0, 0);
+                    f32x4 b = {0.f, 0.f, 0.f, 0.f};  // dP[q][key] = dO V^T
+                    b = __builtin_amdgcn_mfma_f32_16x16x4f32(dof.x, vf[kt].x, b, 0, 0, 0);
+                    b = __builtin_amdgcn_mfma_f32_16x16x4f32(dof.y, vf[kt].y, b, 0, 0, 0);
+                    b = __builtin_amdgcn_mfma_f32_16x16x4f32(dof.z, vf[kt].z, b, 0, 0, 0);
+                    b = __builtin_amdgcn_mfma_f32_16x16x4f32(dof.w, vf[kt].w, b, 0, 0, 0);
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        const int qq = 16 * qt + 4 * g4 + r;  // row of the plain tile
+                        const float l = __shfl(lse[qt], 4 * g4 + r);
+                        const float dl = __shfl(delta[qt], 4 * g4 + r);
+                        float p = expf(a[r] + bias_c[kt] - l);
+                        if (qq >= T) p = 0.f;
+                        const float ds = p * (b[r] - dl);
+                        const int64_t qrow_r = token_row_b(qq, T, E, atom, start);
+                        float dov = 0.f;
+                        if (qq < T) dov = dAO[qrow_r * D + qo + c16];
+                        const float qv = QKV[qrow_r * (3 * D) + qo + c16];
+                        dvv = __builtin_amdgcn_mfma_f32_16x16x4f32(dov, p, dvv, 0, 0, 0);
+                        dk = __builtin_amdgcn_mfma_f32_16x16x4f32(qv, ds, dk, 0, 0, 0);
+                    }
+                }
+            }
+            const int key = 16 * kt + c16;
+            if (key < T) {
+                const int64_t krow = token_row_b(key, T, E, atom, start);
+                *reinterpret_cast<float4*>(dQKV + krow * (3 * D) + ko + 4 * g4) =
+                    make_float4(dk[0] * scale, dk[1] * scale, dk[2] * scale, dk[3] * scale);
+                *reinterpret_cast<float4*>(dQKV + krow * (3 * D) + vo + 4 * g4) =
+                    make_float4(dvv[0], dvv[1], dvv[2], dvv[3]);
+            }
+        }
+    }
+}
+
 // The attention adjoint of the three-kernel form (the forward is always k_attn_fwd_p, one wave per (atom, head) straight from global
 // memory): a persistent kernel with LDS-DMA prefetch (k_attn_bwd_a) for atoms of at most 32 tokens, the per-atom LDS-staged k_attn_bwd_l
 // for the rest. (Rounds 1 - 5 kept a switch, "attn_lds", that sent every atom through k_attn_bwd_l; measured per launch on 8 x 10k-atom
 // boxes: 2.5 ms against 1.8 ms. Removed in round 6 with the two instantiations only it reached.)
-// The generic wave-per-head kernels of pet_fwd.hip / pet_bwd.hip serve more than 64 tokens per atom and trr = 0.
+// The generic wave-per-head kernels above (k_attn_fwd / k_attn_bwd) serve more than 64 tokens per atom and trr = 0.
 
 // Atoms are served by the instantiation that matches their own tile count (registers / LDS, hence waves in
 // flight, scale with NT): one launch per tile count, over the graph's list of the atoms that have it.
-bool attn_fwd_preload(int nt, const float* QKV, const Graph& g, float* AO, float scale, hipStream_t st) {
+static bool attn_fwd_preload(int nt, const float* QKV, const Graph& g, float* AO, float scale, hipStream_t st) {
     if (nt > 4) return false;
     const int N = (int)g.n_nodes;
     if (N <= 4096) {
@@ -865,7 +1162,7 @@ bool attn_fwd_preload(int nt, const float* QKV, const Graph& g, float* AO, float
 #undef PET_ATTN_FWD
     return true;
 }
-bool attn_bwd_preload(int nt, const float* QKV, const float* dAO, const Graph& g, float* dQKV, float* dbias_h,
+static bool attn_bwd_preload(int nt, const float* QKV, const float* dAO, const Graph& g, float* dQKV, float* dbias_h,
                       float scale, hipStream_t st) {
     if (nt > 4) return false;
     const int N = (int)g.n_nodes;
@@ -897,6 +1194,42 @@ bool attn_bwd_preload(int nt, const float* QKV, const float* dAO, const Graph& g
     PET_ATTN_BWD_L(3) PET_ATTN_BWD_L(4)
 #undef PET_ATTN_BWD_L
     return true;
+}
+
+// ---------------------------------------------------------------------------------
+// the two entries of the three-kernel attention (pet_stages.h): the preload variants where the plan asks for them and they serve the
+// tile count, else the wave-per-(atom, head) kernel of the graph's largest tile count
+// ---------------------------------------------------------------------------------
+// calls f with the instantiated tile count as a constant: 1 .. 4 tiles their own, 5 and 6 share <6>, more take <8>
+template <class F>
+static void with_nt(int nt, F f) {
+    switch (nt) {
+        case 1: f(std::integral_constant<int, 1>()); break;
+        case 2: f(std::integral_constant<int, 2>()); break;
+        case 3: f(std::integral_constant<int, 3>()); break;
+        case 4: f(std::integral_constant<int, 4>()); break;
+        case 5: case 6: f(std::integral_constant<int, 6>()); break;
+        default: f(std::integral_constant<int, 8>()); break;
+    }
+}
+
+int attn_fwd(int nt, bool preload, const float* QKV, const Graph& g, float* AO, float scale, hipStream_t st) {
+    if (preload && attn_fwd_preload(nt, QKV, g, AO, scale, st)) return PET_OK;
+    const int N = (int)g.n_nodes;
+    with_nt(nt, [&](auto NT) {  // one wave per (atom, head), four per workgroup
+        k_attn_fwd<NT()><<<cdiv((int64_t)N * NHEAD, 4), 256, 0, st>>>(QKV, g.rowptr, g.fc, AO, g.n_edges, N, scale);
+    });
+    return PET_OK;
+}
+
+int attn_bwd(int nt, bool preload, const float* QKV, const float* dAO, const Graph& g, float* dQKV, float* dbias_h, float scale,
+             hipStream_t st) {
+    if (preload && attn_bwd_preload(nt, QKV, dAO, g, dQKV, dbias_h, scale, st)) return PET_OK;
+    const int N = (int)g.n_nodes;
+    with_nt(nt, [&](auto NT) {
+        k_attn_bwd<NT()><<<cdiv((int64_t)N * NHEAD, 4), 256, 0, st>>>(QKV, dAO, g.rowptr, g.fc, dQKV, dbias_h, g.n_edges, N, scale);
+    });
+    return PET_OK;
 }
 
 }  // namespace pet

@@ -1,7 +1,8 @@
 // Which kernel serves every stage of the tuned first-order pass (default model size), decided once per call in one place:
 // plan_forward / plan_backward (pet_plan.hip) are the only code of that pass that reads switches() to choose a kernel, compares
 // a row, atom or tile count with a policy threshold, or asks whether a weight has the planes a kernel family needs. The drivers
-// (pet_fwd.hip forward_layers, pet_bwd.hip backward_predict / backward_features) switch on the plan; the launchers launch.
+// (pet_fwd.hip forward_layers, pet_bwd.hip backward_predict / backward_features) switch on the plan and call one launcher per arm;
+// the launchers (pet_stages.h, each next to its kernels) launch: grid, dynamic LDS, opt-in, operand forms, template choice.
 // DESIGN.md 4.7 has the table (stage x condition -> kernel, forward and adjoint).
 #pragma once
 #include <stdint.h>
@@ -23,7 +24,7 @@ constexpr int64_t NODE_ROWS32_MAX_ATOMS = 16384;
 constexpr int NODE_SPLIT_MAX_TILES = 128;         // k_node2<1, true> / k_node_bwd2<1, true>: at most this many 32-row tiles
 constexpr int64_t CENTER_BWD_DEEP_MAX_ATOMS = 4096;  // k_center_bwd<DEEP>
 
-// the kernel families of a row stage: LDS-tile kernels (pet_fwd.hip / pet_bwd.hip; the one fallback, and the transformer layers
+// the kernel families of a row stage: LDS-tile kernels (pet_tile.hip; the one fallback, and the transformer layers
 // of PostLN models), software-pipelined register-resident kernels on f16x3 planes (pet_trr.hip, pet_comb*.hip), kernels with a
 // workgroup-shared weight ring, two workgroups per CU (pet_*_s.hip)
 enum class Rows : uint8_t { LdsTile, Pipelined, Ring };

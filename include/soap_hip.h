@@ -108,6 +108,31 @@ int64_t soap_hvp_workspace_bytes(const soap_model_t* m, int64_t n_nodes, int64_t
 int soap_hessian_vector(const soap_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,
                         void* d_hvp_workspace, int64_t hvp_workspace_bytes, const float* d_u, const float* d_u_cell,
                         float* d_hvp_positions, float* d_hvp_cells, float* d_tangent_atomic, void* stream);
+
+/* ---- LLPR: last-layer features, uncertainties, ensembles (llpr/model.py; soap_bpnn/model.py:347-351, 664-697) -----------
+ * F = soap_llpr_feature_size = num_neurons_per_layer (legacy = 0) or n_species * num_neurons_per_layer (legacy = 1). */
+int64_t soap_llpr_feature_size(const soap_model_t* m);
+/* d_llf [N, F] from what soap_forward of this graph left in this workspace; nothing is recomputed and the caller zeroes
+ * nothing. With x_i = silu(a_q[i]) [H] the activation of tail layer q = num_hidden_layers - layer: legacy = 0: row i is x_i;
+ * legacy = 1: x_i sits in columns [s_i H, (s_i + 1) H), s_i the centre's species index, and every other column is 0.
+ * layer = 0: the input of the last layer (the last-layer features: d_llf[i] . concat_s last_layers.energy.<s>.weight is the
+ * atomic energy). layer = 1: one layer below -- the `feature` output of a model whose mlp head was created as the tail's
+ * last hidden layer (a model with a linear head has `feature` = layer 0). Refused: no soap_forward of this graph into this
+ * workspace, a workspace shorter than soap_workspace_bytes, layer = 1 on a one-layer tail. Same bits run to run. */
+int soap_llpr_features(const soap_model_t* m, const pet_graph_t* g, void* d_workspace, int64_t workspace_bytes,
+                       int32_t layer, float* d_llf, void* stream);
+/* The LLPR kernels on [R, F] rows: the arguments of pet_llpr_rows / _covariance_accumulate / _covariance_finalize /
+ * _variance / _ensemble (pet_hip.h), with F checked against this model's soap_llpr_feature_size. */
+int soap_llpr_rows(const soap_model_t* m, int64_t F, const float* d_llf, int64_t n_atoms, const int32_t* d_system_indices,
+                   int64_t n_systems, const uint8_t* d_mask, int mean, float* d_rows, void* stream);
+int soap_llpr_covariance_accumulate(const soap_model_t* m, int64_t F, const float* d_x, int64_t R, double* d_cov,
+                                    void* stream);
+int soap_llpr_covariance_finalize(const soap_model_t* m, int64_t F, double* d_cov, void* stream);
+int soap_llpr_variance(const soap_model_t* m, int64_t F, const float* d_x, int64_t R, const float* d_inv_cholesky,
+                       float alpha, float* d_sigma, void* stream);
+int soap_llpr_ensemble(const soap_model_t* m, int64_t F, const float* d_x, int64_t R, const float* d_weights, int32_t K,
+                       int32_t P, const float* d_prediction, float* d_out, void* stream);
+
 int soap_model_get_grad(const soap_model_t* m, const char* key, float* d_out, int64_t numel, void* stream);
 int soap_model_get_param(const soap_model_t* m, const char* key, float* d_out, int64_t numel, void* stream);
 /* torch.optim.Adam step (no weight decay; `step` counted from 1) on every trainable parameter, then soap_model_finalize. */

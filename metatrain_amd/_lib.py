@@ -79,6 +79,8 @@ SOAP_SYMBOLS = [
     "soap_model_zero_grad", "soap_train_workspace_bytes", "soap_train_gradients", "soap_model_get_grad",
     "soap_model_get_param", "soap_adam_step", "soap_model_set_radial_curvature", "soap_train_gradients_cell",
     "soap_hvp_workspace_bytes", "soap_hessian_vector",
+    "soap_llpr_feature_size", "soap_llpr_features", "soap_llpr_rows", "soap_llpr_covariance_accumulate",
+    "soap_llpr_covariance_finalize", "soap_llpr_variance", "soap_llpr_ensemble",
 ]
 SOAP_MAX_L = 8
 
@@ -380,6 +382,14 @@ def load() -> ctypes.CDLL:
     lib.soap_hvp_workspace_bytes.argtypes = [P, c_int64, c_int64]
     lib.soap_hvp_workspace_bytes.restype = c_int64
     lib.soap_hessian_vector.argtypes = [P, P, P, c_int64, P, c_int64, P, P, P, P, P, P]
+    lib.soap_llpr_feature_size.argtypes = [P]
+    lib.soap_llpr_feature_size.restype = c_int64
+    lib.soap_llpr_features.argtypes = [P, P, P, c_int64, c_int32, P, P]
+    lib.soap_llpr_rows.argtypes = [P, c_int64, P, c_int64, P, c_int64, P, c_int, P, P]
+    lib.soap_llpr_covariance_accumulate.argtypes = [P, c_int64, P, c_int64, P, P]
+    lib.soap_llpr_covariance_finalize.argtypes = [P, c_int64, P, P]
+    lib.soap_llpr_variance.argtypes = [P, c_int64, P, c_int64, P, c_float, P, P]
+    lib.soap_llpr_ensemble.argtypes = [P, c_int64, P, c_int64, P, c_int32, c_int32, P, P, P]
     lib.soap_model_get_grad.argtypes = [P, c_char_p, P, c_int64, P]
     lib.soap_model_get_param.argtypes = [P, c_char_p, P, c_int64, P]
     lib.soap_adam_step.argtypes = [P, c_float, c_float, c_float, c_float, c_int64, P]

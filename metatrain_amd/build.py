@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libpet_hip.so")
-SOURCES = ["abi.hip", "graph.hip", "nl.hip", "pet_plan.hip", "pet_fwd.hip", "pet_bwd.hip", "pet_tile.hip", "pet_node.hip", "pet_trr.hip", "pet_attn.hip", "pet_ablk.hip", "pet_ablk_bwd1.hip", "pet_emlp_s.hip", "pet_head_s.hip", "pet_compress_s.hip", "pet_center_s.hip", "pet_comb.hip", "pet_comb_s.hip", "pet_comb_bwd.hip", "pet_comb_bwd_s.hip", "train.hip", "optim.hip", "so.hip", "so_rows_s.hip", "pet_node_s.hip", "soap.hip", "soap_expand.hip", "soap_ps.hip", "soap_tail.hip", "soap_train.hip", "soap_hvp.hip", "gen.hip", "gen_train.hip", "lora.hip", "llpr.hip", "zbl.hip", "ewald.hip", "p3m.hip", "augment.hip", "wigner.hip", "baseline.hip", "loss.hip"]
+SOURCES = ["abi.hip", "graph.hip", "nl.hip", "pet_plan.hip", "pet_fwd.hip", "pet_bwd.hip", "pet_tile.hip", "pet_node.hip", "pet_trr.hip", "pet_attn.hip", "pet_ablk.hip", "pet_ablk_bwd1.hip", "pet_emlp_s.hip", "pet_head_s.hip", "pet_compress_s.hip", "pet_center_s.hip", "pet_comb.hip", "pet_comb_s.hip", "pet_comb_bwd.hip", "pet_comb_bwd_s.hip", "train.hip", "optim.hip", "so.hip", "so_rows_s.hip", "pet_node_s.hip", "soap.hip", "soap_expand.hip", "soap_ps.hip", "soap_tail.hip", "soap_train.hip", "soap_hvp.hip", "soap_llpr.hip", "gen.hip", "gen_train.hip", "lora.hip", "llpr.hip", "zbl.hip", "ewald.hip", "p3m.hip", "augment.hip", "wigner.hip", "baseline.hip", "loss.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fgpu-rdc"]
 FLAGS += os.environ.get("PET_HIP_EXTRA_FLAGS", "").split()  # debugging builds, e.g. -DAB_PROFILE (pet_ablk.hip)
 # Translation units compiled on their own (no -fgpu-rdc: their device code is generated here, not at the link step) with the

@@ -350,12 +350,24 @@ __global__ __launch_bounds__(256) void k_llpr_ens_gemm(const float* __restrict__
     for (int m = 0; m < 2; m++)
 #pragma unroll
         for (int n = 0; n < 2; n++) acc[m][n] = f4{0.f, 0.f, 0.f, 0.f};
+    // two levels: each 32-wide k chunk is summed from zero (8 chained products) and then added to the running total, so a
+    // result is a chain of 8 + F / 32 roundings, not F / 4 -- at F = 288 .. 512 (SOAP-BPNN) the single chain
+    // missed twice fp32 torch's own error
     for (int k0 = 0; k0 < F; k0 += KC) {
         __syncthreads();
         stage_rows(X, F, R, r0, F, k0, Xs);
         stage_rows(W, F, KP, c0, F, k0, Ws);
         __syncthreads();
-        nt_chunk(Xs, Ws, acc);
+        f4 part[2][2];
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int n = 0; n < 2; n++) part[m][n] = f4{0.f, 0.f, 0.f, 0.f};
+        nt_chunk(Xs, Ws, part);
+#pragma unroll
+        for (int m = 0; m < 2; m++)
+#pragma unroll
+            for (int n = 0; n < 2; n++) acc[m][n] += part[m][n];
     }
 #pragma unroll
     for (int m = 0; m < 2; m++)

@@ -2,7 +2,8 @@
 // building blocks (spherical harmonics, radial splines, cutoff) and block reductions that more than one file uses, and the
 // host entry points of each file. soap.hip has the model, the plan (soap_plan.h) and the two drivers; soap_expand.hip,
 // soap_ps.hip and soap_tail.hip one stage each, both generations and the adjoints, with the stage's launchers;
-// soap_train.hip the training pass; soap_hvp.hip the Hessian-vector product.
+// soap_train.hip the training pass; soap_hvp.hip the Hessian-vector product; soap_llpr.hip the last-layer features and the
+// soap_llpr_* entry points.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -385,4 +386,12 @@ int64_t soap_hvp_ws_bytes(const SoapModel& m, int64_t n_nodes, int64_t n_edges);
 int soap_hvp(const SoapModel& m, const Graph& g, void* ws, int64_t ws_bytes, void* hws, int64_t hws_bytes, const float* u,
              const float* ucell, float* hvp_pos, float* hvp_cell, float* tangent_atomic, hipStream_t st);
 
+// soap_llpr.hip: the last-layer features [N, F] (F = soap_llpr_width) from what the tail kernels left in the workspace
+inline int soap_llpr_width(const SoapDims& d) { return d.legacy ? d.ns * d.H : d.H; }
+int soap_llpr_feats(const SoapModel& m, const Graph& g, void* ws, int64_t ws_bytes, int back, float* llf, hipStream_t st);
+
 }  // namespace pet
+
+struct soap_model {  // (soap_model_t of include/soap_hip.h: the entry points of soap.hip and soap_llpr.hip)
+    pet::SoapModel m;
+};

@@ -286,10 +286,6 @@ static int soap_bwd(const SoapModel& m, const Graph& g, void* ws, int64_t ws_byt
 
 using namespace pet;
 
-struct soap_model {
-    SoapModel m;
-};
-
 extern "C" {
 
 int soap_model_create(const soap_hypers_t* h, soap_model_t** out) {

@@ -120,7 +120,8 @@ class SoapBpnnHip:
         feats = torch.empty((g.n_nodes, self.feature_size), dtype=torch.float32, device=dev) if want_features else None
         check(self.lib.soap_forward(self._handle, g.handle, rt._ptr(ws), ws.numel(), rt._ptr(atomic), rt._ptr(feats),
                                     rt._stream()))
-        self._fwd_of = (weakref.ref(g), ws.data_ptr())  # (hessian_vector_product: whose expansion the workspace holds)
+        # (hessian_vector_product, last_layer_features: whose forward the workspace holds, and of which feature layout)
+        self._fwd_of = (weakref.ref(g), ws.data_ptr(), want_features)
         return (atomic, feats) if want_features else atomic
 
     def backward(self, g: rt.HipGraph, grad_atomic: torch.Tensor, want_cell_grad: bool = False):
@@ -219,6 +220,38 @@ class SoapBpnnHip:
         if self.zbl is not None:
             out = out + self.zbl.hessian_vector_product(self.zbl.graph_for(g, pbcs), u)
         return out
+
+    # ---- last-layer features -----------------------------------------------------------------------
+    @property
+    def llpr_feature_size(self) -> int:
+        """``F``: ``num_neurons_per_layer``, times the number of species when ``legacy`` (``soap_bpnn/model.py:347-351``)."""
+        return int(self.lib.soap_llpr_feature_size(self._handle))
+
+    def _tail_features(self, g: rt.HipGraph, layer: int) -> torch.Tensor:
+        ws = self._workspace(g)
+        # The features are those of the inference forward, ``forward(g)``. Behind ``forward(g, want_features=True)`` they are
+        # re-made by it: that forward keeps the full power spectrum, whose first Linear sums in another order than the packed
+        # one's, so the tail's activations differ in the last bits (DESIGN §28) -- and an uncertainty belongs to the energies
+        # ``forward`` / ``evaluate`` return.
+        fo = getattr(self, "_fwd_of", None)
+        if fo is None or fo[0]() is not g or fo[1] != ws.data_ptr() or fo[2]:
+            self.forward(g)
+        llf = torch.empty((g.n_nodes, self.llpr_feature_size), dtype=torch.float32, device=ws.device)
+        check(self.lib.soap_llpr_features(self._handle, g.handle, rt._ptr(ws), ws.numel(), layer, rt._ptr(llf), rt._stream()))
+        return llf
+
+    def last_layer_features(self, g: rt.HipGraph) -> torch.Tensor:
+        """``mtt::aux::energy_last_layer_features`` ``[N, F]``: the input of ``last_layers.energy.<s>`` per atom (after the
+        head), for ``legacy`` models in the columns of the centre's species and exactly zero elsewhere
+        (``soap_llpr_features``). Reads what ``forward(g)`` left in the workspace, which it runs itself unless this graph's
+        forward was the last one there."""
+        return self._tail_features(g, 0)
+
+    def features(self, g: rt.HipGraph) -> torch.Tensor:
+        """The ``feature`` output ``[N, F]``: the BPNN's output before the head, in the layout of
+        :meth:`last_layer_features` -- and equal to them for a linear head; under an mlp head, which runs as the native
+        tail's last hidden layer, one layer below."""
+        return self._tail_features(g, 1 if self.mlp_head else 0)
 
     def _copy_out(self, fn, keys_shapes) -> Dict[str, torch.Tensor]:
         out = {}

@@ -77,6 +77,13 @@ typedef struct pet_hypers {
                                        GNN layer (conditioning.py, backend.py:121-130,517-545); needs pet_graph_set_conditioning */
     int32_t max_charge;             /* charges in [-max_charge, max_charge]   (10) */
     int32_t max_spin_multiplicity;  /* multiplicities in [1, max]             (10) */
+    int32_t adaptive_grid_probes;   /* PET_ADAPTIVE_GRID: the number of probe cutoffs, len(torch.arange(0.5, cutoff,
+                                       cutoff_width_adaptive / 4)) = ceil((cutoff - 0.5) / (cutoff_width_adaptive / 4)),
+                                       counted by the caller IN DOUBLE from the hypers as the user wrote them: the float
+                                       fields above hold 0.64 or 0.32 rounded down, and the same formula on them counts one
+                                       probe too many (cutoff 4.5: 26 for 25, 51 for 50). 0: counted here from the float
+                                       fields (callers from before the field existed). 2 .. 64 probes are built; any other
+                                       count is PET_ERR_UNSUPPORTED at pet_model_create */
 } pet_hypers_t;
 
 typedef struct pet_model pet_model_t; /* packed weights on the device */

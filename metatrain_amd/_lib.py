@@ -172,6 +172,7 @@ class PetHypers(ctypes.Structure):
         ("system_conditioning", c_int32),
         ("max_charge", c_int32),
         ("max_spin_multiplicity", c_int32),
+        ("adaptive_grid_probes", c_int32),
     ]
 
 

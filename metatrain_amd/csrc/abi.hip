@@ -519,6 +519,19 @@ int pet_model_create(const pet_hypers_t* h, pet_model_t** out) {
                 PET_ERR_UNSUPPORTED, "unknown normalization / transformer_type / featurizer_type");
     PET_REQUIRE(h->adaptive_cutoff_method == PET_ADAPTIVE_SOLVER || h->adaptive_cutoff_method == PET_ADAPTIVE_GRID,
                 PET_ERR_UNSUPPORTED, "unknown adaptive_cutoff_method");
+    if (h->num_neighbors_adaptive > 0.f && h->adaptive_cutoff_method == PET_ADAPTIVE_GRID) {
+        // the probe grid torch.arange(0.5, cutoff, width / 4) (adaptive_cutoff.py:266-277): refused here, before any graph
+        PET_REQUIRE(h->cutoff_width_adaptive > 0.f && h->adaptive_grid_probes >= 0, PET_ERR_ARGUMENT,
+                    "adaptive_cutoff_method = 'grid' needs cutoff_width_adaptive > 0 and adaptive_grid_probes >= 0");
+        const int K = grid_probe_count(*h);
+        // a count made in double differs from the one made on the float32 fields by one probe at the most
+        PET_REQUIRE(std::abs(K - grid_probes_from_floats(*h)) <= 1, PET_ERR_ARGUMENT,
+                    "adaptive_grid_probes = " + std::to_string(K) + " is not the length of torch.arange(0.5, cutoff, "
+                    "cutoff_width_adaptive / 4): the float fields give " + std::to_string(grid_probes_from_floats(*h)));
+        PET_REQUIRE(K >= 2 && K <= GRID_MAX_PROBES, PET_ERR_UNSUPPORTED,
+                    "adaptive_cutoff_method = 'grid': " + std::to_string(K) + " probe cutoffs (2 .. " +
+                        std::to_string(GRID_MAX_PROBES) + " are built)");
+    }
     PET_REQUIRE(!h->system_conditioning || (h->max_charge >= 0 && h->max_spin_multiplicity >= 1), PET_ERR_ARGUMENT,
                 "system_conditioning needs max_charge >= 0 and max_spin_multiplicity >= 1");
     pet_model_t* pm = new pet_model_t();

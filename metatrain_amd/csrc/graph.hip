@@ -858,9 +858,10 @@ static int graph_build_once(const Model& m, const float* pos, const float* cells
                                                          g.scalars + 4);
             k_gather_all<<<cdiv(e0, T), T, 0, st>>>(g.perm0, neighbors, shifts, g.nbr0, g.shift0, (int)e0);
             if (m.h.adaptive_cutoff_method == PET_ADAPTIVE_GRID) {
-                // probe grid = torch.arange(0.5, cutoff, width / 4) (adaptive_cutoff.py:266-277)
+                // probe grid = torch.arange(0.5, cutoff, width / 4) (adaptive_cutoff.py:266-277); pet_model_create has
+                // refused a count outside 2 .. GRID_MAX_PROBES
                 const double dp = (double)m.h.cutoff_width_adaptive / 4.0;
-                const int K = (int)std::ceil(((double)m.h.cutoff - 0.5) / dp);
+                const int K = grid_probe_count(m.h);
                 PET_REQUIRE(K >= 2 && K <= GRID_MAX_PROBES, PET_ERR_UNSUPPORTED,
                             "adaptive_cutoff_method = 'grid': " + std::to_string(K) + " probe cutoffs (2 .. " +
                                 std::to_string(GRID_MAX_PROBES) + " are built)");

@@ -1,6 +1,7 @@
 // Device-resident PET weights: raw copies keyed by the reference state-dict names
 //  plus the packed / derived forms the kernels consume.
 #pragma once
+#include <cmath>
 #include <map>
 #include <set>
 #include <string>
@@ -74,6 +75,16 @@ struct LastW {
 // the tuned kernels are ONE instantiation; every other size runs on the generic path (gen.hip)
 inline bool compiled_size(const pet_hypers_t& h) {
     return h.d_pet == D && h.d_node == DN && h.d_feedforward == DFF && h.d_head == DH && h.num_heads == NHEAD;
+}
+
+// probe cutoffs of adaptive_cutoff_method = "grid": the count the caller made in double from the hypers as written
+// (pet_hypers_t::adaptive_grid_probes), else the same formula on the float32 fields
+inline int grid_probes_from_floats(const pet_hypers_t& h) {
+    const double k = std::ceil(((double)h.cutoff - 0.5) / ((double)h.cutoff_width_adaptive / 4.0));
+    return k < 0.0 ? 0 : k > 1e9 ? 1000000000 : (int)k;  // (far outside what is served either way)
+}
+inline int grid_probe_count(const pet_hypers_t& h) {
+    return h.adaptive_grid_probes > 0 ? h.adaptive_grid_probes : grid_probes_from_floats(h);
 }
 
 // A LoRA adapter on one Linear "<lin>" (keys <lin>.linear.{weight,bias}, <lin>.lora_A.weight [r, k_in],

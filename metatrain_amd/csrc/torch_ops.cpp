@@ -66,8 +66,9 @@ struct PetHipModule : torch::CustomClassHolder {
                  std::vector<at::Tensor> tensors_)
         : hypers(std::move(hypers_)), atomic_types(std::move(atomic_types_)), keys(std::move(keys_)),
           tensors(std::move(tensors_)) {
-        TORCH_CHECK(hypers.size() == 16 || hypers.size() == 19 || hypers.size() == 20 || hypers.size() == 23,
-                    "pet_hip: expected the first 16, 19, 20 or all 23 fields of pet_hypers_t");
+        TORCH_CHECK(hypers.size() == 16 || hypers.size() == 19 || hypers.size() == 20 || hypers.size() == 23 ||
+                        hypers.size() == 24,
+                    "pet_hip: expected the first 16, 19, 20, 23 or all 24 fields of pet_hypers_t");
         TORCH_CHECK(keys.size() == tensors.size(), "pet_hip: keys / tensors length mismatch");
     }
     ~PetHipModule() override {
@@ -90,6 +91,7 @@ struct PetHipModule : torch::CustomClassHolder {
         if (hypers.size() >= 20) h.adaptive_cutoff_method = (int32_t)hypers[19];
         TORCH_CHECK(hypers.size() < 23 || hypers[20] == 0.0,
                     "pet_hip: system conditioning needs the three PETBackend calls (batch_data carries charge / spin)");
+        if (hypers.size() >= 24) h.adaptive_grid_probes = (int32_t)hypers[23];
         return h;
     }
 
@@ -560,9 +562,10 @@ struct PetHipBackend : torch::CustomClassHolder {
                 lora_lins.push_back(k.substr(0, k.size() - sfx.size()));
         TORCH_CHECK(hypers.size() >= lora_lins.size(), "pet_hip: no LoRA scalings");
         n_fields = hypers.size() - lora_lins.size();
-        TORCH_CHECK(n_fields == 17 || n_fields == 20 || n_fields == 21 || n_fields == 24,
+        TORCH_CHECK(n_fields == 17 || n_fields == 20 || n_fields == 21 || n_fields == 24 || n_fields == 25,
                     "pet_hip: expected the first 16 fields of pet_hypers_t, the SiLU flag and (optionally) normalization, "
-                    "transformer_type, featurizer_type, adaptive_cutoff_method, then one scaling per LoRA adapter");
+                    "transformer_type, featurizer_type, adaptive_cutoff_method, the conditioning fields, "
+                    "adaptive_grid_probes, then one scaling per LoRA adapter");
         TORCH_CHECK(hypers[16] == 0.0 || std::none_of(lora_lins.begin(), lora_lins.end(), [](const std::string& l) {
                         return l.size() > 5 && l.compare(l.size() - 5, 5, ".w_in") == 0;
                     }),
@@ -591,6 +594,7 @@ struct PetHipBackend : torch::CustomClassHolder {
             h.system_conditioning = (int32_t)hypers[21]; h.max_charge = (int32_t)hypers[22];
             h.max_spin_multiplicity = (int32_t)hypers[23];
         }
+        if (n_fields >= 25) h.adaptive_grid_probes = (int32_t)hypers[24];
         return h;
     }
 

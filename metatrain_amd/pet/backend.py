@@ -373,7 +373,8 @@ class PETBackend(torch.nn.Module):
         h = rt.hypers_struct(hypers, atomic_types)  # validates; unsupported variants raise here
         fields = [float(getattr(h, name)) for name, _ in h._fields_]
         # PetHipBackend(hypers): the first 16 fields of pet_hypers_t, the SiLU flag, then the remaining fields (normalization,
-        # transformer_type, featurizer_type, adaptive_cutoff_method, system_conditioning, max_charge, max_spin_multiplicity)
+        # transformer_type, featurizer_type, adaptive_cutoff_method, system_conditioning, max_charge, max_spin_multiplicity,
+        # adaptive_grid_probes)
         self._numbers: List[float] = fields[:16] + [1.0 if hypers["activation"] == "SiLU" else 0.0] + fields[16:]
         self.hypers = dict(hypers)
         self.atomic_types: List[int] = [int(z) for z in atomic_types]

@@ -3,6 +3,7 @@ does the work. Nothing here computes on the CPU and nothing falls back to torch 
 """
 import contextlib
 import ctypes
+import math
 from ctypes import byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
 from typing import Dict, Iterable, List, Optional, Tuple, Union
 
@@ -38,6 +39,16 @@ def refuse_long_range(hypers: dict, what: str) -> None:
                           "energies and forces: long_range.LongRangeTrainStep; H u: long_range.hessian_vector_product")
 
 
+def grid_probe_count(cutoff: float, cutoff_width_adaptive: float) -> int:
+    """Probe cutoffs of ``adaptive_cutoff_method = "grid"``: ``len(torch.arange(0.5, cutoff, cutoff_width_adaptive / 4))``
+    (adaptive_cutoff.py:266-277), by ``arange``'s own rule ``ceil((end - start) / step)`` in double. It is counted here, from
+    the hypers as written, because ``pet_hypers_t`` holds them in float32: 0.64 and 0.32 are rounded down there, and the same
+    formula on the rounded values counts 26 and 51 probes at cutoff 4.5 where the reference has 25 and 50."""
+    if not cutoff_width_adaptive > 0.0:
+        raise ValueError(f"cutoff_width_adaptive must be positive, got {cutoff_width_adaptive}")
+    return min(max(int(math.ceil((cutoff - 0.5) / (cutoff_width_adaptive / 4.0))), 0), 10 ** 9)
+
+
 def hypers_struct(hypers: dict, atomic_types: List[int]) -> PetHypers:
     fn = hypers["cutoff_function"].lower()
     if fn not in ("bump", "cosine"):
@@ -54,6 +65,9 @@ def hypers_struct(hypers: dict, atomic_types: List[int]) -> PetHypers:
     if method not in ("solver", "grid"):  # structures.py:229-251
         raise ValueError(f"adaptive_cutoff_method must be 'grid' or 'solver', got {hypers['adaptive_cutoff_method']}")
     variants["adaptive_cutoff_method"] = 1 if method == "grid" else 0
+    if method == "grid" and hypers["num_neighbors_adaptive"]:
+        variants["adaptive_grid_probes"] = grid_probe_count(float(hypers["cutoff"]),
+                                                            float(hypers.get("cutoff_width_adaptive", 1.0)))
     if hypers.get("system_conditioning", False):
         variants.update(system_conditioning=1, max_charge=int(hypers["max_charge"]),
                         max_spin_multiplicity=int(hypers["max_spin_multiplicity"]))

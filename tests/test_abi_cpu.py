@@ -95,6 +95,41 @@ def test_variants_outside_the_build_fail_loudly():
     assert (cond.system_conditioning, cond.max_charge, cond.max_spin_multiplicity) == (1, 4, 10)
 
 
+def test_grid_probe_count_is_the_callers_and_refused_outside_2_to_64(lib):
+    """``pet_hypers_t.adaptive_grid_probes`` is the last field of the struct; the Python layer fills it with the length of
+    ``torch.arange(0.5, cutoff, cutoff_width_adaptive / 4)`` counted in double (25 at width 0.64, where the float32 fields
+    give 26). ``pet_model_create`` serves 2 .. 64 probes (PET_ERR_UNSUPPORTED otherwise, before any graph exists), takes 0
+    as "count from the float fields" and refuses a count that is not within one of that (PET_ERR_ARGUMENT)."""
+    assert _lib.PetHypers._fields_[-1] == ("adaptive_grid_probes", ctypes.c_int32)
+    assert ctypes.sizeof(_lib.PetHypers) == 24 * 4
+
+    def create(h):
+        handle = ctypes.c_void_p()
+        rc = lib.pet_model_create(ctypes.byref(h), ctypes.byref(handle))
+        if rc == 0:
+            lib.pet_model_destroy(handle)
+        return rc, lib.pet_last_error().decode()
+
+    grid = dict(opet.DEFAULT_HYPERS, num_neighbors_adaptive=12, adaptive_cutoff_method="grid")
+    for width, probes in ((1.0, 16), (0.64, 25), (0.32, 50), (0.25, 64)):
+        h = rt.hypers_struct(dict(grid, cutoff_width_adaptive=width), [1, 6])
+        assert h.adaptive_grid_probes == probes
+        assert create(h)[0] == 0, width
+    for hy in (dict(grid, cutoff_width_adaptive=0.24), dict(grid, cutoff=0.7)):
+        rc, message = create(rt.hypers_struct(hy, [1, 6]))
+        assert rc == _lib.PET_ERR_UNSUPPORTED and "probe cutoffs (2 .. 64 are built)" in message, message
+        with pytest.raises(_lib.PetHipError, match=f"error {_lib.PET_ERR_UNSUPPORTED}: .*probe cutoffs"):
+            rt.HipModel(hy, [1, 6])
+    h = rt.hypers_struct(dict(grid, cutoff_width_adaptive=0.64), [1, 6])
+    h.adaptive_grid_probes = 0  # a caller from before the field: the float32 fields count 26, still served
+    assert create(h)[0] == 0
+    h.adaptive_grid_probes = 30
+    assert create(h)[0] == _lib.PET_ERR_ARGUMENT
+    h.adaptive_grid_probes = 30  # neither method nor target asks for the grid: the field is not looked at
+    h.adaptive_cutoff_method = 0
+    assert create(h)[0] == 0
+
+
 def test_cpu_tensors_are_rejected_not_silently_computed():
     """The product has no CPU path: CPU tensors raise instead of falling back."""
     m = rt.HipModel(dict(opet.DEFAULT_HYPERS), [1, 6, 7, 8])

@@ -352,13 +352,21 @@ int pet_model_get_param(const pet_model_t* m, const char* key, float* d_dst, int
 int pet_model_flat_grad(pet_model_t* m, float* d_flat, int64_t numel, int direction, void* stream);
 /* clip_grad_norm_(max_grad_norm; <= 0: off) + torch.optim.Adam (weight_decay < 0) or AdamW
  * (weight_decay >= 0) on every parameter, `step` counted from 1 (pet/trainer.py:367-376,463-467),
- * then re-packs the weights. d_grad_norm (device, may be NULL) receives the pre-clip total norm. */
+ * then re-packs the weights. d_grad_norm (device, may be NULL) receives the pre-clip total norm.
+ * `step` is the step count of a parameter that has taken part in every step. torch counts per parameter and only the
+ * steps in which it has a .grad, so the model keeps, per parameter, the number of calls it sat out frozen
+ * (pet_model_set_trainable) and gives it the bias correction of `step` minus that number: a parameter turned on after k
+ * steps starts at step 1, one that skipped a step lags one behind. */
 int pet_adam_step(pet_model_t* m, float lr, float beta1, float beta2, float eps, float weight_decay,
                   float max_grad_norm, int64_t step, float* d_grad_norm, void* stream);
 /* Adam's first / second moments as two flat fp32 buffers of pet_model_num_params elements in upload order (the layout
  * of pet_model_flat_grad): direction 0 copies them out, 1 copies them in. With the step counter this is the
  * optimizer_state_dict a checkpoint keeps (pet/trainer.py:697-717, trainer checkpoint v15). */
 int pet_optimizer_state(pet_model_t* m, float* d_m, float* d_v, int64_t numel, int direction, void* stream);
+/* The third part of that state: per uploaded float parameter, in upload order, the number of pet_adam_step calls it sat
+ * out frozen (HOST array `counts` of `n` = number of such parameters; direction 0 copies out, 1 copies in). A model that
+ * was never told starts with zeros: every parameter takes the bias correction of `step`. */
+int pet_optimizer_idle_steps(pet_model_t* m, int64_t* counts, int64_t n, int direction, void* stream);
 /* Declare parameter `key` (uploaded as a tensor stacked on itself, see pet_model_set_param) TIED: pet_adam_step sums
  * the gradient slots of its two halves, counts the parameter once in the clipping norm and gives both halves the same
  * update, so that they stay equal. */

@@ -47,7 +47,7 @@ SYMBOLS = [
     "pet_model_num_readout_layers", "pet_forward_layers", "pet_backward_features_layers", "pet_graph_set_conditioning", "pet_graph_set_exchange",
     "pet_model_zero_grad", "pet_model_get_grad", "pet_train_workspace_bytes", "pet_train_workspace_bytes_for",
     "pet_train2_workspace_bytes_for", "pet_backward_train",
-    "pet_model_get_param", "pet_model_flat_grad", "pet_adam_step", "pet_optimizer_state", "pet_model_tie_halves",
+    "pet_model_get_param", "pet_model_flat_grad", "pet_adam_step", "pet_optimizer_state", "pet_optimizer_idle_steps", "pet_model_tie_halves",
     "pet_model_set_lora_scaling", "pet_model_set_trainable",
     "pet_train2_workspace_bytes", "pet_backward_train2", "pet_backward_train2_cell",
     "pet_train_predict", "pet_train_predict_backward", "pet_backward_train_seeded", "pet_backward_train2_seeded",
@@ -257,6 +257,7 @@ def load() -> ctypes.CDLL:
     lib.pet_model_flat_grad.argtypes = [P, P, c_int64, c_int, P]
     lib.pet_adam_step.argtypes = [P, c_float, c_float, c_float, c_float, c_float, c_float, c_int64, P, P]
     lib.pet_optimizer_state.argtypes = [P, P, P, c_int64, c_int, P]
+    lib.pet_optimizer_idle_steps.argtypes = [P, P, c_int64, c_int, P]
     lib.pet_model_tie_halves.argtypes = [P, c_char_p]
     lib.pet_model_set_lora_scaling.argtypes = [P, c_char_p, c_float]
     lib.pet_model_set_trainable.argtypes = [P, c_char_p, c_int]

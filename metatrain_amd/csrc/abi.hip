@@ -608,6 +608,11 @@ int pet_optimizer_state(pet_model_t* pm, float* d_m, float* d_v, int64_t numel, 
     return optimizer_state(pm->m, d_m, d_v, numel, direction, (hipStream_t)stream);
 }
 
+int pet_optimizer_idle_steps(pet_model_t* pm, int64_t* counts, int64_t n, int direction, void* stream) {
+    PET_REQUIRE(pm && counts, PET_ERR_ARGUMENT, "null argument");
+    return optimizer_idle_steps(pm->m, counts, n, direction, (hipStream_t)stream);
+}
+
 int pet_model_finalize(pet_model_t* pm, void* stream) {
     PET_REQUIRE(pm, PET_ERR_ARGUMENT, "null model");
     return finalize(pm->m, (hipStream_t)stream);

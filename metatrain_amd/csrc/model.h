@@ -141,6 +141,12 @@ struct Model {
     float** seg_ptr = nullptr; // device table: parameter storage of segment i
     int64_t* seg_off = nullptr;  // device table: first flat index of segment i (n_seg + 1 entries)
     int n_seg = 0;
+    // per segment: its key, the optimizer steps it has sat out (frozen while the others stepped: its own step count is the
+    // step handed to adam_step minus this), and the (bc1, bc2_sqrt) table a step with such a segment live hands to k_adam
+    std::vector<std::string> seg_keys;
+    std::vector<int64_t> seg_idle;
+    std::vector<float> seg_bc_host;
+    float* seg_bc = nullptr;
     float* opt_scalars = nullptr;  // [4] sum of squares, clip coefficient
     // tied parameters (activation = "SiLU": w_in held as [W; W]): (flat offset, half length) pairs
     std::vector<int64_t> ties;
@@ -199,6 +205,7 @@ int adam_step(Model& m, float lr, float beta1, float beta2, float eps, float wei
 
 int tie_halves(Model& m, const std::string& key);
 int optimizer_state(Model& m, float* d_m, float* d_v, int64_t numel, int direction, hipStream_t st);
+int optimizer_idle_steps(Model& m, int64_t* counts, int64_t n, int direction, hipStream_t st);
 
 // graph.hip
 // na + nb <= MAILBOX_INTS - 1 device integers (two sources, either may be empty) to `out` on the host, ordered after

@@ -809,7 +809,8 @@ int soap_train_grads(SoapModel& m, const Graph& g, void* ws, int64_t ws_bytes, v
 int soap_adam(SoapModel& m, float lr, float b1, float b2, float eps, int64_t step, hipStream_t st) {
     PET_REQUIRE(!m.grad.empty(), PET_ERR_ARGUMENT, "soap_model_zero_grad has not been called");
     PET_REQUIRE(step >= 1, PET_ERR_ARGUMENT, "Adam steps are counted from 1");
-    const float c1 = 1.f - powf(b1, (float)step), c2 = 1.f - powf(b2, (float)step);
+    // in fp64, rounded once: 1 - b2^t cancels, and powf's half ulp of b2^t is 1.5e-5 of 1 - b2^2
+    const float c1 = (float)(1.0 - pow((double)b1, (double)step)), c2 = (float)(1.0 - pow((double)b2, (double)step));
     for (auto& kv : m.grad) {
         float* p = m.raw.at(kv.first).first;
         const int64_t n = kv.second.second;

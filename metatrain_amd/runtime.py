@@ -292,7 +292,15 @@ class HipModel:
         m = torch.empty(self.num_params, dtype=torch.float32, device="cuda")
         v = torch.empty_like(m)
         check(self.lib.pet_optimizer_state(self._handle, _ptr(m), _ptr(v), m.numel(), 0, _stream()))
-        return {"exp_avg": m, "exp_avg_sq": v, "layout": self.flat_layout()}
+        return {"exp_avg": m, "exp_avg_sq": v, "layout": self.flat_layout(), "idle_steps": self._idle_steps()}
+
+    def _idle_steps(self, counts: Optional[Iterable[int]] = None):
+        """Per parameter of :meth:`flat_layout`, the optimizer steps it sat out frozen (``pet_optimizer_idle_steps``): its own
+        step count -- torch's per-parameter ``state["step"]`` -- is the ``step`` handed to :meth:`adam_step` minus this."""
+        n = len(self._ckeys)
+        buf = (ctypes.c_int64 * n)(*([0] * n if counts is None else [int(c) for c in counts]))
+        check(self.lib.pet_optimizer_idle_steps(self._handle, buf, n, 0 if counts is None else 1, _stream()))
+        return list(buf)
 
     def flat_layout(self):
         """``[(state-dict key, numel)]`` in the order of the flat gradient / Adam buffers (= upload order). Saved with the
@@ -309,6 +317,11 @@ class HipModel:
         v = state["exp_avg_sq"].to("cuda", torch.float32).contiguous()
         check(self.lib.pet_optimizer_state(self._handle, _ptr(m), _ptr(v), m.numel(), 1, _stream()))
         torch.cuda.current_stream().synchronize()  # m / v may be temporaries
+        # a state saved without the counts: every parameter counts the trainer's steps, as all of them once did
+        idle = state.get("idle_steps")
+        if idle is not None and len(idle) != len(self._ckeys):
+            raise PetHipError("optimizer state holds %d idle-step counts for %d parameters" % (len(idle), len(self._ckeys)))
+        self._idle_steps([0] * len(self._ckeys) if idle is None else idle)
 
     def adam_step(self, lr: float, step: int, betas=(0.9, 0.999), eps: float = 1e-8,
                   weight_decay: Optional[float] = None, max_grad_norm: float = 0.0) -> torch.Tensor:
